@@ -17,10 +17,15 @@ analyze_alignments -> (RCCL exchange when N > 1) -> finish_coverage -> filter_al
 write_abundance (profile TSV written to a file by rank 0), every step a fresh file for a fresh object.  `value` = total
 records / max-over-ranks time.
 
+A plain run sets up, warms up, times --steps steps and prints its line; --dump-outputs DIR also writes what the last timed
+step computed (dump_outputs).  Every other measurement below runs only with --full (a run of several minutes).
+
 ONE JSON line on rank 0.  Beside the contract's fields:
   roofline            the dominant kernel of the headline workload: algorithmic bytes (16 N + 8 P
                       for the front end) / its dispatch's own duration, measured live by HIP events handed to the
                       launch (hipExtLaunchKernelGGL) on the library's stream inside the timed steps
+With --full (the rest of the line is null without it):
+  step_split / exchange_bins   N > 1: where a step's time goes; the same step with one all-reduce over the bins
   roofline_config2 / _config3 / _config5   the same for BASELINE.json configs[1], [2] (the designated roofline run) and
                       [4] (100 M records, 50 k strain-level refs, 40 hits/read), resident, N = 1 only
   two_files_in_flight two host threads, each taking its files back to back through two contexts of its own: the kernels of
@@ -188,6 +193,47 @@ def cli_one_billion(records: int) -> dict:
     return o
 
 
+DUMP_BIN_SAMPLE = 1 << 19   # coverage bins kept per array by --dump-outputs (a fixed, seeded sample of the bins)
+
+
+def dump_outputs(engine, profile, out_dir, with_bins):
+    """--dump-outputs: what the timed path handed its caller for the LAST timed file, as DIR/<name>.npy in float64 (every
+    integer below 2^53, so exact): the profile rows (taxa_id, unclassified mark '*', abundance, read_count; sorted by id, as
+    row order is not significant), the slimm_get_stats scalars in capi.Stats order, every per-reference column, the direct
+    and the final per-taxon counts (taxid, count; sorted), and -- when the coverage arrays are in HBM -- cov, uniq_cov and
+    uniq_cov2 at a seeded sample of at most DUMP_BIN_SAMPLE bins (bins_index.npy holds the sampled bin numbers).  The
+    sample depends on the number of bins only, so two builds given the same arguments dump the same bins.  About 20 MB."""
+    from slimm_amd import capi
+
+    os.makedirs(out_dir, exist_ok=True)
+    out = {}
+    rows = []
+    for ln in (profile or "").strip("\n").split("\n")[1:]:
+        _, tid, _, ab, cnt = ln.split("\t")
+        rows.append((float(tid.rstrip("*")), float(tid.endswith("*")), float(ab), float(cnt)))
+    out["profile"] = np.array(sorted(rows), dtype=np.float64).reshape(-1, 4)
+    st = engine.stats()
+    out["stats"] = np.array([st[n] for n, _ in capi.Stats._fields_], dtype=np.float64)
+    for name, col in engine.ref_columns().items():
+        out["ref_" + name] = col.astype(np.float64)
+    for stage, name in ((0, "taxon_counts_direct"), (1, "taxon_counts")):
+        tc = engine.taxon_counts(stage)
+        out[name] = np.array(sorted(tc.items()), dtype=np.float64).reshape(-1, 2)
+    if with_bins:
+        n_bins = int(st["total_bins"])
+        if n_bins > DUMP_BIN_SAMPLE:
+            idx = np.unique(np.random.default_rng(20261016).integers(0, n_bins, DUMP_BIN_SAMPLE))
+        else:
+            idx = np.arange(n_bins)
+        out["bins_index"] = idx.astype(np.float64)
+        for which, name in enumerate(("cov", "uniq_cov", "uniq_cov2")):
+            out[name] = engine.bins(which)[idx].astype(np.float64)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= 64 << 20, f"--dump-outputs would write {total} bytes"
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -233,8 +279,15 @@ def main():
                          "through a freshly reset context, every profile written inside the timed region.  1: one context, "
                          "every call of a file behind the one before (rounds 1 - 3)")
     ap.add_argument("--gen-threads", type=int, default=0, help="threads generating chunks (default: the CPU quota / ranks)")
-    # the legs beside the headline (N = 1 only)
-    ap.add_argument("--quick", action="store_true", help="the headline measurement only (no other configs, push, CPU, CLI legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64, about 20 MB; "
+                         "see dump_outputs)")
+    # the measurements beside the headline: only with --full
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: at N = 1 the legs below (other configs, two files in flight, "
+                         "push-inclusive, run-marked, any order, parity in the run, CPU baselines, the command line), at N > 1 "
+                         "step_split and exchange_bins.  Without it a run sets up, warms up, times the steps and prints its line")
+    ap.add_argument("--quick", action="store_true", help="with --full: still no N = 1 legs beside the headline")
     ap.add_argument("--roofline-configs", default="config2,config3,config5",
                     help="configurations measured beside the headline, resident, one context ('' = none)")
     ap.add_argument("--config-steps", type=int, default=5)
@@ -298,7 +351,7 @@ def main():
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
         else:
             dist.init_process_group("gloo", rank=rank, world_size=world)
-    extras = rank == 0 and world == 1 and not args.quick and not args.force_exchange
+    extras = args.full and rank == 0 and world == 1 and not args.quick and not args.force_exchange
     packed = args.form == "packed"
     rec_bytes = 16 if packed else 18
     out_path = os.path.join(tempfile.gettempdir(), f"slimm_bench_profile_{os.getpid()}.tsv")
@@ -499,6 +552,8 @@ def main():
         (eng2 if eng is not eng2 else files.engines[0]).close()
     else:
         elapsed, ktimes, dom_name, profile = measure(eng, step, args.steps, args.warmup, barrier)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, profile, args.dump_outputs, with_bins=not args.no_bins)
     if dist.is_initialized():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -515,7 +570,7 @@ def main():
 
     # ---- N > 1: where a step's time goes, and north_star's literal collective beside the default exchange
     step_split = exchange_bins = None
-    if dist.is_initialized() and world > 1:
+    if args.full and dist.is_initialized() and world > 1:
         import slimm_amd.distributed as sd
 
         def one(exchange):
@@ -669,9 +724,15 @@ def main():
             for k, v in phase_times.items():
                 print(f"# host wall {k:28s} {v / args.steps * 1e6:9.1f} us/step", file=sys.stderr)
 
+        def leg(name):
+            """--full: a line on stderr as each leg starts (the legs take minutes; the JSON line comes at the end)."""
+            if extras:
+                print(f"# bench.py --full: {name} at {time.time() - t0:.0f} s", file=sys.stderr, flush=True)
+
         # ---- two files in flight: two host threads, each working through its files back to back on two contexts of its own,
         # so that the kernels of two files share the device (the front end waits for the scalar unit, the bucketing for the
         # LDS, the histograms for memory).  Reported BESIDE `value`, which keeps one file at a time.
+        leg("two_files_in_flight")
         in_flight = None
         if extras and world == 1 and args.in_flight_files >= 4 and args.record_order == "grouped" and args.engines == 2:
             import threading
@@ -702,6 +763,7 @@ def main():
 
         # ---- push-inclusive rate: the clock starts before the first record leaves host
         # memory and stops when the profile file is written.  PCIe, not the path, bounds it.
+        leg("value_with_push")
         with_push = None
         if want_push:
             eng.reset()
@@ -754,6 +816,7 @@ def main():
         # ---- the same stream as RUN-MARKED records (8 B/record: reference + 1 | mate | "a qName run starts here", position):
         # what a producer of name-grouped input can hand over instead of hashed names (include/slimm_hip.h).  The words are
         # built on the device from the packed arrays; resident rate, k_front under 8 N + 8 P, and the push-inclusive rate.
+        leg("run_marked_records")
         marked = None
         if extras and packed and args.record_order == "grouped" and not args.no_marked:
             word = torch.empty(n_rec, dtype=torch.int32, device=dev)
@@ -840,6 +903,7 @@ def main():
         eng.close()
         # ---- record_order = ANY: the SAME stream with the reads of every chunk interleaved at random (the reference takes
         # records in any order: src/slimm.hpp:204-211), through the device-side grouping
+        leg("record_order_any")
         any_order = {}
         if extras and not args.no_any_order and args.record_order == "grouped":
             res.interleave(args.chunk_records, 7000)
@@ -856,6 +920,7 @@ def main():
         for name in ([c for c in args.roofline_configs.split(",") if c] if extras else []):
             if name == args.config or name not in CONFIGS:
                 continue
+            leg("roofline_" + name)
             cfgk = CONFIGS[name]
             wk = make_workload(cfgk, seed=args.seed)
             nk = len(wk.records)
@@ -929,6 +994,7 @@ def main():
             if name == "config3" and not args.no_cli:
                 w_cli = wk
 
+        leg("cpu_baseline")
         cpu = cpu_mt = None
         if extras and not args.no_cpu_baseline:
             from oracle.binding import Oracle, dense_mt_run  # the CPU restatements (checker / baseline only)
@@ -975,6 +1041,7 @@ def main():
             del recm
 
         # ---- the command line, process start to profile written, on a BAM large enough that HIP start-up amortises
+        leg("cli_end_to_end")
         cli = None
         if extras and not args.no_cli:
             from slimm_amd.synth_bam import write_synthetic_bam
@@ -1119,6 +1186,7 @@ def main():
             # /dev/shm or /tmp: ~5 min): scripts/cli_1B.py in a process of its own, skipped -- with the reason -- when there is no
             # room for the file or the memory for it
             if isinstance(cli, dict) and "error" not in cli and not args.no_cli_1b:
+                leg("cli_end_to_end.one_billion")
                 cli["one_billion"] = cli_one_billion(args.cli_1b_records)
 
         line = {

@@ -150,10 +150,10 @@ def test_bench_multi_process_control_flow_on_one_gpu(nproc):
 def test_bench_launches_its_own_ranks():
     """`python bench.py --gpus 2` with no launcher around it (how the driver's N = 1 record shows bench.py being started):
     the parent starts torch.distributed.run as a child before it touches a GPU, relays rank 0's one line and leaves with the
-    child's exit code.  The N > 1 line carries the step's split and the same step with north_star's literal collective (one
-    all-reduce over the integer bins)."""
-    many = _bench(["--gpus", "2", "--backend", "gloo", "--quick", "--records", "4000000", "--chunk-records", "500000", "--steps", "2",
-                   "--warmup", "1"])
+    child's exit code.  With --full the N > 1 line carries the step's split and the same step with north_star's literal
+    collective (one all-reduce over the integer bins)."""
+    many = _bench(["--gpus", "2", "--backend", "gloo", "--full", "--quick", "--records", "4000000", "--chunk-records", "500000",
+                   "--steps", "2", "--warmup", "1"])
     assert many["n_gpus"] == 2 and many["config"]["process_group_ranks"] == 2 and many["config"]["total_records"] == 4_000_000
     sp = many["step_split"]
     assert sp["kernels_ms"] > 0 and sp["collectives_ms"] > 0 and set(sp["collectives"]) == {"all_gather", "all_reduce"}
@@ -173,7 +173,7 @@ def test_bench_eight_ranks_rehearsal_on_one_gpu():
     slices, `step_split`, `exchange_bins` -- and the same job as the N = 1 line."""
     common = ["--records", "40000000", "--chunk-records", "2500000", "--steps", "2", "--warmup", "1", "--quick"]
     one = _bench(common)
-    many = _bench(["--gpus", "8", "--backend", "gloo"] + common)       # (bench.py starts its own ranks)
+    many = _bench(["--gpus", "8", "--backend", "gloo", "--full"] + common)       # (bench.py starts its own ranks)
     assert many["n_gpus"] == 8 and many["config"]["process_group_ranks"] == 8 and many["config"]["exchange"] == "sliced"
     assert many["config"]["total_records"] == one["config"]["total_records"] == 40_000_000
     for k in ("reads", "targets", "bins", "profile_rows", "profile_sha1"):
