@@ -37,6 +37,8 @@ enum {
     SLIMM_E_KEY_COLLISION = -5, /* records with one read key carry different check words (slimm_push_records_checked) */
     SLIMM_E_REGROUP = -6,   /* a GROUPED stream holds names ending in ".1" / ".2" without a mate flag whose flagged namesakes
                                may lie elsewhere in the file (quirk Q18): push the file again to a SLIMM_ORDER_ANY context */
+    SLIMM_E_SPLIT = -7,     /* slimm_group_stitch_ranges: a member's guess of its first record was wrong (or its range could
+                               not be joined to the one before): read the file through one member instead */
     SLIMM_E_RETRY = 2,      /* not an error: slimm_install_merged_partials asks for slimm_filter_alignments_launch again */
     SLIMM_E_NO_HITS = 1     /* not an error: no mapped record (reference prints a warning and writes nothing, src/slimm.hpp:451-455) */
 };
@@ -538,6 +540,26 @@ enum { SLIMM_EXCHANGE_AUTO = 0, SLIMM_EXCHANGE_SUMMARY = 1, SLIMM_EXCHANGE_SLICE
 int slimm_group_set_exchange(slimm_group* g, int mode);
 int slimm_group_exchange(const slimm_group* g); /* the form in effect (what AUTO resolves to) */
 int slimm_group_get_profiles(slimm_group* g, const char* path); /* path may be NULL; SLIMM_E_NO_HITS like slimm_get_profiles */
+/* ONE BAM FILE SPLIT BY BYTE RANGE over a group (GROUPED files): every member reads, inflates and decodes its own contiguous
+ * range of the file's BGZF blocks at once.  slimm_host_bgzf_ranges plans the ranges (host only, no GPU): offsets_out[0, n]
+ * with offsets_out[0] = 0 and offsets_out[n] = the file's size; range i = [offsets_out[i], offsets_out[i + 1]) starts on a
+ * BGZF block boundary (a header whose next three headers chain through BSIZE + 1, or whose chain reaches the EOF block or
+ * the file's end), ranges may be empty; no cut lies in front of the block that holds inflated byte `skip` (the BAM header's
+ * inflated length: member 0 takes all of it and pushes its first blocks with that skip).  Every member but the first calls
+ * slimm_set_input_mid_file(ctx, 1, ...) before its first push -- its first record is guessed from the bytes, the bytes in
+ * front of it (at most 16 MiB) are kept on the device -- and every member but the last (..., 1): its last push may end
+ * inside a record.  Each member then pushes its range with slimm_push_bgzf_blocks (last = 1 at the range's end), all at
+ * once, and slimm_group_stitch_ranges joins the cuts on the devices: the bytes around a cut are decoded by the member on
+ * its left, which must end exactly where the right member's guess begins (otherwise SLIMM_E_SPLIT: read the file through
+ * member 0 instead); the run of a read name that a cut splits moves, device to device, to the member that holds its
+ * start; the Q18 counts are summed over the members (SLIMM_E_REGROUP as for one context).  slimm_group_get_profiles then
+ * runs on the members' records as they are (no dealing from member 0).  This is also how ONE device takes a file of more
+ * records than one context holds: a group that names the same device several times. */
+int slimm_host_bgzf_ranges(const char* path, uint64_t skip, uint32_t n, uint64_t* offsets_out);
+int slimm_set_input_mid_file(slimm_ctx* ctx, int starts_mid_file, int ends_mid_file);
+int slimm_group_stitch_ranges(slimm_group* g);
+/* the most records one context takes (below 2^31; SLIMM_FORCE record_cap=N lowers it, for tests) */
+uint64_t slimm_record_cap(void);
 /* A GROUPED file may also reach a group through ONE member: push its windows to slimm_group_context(g, 0) (slimm_push_bam_bytes /
  * _bgzf_blocks / _sam_bytes: the device inflates and decodes at the single-context rate) and nothing through
  * slimm_group_push_records*; slimm_group_get_profiles then deals member 0's run-marked records to the members in contiguous

@@ -19,6 +19,7 @@ E_REF_RANGE = -3
 E_RUN_LENGTH = -4
 E_KEY_COLLISION = -5
 E_REGROUP = -6
+E_SPLIT = -7
 E_RETRY = 2
 E_NO_HITS = 1
 
@@ -172,6 +173,10 @@ SYMBOLS = [
     ("slimm_host_q18_note", None, [_P, C.c_int, C.c_int]),
     ("slimm_host_q18_regroup_needed", C.c_int, [_P]),
     ("slimm_get_q18_runs", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("slimm_host_bgzf_ranges", C.c_int, [C.c_char_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]),
+    ("slimm_set_input_mid_file", C.c_int, [_P, C.c_int, C.c_int]),
+    ("slimm_group_stitch_ranges", C.c_int, [_P]),
+    ("slimm_record_cap", C.c_uint64, []),
     ("slimm_shutdown", C.c_int, []),
     ("slimm_version", C.c_char_p, []),
 ]

@@ -391,7 +391,82 @@ __global__ __launch_bounds__(64) void k_bam_carry(const uint8_t* __restrict__ b,
     }
 }
 
+// A range of a split file (split.hip): lanes over the candidate offsets, the smallest plausible one wins
+__global__ __launch_bounds__(256) void k_bam_first_guess(const uint8_t* __restrict__ b, uint64_t lo, uint64_t hi, uint64_t end,
+                                                         uint32_t n_refs, unsigned long long* __restrict__ out) {
+    for (uint64_t o = lo + blockIdx.x * 256ull + threadIdx.x; o < hi; o += static_cast<uint64_t>(gridDim.x) * 256ull) {
+        if (o >= __hip_atomic_load(out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;  // (a smaller one is known)
+        if (bam_plausible(b, o, end, n_refs, 2)) {
+            atomicMin(out, static_cast<unsigned long long>(o));
+            return;
+        }
+    }
+}
+
+// the name of the record at b[o] (its canonical base, as k_bam_carry keeps the last one)
+__global__ __launch_bounds__(64) void k_bam_name_at(const uint8_t* __restrict__ b, uint64_t o, BamCarry* __restrict__ dst) {
+    const uint8_t* r = b + o + 4;
+    uint32_t nlen = r[8] ? r[8] - 1u : 0u;
+    const uint32_t fl0 = ld_u16(r + 14);
+    const uint32_t fl = bam_canonical(r + 32, nlen, fl0);
+    for (uint32_t i = threadIdx.x; i < nlen; i += 64u) dst->name[i] = r[32 + i];
+    if (threadIdx.x == 0) {
+        dst->len = nlen;
+        dst->have = 1;
+        dst->last_short = fl != fl0 ? 1u : 0u;
+        dst->short_starts = dst->short_to_plain = 0;
+    }
+}
+
+// one wave: the right member's first record against the left member's last (k_bam_decode's compare across windows)
+__global__ __launch_bounds__(64) void k_split_join(const BamCarry* __restrict__ left, const BamCarry* __restrict__ first,
+                                                   BamCarry* __restrict__ right, uint32_t* __restrict__ word0) {
+    const uint32_t len = first->len;
+    bool same = left->have && first->have && left->len == len;
+    if (same)
+        for (uint32_t i = threadIdx.x; i < len; i += 64u) same = same && left->name[i] == first->name[i];
+    same = __all(same);
+    if (threadIdx.x == 0) {
+        if (same) {
+            // the record was counted as a run start (Q18: a shortened start); it is a step inside the left's run instead
+            word0[0] = word0[0] & 0x7fffffffu;
+            if (first->last_short)
+                atomicSub(&right->short_starts, 1u);
+            else if (left->last_short)
+                atomicAdd(&right->short_to_plain, 1u);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_split_first_start(const uint32_t* __restrict__ w, uint64_t n, unsigned long long* __restrict__ out) {
+    for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += static_cast<uint64_t>(gridDim.x) * 256ull) {
+        if (i >= __hip_atomic_load(out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+        if (w[i] >> 31) {
+            atomicMin(out, static_cast<unsigned long long>(i));
+            return;
+        }
+    }
+}
+
 }  // namespace
+
+void launch_bam_first_guess(hipStream_t st, const uint8_t* bytes, uint64_t lo, uint64_t hi, uint64_t end, uint32_t n_refs,
+                            unsigned long long* out) {
+    if (hi <= lo) return;
+    const uint64_t blocks = std::min<uint64_t>(1024, (hi - lo + 255) / 256);
+    hipLaunchKernelGGL(k_bam_first_guess, dim3(static_cast<uint32_t>(blocks)), dim3(256), 0, st, bytes, lo, hi, end, n_refs, out);
+}
+void launch_bam_name_at(hipStream_t st, const uint8_t* bytes, uint64_t o, BamCarry* name) {
+    hipLaunchKernelGGL(k_bam_name_at, dim3(1), dim3(64), 0, st, bytes, o, name);
+}
+void launch_split_join(hipStream_t st, const BamCarry* left, const BamCarry* first, BamCarry* right, uint32_t* word0) {
+    hipLaunchKernelGGL(k_split_join, dim3(1), dim3(64), 0, st, left, first, right, word0);
+}
+void launch_split_first_start(hipStream_t st, const uint32_t* words, uint64_t n, unsigned long long* out) {
+    if (!n) return;
+    const uint64_t blocks = std::min<uint64_t>(1024, (n + 255) / 256);
+    hipLaunchKernelGGL(k_split_first_start, dim3(static_cast<uint32_t>(blocks)), dim3(256), 0, st, words, n, out);
+}
 
 uint32_t bam_pieces(uint64_t n_bytes) { return static_cast<uint32_t>((n_bytes + kBamPiece - 1) / kBamPiece); }
 

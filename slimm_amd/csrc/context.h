@@ -208,6 +208,17 @@ struct slimm_ctx {
         // told) and, from it and the first push's ratio, the inflated bytes a gathered window's buffer gets (0 = kBamGather)
         uint64_t size_hint = 0, win_cap = 0;
         bool planned = false;                // the file's first COMPRESSED push has reserved its buffers (or found no hint)
+        // a byte range of a file split over a group (slimm_set_input_mid_file, split.hip): the range starts inside the file
+        // (its first record is guessed; the bytes in front of it -- the head -- wait on the device for the member on the
+        // left) and / or ends inside it (the incomplete last record stays in the carry); the first record's name for the
+        // join; the Q18 counts are summed by the group (slimm_group_stitch_ranges), not checked per member
+        bool starts_mid = false, ends_mid = false, q18_by_group = false;
+        bool found_start = false;   // the first window holds a record start (false: the whole range is head)
+        bool has_first = false;     // `first` holds the name of the range's first record (decoded in any window)
+        DevBuf<uint8_t> head_bytes;
+        uint64_t head_len = 0;
+        DevBuf<BamCarry> first, join;   // (join: the left member's carry, on this member's device)
+        DevBuf<unsigned long long> guess;
         uint64_t held_bytes() const {   // device memory of the window pipeline
             uint64_t n = pieces.cap * sizeof(BamPiece) + offs.cap * 4ull;
             for (uint32_t k = 0; k < kBamRing; ++k) n += bytes[k].cap + comp[k].cap + desc[k].cap * sizeof(BgzfBlock);
@@ -379,6 +390,8 @@ int ensure_work_buffers(slimm_ctx* c, uint32_t n);
 int ensure_pair_table(slimm_ctx* c, uint32_t cap);
 int check_device_errors(slimm_ctx* c, uint32_t err);
 int bam_fetch_q18(slimm_ctx* c);   // windows.hip: the Q18 run counts of the device decoders so far
+// windows.hip: `n` bytes at `src` (on device src_device) as one more window behind the closed file's carry (split.hip)
+int bam_append_window(slimm_ctx* c, const uint8_t* src, int src_device, uint64_t n, bool final, uint64_t& n_rec);
 
 // Grows one record array to `cap` elements, keeping the `used` elements pushed so far (when the array holds them at all:
 // an array the file's record form does not use is neither allocated nor copied).

@@ -437,6 +437,8 @@ int slimm_reset(slimm_ctx* c) {
     c->bam.head = 0;
     c->bam.closed = false;
     c->bam.q18_starts = c->bam.q18_plain = 0;
+    c->bam.starts_mid = c->bam.ends_mid = c->bam.found_start = c->bam.has_first = c->bam.q18_by_group = false;
+    c->bam.head_len = 0;
     c->bam.size_hint = c->bam.win_cap = 0;
     c->bam.planned = false;
     if (c->bam.held_bytes() > slimm_ctx::kBamKeepAcrossFiles) {   // (a large file's windows: the next file sizes its own)
@@ -523,7 +525,8 @@ int slimm_analyze_alignments(slimm_ctx* c) {
         // (windows pushed so far may still be gathered or in flight: analysing now would profile a truncated record stream)
         if (!c->bam.closed)
             return fail(c, SLIMM_E_INVALID, "the file's last window has not been pushed (slimm_push_bam_bytes / _bgzf_blocks / _sam_bytes with last != 0)");
-        if (c->order == SLIMM_ORDER_GROUPED) {  // Q18: a run of shortened names only may have its flagged namesakes elsewhere
+        // (a range of a split file: its group sums the counts over the members, slimm_group_stitch_ranges)
+        if (c->order == SLIMM_ORDER_GROUPED && !c->bam.q18_by_group) {  // Q18: a run of shortened names only may have its flagged namesakes elsewhere
             const int qrc = bam_fetch_q18(c);
             if (qrc != SLIMM_OK) return qrc;
             if (c->bam.q18_starts != c->bam.q18_plain)

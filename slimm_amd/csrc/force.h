@@ -6,6 +6,8 @@
 //   scatter_big=0|1                                   tests/test_gpu_parity.py, test_gpu_layouts.py, test_gpu_group.py
 //   group_bits=N, group_width=N, group_passes=N, group_grid=N, group_staged=0|1      tests/test_gpu_group_by_ident.py
 //   group_collectives=rccl|copy                                                       tests/test_gpu_group.py
+//   record_cap=N (fewer records per context), split_shift_guess (a mid-file member reports its first record one byte
+//   off: slimm_group_stitch_ranges must refuse the join)                             tests/test_cli_split_input.py
 #pragma once
 #include <cstdlib>
 #include <cstring>
@@ -35,6 +37,13 @@ inline bool forced(const char* key, long* value = nullptr) {
     if (!forced_text(key, &t)) return false;
     if (value) *value = t ? atol(t) : 1;
     return true;
+}
+
+// the most records one context takes: below 2^31 (32-bit record indices), lower with SLIMM_FORCE record_cap=N
+inline unsigned long long record_cap() {
+    long v = 0;
+    const unsigned long long cap = 0x7fffffffull;
+    return (forced("record_cap", &v) && v > 0 && static_cast<unsigned long long>(v) < cap) ? static_cast<unsigned long long>(v) : cap;
 }
 
 // SLIMM_TRACE="cli,host,push" (or "all" / "1"): diagnostics on stderr -- cli: the command's stage marks (host/slimm_main.cpp),

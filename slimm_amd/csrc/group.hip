@@ -25,6 +25,7 @@
 
 #include "../../include/slimm_hip.h"
 #include "force.h"
+#include "split.h"
 
 namespace {
 
@@ -125,6 +126,7 @@ struct slimm_group {
     uint32_t n_refs = 0;
     bool have_last = false;
     uint64_t last_key = 0;
+    bool stitched = false;                   // the members read a file by byte range (slimm_group_stitch_ranges): no deal
     std::string err;
 };
 
@@ -551,6 +553,7 @@ int slimm_group_reset(slimm_group* g) {
     g->carry_word.clear();
     g->checked = -1;
     g->have_last = false;
+    g->stitched = false;
     return SLIMM_OK;
 }
 
@@ -643,6 +646,67 @@ static int deal_from_member0(slimm_group* g) {
     return SLIMM_OK;
 }
 
+// A file read by byte range, every member its own (include/slimm_hip.h, "ONE BAM FILE SPLIT BY BYTE RANGE"; split.hip):
+//   1. the bytes around every cut -- the incomplete last record of the nearest member on the left that holds a record
+//      start, and the right member's head -- are decoded by that left member, and must end exactly where the right
+//      member's guess begins (SLIMM_E_SPLIT otherwise); a member without a record start hands its bytes on to the left
+//   2. every such right member's first record against the record in front of it: the same read name clears its run-start
+//      bit (and corrects the Q18 counts); then Q18 over the file, the members' counts summed
+//   3. left to right, the records in front of a member's first run start -- the run a cut split -- go device to device to
+//      the nearest member on the left that keeps records, so that a run over several members ends up in one
+int slimm_group_stitch_ranges(slimm_group* g) {
+    if (!g) return SLIMM_E_INVALID;
+    if (g->order != SLIMM_ORDER_GROUPED) return gfail(g, SLIMM_E_INVALID, "a file split by byte range must be grouped by read name");
+    const uint32_t n = static_cast<uint32_t>(g->ctx.size());
+    static const bool trace = slimm::traced("cli");
+    std::vector<slimm::SplitRange> r(n);
+    for (uint32_t i = 0; i < n; ++i) GTRY(g, i, slimm::split_range(g->ctx[i], &r[i]));
+    std::vector<uint32_t> left_of(n, 0);
+    uint32_t left = 0;
+    for (uint32_t k = 1; k < n; ++k) {
+        uint64_t got = 0;
+        const bool final = r[k].found_start || k + 1 == n;
+        const int rc = slimm::split_append_head(g->ctx[left], g->ctx[k], final, &got);
+        if (rc == SLIMM_E_SPLIT) return gfail(g, SLIMM_E_SPLIT, "cut in front of member %u: %s", k, slimm_last_error(g->ctx[left]));
+        if (rc < 0) return member_failed(g, left, rc, "the bytes around a cut");
+        if (trace)
+            fprintf(stderr, "[trace] split: cut in front of member %u: %llu head bytes, %llu records across it, decoded by member %u\n", k,
+                    static_cast<unsigned long long>(r[k].head_len), static_cast<unsigned long long>(got), left);
+        left_of[k] = left;
+        if (r[k].found_start) left = k;
+    }
+    uint64_t starts = 0, plain = 0;
+    for (uint32_t k = 0; k < n; ++k) {
+        if (k && r[k].found_start) GTRY(g, k, slimm::split_join(g->ctx[left_of[k]], g->ctx[k]));
+    }
+    for (uint32_t k = 0; k < n; ++k) {
+        uint64_t s = 0, p = 0;
+        GTRY(g, k, slimm_get_q18_runs(g->ctx[k], &s, &p));
+        starts += s;
+        plain += p;
+    }
+    if (starts != plain)
+        return gfail(g, SLIMM_E_REGROUP, "read names ending in .1 / .2 without a mate flag, apart from the flagged records of the "
+                                         "shortened name: push this file to a group created with SLIMM_ORDER_ANY");
+    std::vector<uint64_t> from(n, 0);
+    uint32_t keeper = 0;
+    for (uint32_t k = 1; k < n; ++k) {
+        uint64_t p = 0;
+        GTRY(g, k, slimm::split_first_start(g->ctx[k], &p));
+        if (p) GTRY(g, keeper, slimm::split_take(g->ctx[keeper], g->ctx[k], p));
+        from[k] = p;
+        slimm::SplitRange now;
+        GTRY(g, k, slimm::split_range(g->ctx[k], &now));
+        if (trace)
+            fprintf(stderr, "[trace] split: member %u handed %llu records left to member %u, keeps %llu\n", k,
+                    static_cast<unsigned long long>(p), keeper, static_cast<unsigned long long>(now.n_records - p));
+        if (p < now.n_records) keeper = k;
+    }
+    for (uint32_t k = 0; k < n; ++k) GTRY(g, k, slimm::split_keep(g->ctx[k], from[k]));
+    g->stitched = true;
+    return SLIMM_OK;
+}
+
 // slimm::get_profiles() (src/slimm.hpp:447-489) over the members' reads: phases A, B, C(1) on every member with the two
 // exchanges in between, propagation and the profile on member 0 (every member holds the same merged results).
 int slimm_group_get_profiles(slimm_group* g, const char* path) {
@@ -650,7 +714,7 @@ int slimm_group_get_profiles(slimm_group* g, const char* path) {
     const uint32_t n = static_cast<uint32_t>(g->ctx.size());
     int rc = flush_carry(g, g->cur);
     if (rc != SLIMM_OK) return rc;
-    if (n > 1 && g->order == SLIMM_ORDER_GROUPED) {
+    if (n > 1 && g->order == SLIMM_ORDER_GROUPED && !g->stitched) {
         rc = deal_from_member0(g);
         if (rc != SLIMM_OK) return rc;
     }

@@ -217,6 +217,7 @@ bool AlignmentFile::open(const std::string& path) {
     cfill_ = cdone_ = cstart_ = 0;
     spare_.clear();
     order_ = SortOrder::Unknown;
+    header_bytes_ = 0;
     fp_ = fopen(path.c_str(), "rb");
     if (!fp_) {
         err_ = "Could not open " + path + "!";
@@ -480,7 +481,9 @@ bool AlignmentFile::read_bam_header() {
         pos_ += l_name;
         ref_len_.push_back(rd_u32(&buf_[pos_]));
         pos_ += 4;
+        header_bytes_ += 8ull + l_name;
     }
+    header_bytes_ += 12ull + l_text;
     return true;
 }
 

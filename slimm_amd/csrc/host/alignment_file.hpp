@@ -76,6 +76,8 @@ public:
     const std::vector<std::string>& ref_names() const { return ref_names_; }
     const std::vector<uint32_t>& ref_lengths() const { return ref_len_; }
     SortOrder sort_order() const { return order_; }
+    // BAM: the header's inflated bytes -- where the first alignment record starts in the inflated stream
+    uint64_t header_bytes() const { return header_bytes_; }
     // Q18 on a file grouped by QNAME (include/slimm_hip.h, "Q18 ON A GROUPED STREAM"): among the records read_batch /
     // read_into have handed out, some run of adjacent records with one canonical base holds SHORTENED names only -- their
     // flagged namesakes may lie anywhere in the file: the file must go through the any-order path
@@ -141,6 +143,7 @@ private:
     std::vector<std::string> ref_names_;
     std::vector<uint32_t> ref_len_;
     SortOrder order_ = SortOrder::Unknown;
+    uint64_t header_bytes_ = 0;
     // decoded byte window (BAM) / raw text window (SAM)
     // byte buffers whose resize() does not zero-fill: every byte is overwritten by fread / inflate right away
     template <typename T>

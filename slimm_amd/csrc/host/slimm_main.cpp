@@ -5,12 +5,14 @@
 // include/slimm_hip.h.  Extra options (no reference counterpart): --device N, --query-grouped, --any-order,
 // --dump-records (decode only, for reader tests on machines without a GPU).
 #include <dirent.h>
+#include <fcntl.h>
 #include <sys/stat.h>
 #include <sys/mman.h>
 #include <ctime>
 #include <unistd.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -118,6 +120,10 @@ SLIMM_FORWARD(int, slimm_push_records_packed, (slimm_ctx* a, const uint64_t* b, 
 SLIMM_FORWARD(int, slimm_push_bam_bytes, (slimm_ctx* a, const uint8_t* b, uint64_t c, int d, uint64_t* e), (a, b, c, d, e))
 SLIMM_FORWARD(int, slimm_push_bgzf_blocks, (slimm_ctx* a, const uint8_t* b, uint64_t c, uint32_t s, int d, uint64_t* e), (a, b, c, s, d, e))
 SLIMM_FORWARD(int, slimm_pin_host_buffer, (slimm_ctx* a, const void* b, uint64_t c), (a, b, c))
+SLIMM_FORWARD(int, slimm_host_bgzf_ranges, (const char* a, uint64_t b, uint32_t c, uint64_t* d), (a, b, c, d))
+SLIMM_FORWARD(int, slimm_set_input_mid_file, (slimm_ctx* a, int b, int c), (a, b, c))
+SLIMM_FORWARD(int, slimm_group_stitch_ranges, (slimm_group* a), (a))
+SLIMM_FORWARD(uint64_t, slimm_record_cap, (), ())
 SLIMM_FORWARD(int, slimm_shutdown, (), ())
 SLIMM_FORWARD(int, slimm_reset, (slimm_ctx* a), (a))
 SLIMM_FORWARD(int, slimm_check_grouping, (slimm_ctx* a, uint64_t* b), (a, b))
@@ -170,6 +176,7 @@ struct Options {  // arg_options, reference src/slimm.hpp:49-87
     bool verify_grouping = false;  // --verify-grouping: count the read names that come back (slimm_check_grouping) and warn
     unsigned device_inflate = 1;   // --device-inflate K: every K-th window read in place is inflated on the device (0: none)
     unsigned window_mb = 0;        // --window-mb N: bytes per window buffer (tests make windows smaller than a record)
+    bool split_input = false;      // --split-input (with --devices): every member reads its own byte range of a grouped BAM
 };
 bool g_trace = false;              // SLIMM_TRACE=cli (or all): millisecond marks of the stages on stderr
 
@@ -234,7 +241,7 @@ void usage() {
                  "  -ro, --raw-output             write raw reference statistics\n"
                  "  -co, --coverage-output        write raw coverage statistics\n"
                  "  -v,  --verbose\n"
-                 "       --device N | --devices N,M,... | --query-grouped | --any-order | --dump-records | --dump-raw\n"
+                 "       --device N | --devices N,M,... [--split-input] | --query-grouped | --any-order | --dump-records | --dump-raw\n"
                  "       --host-decode | --packed-records | --verify-grouping | --device-inflate K | --window-mb N |\n"
                  "       --decode-threads N | --no-mmap     (SLIMM_TRACE=cli: stage marks on stderr)\n";
 }
@@ -306,6 +313,8 @@ int parse(int argc, char** argv, Options& o) {
                 p = q + 1;
             }
             if (!o.devices.empty()) o.device = o.devices[0];
+        } else if (a == "--split-input") {
+            o.split_input = true;
         } else if (a == "--device") {
             if (!value(v)) return 1;
             o.device = atoi(v.c_str());
@@ -806,6 +815,164 @@ struct RecordPump {
     }
 };
 
+// --split-input: every member of a group reads, inflates and decodes its own contiguous byte range of a GROUPED BAM file
+// at once -- its own pread threads, page-locked buffers and pushing thread -- and the library stitches the cuts on the
+// devices (include/slimm_hip.h, "ONE BAM FILE SPLIT BY BYTE RANGE").  The reader threads are split over the members, not
+// multiplied (a command gets 16 CPUs).  Returns SLIMM_OK or the code of what failed; *why says what.
+struct SplitBuffers {   // (page-locked for the life of the group's contexts: they outlive the group)
+    struct Map {
+        uint8_t* p = nullptr;
+        size_t n = 0;
+        ~Map() {
+            if (p) munmap(p, n);
+        }
+    };
+    std::vector<std::unique_ptr<Map>> maps;
+    uint8_t* get(size_t n) {
+        void* p = mmap(nullptr, n, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
+        if (p == MAP_FAILED) return nullptr;
+        (void)madvise(p, n, MADV_HUGEPAGE);
+        maps.emplace_back(new Map{static_cast<uint8_t*>(p), n});
+        return static_cast<uint8_t*>(p);
+    }
+};
+int read_split(slimm_group* grp, uint32_t G, const std::string& path, uint64_t header_bytes, size_t window_cap, SplitBuffers& bufs,
+               std::string& why) {
+    std::vector<uint64_t> off(G + 1, 0);
+    if (header_bytes >= (1ull << 32) || slimm_host_bgzf_ranges(path.c_str(), header_bytes, G, off.data()) != SLIMM_OK) {
+        why = "the file's BGZF blocks could not be planned into ranges";
+        return SLIMM_E_INVALID;
+    }
+    const int fd = open(path.c_str(), O_RDONLY);
+    if (fd < 0) {
+        why = "could not open " + path;
+        return SLIMM_E_INVALID;
+    }
+    const unsigned cores = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+    const unsigned per_member = std::max(1u, cores / G);
+    // (three buffers a member: one being read, one being copied, the one before it still the library's until the next push)
+    const size_t cap = std::max<size_t>(1u << 20, G <= 2 ? window_cap : window_cap * 2 / G);
+    struct Member {
+        int rc = SLIMM_OK;
+        std::string err;
+        uint64_t records = 0, bytes = 0;
+        double pread_ms = 0, push_ms = 0, last_ms = 0;
+        uint8_t* buf[3] = {};
+    };
+    std::vector<Member> m(G);
+    for (uint32_t i = 0; i < G; ++i)
+        for (auto& b : m[i].buf)
+            if (!(b = bufs.get(cap))) {
+                close(fd);
+                why = "out of host memory for the members' buffers";
+                return SLIMM_E_INVALID;
+            }
+    auto ms = [](std::chrono::steady_clock::time_point a) {
+        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count();
+    };
+    auto member = [&](uint32_t i) {
+        Member& M = m[i];
+        slimm_ctx* ctx = slimm_group_context(grp, i);
+        auto failed = [&](int rc, const std::string& e) {
+            M.rc = rc;
+            M.err = "member " + std::to_string(i) + ": " + e;
+        };
+        int rc = slimm_set_input_mid_file(ctx, i > 0 ? 1 : 0, i + 1 < G ? 1 : 0);
+        if (rc == SLIMM_OK) rc = slimm_set_input_size_hint(ctx, off[i + 1] - off[i]);
+        if (rc != SLIMM_OK) return failed(rc, slimm_last_error(ctx));
+        for (auto* b : M.buf) (void)slimm_pin_host_buffer(ctx, b, cap);   // (pageable memory still works)
+        const uint64_t end = off[i + 1];
+        // whole BGZF blocks of [at, end) into buffer w, at most `cap` bytes, by pread on the member's share of the threads:
+        // the bytes of those blocks (0: none fits), -1 on a read error
+        auto read_blocks = [&](unsigned w, uint64_t at) -> long {
+            const size_t want = static_cast<size_t>(std::min<uint64_t>(cap, end - at));
+            if (!want) return 0;
+            const unsigned nt = static_cast<unsigned>(std::max<size_t>(1, std::min<size_t>(per_member, want >> 20)));
+            const size_t per = (want + nt - 1) / nt;
+            std::atomic<bool> ok{true};
+            std::vector<std::thread> th;
+            for (unsigned t = 0; t < nt; ++t)
+                th.emplace_back([&, t] {
+                    size_t lo = std::min(want, t * per);
+                    const size_t hi = std::min(want, lo + per);
+                    while (lo < hi) {
+                        const ssize_t k = pread(fd, M.buf[w] + lo, hi - lo, static_cast<off_t>(at + lo));
+                        if (k <= 0) {
+                            ok = false;
+                            return;
+                        }
+                        lo += static_cast<size_t>(k);
+                    }
+                });
+            for (auto& t : th) t.join();
+            if (!ok) return -1;
+            size_t n = 0;
+            while (want - n >= 18) {
+                const uint8_t* h = M.buf[w] + n;
+                const size_t bsize = (static_cast<size_t>(h[16]) | (static_cast<size_t>(h[17]) << 8)) + 1u;
+                if (h[0] != 0x1f || h[1] != 0x8b || want - n < bsize) break;
+                n += bsize;
+            }
+            return static_cast<long>(n);
+        };
+        // the next buffer is read while this one is pushed (the one before it is the library's until this push returns)
+        uint64_t pos = off[i];
+        auto t0 = std::chrono::steady_clock::now();
+        long n = read_blocks(0, pos);
+        M.pread_ms += ms(t0);
+        for (unsigned w = 0;; w = (w + 1) % 3) {
+            if (n < 0) return failed(SLIMM_E_INVALID, "read error");
+            if (n == 0 && pos < end) return failed(SLIMM_E_INVALID, "a BGZF block does not fit the window");
+            const bool last = pos + static_cast<uint64_t>(n) == end;
+            long next = 0;
+            double next_ms = 0;
+            std::thread ahead;
+            if (!last)
+                ahead = std::thread([&, w] {
+                    const auto a = std::chrono::steady_clock::now();
+                    next = read_blocks((w + 1) % 3, pos + static_cast<uint64_t>(n));
+                    next_ms = ms(a);
+                });
+            uint64_t got = 0;
+            t0 = std::chrono::steady_clock::now();
+            rc = n ? slimm_push_bgzf_blocks(ctx, M.buf[w], static_cast<uint64_t>(n), pos == off[i] && i == 0 ? static_cast<uint32_t>(header_bytes) : 0u,
+                                            last ? 1 : 0, &got)
+                   : slimm_push_bam_bytes(ctx, nullptr, 0, 1, &got);   // (an empty range)
+            const double t = ms(t0);
+            if (ahead.joinable()) ahead.join();
+            M.pread_ms += next_ms;
+            M.push_ms += t;
+            if (last) M.last_ms = t;
+            if (rc != SLIMM_OK) return failed(rc, slimm_last_error(ctx));
+            M.records += got;
+            M.bytes += static_cast<uint64_t>(n);
+            pos += static_cast<uint64_t>(n);
+            n = next;
+            if (last) return;
+        }
+    };
+    {
+        std::vector<std::thread> th;
+        for (uint32_t i = 0; i < G; ++i) th.emplace_back(member, i);
+        for (auto& t : th) t.join();
+    }
+    close(fd);
+    for (uint32_t i = 0; i < G; ++i) {
+        if (g_trace)
+            fprintf(stderr, "[trace] split member %u: bytes [%llu, %llu) of %llu, %llu records, pread %.2f ms, push %.2f ms, last push (wait) %.2f ms\n", i,
+                    static_cast<unsigned long long>(off[i]), static_cast<unsigned long long>(off[i + 1]), static_cast<unsigned long long>(off[G]),
+                    static_cast<unsigned long long>(m[i].records), m[i].pread_ms, m[i].push_ms, m[i].last_ms);
+    }
+    for (uint32_t i = 0; i < G; ++i)
+        if (m[i].rc != SLIMM_OK) {
+            why = m[i].err;
+            return m[i].rc;
+        }
+    const int rc = slimm_group_stitch_ranges(grp);
+    if (rc != SLIMM_OK) why = slimm_group_last_error(grp);
+    return rc;
+}
+
 // write_raw_stat (src/slimm.hpp:883-943) and write_coverage (:846-881) from a context that holds the finished columns and
 // coverage arrays.  global_bins: `ctx` is member 0 of a group after the bins exchange -- its arrays are the global ones,
 // but its count of non-zero uniq_cov2 bins is that of its own reads: counted here from the global array instead.
@@ -961,7 +1128,11 @@ bool get_profiles(Session& S, size_t file_index, bool regroup = false) {
     // decoding starts now; the records are claimed further down, when the context exists (one context: the device decodes)
     // (a group takes a GROUPED file through member 0's device decoders and deals the records device to device afterwards:
     // slimm_group_get_profiles; any other order: the host reader deals them by key)
-    RecordPump pump(bam, check_words, options.devices.size() <= 1 || record_order == SLIMM_ORDER_GROUPED, options);
+    // --split-input: every member of the group reads its own byte range of a grouped BAM (read_split): no pump
+    const bool split_input = options.split_input && options.devices.size() > 1 && record_order == SLIMM_ORDER_GROUPED && bam.is_bam() &&
+                             bam.regular_file() && !options.host_decode && !options.verify_grouping && !options.packed_records;
+    std::unique_ptr<RecordPump> pump;
+    if (!split_input) pump.reset(new RecordPump(bam, check_words, options.devices.size() <= 1 || record_order == SLIMM_ORDER_GROUPED, options));
 
     std::cerr << "Intializing coverages for all reference genome ... ";
     const uint32_t R = static_cast<uint32_t>(bam.ref_names().size());
@@ -1002,50 +1173,84 @@ bool get_profiles(Session& S, size_t file_index, bool regroup = false) {
     cfg.tax_name = tax_name.data();
     cfg.device = options.device;
     cfg.record_order = record_order;
-    if (options.devices.size() > 1) {
+    // ---- several GPUs, one process (--devices), or members of a group on ONE device for a file of more records than one
+    // context takes (for_cap): 1 = done, 0 = failed, 2 = more members wanted
+    SplitBuffers split_bufs;
+    auto run_group = [&](const std::vector<int>& devs, bool split, bool for_cap) -> int {
         // ---- several GPUs, one process: the group deals the records to its members by read and runs the phases with the
         // two RCCL exchanges in between (slimm_amd/csrc/group.hip); the profile comes from member 0
         slimm_group* grp = nullptr;
-        if (slimm_group_create(&cfg, options.devices.data(), static_cast<uint32_t>(options.devices.size()), &grp) != SLIMM_OK) {
+        if (slimm_group_create(&cfg, devs.data(), static_cast<uint32_t>(devs.size()), &grp) != SLIMM_OK) {
             std::cerr << "slimm: " << slimm_group_last_error(nullptr) << "\n";
-            return false;
+            return 0;
         }
         const bool want_arrays = options.raw_output || options.coverage_output;
         // -ro / -co read the coverage arrays (src/slimm.hpp:846-943): the members then exchange the integer bins themselves
         // (ncclAllReduce over [cov | uniq_cov], and over uniq_cov2 behind phase B) instead of their summaries
         if (want_arrays) (void)slimm_group_set_exchange(grp, SLIMM_EXCHANGE_BINS);
-        for (uint32_t i = 0; i < options.devices.size(); ++i) {
+        for (uint32_t i = 0; i < devs.size(); ++i) {
             (void)slimm_set_cutoff_cache(slimm_group_context(grp, i), S.cc_cache, S.ucc_cache);
             (void)slimm_keep_bins(slimm_group_context(grp, i), want_arrays ? 1 : 0);
         }
         slimm_ctx* c0 = slimm_group_context(grp, 0);
         trace.mark("lineage table + slimm_group_create");
         std::cerr << "[" << watch.lap() << " secs]" << std::endl;
-        std::cerr << "Analysing alignments on " << options.devices.size() << " devices ("
+        std::cerr << "Analysing alignments on " << devs.size() << " devices ("
                   << (slimm_group_uses_rccl(grp) ? "RCCL" : "copy") << " collectives) ... ";
-        if (pump.raw) {   // the file's size: what member 0 sizes its window buffers by
+        bool split_read = false;
+        if (split) {   // every member its own byte range (read_split); what fails there goes through member 0 after all
+            std::string why;
+            const int src = read_split(grp, static_cast<uint32_t>(devs.size()), path, bam.header_bytes(), RecordPump::raw_cap(), split_bufs, why);
+            trace.mark("split: read + decode + stitch");
+            if (src == SLIMM_E_REGROUP) {
+                slimm_group_destroy(grp);
+                return read_again_in_any_order() ? 1 : 0;
+            }
+            if (src != SLIMM_OK && for_cap && why.find("fewer than 2^31 records") != std::string::npos) {
+                slimm_group_destroy(grp);
+                return 2;   // (more members)
+            }
+            if (src != SLIMM_OK) {
+                std::cerr << "(split input: " << why << "; reading the file through member 0) ";
+                if (slimm_group_reset(grp) != SLIMM_OK) {
+                    std::cerr << "slimm: " << slimm_group_last_error(grp) << "\n";
+                    slimm_group_destroy(grp);
+                    return 0;
+                }
+                bam.close();
+                if (!bam.open(path)) {
+                    std::cerr << bam.error() << "\n";
+                    slimm_group_destroy(grp);
+                    return 0;
+                }
+            }
+            split_read = src == SLIMM_OK;
+        }
+        if (!pump && !split_read) pump.reset(new RecordPump(bam, check_words, true, options));
+        if (!split_read) {
+        if (pump->raw) {   // the file's size: what member 0 sizes its window buffers by
             struct stat fst;
             if (stat(path.c_str(), &fst) == 0 && S_ISREG(fst.st_mode)) (void)slimm_set_input_size_hint(c0, static_cast<uint64_t>(fst.st_size));
         }
-        bool pushed = (pump.raw ? pump.attach(c0) : pump.attach_group(grp)) && pump.finish();
-        long read_rc = pump.read_rc;
-        if (trace.on && pump.raw)
+        bool pushed = (pump->raw ? pump->attach(c0) : pump->attach_group(grp)) && pump->finish();
+        long read_rc = pump->read_rc;
+        if (trace.on && pump->raw)
             fprintf(stderr, "[trace] device decode on member 0: slimm_push_bam_bytes %.2f ms for %llu records, pusher waited %.2f ms for windows\n",
-                    pump.raw_push_ms, static_cast<unsigned long long>(pump.raw_records), pump.wait_ms);
-        if (!pushed && pump.raw && read_rc >= 0 &&
+                    pump->raw_push_ms, static_cast<unsigned long long>(pump->raw_records), pump->wait_ms);
+        if (!pushed && pump->raw && read_rc >= 0 &&
             (strstr(slimm_last_error(c0), "decode this file on the host") || strstr(slimm_last_error(c0), "fewer than 2^31 records"))) {
             // a record longer than the device decoder's carry, or more records than ONE context takes: the host reader deals them
             std::cerr << "(" << slimm_last_error(c0) << ": decoding on the host) ";
             if (slimm_group_reset(grp) != SLIMM_OK) {
                 std::cerr << "slimm: " << slimm_group_last_error(grp) << "\n";
                 slimm_group_destroy(grp);
-                return false;
+                return 0;
             }
             bam.close();
             if (!bam.open(path)) {
                 std::cerr << bam.error() << "\n";
                 slimm_group_destroy(grp);
-                return false;
+                return 0;
             }
             RecordPump again(bam, check_words, false, options);
             pushed = again.attach_group(grp) && again.finish();
@@ -1053,23 +1258,24 @@ bool get_profiles(Session& S, size_t file_index, bool regroup = false) {
         }
         trace.mark("rest of read + decode + push");
         if (!pushed || read_rc < 0) {
-            std::cerr << (pushed ? bam.error() : std::string("pushing records: ") + (pump.raw ? slimm_last_error(c0) : slimm_group_last_error(grp))) << "\n";
+            std::cerr << (pushed ? bam.error() : std::string("pushing records: ") + (pump->raw ? slimm_last_error(c0) : slimm_group_last_error(grp))) << "\n";
             slimm_group_destroy(grp);
-            return false;
+            return 0;
         }
+        }   // (!split_read)
         if (record_order == SLIMM_ORDER_GROUPED && bam.q18_regroup_needed()) {
             slimm_group_destroy(grp);
-            return read_again_in_any_order();
+            return read_again_in_any_order() ? 1 : 0;
         }
         const int grc = slimm_group_get_profiles(grp, get_tsv_file_name(options.output_prefix, path, "_profile").c_str());
         if (grc == SLIMM_E_REGROUP) {   // (member 0's decoders counted a run of shortened names only: Q18)
             slimm_group_destroy(grp);
-            return read_again_in_any_order();
+            return read_again_in_any_order() ? 1 : 0;
         }
         if (grc < 0) {
             std::cerr << "slimm: " << slimm_group_last_error(grp) << "\n";
             slimm_group_destroy(grp);
-            return false;
+            return 0;
         }
         trace.mark("phases + exchanges + profile");
         if (trace.on) trace_memory(c0);
@@ -1080,7 +1286,7 @@ bool get_profiles(Session& S, size_t file_index, bool regroup = false) {
         if (grc == SLIMM_E_NO_HITS) {
             std::cerr << "[WARNING] No mapped reads found in BAM file!" << std::endl;
             slimm_group_destroy(grp);
-            return true;
+            return 1;
         }
         if (options.min_reads == 0) options.min_reads = st.min_reads;
         if (options.verbose) {
@@ -1095,13 +1301,14 @@ bool get_profiles(Session& S, size_t file_index, bool regroup = false) {
         }
         if (want_arrays && !write_raw_and_coverage(S, c0, true, path, bam, accession, taxa_id, lineage, watch)) {
             slimm_group_destroy(grp);
-            return false;
+            return 0;
         }
         std::cerr << "[Done!] File took " << watch.elapsed() << " secs to process.\n";
         (void)slimm_get_cutoff_cache(c0, &S.cc_cache, &S.ucc_cache);
         slimm_group_destroy(grp);
-        return true;
-    }
+        return 1;
+    };
+    if (options.devices.size() > 1) return run_group(options.devices, split_input, false) == 1;
     slimm_ctx* ctx = nullptr;
     if (slimm_create(&cfg, &ctx) != SLIMM_OK) {
         std::cerr << "slimm: " << slimm_last_error(nullptr) << "\n";
@@ -1118,20 +1325,43 @@ bool get_profiles(Session& S, size_t file_index, bool regroup = false) {
 
     std::cerr << "Analysing alignments, reads and references ....... ";
     {
-        const bool pushed = pump.attach(ctx) && pump.finish();
-        if (trace.on && pump.raw)
+        const bool pushed = pump->attach(ctx) && pump->finish();
+        if (trace.on && pump->raw)
             fprintf(stderr, "[trace] device decode: inflate %.2f ms (on its own thread, from the moment the file was open), "
                             "slimm_push_bam_bytes %.2f ms for %llu records, pusher waited %.2f ms for windows; of the windows read in "
                             "place %llu were inflated on the host, %llu on the device\n",
-                    pump.decode_ms, pump.raw_push_ms, static_cast<unsigned long long>(pump.raw_records), pump.wait_ms,
-                    static_cast<unsigned long long>(pump.raw_windows_host), static_cast<unsigned long long>(pump.raw_windows_device));
+                    pump->decode_ms, pump->raw_push_ms, static_cast<unsigned long long>(pump->raw_records), pump->wait_ms,
+                    static_cast<unsigned long long>(pump->raw_windows_host), static_cast<unsigned long long>(pump->raw_windows_device));
         else if (trace.on)
             fprintf(stderr, "[trace] decode %.2f ms (on its own thread, from the moment the file was open), waiting for staging sets %.2f ms\n",
-                    pump.decode_ms, pump.wait_ms);
+                    pump->decode_ms, pump->wait_ms);
         trace.mark("rest of read + decode + push");
-        long n = pump.read_rc;
+        long n = pump->read_rc;
+        const uint64_t pump_records = pump->raw_records;
         bool ok = pushed;
-        if (!pushed && pump.raw && n >= 0 && strstr(slimm_last_error(ctx), "decode this file on the host")) {
+        if (!pushed && pump->raw && n >= 0 && record_order == SLIMM_ORDER_GROUPED && bam.is_bam() && bam.regular_file() &&
+            strstr(slimm_last_error(ctx), "fewer than 2^31 records")) {
+            // more records than one context takes: contexts of a group on this one device, each its own byte range of the
+            // file (read_split) -- twice as many until each range fits
+            std::cerr << "(" << slimm_last_error(ctx) << ": reading the file by byte range into several contexts of device "
+                      << options.device << ") ";
+            slimm_destroy(ctx);
+            pump.reset();
+            const uint64_t cap = slimm_record_cap();
+            uint32_t G = std::max<uint32_t>(2u, static_cast<uint32_t>(std::min<uint64_t>(64u, 2u * (pump_records + cap - 1) / cap)));
+            for (; G <= 128u; G *= 2u) {
+                bam.close();
+                if (!bam.open(path)) {
+                    std::cerr << bam.error() << "\n";
+                    return false;
+                }
+                const int r = run_group(std::vector<int>(G, options.device), true, true);
+                if (r != 2) return r == 1;
+            }
+            std::cerr << "slimm: more records than " << G / 2 << " contexts take\n";
+            return false;
+        }
+        if (!pushed && pump->raw && n >= 0 && strstr(slimm_last_error(ctx), "decode this file on the host")) {
             // a record longer than the device decoder's carry (16 MiB): this file goes through the host decoder after all
             std::cerr << "(" << slimm_last_error(ctx) << ": decoding on the host) ";
             CHECK(ctx, slimm_reset(ctx));

@@ -285,6 +285,17 @@ void launch_bam_find(hipStream_t st, const uint8_t* bytes, uint64_t lo, uint64_t
 void launch_bam_decode(hipStream_t st, const uint8_t* bytes, uint64_t lo, uint64_t end, const BamPiece* pieces, const uint32_t* offs,
                        BamCarry* carry, const BamWindowResult* result, bool marked, uint64_t out_at, uint64_t* key, int32_t* ref,
                        int32_t* pos, uint16_t* flag, uint32_t* check);
+// a byte range that starts inside a file (split.hip): the first offset in [lo, hi) where a plausible record starts (as
+// k_bam_pieces guesses a piece's first record) -> atomicMin into *out (set it to ~0 first); the name of the record at o
+// -> *name (as the carry keeps it)
+void launch_bam_first_guess(hipStream_t st, const uint8_t* bytes, uint64_t lo, uint64_t hi, uint64_t end, uint32_t n_refs,
+                            unsigned long long* out);
+void launch_bam_name_at(hipStream_t st, const uint8_t* bytes, uint64_t o, BamCarry* name);
+// the join of two members: does the right one's first record (first) continue the run the left one ended with (left)?
+// If so its run-start bit (word0) is cleared and the right member's Q18 counts (right) are corrected
+void launch_split_join(hipStream_t st, const BamCarry* left, const BamCarry* first, BamCarry* right, uint32_t* word0);
+// the index of the first record of words[0, n) that starts a run (n when none does) -> atomicMin into *out (set to n first)
+void launch_split_first_start(hipStream_t st, const uint32_t* words, uint64_t n, unsigned long long* out);
 
 // the scan of the pieces' counts + the window's result; sam_lo != 0xffffffff: SAM text (the window's stop is where the last
 // complete line ends; sam_lo when there is none)

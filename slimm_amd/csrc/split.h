@@ -1,0 +1,29 @@
+// Internal to the library: the per-member steps of slimm_group_stitch_ranges (group.hip drives them, split.hip holds them)
+// -- one BAM file split by byte range over a group's members (include/slimm_hip.h, "ONE BAM FILE SPLIT BY BYTE RANGE").
+// Every step finishes its own device work before it returns: the next step may run on another member's device.
+#pragma once
+#include <stdint.h>
+
+#include "../../include/slimm_hip.h"
+
+namespace slimm {
+
+struct SplitRange {
+    bool found_start = false;   // the range holds a record start (false: all its bytes are head)
+    uint64_t head_len = 0;      // bytes in front of its first record
+    uint64_t n_records = 0;     // records decoded so far
+};
+int split_range(slimm_ctx* c, SplitRange* out);
+// the head of `right` as one more window of `left` (final: it must end with a complete record, else SLIMM_E_SPLIT)
+int split_append_head(slimm_ctx* left, slimm_ctx* right, bool final, uint64_t* n_records);
+// `right`'s first record against the last record of `left` (its carry): the same name clears the run-start bit and
+// corrects right's Q18 counts
+int split_join(slimm_ctx* left, slimm_ctx* right);
+// the index of the first record that starts a run (the record count when none does)
+int split_first_start(slimm_ctx* c, uint64_t* index);
+// records [0, n) of src appended to dst, device to device
+int split_take(slimm_ctx* dst, slimm_ctx* src, uint64_t n);
+// the member's records are [from, its count) from now on; its Q18 counts are the group's business
+int split_keep(slimm_ctx* c, uint64_t from);
+
+}  // namespace slimm

@@ -1,0 +1,204 @@
+// One BAM file split by byte range over a group's members (include/slimm_hip.h, "ONE BAM FILE SPLIT BY BYTE RANGE"):
+// the host's plan of the ranges (slimm_host_bgzf_ranges) and the per-member steps of slimm_group_stitch_ranges (split.h;
+// group.hip runs them cut by cut).  A range that starts inside the file guesses its first record as k_bam_pieces guesses
+// a piece's (windows.hip, bam_decode.hip: k_bam_first_guess); the member on its left confirms the guess one level up, as
+// k_bam_verify confirms a piece's: its incomplete last record followed by the right member's head must be whole records
+// that end exactly where the guess begins.  The reference reads one file with one reader (src/misc.hpp:498-522).
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include "context.h"
+#include "split.h"
+
+namespace {
+
+inline uint32_t rd16(const uint8_t* p) { return static_cast<uint32_t>(p[0]) | (static_cast<uint32_t>(p[1]) << 8); }
+inline uint32_t rd32(const uint8_t* p) { return rd16(p) | (rd16(p + 2) << 16); }
+
+// the BGZF header at h (18 bytes): the block's size (BSIZE + 1), 0 when h is none -- gzip magic, deflate, FEXTRA, XLEN = 6,
+// one BC subfield of two bytes (SAM specification 4.1), and room for the 8-byte trailer and an empty deflate stream
+uint32_t bgzf_header_size(const uint8_t* h) {
+    if (h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || !(h[3] & 4)) return 0;
+    if (rd16(h + 10) != 6 || h[12] != 'B' || h[13] != 'C' || rd16(h + 14) != 2) return 0;
+    const uint32_t total = rd16(h + 16) + 1u;
+    return total >= 28u ? total : 0u;
+}
+
+struct File {
+    int fd = -1;
+    uint64_t size = 0;
+    ~File() {
+        if (fd >= 0) ::close(fd);
+    }
+    bool read(uint64_t off, uint8_t* dst, size_t n) const {
+        while (n) {
+            const ssize_t k = pread(fd, dst, n, static_cast<off_t>(off));
+            if (k <= 0) return false;
+            dst += k;
+            off += static_cast<uint64_t>(k);
+            n -= static_cast<size_t>(k);
+        }
+        return true;
+    }
+    uint32_t header_at(uint64_t off) const {   // the block size of a header at off, 0 when there is none
+        uint8_t h[18];
+        if (off + 18 > size || !read(off, h, 18)) return 0;
+        const uint32_t total = bgzf_header_size(h);
+        return (total && off + total <= size) ? total : 0u;
+    }
+    // a block starts at p: its header and the next three chain through BSIZE + 1, or the chain reaches the EOF block
+    // (28 bytes, ISIZE 0) or the file's end.  (Compressed bytes may hold a header look-alike; a chain of them hardly.)
+    bool chain_at(uint64_t p) const {
+        uint64_t off = p;
+        for (int k = 0; k < 4; ++k) {
+            if (k && off == size) return true;
+            const uint32_t total = header_at(off);
+            if (!total) return false;
+            if (k && total == 28u) {
+                uint8_t t[4];
+                if (read(off + 24, t, 4) && rd32(t) == 0) return true;
+            }
+            off += total;
+        }
+        return true;
+    }
+    // the first block start at or behind t (the file's size when there is none)
+    uint64_t cut_at(uint64_t t) const {
+        std::vector<uint8_t> buf(1u << 20);
+        while (t + 18 <= size) {
+            const size_t n = static_cast<size_t>(std::min<uint64_t>(buf.size(), size - t));
+            if (!read(t, buf.data(), n)) return size;
+            for (size_t i = 0; i + 18 <= n; ++i)
+                if (buf[i] == 0x1f && buf[i + 1] == 0x8b && bgzf_header_size(&buf[i]) && chain_at(t + i)) return t + i;
+            t += n - 17;
+        }
+        return size;
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+uint64_t slimm_record_cap(void) { return slimm::record_cap(); }
+
+int slimm_host_bgzf_ranges(const char* path, uint64_t skip, uint32_t n, uint64_t* offsets_out) {
+    if (!path || !n || !offsets_out) return SLIMM_E_INVALID;
+    File f;
+    f.fd = open(path, O_RDONLY);
+    struct stat sb;
+    if (f.fd < 0 || fstat(f.fd, &sb) != 0 || !S_ISREG(sb.st_mode)) return SLIMM_E_INVALID;
+    f.size = static_cast<uint64_t>(sb.st_size);
+    // no cut in front of the first block whose inflated bytes start at or behind `skip`: member 0 holds the whole header
+    uint64_t floor = 0, before = 0;
+    while (skip && before < skip && floor < f.size) {
+        const uint32_t total = f.header_at(floor);
+        uint8_t t[4];
+        if (!total || !f.read(floor + total - 4, t, 4)) return SLIMM_E_INVALID;   // (not a BGZF file)
+        before += rd32(t);
+        floor += total;
+    }
+    offsets_out[0] = 0;
+    for (uint32_t i = 1; i < n; ++i) {
+        const uint64_t t = floor + static_cast<uint64_t>(static_cast<unsigned __int128>(f.size - floor) * i / n);
+        offsets_out[i] = std::max(f.cut_at(t), offsets_out[i - 1]);
+    }
+    offsets_out[n] = f.size;
+    return SLIMM_OK;
+}
+
+}  // extern "C"
+
+namespace slimm {
+
+int split_range(slimm_ctx* c, SplitRange* out) {
+    if (!c || !out) return SLIMM_E_INVALID;
+    if (c->device < 0 || !c->bam.active || !c->bam.closed || c->bam.sam || c->order != SLIMM_ORDER_GROUPED)
+        return fail(c, SLIMM_E_INVALID, "a range of a split file: a GROUPED BAM range pushed to its end");
+    out->found_start = c->bam.found_start || !c->bam.starts_mid;
+    out->head_len = c->bam.starts_mid ? c->bam.head_len : 0u;
+    out->n_records = c->n_pushed;
+    return SLIMM_OK;
+}
+
+int split_append_head(slimm_ctx* left, slimm_ctx* right, bool final, uint64_t* n_records) {
+    (void)hipSetDevice(right->device);
+    HIP_TRY(right, hipStreamSynchronize(right->stream));   // (the head was copied aside on the right member's stream)
+    const uint64_t n = right->bam.starts_mid ? right->bam.head_len : 0u;
+    uint64_t got = 0;
+    const int rc = bam_append_window(left, right->bam.head_bytes.p, right->device, n, final, got);
+    if (rc != SLIMM_OK) return rc;
+    HIP_TRY(left, hipStreamSynchronize(left->stream));
+    if (n_records) *n_records = got;
+    return SLIMM_OK;
+}
+
+int split_join(slimm_ctx* left, slimm_ctx* right) {
+    slimm_ctx::BamDecode& R = right->bam;
+    if (!R.has_first || !right->n_pushed || !left->bam.carry.p) return SLIMM_OK;   // (nothing on one side: no run to join)
+    (void)hipSetDevice(left->device);
+    HIP_TRY(left, hipStreamSynchronize(left->stream));
+    (void)hipSetDevice(right->device);
+    HIP_TRY(right, R.join.ensure(1));
+    if (left->device == right->device)
+        HIP_TRY(right, hipMemcpyAsync(R.join.p, left->bam.carry.p, sizeof(BamCarry), hipMemcpyDeviceToDevice, right->stream));
+    else
+        HIP_TRY(right, hipMemcpyPeerAsync(R.join.p, right->device, left->bam.carry.p, left->device, sizeof(BamCarry), right->stream));
+    launch_split_join(right->stream, R.join.p, R.first.p, R.carry.p, reinterpret_cast<uint32_t*>(right->in_ref.p));
+    HIP_TRY(right, hipGetLastError());
+    HIP_TRY(right, hipStreamSynchronize(right->stream));
+    return SLIMM_OK;
+}
+
+int split_first_start(slimm_ctx* c, uint64_t* index) {
+    const uint64_t n = c->n_pushed;
+    *index = n;
+    if (!n) return SLIMM_OK;
+    (void)hipSetDevice(c->device);
+    HIP_TRY(c, c->bam.guess.ensure(1));
+    unsigned long long v = n;
+    HIP_TRY(c, hipMemcpyAsync(c->bam.guess.p, &v, sizeof(v), hipMemcpyHostToDevice, c->stream));
+    launch_split_first_start(c->stream, reinterpret_cast<const uint32_t*>(c->in_ref.p), n, c->bam.guess.p);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(&v, c->bam.guess.p, sizeof(v), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    *index = v;
+    return SLIMM_OK;
+}
+
+int split_take(slimm_ctx* dst, slimm_ctx* src, uint64_t n) {
+    if (!n) return SLIMM_OK;
+    if (n > src->n_pushed) return fail(dst, SLIMM_E_INVALID, "split_take: more records than the member holds");
+    if (dst->n_pushed + n >= record_cap()) return fail(dst, SLIMM_E_INVALID, "a context handles fewer than 2^31 records; shard the stream");
+    (void)hipSetDevice(src->device);
+    HIP_TRY(src, hipStreamSynchronize(src->stream));
+    (void)hipSetDevice(dst->device);
+    int rc = slimm_reserve(dst, dst->n_pushed + n);
+    if (rc != SLIMM_OK) return rc;
+    const uint64_t at = dst->n_pushed;
+    if (dst->device == src->device) {
+        HIP_TRY(dst, hipMemcpyAsync(dst->in_ref.p + at, src->in_ref.p, n * 4, hipMemcpyDeviceToDevice, dst->stream));
+        HIP_TRY(dst, hipMemcpyAsync(dst->in_pos.p + at, src->in_pos.p, n * 4, hipMemcpyDeviceToDevice, dst->stream));
+    } else {
+        HIP_TRY(dst, hipMemcpyPeerAsync(dst->in_ref.p + at, dst->device, src->in_ref.p, src->device, n * 4, dst->stream));
+        HIP_TRY(dst, hipMemcpyPeerAsync(dst->in_pos.p + at, dst->device, src->in_pos.p, src->device, n * 4, dst->stream));
+    }
+    HIP_TRY(dst, hipStreamSynchronize(dst->stream));
+    dst->n_pushed += n;
+    return SLIMM_OK;
+}
+
+int split_keep(slimm_ctx* c, uint64_t from) {
+    if (from > c->n_pushed) return fail(c, SLIMM_E_INVALID, "split_keep: past the member's records");
+    c->rec = DeviceRecords();
+    c->rec.ref = c->in_ref.p ? c->in_ref.p + from : nullptr;
+    c->rec.pos = c->in_pos.p ? c->in_pos.p + from : nullptr;
+    c->rec.marked = true;
+    c->rec.n = static_cast<uint32_t>(c->n_pushed - from);
+    c->marked = true;
+    c->bam.q18_by_group = true;
+    return SLIMM_OK;
+}
+
+}  // namespace slimm

@@ -54,7 +54,34 @@ int bam_finish_window(slimm_ctx* c, uint64_t j, uint64_t n_bytes, bool is_last, 
     hipStream_t st = c->stream;
     const bool marked = c->order == SLIMM_ORDER_GROUPED;
     const uint32_t b = static_cast<uint32_t>(j % slimm_ctx::kBamRing), nb = static_cast<uint32_t>((j + 1u) % slimm_ctx::kBamRing);
-    const uint64_t lo = kBamSlack - B.carry_bytes, end = kBamSlack + n_bytes;
+    uint64_t lo = kBamSlack - B.carry_bytes;
+    const uint64_t end = kBamSlack + n_bytes;
+    if (B.starts_mid && j == 0 && !B.sam) {
+        // A range that starts inside the file (slimm_set_input_mid_file): its first record is guessed from the bytes, as
+        // k_bam_pieces guesses a piece's; the bytes in front of it (the head, at most 16 MiB) stay on the device for the
+        // member on the left, which confirms the guess (slimm_group_stitch_ranges).  No record start at all: the whole
+        // window is head (a range inside one long record) -- only when it is the range's last window
+        if (n_bytes) HIP_TRY(c, hipStreamWaitEvent(st, B.copied[b], 0));
+        HIP_TRY(c, B.guess.ensure(1));
+        HIP_TRY(c, hipMemsetAsync(B.guess.p, 0xff, sizeof(unsigned long long), st));
+        launch_bam_first_guess(st, B.bytes[b].p, lo, std::min<uint64_t>(end, lo + kBamSlack + 1u), end, c->R, B.guess.p);
+        unsigned long long g = 0;
+        HIP_TRY(c, hipMemcpyAsync(&g, B.guess.p, sizeof(g), hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        B.found_start = g != ~0ull;
+        if (!B.found_start) {
+            if (!is_last || end - lo > kBamSlack)
+                return fail(c, SLIMM_E_SPLIT, "no record starts in the first 16 MiB of a range that starts inside the file");
+            g = end;
+        }
+        const uint64_t head = g - lo;
+        HIP_TRY(c, B.head_bytes.ensure(std::max<uint64_t>(head + 64u, 4096u)));
+        if (head) HIP_TRY(c, hipMemcpyAsync(B.head_bytes.p, B.bytes[b].p + lo, head, hipMemcpyDeviceToDevice, st));
+        B.head_len = head;
+        // (SLIMM_FORCE split_shift_guess: the join sees a guess one byte off, and must refuse it)
+        if (B.found_start && forced("split_shift_guess")) B.head_len = head ? head - 1u : 1u;
+        lo = g;
+    }
     const uint32_t np = B.sam ? sam_pieces(end - lo) : bam_pieces(end - lo);
     // (with room to spare and without a hipFree: windows differ by a few pieces, and a hipFree waits for the inflate kernels
     // of the windows behind this one)
@@ -83,8 +110,8 @@ int bam_finish_window(slimm_ctx* c, uint64_t j, uint64_t n_bytes, bool is_last, 
     if (tail > kBamSlack)
         return fail(c, SLIMM_E_INVALID, B.sam ? "a SAM line longer than 16 MiB: decode this file on the host"
                                               : "a BAM record longer than 16 MiB: decode this file on the host");
-    if (is_last && tail) return fail(c, SLIMM_E_INVALID, "truncated BAM record");
-    if (c->n_pushed + n_rec >= 0x7fffffffull) return fail(c, SLIMM_E_INVALID, "a context handles fewer than 2^31 records; shard the stream");
+    if (is_last && tail && !B.ends_mid) return fail(c, SLIMM_E_INVALID, "truncated BAM record");
+    if (c->n_pushed + n_rec >= record_cap()) return fail(c, SLIMM_E_INVALID, "a context handles fewer than 2^31 records; shard the stream");
     int rc = slimm_reserve(c, c->n_pushed + n_rec);
     if (rc != SLIMM_OK) return rc;
     if (!marked) {  // (the four-array form's flag and check arrays appear at a file's first window)
@@ -104,6 +131,11 @@ int bam_finish_window(slimm_ctx* c, uint64_t j, uint64_t n_bytes, bool is_last, 
     else
         launch_bam_decode(st, B.bytes[b].p, lo, end, B.pieces.p, B.offs.p, B.carry.p, B.result.p, marked, c->n_pushed, c->in_key.p,
                           c->in_ref.p, c->in_pos.p, c->in_flag.p, c->in_check.p);
+    if (B.starts_mid && !B.has_first && n_rec && !B.sam) {   // (the range's first record: a window's first record starts at lo)
+        HIP_TRY(c, B.first.ensure(1));
+        launch_bam_name_at(st, B.bytes[b].p, lo, B.first.p);
+        B.has_first = true;
+    }
     if (tail) {  // the incomplete record goes in front of the next window (whose own bytes may be on their way already)
         if (B.bytes[nb].cap < kBamSlack + 64) HIP_TRY(c, B.bytes[nb].ensure(kBamSlack + 64));
         HIP_TRY(c, hipMemcpyAsync(B.bytes[nb].p + kBamSlack - tail, B.bytes[b].p + stop, tail, hipMemcpyDeviceToDevice, st));
@@ -126,6 +158,15 @@ int bam_finish_window(slimm_ctx* c, uint64_t j, uint64_t n_bytes, bool is_last, 
     return SLIMM_OK;
 }
 }  // namespace
+
+
+int slimm_set_input_mid_file(slimm_ctx* c, int starts_mid_file, int ends_mid_file) {
+    if (!c) return SLIMM_E_INVALID;
+    if (c->bam.active) return fail(c, SLIMM_E_INVALID, "slimm_set_input_mid_file: before the range's first window");
+    c->bam.starts_mid = starts_mid_file != 0;
+    c->bam.ends_mid = ends_mid_file != 0;
+    return SLIMM_OK;
+}
 
 namespace {
 enum { kFormatBam = 0, kFormatBgzf = 1, kFormatSam = 2 };
@@ -364,6 +405,8 @@ int bam_push_window(slimm_ctx* c, const uint8_t* bytes, uint64_t src_bytes, int 
         B.sam = sam;
         B.planned = false;
         B.sam_last_byte = '\n';
+        B.found_start = B.has_first = B.q18_by_group = false;
+        B.head_len = 0;
         c->marked = marked;
         c->has_check = !marked;
         c->packed = false;
@@ -522,7 +565,7 @@ int bam_push_window(slimm_ctx* c, const uint8_t* bytes, uint64_t src_bytes, int 
         total += got;
     }
     if (last) {
-        if (!had_any && B.carry_bytes) return fail(c, SLIMM_E_INVALID, "truncated BAM record");
+        if (!had_any && B.carry_bytes && !B.ends_mid) return fail(c, SLIMM_E_INVALID, "truncated BAM record");
         B.closed = true;
         bam_free_outgrown(c);
     } else {
@@ -539,3 +582,37 @@ int bam_push_window(slimm_ctx* c, const uint8_t* bytes, uint64_t src_bytes, int 
 
 
 }  // extern "C"
+
+namespace slimm {
+// slimm_group_stitch_ranges (split.hip): the head of the member on the right -- n bytes at src, on device src_device -- as one
+// more window of this member, behind the incomplete record its last window ended with.  final: the window must end with a
+// complete record; anything else means the right member guessed its first record wrong (SLIMM_E_SPLIT)
+int bam_append_window(slimm_ctx* c, const uint8_t* src, int src_device, uint64_t n, bool final, uint64_t& n_rec) {
+    slimm_ctx::BamDecode& B = c->bam;
+    n_rec = 0;
+    if (!B.active || !B.closed || B.head != B.windows || B.sam) return fail(c, SLIMM_E_INVALID, "a range's bytes are joined once it is pushed");
+    (void)hipSetDevice(c->device);
+    int rc = bam_window_buffer(c, n);
+    if (rc != SLIMM_OK) return rc;
+    const uint64_t j = B.windows;
+    const uint32_t b = static_cast<uint32_t>(j % slimm_ctx::kBamRing);
+    if (n) {
+        if (src_device == c->device)
+            HIP_TRY(c, hipMemcpyAsync(B.bytes[b].p + kBamSlack, src, n, hipMemcpyDeviceToDevice, c->stream));
+        else
+            HIP_TRY(c, hipMemcpyPeerAsync(B.bytes[b].p + kBamSlack, c->device, src, src_device, n, c->stream));
+        HIP_TRY(c, hipEventRecord(B.copied[b], c->stream));
+    }
+    B.inflated[b] = false;
+    B.win_bytes[b] = n;
+    ++B.windows;
+    const bool starts_mid = B.starts_mid;
+    B.starts_mid = B.starts_mid && B.found_start;   // (a range of no record start: its first record is in this window)
+    rc = bam_finish_window(c, j, n, false, n_rec);
+    B.starts_mid = starts_mid;
+    ++B.head;
+    if (rc != SLIMM_OK) return fail(c, SLIMM_E_SPLIT, "the bytes around a cut: %s", c->err.c_str());
+    if (final && B.carry_bytes) return fail(c, SLIMM_E_SPLIT, "the record chain across a cut does not end where the next range's first record was guessed");
+    return SLIMM_OK;
+}
+}  // namespace slimm
