@@ -70,7 +70,7 @@ public:
     void close();
     const std::string& error() const { return err_; }
     bool is_bam() const { return bam_; }
-    // "libdeflate" when libdeflate.so.0 could be dlopen()ed (and SLIMM_INFLATE is not "zlib"), else "zlib"
+    // "libdeflate" when libdeflate.so.0 could be dlopen()ed, else "zlib"
     static const char* inflate_backend();
 
     const std::vector<std::string>& ref_names() const { return ref_names_; }

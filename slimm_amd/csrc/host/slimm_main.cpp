@@ -423,24 +423,48 @@ struct Session {  // what the one `slimm` object of the reference keeps across f
     uint32_t total_hits = 0;
 };
 
+// What one reading of a file comes to
+enum class Outcome {
+    Done,
+    Failed,              // (the reason is printed)
+    ReadAgainAnyOrder,   // Q18 on a file read as a grouped one: the file goes through the any-order path instead
+    MoreMembers,         // more records than the contexts of the group take (a group on one device: run_group)
+};
+
 #define CHECK(ctx, call)                                                            \
     do {                                                                            \
-        int rc_ = (call);                                                           \
-        if (rc_ < 0) {                                                              \
+        if ((call) < 0) {                                                           \
             std::cerr << "slimm: " << #call << ": " << slimm_last_error(ctx) << "\n"; \
-            if (ctx) slimm_destroy(ctx);                                            \
-            return false;                                                           \
+            return Outcome::Failed;                                                 \
         }                                                                           \
     } while (0)
 
-#define CHECK_KEEP(ctx, call)                                                       \
-    do {                                                                            \
-        int rc_ = (call);                                                           \
-        if (rc_ < 0) {                                                              \
-            std::cerr << "slimm: " << #call << ": " << slimm_last_error(ctx) << "\n"; \
-            return false;                                                           \
-        }                                                                           \
-    } while (0)
+// the library's handles, destroyed when their owner goes
+using CtxPtr = std::unique_ptr<slimm_ctx, void (*)(slimm_ctx*)>;
+using GroupPtr = std::unique_ptr<slimm_group, void (*)(slimm_group*)>;
+
+// the file's size: what the library sizes its window buffers by (include/slimm_hip.h, slimm_set_input_size_hint)
+void set_size_hint(slimm_ctx* ctx, const std::string& path) {
+    struct stat st;
+    if (stat(path.c_str(), &st) == 0 && S_ISREG(st.st_mode)) (void)slimm_set_input_size_hint(ctx, static_cast<uint64_t>(st.st_size));
+}
+
+// the file from its first record again; false after printing why it could not be opened
+bool reopen(AlignmentFile& bam, const std::string& path) {
+    bam.close();
+    if (bam.open(path)) return true;
+    std::cerr << bam.error() << "\n";
+    return false;
+}
+
+// The two failed pushes the command reacts to, told apart by the library's message (they share SLIMM_E_INVALID with every
+// other failed push): a record longer than the device decoder's carry, and more records than one context takes.
+enum class PushError { HostDecode, RecordCap, Other };
+PushError classify(const char* message) {
+    if (strstr(message, "decode this file on the host")) return PushError::HostDecode;
+    if (strstr(message, "fewer than 2^31 records")) return PushError::RecordCap;
+    return PushError::Other;
+}
 
 float depth_of(const uint32_t* bins, uint32_t n, uint32_t nz) {  // reference_contig.hpp:188-207 + misc.hpp:285-289
     if (nz == 0) return 0.0f;
@@ -478,6 +502,26 @@ void trace_memory(slimm_ctx* ctx) {
             total / 1e9, win / 1e9, hwm_kb / 1e6);
 }
 
+// Where a file's records go: one context, or a group that deals the decoded records to its members (ctx is then member 0,
+// which takes the device decoders' bytes: slimm_group_get_profiles deals those records device to device afterwards).
+struct Target {
+    slimm_ctx* ctx = nullptr;
+    slimm_group* group = nullptr;
+    int push_checked(const uint64_t* key, const int32_t* ref, const int32_t* pos, const uint16_t* flag, const uint32_t* check,
+                     uint64_t n) const {
+        return group ? slimm_group_push_records_checked(group, key, ref, pos, flag, check, n)
+                     : slimm_push_records_checked(ctx, key, ref, pos, flag, check, n);
+    }
+    int push_marked(const uint32_t* word, const int32_t* pos, uint64_t n) const {
+        return group ? slimm_group_push_records_marked(group, word, pos, n) : slimm_push_records_marked(ctx, word, pos, n);
+    }
+    int push_packed(const uint64_t* key, const int32_t* ref, const int32_t* pos, uint64_t n) const {
+        return group ? slimm_group_push_records_packed(group, key, ref, pos, n) : slimm_push_records_packed(ctx, key, ref, pos, n);
+    }
+    int reset() const { return group ? slimm_group_reset(group) : slimm_reset(ctx); }
+    const char* error() const { return group ? slimm_group_last_error(group) : slimm_last_error(ctx); }
+};
+
 // The record stream of one file, decoded on a thread of its own from the moment the file is open: while the main thread
 // builds the lineage table and creates the context (the HIP runtime's start-up included), batches pile up in host
 // memory; once the context exists they are pushed in order and the decoder switches to the context's page-locked
@@ -506,8 +550,7 @@ struct RecordPump {
     std::mutex mu;
     std::condition_variable cv;
     std::deque<Batch> queued;
-    slimm_ctx* ctx = nullptr;  // set by attach(): from then on the decoder pushes by itself
-    slimm_group* group = nullptr;  // ... or a group of contexts (--devices): the group deals the records to its members
+    Target target;             // set by drain(): from then on the decoder pushes by itself
     bool failed = false;       // a push failed (slimm_last_error says why)
     long read_rc = 0;          // the reader's last answer: 0 = end of file, -1 = format error
     double decode_ms = 0, wait_ms = 0;
@@ -702,18 +745,11 @@ struct RecordPump {
         have_last = true;
         return word;
     }
-    int push(slimm_ctx* c, Batch& b) {
-        if (b.check) return slimm_push_records_checked(c, b.key.get(), b.ref.get(), b.pos.get(), b.flag.get(), b.check.get(), b.n);
-        if (marked) return slimm_push_records_marked(c, mark(b.key.get(), b.flag.get(), b.ref.get(), b.n), b.pos.get(), b.n);
+    int push(Batch& b) {
+        if (b.check) return target.push_checked(b.key.get(), b.ref.get(), b.pos.get(), b.flag.get(), b.check.get(), b.n);
+        if (marked) return target.push_marked(mark(b.key.get(), b.flag.get(), b.ref.get(), b.n), b.pos.get(), b.n);
         pack(b.key.get(), b.flag.get(), b.n);
-        return slimm_push_records_packed(c, b.key.get(), b.ref.get(), b.pos.get(), b.n);
-    }
-    int group_push(slimm_group* g, Batch& b) {
-        if (b.check)
-            return slimm_group_push_records_checked(g, b.key.get(), b.ref.get(), b.pos.get(), b.flag.get(), b.check.get(), b.n);
-        if (marked) return slimm_group_push_records_marked(g, mark(b.key.get(), b.flag.get(), b.ref.get(), b.n), b.pos.get(), b.n);
-        pack(b.key.get(), b.flag.get(), b.n);
-        return slimm_group_push_records_packed(g, b.key.get(), b.ref.get(), b.pos.get(), b.n);
+        return target.push_packed(b.key.get(), b.ref.get(), b.pos.get(), b.n);
     }
     static double ms(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
         return std::chrono::duration<double, std::milli>(b - a).count();
@@ -725,7 +761,7 @@ struct RecordPump {
             {
                 std::lock_guard<std::mutex> g(mu);
                 if (failed) return;
-                c = (group || want_check) ? nullptr : ctx;
+                c = (target.group || want_check) ? nullptr : target.ctx;
             }
             if (c) {  // straight into a staging set
                 uint64_t* key;
@@ -763,12 +799,10 @@ struct RecordPump {
             }
             b.n = static_cast<uint64_t>(n);
             std::unique_lock<std::mutex> g(mu);
-            cv.wait(g, [&] { return ctx || group || failed || queued.size() < kMaxQueued; });
+            cv.wait(g, [&] { return target.ctx || failed || queued.size() < kMaxQueued; });
             if (failed) return;
-            if (group) {
-                if (group_push(group, b) < 0) break;
-            } else if (ctx) {  // attached meanwhile: everything queued before has been pushed, this batch follows
-                if (push(ctx, b) < 0) break;
+            if (target.ctx) {  // attached: everything queued before has been pushed, this batch follows
+                if (push(b) < 0) break;
             } else {
                 queued.push_back(std::move(b));
             }
@@ -776,42 +810,42 @@ struct RecordPump {
         std::lock_guard<std::mutex> g(mu);
         failed = true;
     }
-    // pushes what was decoded so far and hands the context to the decoder; false when a push failed
-    bool attach(slimm_ctx* c) {
+    // pushes what was decoded so far into `t`, hands `t` to the decoder and waits for the end of the file: the threads are
+    // joined before this returns, so that `t` may go right after; false on a failed push
+    bool drain(Target t) {
         if (raw) {
-            raw_pusher = std::thread([this, c] { push_raw(c); });
-            return true;
+            raw_pusher = std::thread([this, c = t.ctx] { push_raw(c); });
+        } else {
+            std::unique_lock<std::mutex> g(mu);
+            target = t;
+            for (Batch& b : queued)
+                if (push(b) < 0) {
+                    failed = true;
+                    break;
+                }
+            queued.clear();
+            cv.notify_all();
         }
-        std::unique_lock<std::mutex> g(mu);
-        for (Batch& b : queued)
-            if (push(c, b) < 0) {
-                failed = true;
-                cv.notify_all();
-                return false;
-            }
-        queued.clear();
-        ctx = c;
-        cv.notify_all();
-        return true;
-    }
-    bool attach_group(slimm_group* grp) {
-        std::unique_lock<std::mutex> g(mu);
-        for (Batch& b : queued)
-            if (group_push(grp, b) < 0) {
-                failed = true;
-                cv.notify_all();
-                return false;
-            }
-        queued.clear();
-        group = grp;
-        cv.notify_all();
-        return true;
-    }
-    // waits for the end of the file; false on a failed push
-    bool finish() {
         th.join();
         if (raw_pusher.joinable()) raw_pusher.join();
         return !failed;
+    }
+    // SLIMM_TRACE=cli: what the threads took (a group: member 0's device decode only)
+    void report(bool group) const {
+        if (group) {
+            if (raw)
+                fprintf(stderr, "[trace] device decode on member 0: slimm_push_bam_bytes %.2f ms for %llu records, pusher waited %.2f ms for windows\n",
+                        raw_push_ms, static_cast<unsigned long long>(raw_records), wait_ms);
+        } else if (raw) {
+            fprintf(stderr, "[trace] device decode: inflate %.2f ms (on its own thread, from the moment the file was open), "
+                            "slimm_push_bam_bytes %.2f ms for %llu records, pusher waited %.2f ms for windows; of the windows read in "
+                            "place %llu were inflated on the host, %llu on the device\n",
+                    decode_ms, raw_push_ms, static_cast<unsigned long long>(raw_records), wait_ms,
+                    static_cast<unsigned long long>(raw_windows_host), static_cast<unsigned long long>(raw_windows_device));
+        } else {
+            fprintf(stderr, "[trace] decode %.2f ms (on its own thread, from the moment the file was open), waiting for staging sets %.2f ms\n",
+                    decode_ms, wait_ms);
+        }
     }
 };
 
@@ -973,14 +1007,30 @@ int read_split(slimm_group* grp, uint32_t G, const std::string& path, uint64_t h
     return rc;
 }
 
+// One reading of a file up to its context: the file open at its first record, the choices its header and the options make,
+// the pump that decodes from the moment the file is open, and the tables slimm_config points into.
+struct Reading {
+    std::string path;
+    Lap watch;
+    Trace trace;
+    AlignmentFile bam;
+    int record_order = SLIMM_ORDER_ANY;
+    bool check_words = false;   // the stream is in no particular order: every record carries a second hash of its name
+    bool split_input = false;   // --split-input: every member of the group reads its own byte range (read_split): no pump
+    std::unique_ptr<RecordPump> pump;
+    SplitBuffers split_bufs;
+    std::vector<std::string> accession;
+    std::vector<uint32_t> taxa_id, lineage, tax_id, tax_rank;
+    std::vector<const char*> tax_name;
+    slimm_config cfg;
+};
+
 // write_raw_stat (src/slimm.hpp:883-943) and write_coverage (:846-881) from a context that holds the finished columns and
 // coverage arrays.  global_bins: `ctx` is member 0 of a group after the bins exchange -- its arrays are the global ones,
 // but its count of non-zero uniq_cov2 bins is that of its own reads: counted here from the global array instead.
-bool write_raw_and_coverage(Session& S, slimm_ctx* ctx, bool global_bins, const std::string& path, const AlignmentFile& bam,
-                            const std::vector<std::string>& accession, const std::vector<uint32_t>& taxa_id,
-                            const std::vector<uint32_t>& lineage, Lap& watch) {
+Outcome write_raw_and_coverage(Session& S, Reading& F, slimm_ctx* ctx, bool global_bins) {
     const Options& options = S.options;
-    const uint32_t R = static_cast<uint32_t>(accession.size());
+    const uint32_t R = static_cast<uint32_t>(F.accession.size());
     slimm_stats st;
     slimm_get_stats(ctx, &st);
     std::vector<uint32_t> reads(R), uniq(R), uniq2(R), nbins(R), nz(R), nzu(R), nzu2(R);
@@ -990,13 +1040,13 @@ bool write_raw_and_coverage(Session& S, slimm_ctx* ctx, bool global_bins, const 
     if (options.raw_output || options.coverage_output) {
         slimm_ref_columns cols = {reads.data(), uniq.data(), uniq2.data(), nbins.data(), nz.data(),
                                   nzu.data(),   nzu2.data(), valid.data(), ab.data(),    uab.data()};
-        CHECK_KEEP(ctx, slimm_get_ref_columns(ctx, &cols));
+        CHECK(ctx, slimm_get_ref_columns(ctx, &cols));
         cov.resize(st.total_bins);
         ucov.resize(st.total_bins);
         ucov2.resize(st.total_bins);
-        CHECK_KEEP(ctx, slimm_get_bins(ctx, 0, cov.data()));
-        CHECK_KEEP(ctx, slimm_get_bins(ctx, 1, ucov.data()));
-        CHECK_KEEP(ctx, slimm_get_bins(ctx, 2, ucov2.data()));
+        CHECK(ctx, slimm_get_bins(ctx, 0, cov.data()));
+        CHECK(ctx, slimm_get_bins(ctx, 1, ucov.data()));
+        CHECK(ctx, slimm_get_bins(ctx, 2, ucov2.data()));
         if (global_bins) {  // reference_contig.hpp:84-91 over the global uniq_cov2
             uint64_t off = 0;
             for (uint32_t i = 0; i < R; ++i) {
@@ -1013,39 +1063,39 @@ bool write_raw_and_coverage(Session& S, slimm_ctx* ctx, bool global_bins, const 
     };
     if (options.raw_output) {  // write_raw_stat :883-943
         std::cerr << "Writing features to a file ....................... ";
-        std::ofstream o(get_tsv_file_name(options.output_prefix, path, "_raw"));
+        std::ofstream o(get_tsv_file_name(options.output_prefix, F.path, "_raw"));
         o << "accesion\ttaxaid\tname\treads_count\tabundance\tuniq1_abundance\tuniq2_abundance\tgenome_length\t"
              "uniq1_reads_count\tuniq2_reads_count\tbins_count\tbins_count(>0)\tuniq1_bins_count(>0)\t"
              "uniq2_bins_count(>0)\tcoverage_depth\tuniq1_coverage_depth\tuniq2_coverage_depth\tcoverage(%)\t"
              "uniq1_coverage(%)\tuniq2_coverage(%)\n";
         uint64_t off = 0;
         for (uint32_t i = 0; i < R; ++i) {
-            std::string nm = name_of(taxa_id[i]);
+            std::string nm = name_of(F.taxa_id[i]);
             if (nm.empty()) nm = "no_name_found";
             const uint32_t nb = nbins[i];
-            o << accession[i] << "\t" << taxa_id[i] << "\t" << nm << "\t" << reads[i] << "\t" << ab[i] << "\t" << uab[i] << "\t"
-              << 0.0f << "\t" << bam.ref_lengths()[i] << "\t" << uniq[i] << "\t" << uniq2[i] << "\t" << nb << "\t" << nz[i] << "\t"
+            o << F.accession[i] << "\t" << F.taxa_id[i] << "\t" << nm << "\t" << reads[i] << "\t" << ab[i] << "\t" << uab[i] << "\t"
+              << 0.0f << "\t" << F.bam.ref_lengths()[i] << "\t" << uniq[i] << "\t" << uniq2[i] << "\t" << nb << "\t" << nz[i] << "\t"
               << nzu[i] << "\t" << nzu2[i] << "\t" << depth_of(&cov[off], nb, nz[i]) << "\t" << depth_of(&ucov[off], nb, nzu[i])
               << "\t" << depth_of(&ucov2[off], nb, nzu2[i]) << "\t" << float(nz[i]) / nb << "\t" << float(nzu[i]) / nb << "\t"
               << float(nzu2[i]) / nb << "\n";
             off += nb;
         }
-        std::cerr << "[" << watch.lap() << " secs]" << std::endl;
+        std::cerr << "[" << F.watch.lap() << " secs]" << std::endl;
     }
     if (options.coverage_output) {  // write_coverage :846-881
         std::cerr << "Writing coverage profiles to a file ....................... ";
-        std::ofstream a(get_tsv_file_name(options.output_prefix, path, "_coverage"));
-        std::ofstream b(get_tsv_file_name(options.output_prefix, path, "_uniq_coverage"));
-        std::ofstream c(get_tsv_file_name(options.output_prefix, path, "_uniq_coverage2"));
+        std::ofstream a(get_tsv_file_name(options.output_prefix, F.path, "_coverage"));
+        std::ofstream b(get_tsv_file_name(options.output_prefix, F.path, "_uniq_coverage"));
+        std::ofstream c(get_tsv_file_name(options.output_prefix, F.path, "_uniq_coverage2"));
         uint64_t off = 0;
         for (uint32_t i = 0; i < R; ++i) {
             const uint32_t nb = nbins[i];
             if (valid[i]) {
-                a << accession[i];
-                b << accession[i];
-                c << accession[i];
+                a << F.accession[i];
+                b << F.accession[i];
+                c << F.accession[i];
                 for (int k = 0; k < 8; ++k) {
-                    std::string nm = name_of(lineage[static_cast<size_t>(i) * 8 + k]);
+                    std::string nm = name_of(F.lineage[static_cast<size_t>(i) * 8 + k]);
                     a << "," << nm;
                     b << "," << nm;
                     c << "," << nm;
@@ -1061,368 +1111,296 @@ bool write_raw_and_coverage(Session& S, slimm_ctx* ctx, bool global_bins, const 
             }
             off += nb;
         }
-        std::cerr << "[" << watch.lap() << " secs]" << std::endl;
+        std::cerr << "[" << F.watch.lap() << " secs]" << std::endl;
     }
 
-    return true;
+    return Outcome::Done;
 }
 
-// slimm::get_profiles() for one file (src/slimm.hpp:395-496)
-// regroup: the file was found to need the any-order path while it was read as a grouped one (Q18, below): second reading
-bool get_profiles(Session& S, size_t file_index, bool regroup = false) {
+// average read length from a sample of 100k records with a sequence (src/misc.hpp:509-522); 0: no record has one
+uint32_t average_read_length(AlignmentFile& bam) {
+    RecordBatch b;
+    uint32_t count = 0, total = 0;
+    while (count < 100000) {
+        b.clear();
+        long n = bam.read_batch(b, 4096);
+        if (n <= 0) break;
+        for (size_t i = 0; i < b.size() && count < 100000; ++i) {
+            if (b.l_seq[i] == 0) continue;
+            total += b.l_seq[i];
+            ++count;
+        }
+    }
+    return count ? total / count : 0;
+}
+
+// Opens the file and sets a reading of it up (src/slimm.hpp:395-445).  any_order: the second reading of a file that asked
+// for the any-order path.  nullptr when the file ends here: `end` says how (Done: skipped, src/misc.hpp:500-504).
+std::unique_ptr<Reading> set_up(Session& S, const std::string& path, bool any_order, Outcome& end) {
     Options& options = S.options;
-    const std::string path = S.input_paths[file_index];
-    Lap watch;
-    Trace trace;
-    if (!regroup)
-        std::cerr << "\nReading " << file_index + 1 << " of " << S.input_paths.size() << " files ... (" << get_file_name(path) << ")\n"
-                  << "=================================================================\n";
-    // Q18 on a file grouped by QNAME (include/slimm_hip.h, "Q18 ON A GROUPED STREAM"): a read named `r.1` without a mate flag
-    // is the reference's read of the first-in-pair records of `r`, wherever those lie in the file (src/slimm.hpp:204-211).
-    // The readers count the runs of such shortened names that stand apart from their namesakes; a file that has one is read
-    // again, in any order (a fresh context of the same process: the HIP runtime and the page cache are warm).
-    auto read_again_in_any_order = [&]() {
-        std::cerr << "\n(read names ending in .1 / .2 without a mate flag, apart from the flagged records of the shortened name: "
-                     "reading " << get_file_name(path) << " again as a file in no particular order)\n";
-        return get_profiles(S, file_index, true);
-    };
-    AlignmentFile bam;
+    std::unique_ptr<Reading> F(new Reading);
+    F->path = path;
+    AlignmentFile& bam = F->bam;
+    end = Outcome::Done;
     if (!bam.open(path)) {  // src/misc.hpp:500-504: message, skip the file
         std::cerr << bam.error() << "\n";
-        return true;
+        return nullptr;
     }
-    // average read length from a sample of 100k records with a sequence (src/misc.hpp:509-522)
-    uint32_t avg_read_length = 0;
-    {
-        RecordBatch b;
-        uint32_t count = 0, total = 0;
-        while (count < 100000) {
-            b.clear();
-            long n = bam.read_batch(b, 4096);
-            if (n <= 0) break;
-            for (size_t i = 0; i < b.size() && count < 100000; ++i) {
-                if (b.l_seq[i] == 0) continue;
-                total += b.l_seq[i];
-                ++count;
-            }
-        }
-        if (count == 0) {
-            std::cerr << "[ERROR] no record with a sequence in " << path << " (the reference divides by zero here)\n";
-            return false;
-        }
-        avg_read_length = total / count;
+    const uint32_t avg_read_length = average_read_length(bam);
+    if (avg_read_length == 0) {
+        std::cerr << "[ERROR] no record with a sequence in " << path << " (the reference divides by zero here)\n";
+        end = Outcome::Failed;
+        return nullptr;
     }
     if (options.bin_width == 0) options.bin_width = avg_read_length;  // :412-413, persists across files
-    trace.mark("open + read-length sample");
-    bam.close();
-    if (!bam.open(path)) return true;
+    F->trace.mark("open + read-length sample");
+    if (!reopen(bam, path)) return nullptr;
     // only a header that promises name grouping is trusted; anything else is sorted on the device
-    const int record_order = regroup ? SLIMM_ORDER_ANY
-                             : options.order >= 0
-                                 ? options.order
-                                 : ((bam.sort_order() == SortOrder::QueryName || bam.sort_order() == SortOrder::QueryGrouped)
-                                        ? SLIMM_ORDER_GROUPED
-                                        : SLIMM_ORDER_ANY);
+    F->record_order = any_order ? SLIMM_ORDER_ANY
+                      : options.order >= 0
+                          ? options.order
+                          : ((bam.sort_order() == SortOrder::QueryName || bam.sort_order() == SortOrder::QueryGrouped)
+                                 ? SLIMM_ORDER_GROUPED
+                                 : SLIMM_ORDER_ANY);
     // (grouped streams are exact already: the reader compares the names of adjacent records)
-    const bool check_words = record_order == SLIMM_ORDER_ANY;
+    F->check_words = F->record_order == SLIMM_ORDER_ANY;
     // decoding starts now; the records are claimed further down, when the context exists (one context: the device decodes)
     // (a group takes a GROUPED file through member 0's device decoders and deals the records device to device afterwards:
     // slimm_group_get_profiles; any other order: the host reader deals them by key)
-    // --split-input: every member of the group reads its own byte range of a grouped BAM (read_split): no pump
-    const bool split_input = options.split_input && options.devices.size() > 1 && record_order == SLIMM_ORDER_GROUPED && bam.is_bam() &&
-                             bam.regular_file() && !options.host_decode && !options.verify_grouping && !options.packed_records;
-    std::unique_ptr<RecordPump> pump;
-    if (!split_input) pump.reset(new RecordPump(bam, check_words, options.devices.size() <= 1 || record_order == SLIMM_ORDER_GROUPED, options));
+    F->split_input = options.split_input && options.devices.size() > 1 && F->record_order == SLIMM_ORDER_GROUPED && bam.is_bam() &&
+                     bam.regular_file() && !options.host_decode && !options.verify_grouping && !options.packed_records;
+    if (!F->split_input)
+        F->pump.reset(new RecordPump(bam, F->check_words, options.devices.size() <= 1 || F->record_order == SLIMM_ORDER_GROUPED, options));
 
     std::cerr << "Intializing coverages for all reference genome ... ";
     const uint32_t R = static_cast<uint32_t>(bam.ref_names().size());
-    std::vector<std::string> accession(R);
-    std::vector<uint32_t> taxa_id(R, 0), lineage(static_cast<size_t>(R) * 8, 0);
+    F->accession.resize(R);
+    F->taxa_id.assign(R, 0);
+    F->lineage.assign(static_cast<size_t>(R) * 8, 0);
     for (uint32_t i = 0; i < R; ++i) {  // :430-445
-        accession[i] = get_accession_id(bam.ref_names()[i]);
-        auto it = S.db.ac_taxid.find(accession[i]);
+        F->accession[i] = get_accession_id(bam.ref_names()[i]);
+        auto it = S.db.ac_taxid.find(F->accession[i]);
         if (it != S.db.ac_taxid.end()) {
-            taxa_id[i] = it->second.empty() ? 0 : it->second[0];
-            for (size_t k = 0; k < 8 && k < it->second.size(); ++k) lineage[static_cast<size_t>(i) * 8 + k] = it->second[k];
+            F->taxa_id[i] = it->second.empty() ? 0 : it->second[0];
+            for (size_t k = 0; k < 8 && k < it->second.size(); ++k) F->lineage[static_cast<size_t>(i) * 8 + k] = it->second[k];
         } else {
-            S.db.ac_taxid[accession[i]] = std::vector<uint32_t>(8, 0);  // Q13
+            S.db.ac_taxid[F->accession[i]] = std::vector<uint32_t>(8, 0);  // Q13
         }
     }
-    std::vector<uint32_t> tax_id, tax_rank;
-    std::vector<const char*> tax_name;
-    tax_id.reserve(S.db.taxid_name.size());
+    F->tax_id.reserve(S.db.taxid_name.size());
     for (auto& kv : S.db.taxid_name) {
-        tax_id.push_back(kv.first);
-        tax_rank.push_back(kv.second.first);
-        tax_name.push_back(kv.second.second.c_str());
+        F->tax_id.push_back(kv.first);
+        F->tax_rank.push_back(kv.second.first);
+        F->tax_name.push_back(kv.second.second.c_str());
     }
-    slimm_config cfg;
+    slimm_config& cfg = F->cfg;
     memset(&cfg, 0, sizeof(cfg));
     cfg.n_refs = R;
     cfg.ref_len = bam.ref_lengths().data();
-    cfg.lineage = lineage.data();
+    cfg.lineage = F->lineage.data();
     cfg.bin_width = options.bin_width;
     cfg.avg_read_len = avg_read_length;
     cfg.min_reads = options.min_reads;
     cfg.cov_cut_off = options.cov_cut_off;
     cfg.abundance_cut_off = options.abundance_cut_off;
     cfg.rank = options.rank.c_str();
-    cfg.n_taxa = static_cast<uint32_t>(tax_id.size());
-    cfg.tax_id = tax_id.data();
-    cfg.tax_rank = tax_rank.data();
-    cfg.tax_name = tax_name.data();
+    cfg.n_taxa = static_cast<uint32_t>(F->tax_id.size());
+    cfg.tax_id = F->tax_id.data();
+    cfg.tax_rank = F->tax_rank.data();
+    cfg.tax_name = F->tax_name.data();
     cfg.device = options.device;
-    cfg.record_order = record_order;
-    // ---- several GPUs, one process (--devices), or members of a group on ONE device for a file of more records than one
-    // context takes (for_cap): 1 = done, 0 = failed, 2 = more members wanted
-    SplitBuffers split_bufs;
-    auto run_group = [&](const std::vector<int>& devs, bool split, bool for_cap) -> int {
-        // ---- several GPUs, one process: the group deals the records to its members by read and runs the phases with the
-        // two RCCL exchanges in between (slimm_amd/csrc/group.hip); the profile comes from member 0
-        slimm_group* grp = nullptr;
-        if (slimm_group_create(&cfg, devs.data(), static_cast<uint32_t>(devs.size()), &grp) != SLIMM_OK) {
-            std::cerr << "slimm: " << slimm_group_last_error(nullptr) << "\n";
-            return 0;
+    cfg.record_order = F->record_order;
+    return F;
+}
+
+// What a push that found more records than one context takes leads to (the --split-input reading decides in run_group):
+// a group reading through member 0 -- HostDecode, the host reader deals them; one context of a grouped BAM -- MoreMembers,
+// a group on the device reads the file by byte range; any other one context -- Fail.
+enum class OnCap { Fail, HostDecode, MoreMembers };
+
+// The file's records through F.pump into `t`: Done, or Failed with the reason printed.  A record longer than the device
+// decoder's carry (16 MiB) resets `t`, reopens the file and sends it through the host decoder after all; more records than
+// one context takes go by `on_cap`.
+Outcome push_file(Session& S, Reading& F, Target t, OnCap on_cap) {
+    RecordPump& pump = *F.pump;
+    bool ok = pump.drain(t);
+    long read_rc = pump.read_rc;
+    if (F.trace.on) pump.report(t.group != nullptr);
+    if (!t.group) F.trace.mark("rest of read + decode + push");   // (one context: the host decoder's pass is not in the mark)
+    const PushError why = ok || !pump.raw || read_rc < 0 ? PushError::Other : classify(slimm_last_error(t.ctx));
+    if (why == PushError::RecordCap && on_cap == OnCap::MoreMembers) return Outcome::MoreMembers;
+    if (why == PushError::HostDecode || (why == PushError::RecordCap && on_cap == OnCap::HostDecode)) {
+        std::cerr << "(" << slimm_last_error(t.ctx) << ": decoding on the host) ";
+        if (t.reset() != SLIMM_OK) {
+            std::cerr << "slimm: " << (t.group ? "" : "slimm_reset(ctx): ") << t.error() << "\n";
+            return Outcome::Failed;
         }
-        const bool want_arrays = options.raw_output || options.coverage_output;
-        // -ro / -co read the coverage arrays (src/slimm.hpp:846-943): the members then exchange the integer bins themselves
-        // (ncclAllReduce over [cov | uniq_cov], and over uniq_cov2 behind phase B) instead of their summaries
-        if (want_arrays) (void)slimm_group_set_exchange(grp, SLIMM_EXCHANGE_BINS);
-        for (uint32_t i = 0; i < devs.size(); ++i) {
-            (void)slimm_set_cutoff_cache(slimm_group_context(grp, i), S.cc_cache, S.ucc_cache);
-            (void)slimm_keep_bins(slimm_group_context(grp, i), want_arrays ? 1 : 0);
-        }
-        slimm_ctx* c0 = slimm_group_context(grp, 0);
-        trace.mark("lineage table + slimm_group_create");
-        std::cerr << "[" << watch.lap() << " secs]" << std::endl;
-        std::cerr << "Analysing alignments on " << devs.size() << " devices ("
-                  << (slimm_group_uses_rccl(grp) ? "RCCL" : "copy") << " collectives) ... ";
-        bool split_read = false;
-        if (split) {   // every member its own byte range (read_split); what fails there goes through member 0 after all
-            std::string why;
-            const int src = read_split(grp, static_cast<uint32_t>(devs.size()), path, bam.header_bytes(), RecordPump::raw_cap(), split_bufs, why);
-            trace.mark("split: read + decode + stitch");
-            if (src == SLIMM_E_REGROUP) {
-                slimm_group_destroy(grp);
-                return read_again_in_any_order() ? 1 : 0;
+        if (!reopen(F.bam, F.path)) return Outcome::Failed;
+        RecordPump again(F.bam, F.check_words, false, S.options);
+        ok = again.drain(t);
+        read_rc = again.read_rc;
+    }
+    if (t.group) F.trace.mark("rest of read + decode + push");
+    if (!ok) {   // (a pump that fed the device decoders: their context's message, after the host decoder's pass too)
+        std::cerr << (t.group ? "" : "slimm: ") << "pushing records: " << (pump.raw ? slimm_last_error(t.ctx) : t.error()) << "\n";
+        return Outcome::Failed;
+    }
+    if (read_rc < 0) {
+        std::cerr << F.bam.error() << "\n";
+        return Outcome::Failed;
+    }
+    return Outcome::Done;
+}
+
+// ---- several GPUs, one process (--devices), or members of a group on ONE device for a file of more records than one
+// context takes (for_cap): the group deals the records to its members by read and runs the phases with the two RCCL
+// exchanges in between (slimm_amd/csrc/group.hip); the profile comes from member 0
+Outcome run_group(Session& S, Reading& F, const std::vector<int>& devs, bool split, bool for_cap) {
+    Options& options = S.options;
+    slimm_group* created = nullptr;
+    if (slimm_group_create(&F.cfg, devs.data(), static_cast<uint32_t>(devs.size()), &created) != SLIMM_OK) {
+        std::cerr << "slimm: " << slimm_group_last_error(nullptr) << "\n";
+        return Outcome::Failed;
+    }
+    const GroupPtr grp(created, slimm_group_destroy);
+    const bool want_arrays = options.raw_output || options.coverage_output;
+    // -ro / -co read the coverage arrays (src/slimm.hpp:846-943): the members then exchange the integer bins themselves
+    // (ncclAllReduce over [cov | uniq_cov], and over uniq_cov2 behind phase B) instead of their summaries
+    if (want_arrays) (void)slimm_group_set_exchange(grp.get(), SLIMM_EXCHANGE_BINS);
+    for (uint32_t i = 0; i < devs.size(); ++i) {
+        (void)slimm_set_cutoff_cache(slimm_group_context(grp.get(), i), S.cc_cache, S.ucc_cache);
+        (void)slimm_keep_bins(slimm_group_context(grp.get(), i), want_arrays ? 1 : 0);
+    }
+    slimm_ctx* c0 = slimm_group_context(grp.get(), 0);
+    F.trace.mark("lineage table + slimm_group_create");
+    std::cerr << "[" << F.watch.lap() << " secs]" << std::endl;
+    std::cerr << "Analysing alignments on " << devs.size() << " devices ("
+              << (slimm_group_uses_rccl(grp.get()) ? "RCCL" : "copy") << " collectives) ... ";
+    bool split_read = false;
+    if (split) {   // every member its own byte range (read_split); what fails there goes through member 0 after all
+        std::string why;
+        const int src = read_split(grp.get(), static_cast<uint32_t>(devs.size()), F.path, F.bam.header_bytes(), RecordPump::raw_cap(),
+                                   F.split_bufs, why);
+        F.trace.mark("split: read + decode + stitch");
+        if (src == SLIMM_E_REGROUP) return Outcome::ReadAgainAnyOrder;
+        if (src != SLIMM_OK && for_cap && classify(why.c_str()) == PushError::RecordCap) return Outcome::MoreMembers;
+        if (src != SLIMM_OK) {
+            std::cerr << "(split input: " << why << "; reading the file through member 0) ";
+            if (slimm_group_reset(grp.get()) != SLIMM_OK) {
+                std::cerr << "slimm: " << slimm_group_last_error(grp.get()) << "\n";
+                return Outcome::Failed;
             }
-            if (src != SLIMM_OK && for_cap && why.find("fewer than 2^31 records") != std::string::npos) {
-                slimm_group_destroy(grp);
-                return 2;   // (more members)
-            }
-            if (src != SLIMM_OK) {
-                std::cerr << "(split input: " << why << "; reading the file through member 0) ";
-                if (slimm_group_reset(grp) != SLIMM_OK) {
-                    std::cerr << "slimm: " << slimm_group_last_error(grp) << "\n";
-                    slimm_group_destroy(grp);
-                    return 0;
-                }
-                bam.close();
-                if (!bam.open(path)) {
-                    std::cerr << bam.error() << "\n";
-                    slimm_group_destroy(grp);
-                    return 0;
-                }
-            }
-            split_read = src == SLIMM_OK;
+            if (!reopen(F.bam, F.path)) return Outcome::Failed;
         }
-        if (!pump && !split_read) pump.reset(new RecordPump(bam, check_words, true, options));
-        if (!split_read) {
-        if (pump->raw) {   // the file's size: what member 0 sizes its window buffers by
-            struct stat fst;
-            if (stat(path.c_str(), &fst) == 0 && S_ISREG(fst.st_mode)) (void)slimm_set_input_size_hint(c0, static_cast<uint64_t>(fst.st_size));
-        }
-        bool pushed = (pump->raw ? pump->attach(c0) : pump->attach_group(grp)) && pump->finish();
-        long read_rc = pump->read_rc;
-        if (trace.on && pump->raw)
-            fprintf(stderr, "[trace] device decode on member 0: slimm_push_bam_bytes %.2f ms for %llu records, pusher waited %.2f ms for windows\n",
-                    pump->raw_push_ms, static_cast<unsigned long long>(pump->raw_records), pump->wait_ms);
-        if (!pushed && pump->raw && read_rc >= 0 &&
-            (strstr(slimm_last_error(c0), "decode this file on the host") || strstr(slimm_last_error(c0), "fewer than 2^31 records"))) {
-            // a record longer than the device decoder's carry, or more records than ONE context takes: the host reader deals them
-            std::cerr << "(" << slimm_last_error(c0) << ": decoding on the host) ";
-            if (slimm_group_reset(grp) != SLIMM_OK) {
-                std::cerr << "slimm: " << slimm_group_last_error(grp) << "\n";
-                slimm_group_destroy(grp);
-                return 0;
-            }
-            bam.close();
-            if (!bam.open(path)) {
-                std::cerr << bam.error() << "\n";
-                slimm_group_destroy(grp);
-                return 0;
-            }
-            RecordPump again(bam, check_words, false, options);
-            pushed = again.attach_group(grp) && again.finish();
-            read_rc = again.read_rc;
-        }
-        trace.mark("rest of read + decode + push");
-        if (!pushed || read_rc < 0) {
-            std::cerr << (pushed ? bam.error() : std::string("pushing records: ") + (pump->raw ? slimm_last_error(c0) : slimm_group_last_error(grp))) << "\n";
-            slimm_group_destroy(grp);
-            return 0;
-        }
-        }   // (!split_read)
-        if (record_order == SLIMM_ORDER_GROUPED && bam.q18_regroup_needed()) {
-            slimm_group_destroy(grp);
-            return read_again_in_any_order() ? 1 : 0;
-        }
-        const int grc = slimm_group_get_profiles(grp, get_tsv_file_name(options.output_prefix, path, "_profile").c_str());
-        if (grc == SLIMM_E_REGROUP) {   // (member 0's decoders counted a run of shortened names only: Q18)
-            slimm_group_destroy(grp);
-            return read_again_in_any_order() ? 1 : 0;
-        }
-        if (grc < 0) {
-            std::cerr << "slimm: " << slimm_group_last_error(grp) << "\n";
-            slimm_group_destroy(grp);
-            return 0;
-        }
-        trace.mark("phases + exchanges + profile");
-        if (trace.on) trace_memory(c0);
-        std::cerr << "[" << watch.lap() << " secs]" << std::endl;
-        slimm_stats st;
-        slimm_get_stats(c0, &st);
-        S.total_hits += st.hits_count;
-        if (grc == SLIMM_E_NO_HITS) {
-            std::cerr << "[WARNING] No mapped reads found in BAM file!" << std::endl;
-            slimm_group_destroy(grp);
-            return 1;
-        }
-        if (options.min_reads == 0) options.min_reads = st.min_reads;
-        if (options.verbose) {
-            std::cerr << "  " << st.hits_count << " records processed." << std::endl;
-            std::cerr << "    " << st.matches_count << " matching reads" << std::endl;
-            std::cerr << "    " << st.uniq_matches_count << " uniquily matching reads" << std::endl;
-            std::cerr << "  references with reads = " << st.reference_count << std::endl;
-            std::cerr << "  " << st.n_valid << " passed the threshould coverage.\n";
-            std::cerr << "  uniquily matching reads increased from " << st.uniq_matches_count << " to " << st.uniq_matches_count2 << "\n";
-            std::cerr << std::setw(4) << st.profile_count << std::setw(15) << (options.rank) << " (" << st.profile_failed
-                      << " bellow cutoff i.e. " << options.abundance_cut_off << ")\n";
-        }
-        if (want_arrays && !write_raw_and_coverage(S, c0, true, path, bam, accession, taxa_id, lineage, watch)) {
-            slimm_group_destroy(grp);
-            return 0;
-        }
-        std::cerr << "[Done!] File took " << watch.elapsed() << " secs to process.\n";
-        (void)slimm_get_cutoff_cache(c0, &S.cc_cache, &S.ucc_cache);
-        slimm_group_destroy(grp);
-        return 1;
-    };
-    if (options.devices.size() > 1) return run_group(options.devices, split_input, false) == 1;
-    slimm_ctx* ctx = nullptr;
-    if (slimm_create(&cfg, &ctx) != SLIMM_OK) {
+        split_read = src == SLIMM_OK;
+    }
+    if (!split_read) {   // member 0 reads the whole file
+        if (!F.pump) F.pump.reset(new RecordPump(F.bam, F.check_words, true, options));
+        if (F.pump->raw) set_size_hint(c0, F.path);   // (what member 0 sizes its window buffers by)
+        const Outcome pushed = push_file(S, F, Target{c0, grp.get()}, OnCap::HostDecode);
+        if (pushed != Outcome::Done) return pushed;
+    }
+    if (F.record_order == SLIMM_ORDER_GROUPED && F.bam.q18_regroup_needed()) return Outcome::ReadAgainAnyOrder;
+    const int grc = slimm_group_get_profiles(grp.get(), get_tsv_file_name(options.output_prefix, F.path, "_profile").c_str());
+    if (grc == SLIMM_E_REGROUP) return Outcome::ReadAgainAnyOrder;   // (member 0's decoders counted a run of shortened names only: Q18)
+    if (grc < 0) {
+        std::cerr << "slimm: " << slimm_group_last_error(grp.get()) << "\n";
+        return Outcome::Failed;
+    }
+    F.trace.mark("phases + exchanges + profile");
+    if (F.trace.on) trace_memory(c0);
+    std::cerr << "[" << F.watch.lap() << " secs]" << std::endl;
+    slimm_stats st;
+    slimm_get_stats(c0, &st);
+    S.total_hits += st.hits_count;
+    if (grc == SLIMM_E_NO_HITS) {
+        std::cerr << "[WARNING] No mapped reads found in BAM file!" << std::endl;
+        return Outcome::Done;
+    }
+    if (options.min_reads == 0) options.min_reads = st.min_reads;
+    if (options.verbose) {
+        std::cerr << "  " << st.hits_count << " records processed." << std::endl;
+        std::cerr << "    " << st.matches_count << " matching reads" << std::endl;
+        std::cerr << "    " << st.uniq_matches_count << " uniquily matching reads" << std::endl;
+        std::cerr << "  references with reads = " << st.reference_count << std::endl;
+        std::cerr << "  " << st.n_valid << " passed the threshould coverage.\n";
+        std::cerr << "  uniquily matching reads increased from " << st.uniq_matches_count << " to " << st.uniq_matches_count2 << "\n";
+        std::cerr << std::setw(4) << st.profile_count << std::setw(15) << (options.rank) << " (" << st.profile_failed
+                  << " bellow cutoff i.e. " << options.abundance_cut_off << ")\n";
+    }
+    if (want_arrays && write_raw_and_coverage(S, F, c0, true) != Outcome::Done) return Outcome::Failed;
+    std::cerr << "[Done!] File took " << F.watch.elapsed() << " secs to process.\n";
+    (void)slimm_get_cutoff_cache(c0, &S.cc_cache, &S.ucc_cache);
+    return Outcome::Done;
+}
+
+Outcome run_context(Session& S, Reading& F) {
+    Options& options = S.options;
+    slimm_ctx* created = nullptr;
+    if (slimm_create(&F.cfg, &created) != SLIMM_OK) {
         std::cerr << "slimm: " << slimm_last_error(nullptr) << "\n";
-        return false;
+        return Outcome::Failed;
     }
+    CtxPtr owned(created, slimm_destroy);
+    slimm_ctx* ctx = owned.get();
     CHECK(ctx, slimm_set_cutoff_cache(ctx, S.cc_cache, S.ucc_cache));
-    {   // the file's size: what the library sizes its window buffers by (include/slimm_hip.h, slimm_set_input_size_hint)
-        struct stat fst;
-        if (stat(path.c_str(), &fst) == 0 && S_ISREG(fst.st_mode)) (void)slimm_set_input_size_hint(ctx, static_cast<uint64_t>(fst.st_size));
-    }
-    slimm_keep_bins(ctx, (S.options.raw_output || S.options.coverage_output) ? 1 : 0);  // (only -ro / -co read the arrays back)
-    trace.mark("lineage table + slimm_create");
-    std::cerr << "[" << watch.lap() << " secs]" << std::endl;
+    set_size_hint(ctx, F.path);
+    slimm_keep_bins(ctx, (options.raw_output || options.coverage_output) ? 1 : 0);  // (only -ro / -co read the arrays back)
+    F.trace.mark("lineage table + slimm_create");
+    std::cerr << "[" << F.watch.lap() << " secs]" << std::endl;
 
     std::cerr << "Analysing alignments, reads and references ....... ";
-    {
-        const bool pushed = pump->attach(ctx) && pump->finish();
-        if (trace.on && pump->raw)
-            fprintf(stderr, "[trace] device decode: inflate %.2f ms (on its own thread, from the moment the file was open), "
-                            "slimm_push_bam_bytes %.2f ms for %llu records, pusher waited %.2f ms for windows; of the windows read in "
-                            "place %llu were inflated on the host, %llu on the device\n",
-                    pump->decode_ms, pump->raw_push_ms, static_cast<unsigned long long>(pump->raw_records), pump->wait_ms,
-                    static_cast<unsigned long long>(pump->raw_windows_host), static_cast<unsigned long long>(pump->raw_windows_device));
-        else if (trace.on)
-            fprintf(stderr, "[trace] decode %.2f ms (on its own thread, from the moment the file was open), waiting for staging sets %.2f ms\n",
-                    pump->decode_ms, pump->wait_ms);
-        trace.mark("rest of read + decode + push");
-        long n = pump->read_rc;
-        const uint64_t pump_records = pump->raw_records;
-        bool ok = pushed;
-        if (!pushed && pump->raw && n >= 0 && record_order == SLIMM_ORDER_GROUPED && bam.is_bam() && bam.regular_file() &&
-            strstr(slimm_last_error(ctx), "fewer than 2^31 records")) {
-            // more records than one context takes: contexts of a group on this one device, each its own byte range of the
-            // file (read_split) -- twice as many until each range fits
-            std::cerr << "(" << slimm_last_error(ctx) << ": reading the file by byte range into several contexts of device "
-                      << options.device << ") ";
-            slimm_destroy(ctx);
-            pump.reset();
-            const uint64_t cap = slimm_record_cap();
-            uint32_t G = std::max<uint32_t>(2u, static_cast<uint32_t>(std::min<uint64_t>(64u, 2u * (pump_records + cap - 1) / cap)));
-            for (; G <= 128u; G *= 2u) {
-                bam.close();
-                if (!bam.open(path)) {
-                    std::cerr << bam.error() << "\n";
-                    return false;
-                }
-                const int r = run_group(std::vector<int>(G, options.device), true, true);
-                if (r != 2) return r == 1;
-            }
-            std::cerr << "slimm: more records than " << G / 2 << " contexts take\n";
-            return false;
+    const bool byte_ranges = F.record_order == SLIMM_ORDER_GROUPED && F.bam.is_bam() && F.bam.regular_file();
+    const Outcome pushed = push_file(S, F, Target{ctx}, byte_ranges ? OnCap::MoreMembers : OnCap::Fail);
+    if (pushed == Outcome::MoreMembers) {
+        // more records than one context takes: contexts of a group on this one device, each its own byte range of the
+        // file (read_split) -- twice as many until each range fits
+        std::cerr << "(" << slimm_last_error(ctx) << ": reading the file by byte range into several contexts of device " << options.device
+                  << ") ";
+        const uint64_t records = F.pump->raw_records;
+        owned.reset();
+        F.pump.reset();
+        const uint64_t cap = slimm_record_cap();
+        uint32_t G = std::max<uint32_t>(2u, static_cast<uint32_t>(std::min<uint64_t>(64u, 2u * (records + cap - 1) / cap)));
+        for (; G <= 128u; G *= 2u) {
+            if (!reopen(F.bam, F.path)) return Outcome::Failed;
+            const Outcome r = run_group(S, F, std::vector<int>(G, options.device), true, true);
+            if (r != Outcome::MoreMembers) return r;
         }
-        if (!pushed && pump->raw && n >= 0 && strstr(slimm_last_error(ctx), "decode this file on the host")) {
-            // a record longer than the device decoder's carry (16 MiB): this file goes through the host decoder after all
-            std::cerr << "(" << slimm_last_error(ctx) << ": decoding on the host) ";
-            CHECK(ctx, slimm_reset(ctx));
-            bam.close();
-            if (!bam.open(path)) {
-                std::cerr << bam.error() << "\n";
-                slimm_destroy(ctx);
-                return false;
-            }
-            RecordPump again(bam, check_words, false, options);
-            ok = again.attach(ctx) && again.finish();
-            n = again.read_rc;
-        }
-        if (!ok) {
-            std::cerr << "slimm: pushing records: " << slimm_last_error(ctx) << "\n";
-            slimm_destroy(ctx);
-            return false;
-        }
-        if (n < 0) {
-            std::cerr << bam.error() << "\n";
-            slimm_destroy(ctx);
-            return false;
-        }
+        std::cerr << "slimm: more records than " << G / 2 << " contexts take\n";
+        return Outcome::Failed;
     }
-    if (record_order == SLIMM_ORDER_GROUPED && options.verify_grouping) {
+    if (pushed != Outcome::Done) return pushed;
+    if (F.record_order == SLIMM_ORDER_GROUPED && options.verify_grouping) {
         // the header (or --query-grouped) promises that the records of a read name are adjacent; nothing checks the promise
         // unless asked: a name that comes back later would be counted as two reads (include/slimm_hip.h, slimm_check_grouping)
         uint64_t split = 0;
         CHECK(ctx, slimm_check_grouping(ctx, &split));
         if (split)
-            std::cerr << "\n[WARNING] " << split << " read name run(s) repeat a name seen earlier in " << get_file_name(path)
+            std::cerr << "\n[WARNING] " << split << " read name run(s) repeat a name seen earlier in " << get_file_name(F.path)
                       << ": the file is NOT grouped by read name although it is declared so; run with --any-order\n";
     }
-    {
-        // (the device decoders count inside the library: SLIMM_E_REGROUP; the host decoder counts in the reader)
-        const int arc = record_order == SLIMM_ORDER_GROUPED && bam.q18_regroup_needed() ? SLIMM_E_REGROUP : slimm_analyze_alignments(ctx);
-        if (arc == SLIMM_E_REGROUP) {
-            slimm_destroy(ctx);
-            return read_again_in_any_order();
-        }
-        if (arc < 0) {
-            std::cerr << "slimm: slimm_analyze_alignments(ctx): " << slimm_last_error(ctx) << "\n";
-            slimm_destroy(ctx);
-            return false;
-        }
+    // (the device decoders count inside the library: SLIMM_E_REGROUP; the host decoder counts in the reader)
+    if (F.record_order == SLIMM_ORDER_GROUPED && F.bam.q18_regroup_needed()) return Outcome::ReadAgainAnyOrder;
+    const int arc = slimm_analyze_alignments(ctx);
+    if (arc == SLIMM_E_REGROUP) return Outcome::ReadAgainAnyOrder;
+    if (arc < 0) {
+        std::cerr << "slimm: slimm_analyze_alignments(ctx): " << slimm_last_error(ctx) << "\n";
+        return Outcome::Failed;
     }
-    int rc = slimm_finish_coverage(ctx);
+    const int rc = slimm_finish_coverage(ctx);
     if (rc < 0) {
         std::cerr << "slimm: " << slimm_last_error(ctx) << "\n";
-        slimm_destroy(ctx);
-        return false;
+        return Outcome::Failed;
     }
-    trace.mark("analyze_alignments + finish_coverage");
-    std::cerr << "[" << watch.lap() << " secs]" << std::endl;
+    F.trace.mark("analyze_alignments + finish_coverage");
+    std::cerr << "[" << F.watch.lap() << " secs]" << std::endl;
     slimm_stats st;
     slimm_get_stats(ctx, &st);
     S.total_hits += st.hits_count;
     if (rc == SLIMM_E_NO_HITS) {
         std::cerr << "[WARNING] No mapped reads found in BAM file!" << std::endl;
-        slimm_destroy(ctx);
-        return true;
+        return Outcome::Done;
     }
     if (options.min_reads == 0) options.min_reads = st.min_reads;  // :458-459, persists across files
     if (options.verbose) {                                         // print_matches_stat :621-630
@@ -1437,7 +1415,7 @@ bool get_profiles(Session& S, size_t file_index, bool regroup = false) {
 
     std::cerr << "Filtering unlikely sequences ..................... ";
     CHECK(ctx, slimm_filter_alignments(ctx));
-    std::cerr << "[" << watch.lap() << " secs]" << std::endl;
+    std::cerr << "[" << F.watch.lap() << " secs]" << std::endl;
     slimm_get_stats(ctx, &st);
     if (options.verbose) {  // print_filter_stat :613-619
         std::cerr << "  " << st.n_valid << " passed the threshould coverage.\n";
@@ -1446,32 +1424,52 @@ bool get_profiles(Session& S, size_t file_index, bool regroup = false) {
         std::cerr << "  uniquily matching reads increased from " << st.uniq_matches_count << " to " << st.uniq_matches_count2 << "\n\n";
     }
 
-    if (options.raw_output || options.coverage_output) {
-        if (!write_raw_and_coverage(S, ctx, false, path, bam, accession, taxa_id, lineage, watch)) {
-            slimm_destroy(ctx);
-            return false;
-        }
-    }
+    if ((options.raw_output || options.coverage_output) && write_raw_and_coverage(S, F, ctx, false) != Outcome::Done) return Outcome::Failed;
     std::cerr << "Assigning reads to Least Common Ancestor (LCA) ... ";
     CHECK(ctx, slimm_get_reads_lca_count(ctx));
-    std::cerr << "[" << watch.lap() << " secs]" << std::endl;
+    std::cerr << "[" << F.watch.lap() << " secs]" << std::endl;
 
     std::cerr << "Writing taxnomic profile(s) ...................... ";
-    CHECK(ctx, slimm_write_abundance_file(ctx, get_tsv_file_name(options.output_prefix, path, "_profile").c_str()));
+    CHECK(ctx, slimm_write_abundance_file(ctx, get_tsv_file_name(options.output_prefix, F.path, "_profile").c_str()));
     if (options.verbose) {
         slimm_get_stats(ctx, &st);
         std::cerr << "\n" << std::setw(4) << st.profile_count << std::setw(15) << (options.rank) << " (" << st.profile_failed
                   << " bellow cutoff i.e. " << options.abundance_cut_off << ")";
         std::cerr << "\n.................................................. ";
     }
-    std::cerr << "[" << watch.lap() << " secs]" << std::endl;
-    trace.mark("filter + LCA + outputs");
-    if (trace.on) trace_memory(ctx);
-    std::cerr << "[Done!] File took " << watch.elapsed() << " secs to process.\n";
+    std::cerr << "[" << F.watch.lap() << " secs]" << std::endl;
+    F.trace.mark("filter + LCA + outputs");
+    if (F.trace.on) trace_memory(ctx);
+    std::cerr << "[Done!] File took " << F.watch.elapsed() << " secs to process.\n";
     CHECK(ctx, slimm_get_cutoff_cache(ctx, &S.cc_cache, &S.ucc_cache));
-    slimm_destroy(ctx);
-    trace.mark("slimm_destroy");
-    return true;
+    owned.reset();
+    F.trace.mark("slimm_destroy");
+    return Outcome::Done;
+}
+
+// slimm::get_profiles() for one file (src/slimm.hpp:395-496)
+bool get_profiles(Session& S, size_t file_index) {
+    const std::string& path = S.input_paths[file_index];
+    std::cerr << "\nReading " << file_index + 1 << " of " << S.input_paths.size() << " files ... (" << get_file_name(path) << ")\n"
+              << "=================================================================\n";
+    auto read = [&](bool any_order) {   // one reading of the file, through a group (--devices) or one context
+        Outcome end;
+        std::unique_ptr<Reading> F = set_up(S, path, any_order, end);
+        if (!F) return end;
+        return S.options.devices.size() > 1 ? run_group(S, *F, S.options.devices, F->split_input, false) : run_context(S, *F);
+    };
+    Outcome r = read(false);
+    if (r == Outcome::ReadAgainAnyOrder) {
+        // Q18 on a file grouped by QNAME (include/slimm_hip.h, "Q18 ON A GROUPED STREAM"): a read named `r.1` without a mate
+        // flag is the reference's read of the first-in-pair records of `r`, wherever those lie in the file
+        // (src/slimm.hpp:204-211).  The readers count the runs of such shortened names that stand apart from their
+        // namesakes; a file that has one is read again, in any order (a fresh context of the same process: the HIP runtime
+        // and the page cache are warm).  The any-order path never asks for it.
+        std::cerr << "\n(read names ending in .1 / .2 without a mate flag, apart from the flagged records of the shortened name: "
+                     "reading " << get_file_name(path) << " again as a file in no particular order)\n";
+        r = read(true);
+    }
+    return r == Outcome::Done;
 }
 
 }  // namespace

@@ -25,7 +25,7 @@ int main(int argc, char** argv) {
             // read_raw (the windows `slimm` hands to slimm_push_bam_bytes): small and large windows, the compressed bytes
             // from a mapping of the file and through buffered reads, a few records taken by read_batch first
             for (int mode = 0; mode < 6; ++mode) {
-                if (mode & 1) setenv("SLIMM_NO_MMAP", "1", 1); else unsetenv("SLIMM_NO_MMAP");
+                AlignmentFile::settings().no_mmap = (mode & 1) != 0;
                 const size_t cap = mode < 2 ? (1u << 20) : mode < 4 ? (3u << 20) + 12345u : (64u << 20);
                 AlignmentFile g;
                 if (!g.open(p)) continue;
@@ -40,7 +40,7 @@ int main(int argc, char** argv) {
                 printf("%s: read_raw mode %d cap %zu: %llu bytes in %d windows (sum %llu) rc=%ld %s\n", p.c_str(), mode, cap, bytes,
                        windows, sum, k, g.error().c_str());
             }
-            unsetenv("SLIMM_NO_MMAP");
+            AlignmentFile::settings().no_mmap = false;
             // read_blocks (the windows `slimm` hands to slimm_push_bgzf_blocks: whole BGZF blocks by pread), alternating with
             // read_raw, small and large buffers, an inflated-size limit that ends windows early
             for (int mode = 0; mode < 3; ++mode) {
