@@ -259,6 +259,14 @@ int slimm_device_memory(slimm_ctx* ctx, uint64_t* used_bytes, uint64_t* total_by
  * the host". */
 int slimm_set_reference_names(slimm_ctx* ctx, const char* const* names);
 int slimm_push_sam_bytes(slimm_ctx* ctx, const uint8_t* text, uint64_t n_bytes, int last, uint64_t* n_records);
+/* BGZF-COMPRESSED SAM TEXT (`bgzip x.sam`) with the inflate on the device as well: `blocks` = n_bytes of whole BGZF blocks
+ * of the file, in file order across calls, of whose inflated bytes the first `skip` are the header (in front of the first
+ * alignment line; 0 in every later call).  The blocks are gathered, inflated and checked as by slimm_push_bgzf_blocks, and
+ * the inflated text is found and decoded as by slimm_push_sam_bytes (slimm_set_reference_names first); a line straddles
+ * windows as there.  Windows of this form and of slimm_push_sam_bytes (text the caller inflated) may alternate within a file;
+ * SAM and BAM do not mix.  A file's last line without its newline is a line also when the device inflated it (the caller
+ * never sees those bytes).  Errors: those of the two, SLIMM_E_INVALID "corrupt BGZF block" among them. */
+int slimm_push_bgzf_sam_blocks(slimm_ctx* ctx, const uint8_t* blocks, uint64_t n_bytes, uint32_t skip, int last, uint64_t* n_records);
 /* Page-locks a buffer of the caller (hipHostRegister) until the context is destroyed: copies out of it then run at the
  * speed of the bus instead of the runtime's own staging. */
 int slimm_pin_host_buffer(slimm_ctx* ctx, const void* buffer, uint64_t n_bytes);

@@ -201,6 +201,10 @@ struct slimm_ctx {
         DevBuf<uint8_t> sam_names;
         uint32_t sam_mask = 0;
         uint8_t sam_last_byte = '\n';
+        // ... unless the text's last bytes so far were inflated on the device (slimm_push_bgzf_sam_blocks): the device then ends
+        // a last line without its newline; lines it ended so far (SLIMM_TRACE=push)
+        bool sam_dev_tail = false;
+        uint64_t sam_lines_ended = 0;
         std::vector<BgzfBlock> desc_host[kBamRing];   // (a buffer's descriptors stay until the buffer's turn comes again: the copy reads them)
         // Q18 on a grouped stream (kernels.h: BamCarry): the decoders' two counts of the windows finished so far
         uint64_t q18_starts = 0, q18_plain = 0;

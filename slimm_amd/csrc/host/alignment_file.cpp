@@ -170,6 +170,8 @@ void AlignmentFile::close() {
     map_size_ = map_pos_ = 0;
     if (fp_) fclose(fp_);
     fp_ = nullptr;
+    if (gz_) inflateEnd(gz_.get());
+    gz_.reset();
     workers_.reset();
     inflaters_.reset();
 }
@@ -218,16 +220,67 @@ bool AlignmentFile::open(const std::string& path) {
     spare_.clear();
     order_ = SortOrder::Unknown;
     header_bytes_ = 0;
+    err_.clear();
+    bam_ = false;
+    comp_ = Compression::None;
+    gz_in_.clear();
+    gz_in_eof_ = gz_member_open_ = gz_end_ = text_bad_ = false;
+    lead_.clear();
+    lead_off_ = 0;
     fp_ = fopen(path.c_str(), "rb");
     if (!fp_) {
         err_ = "Could not open " + path + "!";
         return false;
     }
-    unsigned char magic[2] = {0, 0};
-    size_t got = fread(magic, 1, 2, fp_);
+    // The compression from the first bytes (a gzip member whose header carries the BC extra subfield is BGZF), the format
+    // from the payload: "BAM\1" is BAM, anything else SAM text -- like the reference's BamFileIn, which takes SAM, BAM and
+    // compressed SAM alike
+    std::vector<uint8_t> head(12);
+    head.resize(fread(head.data(), 1, head.size(), fp_));
+    const bool gzip = head.size() >= 2 && head[0] == 0x1f && head[1] == 0x8b;
+    bool bgzf = false;
+    if (gzip && head.size() == 12 && head[2] == 8 && (head[3] & 4)) {
+        const size_t xlen = rd_u16(&head[10]);
+        head.resize(12 + xlen);
+        if (fread(head.data() + 12, 1, xlen, fp_) == xlen)
+            for (size_t o = 0; o + 4 <= xlen;) {
+                const uint8_t* x = &head[12 + o];
+                const uint16_t slen = rd_u16(x + 2);
+                if (x[0] == 'B' && x[1] == 'C' && slen == 2 && o + 6 <= xlen) bgzf = true;
+                o += 4 + slen;
+            }
+    }
     rewind(fp_);
-    bam_ = (got == 2 && magic[0] == 0x1f && magic[1] == 0x8b);
-    bool ok = bam_ ? read_bam_header() : read_sam_header();
+    auto starts = [&](const char* m, size_t n) { return head.size() >= n && memcmp(head.data(), m, n) == 0; };
+    bool ok;
+    if (starts("BZh", 3) || starts("\xfd" "7zXZ\0", 6) || starts("\x28\xb5\x2f\xfd", 4)) {
+        err_ = std::string(starts("BZh", 3) ? "bzip2" : starts("\x28", 1) ? "zstd" : "xz") + "-compressed input is not supported (SAM / BAM, "
+               "BGZF or gzip): " + path;
+        ok = false;
+    } else if (bgzf) {
+        comp_ = Compression::Bgzf;
+        ok = fill(4) || err_.empty();   // (false without an error: fewer than 4 bytes in all)
+        bam_ = ok && buf_.size() - pos_ >= 4 && memcmp(&buf_[pos_], "BAM\1", 4) == 0;
+        if (ok && !bam_) sam_buf_off_ = 0 - pos_;   // (mod 2^64: the window's slack lies in front of the text's first byte)
+        if (ok) ok = bam_ ? read_bam_header() : read_sam_header();
+    } else if (gzip) {
+        comp_ = Compression::Gzip;
+        gz_.reset(new z_stream);
+        memset(gz_.get(), 0, sizeof(z_stream));
+        if (inflateInit2(gz_.get(), 15 + 16) != Z_OK) {   // (gzip wrapping only)
+            gz_.reset();
+            err_ = "zlib: inflateInit2 failed";
+            return false;
+        }
+        ok = refill_text() || !text_bad_;
+        if (ok && buf_.size() >= 4 && memcmp(buf_.data(), "BAM\1", 4) == 0) {
+            err_ = "a plain gzip stream that holds BAM (not BGZF): BAM is read from BGZF blocks only: " + path;
+            ok = false;
+        }
+        if (ok) ok = read_sam_header();
+    } else {
+        ok = read_sam_header();
+    }
     if (!ok && err_.empty()) err_ = "bad header in " + path;
     return ok;
 }
@@ -488,20 +541,99 @@ bool AlignmentFile::read_bam_header() {
 }
 
 // ---- SAM text --------------------------------------------------------------------------------------------------
+// The next stretch of the text into buf_[pos_ ...): read as it lies in the file, inflated by the BGZF machinery of BAM
+// (fill: the prefetch thread and the inflate workers), or inflated from the one gzip stream.  sam_buf_off_ stays the
+// text offset of buf_[0].  false at the end of the text, or on a format error (text_bad_, err_).
+bool AlignmentFile::refill_text() {
+    if (text_bad_) return false;
+    const size_t consumed = sam_buf_off_ + buf_.size();
+    if (comp_ == Compression::Bgzf) {
+        pos_ = buf_.size();
+        if (!fill(1)) {
+            text_bad_ = !err_.empty();
+            return false;
+        }
+        sam_buf_off_ = consumed - pos_;
+        return true;
+    }
+    buf_.resize(1 << 20);
+    const long got = comp_ == Compression::Gzip ? gz_read(buf_.data(), buf_.size())
+                                                : static_cast<long>(fread(buf_.data(), 1, buf_.size(), fp_));
+    buf_.resize(got > 0 ? static_cast<size_t>(got) : 0u);
+    pos_ = 0;
+    sam_buf_off_ = consumed;
+    if (got <= 0) eof_ = true;
+    return got > 0;
+}
+
+// Plain gzip (one deflate stream per member, members back to back): inflated in order by zlib on the calling thread --
+// a deflate stream has no place to cut it for other threads -- up to `cap` bytes.  0 at the end, -1 + err_.
+long AlignmentFile::gz_read(uint8_t* dst, size_t cap) {
+    if (text_bad_) return -1;
+    z_stream& zs = *gz_;
+    size_t out = 0;
+    while (out < cap && !gz_end_) {
+        if (zs.avail_in == 0 && !gz_in_eof_) {
+            StageClock clk(ms_read_);
+            gz_in_.resize(4u << 20);
+            const size_t got = fread(gz_in_.data(), 1, gz_in_.size(), fp_);
+            if (got < gz_in_.size()) gz_in_eof_ = true;
+            zs.next_in = gz_in_.data();
+            zs.avail_in = static_cast<uInt>(got);
+        }
+        if (zs.avail_in == 0) {   // the file is used up: between two members, or inside one
+            if (gz_member_open_) {
+                err_ = "truncated gzip stream";
+                text_bad_ = true;
+                return -1;
+            }
+            gz_end_ = true;
+            break;
+        }
+        gz_member_open_ = true;
+        zs.next_out = dst + out;
+        zs.avail_out = static_cast<uInt>(std::min<size_t>(cap - out, 1u << 30));
+        const int rc = inflate(&zs, Z_NO_FLUSH);
+        out = static_cast<size_t>(zs.next_out - dst);
+        if (rc == Z_STREAM_END) {   // (the member's CRC and ISIZE are checked; another member may follow)
+            gz_member_open_ = false;
+            if (inflateReset(&zs) == Z_OK) continue;
+        } else if (rc == Z_OK || (rc == Z_BUF_ERROR && zs.avail_in == 0)) {
+            continue;
+        }
+        err_ = std::string("corrupt gzip stream (") + (zs.msg ? zs.msg : "inflate failed") + ")";
+        text_bad_ = true;
+        return -1;
+    }
+    return static_cast<long>(out);
+}
+
+// Compressed SAM: what the header parse has inflated already -- the first alignment line as it stood, then the rest of
+// buf_ -- into dst; the bytes written (0: nothing of it is left)
+size_t AlignmentFile::take_lead(uint8_t* dst, size_t cap) {
+    size_t out = 0;
+    if (lead_off_ < lead_.size()) {
+        out = std::min(cap, lead_.size() - lead_off_);
+        memcpy(dst, lead_.data() + lead_off_, out);
+        lead_off_ += out;
+    }
+    if (out < cap && lead_off_ >= lead_.size() && pos_ < buf_.size()) {
+        const size_t n = std::min(cap - out, buf_.size() - pos_);
+        memcpy(dst + out, buf_.data() + pos_, n);
+        pos_ += n;
+        out += n;
+    }
+    return out;
+}
+
 bool AlignmentFile::next_sam_line(std::string& line) {
     line.clear();
+    line_cr_ = line_nl_ = false;
     bool started = false;
     while (true) {
         if (pos_ >= buf_.size()) {
-            sam_buf_off_ += buf_.size();
-            buf_.resize(1 << 20);
-            size_t got = fread(buf_.data(), 1, buf_.size(), fp_);
-            buf_.resize(got);
-            pos_ = 0;
-            if (got == 0) {
-                eof_ = true;
-                return !line.empty();
-            }
+            // (a format error of the compressed text drops the line it cuts: the error is the reader's answer)
+            if (!refill_text()) return !text_bad_ && !line.empty();
         }
         const uint8_t* b = buf_.data() + pos_;
         if (!started) {
@@ -512,7 +644,11 @@ bool AlignmentFile::next_sam_line(std::string& line) {
         if (e) {
             line.append(reinterpret_cast<const char*>(b), e - b);
             pos_ += static_cast<size_t>(e - b) + 1;
-            if (!line.empty() && line.back() == '\r') line.pop_back();
+            line_nl_ = true;
+            if (!line.empty() && line.back() == '\r') {
+                line.pop_back();
+                line_cr_ = true;
+            }
             return true;
         }
         line.append(reinterpret_cast<const char*>(b), buf_.size() - pos_);
@@ -524,12 +660,15 @@ bool AlignmentFile::read_sam_header() {
     std::string line;
     for (;;) {
         if (!next_sam_line(line)) {
+            if (text_bad_) return false;
             sam_body_off_ = sam_buf_off_ + pos_;   // (no alignment line at all)
             break;
         }
         if (line.empty()) continue;
         if (line[0] != '@') {
             sam_body_off_ = sam_line_off_;   // where the alignment lines start in the file (read_text)
+            // (compressed: the line as it stood goes in front of what read_text / read_raw hand out)
+            if (comp_ != Compression::None) lead_ = line + (line_cr_ ? "\r" : "") + (line_nl_ ? "\n" : "");
             pending_line_ = line;
             have_pending_ = true;
             break;
@@ -550,6 +689,7 @@ bool AlignmentFile::read_sam_header() {
             ref_len_.push_back(len);
         }
     }
+    if (comp_ == Compression::Bgzf) header_bytes_ = sam_body_off_;
     return true;
 }
 
@@ -811,8 +951,8 @@ void AlignmentFile::separate_adjacent_names(uint64_t* key, const std::vector<siz
 // BGZF blocks are inflated straight into the caller's buffer, as many as fit.
 long AlignmentFile::read_blocks(uint8_t* dst, size_t cap, size_t max_inflated, size_t* inflated) {
     if (inflated) *inflated = 0;
-    if (!bam_ || !dst || !inflated || raw_stage_ != 2 || !map_) {
-        err_ = "read_blocks: only behind read_raw, on a mapped BAM file";
+    if (comp_ != Compression::Bgzf || !dst || !inflated || raw_stage_ != 2 || !map_) {
+        err_ = "read_blocks: only behind read_raw, on a mapped BGZF file";
         return -1;
     }
     if (eof_) return 0;
@@ -905,9 +1045,21 @@ long AlignmentFile::read_blocks(uint8_t* dst, size_t cap, size_t max_inflated, s
 }
 
 long AlignmentFile::read_text(uint8_t* dst, size_t cap) {
-    if (bam_ || !fp_ || !dst || cap < (1u << 16)) {
-        err_ = "read_text: a SAM file and a buffer of at least 64 KiB";
+    if (bam_ || comp_ == Compression::Bgzf || !fp_ || !dst || cap < (1u << 16)) {
+        err_ = "read_text: a SAM file (plain or gzip) and a buffer of at least 64 KiB";
         return -1;
+    }
+    if (comp_ == Compression::Gzip) {   // (on the caller's thread: the command's reader thread, beside the device's work)
+        StageClock clk(ms_inflate_);
+        sam_text_started_ = true;
+        size_t out = take_lead(dst, cap);
+        if (out < cap) {
+            const long n = gz_read(dst + out, cap - out);
+            if (n < 0) return -1;
+            out += static_cast<size_t>(n);
+        }
+        if (out) ++n_windows_;
+        return static_cast<long>(out);
     }
     if (!sam_text_started_) {
         struct stat sb;
@@ -948,17 +1100,13 @@ long AlignmentFile::read_text(uint8_t* dst, size_t cap) {
 }
 
 long AlignmentFile::read_raw(uint8_t* dst, size_t cap) {
-    if (!bam_ || !dst || cap < (1u << 20)) {
-        err_ = "read_raw: a BAM file and a buffer of at least 1 MiB";
+    if (comp_ != Compression::Bgzf || !dst || cap < (1u << 20)) {
+        err_ = "read_raw: a BGZF file (BAM or SAM) and a buffer of at least 1 MiB";
         return -1;
     }
     if (raw_stage_ == 0) {  // what is unread of the decoded window (in pieces, when it is larger than the buffer)
-        const size_t n = std::min(buf_.size() - pos_, cap);
-        if (n) {
-            memcpy(dst, buf_.data() + pos_, n);
-            pos_ += n;
-            return static_cast<long>(n);
-        }
+        const size_t n = take_lead(dst, cap);   // (SAM: the first alignment line in front of it)
+        if (n) return static_cast<long>(n);
         raw_stage_ = 1;
         raw_off_ = kSlack;
         if (prefetch_.joinable()) {
@@ -1259,6 +1407,7 @@ long AlignmentFile::read_batch(RecordBatch& out, size_t max_records, bool keep_n
             line.swap(pending_line_);
             have_pending_ = false;
         } else if (!next_sam_line(line)) {
+            if (text_bad_) return -1;
             break;
         }
         if (line.empty() || line[0] == '@') continue;

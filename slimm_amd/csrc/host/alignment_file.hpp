@@ -4,7 +4,8 @@
 // src/slimm.hpp:194-208, 420-424): header reference names + lengths in header order (= refID), and per record
 // qName, flag, refID, 0-based position and sequence length.  CIGAR, MAPQ, qualities and tags are never looked at by
 // SLIMM and are skipped.  BAM = BGZF (concatenated gzip members, inflated with libdeflate when the box has it, else zlib) carrying the binary records of the
-// SAM specification; SAM = the tab-separated text form.  Written against the SAM/BAM specification -- SeqAn's source
+// SAM specification; SAM = the tab-separated text form, as it is, in BGZF blocks (bgzip) or in a plain gzip stream of one
+// or more members (gzip, inflated by zlib: a deflate stream cannot be cut for threads).  Written against the SAM/BAM specification -- SeqAn's source
 // is not part of the reference checkout -- and cross-checked in tests against files produced by an independent
 // Python writer (tests/bam_io.py).
 #pragma once
@@ -17,6 +18,8 @@
 #include <vector>
 
 #include "../read_identity.h"
+
+struct z_stream_s;   // (zlib.h)
 
 namespace slimm {
 
@@ -41,6 +44,9 @@ struct RecordBatch {
 };
 
 enum class SortOrder { Unknown, Unsorted, QueryName, Coordinate, QueryGrouped };
+// How the file's bytes are stored: as they are, in BGZF blocks (BAM, or SAM text from bgzip), or as one plain gzip stream of
+// one or more members (SAM text from gzip)
+enum class Compression { None, Bgzf, Gzip };
 
 // 62-bit identity of a read name.  The reader makes it exact where grouped input needs it to be: a record whose name
 // differs from its predecessor's never gets the predecessor's key (separate_adjacent_names).  Names colliding far
@@ -69,14 +75,15 @@ public:
     bool open(const std::string& path);
     void close();
     const std::string& error() const { return err_; }
-    bool is_bam() const { return bam_; }
+    bool is_bam() const { return bam_; }   // the payload: BAM records (else SAM text)
+    Compression compression() const { return comp_; }
     // "libdeflate" when libdeflate.so.0 could be dlopen()ed, else "zlib"
     static const char* inflate_backend();
 
     const std::vector<std::string>& ref_names() const { return ref_names_; }
     const std::vector<uint32_t>& ref_lengths() const { return ref_len_; }
     SortOrder sort_order() const { return order_; }
-    // BAM: the header's inflated bytes -- where the first alignment record starts in the inflated stream
+    // BAM / BGZF SAM: the header's inflated bytes -- where the first alignment record (line) starts in the inflated stream
     uint64_t header_bytes() const { return header_bytes_; }
     // Q18 on a file grouped by QNAME (include/slimm_hip.h, "Q18 ON A GROUPED STREAM"): among the records read_batch /
     // read_into have handed out, some run of adjacent records with one canonical base holds SHORTENED names only -- their
@@ -90,7 +97,7 @@ public:
     long read_into(uint64_t* read_key, int32_t* ref_id, int32_t* begin_pos, uint16_t* flag, size_t max_records,
                    uint32_t* check = nullptr);
 
-    // BAM only: the inflated bytes of the alignment records -- everything behind the header, or behind the last record a
+    // BGZF only (BAM, or SAM text from bgzip): the inflated bytes of the alignment records -- everything behind the header, or behind the last record a
     // read_* call handed out -- window by window straight into the caller's buffer (for slimm_push_bam_bytes: the records
     // are then found and decoded on the device).  Returns the bytes written (whole BGZF blocks, at most `cap`), 0 at the
     // end of the file, -1 + error() on a format error.  Not to be mixed with read_batch / read_into afterwards.
@@ -103,13 +110,17 @@ public:
     bool can_read_blocks() const { return raw_stage_ == 2 && map_ != nullptr && !eof_; }
     // SAM only: the file's text behind the header -- the alignment lines -- window by window straight into the caller's
     // buffer, cut anywhere (for slimm_push_sam_bytes: the lines are found and decoded on the device); read by pread on
-    // several threads.  Returns the bytes written, 0 at the end of the file, -1 + error().  Not to be mixed with
-    // read_batch / read_into afterwards.
+    // several threads, or -- a plain gzip file -- inflated by one zlib stream on the calling thread.  Returns the bytes
+    // written, 0 at the end of the file, -1 + error().  Not to be mixed with read_batch / read_into afterwards.  (BGZF
+    // SAM goes through read_raw / read_blocks.)
     long read_text(uint8_t* dst, size_t cap);
-    bool can_read_text() const { return !bam_ && fp_ != nullptr; }
+    bool can_read_text() const { return !bam_ && comp_ != Compression::Bgzf && fp_ != nullptr; }
     bool regular_file() const;   // (read_text and the mapped reads want one; a pipe or a device goes through the buffered reads)
     // after a read_raw that returned bytes: nothing will follow them (false may also mean "not known yet")
-    bool raw_exhausted() const { return raw_stage_ == 2 ? eof_ : (raw_stage_ == 1 && eof_ && raw_off_ >= spare_.size()); }
+    bool raw_exhausted() const {
+        if (comp_ == Compression::Gzip) return gz_end_ && lead_off_ >= lead_.size() && pos_ >= buf_.size();
+        return raw_stage_ == 2 ? eof_ : (raw_stage_ == 1 && eof_ && raw_off_ >= spare_.size());
+    }
 
 private:
     size_t raw_off_ = 0;
@@ -135,10 +146,24 @@ private:
     bool read_bam_header();
     bool read_sam_header();
     bool next_sam_line(std::string& line);
+    bool refill_text();       // the next stretch of SAM text into buf_ (false: its end, or an error in err_)
+    long gz_read(uint8_t* dst, size_t cap);   // plain gzip: the next inflated bytes of the stream (0 at its end, -1 + err_)
+    size_t take_lead(uint8_t* dst, size_t cap);   // compressed SAM: the first alignment line and the rest of buf_, once
     void parse_hd_line(const std::string& line);
 
     FILE* fp_ = nullptr;
     bool bam_ = false, eof_ = false;
+    Compression comp_ = Compression::None;
+    // plain gzip: the zlib stream, its compressed input, the input's end, a member begun and not finished, the stream's end
+    std::unique_ptr<::z_stream_s> gz_;
+    std::vector<uint8_t> gz_in_;
+    bool gz_in_eof_ = false, gz_member_open_ = false, gz_end_ = false;
+    bool text_bad_ = false;   // compressed SAM: the text ran into a format error (err_); the reader's answer from then on
+    // compressed SAM: the first alignment line as it stands in the text (the header parse took it out of buf_), handed out
+    // in front of the rest by read_text / read_raw; line_cr_ / line_nl_: the last line next_sam_line read ended with CR LF / LF
+    std::string lead_;
+    size_t lead_off_ = 0;
+    bool line_cr_ = false, line_nl_ = false;
     std::string err_;
     std::vector<std::string> ref_names_;
     std::vector<uint32_t> ref_len_;

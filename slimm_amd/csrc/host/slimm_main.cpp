@@ -119,6 +119,7 @@ SLIMM_FORWARD(int, slimm_push_records_packed, (slimm_ctx* a, const uint64_t* b, 
               (a, b, c, d, e))
 SLIMM_FORWARD(int, slimm_push_bam_bytes, (slimm_ctx* a, const uint8_t* b, uint64_t c, int d, uint64_t* e), (a, b, c, d, e))
 SLIMM_FORWARD(int, slimm_push_bgzf_blocks, (slimm_ctx* a, const uint8_t* b, uint64_t c, uint32_t s, int d, uint64_t* e), (a, b, c, s, d, e))
+SLIMM_FORWARD(int, slimm_push_bgzf_sam_blocks, (slimm_ctx* a, const uint8_t* b, uint64_t c, uint32_t s, int d, uint64_t* e), (a, b, c, s, d, e))
 SLIMM_FORWARD(int, slimm_pin_host_buffer, (slimm_ctx* a, const void* b, uint64_t c), (a, b, c))
 SLIMM_FORWARD(int, slimm_host_bgzf_ranges, (const char* a, uint64_t b, uint32_t c, uint64_t* d), (a, b, c, d))
 SLIMM_FORWARD(int, slimm_set_input_mid_file, (slimm_ctx* a, int b, int c), (a, b, c))
@@ -368,8 +369,8 @@ int parse(int argc, char** argv, Options& o) {
     return 0;
 }
 
-// --dump-raw: what the device decoder is fed -- the inflated bytes behind the BAM header, in windows of
-// --window-mb (default 1) MiB -- to stdout, the window sizes to stderr
+// --dump-raw: what the device decoder is fed -- the inflated bytes behind the BAM header (the text behind the header of a
+// compressed SAM file), in windows of --window-mb (default 1) MiB -- to stdout, the window sizes to stderr
 int dump_raw(const Options& o) {
     AlignmentFile f;
     if (!f.open(o.input_path)) {
@@ -379,7 +380,8 @@ int dump_raw(const Options& o) {
     const size_t cap = static_cast<size_t>(std::max(1u, o.window_mb)) << 20;
     std::vector<uint8_t> buf(cap);
     long n;
-    while ((n = f.read_raw(buf.data(), cap)) > 0) {
+    const bool gzip = f.compression() == Compression::Gzip;
+    while ((n = gzip ? f.read_text(buf.data(), cap) : f.read_raw(buf.data(), cap)) > 0) {
         std::cerr << "window\t" << n << "\t" << (f.raw_exhausted() ? "last" : "more") << "\n";
         if (fwrite(buf.data(), 1, static_cast<size_t>(n), stdout) != static_cast<size_t>(n)) return 1;
     }
@@ -624,8 +626,10 @@ struct RecordPump {
             if (raw_pusher.joinable()) raw_pusher.join();
         }
     }
-    // the inflater of the device-decode mode: fills the window buffers in turn
+    // the inflater of the device-decode mode: fills the window buffers in turn.  BGZF files -- BAM, or SAM text -- alike:
+    // windows the host inflates (read_raw) and, every device_period-th of those read in place, whole blocks (read_blocks)
     void run_raw() {
+        const bool bgzf = bam.compression() == Compression::Bgzf;
         for (unsigned w = 0;; w = (w + 1) % kRawBuffers) {
             {
                 std::unique_lock<std::mutex> g(mu);
@@ -644,7 +648,7 @@ struct RecordPump {
             // (every device_period-th of the windows read in place)
             bool compressed = false;
             long n;
-            if (!bam.is_bam()) {   // SAM: the text as it lies in the file (slimm_push_sam_bytes finds and decodes the lines)
+            if (bam.can_read_text()) {   // SAM, plain or gzip: the text (slimm_push_sam_bytes finds and decodes the lines)
                 n = bam.read_text(raw_buf[w].get(), raw_cap());
                 ++raw_windows_device;
             } else if (device_period && bam.can_read_blocks() && (raw_windows_device + raw_windows_host) % device_period == device_period - 1u) {
@@ -659,7 +663,7 @@ struct RecordPump {
             decode_ms += ms(t1, std::chrono::steady_clock::now());
             {
                 std::lock_guard<std::mutex> g(mu);
-                raw_ready.push_back(RawWindow{w, n, n > 0 && bam.is_bam() && bam.raw_exhausted(), compressed});
+                raw_ready.push_back(RawWindow{w, n, n > 0 && bgzf && bam.raw_exhausted(), compressed});
             }
             cv.notify_all();
             if (n <= 0) {
@@ -704,9 +708,11 @@ struct RecordPump {
                     (void)slimm_pin_host_buffer(c, raw_buf[w.which].get(), raw_cap());  // (pageable memory still works)
                     pinned[w.which] = true;
                 }
-                rc = text ? slimm_push_sam_bytes(c, raw_buf[w.which].get(), static_cast<uint64_t>(w.n), w.last ? 1 : 0, &got)
-                     : w.compressed ? slimm_push_bgzf_blocks(c, raw_buf[w.which].get(), static_cast<uint64_t>(w.n), 0u, w.last ? 1 : 0, &got)
-                                    : slimm_push_bam_bytes(c, raw_buf[w.which].get(), static_cast<uint64_t>(w.n), w.last ? 1 : 0, &got);
+                const uint8_t* p = raw_buf[w.which].get();
+                const uint64_t n = static_cast<uint64_t>(w.n);
+                const int last = w.last ? 1 : 0;
+                rc = w.compressed ? (text ? slimm_push_bgzf_sam_blocks(c, p, n, 0u, last, &got) : slimm_push_bgzf_blocks(c, p, n, 0u, last, &got))
+                                  : (text ? slimm_push_sam_bytes(c, p, n, last, &got) : slimm_push_bam_bytes(c, p, n, last, &got));
                 closed = w.last;
             } else if (!closed) {
                 rc = text ? slimm_push_sam_bytes(c, nullptr, 0, 1, &got)

@@ -313,6 +313,9 @@ struct SamRefEntry {   // open addressing over the header's reference names (ref
 uint32_t sam_pieces(uint64_t n_bytes);
 uint64_t sam_name_hash(const char* s, size_t n);
 void launch_sam_find(hipStream_t st, const uint8_t* bytes, uint64_t lo, uint64_t end, BamPiece* pieces, uint32_t* offs, BamWindowResult* result);
+// the file's last window of SAM text, when the device inflated the text's end: a last line in bytes[lo, end) without its newline
+// gets one at bytes[end] (the buffer has room behind `end`); *ended = 1 when it did, else 0
+void launch_sam_end_line(hipStream_t st, uint8_t* bytes, uint64_t lo, uint64_t end, uint32_t* ended);
 void launch_sam_decode(hipStream_t st, const uint8_t* bytes, uint64_t lo, uint64_t end, const BamPiece* pieces, const uint32_t* offs,
                        BamCarry* carry, const BamWindowResult* result, bool marked, uint64_t out_at, uint64_t* key, int32_t* ref, int32_t* pos,
                        uint16_t* flag, uint32_t* check, const SamRefEntry* table, uint32_t table_mask, const uint8_t* names);

@@ -8,6 +8,7 @@
 //                  found by word arithmetic --, their offsets (bit 31: the line has fewer than ten fields, is empty or starts
 //                  with '@': an error of the push, like the host reader's), and where the last of them ends.  A newline is an
 //                  exact boundary: nothing is guessed, nothing verified.
+//   k_sam_end_line the file's last window, inflated here: a last line without its newline gets one
 //   k_bam_scan     (bam_decode.hip) lines in front of every piece, the window's totals, where its last complete line ends
 //   k_sam_decode   a WAVE per piece, a lane per line: the fields; RNAME through a hash table of the header's names (exact:
 //                  the bytes are compared); input grouped by name: QNAME compared with the line before (its canonical base:
@@ -297,6 +298,15 @@ __global__ __launch_bounds__(64) void k_sam_carry(const uint8_t* __restrict__ b,
     }
 }
 
+// The text's last line, when its last bytes were inflated here: without its newline it ends at `end` all the same, as a
+// line the host hands over does (bam_push_window gives that one its newline before the copy).  One lane: a byte is looked at.
+__global__ __launch_bounds__(64) void k_sam_end_line(uint8_t* __restrict__ b, uint64_t lo, uint64_t end, uint32_t* __restrict__ ended) {
+    if (threadIdx.x != 0) return;
+    const bool open = end > lo && b[end - 1] != '\n';
+    if (open) b[end] = '\n';
+    *ended = open ? 1u : 0u;
+}
+
 }  // namespace
 
 uint32_t sam_pieces(uint64_t n_bytes) { return static_cast<uint32_t>((n_bytes + kSamPiece - 1) / kSamPiece); }
@@ -314,6 +324,10 @@ void launch_sam_find(hipStream_t st, const uint8_t* bytes, uint64_t lo, uint64_t
     const uint32_t np = sam_pieces(end - lo);
     if (np) hipLaunchKernelGGL(k_sam_pieces, dim3((np + 63u) / 64u), dim3(64), 0, st, bytes, lo, end, np, pieces, offs);
     launch_bam_scan(st, pieces, np, end, result, static_cast<uint32_t>(lo));
+}
+
+void launch_sam_end_line(hipStream_t st, uint8_t* bytes, uint64_t lo, uint64_t end, uint32_t* ended) {
+    hipLaunchKernelGGL(k_sam_end_line, dim3(1), dim3(64), 0, st, bytes, lo, end, ended);
 }
 
 void launch_sam_decode(hipStream_t st, const uint8_t* bytes, uint64_t lo, uint64_t end, const BamPiece* pieces, const uint32_t* offs,

@@ -55,7 +55,7 @@ int bam_finish_window(slimm_ctx* c, uint64_t j, uint64_t n_bytes, bool is_last, 
     const bool marked = c->order == SLIMM_ORDER_GROUPED;
     const uint32_t b = static_cast<uint32_t>(j % slimm_ctx::kBamRing), nb = static_cast<uint32_t>((j + 1u) % slimm_ctx::kBamRing);
     uint64_t lo = kBamSlack - B.carry_bytes;
-    const uint64_t end = kBamSlack + n_bytes;
+    uint64_t end = kBamSlack + n_bytes;
     if (B.starts_mid && j == 0 && !B.sam) {
         // A range that starts inside the file (slimm_set_input_mid_file): its first record is guessed from the bytes, as
         // k_bam_pieces guesses a piece's; the bytes in front of it (the head, at most 16 MiB) stay on the device for the
@@ -90,6 +90,22 @@ int bam_finish_window(slimm_ctx* c, uint64_t j, uint64_t n_bytes, bool is_last, 
         HIP_TRY(c, B.offs.ensure_later((static_cast<size_t>(np) + (np >> 2) + 64) * kBamSlots, B.outgrown));
     if (n_bytes) HIP_TRY(c, hipStreamWaitEvent(st, B.copied[b], 0));
     const bool inflated_here = n_bytes && B.inflated[b];
+    if (B.sam && is_last && B.sam_dev_tail) {
+        // the text's last bytes were inflated here: the host could not give a last line without its newline one (status
+        // word 3 of the buffer: the line was ended)
+        uint32_t* ended = B.inflate_status.p + 4u * b + 3u;
+        launch_sam_end_line(st, B.bytes[b].p, lo, end, ended);
+        HIP_TRY(c, hipMemcpyAsync(B.h_inflate_status.p, B.inflate_status.p + 4u * b, 16, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        if (inflated_here && B.h_inflate_status.p[0])
+            return fail(c, SLIMM_E_INVALID, "corrupt BGZF block (device inflate: error %u in block %u of the window)", B.h_inflate_status.p[0],
+                        B.h_inflate_status.p[1]);
+        if (B.h_inflate_status.p[3]) {
+            ++B.sam_lines_ended;
+            push_trace("window %llu: the text's last line ended on the device", (unsigned long long)j);
+        }
+        end += B.h_inflate_status.p[3];
+    }
     if (inflated_here)
         HIP_TRY(c, hipMemcpyAsync(B.h_inflate_status.p, B.inflate_status.p + 4u * b, 16, hipMemcpyDeviceToHost, st));
     if (B.sam)
@@ -169,7 +185,7 @@ int slimm_set_input_mid_file(slimm_ctx* c, int starts_mid_file, int ends_mid_fil
 }
 
 namespace {
-enum { kFormatBam = 0, kFormatBgzf = 1, kFormatSam = 2 };
+enum { kFormatBam = 0, kFormatBgzf = 1, kFormatSam = 2, kFormatBgzfSam = 3 };
 int bam_push_window(slimm_ctx* c, const uint8_t* bytes, uint64_t n_bytes, int format, uint32_t skip, int last, uint64_t* n_records);
 }
 int slimm_set_input_size_hint(slimm_ctx* c, uint64_t compressed_bytes) {
@@ -201,6 +217,9 @@ int slimm_push_bgzf_blocks(slimm_ctx* c, const uint8_t* blocks, uint64_t n_bytes
 }
 int slimm_push_sam_bytes(slimm_ctx* c, const uint8_t* text, uint64_t n_bytes, int last, uint64_t* n_records) {
     return bam_push_window(c, text, n_bytes, kFormatSam, 0u, last, n_records);
+}
+int slimm_push_bgzf_sam_blocks(slimm_ctx* c, const uint8_t* blocks, uint64_t n_bytes, uint32_t skip, int last, uint64_t* n_records) {
+    return bam_push_window(c, blocks, n_bytes, kFormatBgzfSam, skip, last, n_records);
 }
 // The header's reference names (@SQ SN, index = the reference id) for slimm_push_sam_bytes: a hash table on the device.
 int slimm_set_reference_names(slimm_ctx* c, const char* const* names) {
@@ -349,8 +368,8 @@ int bam_launch_gathered(slimm_ctx* c) {
 int bam_push_window(slimm_ctx* c, const uint8_t* bytes, uint64_t src_bytes, int format, uint32_t skip, int last, uint64_t* n_records) {
     if (!c) return SLIMM_E_INVALID;
     if (n_records) *n_records = 0;
-    bool compressed = format == kFormatBgzf;
-    const bool sam = format == kFormatSam;
+    bool compressed = format == kFormatBgzf || format == kFormatBgzfSam;
+    const bool sam = format == kFormatSam || format == kFormatBgzfSam;
     if (sam && !c->bam.sam_mask) return fail(c, SLIMM_E_INVALID, "slimm_set_reference_names first: SAM text names its references");
     if (c->bam.active && c->bam.sam != sam) return fail(c, SLIMM_E_INVALID, "SAM text and BAM bytes do not mix within a file");
     uint64_t n_bytes = src_bytes;  // the push's record bytes
@@ -405,6 +424,7 @@ int bam_push_window(slimm_ctx* c, const uint8_t* bytes, uint64_t src_bytes, int 
         B.sam = sam;
         B.planned = false;
         B.sam_last_byte = '\n';
+        B.sam_dev_tail = false;
         B.found_start = B.has_first = B.q18_by_group = false;
         B.head_len = 0;
         c->marked = marked;
@@ -479,7 +499,7 @@ int bam_push_window(slimm_ctx* c, const uint8_t* bytes, uint64_t src_bytes, int 
                     }
                     for (uint32_t k = 0; k < std::min<uint32_t>(2u, nbuf); ++k)
                         HIP_TRY(c, B.inflate_scratch[k].ensure_later(bgzf_inflate_scratch_bytes(blocks_max, tok_max), B.outgrown));
-                    const size_t np_max = bam_pieces(B.win_cap + kBamSlack) + 64;
+                    const size_t np_max = (sam ? sam_pieces(B.win_cap + kBamSlack) : bam_pieces(B.win_cap + kBamSlack)) + 64;
                     HIP_TRY(c, B.pieces.ensure_later(np_max, B.outgrown));
                     HIP_TRY(c, B.offs.ensure_later(np_max * kBamSlots, B.outgrown));
                     push_trace("buffers reserved");
@@ -515,16 +535,21 @@ int bam_push_window(slimm_ctx* c, const uint8_t* bytes, uint64_t src_bytes, int 
         B.desc_host[b].insert(B.desc_host[b].end(), dh.begin(), dh.end());
         B.acc_src += src_bytes;
         B.acc_dst += inflated;
+        B.sam_dev_tail = sam;   // (the text's last bytes so far are the device's to see)
         if (B.acc_dst >= slimm_ctx::kBamGatherGoal) {
             const int rc = bam_launch_gathered(c);
             if (rc != SLIMM_OK) return rc;
         }
-    } else if (n_bytes || (sam && last && B.sam_last_byte != '\n')) {  // inflated bytes / text: a window of their own, behind what was gathered
+    } else if (n_bytes || (sam && last && (B.sam_last_byte != '\n' || B.sam_dev_tail))) {  // inflated bytes / text: a window of their own, behind what was gathered
         int rc = bam_launch_gathered(c);
         if (rc != SLIMM_OK) return rc;
-        // (SAM text whose last line has no newline gets one: a line ends where its newline is)
-        if (sam && n_bytes) B.sam_last_byte = bytes[n_bytes - 1];
-        const bool add_newline = sam && last && B.sam_last_byte != '\n';
+        // (SAM text whose last line has no newline gets one: a line ends where its newline is.  When the text's last bytes
+        // were inflated on the device, an empty last window goes behind them and the device ends that line: bam_finish_window)
+        if (sam && n_bytes) {
+            B.sam_last_byte = bytes[n_bytes - 1];
+            B.sam_dev_tail = false;
+        }
+        const bool add_newline = sam && last && !B.sam_dev_tail && B.sam_last_byte != '\n';
         rc = bam_window_buffer(c, n_bytes + (add_newline ? 1u : 0u));
         if (rc != SLIMM_OK) return rc;
         const uint32_t b = static_cast<uint32_t>(B.windows % slimm_ctx::kBamRing);

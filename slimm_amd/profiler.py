@@ -287,13 +287,15 @@ class Slimm:
             total += got.value
         return total
 
-    def push_bgzf_blocks(self, blob, skip: int = 0, window: int = 0, host_every: int = 0) -> int:
+    def push_bgzf_blocks(self, blob, skip: int = 0, window: int = 0, host_every: int = 0, sam: bool = False) -> int:
         """slimm_push_bgzf_blocks: whole BGZF blocks of a BAM file (compressed), the first of which holds the first alignment
         record `skip` inflated bytes in; windows of about `window` compressed bytes (0: one), cut at block boundaries.  The
         device inflates the blocks, finds the records and decodes them.  host_every = k > 0: every k-th window is inflated
         HERE (zlib) and handed over through slimm_push_bam_bytes instead -- the two forms may alternate within a file.
-        Returns the number of records."""
+        sam: the blocks hold SAM text (push_bgzf_sam_blocks).  Returns the number of records."""
         import zlib
+        push_blocks = self.L.slimm_push_bgzf_sam_blocks if sam else self.L.slimm_push_bgzf_blocks
+        push_bytes = self.L.slimm_push_sam_bytes if sam else self.L.slimm_push_bam_bytes
         buf = np.frombuffer(blob, dtype=np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob, dtype=np.uint8)
         n = buf.shape[0]
         cuts, p = [0], 0
@@ -306,7 +308,7 @@ class Slimm:
             cuts.append(n)
         total, got, keep = 0, C.c_uint64(), []
         if n == 0:
-            self._check(self.L.slimm_push_bgzf_blocks(self.ctx, None, 0, 0, 1, C.byref(got)))
+            self._check(push_blocks(self.ctx, None, 0, 0, 1, C.byref(got)))
         for k in range(len(cuts) - 1):
             piece = np.ascontiguousarray(buf[cuts[k]:cuts[k + 1]])
             last = 1 if k == len(cuts) - 2 else 0
@@ -317,12 +319,18 @@ class Slimm:
                     raw += d.decompress(rest)
                     rest = d.unused_data
                 piece = np.frombuffer(bytes(raw[(skip if k == 0 else 0):]), dtype=np.uint8)
-                self._check(self.L.slimm_push_bam_bytes(self.ctx, _p(piece) if piece.size else None, piece.size, last, C.byref(got)))
+                self._check(push_bytes(self.ctx, _p(piece) if piece.size else None, piece.size, last, C.byref(got)))
             else:
-                self._check(self.L.slimm_push_bgzf_blocks(self.ctx, _p(piece), piece.size, skip if k == 0 else 0, last, C.byref(got)))
+                self._check(push_blocks(self.ctx, _p(piece), piece.size, skip if k == 0 else 0, last, C.byref(got)))
             keep = (keep + [piece])[-3:]   # (a window's buffer stays until the next call has returned)
             total += got.value
         return total
+
+    def push_bgzf_sam_blocks(self, blob, skip: int = 0, window: int = 0, host_every: int = 0) -> int:
+        """slimm_push_bgzf_sam_blocks: whole BGZF blocks of a SAM file (compressed text), the first alignment line `skip`
+        inflated bytes in (set_reference_names first); windows as in push_bgzf_blocks, every host_every-th of them inflated
+        here and handed over through slimm_push_sam_bytes.  Returns the number of records."""
+        return self.push_bgzf_blocks(blob, skip=skip, window=window, host_every=host_every, sam=True)
 
     def push_wait(self):
         self._check(self.L.slimm_push_wait(self.ctx))
