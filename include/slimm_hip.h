@@ -242,7 +242,14 @@ int slimm_push_bgzf_blocks(slimm_ctx* ctx, const uint8_t* blocks, uint64_t n_byt
  * file: one window of ~0.3 GB; a file of many gigabytes: four windows, ~14 GB at a ratio of 3) -- reserving ahead matters
  * because an allocation made while inflate kernels run waits for them.  Without a hint nothing is reserved ahead and buffers
  * appear as windows need them (the same totals, some stalls).  slimm_reset keeps up to 4 GiB of these buffers for the next
- * file and releases them above that; slimm_window_memory reports what is held.  The hint is per file (cleared by slimm_reset). */
+ * file and releases them above that; slimm_window_memory reports what is held.  The hint is per file (cleared by slimm_reset).
+ * bzip2 SAM (slimm_push_bzip2_sam_bytes) gathers no compressed window on the device: a batch of blocks is decoded at a time,
+ * with 4.5 MB of scratch per block of the batch (900 kB of BWT string -- then its RLE1 text -- and 3.6 MB of inverse-BWT
+ * links) + 1 KB of byte histogram, for 16 to 256 blocks (the hint / 64 kB; 64 without a hint): at most 1.15 GB, sized for
+ * each file at its first decode (it grows, never shrinks, between files; slimm_reset releases it with the rest above 4 GiB);
+ * plus the compressed bytes of a round (the pushes since the last one, at most 448 MB reserved from the hint) and 8 B per
+ * block magic found.  Its text windows take the ring of window buffers above, one batch's text
+ * each (< 1.9 GB): within today's total of <= 17 GB per file. */
 int slimm_set_input_size_hint(slimm_ctx* ctx, uint64_t compressed_bytes);
 int slimm_window_memory(slimm_ctx* ctx, uint64_t* device_bytes);
 /* hipMemGetInfo of the context's device: bytes in use (by every process and context on it) and the device's total. */
@@ -267,6 +274,18 @@ int slimm_push_sam_bytes(slimm_ctx* ctx, const uint8_t* text, uint64_t n_bytes, 
  * SAM and BAM do not mix.  A file's last line without its newline is a line also when the device inflated it (the caller
  * never sees those bytes).  Errors: those of the two, SLIMM_E_INVALID "corrupt BGZF block" among them. */
 int slimm_push_bgzf_sam_blocks(slimm_ctx* ctx, const uint8_t* blocks, uint64_t n_bytes, uint32_t skip, int last, uint64_t* n_records);
+/* BZIP2-COMPRESSED SAM TEXT (`bzip2 x.sam`; pbzip2 / lbzip2: streams back to back, of any levels) decoded on the device:
+ * `bytes` = the file's next n_bytes, from its first byte on and in order across calls, cut anywhere (inside a block, inside
+ * a magic); of the decoded text the first `skip` bytes are the header (in front of the first alignment line; 0 in every
+ * later call).  Pushes are gathered on the host and decoded in rounds: the device finds block magics at every bit offset,
+ * decodes the blocks of a batch at once (Huffman, MTF, inverse BWT, RLE1), checks every block CRC and -- on the host --
+ * each stream's combined CRC, and hands the text to the SAM finder and decoder as slimm_push_sam_bytes does
+ * (slimm_set_reference_names first).  The caller's buffer is free when the call returns.  A block whose bytes have not all
+ * come yet waits for the next push.  This form does not mix with the others within a file.  Errors: SLIMM_E_INVALID
+ * "bzip2-compressed input is not supported unless it decodes: <where>: <cause>" -- truncation, a bad Huffman code, a block
+ * or combined CRC mismatch, origPtr out of range, a block longer than its level allows, a randomised block (never
+ * written since bzip2 0.9.5: refused), bytes after the last end-of-stream marker. */
+int slimm_push_bzip2_sam_bytes(slimm_ctx* ctx, const uint8_t* bytes, uint64_t n_bytes, uint32_t skip, int last, uint64_t* n_records);
 /* Page-locks a buffer of the caller (hipHostRegister) until the context is destroyed: copies out of it then run at the
  * speed of the bus instead of the runtime's own staging. */
 int slimm_pin_host_buffer(slimm_ctx* ctx, const void* buffer, uint64_t n_bytes);

@@ -1,0 +1,439 @@
+// bzip2-compressed SAM decoded on the device (include/slimm_hip.h: slimm_push_bzip2_sam_bytes; the block format:
+// bzip2_block.h).  The host cannot know where a block ends, nor how much text it holds, without decoding it, so a window of
+// compressed bytes goes through stages:
+//   k_bz2_find    every bit offset of the bytes: the 48-bit block magic there?  Candidates -- a magic may also occur by
+//                 chance inside compressed data (2^-48 per bit), so none is trusted
+//   k_bz2_decode  a WAVE per candidate of a batch (lane 0; the block's tables in LDS): Huffman, selectors, MTF, RUNA/RUNB
+//                 -> the block's BWT string, its byte histogram, where it ended (or that the bytes ran out)
+//   (host)        the chain: from the first block, known real, each block's end to the next magic, end-of-stream markers
+//                 (combined CRC, padding, a next "BZh" stream) checked on the host's copy of the bytes; candidates
+//                 inside real blocks are dropped; a block that ran out of bytes waits, with its bytes, for the next push
+//   k_bz2_unbwt   a workgroup per block: the inverse BWT's links (a counting sort), then the walk from origPtr cut at
+//                 rulers (every kRuler-th position): each thread walks from a ruler to the next, the rulers of the cycle
+//                 through origPtr are put in order, each walk is repeated writing its bytes in place (a text that repeats
+//                 itself has several cycles: the one through origPtr is repeated, as bzip2's n-step walk does); then the
+//                 RLE1 text's length
+//   k_bz2_emit    a wave per block: RLE1 undone into the window buffer behind the blocks in front of it (the lengths'
+//                 prefix sum), contiguous as the SAM decoder wants it, the block's CRC checked
+// The window then goes to the SAM finder and decoder as any text window does (windows.hip).
+#include "context.h"
+
+namespace slimm {
+namespace {
+
+constexpr uint32_t kRuler = 256;   // positions between two rulers of the inverse BWT's walk
+constexpr uint32_t kMaxRulers = bz2::kMaxBlock / kRuler + 2;
+constexpr uint64_t kBz2Tail = 16;  // zeroed bytes behind the compressed bytes on the device
+
+__global__ __launch_bounds__(256) void k_bz2_find(const uint8_t* __restrict__ b, uint64_t n_bytes, uint64_t bit_lo, uint64_t bit_hi,
+                                                   unsigned long long* __restrict__ cand, uint32_t* __restrict__ count, uint32_t cap) {
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+    for (uint64_t i = (bit_lo >> 3) + static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n_bytes; i += stride) {
+        uint64_t v = 0;   // bytes i .. i + 7, the first one highest (the buffer has kBz2Tail zeroed bytes behind n_bytes)
+        for (uint32_t k = 0; k < 8; ++k) v = (v << 8) | b[i + k];
+        for (uint32_t k = 0; k < 8; ++k) {
+            const uint64_t bit = i * 8u + k;
+            if (bit < bit_lo || bit + 48u > bit_hi) continue;
+            if (((v >> (16u - k)) & 0xffffffffffffull) == bz2::kBlockMagic) {
+                const uint32_t at = atomicAdd(count, 1u);
+                if (at < cap) cand[at] = bit;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void k_bz2_decode(const uint8_t* __restrict__ b, uint64_t end_bit, const unsigned long long* __restrict__ cand,
+                                                    uint8_t* __restrict__ ll, uint32_t* __restrict__ hist, bz2::BlockInfo* __restrict__ info) {
+    __shared__ bz2::Tables t;
+    if (threadIdx.x != 0) return;
+    const uint32_t s = blockIdx.x;
+    bz2::BlockInfo r;
+    bz2::decode_block(b, cand[s], end_bit, bz2::kMaxBlock, t, ll + static_cast<uint64_t>(s) * bz2::kMaxBlock, hist + s * 256u, r);
+    info[s] = r;
+}
+
+// text_len[k] = the RLE1 text's bytes of the block in slot slots[k]; ~0u: its links are no permutation (never for links
+// made by link_block: a guard against an out-of-range walk)
+__global__ __launch_bounds__(256) void k_bz2_unbwt(const uint32_t* __restrict__ slots, const bz2::BlockInfo* __restrict__ info,
+                                                    uint8_t* __restrict__ ll_all, uint32_t* __restrict__ link_all, const uint32_t* __restrict__ hist,
+                                                    uint32_t* __restrict__ text_len) {
+    __shared__ uint32_t r_len[kMaxRulers], r_next[kMaxRulers], r_off[kMaxRulers];
+    __shared__ uint32_t cf[256];
+    __shared__ uint32_t bad, period;
+    const uint32_t s = slots[blockIdx.x];
+    const uint32_t n = info[s].n, orig = info[s].orig_ptr;
+    uint8_t* ll = ll_all + static_cast<uint64_t>(s) * bz2::kMaxBlock;
+    uint32_t* link = link_all + static_cast<uint64_t>(s) * bz2::kMaxBlock;
+    if (threadIdx.x == 0) {
+        bz2::link_block(ll, n, hist + s * 256u, link, cf);
+        bad = 0;
+    }
+    __syncthreads();
+    // the rulers: positions r * kRuler, and origPtr (index nr) unless it is one of them
+    const uint32_t nr = (n + kRuler - 1u) / kRuler, total = nr + (orig % kRuler ? 1u : 0u);
+    auto ruler_of = [&](uint32_t p) -> uint32_t { return p % kRuler == 0 ? p / kRuler : (p == orig ? nr : ~0u); };
+    auto ruler_pos = [&](uint32_t r) -> uint32_t { return r < nr ? r * kRuler : orig; };
+    for (uint32_t r = threadIdx.x; r < total; r += blockDim.x) {
+        uint32_t p = ruler_pos(r), len = 0, nx;
+        do {
+            p = link[p] & bz2::kLinkMask;
+            ++len;
+            nx = p < n ? ruler_of(p) : ~1u;
+        } while (nx == ~0u && len <= n);
+        r_len[r] = len;
+        r_next[r] = nx;
+        r_off[r] = ~0u;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        // the rulers of the cycle through origPtr in the walk's order: where each one's stretch of the text starts, until
+        // the cycle closes after `period` positions (n, unless the text repeats itself)
+        const uint32_t first = ruler_of(orig);
+        uint32_t r = first, off = 0;
+        do {
+            if (r >= total || r_off[r] != ~0u || r_len[r] > n - off) {
+                bad = 1;
+                break;
+            }
+            r_off[r] = off;
+            off += r_len[r];
+            r = r_next[r];
+        } while (r != first);
+        period = off;
+        if (off == 0) bad = 1;
+    }
+    __syncthreads();
+    if (bad) {
+        if (threadIdx.x == 0) text_len[blockIdx.x] = ~0u;
+        return;
+    }
+    for (uint32_t r = threadIdx.x; r < total; r += blockDim.x) {
+        uint32_t p = ruler_pos(r), o = r_off[r];
+        if (o == ~0u) continue;   // (a ruler of another cycle)
+        const uint32_t e = o + r_len[r];
+        for (; o < e; ++o) {
+            const uint32_t u = link[p];
+            ll[o] = static_cast<uint8_t>(u >> 24);
+            p = u & bz2::kLinkMask;
+        }
+    }
+    __syncthreads();
+    // n steps round a cycle of `period` positions: the stretch again and again (reads below `period`, writes above it)
+    for (uint32_t k = period + threadIdx.x; k < n; k += blockDim.x) ll[k] = ll[k % period];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        bz2::Rle1 st;
+        uint32_t len = 0, byte;
+        for (uint32_t k = 0; k < n; ++k) len += st.step(ll[k], byte);
+        text_len[blockIdx.x] = len;
+    }
+}
+
+// the RLE1 text of block k (slot slots[k]) into dst: its byte j at dst[at[2k] + j] for j >= at[2k + 1] (bytes in front are
+// skipped: the header); crc_ok[k] = its CRC matches
+__global__ __launch_bounds__(64) void k_bz2_emit(const uint32_t* __restrict__ slots, const uint8_t* __restrict__ ll_all,
+                                                  const bz2::BlockInfo* __restrict__ info, const int64_t* __restrict__ at, uint8_t* __restrict__ dst,
+                                                  uint32_t* __restrict__ crc_ok) {
+    __shared__ uint32_t tab[256];
+    for (uint32_t i = threadIdx.x; i < 256; i += blockDim.x) {
+        uint32_t c = i << 24;
+        for (int k = 0; k < 8; ++k) c = (c & 0x80000000u) ? (c << 1) ^ 0x04c11db7u : (c << 1);
+        tab[i] = c;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const uint32_t s = slots[blockIdx.x], n = info[s].n;
+    const uint8_t* ll = ll_all + static_cast<uint64_t>(s) * bz2::kMaxBlock;
+    const int64_t base = at[2u * blockIdx.x], drop = at[2u * blockIdx.x + 1u];
+    bz2::Rle1 st;
+    uint32_t crc = 0xffffffffu, byte;
+    int64_t j = 0;
+    for (uint32_t k = 0; k < n; ++k) {
+        const uint32_t copies = st.step(ll[k], byte);
+        for (uint32_t c = 0; c < copies; ++c, ++j) {
+            crc = bz2::crc_byte(tab, crc, byte);
+            if (j >= drop) dst[base + j] = static_cast<uint8_t>(byte);
+        }
+    }
+    crc_ok[blockIdx.x] = ~crc == info[s].crc ? 1u : 0u;
+}
+
+void push_trace_bz2(const char* fmt, ...) {
+    static const bool on = traced("push");
+    if (!on) return;
+    va_list ap;
+    va_start(ap, fmt);
+    fprintf(stderr, "[push bzip2] ");
+    vfprintf(stderr, fmt, ap);
+    fputc('\n', stderr);
+    va_end(ap);
+}
+
+double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+#define BZ2_FAIL(fmt, ...) fail(c, SLIMM_E_INVALID, "bzip2-compressed input is not supported unless it decodes: " fmt, __VA_ARGS__)
+
+// the block magics of pend from Z.bit on, in order: the bytes not read yet go to the device first (those in front of
+// Z.bit are dropped from pend)
+int bz2_find(slimm_ctx* c) {
+    slimm_ctx::BamDecode::Bzip2& Z = c->bam.bz2;
+    hipStream_t st = c->stream;
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t drop = static_cast<size_t>(Z.bit >> 3);
+    if (drop) {
+        Z.pend.erase(Z.pend.begin(), Z.pend.begin() + static_cast<long>(drop));
+        Z.base += drop;
+        Z.bit -= drop * 8u;
+    }
+    const uint64_t n = Z.pend.size();
+    if (Z.comp.cap < n + kBz2Tail) HIP_TRY(c, Z.comp.ensure_later(n + (n >> 3) + kBz2Tail, c->bam.outgrown));
+    if (n) HIP_TRY(c, hipMemcpyAsync(Z.comp.p, Z.pend.data(), n, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemsetAsync(Z.comp.p + n, 0, kBz2Tail, st));
+    HIP_TRY(c, Z.count.ensure(4));
+    uint32_t cap = static_cast<uint32_t>(std::min<uint64_t>(n / 64u + 256u, 1u << 26));
+    for (;;) {
+        if (Z.d_cand.cap < cap) HIP_TRY(c, Z.d_cand.ensure_later(cap, c->bam.outgrown));
+        HIP_TRY(c, hipMemsetAsync(Z.count.p, 0, 4, st));
+        const uint64_t span = n > (Z.bit >> 3) ? n - (Z.bit >> 3) : 0;
+        const uint32_t grid = static_cast<uint32_t>(std::max<uint64_t>(1u, std::min<uint64_t>((span + 255u) / 256u, 4096u)));
+        if (span) hipLaunchKernelGGL(k_bz2_find, dim3(grid), dim3(256), 0, st, Z.comp.p, n, Z.bit, n * 8u, Z.d_cand.p, Z.count.p, cap);
+        HIP_TRY(c, hipGetLastError());
+        uint32_t got = 0;
+        HIP_TRY(c, hipMemcpyAsync(&got, Z.count.p, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        if (got > cap) {   // (more magics than room: blocks of a few bytes each, pbzip2 on a tiny input)
+            cap = got + (got >> 2) + 256u;
+            continue;
+        }
+        Z.cand.resize(got);
+        if (got) HIP_TRY(c, hipMemcpy(Z.cand.data(), Z.d_cand.p, got * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        break;
+    }
+    std::sort(Z.cand.begin(), Z.cand.end());
+    long every = 0;
+    if (forced("bzip2_false_magics", &every)) {
+        // (tests: candidates that are no blocks -- a few bits into every real one, and every `every` bits, 4096 by default
+        // -- must be decoded and dropped without changing anything)
+        const uint64_t step = every > 1 ? static_cast<uint64_t>(every) : 4096u;
+        std::vector<uint64_t> extra;
+        for (uint64_t b : Z.cand) extra.push_back(b + 13u);
+        for (uint64_t b = Z.bit + 5u; b + 48u <= n * 8u; b += step) extra.push_back(b);
+        Z.cand.insert(Z.cand.end(), extra.begin(), extra.end());
+        std::sort(Z.cand.begin(), Z.cand.end());
+        Z.cand.erase(std::unique(Z.cand.begin(), Z.cand.end()), Z.cand.end());
+    }
+    Z.next_cand = 0;
+    Z.found = true;
+    Z.ms_find += ms_since(t0);
+    return SLIMM_OK;
+}
+
+// the decode scratch for `slots` blocks at a time, once per file
+int bz2_reserve(slimm_ctx* c) {
+    slimm_ctx::BamDecode::Bzip2& Z = c->bam.bz2;
+    if (Z.slots) return SLIMM_OK;
+    // (a batch of blocks: as many as the file has, about -- a 900 k block compresses SAM text to 60 - 250 kB --, 16 to 256)
+    const uint64_t hint = c->bam.size_hint;
+    Z.slots = hint ? static_cast<uint32_t>(std::min<uint64_t>(256u, std::max<uint64_t>(16u, hint / 65536u + 2u))) : 64u;
+    HIP_TRY(c, Z.ll.ensure(static_cast<size_t>(Z.slots) * bz2::kMaxBlock));
+    HIP_TRY(c, Z.link.ensure(static_cast<size_t>(Z.slots) * bz2::kMaxBlock));
+    HIP_TRY(c, Z.hist.ensure(static_cast<size_t>(Z.slots) * 256u));
+    HIP_TRY(c, Z.info.ensure(Z.slots));
+    HIP_TRY(c, Z.text_len.ensure(2u * Z.slots));
+    HIP_TRY(c, Z.out_at.ensure(2u * Z.slots));
+    if (hint && Z.comp.cap < hint + kBz2Tail) {
+        const uint64_t comp = std::min<uint64_t>(hint, 448ull << 20) + kBz2Tail;   // (a window: the pushes since the last batch)
+        HIP_TRY(c, Z.comp.ensure(comp));
+        HIP_TRY(c, Z.d_cand.ensure(comp / 64u + 256u));
+    }
+    push_trace_bz2("%u blocks a batch: %.0f MB of decode scratch", Z.slots, Z.held() / 1e6);
+    return SLIMM_OK;
+}
+
+}  // namespace
+
+int bz2_decode_batch(slimm_ctx* c, bool last) {
+    slimm_ctx::BamDecode::Bzip2& Z = c->bam.bz2;
+    hipStream_t st = c->stream;
+    Z.ready.clear();
+    Z.ready_pos = 0;
+    if (Z.waiting && !last) return SLIMM_OK;   // (no byte has come since the chain stopped for want of them)
+    int rc = bz2_reserve(c);
+    if (rc != SLIMM_OK) return rc;
+    if (!Z.found) {
+        rc = bz2_find(c);
+        if (rc != SLIMM_OK) return rc;
+    }
+    const uint64_t end_bit = Z.pend.size() * 8u;
+    auto at = [&](uint64_t bit) { return static_cast<unsigned long long>(Z.base + (bit >> 3)); };
+    std::vector<bz2::BlockInfo> hinfo;
+    size_t batch0 = 0, nb = 0;   // the batch: candidates [batch0, batch0 + nb) in slots 0 .. nb - 1
+    std::vector<uint32_t> slots;
+    std::vector<uint32_t> crcs;
+    std::vector<uint64_t> ats;
+    for (;;) {
+        if (!Z.in_stream) {   // a stream header, at a byte
+            const uint64_t byte = Z.bit >> 3;
+            const uint64_t avail = Z.pend.size() - byte;
+            const uint8_t* h = Z.pend.data() + byte;
+            if (avail == 0) {
+                if (last && Z.streams == 0) return BZ2_FAIL("truncated at byte %llu", at(Z.bit));
+                Z.waiting = true;
+                break;
+            }
+            if (avail < 4 && !last && memcmp(h, "BZh", avail) == 0) {
+                Z.waiting = true;
+                break;
+            }
+            if (avail < 4 || memcmp(h, "BZh", 3) != 0 || h[3] < '1' || h[3] > '9') {
+                if (avail < 4 && memcmp(h, "BZh", avail) == 0) return BZ2_FAIL("truncated stream header at byte %llu", at(Z.bit));
+                if (Z.streams) return BZ2_FAIL("bytes after the last end-of-stream marker, at byte %llu", at(Z.bit));
+                return BZ2_FAIL("not a bzip2 stream%s", "");
+            }
+            Z.level = static_cast<uint32_t>(h[3] - '0');
+            Z.combined = 0;
+            Z.in_stream = true;
+            ++Z.streams;
+            Z.bit += 32;
+        }
+        bz2::Bits br(Z.pend.data(), Z.bit, end_bit);
+        uint64_t magic;
+        if (!br.peek48(magic)) {
+            if (last) return BZ2_FAIL("truncated at byte %llu", at(Z.bit));
+            Z.waiting = true;
+            break;
+        }
+        if (magic == bz2::kEosMagic) {
+            uint32_t v, hi, lo;
+            if (!br.get(24, v) || !br.get(24, v) || !br.get(16, hi) || !br.get(16, lo)) {
+                if (last) return BZ2_FAIL("truncated end-of-stream marker at byte %llu", at(Z.bit));
+                Z.waiting = true;
+                break;
+            }
+            if (((hi << 16) | lo) != Z.combined) {
+                if (!slots.empty()) break;   // (the blocks in front go first: a block CRC that does not match is named as such)
+                return BZ2_FAIL("end-of-stream marker at byte %llu: combined CRC mismatch", at(Z.bit));
+            }
+            Z.bit = (br.pos() + 7u) & ~7ull;
+            Z.in_stream = false;
+            continue;
+        }
+        if (magic != bz2::kBlockMagic) return BZ2_FAIL("at byte %llu: %s", at(Z.bit), bz2::status_text(bz2::kNoBlock));
+        // a block: decoded in the batch at hand, or first in a new batch (once the blocks of this one are through)
+        while (Z.next_cand < Z.cand.size() && Z.cand[Z.next_cand] < Z.bit) {   // (magics inside the blocks in front: no blocks)
+            ++Z.next_cand;
+            ++Z.false_magics;
+        }
+        if (Z.next_cand >= Z.cand.size() || Z.cand[Z.next_cand] != Z.bit)
+            return fail(c, SLIMM_E_INVALID, "bzip2: the block magic at byte %llu was not found by the device's scan", at(Z.bit));
+        if (Z.next_cand >= batch0 + nb) {
+            if (!slots.empty()) break;
+            const auto t0 = std::chrono::steady_clock::now();
+            batch0 = Z.next_cand;
+            nb = std::min<size_t>(Z.slots, Z.cand.size() - batch0);
+            HIP_TRY(c, hipMemcpyAsync(Z.d_cand.p, Z.cand.data() + batch0, nb * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(k_bz2_decode, dim3(static_cast<uint32_t>(nb)), dim3(64), 0, st, Z.comp.p, end_bit, Z.d_cand.p, Z.ll.p, Z.hist.p,
+                               Z.info.p);
+            HIP_TRY(c, hipGetLastError());
+            hinfo.resize(nb);
+            HIP_TRY(c, hipMemcpyAsync(hinfo.data(), Z.info.p, nb * sizeof(bz2::BlockInfo), hipMemcpyDeviceToHost, st));
+            HIP_TRY(c, hipStreamSynchronize(st));
+            Z.ms_decode += ms_since(t0);
+            ++Z.batches;
+        }
+        const uint32_t s = static_cast<uint32_t>(Z.next_cand - batch0);
+        const bz2::BlockInfo& r = hinfo[s];
+        if (r.status == bz2::kRanOut) {   // (the block's bytes go on with the next push)
+            if (last) return BZ2_FAIL("block at byte %llu: truncated", at(Z.bit));
+            Z.waiting = true;
+            break;
+        }
+        if (r.status != bz2::kOk) return BZ2_FAIL("block at byte %llu: %s", at(Z.bit), bz2::status_text(r.status));
+        if (r.n > Z.level * 100000u) return BZ2_FAIL("block at byte %llu: %s", at(Z.bit), bz2::status_text(bz2::kTooLong));
+        slots.push_back(s);
+        crcs.push_back(r.crc);
+        ats.push_back(at(Z.bit));
+        Z.combined = ((Z.combined << 1) | (Z.combined >> 31)) ^ r.crc;
+        Z.bit = r.end_bit;
+        ++Z.next_cand;
+    }
+    if (slots.empty()) return SLIMM_OK;
+    // the blocks of the chain: inverse BWT, text lengths
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint32_t k = static_cast<uint32_t>(slots.size());
+    HIP_TRY(c, hipMemcpyAsync(Z.text_len.p + Z.slots, slots.data(), k * 4u, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_bz2_unbwt, dim3(k), dim3(256), 0, st, Z.text_len.p + Z.slots, Z.info.p, Z.ll.p, Z.link.p, Z.hist.p, Z.text_len.p);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<uint32_t> len(k);
+    HIP_TRY(c, hipMemcpyAsync(len.data(), Z.text_len.p, k * 4u, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    Z.ms_bwt += ms_since(t0);
+    for (uint32_t i = 0; i < k; ++i) {
+        if (len[i] == ~0u) return BZ2_FAIL("block at byte %llu: %s", static_cast<unsigned long long>(ats[i]), bz2::status_text(bz2::kBadLinks));
+        slimm_ctx::BamDecode::Bzip2::Ready b;
+        b.slot = slots[i];
+        b.crc = crcs[i];
+        b.len = len[i];
+        b.drop = std::min<uint64_t>(Z.skip_left, b.len);
+        Z.skip_left -= b.drop;
+        b.at = ats[i];
+        Z.ready.push_back(b);
+    }
+    Z.blocks += k;
+    return SLIMM_OK;
+}
+
+void bz2_trace_file(const slimm_ctx* c) {
+    if (!traced("push")) return;
+    const slimm_ctx::BamDecode::Bzip2& Z = c->bam.bz2;
+    fprintf(stderr, "[push bzip2] %llu streams, %llu blocks in %llu batches, %llu false magics; find %.1f ms, decode %.1f ms, "
+                    "inverse BWT %.1f ms, text %.1f ms\n", (unsigned long long)Z.streams, (unsigned long long)Z.blocks,
+            (unsigned long long)Z.batches, (unsigned long long)Z.false_magics, Z.ms_find, Z.ms_decode, Z.ms_bwt, Z.ms_emit);
+}
+
+uint64_t bz2_window_bytes(const slimm_ctx* c, uint64_t cap, size_t* n_blocks) {
+    const slimm_ctx::BamDecode::Bzip2& Z = c->bam.bz2;
+    uint64_t n = 0;
+    size_t i = Z.ready_pos;
+    for (; i < Z.ready.size(); ++i) {
+        const uint64_t m = Z.ready[i].len - Z.ready[i].drop;
+        if (i > Z.ready_pos && n + m > cap) break;
+        n += m;
+    }
+    *n_blocks = i - Z.ready_pos;
+    return n;
+}
+
+int bz2_emit(slimm_ctx* c, uint8_t* dst, size_t n_blocks, uint8_t* last_byte) {
+    slimm_ctx::BamDecode::Bzip2& Z = c->bam.bz2;
+    hipStream_t st = c->stream;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<uint32_t> slots(n_blocks);
+    std::vector<int64_t> at(2 * n_blocks);
+    int64_t off = 0;
+    for (size_t i = 0; i < n_blocks; ++i) {
+        const auto& b = Z.ready[Z.ready_pos + i];
+        slots[i] = b.slot;
+        at[2 * i] = off - static_cast<int64_t>(b.drop);
+        at[2 * i + 1] = static_cast<int64_t>(b.drop);
+        off += static_cast<int64_t>(b.len - b.drop);
+    }
+    const uint32_t k = static_cast<uint32_t>(n_blocks);
+    HIP_TRY(c, hipMemcpyAsync(Z.text_len.p + Z.slots, slots.data(), k * 4u, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(Z.out_at.p, at.data(), at.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_bz2_emit, dim3(k), dim3(64), 0, st, Z.text_len.p + Z.slots, Z.ll.p, Z.info.p, Z.out_at.p, dst, Z.text_len.p);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<uint32_t> ok(k);
+    HIP_TRY(c, hipMemcpyAsync(ok.data(), Z.text_len.p, k * 4u, hipMemcpyDeviceToHost, st));
+    if (off) HIP_TRY(c, hipMemcpyAsync(last_byte, dst + off - 1, 1, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    Z.ms_emit += ms_since(t0);
+    for (uint32_t i = 0; i < k; ++i)
+        if (!ok[i]) return BZ2_FAIL("block at byte %llu: %s", static_cast<unsigned long long>(Z.ready[Z.ready_pos + i].at), bz2::status_text(bz2::kBadCrc));
+    Z.ready_pos += n_blocks;
+    return SLIMM_OK;
+}
+
+}  // namespace slimm

@@ -20,6 +20,7 @@
 #include "../../include/slimm_hip.h"
 #include "host_profile.hpp"
 #include "force.h"
+#include "bzip2_block.h"
 #include "kernels.h"
 #include "read_identity.h"
 
@@ -223,8 +224,42 @@ struct slimm_ctx {
         uint64_t head_len = 0;
         DevBuf<BamCarry> first, join;   // (join: the left member's carry, on this member's device)
         DevBuf<unsigned long long> guess;
+        // bzip2 SAM (slimm_push_bzip2_sam_bytes, bzip2_decode.hip).  Host side: the compressed bytes not decoded yet (file
+        // offset `base` on; the next bit to read), the stream being read (its level, combined CRC so far), the decoded bytes
+        // still to skip; the block magics found in them (bit offsets into pend, in order) and the next one to look at.
+        // Device side: pend's copy, the candidates, and per slot of a batch the BWT string -- then its RLE1 text --, the
+        // inverse BWT's links, the byte histogram, what decoding found and the text's length; the blocks of the last batch
+        // decoded and not yet written into a window
+        struct Bzip2 {
+            bool on = false;
+            std::vector<uint8_t> pend;
+            uint64_t base = 0, bit = 0;
+            bool in_stream = false;
+            uint32_t level = 0, combined = 0, streams = 0;
+            uint64_t skip_left = 0;
+            std::vector<uint64_t> cand;
+            size_t next_cand = 0;
+            bool found = false;     // cand holds the magics of pend as it is
+            bool waiting = false;   // the chain stopped for want of bytes: nothing to decode until pend grows
+            uint32_t slots = 0;     // blocks a batch decodes at most (the scratch below holds that many; sized per file)
+            DevBuf<uint8_t> comp, ll;
+            DevBuf<uint32_t> link, hist, count, text_len;
+            DevBuf<unsigned long long> d_cand;
+            DevBuf<bz2::BlockInfo> info;
+            DevBuf<int64_t> out_at;
+            struct Ready {
+                uint32_t slot, crc;
+                uint64_t len, drop;   // text bytes; of them the first `drop` are skipped (the header)
+                uint64_t at;          // file offset of the block (errors)
+            };
+            std::vector<Ready> ready;
+            size_t ready_pos = 0;
+            uint64_t blocks = 0, batches = 0, false_magics = 0;   // (SLIMM_TRACE=push; false_magics: candidates the chain passed over)
+            double ms_find = 0, ms_decode = 0, ms_bwt = 0, ms_emit = 0;
+            uint64_t held() const { return comp.cap + ll.cap + link.cap * 4ull + hist.cap * 4ull + d_cand.cap * 8ull; }
+        } bz2;
         uint64_t held_bytes() const {   // device memory of the window pipeline
-            uint64_t n = pieces.cap * sizeof(BamPiece) + offs.cap * 4ull;
+            uint64_t n = pieces.cap * sizeof(BamPiece) + offs.cap * 4ull + bz2.held();
             for (uint32_t k = 0; k < kBamRing; ++k) n += bytes[k].cap + comp[k].cap + desc[k].cap * sizeof(BgzfBlock);
             for (auto& sc : inflate_scratch) n += sc.cap;
             return n;
@@ -396,6 +431,14 @@ int check_device_errors(slimm_ctx* c, uint32_t err);
 int bam_fetch_q18(slimm_ctx* c);   // windows.hip: the Q18 run counts of the device decoders so far
 // windows.hip: `n` bytes at `src` (on device src_device) as one more window behind the closed file's carry (split.hip)
 int bam_append_window(slimm_ctx* c, const uint8_t* src, int src_device, uint64_t n, bool final, uint64_t& n_rec);
+// bzip2_decode.hip (slimm_push_bzip2_sam_bytes): the next batch of whole blocks of bam.bz2.pend decoded up to their text
+// lengths (bam.bz2.ready; none: the chain waits for more bytes, or the streams have ended); at `last` what is left must
+// end the streams.  Then, window by window: the text bytes of the next ready blocks that fit in `cap` (at least one
+// block), and those written to dst on the context's stream, their CRCs checked, *last_byte = the text's last byte
+int bz2_decode_batch(slimm_ctx* c, bool last);
+uint64_t bz2_window_bytes(const slimm_ctx* c, uint64_t cap, size_t* n_blocks);
+int bz2_emit(slimm_ctx* c, uint8_t* dst, size_t n_blocks, uint8_t* last_byte);
+void bz2_trace_file(const slimm_ctx* c);   // SLIMM_TRACE=push (read at every call): the file's streams, blocks, false magics, times
 
 // Grows one record array to `cap` elements, keeping the `used` elements pushed so far (when the array holds them at all:
 // an array the file's record form does not use is neither allocated nor copied).

@@ -451,7 +451,18 @@ int slimm_reset(slimm_ctx* c) {
         for (auto& sc : c->bam.inflate_scratch) sc.release();
         c->bam.pieces.release();
         c->bam.offs.release();
+        slimm_ctx::BamDecode::Bzip2& Z = c->bam.bz2;
+        Z.comp.release();
+        Z.ll.release();
+        Z.link.release();
+        Z.hist.release();
+        Z.d_cand.release();
     }
+    // (bzip2 SAM: the next file sizes its own decode scratch; what the host held of this one's bytes goes)
+    c->bam.bz2.slots = 0;
+    std::vector<uint8_t>().swap(c->bam.bz2.pend);
+    std::vector<uint64_t>().swap(c->bam.bz2.cand);
+    c->bam.bz2.ready.clear();
     c->has_check = false;
     c->packed = false;
     c->marked = false;

@@ -8,6 +8,8 @@
 //   group_collectives=rccl|copy                                                       tests/test_gpu_group.py
 //   record_cap=N (fewer records per context), split_shift_guess (a mid-file member reports its first record one byte
 //   off: slimm_group_stitch_ranges must refuse the join)                             tests/test_cli_split_input.py
+//   bzip2_false_magics[=N] (block candidates that are no blocks: inside every real one, and every N bits), bzip2_round=N
+//   (bzip2 SAM decoded every N compressed bytes: blocks cut across rounds)          tests/test_gpu_bzip2_sam.py
 #pragma once
 #include <cstdlib>
 #include <cstring>

@@ -1,5 +1,7 @@
 #include "alignment_file.hpp"
 
+#include "bzip2.hpp"
+
 #include <dlfcn.h>
 #include <zlib.h>
 
@@ -172,6 +174,7 @@ void AlignmentFile::close() {
     fp_ = nullptr;
     if (gz_) inflateEnd(gz_.get());
     gz_.reset();
+    bz_.reset();
     workers_.reset();
     inflaters_.reset();
 }
@@ -225,6 +228,8 @@ bool AlignmentFile::open(const std::string& path) {
     comp_ = Compression::None;
     gz_in_.clear();
     gz_in_eof_ = gz_member_open_ = gz_end_ = text_bad_ = false;
+    bz_end_ = bz_raw_started_ = false;
+    bz_raw_pos_ = bz_raw_size_ = 0;
     lead_.clear();
     lead_off_ = 0;
     fp_ = fopen(path.c_str(), "rb");
@@ -252,8 +257,22 @@ bool AlignmentFile::open(const std::string& path) {
     }
     rewind(fp_);
     auto starts = [&](const char* m, size_t n) { return head.size() >= n && memcmp(head.data(), m, n) == 0; };
+    // bzip2: "BZh" + the level, then a block magic or (an empty stream) the end-of-stream magic
+    const bool bzip2 = starts("BZh", 3) && head.size() >= 10 && head[3] >= '1' && head[3] <= '9' &&
+                       (memcmp(&head[4], "\x31\x41\x59\x26\x53\x59", 6) == 0 || memcmp(&head[4], "\x17\x72\x45\x38\x50\x90", 6) == 0);
     bool ok;
-    if (starts("BZh", 3) || starts("\xfd" "7zXZ\0", 6) || starts("\x28\xb5\x2f\xfd", 4)) {
+    if (bzip2) {
+        comp_ = Compression::Bzip2;
+        FILE* fp = fp_;
+        bz_.reset(new Bzip2Reader([fp](uint8_t* d, size_t n) { return fread(d, 1, n, fp); }));
+        ok = refill_text() || !text_bad_;
+        if (ok && buf_.size() >= 4 && memcmp(buf_.data(), "BAM\1", 4) == 0) {
+            err_ = "a bzip2 stream that holds BAM: BAM is read from BGZF blocks only: " + path;
+            ok = false;
+        }
+        if (ok) ok = read_sam_header();
+        if (!ok && text_bad_) err_ += ": " + path;
+    } else if (starts("BZh", 3) || starts("\xfd" "7zXZ\0", 6) || starts("\x28\xb5\x2f\xfd", 4)) {
         err_ = std::string(starts("BZh", 3) ? "bzip2" : starts("\x28", 1) ? "zstd" : "xz") + "-compressed input is not supported (SAM / BAM, "
                "BGZF or gzip): " + path;
         ok = false;
@@ -557,8 +576,9 @@ bool AlignmentFile::refill_text() {
         return true;
     }
     buf_.resize(1 << 20);
-    const long got = comp_ == Compression::Gzip ? gz_read(buf_.data(), buf_.size())
-                                                : static_cast<long>(fread(buf_.data(), 1, buf_.size(), fp_));
+    const long got = comp_ == Compression::Gzip    ? gz_read(buf_.data(), buf_.size())
+                     : comp_ == Compression::Bzip2 ? bz_read(buf_.data(), buf_.size())
+                                                   : static_cast<long>(fread(buf_.data(), 1, buf_.size(), fp_));
     buf_.resize(got > 0 ? static_cast<size_t>(got) : 0u);
     pos_ = 0;
     sam_buf_off_ = consumed;
@@ -606,6 +626,20 @@ long AlignmentFile::gz_read(uint8_t* dst, size_t cap) {
         return -1;
     }
     return static_cast<long>(out);
+}
+
+// bzip2 (streams back to back, blocks decoded in order on the calling thread: host/bzip2.cpp), up to `cap` bytes.  0 at
+// the end, -1 + err_ -- which keeps the words of the reader that did not decode bzip2 at all, and says why this did not.
+long AlignmentFile::bz_read(uint8_t* dst, size_t cap) {
+    if (text_bad_) return -1;
+    const long n = bz_->read(dst, cap);
+    if (n < 0) {
+        err_ = "bzip2-compressed input is not supported unless it decodes: " + bz_->error();
+        text_bad_ = true;
+    } else if (n == 0) {
+        bz_end_ = true;
+    }
+    return n;
 }
 
 // Compressed SAM: what the header parse has inflated already -- the first alignment line as it stood, then the rest of
@@ -689,7 +723,7 @@ bool AlignmentFile::read_sam_header() {
             ref_len_.push_back(len);
         }
     }
-    if (comp_ == Compression::Bgzf) header_bytes_ = sam_body_off_;
+    if (comp_ == Compression::Bgzf || comp_ == Compression::Bzip2) header_bytes_ = sam_body_off_;
     return true;
 }
 
@@ -1044,17 +1078,48 @@ long AlignmentFile::read_blocks(uint8_t* dst, size_t cap, size_t max_inflated, s
     return static_cast<long>(out);
 }
 
+long AlignmentFile::read_compressed(uint8_t* dst, size_t cap) {
+    if (comp_ != Compression::Bzip2 || !fp_ || !dst) {
+        err_ = "read_compressed: a bzip2 SAM file";
+        return -1;
+    }
+    const int fd = fileno(fp_);
+    if (!bz_raw_started_) {
+        struct stat sb;
+        if (fstat(fd, &sb) != 0) {
+            err_ = "read_compressed: fstat failed";
+            return -1;
+        }
+        bz_raw_size_ = static_cast<size_t>(sb.st_size);
+        bz_raw_started_ = true;
+    }
+    StageClock clk(ms_read_);
+    size_t out = 0;
+    const size_t want = std::min(cap, bz_raw_size_ - bz_raw_pos_);
+    while (out < want) {
+        const ssize_t got = pread(fd, dst + out, want - out, static_cast<off_t>(bz_raw_pos_ + out));
+        if (got <= 0) {
+            err_ = "truncated bzip2 stream (the file shrank while it was read)";
+            return -1;
+        }
+        out += static_cast<size_t>(got);
+    }
+    bz_raw_pos_ += out;
+    if (out) ++n_windows_;
+    return static_cast<long>(out);
+}
+
 long AlignmentFile::read_text(uint8_t* dst, size_t cap) {
     if (bam_ || comp_ == Compression::Bgzf || !fp_ || !dst || cap < (1u << 16)) {
         err_ = "read_text: a SAM file (plain or gzip) and a buffer of at least 64 KiB";
         return -1;
     }
-    if (comp_ == Compression::Gzip) {   // (on the caller's thread: the command's reader thread, beside the device's work)
+    if (comp_ == Compression::Gzip || comp_ == Compression::Bzip2) {   // (on the caller's thread: the command's reader thread, beside the device's work)
         StageClock clk(ms_inflate_);
         sam_text_started_ = true;
         size_t out = take_lead(dst, cap);
         if (out < cap) {
-            const long n = gz_read(dst + out, cap - out);
+            const long n = comp_ == Compression::Gzip ? gz_read(dst + out, cap - out) : bz_read(dst + out, cap - out);
             if (n < 0) return -1;
             out += static_cast<size_t>(n);
         }

@@ -44,9 +44,11 @@ struct RecordBatch {
 };
 
 enum class SortOrder { Unknown, Unsorted, QueryName, Coordinate, QueryGrouped };
-// How the file's bytes are stored: as they are, in BGZF blocks (BAM, or SAM text from bgzip), or as one plain gzip stream of
-// one or more members (SAM text from gzip)
-enum class Compression { None, Bgzf, Gzip };
+// How the file's bytes are stored: as they are, in BGZF blocks (BAM, or SAM text from bgzip), as one plain gzip stream of
+// one or more members (SAM text from gzip), or as bzip2 streams back to back (SAM text from bzip2 / pbzip2 / lbzip2)
+enum class Compression { None, Bgzf, Gzip, Bzip2 };
+
+class Bzip2Reader;   // (bzip2.hpp)
 
 // 62-bit identity of a read name.  The reader makes it exact where grouped input needs it to be: a record whose name
 // differs from its predecessor's never gets the predecessor's key (separate_adjacent_names).  Names colliding far
@@ -83,7 +85,8 @@ public:
     const std::vector<std::string>& ref_names() const { return ref_names_; }
     const std::vector<uint32_t>& ref_lengths() const { return ref_len_; }
     SortOrder sort_order() const { return order_; }
-    // BAM / BGZF SAM: the header's inflated bytes -- where the first alignment record (line) starts in the inflated stream
+    // BAM / BGZF SAM / bzip2 SAM: the header's inflated bytes -- where the first alignment record (line) starts in the
+    // inflated (decoded) stream
     uint64_t header_bytes() const { return header_bytes_; }
     // Q18 on a file grouped by QNAME (include/slimm_hip.h, "Q18 ON A GROUPED STREAM"): among the records read_batch /
     // read_into have handed out, some run of adjacent records with one canonical base holds SHORTENED names only -- their
@@ -115,10 +118,16 @@ public:
     // SAM goes through read_raw / read_blocks.)
     long read_text(uint8_t* dst, size_t cap);
     bool can_read_text() const { return !bam_ && comp_ != Compression::Bgzf && fp_ != nullptr; }
+    // bzip2 SAM: the file's bytes as they lie in it, from its first byte on, window by window (for
+    // slimm_push_bzip2_sam_bytes: the device decodes the blocks; the header's header_bytes() decoded bytes are skipped
+    // there).  Read by pread, beside whatever read_text read.  Returns the bytes written, 0 at the end, -1 + error().
+    long read_compressed(uint8_t* dst, size_t cap);
+    bool compressed_exhausted() const { return bz_raw_pos_ >= bz_raw_size_ && bz_raw_started_; }
     bool regular_file() const;   // (read_text and the mapped reads want one; a pipe or a device goes through the buffered reads)
     // after a read_raw that returned bytes: nothing will follow them (false may also mean "not known yet")
     bool raw_exhausted() const {
         if (comp_ == Compression::Gzip) return gz_end_ && lead_off_ >= lead_.size() && pos_ >= buf_.size();
+        if (comp_ == Compression::Bzip2) return bz_end_ && lead_off_ >= lead_.size() && pos_ >= buf_.size();
         return raw_stage_ == 2 ? eof_ : (raw_stage_ == 1 && eof_ && raw_off_ >= spare_.size());
     }
 
@@ -148,6 +157,7 @@ private:
     bool next_sam_line(std::string& line);
     bool refill_text();       // the next stretch of SAM text into buf_ (false: its end, or an error in err_)
     long gz_read(uint8_t* dst, size_t cap);   // plain gzip: the next inflated bytes of the stream (0 at its end, -1 + err_)
+    long bz_read(uint8_t* dst, size_t cap);   // bzip2: the next decoded bytes of the streams (0 at their end, -1 + err_)
     size_t take_lead(uint8_t* dst, size_t cap);   // compressed SAM: the first alignment line and the rest of buf_, once
     void parse_hd_line(const std::string& line);
 
@@ -158,6 +168,10 @@ private:
     std::unique_ptr<::z_stream_s> gz_;
     std::vector<uint8_t> gz_in_;
     bool gz_in_eof_ = false, gz_member_open_ = false, gz_end_ = false;
+    // bzip2: the host decoder, the end of its streams; read_compressed's file position and the file's size
+    std::unique_ptr<Bzip2Reader> bz_;
+    bool bz_end_ = false, bz_raw_started_ = false;
+    size_t bz_raw_pos_ = 0, bz_raw_size_ = 0;
     bool text_bad_ = false;   // compressed SAM: the text ran into a format error (err_); the reader's answer from then on
     // compressed SAM: the first alignment line as it stands in the text (the header parse took it out of buf_), handed out
     // in front of the rest by read_text / read_raw; line_cr_ / line_nl_: the last line next_sam_line read ended with CR LF / LF

@@ -120,6 +120,7 @@ SLIMM_FORWARD(int, slimm_push_records_packed, (slimm_ctx* a, const uint64_t* b, 
 SLIMM_FORWARD(int, slimm_push_bam_bytes, (slimm_ctx* a, const uint8_t* b, uint64_t c, int d, uint64_t* e), (a, b, c, d, e))
 SLIMM_FORWARD(int, slimm_push_bgzf_blocks, (slimm_ctx* a, const uint8_t* b, uint64_t c, uint32_t s, int d, uint64_t* e), (a, b, c, s, d, e))
 SLIMM_FORWARD(int, slimm_push_bgzf_sam_blocks, (slimm_ctx* a, const uint8_t* b, uint64_t c, uint32_t s, int d, uint64_t* e), (a, b, c, s, d, e))
+SLIMM_FORWARD(int, slimm_push_bzip2_sam_bytes, (slimm_ctx* a, const uint8_t* b, uint64_t c, uint32_t s, int d, uint64_t* e), (a, b, c, s, d, e))
 SLIMM_FORWARD(int, slimm_pin_host_buffer, (slimm_ctx* a, const void* b, uint64_t c), (a, b, c))
 SLIMM_FORWARD(int, slimm_host_bgzf_ranges, (const char* a, uint64_t b, uint32_t c, uint64_t* d), (a, b, c, d))
 SLIMM_FORWARD(int, slimm_set_input_mid_file, (slimm_ctx* a, int b, int c), (a, b, c))
@@ -380,8 +381,8 @@ int dump_raw(const Options& o) {
     const size_t cap = static_cast<size_t>(std::max(1u, o.window_mb)) << 20;
     std::vector<uint8_t> buf(cap);
     long n;
-    const bool gzip = f.compression() == Compression::Gzip;
-    while ((n = gzip ? f.read_text(buf.data(), cap) : f.read_raw(buf.data(), cap)) > 0) {
+    const bool text = f.compression() == Compression::Gzip || f.compression() == Compression::Bzip2;
+    while ((n = text ? f.read_text(buf.data(), cap) : f.read_raw(buf.data(), cap)) > 0) {
         std::cerr << "window\t" << n << "\t" << (f.raw_exhausted() ? "last" : "more") << "\n";
         if (fwrite(buf.data(), 1, static_cast<size_t>(n), stdout) != static_cast<size_t>(n)) return 1;
     }
@@ -629,7 +630,7 @@ struct RecordPump {
     // the inflater of the device-decode mode: fills the window buffers in turn.  BGZF files -- BAM, or SAM text -- alike:
     // windows the host inflates (read_raw) and, every device_period-th of those read in place, whole blocks (read_blocks)
     void run_raw() {
-        const bool bgzf = bam.compression() == Compression::Bgzf;
+        const bool bgzf = bam.compression() == Compression::Bgzf, bzip2 = bam.compression() == Compression::Bzip2;
         for (unsigned w = 0;; w = (w + 1) % kRawBuffers) {
             {
                 std::unique_lock<std::mutex> g(mu);
@@ -648,7 +649,11 @@ struct RecordPump {
             // (every device_period-th of the windows read in place)
             bool compressed = false;
             long n;
-            if (bam.can_read_text()) {   // SAM, plain or gzip: the text (slimm_push_sam_bytes finds and decodes the lines)
+            if (bzip2) {   // bzip2 SAM: the file's bytes as they lie in it (slimm_push_bzip2_sam_bytes decodes the blocks)
+                n = bam.read_compressed(raw_buf[w].get(), raw_cap());
+                compressed = true;
+                ++raw_windows_device;
+            } else if (bam.can_read_text()) {   // SAM, plain or gzip: the text (slimm_push_sam_bytes finds and decodes the lines)
                 n = bam.read_text(raw_buf[w].get(), raw_cap());
                 ++raw_windows_device;
             } else if (device_period && bam.can_read_blocks() && (raw_windows_device + raw_windows_host) % device_period == device_period - 1u) {
@@ -663,7 +668,7 @@ struct RecordPump {
             decode_ms += ms(t1, std::chrono::steady_clock::now());
             {
                 std::lock_guard<std::mutex> g(mu);
-                raw_ready.push_back(RawWindow{w, n, n > 0 && bgzf && bam.raw_exhausted(), compressed});
+                raw_ready.push_back(RawWindow{w, n, n > 0 && ((bgzf && bam.raw_exhausted()) || (bzip2 && bam.compressed_exhausted())), compressed});
             }
             cv.notify_all();
             if (n <= 0) {
@@ -677,7 +682,9 @@ struct RecordPump {
         bool pinned[kRawBuffers] = {};
         bool closed = false;  // a window went out as the file's last
         bool in_flight = false;  // the window pushed last is still being copied out of its buffer
-        const bool text = !bam.is_bam();
+        const bool text = !bam.is_bam(), bzip2 = bam.compression() == Compression::Bzip2;
+        // (bzip2 SAM goes from the file's first byte: the first push skips the header's decoded bytes)
+        uint32_t skip = bzip2 ? static_cast<uint32_t>(bam.header_bytes()) : 0u;
         if (text) {   // SAM text names its references: the header's names for the device's look-up
             std::vector<const char*> names;
             for (const std::string& nm : bam.ref_names()) names.push_back(nm.c_str());
@@ -711,12 +718,15 @@ struct RecordPump {
                 const uint8_t* p = raw_buf[w.which].get();
                 const uint64_t n = static_cast<uint64_t>(w.n);
                 const int last = w.last ? 1 : 0;
-                rc = w.compressed ? (text ? slimm_push_bgzf_sam_blocks(c, p, n, 0u, last, &got) : slimm_push_bgzf_blocks(c, p, n, 0u, last, &got))
-                                  : (text ? slimm_push_sam_bytes(c, p, n, last, &got) : slimm_push_bam_bytes(c, p, n, last, &got));
+                rc = bzip2          ? slimm_push_bzip2_sam_bytes(c, p, n, skip, last, &got)
+                     : w.compressed ? (text ? slimm_push_bgzf_sam_blocks(c, p, n, 0u, last, &got) : slimm_push_bgzf_blocks(c, p, n, 0u, last, &got))
+                                    : (text ? slimm_push_sam_bytes(c, p, n, last, &got) : slimm_push_bam_bytes(c, p, n, last, &got));
+                skip = 0;
                 closed = w.last;
             } else if (!closed) {
-                rc = text ? slimm_push_sam_bytes(c, nullptr, 0, 1, &got)
-                          : slimm_push_bam_bytes(c, nullptr, 0, 1, &got);  // (the end came without notice: an incomplete record is an error)
+                rc = bzip2  ? slimm_push_bzip2_sam_bytes(c, nullptr, 0, skip, 1, &got)
+                     : text ? slimm_push_sam_bytes(c, nullptr, 0, 1, &got)
+                            : slimm_push_bam_bytes(c, nullptr, 0, 1, &got);  // (the end came without notice: an incomplete record is an error)
             }
             raw_push_ms += ms(t1, std::chrono::steady_clock::now());
             raw_records += got;

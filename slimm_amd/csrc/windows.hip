@@ -185,7 +185,10 @@ int slimm_set_input_mid_file(slimm_ctx* c, int starts_mid_file, int ends_mid_fil
 }
 
 namespace {
-enum { kFormatBam = 0, kFormatBgzf = 1, kFormatSam = 2, kFormatBgzfSam = 3 };
+enum { kFormatBam = 0, kFormatBgzf = 1, kFormatSam = 2, kFormatBgzfSam = 3, kFormatBzip2Sam = 4 };
+// bzip2 SAM: compressed bytes gathered on the host before their blocks are looked for and decoded (a round; the command's
+// pushes are larger, the ABI's may be of any size)
+constexpr uint64_t kBzip2Round = 32ull << 20;
 int bam_push_window(slimm_ctx* c, const uint8_t* bytes, uint64_t n_bytes, int format, uint32_t skip, int last, uint64_t* n_records);
 }
 int slimm_set_input_size_hint(slimm_ctx* c, uint64_t compressed_bytes) {
@@ -220,6 +223,9 @@ int slimm_push_sam_bytes(slimm_ctx* c, const uint8_t* text, uint64_t n_bytes, in
 }
 int slimm_push_bgzf_sam_blocks(slimm_ctx* c, const uint8_t* blocks, uint64_t n_bytes, uint32_t skip, int last, uint64_t* n_records) {
     return bam_push_window(c, blocks, n_bytes, kFormatBgzfSam, skip, last, n_records);
+}
+int slimm_push_bzip2_sam_bytes(slimm_ctx* c, const uint8_t* bytes, uint64_t n_bytes, uint32_t skip, int last, uint64_t* n_records) {
+    return bam_push_window(c, bytes, n_bytes, kFormatBzip2Sam, skip, last, n_records);
 }
 // The header's reference names (@SQ SN, index = the reference id) for slimm_push_sam_bytes: a hash table on the device.
 int slimm_set_reference_names(slimm_ctx* c, const char* const* names) {
@@ -359,6 +365,23 @@ int bam_launch_gathered(slimm_ctx* c) {
     return SLIMM_OK;
 }
 
+// the oldest windows finished while more than kBamLag windows (or kBamInFlight bytes) are in flight; their records added to total
+int bam_finish_lagging(slimm_ctx* c, uint64_t& total) {
+    slimm_ctx::BamDecode& B = c->bam;
+    for (;;) {
+        if (B.head >= B.windows) return SLIMM_OK;
+        uint64_t in_flight = 0;
+        for (uint64_t j = B.head; j < B.windows; ++j) in_flight += B.win_bytes[j % slimm_ctx::kBamRing];
+        if (B.windows - B.head <= slimm_ctx::kBamLag && in_flight <= slimm_ctx::kBamInFlight) return SLIMM_OK;
+        uint64_t got = 0;
+        const uint64_t j = B.head;
+        const int rc = bam_finish_window(c, j, B.win_bytes[j % slimm_ctx::kBamRing], false, got);
+        ++B.head;
+        if (rc != SLIMM_OK) return rc;
+        total += got;
+    }
+}
+
 // A window of a BAM file's alignment-record bytes: inflated already (`bytes` are the records' bytes) or as whole BGZF blocks
 // (`bytes` are compressed; the first `skip` inflated bytes are not records).  src_bytes = what crosses the bus.
 // BGZF pushes are GATHERED: their compressed bytes are copied behind each other into the next window's buffer, and the window
@@ -369,9 +392,13 @@ int bam_push_window(slimm_ctx* c, const uint8_t* bytes, uint64_t src_bytes, int 
     if (!c) return SLIMM_E_INVALID;
     if (n_records) *n_records = 0;
     bool compressed = format == kFormatBgzf || format == kFormatBgzfSam;
-    const bool sam = format == kFormatSam || format == kFormatBgzfSam;
+    const bool sam = format == kFormatSam || format == kFormatBgzfSam || format == kFormatBzip2Sam;
+    const bool bzip2 = format == kFormatBzip2Sam;
     if (sam && !c->bam.sam_mask) return fail(c, SLIMM_E_INVALID, "slimm_set_reference_names first: SAM text names its references");
     if (c->bam.active && c->bam.sam != sam) return fail(c, SLIMM_E_INVALID, "SAM text and BAM bytes do not mix within a file");
+    if (c->bam.active && c->bam.bz2.on != bzip2)
+        return fail(c, SLIMM_E_INVALID, "bzip2 SAM bytes and the other forms do not mix within a file");
+    if (bzip2 && skip && c->bam.active) return fail(c, SLIMM_E_INVALID, "skip: only in front of a file's first records");
     uint64_t n_bytes = src_bytes;  // the push's record bytes
     std::vector<BgzfBlock> dh;
     uint64_t inflated = 0;
@@ -425,6 +452,18 @@ int bam_push_window(slimm_ctx* c, const uint8_t* bytes, uint64_t src_bytes, int 
         B.planned = false;
         B.sam_last_byte = '\n';
         B.sam_dev_tail = false;
+        B.bz2.on = bzip2;
+        B.bz2.pend.clear();
+        B.bz2.base = B.bz2.bit = 0;
+        B.bz2.in_stream = B.bz2.found = false;
+        B.bz2.streams = B.bz2.combined = 0;
+        B.bz2.skip_left = bzip2 ? skip : 0u;
+        B.bz2.ready.clear();
+        B.bz2.ready_pos = 0;
+        B.bz2.blocks = B.bz2.batches = B.bz2.false_magics = 0;
+        B.bz2.slots = 0;   // (the decode scratch is sized for each file at its first decode: bz2_reserve)
+        B.bz2.waiting = false;
+        B.bz2.ms_find = B.bz2.ms_decode = B.bz2.ms_bwt = B.bz2.ms_emit = 0;
         B.found_start = B.has_first = B.q18_by_group = false;
         B.head_len = 0;
         c->marked = marked;
@@ -442,7 +481,54 @@ int bam_push_window(slimm_ctx* c, const uint8_t* bytes, uint64_t src_bytes, int 
     uint64_t total = 0;
     bool copy_started = false;
     push_trace("push: %.0f MB %s -> %.0f MB%s", src_bytes / 1e6, compressed ? "of blocks" : "inflated", n_bytes / 1e6, last ? " (last)" : "");
-    if (n_bytes && compressed) {
+    if (bzip2) {
+        // bzip2: the bytes wait on the host until a round's worth has come (or the file ends); then the blocks are decoded
+        // batch by batch (bzip2_decode.hip), and each batch's text becomes windows of its own
+        if (n_bytes) {
+            B.bz2.pend.insert(B.bz2.pend.end(), bytes, bytes + n_bytes);
+            B.bz2.found = B.bz2.waiting = false;
+        }
+        long round = 0;   // (SLIMM_FORCE bzip2_round=N: rounds of N bytes -- tests cut blocks across rounds with small files)
+        if (!forced("bzip2_round", &round) || round <= 0) round = static_cast<long>(kBzip2Round);
+        if (last || B.bz2.pend.size() - (B.bz2.bit >> 3) >= static_cast<uint64_t>(round)) {
+            for (;;) {
+                int rc = bz2_decode_batch(c, last != 0);
+                if (rc != SLIMM_OK) return rc;
+                if (B.bz2.ready.empty()) break;
+                while (B.bz2.ready_pos < B.bz2.ready.size()) {
+                    size_t nblk = 0;
+                    const uint64_t n = bz2_window_bytes(c, slimm_ctx::kBamGather, &nblk);
+                    rc = bam_window_buffer(c, n + 1u);
+                    if (rc != SLIMM_OK) return rc;
+                    const uint32_t b = static_cast<uint32_t>(B.windows % slimm_ctx::kBamRing);
+                    uint8_t lb = '\n';
+                    rc = bz2_emit(c, B.bytes[b].p + kBamSlack, nblk, &lb);
+                    if (rc != SLIMM_OK) return rc;
+                    if (!n) continue;   // (blocks of header only)
+                    B.sam_last_byte = lb;
+                    B.inflated[b] = false;
+                    HIP_TRY(c, hipEventRecord(B.copied[b], st));
+                    B.win_bytes[b] = n;
+                    ++B.windows;
+                    push_trace("window %llu: %zu bzip2 blocks -> %.1f MB of text", (unsigned long long)(B.windows - 1), nblk, n / 1e6);
+                    rc = bam_finish_lagging(c, total);
+                    if (rc != SLIMM_OK) return rc;
+                }
+            }
+        }
+        if (last && B.sam_last_byte != '\n') {   // (a last line without its newline gets one, in a window of its own)
+            int rc = bam_window_buffer(c, 1u);
+            if (rc != SLIMM_OK) return rc;
+            const uint32_t b = static_cast<uint32_t>(B.windows % slimm_ctx::kBamRing);
+            HIP_TRY(c, hipMemsetAsync(B.bytes[b].p + kBamSlack, '\n', 1, st));
+            HIP_TRY(c, hipEventRecord(B.copied[b], st));
+            B.inflated[b] = false;
+            B.win_bytes[b] = 1;
+            ++B.windows;
+            B.sam_last_byte = '\n';
+        }
+        if (last) bz2_trace_file(c);
+    } else if (n_bytes && compressed) {
         // behind what is gathered already -- unless the window would grow past its size: that one goes first
         if (B.acc_open && B.acc_dst + inflated > slimm_ctx::kBamGather) {
             const int rc = bam_launch_gathered(c);
