@@ -20,7 +20,10 @@ s = Slimm.for_workload(w, device=0)
 lib = ctypes.CDLL(os.environ["SLIMM_HIP_LIB"])
 n = 8 * 4096
 buf = (ctypes.c_ulonglong * n)()
-names = {"8": ["prologue", "clear", "lds count", "cursor atomics", "scan", "stage", "store", "kernel"],
+# (EXP 8, the slots of k_tile_scatter_big: 2 = the LDS adds that count and rank, 3 = reservations + scan + offsets written,
+#  4 = the values into the stage, 1 = the wait for the reservations + the second table, 5 = the next round's values asked
+#  for (the walk over the slots) + the barrier, 6 = write-out + the first table cleared)
+names = {"8": ["prologue", "reservations back", "count+rank", "reserve+scan", "stage", "next loads", "store", "kernel"],
          "9": ["-", "item+clear", "count", "barrier", "stats", "store", "-", "kernel"]}[os.environ.get("TPROF_EXP", "8")]
 for it in range(4):
     s.reset(); s.reset_cutoffs(); s.set_records_device(key, ref, pos, flag)

@@ -714,11 +714,12 @@ __global__ __launch_bounds__(kTBlock) void k_tile_scatter(const uint32_t* __rest
 // The direct rounds (k_tile_scatter) store every 2-byte entry from a register: one L2 write request per value, 617 M at
 // 1 B records -- about what the L2's channels take in the kernel's 2.4 ms -- beside one returning atomic per touched
 // tile and round of 16 K values.  Here a workgroup of kBigBlock threads (the ONE of its CU: the LDS is its own) takes
-// rounds of kBigBlock x kBigPieces values, and ONE table of a word per tile serves in turn as the round's histogram,
-// as the tiles' cursors inside the stage (placement: a returning add), and as "global position of the tile's
-// run minus its offset in the stage" (write-out: consecutive lanes store consecutive bucket positions of one
-// tile -- a request per run, not per value).  Thread t owns tiles t, t + kBigBlock, ...: their counts, their reservations
-// (in registers between the steps) and their runs' places in the stage -- thread-major, so that the scan is over threads.
+// rounds of kBigBlock x kBigPieces values.  A table of a word per tile is the round's histogram -- the add that
+// counts a value returns its rank inside its tile -- and then the tiles' offsets in the stage (placement: offset + rank,
+// a plain read); a second one holds "global position of the tile's run minus its offset in the stage" (write-out:
+// consecutive lanes store consecutive bucket positions of one tile -- a request per run, not per value).  Thread t owns
+// tiles t, t + kBigBlock, ...: their counts, their reservations (in registers between the steps) and their runs' places
+// in the stage -- thread-major, so that the scan is over threads.
 // Same slot ranges and counter copies as k_tile_count (same grid, same fold): copy = blockIdx.x % reps, and the
 // workgroups of a copy share an XCD (blockIdx.x % 8) like the frontiers they append to.
 // ---------------------------------------------------------------------------------------------------------
@@ -738,66 +739,85 @@ __global__ __launch_bounds__(kBigBlock) void k_tile_scatter_big(const uint32_t* 
                                                                 uint32_t* __restrict__ ucov,
                                                                 const uint32_t* __restrict__ rep_base_all, uint32_t reps,
                                                                 uint32_t rep_stride, uint32_t tile_sub) {
-    // s_tab[kE * kBigBlock] | 64 more entries, nobody's tiles: where a lane's "no value" counts | s_stage[kBigRound] | 64
-    // more words, where a lane's "no value" is put -- the rounds' LDS operations are issued unconditionally, batch after
-    // batch (a value behind `if (there is one)` is a branch, and a returning LDS atomic inside a branch is waited for
-    // inside it).  An entry per LANE: lanes without a value (behind a slot's short last piece: up to a fifth of a round's
-    // before piece_load_packed) would meet in one shared entry and take it one after the other -- measured: 3 x slower.
+    // s_tab[kE * kBigBlock] | 64 more entries, nobody's tiles: where a lane's "no value" counts | s_dst, as large |
+    // s_stage[kBigRound] | 64 more words, where a lane's "no value" is put -- the rounds' LDS operations are issued
+    // unconditionally, batch after batch (a value behind `if (there is one)` is a branch, and a returning LDS atomic inside
+    // a branch is waited for inside it).  An entry per LANE: lanes without a value (behind a slot's short last piece: up to
+    // a fifth of a round's before piece_load_packed) would meet in one shared entry and take it one after the other --
+    // measured: 3 x slower.
+    //
+    // A round: ONE LDS atomic per value -- the histogram's add returns the value's rank inside its tile (two 16-bit ranks
+    // to a register) -- and a plain read of the tile's offset when the value goes into the stage.  Two tables: s_tab holds
+    // the round's counts, then the tiles' offsets in the stage; s_dst "where the tile's run goes, minus where it lies in
+    // the stage".  s_dst is written behind the staging without a barrier between (nobody reads it before the write-out),
+    // and s_tab is cleared for the next round by the write-out, which no longer reads it: five barriers a round.
     HIP_DYNAMIC_SHARED(uint32_t, s_dyn)
     __shared__ uint32_t s_more[kBigBlock / 64], s_wtot[kBigBlock / 64];
     constexpr uint32_t kNoTile = kE * kBigBlock;
+    static_assert(kBigPieces * (kBigBlock / 64) < 65536 && kBigRound < 65536, "ranks are packed as 16-bit halves");
     uint32_t* const s_tab = s_dyn;
-    uint32_t* const s_stage = s_dyn + kNoTile + 64;
+    uint32_t* const s_dst = s_dyn + kNoTile + 64;
+    uint32_t* const s_stage = s_dst + kNoTile + 64;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    if (tid < 64u) s_tab[kNoTile + tid] = 0u;
     const uint32_t no_tile = kNoTile + lane;
     const size_t rep_off = static_cast<size_t>(blockIdx.x % reps) * rep_stride;
     uint32_t* __restrict__ tile_cursor = tile_cursor_all + rep_off;
     const uint32_t* __restrict__ rep_base = rep_base_all + rep_off;
+    uint32_t at[kE];  // where this copy's stretch of my tiles' buckets begins
+#pragma unroll
+    for (int u = 0; u < kE; ++u) {
+        const uint32_t i = u * kBigBlock + tid;
+        at[u] = rep_base[i < ntiles ? i : 0u];
+    }
     TPROF_T(q0);
     if (tid < kTBlock) zero_split_tiles(tile_base, ntiles, cov, ucov, tile_sub);
     SlotWalk walk = slot_walk(slots, nslots, per_read != 0, kCountFold);
-    // (a round's values are asked for while the round before it leaves: step 3 is the last to read them)
+    // (a round's values are asked for while the round before it leaves: the staging is the last to read them)
     uint32_t v[kBigPieces];
     bool mine = round_load<kBigPieces, true>(walk, vals, lane, v);
+    if (lane == 0u) s_more[wave] = mine ? 1u : 0u;
+#pragma unroll
+    for (int u = 0; u < kE; ++u) s_tab[u * kBigBlock + tid] = 0u;
+    if (tid < 64u) s_tab[kNoTile + tid] = 0u, s_dst[kNoTile + tid] = 0u;
+    __syncthreads();
     TPROF_T(q1);
     if (wave < 8u) TPROF_ADD(0, q0, q1);
     while (true) {
-        TPROF_T(p0);
-        if (lane == 0u) s_more[wave] = mine ? 1u : 0u;
-#pragma unroll
-        for (int u = 0; u < kE; ++u) s_tab[u * kBigBlock + tid] = 0u;
-        __syncthreads();
+        TPROF_T(p1);
         uint32_t any = 0;
 #pragma unroll
         for (int w = 0; w < kBigBlock / 64; ++w) any |= s_more[w];
         if (!any) break;
-        TPROF_T(p1);
-        if (wave < 8u) TPROF_ADD(1, p0, p1);
-        // 1. the round's histogram
+        // 1. the round's histogram; what the add returns is the value's rank among its tile's values of this round
+        uint32_t r2[kBigPieces / 2];
 #pragma unroll
-        for (int k = 0; k < kBigPieces; ++k) atomicAdd(&s_tab[v[k] != 0xffffffffu ? tile_of(v[k]) : no_tile], 1u);
+        for (int k0 = 0; k0 < kBigPieces; k0 += 8) {
+            uint32_t r[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) r[k] = atomicAdd(&s_tab[v[k0 + k] != 0xffffffffu ? tile_of(v[k0 + k]) : no_tile], 1u);
+#pragma unroll
+            for (int k = 0; k < 8; k += 2) r2[(k0 + k) / 2] = r[k] | (r[k + 1] << 16);
+            __builtin_amdgcn_sched_barrier(0);  // (all the round's adds issued first: 24 live results, and spills)
+        }
         __syncthreads();
         TPROF_T(p2);
         if (wave < 8u) TPROF_ADD(2, p1, p2);
         // 2. my tiles: their stretch of the bucket for this round (one returning atomic per touched tile, all of a
-        // thread's under way during the scan), their offsets in the stage
+        // thread's under way during the scan and the staging), their offsets in the stage
         // (Nothing but the atomic inside its condition, and no use of the result before step 4: "h ? atomicAdd() + base : 0"
         // is a branch with a wait at its end per tile -- the thread's reservations one round trip after the other.)
-        uint32_t got[kE], at[kE], sum = 0;
+        uint32_t got[kE], sum = 0;
         {
             uint32_t h[kE];
-#pragma unroll
-            for (int u = 0; u < kE; ++u) {
-                const uint32_t i = u * kBigBlock + tid;
-                at[u] = rep_base[i < ntiles ? i : 0u];
-            }
+            // (the base taken anew every round -- `any` is 1 here -- so that the six addresses are a uniform base and the
+            // lane's offset: kept over the rounds as 64-bit values they were spilled, with a wait before every atomic)
+            uint32_t* __restrict__ cursor = tile_cursor + (any >> 1);
 #pragma unroll
             for (int u = 0; u < kE; ++u) {
                 const uint32_t i = u * kBigBlock + tid;
                 h[u] = s_tab[i];
                 got[u] = 0u;
-                if (h[u] && i < ntiles) got[u] = atomicAdd(&tile_cursor[i], h[u]);
+                if (h[u] && i < ntiles) got[u] = atomicAdd(&cursor[i], h[u]);
                 sum += h[u];
             }
             uint32_t inc = sum;
@@ -813,52 +833,50 @@ __global__ __launch_bounds__(kBigBlock) void k_tile_scatter_big(const uint32_t* 
 #pragma unroll
             for (int w = 0; w < kBigBlock / 64; ++w)
                 if (w < static_cast<int>(wave)) run += s_wtot[w];
-            sum = run;  // my first tile's offset in the stage
 #pragma unroll
             for (int u = 0; u < kE; ++u) {
                 s_tab[u * kBigBlock + tid] = run;
+                s_dst[u * kBigBlock + tid] = at[u] - run;  // (but for the reservation, which step 4 adds: my own word)
                 run += h[u];
             }
         }
         uint32_t total = 0;
 #pragma unroll
         for (int w = 0; w < kBigBlock / 64; ++w) total += s_wtot[w];
+        if (tid < 64u) s_tab[kNoTile + tid] = 0u;  // (the ranks of "no value" stay small: they share a register in pairs)
         __syncthreads();
         TPROF_T(p3);
         if (wave < 8u) TPROF_ADD(3, p2, p3);
-        // 3. the values into the stage, tile after tile: a value's place is what its tile's offset was when it came by
-        // (the order inside a tile's run is of no consequence to a histogram)
+        // 3. the values into the stage, tile after tile: a value's place is its tile's offset plus its rank (the order
+        // inside a tile's run is of no consequence to a histogram)
 #pragma unroll
         for (int k0 = 0; k0 < kBigPieces; k0 += 8) {
             uint32_t at_[8];
 #pragma unroll
-            for (int k = 0; k < 8; ++k) at_[k] = atomicAdd(&s_tab[v[k0 + k] != 0xffffffffu ? tile_of(v[k0 + k]) : no_tile], 1u);
+            for (int k = 0; k < 8; ++k) at_[k] = s_tab[v[k0 + k] != 0xffffffffu ? tile_of(v[k0 + k]) : no_tile];
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 const uint32_t t = tile_of(v[k0 + k]);
-                s_stage[v[k0 + k] != 0xffffffffu ? at_[k] : kBigRound + lane] = (t << kEntryBits) | entry_of(v[k0 + k]);
+                const uint32_t rk = (k & 1) ? r2[(k0 + k) / 2] >> 16 : r2[(k0 + k) / 2] & 0xffffu;
+                s_stage[v[k0 + k] != 0xffffffffu ? at_[k] + rk : kBigRound + lane] = (t << kEntryBits) | entry_of(v[k0 + k]);
             }
         }
-        __syncthreads();
         TPROF_T(p4);
         if (wave < 8u) TPROF_ADD(4, p3, p4);
-        // 4. the table turns into "where the tile's run goes, minus where it lies in the stage" (an entry holds the END
-        // of its run now = the start of my next tile's)
-        {
-            uint32_t off = sum;
+        // 4. the second table: where the tile's run goes, minus where it lies in the stage
 #pragma unroll
-            for (int u = 0; u < kE; ++u) {
-                const uint32_t end = s_tab[u * kBigBlock + tid];
-                s_tab[u * kBigBlock + tid] = got[u] + at[u] - off;
-                off = end;
-            }
-        }
+        for (int u = 0; u < kE; ++u) s_dst[u * kBigBlock + tid] += got[u];
+        TPROF_T(p4b);
+        if (wave < 8u) TPROF_ADD(1, p4, p4b);
         mine = round_load<kBigPieces, true>(walk, vals, lane, v);  // (behind step 4: a wait for the reservations would
                                                                     // be a wait for these loads too)
+        if (lane == 0u) s_more[wave] = mine ? 1u : 0u;
         __syncthreads();
         TPROF_T(p5);
-        if (wave < 8u) TPROF_ADD(5, p4, p5);
-        // 5. out: consecutive lanes, consecutive entries
+        if (wave < 8u) TPROF_ADD(5, p4b, p5);
+        // 5. out: consecutive lanes, consecutive entries; and the first table cleared for the next round
+#pragma unroll
+        for (int u = 0; u < kE; ++u) s_tab[u * kBigBlock + tid] = 0u;
 #pragma unroll
         for (int k0 = 0; k0 < kBigPieces; k0 += 4) {  // (four stage reads, then four table reads, then the stores)
             if (static_cast<uint32_t>(k0) * kBigBlock >= total) break;
@@ -866,25 +884,25 @@ __global__ __launch_bounds__(kBigBlock) void k_tile_scatter_big(const uint32_t* 
 #pragma unroll
             for (int k = 0; k < 4; ++k) e[k] = s_stage[(k0 + k) * kBigBlock + tid];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) d[k] = s_tab[min(e[k] >> kEntryBits, kNoTile)];  // (behind `total`: whatever the stage holds)
+            for (int k = 0; k < 4; ++k) d[k] = s_dst[min(e[k] >> kEntryBits, kNoTile)];  // (behind `total`: whatever the stage holds)
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const uint32_t j = (k0 + k) * kBigBlock + tid;
                 if (j < total) bucket[d[k] + j] = static_cast<uint16_t>(e[k] & ((1u << kEntryBits) - 1u));
             }
         }
-        __syncthreads();  // (the next round clears the table and refills the stage)
+        __syncthreads();  // (the next round counts in the first table and refills the stage)
         TPROF_T(p6);
         if (wave < 8u) TPROF_ADD(6, p5, p6);
     }
     TPROF_T(q2);
     if (wave < 8u) TPROF_ADD(7, q0, q2);
 }
-constexpr size_t big_lds_bytes(int e) { return (static_cast<size_t>(e) * kBigBlock + kBigRound + 128u) * 4u; }
+constexpr size_t big_lds_bytes(int e) { return (2u * static_cast<size_t>(e) * kBigBlock + kBigRound + 192u) * 4u; }
 // (kBigE = 12, for the 12 183 tiles of config 5 -- two values per tile and round --, measured slower than the direct
 // rounds there: 236 against 201 us)
 constexpr int kBigE = 6;
-static_assert(big_lds_bytes(kBigE) <= 160u * 1024u - 256u, "the table and the stage share a CU's LDS");
+static_assert(big_lds_bytes(kBigE) <= 160u * 1024u - 256u, "the two tables and the stage share a CU's LDS");
 static_assert(kBigE * kBigBlock == kBigRoundTiles, "kernels.h tells the context which layouts take these rounds");
 static_assert(kTileShift + 1 + 14 <= 32, "a stage entry holds the tile and the bucket entry");
 
