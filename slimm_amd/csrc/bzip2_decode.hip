@@ -158,14 +158,10 @@ __global__ __launch_bounds__(64) void k_bz2_emit(const uint32_t* __restrict__ sl
     crc_ok[blockIdx.x] = ~crc == info[s].crc ? 1u : 0u;
 }
 
-void push_trace_bz2(const char* fmt, ...) {
-    static const bool on = traced("push");
-    if (!on) return;
+void push_trace_bz2(const char* fmt, ...) {   // "[push bzip2] ..."
     va_list ap;
     va_start(ap, fmt);
-    fprintf(stderr, "[push bzip2] ");
-    vfprintf(stderr, fmt, ap);
-    fputc('\n', stderr);
+    push_trace_line("bzip2", fmt, ap);
     va_end(ap);
 }
 
@@ -178,7 +174,8 @@ double ms_since(std::chrono::steady_clock::time_point t0) {
 // the block magics of pend from Z.bit on, in order: the bytes not read yet go to the device first (those in front of
 // Z.bit are dropped from pend)
 int bz2_find(slimm_ctx* c) {
-    slimm_ctx::BamDecode::Bzip2& Z = c->bam.bz2;
+    WindowPipeline::File::Bzip2& Z = c->win.file.bz2;
+    WindowPipeline::Bzip2& S = c->win.bz2;
     hipStream_t st = c->stream;
     const auto t0 = std::chrono::steady_clock::now();
     const size_t drop = static_cast<size_t>(Z.bit >> 3);
@@ -188,27 +185,27 @@ int bz2_find(slimm_ctx* c) {
         Z.bit -= drop * 8u;
     }
     const uint64_t n = Z.pend.size();
-    if (Z.comp.cap < n + kBz2Tail) HIP_TRY(c, Z.comp.ensure_later(n + (n >> 3) + kBz2Tail, c->bam.outgrown));
-    if (n) HIP_TRY(c, hipMemcpyAsync(Z.comp.p, Z.pend.data(), n, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemsetAsync(Z.comp.p + n, 0, kBz2Tail, st));
-    HIP_TRY(c, Z.count.ensure(4));
+    if (S.comp.cap < n + kBz2Tail) HIP_TRY(c, S.comp.ensure_later(n + (n >> 3) + kBz2Tail, c->win.outgrown));
+    if (n) HIP_TRY(c, hipMemcpyAsync(S.comp.p, Z.pend.data(), n, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemsetAsync(S.comp.p + n, 0, kBz2Tail, st));
+    HIP_TRY(c, S.count.ensure(4));
     uint32_t cap = static_cast<uint32_t>(std::min<uint64_t>(n / 64u + 256u, 1u << 26));
     for (;;) {
-        if (Z.d_cand.cap < cap) HIP_TRY(c, Z.d_cand.ensure_later(cap, c->bam.outgrown));
-        HIP_TRY(c, hipMemsetAsync(Z.count.p, 0, 4, st));
+        if (S.d_cand.cap < cap) HIP_TRY(c, S.d_cand.ensure_later(cap, c->win.outgrown));
+        HIP_TRY(c, hipMemsetAsync(S.count.p, 0, 4, st));
         const uint64_t span = n > (Z.bit >> 3) ? n - (Z.bit >> 3) : 0;
         const uint32_t grid = static_cast<uint32_t>(std::max<uint64_t>(1u, std::min<uint64_t>((span + 255u) / 256u, 4096u)));
-        if (span) hipLaunchKernelGGL(k_bz2_find, dim3(grid), dim3(256), 0, st, Z.comp.p, n, Z.bit, n * 8u, Z.d_cand.p, Z.count.p, cap);
+        if (span) hipLaunchKernelGGL(k_bz2_find, dim3(grid), dim3(256), 0, st, S.comp.p, n, Z.bit, n * 8u, S.d_cand.p, S.count.p, cap);
         HIP_TRY(c, hipGetLastError());
         uint32_t got = 0;
-        HIP_TRY(c, hipMemcpyAsync(&got, Z.count.p, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipMemcpyAsync(&got, S.count.p, 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(c, hipStreamSynchronize(st));
         if (got > cap) {   // (more magics than room: blocks of a few bytes each, pbzip2 on a tiny input)
             cap = got + (got >> 2) + 256u;
             continue;
         }
         Z.cand.resize(got);
-        if (got) HIP_TRY(c, hipMemcpy(Z.cand.data(), Z.d_cand.p, got * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        if (got) HIP_TRY(c, hipMemcpy(Z.cand.data(), S.d_cand.p, got * sizeof(uint64_t), hipMemcpyDeviceToHost));
         break;
     }
     std::sort(Z.cand.begin(), Z.cand.end());
@@ -232,39 +229,39 @@ int bz2_find(slimm_ctx* c) {
 
 // the decode scratch for `slots` blocks at a time, once per file
 int bz2_reserve(slimm_ctx* c) {
-    slimm_ctx::BamDecode::Bzip2& Z = c->bam.bz2;
+    WindowPipeline::File::Bzip2& Z = c->win.file.bz2;
+    WindowPipeline::Bzip2& S = c->win.bz2;
     if (Z.slots) return SLIMM_OK;
     // (a batch of blocks: as many as the file has, about -- a 900 k block compresses SAM text to 60 - 250 kB --, 16 to 256)
-    const uint64_t hint = c->bam.size_hint;
+    const uint64_t hint = c->win.announced.size_hint;
     Z.slots = hint ? static_cast<uint32_t>(std::min<uint64_t>(256u, std::max<uint64_t>(16u, hint / 65536u + 2u))) : 64u;
-    HIP_TRY(c, Z.ll.ensure(static_cast<size_t>(Z.slots) * bz2::kMaxBlock));
-    HIP_TRY(c, Z.link.ensure(static_cast<size_t>(Z.slots) * bz2::kMaxBlock));
-    HIP_TRY(c, Z.hist.ensure(static_cast<size_t>(Z.slots) * 256u));
-    HIP_TRY(c, Z.info.ensure(Z.slots));
-    HIP_TRY(c, Z.text_len.ensure(2u * Z.slots));
-    HIP_TRY(c, Z.out_at.ensure(2u * Z.slots));
-    if (hint && Z.comp.cap < hint + kBz2Tail) {
+    HIP_TRY(c, S.ll.ensure(static_cast<size_t>(Z.slots) * bz2::kMaxBlock));
+    HIP_TRY(c, S.link.ensure(static_cast<size_t>(Z.slots) * bz2::kMaxBlock));
+    HIP_TRY(c, S.hist.ensure(static_cast<size_t>(Z.slots) * 256u));
+    HIP_TRY(c, S.info.ensure(Z.slots));
+    HIP_TRY(c, S.text_len.ensure(2u * Z.slots));
+    HIP_TRY(c, S.out_at.ensure(2u * Z.slots));
+    if (hint && S.comp.cap < hint + kBz2Tail) {
         const uint64_t comp = std::min<uint64_t>(hint, 448ull << 20) + kBz2Tail;   // (a window: the pushes since the last batch)
-        HIP_TRY(c, Z.comp.ensure(comp));
-        HIP_TRY(c, Z.d_cand.ensure(comp / 64u + 256u));
+        HIP_TRY(c, S.comp.ensure(comp));
+        HIP_TRY(c, S.d_cand.ensure(comp / 64u + 256u));
     }
-    push_trace_bz2("%u blocks a batch: %.0f MB of decode scratch", Z.slots, Z.held() / 1e6);
+    push_trace_bz2("%u blocks a batch: %.0f MB of decode scratch", Z.slots, S.held() / 1e6);
     return SLIMM_OK;
 }
 
 }  // namespace
 
 int bz2_decode_batch(slimm_ctx* c, bool last) {
-    slimm_ctx::BamDecode::Bzip2& Z = c->bam.bz2;
+    WindowPipeline::File::Bzip2& Z = c->win.file.bz2;
+    WindowPipeline::Bzip2& S = c->win.bz2;
     hipStream_t st = c->stream;
     Z.ready.clear();
     Z.ready_pos = 0;
     if (Z.waiting && !last) return SLIMM_OK;   // (no byte has come since the chain stopped for want of them)
-    int rc = bz2_reserve(c);
-    if (rc != SLIMM_OK) return rc;
+    SLIMM_TRY(bz2_reserve(c));
     if (!Z.found) {
-        rc = bz2_find(c);
-        if (rc != SLIMM_OK) return rc;
+        SLIMM_TRY(bz2_find(c));
     }
     const uint64_t end_bit = Z.pend.size() * 8u;
     auto at = [&](uint64_t bit) { return static_cast<unsigned long long>(Z.base + (bit >> 3)); };
@@ -333,12 +330,12 @@ int bz2_decode_batch(slimm_ctx* c, bool last) {
             const auto t0 = std::chrono::steady_clock::now();
             batch0 = Z.next_cand;
             nb = std::min<size_t>(Z.slots, Z.cand.size() - batch0);
-            HIP_TRY(c, hipMemcpyAsync(Z.d_cand.p, Z.cand.data() + batch0, nb * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(k_bz2_decode, dim3(static_cast<uint32_t>(nb)), dim3(64), 0, st, Z.comp.p, end_bit, Z.d_cand.p, Z.ll.p, Z.hist.p,
-                               Z.info.p);
+            HIP_TRY(c, hipMemcpyAsync(S.d_cand.p, Z.cand.data() + batch0, nb * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(k_bz2_decode, dim3(static_cast<uint32_t>(nb)), dim3(64), 0, st, S.comp.p, end_bit, S.d_cand.p, S.ll.p, S.hist.p,
+                               S.info.p);
             HIP_TRY(c, hipGetLastError());
             hinfo.resize(nb);
-            HIP_TRY(c, hipMemcpyAsync(hinfo.data(), Z.info.p, nb * sizeof(bz2::BlockInfo), hipMemcpyDeviceToHost, st));
+            HIP_TRY(c, hipMemcpyAsync(hinfo.data(), S.info.p, nb * sizeof(bz2::BlockInfo), hipMemcpyDeviceToHost, st));
             HIP_TRY(c, hipStreamSynchronize(st));
             Z.ms_decode += ms_since(t0);
             ++Z.batches;
@@ -363,16 +360,16 @@ int bz2_decode_batch(slimm_ctx* c, bool last) {
     // the blocks of the chain: inverse BWT, text lengths
     const auto t0 = std::chrono::steady_clock::now();
     const uint32_t k = static_cast<uint32_t>(slots.size());
-    HIP_TRY(c, hipMemcpyAsync(Z.text_len.p + Z.slots, slots.data(), k * 4u, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_bz2_unbwt, dim3(k), dim3(256), 0, st, Z.text_len.p + Z.slots, Z.info.p, Z.ll.p, Z.link.p, Z.hist.p, Z.text_len.p);
+    HIP_TRY(c, hipMemcpyAsync(S.text_len.p + Z.slots, slots.data(), k * 4u, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_bz2_unbwt, dim3(k), dim3(256), 0, st, S.text_len.p + Z.slots, S.info.p, S.ll.p, S.link.p, S.hist.p, S.text_len.p);
     HIP_TRY(c, hipGetLastError());
     std::vector<uint32_t> len(k);
-    HIP_TRY(c, hipMemcpyAsync(len.data(), Z.text_len.p, k * 4u, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(len.data(), S.text_len.p, k * 4u, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
     Z.ms_bwt += ms_since(t0);
     for (uint32_t i = 0; i < k; ++i) {
         if (len[i] == ~0u) return BZ2_FAIL("block at byte %llu: %s", static_cast<unsigned long long>(ats[i]), bz2::status_text(bz2::kBadLinks));
-        slimm_ctx::BamDecode::Bzip2::Ready b;
+        WindowPipeline::File::Bzip2::Ready b;
         b.slot = slots[i];
         b.crc = crcs[i];
         b.len = len[i];
@@ -387,14 +384,14 @@ int bz2_decode_batch(slimm_ctx* c, bool last) {
 
 void bz2_trace_file(const slimm_ctx* c) {
     if (!traced("push")) return;
-    const slimm_ctx::BamDecode::Bzip2& Z = c->bam.bz2;
+    const WindowPipeline::File::Bzip2& Z = c->win.file.bz2;
     fprintf(stderr, "[push bzip2] %llu streams, %llu blocks in %llu batches, %llu false magics; find %.1f ms, decode %.1f ms, "
                     "inverse BWT %.1f ms, text %.1f ms\n", (unsigned long long)Z.streams, (unsigned long long)Z.blocks,
             (unsigned long long)Z.batches, (unsigned long long)Z.false_magics, Z.ms_find, Z.ms_decode, Z.ms_bwt, Z.ms_emit);
 }
 
 uint64_t bz2_window_bytes(const slimm_ctx* c, uint64_t cap, size_t* n_blocks) {
-    const slimm_ctx::BamDecode::Bzip2& Z = c->bam.bz2;
+    const WindowPipeline::File::Bzip2& Z = c->win.file.bz2;
     uint64_t n = 0;
     size_t i = Z.ready_pos;
     for (; i < Z.ready.size(); ++i) {
@@ -407,7 +404,8 @@ uint64_t bz2_window_bytes(const slimm_ctx* c, uint64_t cap, size_t* n_blocks) {
 }
 
 int bz2_emit(slimm_ctx* c, uint8_t* dst, size_t n_blocks, uint8_t* last_byte) {
-    slimm_ctx::BamDecode::Bzip2& Z = c->bam.bz2;
+    WindowPipeline::File::Bzip2& Z = c->win.file.bz2;
+    WindowPipeline::Bzip2& S = c->win.bz2;
     hipStream_t st = c->stream;
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<uint32_t> slots(n_blocks);
@@ -421,12 +419,12 @@ int bz2_emit(slimm_ctx* c, uint8_t* dst, size_t n_blocks, uint8_t* last_byte) {
         off += static_cast<int64_t>(b.len - b.drop);
     }
     const uint32_t k = static_cast<uint32_t>(n_blocks);
-    HIP_TRY(c, hipMemcpyAsync(Z.text_len.p + Z.slots, slots.data(), k * 4u, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(Z.out_at.p, at.data(), at.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_bz2_emit, dim3(k), dim3(64), 0, st, Z.text_len.p + Z.slots, Z.ll.p, Z.info.p, Z.out_at.p, dst, Z.text_len.p);
+    HIP_TRY(c, hipMemcpyAsync(S.text_len.p + Z.slots, slots.data(), k * 4u, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(S.out_at.p, at.data(), at.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_bz2_emit, dim3(k), dim3(64), 0, st, S.text_len.p + Z.slots, S.ll.p, S.info.p, S.out_at.p, dst, S.text_len.p);
     HIP_TRY(c, hipGetLastError());
     std::vector<uint32_t> ok(k);
-    HIP_TRY(c, hipMemcpyAsync(ok.data(), Z.text_len.p, k * 4u, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(ok.data(), S.text_len.p, k * 4u, hipMemcpyDeviceToHost, st));
     if (off) HIP_TRY(c, hipMemcpyAsync(last_byte, dst + off - 1, 1, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
     Z.ms_emit += ms_since(t0);

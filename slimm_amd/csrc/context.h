@@ -1,6 +1,7 @@
 // Internal to the library: the context behind the C ABI (include/slimm_hip.h) and what its translation units share --
-// context.hip (create / reset, phases A and B, the getters), records.hip (decoded records in), windows.hip (BAM / BGZF /
-// SAM windows decoded on the device).
+// context.hip (create / reset, phases A and B, the getters), records.hip (decoded records in), windows.hip (a file's bytes in
+// windows -- BAM records, BGZF blocks of them, SAM text, BGZF blocks of it, bzip2 SAM -- inflated and decoded on the device;
+// its state: windows.h).
 #pragma once
 #include <cerrno>
 #include <fcntl.h>
@@ -50,13 +51,24 @@ struct DevBuf {
     // the same without hipFree (which waits for every kernel in flight on the device): what the buffer was goes to `old`,
     // whose owner frees it when the device has nothing to do anyway
     hipError_t ensure_later(size_t n, std::vector<void*>& old) {
-        if (n <= cap) return hipSuccess;
-        if (p) old.push_back(p);
-        p = nullptr;
-        cap = 0;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), n * sizeof(T));
-        if (e == hipSuccess) cap = n;
-        return e;
+        return n <= cap ? hipSuccess : grow_keeping(n, 0, 0, nullptr, false, &old);
+    }
+    // Grows to n elements keeping elements [from, from + count) where they are: copied on `st`, and waited for by the host
+    // when `sync`.  What the buffer was goes to `old` (no hipFree now, as above); without one it is freed here
+    hipError_t grow_keeping(size_t n, size_t from, size_t count, hipStream_t st, bool sync, std::vector<void*>* old) {
+        DevBuf<T> nb;
+        hipError_t e = nb.ensure(n);
+        if (e == hipSuccess && count) e = hipMemcpyAsync(nb.p + from, p + from, count * sizeof(T), hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess && sync) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return e;
+        std::swap(p, nb.p);
+        std::swap(cap, nb.cap);
+        if (old && nb.p) {
+            old->push_back(nb.p);
+            nb.p = nullptr;
+            nb.cap = 0;
+        }
+        return hipSuccess;
     }
 };
 
@@ -88,6 +100,8 @@ extern const char* kKernelNames[K_COUNT];
 constexpr uint32_t kTailWords = 64;
 
 }  // namespace slimm
+
+#include "windows.h"
 
 using namespace slimm;   // (library-internal header)
 
@@ -150,121 +164,7 @@ struct slimm_ctx {
     bool has_check = false;        // ... all pushed batches carry one (checked and unchecked pushes do not mix)
     bool packed = false;           // slimm_push_records_packed: 16 bytes per record, no flag array (forms do not mix)
     bool marked = false;           // slimm_push_records_marked: 8 bytes per record, no key array (grouped input only)
-    // slimm_push_bam_bytes: BAM records decoded on the device (bam_decode.hip).  Two byte buffers [slack | window] take the
-    // windows in turn; the incomplete record at a window's end is copied in front of the next window
-    // (the ring of window buffers: a window is copied -- or inflated -- into one while older ones are still on their way or
-    // being decoded: at most kBamLag of them, and at most kBamInFlight bytes -- windows that arrive as BGZF blocks are
-    // gathered into device windows of up to kBamGather inflated bytes, three of which keep both inflate streams busy; a ring
-    // of 16 buffers of that size was 20 - 25 GB of HBM per context)
-    static constexpr uint32_t kBamRing = 4, kBamLag = kBamRing - 2;
-    static constexpr uint64_t kBamInFlight = 4ull << 30;    // finish the oldest window when more than this is in flight
-    static constexpr uint64_t kBamGather = 1900ull << 20;   // inflated bytes of a gathered device window (a window is < 2 GiB)
-    static constexpr uint64_t kBamGatherGoal = 1400ull << 20;  // ... which is launched once it holds this much
-    static constexpr uint64_t kBamKeepAcrossFiles = 4ull << 30; // slimm_reset gives the pipeline's buffers back above this
-    struct BamDecode {
-        DevBuf<uint8_t> bytes[kBamRing];
-        DevBuf<BamPiece> pieces;
-        DevBuf<uint32_t> offs;
-        DevBuf<BamCarry> carry;
-        PinBuf<BamWindowResult> result;     // written by k_bam_scan straight into page-locked host memory
-        std::vector<std::pair<const uint8_t*, size_t>> registered;  // caller buffers page-locked by hipHostRegister
-        uint64_t windows = 0;               // of this file, handed over so far
-        uint64_t head = 0;                  // ... of which [head, windows) are not finished yet (copied / inflating / waiting)
-        uint64_t win_bytes[kBamRing] = {};  // record bytes of the windows in flight
-        uint64_t carry_bytes = 0;
-        bool active = false;                // this file's records come from slimm_push_bam_bytes / slimm_push_bgzf_blocks
-        bool closed = false;                // the file's last window went in
-        hipEvent_t copied[kBamRing] = {};   // the window's bytes are in its buffer (behind the copy, or behind the inflate)
-        hipEvent_t h2d_done[4] = {};        // the caller's buffer of a push has been read (the pushes' events, in turn)
-        uint64_t pushes = 0;                // pushes of this file that started a copy
-        // windows that arrive as BGZF blocks (slimm_push_bgzf_blocks): compressed bytes + block descriptors per buffer, the
-        // inflater's scratch and {error code, first bad block} per buffer; inflated[b]: that window was inflated here
-        DevBuf<uint8_t> comp[kBamRing];
-        DevBuf<BgzfBlock> desc[kBamRing];
-        DevBuf<uint8_t> inflate_scratch[2];
-        DevBuf<uint32_t> inflate_status;       // 4 words per buffer
-        PinBuf<uint32_t> h_inflate_status;     // ... fetched with the window's other results
-        bool inflated[kBamRing] = {};
-        // the inflate kernels' own streams, taken in turn by the device windows: the copies of other windows go on beside
-        // them, and the Huffman phase of one window (a lane per block: 30 K blocks are half the lanes) beside the other's
-        hipStream_t inflate_stream[2] = {nullptr, nullptr};
-        hipEvent_t comp_copied = nullptr;
-        // BGZF pushes gathered for the next device window (buffer windows % kBamRing): compressed bytes so far, inflated
-        // bytes so far, the inflated bytes in front of the file's first record
-        bool acc_open = false;
-        uint64_t acc_src = 0, acc_dst = 0;
-        uint32_t acc_skip = 0, acc_tok = 0;   // (acc_tok: words of token room of the gathered blocks)
-        std::vector<void*> outgrown;   // device buffers replaced by larger ones while kernels were in flight: freed at the file's end
-        // SAM text (slimm_push_sam_bytes, sam_decode.hip): this file's windows are text; the header's reference names as a
-        // hash table on the device (slimm_set_reference_names); the last byte pushed (a last line without its newline gets one)
-        bool sam = false;
-        DevBuf<SamRefEntry> sam_table;
-        DevBuf<uint8_t> sam_names;
-        uint32_t sam_mask = 0;
-        uint8_t sam_last_byte = '\n';
-        // ... unless the text's last bytes so far were inflated on the device (slimm_push_bgzf_sam_blocks): the device then ends
-        // a last line without its newline; lines it ended so far (SLIMM_TRACE=push)
-        bool sam_dev_tail = false;
-        uint64_t sam_lines_ended = 0;
-        std::vector<BgzfBlock> desc_host[kBamRing];   // (a buffer's descriptors stay until the buffer's turn comes again: the copy reads them)
-        // Q18 on a grouped stream (kernels.h: BamCarry): the decoders' two counts of the windows finished so far
-        uint64_t q18_starts = 0, q18_plain = 0;
-        // what the file's gathered windows are sized for: slimm_set_input_size_hint (the file's compressed bytes; 0 = not
-        // told) and, from it and the first push's ratio, the inflated bytes a gathered window's buffer gets (0 = kBamGather)
-        uint64_t size_hint = 0, win_cap = 0;
-        bool planned = false;                // the file's first COMPRESSED push has reserved its buffers (or found no hint)
-        // a byte range of a file split over a group (slimm_set_input_mid_file, split.hip): the range starts inside the file
-        // (its first record is guessed; the bytes in front of it -- the head -- wait on the device for the member on the
-        // left) and / or ends inside it (the incomplete last record stays in the carry); the first record's name for the
-        // join; the Q18 counts are summed by the group (slimm_group_stitch_ranges), not checked per member
-        bool starts_mid = false, ends_mid = false, q18_by_group = false;
-        bool found_start = false;   // the first window holds a record start (false: the whole range is head)
-        bool has_first = false;     // `first` holds the name of the range's first record (decoded in any window)
-        DevBuf<uint8_t> head_bytes;
-        uint64_t head_len = 0;
-        DevBuf<BamCarry> first, join;   // (join: the left member's carry, on this member's device)
-        DevBuf<unsigned long long> guess;
-        // bzip2 SAM (slimm_push_bzip2_sam_bytes, bzip2_decode.hip).  Host side: the compressed bytes not decoded yet (file
-        // offset `base` on; the next bit to read), the stream being read (its level, combined CRC so far), the decoded bytes
-        // still to skip; the block magics found in them (bit offsets into pend, in order) and the next one to look at.
-        // Device side: pend's copy, the candidates, and per slot of a batch the BWT string -- then its RLE1 text --, the
-        // inverse BWT's links, the byte histogram, what decoding found and the text's length; the blocks of the last batch
-        // decoded and not yet written into a window
-        struct Bzip2 {
-            bool on = false;
-            std::vector<uint8_t> pend;
-            uint64_t base = 0, bit = 0;
-            bool in_stream = false;
-            uint32_t level = 0, combined = 0, streams = 0;
-            uint64_t skip_left = 0;
-            std::vector<uint64_t> cand;
-            size_t next_cand = 0;
-            bool found = false;     // cand holds the magics of pend as it is
-            bool waiting = false;   // the chain stopped for want of bytes: nothing to decode until pend grows
-            uint32_t slots = 0;     // blocks a batch decodes at most (the scratch below holds that many; sized per file)
-            DevBuf<uint8_t> comp, ll;
-            DevBuf<uint32_t> link, hist, count, text_len;
-            DevBuf<unsigned long long> d_cand;
-            DevBuf<bz2::BlockInfo> info;
-            DevBuf<int64_t> out_at;
-            struct Ready {
-                uint32_t slot, crc;
-                uint64_t len, drop;   // text bytes; of them the first `drop` are skipped (the header)
-                uint64_t at;          // file offset of the block (errors)
-            };
-            std::vector<Ready> ready;
-            size_t ready_pos = 0;
-            uint64_t blocks = 0, batches = 0, false_magics = 0;   // (SLIMM_TRACE=push; false_magics: candidates the chain passed over)
-            double ms_find = 0, ms_decode = 0, ms_bwt = 0, ms_emit = 0;
-            uint64_t held() const { return comp.cap + ll.cap + link.cap * 4ull + hist.cap * 4ull + d_cand.cap * 8ull; }
-        } bz2;
-        uint64_t held_bytes() const {   // device memory of the window pipeline
-            uint64_t n = pieces.cap * sizeof(BamPiece) + offs.cap * 4ull + bz2.held();
-            for (uint32_t k = 0; k < kBamRing; ++k) n += bytes[k].cap + comp[k].cap + desc[k].cap * sizeof(BgzfBlock);
-            for (auto& sc : inflate_scratch) n += sc.cap;
-            return n;
-        }
-    } bam;
+    WindowPipeline win;     // a file's bytes in windows, inflated and decoded on the device (windows.h, windows.hip)
     DeviceRecords rec;      // what analyze reads (owned buffers or borrowed pointers)
     bool borrowed = false;
     uint64_t n_pushed = 0;
@@ -397,6 +297,12 @@ int fail(slimm_ctx* c, int code, const char* fmt, ...);
         if (e_ != hipSuccess) return fail((c), SLIMM_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
+#define SLIMM_TRY(expr)                      \
+    do {                                     \
+        const int rc_ = (expr);              \
+        if (rc_ != SLIMM_OK) return rc_;     \
+    } while (0)
+
 struct KernelTimer {  // brackets one launch (or a group) with events when timing is on
     slimm_ctx* c;
     slimm_ctx::Ev ev{};
@@ -428,22 +334,9 @@ void drain_events(slimm_ctx* c);
 int ensure_work_buffers(slimm_ctx* c, uint32_t n);
 int ensure_pair_table(slimm_ctx* c, uint32_t cap);
 int check_device_errors(slimm_ctx* c, uint32_t err);
-int bam_fetch_q18(slimm_ctx* c);   // windows.hip: the Q18 run counts of the device decoders so far
-// windows.hip: `n` bytes at `src` (on device src_device) as one more window behind the closed file's carry (split.hip)
-int bam_append_window(slimm_ctx* c, const uint8_t* src, int src_device, uint64_t n, bool final, uint64_t& n_rec);
-// bzip2_decode.hip (slimm_push_bzip2_sam_bytes): the next batch of whole blocks of bam.bz2.pend decoded up to their text
-// lengths (bam.bz2.ready; none: the chain waits for more bytes, or the streams have ended); at `last` what is left must
-// end the streams.  Then, window by window: the text bytes of the next ready blocks that fit in `cap` (at least one
-// block), and those written to dst on the context's stream, their CRCs checked, *last_byte = the text's last byte
-int bz2_decode_batch(slimm_ctx* c, bool last);
-uint64_t bz2_window_bytes(const slimm_ctx* c, uint64_t cap, size_t* n_blocks);
-int bz2_emit(slimm_ctx* c, uint8_t* dst, size_t n_blocks, uint8_t* last_byte);
-void bz2_trace_file(const slimm_ctx* c);   // SLIMM_TRACE=push (read at every call): the file's streams, blocks, false magics, times
+// records.hip: c->rec = the owned record arrays in_* from record `from` on, in the file's form (marked / packed / has_check)
+void view_records(slimm_ctx* c, uint64_t from = 0);
 
-// Grows one record array to `cap` elements, keeping the `used` elements pushed so far (when the array holds them at all:
-// an array the file's record form does not use is neither allocated nor copied).
-// later != nullptr: no hipFree now (it waits for every kernel in flight -- the inflate of the windows behind this one):
-// what the array was goes there and is freed when the file has ended
 enum StreamClass { kStreamHigh = 0, kStreamNormal = 1, kStreamLow = 2 };
 inline hipError_t need_stream(hipStream_t& s, StreamClass cls = kStreamNormal) {
     if (s) return hipSuccess;
@@ -453,25 +346,15 @@ inline hipError_t need_stream(hipStream_t& s, StreamClass cls = kStreamNormal) {
     return hipStreamCreateWithPriority(&s, hipStreamNonBlocking, cls == kStreamHigh ? greatest : least);
 }
 
+// Grows one record array to `cap` elements, keeping the `used` elements pushed so far (when the array holds them at all:
+// an array the file's record form does not use is neither allocated nor copied).
+// later != nullptr: no hipFree now (it waits for every kernel in flight -- the inflate of the windows behind this one):
+// what the array was goes there and is freed when the file has ended
 template <typename T>
 hipError_t grow_record_array(DevBuf<T>& buf, uint64_t cap, uint64_t used, hipStream_t st, std::vector<void*>* later = nullptr) {
     if (cap <= buf.cap) return hipSuccess;
     if (used == 0 || buf.cap < used) return later ? buf.ensure_later(cap, *later) : buf.ensure(cap);  // nothing of this file in it
-    DevBuf<T> nb;
-    hipError_t e = nb.ensure(cap);
-    if (e != hipSuccess) return e;
-    e = hipMemcpyAsync(nb.p, buf.p, used * sizeof(T), hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess) return e;
-    e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return e;
-    std::swap(buf.p, nb.p);
-    std::swap(buf.cap, nb.cap);
-    if (later && nb.p) {
-        later->push_back(nb.p);
-        nb.p = nullptr;
-        nb.cap = 0;
-    }
-    return hipSuccess;
+    return buf.grow_keeping(cap, 0, used, st, true, later);
 }
 
 }  // namespace slimm

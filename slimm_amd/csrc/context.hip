@@ -377,12 +377,6 @@ void slimm_destroy(slimm_ctx* c) {
             (void)hipStreamSynchronize(c->side_stream);
             (void)hipStreamDestroy(c->side_stream);
         }
-        for (auto& is : c->bam.inflate_stream)
-            if (is) {
-                (void)hipStreamSynchronize(is);
-                (void)hipStreamDestroy(is);
-            }
-        if (c->bam.comp_copied) (void)hipEventDestroy(c->bam.comp_copied);
         if (c->front_done) (void)hipEventDestroy(c->front_done);
         if (c->prefix_done) (void)hipEventDestroy(c->prefix_done);
         if (c->copy_stream) {
@@ -390,12 +384,7 @@ void slimm_destroy(slimm_ctx* c) {
             (void)hipStreamDestroy(c->copy_stream);
         }
         if (c->copy_done) (void)hipEventDestroy(c->copy_done);
-        for (auto& r : c->bam.registered) (void)hipHostUnregister(const_cast<uint8_t*>(r.first));
-        for (void* p : c->bam.outgrown) (void)hipFree(p);
-        for (auto& e : c->bam.copied)
-            if (e) (void)hipEventDestroy(e);
-        for (auto& e : c->bam.h2d_done)
-            if (e) (void)hipEventDestroy(e);
+        c->win.destroy();   // (behind the main and the copy stream, which its buffers and events were used on)
         for (auto& sg : c->staging)
             if (sg.done) (void)hipEventDestroy(sg.done);
         if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -411,58 +400,10 @@ int slimm_reset(slimm_ctx* c) {
         c->copy_pending = false;
         for (auto& sg : c->staging) sg.pending = false;
     }
-    if (c->bam.active && c->bam.head < c->bam.windows) {  // a file abandoned with windows in flight (an error, a caller's
-        (void)hipSetDevice(c->device);                    // change of mind): their copies and inflates must not land in the
-        if (c->copy_stream) HIP_TRY(c, hipStreamSynchronize(c->copy_stream));  // next file's buffers
-        for (auto& is : c->bam.inflate_stream)
-            if (is) HIP_TRY(c, hipStreamSynchronize(is));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    if (c->bam.acc_open) {  // (a gathered window that was never launched: its copies)
-        (void)hipSetDevice(c->device);
-        if (c->copy_stream) HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
-    }
-    c->bam.acc_open = false;
-    c->bam.acc_src = c->bam.acc_dst = 0;
-    c->bam.acc_skip = 0;
-    c->bam.pushes = 0;
-    for (void* p : c->bam.outgrown) (void)hipFree(p);
-    c->bam.outgrown.clear();
+    SLIMM_TRY(c->win.end_file(c));
     c->host->reset();
     c->analyzed = c->covered = c->filtered = c->counted = c->no_hits = false;
     c->n_pushed = 0;
-    c->bam.windows = 0;
-    c->bam.carry_bytes = 0;
-    c->bam.active = false;
-    c->bam.head = 0;
-    c->bam.closed = false;
-    c->bam.q18_starts = c->bam.q18_plain = 0;
-    c->bam.starts_mid = c->bam.ends_mid = c->bam.found_start = c->bam.has_first = c->bam.q18_by_group = false;
-    c->bam.head_len = 0;
-    c->bam.size_hint = c->bam.win_cap = 0;
-    c->bam.planned = false;
-    if (c->bam.held_bytes() > slimm_ctx::kBamKeepAcrossFiles) {   // (a large file's windows: the next file sizes its own)
-        (void)hipSetDevice(c->device);
-        for (uint32_t k = 0; k < slimm_ctx::kBamRing; ++k) {
-            c->bam.bytes[k].release();
-            c->bam.comp[k].release();
-            c->bam.desc[k].release();
-        }
-        for (auto& sc : c->bam.inflate_scratch) sc.release();
-        c->bam.pieces.release();
-        c->bam.offs.release();
-        slimm_ctx::BamDecode::Bzip2& Z = c->bam.bz2;
-        Z.comp.release();
-        Z.ll.release();
-        Z.link.release();
-        Z.hist.release();
-        Z.d_cand.release();
-    }
-    // (bzip2 SAM: the next file sizes its own decode scratch; what the host held of this one's bytes goes)
-    c->bam.bz2.slots = 0;
-    std::vector<uint8_t>().swap(c->bam.bz2.pend);
-    std::vector<uint64_t>().swap(c->bam.bz2.cand);
-    c->bam.bz2.ready.clear();
     c->has_check = false;
     c->packed = false;
     c->marked = false;
@@ -532,23 +473,22 @@ int slimm_analyze_alignments(slimm_ctx* c) {
     HostTrace tr("analyze_alignments");
     (void)hipSetDevice(c->device);
     (void)hipGetLastError();  // (the launches below answer for themselves: what another user of the runtime left in this thread is not theirs)
-    if (c->bam.active) {
+    if (c->win.file.active) {
         // (windows pushed so far may still be gathered or in flight: analysing now would profile a truncated record stream)
-        if (!c->bam.closed)
+        if (!c->win.file.closed)
             return fail(c, SLIMM_E_INVALID, "the file's last window has not been pushed (slimm_push_bam_bytes / _bgzf_blocks / _sam_bytes with last != 0)");
         // (a range of a split file: its group sums the counts over the members, slimm_group_stitch_ranges)
-        if (c->order == SLIMM_ORDER_GROUPED && !c->bam.q18_by_group) {  // Q18: a run of shortened names only may have its flagged namesakes elsewhere
-            const int qrc = bam_fetch_q18(c);
+        if (c->order == SLIMM_ORDER_GROUPED && !c->win.file.q18_by_group) {  // Q18: a run of shortened names only may have its flagged namesakes elsewhere
+            const int qrc = fetch_q18(c);
             if (qrc != SLIMM_OK) return qrc;
-            if (c->bam.q18_starts != c->bam.q18_plain)
+            if (c->win.file.q18_starts != c->win.file.q18_plain)
                 return fail(c, SLIMM_E_REGROUP,
                             "read names ending in .1 / .2 without a mate flag, apart from the flagged records of the shortened name: "
                             "push this file to a context created with SLIMM_ORDER_ANY");
         }
     }
     const uint32_t n = c->rec.n;
-    int rc = ensure_work_buffers(c, n);
-    if (rc != SLIMM_OK) return rc;
+    SLIMM_TRY(ensure_work_buffers(c, n));
     tr.mark("set device + buffers");
     hipStream_t st = c->stream;
     if (c->copy_pending) HIP_TRY(c, hipStreamWaitEvent(st, c->copy_done, 0));  // streamed ingest: device-side ordering
@@ -758,8 +698,7 @@ int finish_from_device_stats(slimm_ctx* c) {
     tr.mark("stream sync (device phase A + copy)");
     const uint32_t* cnt = c->h_stats.p + R4;
     const uint32_t* tl = c->h_stats.p + R4 + 32;
-    int rc = check_device_errors(c, cnt[CNT_ERR] | tl[3]);
-    if (rc != SLIMM_OK) return rc;
+    SLIMM_TRY(check_device_errors(c, cnt[CNT_ERR] | tl[3]));
     c->local_V = cnt[CNT_V];
     c->local_M = cnt[CNT_M];
     c->local_P = cnt[CNT_P];
@@ -1118,8 +1057,7 @@ int filter_check_counters(slimm_ctx* c, const uint32_t* h_cnt, bool& again) {
     again = false;
     if (h_cnt[CNT_ERR] & ERR_PAIR_OVERFLOW) {
         if (c->pair_cap >= (1u << 30)) return fail(c, SLIMM_E_INVALID, "(taxon, reference) pair set overflow");
-        int rc = ensure_pair_table(c, c->pair_cap * 4);
-        if (rc != SLIMM_OK) return rc;
+        SLIMM_TRY(ensure_pair_table(c, c->pair_cap * 4));
         c->pair_clean = false;
         again = true;
         return SLIMM_OK;
@@ -1144,8 +1082,7 @@ int slimm_filter_alignments(slimm_ctx* c) {
     HostProfile& h = *c->host;
     HostTrace tr("filter_alignments");
     bool rows_ride_along = false;
-    int rc = filter_prepare(c, rows_ride_along);
-    if (rc != SLIMM_OK) return rc;
+    SLIMM_TRY(filter_prepare(c, rows_ride_along));
     if (c->device < 0) {  // host-only: the per-read part arrives through slimm_set_partials
         c->filtered = true;
         return SLIMM_OK;
@@ -1155,16 +1092,14 @@ int slimm_filter_alignments(slimm_ctx* c) {
     uint32_t* const blockB = c->ref_stats.p + c->statsA_words();
     c->filter_pending = false;
     for (int attempt = 0; attempt < 8; ++attempt) {
-        rc = filter_launch(c, rows_ride_along && attempt == 0);
-        if (rc != SLIMM_OK) return rc;
+        SLIMM_TRY(filter_launch(c, rows_ride_along && attempt == 0));
         uint32_t* const hB = c->h_stats.p + c->statsA_words();
         tr.mark("phase B launches");
         launch_copy_out(st, hB, blockB, static_cast<uint32_t>(c->statsB_words()));
         HIP_TRY(c, hipStreamSynchronize(st));
         tr.mark("stream sync (device phase B + copy)");
         bool again = false;
-        rc = filter_check_counters(c, hB + 4ull * R, again);
-        if (rc != SLIMM_OK) return rc;
+        SLIMM_TRY(filter_check_counters(c, hB + 4ull * R, again));
         if (!again) break;
     }
     // the packed rows {uniq_reads_count2 = sum of uniq_cov2 bins, non-zero uniq_cov2 bins, -, -}, the level marks and the
@@ -1187,13 +1122,9 @@ int slimm_filter_alignments_launch(slimm_ctx* c) {
     if (c->no_hits) return SLIMM_E_NO_HITS;
     if (c->device < 0) return fail(c, SLIMM_E_INVALID, "host-only context: use slimm_filter_alignments + slimm_set_partials");
     bool rows_ride_along = false;
-    int rc = SLIMM_OK;
-    if (!c->filter_pending) {  // (a retry keeps the valid set and the rows that are on the device already)
-        rc = filter_prepare(c, rows_ride_along);
-        if (rc != SLIMM_OK) return rc;
-    }
-    rc = filter_launch(c, rows_ride_along);
-    if (rc != SLIMM_OK) return rc;
+    // (a retry keeps the valid set and the rows that are on the device already)
+    if (!c->filter_pending) SLIMM_TRY(filter_prepare(c, rows_ride_along));
+    SLIMM_TRY(filter_launch(c, rows_ride_along));
     const uint64_t W = 3ull * c->R + c->T + 2;
     HIP_TRY(c, c->d_partials.ensure(W + 2));
     launch_partials_pack(c->stream, c->ref_stats.p + c->statsA_words(), c->R, c->T, c->d_partials.p);
@@ -1236,8 +1167,7 @@ int slimm_install_merged_partials(slimm_ctx* c, uint32_t* total_pairs) {
         // summed with everything else, so every rank sees "some rank overflowed" and every rank goes round again.
         if (h[W - 1] != 0u) {
             if (c->pair_cap >= (1u << 30)) return fail(c, SLIMM_E_INVALID, "(taxon, reference) pair set overflow");
-            int rc = ensure_pair_table(c, c->pair_cap * 4);
-            if (rc != SLIMM_OK) return rc;
+            SLIMM_TRY(ensure_pair_table(c, c->pair_cap * 4));
             c->pair_clean = false;
             return SLIMM_E_RETRY;
         }
@@ -1245,8 +1175,7 @@ int slimm_install_merged_partials(slimm_ctx* c, uint32_t* total_pairs) {
         local[CNT_PAIRS] = h[W];
         local[CNT_ERR] = h[W + 1];
         bool again = false;
-        int rc = filter_check_counters(c, local, again);
-        if (rc != SLIMM_OK) return rc;
+        SLIMM_TRY(filter_check_counters(c, local, again));
         c->filter_pending = false;
     }
     c->part_u2.assign(h, h + R);
@@ -1328,14 +1257,10 @@ int slimm_get_reads_lca_count(slimm_ctx* c) {
 }
 
 int slimm_get_profiles(slimm_ctx* c, const char* path) {  // src/slimm.hpp:447-489, one file on one GPU
-    int rc = slimm_analyze_alignments(c);
-    if (rc != SLIMM_OK) return rc;
-    rc = slimm_finish_coverage(c);
-    if (rc != SLIMM_OK) return rc;  // SLIMM_E_NO_HITS: "[WARNING] No mapped reads found" (:451-455), nothing written
-    rc = slimm_filter_alignments(c);
-    if (rc != SLIMM_OK) return rc;
-    rc = slimm_get_reads_lca_count(c);
-    if (rc != SLIMM_OK) return rc;
+    SLIMM_TRY(slimm_analyze_alignments(c));
+    SLIMM_TRY(slimm_finish_coverage(c));  // SLIMM_E_NO_HITS: "[WARNING] No mapped reads found" (:451-455), nothing written
+    SLIMM_TRY(slimm_filter_alignments(c));
+    SLIMM_TRY(slimm_get_reads_lca_count(c));
     return path ? slimm_write_abundance_file(c, path) : SLIMM_OK;
 }
 
@@ -1353,8 +1278,7 @@ int slimm_write_abundance_file(slimm_ctx* c, const char* path) {
     const char* text = nullptr;
     uint64_t len = 0;
     HostTrace tr("write_abundance_file");
-    int rc = slimm_write_abundance(c, &text, &len);
-    if (rc != SLIMM_OK) return rc;
+    SLIMM_TRY(slimm_write_abundance(c, &text, &len));
     tr.mark("profile text");
     // (plain descriptors: three system calls, no stdio buffer to allocate and flush for a few KB written once)
     const int fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0666);
@@ -1619,11 +1543,10 @@ int slimm_host_q18_regroup_needed(const slimm_q18_runs* q) { return q && q->shor
 int slimm_get_q18_runs(slimm_ctx* c, uint64_t* short_starts, uint64_t* short_to_plain) {
     if (!c || !short_starts || !short_to_plain) return SLIMM_E_INVALID;
     *short_starts = *short_to_plain = 0;
-    if (c->device < 0 || !c->bam.active || c->order != SLIMM_ORDER_GROUPED) return SLIMM_OK;
-    const int rc = bam_fetch_q18(c);
-    if (rc != SLIMM_OK) return rc;
-    *short_starts = c->bam.q18_starts;
-    *short_to_plain = c->bam.q18_plain;
+    if (c->device < 0 || !c->win.file.active || c->order != SLIMM_ORDER_GROUPED) return SLIMM_OK;
+    SLIMM_TRY(fetch_q18(c));
+    *short_starts = c->win.file.q18_starts;
+    *short_to_plain = c->win.file.q18_plain;
     return SLIMM_OK;
 }
 uint32_t slimm_host_bin_of(int32_t begin_pos, uint32_t avg_read_len, uint32_t ref_len, uint32_t bin_width) {

@@ -259,6 +259,7 @@ constexpr uint32_t kBamPiece = 16384;                 // bytes per piece: a lane
 constexpr uint32_t kBamSlots = kBamPiece / 36 + 2;    // record offsets a piece can hold (a record is at least 36 bytes)
 constexpr uint32_t kBamPieceBad = 1;
 constexpr uint64_t kBamSlack = 16ull << 20;           // room in front of a window for the incomplete record of the one before
+                                                      // (SAM windows have the same slack for an incomplete line: the name stays)
 struct BamPiece {
     uint32_t guess, stop, count, flags;  // where its first record starts (guessed, then verified); where its walk ended; records
     uint32_t base, pad[3];               // records of the window in front of it

@@ -3,6 +3,23 @@
 // analyze_alignments reads from each BamAlignmentRecord (reference src/slimm.hpp:194-211).
 #include "context.h"
 
+namespace slimm {
+// (run-marked: ref (the words) | pos; packed: key | ref | pos; four arrays: key | ref | pos | flag; check words when every batch had them)
+void view_records(slimm_ctx* c, uint64_t from) {
+    auto at = [from](auto* p) { return p ? p + from : nullptr; };
+    DeviceRecords r;
+    r.marked = c->marked;
+    r.packed = c->packed;
+    if (!c->marked) r.key = at(c->in_key.p);
+    r.ref = at(c->in_ref.p);
+    r.pos = at(c->in_pos.p);
+    if (!c->marked && !c->packed) r.flag = at(c->in_flag.p);
+    if (c->has_check) r.check = at(c->in_check.p);
+    r.n = static_cast<uint32_t>(c->n_pushed - from);
+    c->rec = r;
+}
+}  // namespace slimm
+
 extern "C" {
 
 // Room for n records of the file's form: the four-array form holds key | ref | pos | flag (| check), the packed form
@@ -25,7 +42,7 @@ int slimm_reserve(slimm_ctx* c, uint64_t n) {
     uint64_t cap = n <= c->in_ref.cap ? c->in_ref.cap : std::max<uint64_t>(n, c->in_ref.cap * 2);  // (double only to grow)
     if (cap >= 0x7fffffffull) cap = 0x7ffffffeull;
     const uint64_t used = c->n_pushed;
-    std::vector<void*>* later = c->bam.active ? &c->bam.outgrown : nullptr;  // (windows of a BAM file may be inflating)
+    std::vector<void*>* later = c->win.file.active ? &c->win.outgrown : nullptr;  // (windows of the file may be inflating)
     HIP_TRY(c, grow_record_array(c->in_ref, cap, used, c->stream, later));
     HIP_TRY(c, grow_record_array(c->in_pos, cap, used, c->stream, later));
     if (need_key) HIP_TRY(c, grow_record_array(c->in_key, cap, used, c->stream, later));
@@ -43,8 +60,7 @@ int slimm_push_records(slimm_ctx* c, const uint64_t* key, const int32_t* ref, co
     if (c->has_check) return fail(c, SLIMM_E_INVALID, "earlier batches carried check words: push this one with slimm_push_records_checked");
     if (c->packed || c->marked)
         return fail(c, SLIMM_E_INVALID, "earlier batches were packed or run-marked records: the forms do not mix within a file");
-    int rc = slimm_reserve(c, c->n_pushed + n);
-    if (rc != SLIMM_OK) return rc;
+    SLIMM_TRY(slimm_reserve(c, c->n_pushed + n));
     if (c->in_flag.cap < c->in_key.cap) HIP_TRY(c, c->in_flag.ensure(c->in_key.cap));  // (only ever at a file's first push)
     const uint64_t o = c->n_pushed;
     HIP_TRY(c, hipMemcpyAsync(c->in_key.p + o, key, n * 8, hipMemcpyHostToDevice, c->stream));
@@ -53,11 +69,7 @@ int slimm_push_records(slimm_ctx* c, const uint64_t* key, const int32_t* ref, co
     HIP_TRY(c, hipMemcpyAsync(c->in_flag.p + o, flag, n * 2, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));  // the caller may reuse its buffers on return
     c->n_pushed += n;
-    c->rec.key = c->in_key.p;
-    c->rec.ref = c->in_ref.p;
-    c->rec.pos = c->in_pos.p;
-    c->rec.flag = c->in_flag.p;
-    c->rec.n = static_cast<uint32_t>(c->n_pushed);
+    view_records(c);
     return SLIMM_OK;
 }
 
@@ -75,8 +87,7 @@ int slimm_push_records_checked(slimm_ctx* c, const uint64_t* key, const int32_t*
     if (c->packed || c->marked)
         return fail(c, SLIMM_E_INVALID, "earlier batches were packed or run-marked records: the forms do not mix within a file");
     c->has_check = true;
-    int rc = slimm_reserve(c, c->n_pushed + n);
-    if (rc != SLIMM_OK) return rc;
+    SLIMM_TRY(slimm_reserve(c, c->n_pushed + n));
     HIP_TRY(c, c->in_check.ensure(c->in_key.cap));
     if (c->in_flag.cap < c->in_key.cap) HIP_TRY(c, c->in_flag.ensure(c->in_key.cap));
     const uint64_t o = c->n_pushed;
@@ -87,12 +98,7 @@ int slimm_push_records_checked(slimm_ctx* c, const uint64_t* key, const int32_t*
     HIP_TRY(c, hipMemcpyAsync(c->in_check.p + o, check, n * 4, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->n_pushed += n;
-    c->rec.key = c->in_key.p;
-    c->rec.ref = c->in_ref.p;
-    c->rec.pos = c->in_pos.p;
-    c->rec.flag = c->in_flag.p;
-    c->rec.check = c->in_check.p;
-    c->rec.n = static_cast<uint32_t>(c->n_pushed);
+    view_records(c);
     return SLIMM_OK;
 }
 
@@ -109,8 +115,7 @@ int slimm_push_records_async(slimm_ctx* c, const uint64_t* key, const int32_t* r
     if (c->has_check) return fail(c, SLIMM_E_INVALID, "earlier batches carried check words: push this one with slimm_push_records_checked");
     if (c->packed || c->marked)
         return fail(c, SLIMM_E_INVALID, "earlier batches were packed or run-marked records: the forms do not mix within a file");
-    int rc = slimm_reserve(c, c->n_pushed + n);
-    if (rc != SLIMM_OK) return rc;
+    SLIMM_TRY(slimm_reserve(c, c->n_pushed + n));
     if (c->in_flag.cap < c->in_key.cap) HIP_TRY(c, c->in_flag.ensure(c->in_key.cap));
     HIP_TRY(c, need_stream(c->copy_stream, kStreamHigh));
     const uint64_t o = c->n_pushed;
@@ -121,11 +126,7 @@ int slimm_push_records_async(slimm_ctx* c, const uint64_t* key, const int32_t* r
     HIP_TRY(c, hipEventRecord(c->copy_done, c->copy_stream));
     c->copy_pending = true;
     c->n_pushed += n;
-    c->rec.key = c->in_key.p;
-    c->rec.ref = c->in_ref.p;
-    c->rec.pos = c->in_pos.p;
-    c->rec.flag = c->in_flag.p;
-    c->rec.n = static_cast<uint32_t>(c->n_pushed);
+    view_records(c);
     return SLIMM_OK;
 }
 
@@ -139,8 +140,7 @@ static int push_packed(slimm_ctx* c, const uint64_t* key, const int32_t* ref, co
     if (c->has_check || c->marked || (c->n_pushed && !c->packed))
         return fail(c, SLIMM_E_INVALID, "earlier batches were not packed records: the forms do not mix within a file");
     c->packed = true;
-    int rc = slimm_reserve(c, c->n_pushed + n);
-    if (rc != SLIMM_OK) return rc;
+    SLIMM_TRY(slimm_reserve(c, c->n_pushed + n));
     const uint64_t o = c->n_pushed;
     if (on_copy_stream) HIP_TRY(c, need_stream(c->copy_stream, kStreamHigh));
     hipStream_t st = on_copy_stream ? c->copy_stream : c->stream;
@@ -154,12 +154,7 @@ static int push_packed(slimm_ctx* c, const uint64_t* key, const int32_t* ref, co
         HIP_TRY(c, hipStreamSynchronize(c->stream));  // the caller may reuse its buffers on return
     }
     c->n_pushed += n;
-    c->rec.key = c->in_key.p;
-    c->rec.ref = c->in_ref.p;
-    c->rec.pos = c->in_pos.p;
-    c->rec.flag = nullptr;
-    c->rec.packed = true;
-    c->rec.n = static_cast<uint32_t>(c->n_pushed);
+    view_records(c);
     return SLIMM_OK;
 }
 int slimm_push_records_packed(slimm_ctx* c, const uint64_t* key, const int32_t* ref, const int32_t* pos, uint64_t n) {
@@ -189,8 +184,7 @@ static int push_marked(slimm_ctx* c, const uint32_t* word, const int32_t* pos, u
     if (c->has_check || c->packed || (c->n_pushed && !c->marked))
         return fail(c, SLIMM_E_INVALID, "earlier batches were not run-marked records: the forms do not mix within a file");
     c->marked = true;
-    int rc = slimm_reserve(c, c->n_pushed + n);
-    if (rc != SLIMM_OK) return rc;
+    SLIMM_TRY(slimm_reserve(c, c->n_pushed + n));
     const uint64_t o = c->n_pushed;
     if (on_copy_stream) HIP_TRY(c, need_stream(c->copy_stream, kStreamHigh));
     hipStream_t st = on_copy_stream ? c->copy_stream : c->stream;
@@ -203,11 +197,7 @@ static int push_marked(slimm_ctx* c, const uint32_t* word, const int32_t* pos, u
         HIP_TRY(c, hipStreamSynchronize(c->stream));  // the caller may reuse its buffers on return
     }
     c->n_pushed += n;
-    c->rec = DeviceRecords();
-    c->rec.ref = c->in_ref.p;
-    c->rec.pos = c->in_pos.p;
-    c->rec.marked = true;
-    c->rec.n = static_cast<uint32_t>(c->n_pushed);
+    view_records(c);
     return SLIMM_OK;
 }
 int slimm_push_records_marked(slimm_ctx* c, const uint32_t* word, const int32_t* pos, uint64_t n) {
@@ -267,8 +257,7 @@ int slimm_push_staged_async(slimm_ctx* c, uint32_t which, uint64_t n) {
     slimm_ctx::Staging& sg = c->staging[which];
     if (n > sg.key.cap) return fail(c, SLIMM_E_INVALID, "more records than the staging set holds");
     if (n == 0) return SLIMM_OK;
-    int rc = slimm_push_records_async(c, sg.key.p, sg.ref.p, sg.pos.p, sg.flag.p, n);
-    if (rc != SLIMM_OK) return rc;
+    SLIMM_TRY(slimm_push_records_async(c, sg.key.p, sg.ref.p, sg.pos.p, sg.flag.p, n));
     HIP_TRY(c, hipEventRecord(sg.done, c->copy_stream));
     sg.pending = true;
     return SLIMM_OK;
@@ -279,8 +268,7 @@ int slimm_push_staged_packed_async(slimm_ctx* c, uint32_t which, uint64_t n) {  
     slimm_ctx::Staging& sg = c->staging[which];
     if (n > sg.key.cap) return fail(c, SLIMM_E_INVALID, "more records than the staging set holds");
     if (n == 0) return SLIMM_OK;
-    int rc = push_packed(c, sg.key.p, sg.ref.p, sg.pos.p, n, true);
-    if (rc != SLIMM_OK) return rc;
+    SLIMM_TRY(push_packed(c, sg.key.p, sg.ref.p, sg.pos.p, n, true));
     HIP_TRY(c, hipEventRecord(sg.done, c->copy_stream));
     sg.pending = true;
     return SLIMM_OK;
@@ -291,8 +279,7 @@ int slimm_push_staged_marked_async(slimm_ctx* c, uint32_t which, uint64_t n) {  
     slimm_ctx::Staging& sg = c->staging[which];
     if (n > sg.key.cap) return fail(c, SLIMM_E_INVALID, "more records than the staging set holds");
     if (n == 0) return SLIMM_OK;
-    int rc = push_marked(c, reinterpret_cast<const uint32_t*>(sg.ref.p), sg.pos.p, n, true);
-    if (rc != SLIMM_OK) return rc;
+    SLIMM_TRY(push_marked(c, reinterpret_cast<const uint32_t*>(sg.ref.p), sg.pos.p, n, true));
     HIP_TRY(c, hipEventRecord(sg.done, c->copy_stream));
     sg.pending = true;
     return SLIMM_OK;

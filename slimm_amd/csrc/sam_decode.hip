@@ -2,7 +2,7 @@
 // src/slimm.hpp:194-208; src/file_helper.hpp:73-75 takes .sam and .bam alike) for the four fields its record loop reads --
 // QNAME, FLAG, RNAME (-> the header's reference index), POS -- from windows of the file's text behind the header.
 // The counterpart of bam_decode.hip; the window pipeline around it (copies, the incomplete last line carried in front of the
-// next window, the record arrays) is the same (context.hip: bam_push_window).
+// next window, the record arrays) is the same (windows.hip: push_window).
 //
 //   k_sam_pieces   a LANE per 8 KB piece: the lines that START in the piece -- 16 bytes at a time, newline and tab bytes
 //                  found by word arithmetic --, their offsets (bit 31: the line has fewer than ten fields, is empty or starts
@@ -299,7 +299,7 @@ __global__ __launch_bounds__(64) void k_sam_carry(const uint8_t* __restrict__ b,
 }
 
 // The text's last line, when its last bytes were inflated here: without its newline it ends at `end` all the same, as a
-// line the host hands over does (bam_push_window gives that one its newline before the copy).  One lane: a byte is looked at.
+// line the host hands over does (windows.hip: push_plain gives that one its newline before the copy).  One lane: a byte is looked at.
 __global__ __launch_bounds__(64) void k_sam_end_line(uint8_t* __restrict__ b, uint64_t lo, uint64_t end, uint32_t* __restrict__ ended) {
     if (threadIdx.x != 0) return;
     const bool open = end > lo && b[end - 1] != '\n';

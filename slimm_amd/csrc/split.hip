@@ -114,10 +114,10 @@ namespace slimm {
 
 int split_range(slimm_ctx* c, SplitRange* out) {
     if (!c || !out) return SLIMM_E_INVALID;
-    if (c->device < 0 || !c->bam.active || !c->bam.closed || c->bam.sam || c->order != SLIMM_ORDER_GROUPED)
+    if (c->device < 0 || !c->win.file.active || !c->win.file.closed || c->win.file.sam || c->order != SLIMM_ORDER_GROUPED)
         return fail(c, SLIMM_E_INVALID, "a range of a split file: a GROUPED BAM range pushed to its end");
-    out->found_start = c->bam.found_start || !c->bam.starts_mid;
-    out->head_len = c->bam.starts_mid ? c->bam.head_len : 0u;
+    out->found_start = c->win.file.found_start || !c->win.announced.starts_mid;
+    out->head_len = c->win.announced.starts_mid ? c->win.file.head_len : 0u;
     out->n_records = c->n_pushed;
     return SLIMM_OK;
 }
@@ -125,26 +125,25 @@ int split_range(slimm_ctx* c, SplitRange* out) {
 int split_append_head(slimm_ctx* left, slimm_ctx* right, bool final, uint64_t* n_records) {
     (void)hipSetDevice(right->device);
     HIP_TRY(right, hipStreamSynchronize(right->stream));   // (the head was copied aside on the right member's stream)
-    const uint64_t n = right->bam.starts_mid ? right->bam.head_len : 0u;
+    const uint64_t n = right->win.announced.starts_mid ? right->win.file.head_len : 0u;
     uint64_t got = 0;
-    const int rc = bam_append_window(left, right->bam.head_bytes.p, right->device, n, final, got);
-    if (rc != SLIMM_OK) return rc;
+    SLIMM_TRY(append_window(left, right->win.head_bytes.p, right->device, n, final, got));
     HIP_TRY(left, hipStreamSynchronize(left->stream));
     if (n_records) *n_records = got;
     return SLIMM_OK;
 }
 
 int split_join(slimm_ctx* left, slimm_ctx* right) {
-    slimm_ctx::BamDecode& R = right->bam;
-    if (!R.has_first || !right->n_pushed || !left->bam.carry.p) return SLIMM_OK;   // (nothing on one side: no run to join)
+    WindowPipeline& R = right->win;
+    if (!R.file.has_first || !right->n_pushed || !left->win.carry.p) return SLIMM_OK;   // (nothing on one side: no run to join)
     (void)hipSetDevice(left->device);
     HIP_TRY(left, hipStreamSynchronize(left->stream));
     (void)hipSetDevice(right->device);
     HIP_TRY(right, R.join.ensure(1));
     if (left->device == right->device)
-        HIP_TRY(right, hipMemcpyAsync(R.join.p, left->bam.carry.p, sizeof(BamCarry), hipMemcpyDeviceToDevice, right->stream));
+        HIP_TRY(right, hipMemcpyAsync(R.join.p, left->win.carry.p, sizeof(BamCarry), hipMemcpyDeviceToDevice, right->stream));
     else
-        HIP_TRY(right, hipMemcpyPeerAsync(R.join.p, right->device, left->bam.carry.p, left->device, sizeof(BamCarry), right->stream));
+        HIP_TRY(right, hipMemcpyPeerAsync(R.join.p, right->device, left->win.carry.p, left->device, sizeof(BamCarry), right->stream));
     launch_split_join(right->stream, R.join.p, R.first.p, R.carry.p, reinterpret_cast<uint32_t*>(right->in_ref.p));
     HIP_TRY(right, hipGetLastError());
     HIP_TRY(right, hipStreamSynchronize(right->stream));
@@ -156,12 +155,12 @@ int split_first_start(slimm_ctx* c, uint64_t* index) {
     *index = n;
     if (!n) return SLIMM_OK;
     (void)hipSetDevice(c->device);
-    HIP_TRY(c, c->bam.guess.ensure(1));
+    HIP_TRY(c, c->win.guess.ensure(1));
     unsigned long long v = n;
-    HIP_TRY(c, hipMemcpyAsync(c->bam.guess.p, &v, sizeof(v), hipMemcpyHostToDevice, c->stream));
-    launch_split_first_start(c->stream, reinterpret_cast<const uint32_t*>(c->in_ref.p), n, c->bam.guess.p);
+    HIP_TRY(c, hipMemcpyAsync(c->win.guess.p, &v, sizeof(v), hipMemcpyHostToDevice, c->stream));
+    launch_split_first_start(c->stream, reinterpret_cast<const uint32_t*>(c->in_ref.p), n, c->win.guess.p);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(&v, c->bam.guess.p, sizeof(v), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&v, c->win.guess.p, sizeof(v), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     *index = v;
     return SLIMM_OK;
@@ -174,8 +173,7 @@ int split_take(slimm_ctx* dst, slimm_ctx* src, uint64_t n) {
     (void)hipSetDevice(src->device);
     HIP_TRY(src, hipStreamSynchronize(src->stream));
     (void)hipSetDevice(dst->device);
-    int rc = slimm_reserve(dst, dst->n_pushed + n);
-    if (rc != SLIMM_OK) return rc;
+    SLIMM_TRY(slimm_reserve(dst, dst->n_pushed + n));
     const uint64_t at = dst->n_pushed;
     if (dst->device == src->device) {
         HIP_TRY(dst, hipMemcpyAsync(dst->in_ref.p + at, src->in_ref.p, n * 4, hipMemcpyDeviceToDevice, dst->stream));
@@ -191,13 +189,9 @@ int split_take(slimm_ctx* dst, slimm_ctx* src, uint64_t n) {
 
 int split_keep(slimm_ctx* c, uint64_t from) {
     if (from > c->n_pushed) return fail(c, SLIMM_E_INVALID, "split_keep: past the member's records");
-    c->rec = DeviceRecords();
-    c->rec.ref = c->in_ref.p ? c->in_ref.p + from : nullptr;
-    c->rec.pos = c->in_pos.p ? c->in_pos.p + from : nullptr;
-    c->rec.marked = true;
-    c->rec.n = static_cast<uint32_t>(c->n_pushed - from);
     c->marked = true;
-    c->bam.q18_by_group = true;
+    view_records(c, from);
+    c->win.file.q18_by_group = true;
     return SLIMM_OK;
 }
 

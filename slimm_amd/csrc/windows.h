@@ -1,0 +1,174 @@
+// The window pipeline's state (windows.hip; bzip2_decode.hip and split.hip work on it too), in three parts by how long they
+// live: what the context keeps (buffers, streams, events), what the caller announces for the next file, and the file's own
+// state, which is reset in one place.  Included by context.h (DevBuf, PinBuf).
+#pragma once
+
+struct slimm_ctx;
+namespace slimm {
+
+struct WindowPipeline {
+    // The ring of window buffers [slack | window]: a window is copied -- or inflated -- into one while older ones are still
+    // on their way or being decoded: at most kWindowLag of them, and at most kWindowInFlight bytes; the incomplete record at
+    // a window's end is copied in front of the next window.  Windows that arrive as BGZF blocks are gathered into device
+    // windows of up to kWindowGather inflated bytes, three of which keep both inflate streams busy; a ring of 16 buffers of
+    // that size was 20 - 25 GB of HBM per context, ADVICE round 4
+    static constexpr uint32_t kWindowRing = 4, kWindowLag = kWindowRing - 2;
+    static constexpr uint64_t kWindowInFlight = 4ull << 30;    // finish the oldest window when more than this is in flight
+    static constexpr uint64_t kWindowGather = 1900ull << 20;   // inflated bytes of a gathered device window (a window is < 2 GiB)
+    static constexpr uint64_t kWindowGatherGoal = 1400ull << 20;  // ... which is launched once it holds this much
+    static constexpr uint64_t kWindowKeepAcrossFiles = 4ull << 30; // end_file gives the pipeline's buffers back above this
+
+    // ---- as long as the context
+    DevBuf<uint8_t> bytes[kWindowRing];
+    DevBuf<BamPiece> pieces;
+    DevBuf<uint32_t> offs;
+    DevBuf<BamCarry> carry;
+    PinBuf<BamWindowResult> result;     // written by k_bam_scan straight into page-locked host memory
+    std::vector<std::pair<const uint8_t*, size_t>> registered;  // caller buffers page-locked by hipHostRegister
+    hipEvent_t copied[kWindowRing] = {};   // the window's bytes are in its buffer (behind the copy, or behind the inflate)
+    hipEvent_t h2d_done[4] = {};        // the caller's buffer of a push has been read (the pushes' events, in turn)
+    // windows that arrive as BGZF blocks (slimm_push_bgzf_blocks, slimm_push_bgzf_sam_blocks): compressed bytes + block
+    // descriptors per buffer, the inflater's scratch and {error code, first bad block, -, last line ended} per buffer
+    DevBuf<uint8_t> comp[kWindowRing];
+    DevBuf<BgzfBlock> desc[kWindowRing];
+    std::vector<BgzfBlock> desc_host[kWindowRing];   // (a buffer's descriptors stay until the buffer's turn comes again: the copy reads them)
+    DevBuf<uint8_t> inflate_scratch[2];
+    DevBuf<uint32_t> inflate_status;       // 4 words per buffer
+    PinBuf<uint32_t> h_inflate_status;     // ... fetched with the window's other results
+    // the inflate kernels' own streams, taken in turn by the device windows: the copies of other windows go on beside
+    // them, and the Huffman phase of one window (a lane per block: 30 K blocks are half the lanes) beside the other's
+    hipStream_t inflate_stream[2] = {nullptr, nullptr};
+    hipEvent_t comp_copied = nullptr;
+    std::vector<void*> outgrown;   // device buffers replaced by larger ones while kernels were in flight: freed at the file's end
+    // SAM text (sam_decode.hip): the header's reference names as a hash table on the device (slimm_set_reference_names)
+    DevBuf<SamRefEntry> sam_table;
+    DevBuf<uint8_t> sam_names;
+    uint32_t sam_mask = 0;
+    // a byte range of a split file (split.hip): the head, the first record's name, the left member's carry, the guess
+    DevBuf<uint8_t> head_bytes;
+    DevBuf<BamCarry> first, join;
+    DevBuf<unsigned long long> guess;
+    // bzip2 SAM (bzip2_decode.hip), the decode scratch: the compressed bytes not decoded yet, the candidates (block magics),
+    // and per slot of a batch the BWT string -- then its RLE1 text --, the inverse BWT's links, the byte histogram, what
+    // decoding found and the text's length
+    struct Bzip2 {
+        DevBuf<uint8_t> comp, ll;
+        DevBuf<uint32_t> link, hist, count, text_len;
+        DevBuf<unsigned long long> d_cand;
+        DevBuf<bz2::BlockInfo> info;
+        DevBuf<int64_t> out_at;
+        template <typename F>
+        void each_held(F&& f) { f(comp), f(ll), f(link), f(hist), f(d_cand); }   // (the large ones: see each_held below)
+        uint64_t held() {
+            uint64_t n = 0;
+            each_held([&](auto& b) { n += b.cap * sizeof(*b.p); });
+            return n;
+        }
+    } bz2;
+
+    // ---- announced before the file's first window (slimm_set_input_size_hint, slimm_set_input_mid_file), cleared when it ends
+    struct Announced {
+        uint64_t size_hint = 0;   // the file's compressed bytes (0 = not told): what its gathered windows are sized for
+        // a byte range of a file split over a group: it starts inside the file (its first record is guessed; the bytes in
+        // front, the head, wait on the device for the member on the left) and / or ends inside it (the carry stays)
+        bool starts_mid = false, ends_mid = false;
+    } announced;
+
+    // ---- this file: reset as a whole, by end_file alone -- a new member needs its initialiser and nothing else
+    struct File {
+        bool active = false;                // this file's records come through the window pipeline
+        bool closed = false;                // the file's last window went in
+        bool sam = false;                   // its windows are SAM text
+        uint64_t windows = 0;               // handed over so far
+        uint64_t head = 0;                  // ... of which [head, windows) are not finished yet (copied / inflating / waiting)
+        uint64_t win_bytes[kWindowRing] = {};  // record bytes of the windows in flight
+        bool inflated[kWindowRing] = {};    // that window was inflated here
+        uint64_t carry_bytes = 0;
+        uint64_t pushes = 0;                // pushes that started a copy
+        // BGZF pushes gathered for the next device window (buffer windows % kWindowRing): compressed bytes so far, inflated
+        // bytes so far, the inflated bytes in front of the file's first record
+        bool acc_open = false;
+        uint64_t acc_src = 0, acc_dst = 0;
+        uint32_t acc_skip = 0, acc_tok = 0;   // (acc_tok: words of token room of the gathered blocks)
+        // from the size hint and the first push's ratio: the inflated bytes a gathered window's buffer gets (0 = kWindowGather)
+        uint64_t win_cap = 0;
+        bool planned = false;               // the file's first COMPRESSED push has reserved its buffers (or found no hint)
+        // SAM text: the last byte pushed (a last line without its newline gets one) -- unless the text's last bytes so far
+        // were inflated on the device: the device then ends such a line; lines it ended so far (SLIMM_TRACE=push)
+        uint8_t sam_last_byte = '\n';
+        bool sam_dev_tail = false;
+        uint64_t sam_lines_ended = 0;
+        // Q18 on a grouped stream (kernels.h: BamCarry): the decoders' two counts of the windows finished so far; a range
+        // of a split file: summed by the group (slimm_group_stitch_ranges), not checked per member
+        uint64_t q18_starts = 0, q18_plain = 0;
+        bool q18_by_group = false;
+        bool found_start = false;   // a range that starts inside the file: its first window holds a record start (false: all head)
+        bool has_first = false;     // `first` holds the name of the range's first record (decoded in any window)
+        uint64_t head_len = 0;
+        // bzip2 SAM, the host's side: the compressed bytes not decoded yet (file offset `base` on; the next bit to read),
+        // the stream being read (its level, combined CRC so far), the decoded bytes still to skip; the block magics found
+        // in them (bit offsets into pend, in order) and the next one to look at; the blocks of the last batch decoded and
+        // not yet written into a window
+        struct Bzip2 {
+            bool on = false;
+            std::vector<uint8_t> pend;
+            uint64_t base = 0, bit = 0;
+            bool in_stream = false;
+            uint32_t level = 0, combined = 0, streams = 0;
+            uint64_t skip_left = 0;
+            std::vector<uint64_t> cand;
+            size_t next_cand = 0;
+            bool found = false;     // cand holds the magics of pend as it is
+            bool waiting = false;   // the chain stopped for want of bytes: nothing to decode until pend grows
+            uint32_t slots = 0;     // blocks a batch decodes at most (the scratch holds that many; sized per file: bz2_reserve)
+            struct Ready {
+                uint32_t slot, crc;
+                uint64_t len, drop;   // text bytes; of them the first `drop` are skipped (the header)
+                uint64_t at;          // file offset of the block (errors)
+            };
+            std::vector<Ready> ready;
+            size_t ready_pos = 0;
+            uint64_t blocks = 0, batches = 0, false_magics = 0;   // (SLIMM_TRACE=push; false_magics: candidates the chain passed over)
+            double ms_find = 0, ms_decode = 0, ms_bwt = 0, ms_emit = 0;
+        } bz2;
+    } file;
+
+    // the buffers that grow with a file's windows: what held_bytes() counts is what end_file gives back
+    template <typename F>
+    void each_held(F&& f) {
+        for (uint32_t k = 0; k < kWindowRing; ++k) f(bytes[k]), f(comp[k]), f(desc[k]);
+        for (auto& sc : inflate_scratch) f(sc);
+        f(pieces), f(offs);
+        bz2.each_held(f);
+    }
+    uint64_t held_bytes() {   // device memory of the window pipeline (slimm_window_memory)
+        uint64_t n = 0;
+        each_held([&](auto& b) { n += b.cap * sizeof(*b.p); });
+        return n;
+    }
+    void free_outgrown();
+    // slimm_reset: abandoned windows and an unlaunched gather waited for, `outgrown` freed, the file's and the announced
+    // state fresh, the buffers given back when they hold more than kWindowKeepAcrossFiles.  No HIP call unless windows or a
+    // gather are pending or there is something to free (a host-only context is reset too)
+    int end_file(slimm_ctx* c);
+    // slimm_destroy, once the context's main and copy streams are idle: the inflate streams waited for and destroyed, the
+    // caller's buffers unlocked, `outgrown` freed, the events destroyed (the buffers free themselves)
+    void destroy();
+};
+
+// SLIMM_TRACE=push: what the pipeline does and when, on stderr: "[push <ms since the first line>] ...", or "[push <tag>] ..."
+void push_trace_line(const char* tag, const char* fmt, va_list ap);
+void push_trace(const char* fmt, ...);
+int fetch_q18(slimm_ctx* c);   // the Q18 run counts of the device decoders so far (every window launched) -> file.q18_*
+// `n` bytes at `src` (on device src_device) as one more window behind the closed file's carry (split.hip)
+int append_window(slimm_ctx* c, const uint8_t* src, int src_device, uint64_t n, bool final, uint64_t& n_rec);
+// bzip2_decode.hip (slimm_push_bzip2_sam_bytes): the next batch of whole blocks of file.bz2.pend decoded up to their text
+// lengths (file.bz2.ready; none: the chain waits for more bytes, or the streams have ended); at `last` what is left must
+// end the streams.  Then, window by window: the text bytes of the next ready blocks that fit in `cap` (at least one
+// block), and those written to dst on the context's stream, their CRCs checked, *last_byte = the text's last byte
+int bz2_decode_batch(slimm_ctx* c, bool last);
+uint64_t bz2_window_bytes(const slimm_ctx* c, uint64_t cap, size_t* n_blocks);
+int bz2_emit(slimm_ctx* c, uint8_t* dst, size_t n_blocks, uint8_t* last_byte);
+void bz2_trace_file(const slimm_ctx* c);   // SLIMM_TRACE=push (read at every call): the file's streams, blocks, false magics, times
+
+}  // namespace slimm
