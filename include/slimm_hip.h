@@ -567,22 +567,36 @@ enum { SLIMM_EXCHANGE_AUTO = 0, SLIMM_EXCHANGE_SUMMARY = 1, SLIMM_EXCHANGE_SLICE
 int slimm_group_set_exchange(slimm_group* g, int mode);
 int slimm_group_exchange(const slimm_group* g); /* the form in effect (what AUTO resolves to) */
 int slimm_group_get_profiles(slimm_group* g, const char* path); /* path may be NULL; SLIMM_E_NO_HITS like slimm_get_profiles */
-/* ONE BAM FILE SPLIT BY BYTE RANGE over a group (GROUPED files): every member reads, inflates and decodes its own contiguous
- * range of the file's BGZF blocks at once.  slimm_host_bgzf_ranges plans the ranges (host only, no GPU): offsets_out[0, n]
- * with offsets_out[0] = 0 and offsets_out[n] = the file's size; range i = [offsets_out[i], offsets_out[i + 1]) starts on a
+/* ONE FILE SPLIT BY BYTE RANGE over a group (GROUPED files): every member reads, inflates and decodes its own contiguous
+ * range of the file at once.  Three forms of file: BAM, SAM text, and SAM text in BGZF blocks (bgzip).  (A plain gzip
+ * stream cannot be cut, and a bzip2 file's blocks start at bit offsets: those go through one member.)
+ *   The plan (host only, no GPU): offsets_out[0, n]; range i = [offsets_out[i], offsets_out[i + 1]), ranges may be empty.
+ * slimm_host_bgzf_ranges -- BAM and BGZF SAM --: offsets_out[0] = 0, offsets_out[n] = the file's size; a range starts on a
  * BGZF block boundary (a header whose next three headers chain through BSIZE + 1, or whose chain reaches the EOF block or
- * the file's end), ranges may be empty; no cut lies in front of the block that holds inflated byte `skip` (the BAM header's
- * inflated length: member 0 takes all of it and pushes its first blocks with that skip).  Every member but the first calls
- * slimm_set_input_mid_file(ctx, 1, ...) before its first push -- its first record is guessed from the bytes, the bytes in
- * front of it (at most 16 MiB) are kept on the device -- and every member but the last (..., 1): its last push may end
- * inside a record.  Each member then pushes its range with slimm_push_bgzf_blocks (last = 1 at the range's end), all at
- * once, and slimm_group_stitch_ranges joins the cuts on the devices: the bytes around a cut are decoded by the member on
- * its left, which must end exactly where the right member's guess begins (otherwise SLIMM_E_SPLIT: read the file through
+ * the file's end); no cut lies in front of the block that holds inflated byte `skip` (the header's inflated length: member
+ * 0 takes all of it and pushes its first blocks with that skip).  slimm_host_text_ranges -- plain SAM --: offsets_out[0] =
+ * skip, the file offset of the first alignment line, offsets_out[n] = the file's size, the bytes between divided evenly
+ * and cut anywhere; SLIMM_E_INVALID for a path that is no regular file or a skip beyond its size.
+ *   What a member does FIRST, before its first push: SAM text in either form names its references, so every member gets
+ * the header's names with slimm_set_reference_names; every member but the first calls slimm_set_input_mid_file(ctx, 1, ...)
+ * and every member but the last (..., 1); slimm_set_input_size_hint(ctx, the range's bytes) sizes a BGZF range's windows.
+ * A range that starts inside the file finds its first record in its first window, on the device, and keeps the bytes in
+ * front of it -- the head, at most 16 MiB -- there for the member on its left.  BAM: the first record is guessed from the
+ * bytes.  SAM: the first line starts behind the first newline, the head is the bytes through that newline (a whole line
+ * when the cut fell on a line start), and no newline within 16 MiB of a range's first window that is not also its last is
+ * SLIMM_E_SPLIT.  A range that ends inside the file may end inside a record or a line: what is left stays as the carry;
+ * an incomplete last line gets no newline there (only the file's last member ends a last line that lacks one; when that
+ * member's range holds no text at all -- it is empty, or a BGZF EOF block only -- the stitch ends the line instead).
+ *   Each member then pushes its range -- slimm_push_bgzf_blocks, slimm_push_sam_bytes or slimm_push_bgzf_sam_blocks, last =
+ * 1 at the range's end; an empty range is one push of no bytes with last = 1 -- all members at once, and
+ * slimm_group_stitch_ranges joins the cuts on the devices: the bytes around a cut are decoded by the member on its left,
+ * which must end exactly where the right member's first record begins (otherwise SLIMM_E_SPLIT: read the file through
  * member 0 instead); the run of a read name that a cut splits moves, device to device, to the member that holds its
  * start; the Q18 counts are summed over the members (SLIMM_E_REGROUP as for one context).  slimm_group_get_profiles then
  * runs on the members' records as they are (no dealing from member 0).  This is also how ONE device takes a file of more
  * records than one context holds: a group that names the same device several times. */
 int slimm_host_bgzf_ranges(const char* path, uint64_t skip, uint32_t n, uint64_t* offsets_out);
+int slimm_host_text_ranges(const char* path, uint64_t skip, uint32_t n, uint64_t* offsets_out);
 int slimm_set_input_mid_file(slimm_ctx* ctx, int starts_mid_file, int ends_mid_file);
 int slimm_group_stitch_ranges(slimm_group* g);
 /* the most records one context takes (below 2^31; SLIMM_FORCE record_cap=N lowers it, for tests) */

@@ -646,7 +646,7 @@ static int deal_from_member0(slimm_group* g) {
     return SLIMM_OK;
 }
 
-// A file read by byte range, every member its own (include/slimm_hip.h, "ONE BAM FILE SPLIT BY BYTE RANGE"; split.hip):
+// A file read by byte range, every member its own (include/slimm_hip.h, "ONE FILE SPLIT BY BYTE RANGE"; split.hip):
 //   1. the bytes around every cut -- the incomplete last record of the nearest member on the left that holds a record
 //      start, and the right member's head -- are decoded by that left member, and must end exactly where the right
 //      member's guess begins (SLIMM_E_SPLIT otherwise); a member without a record start hands its bytes on to the left

@@ -723,7 +723,7 @@ bool AlignmentFile::read_sam_header() {
             ref_len_.push_back(len);
         }
     }
-    if (comp_ == Compression::Bgzf || comp_ == Compression::Bzip2) header_bytes_ = sam_body_off_;
+    if (comp_ != Compression::Gzip) header_bytes_ = sam_body_off_;   // (plain text: the file offset itself)
     return true;
 }
 

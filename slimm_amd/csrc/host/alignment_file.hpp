@@ -86,7 +86,7 @@ public:
     const std::vector<uint32_t>& ref_lengths() const { return ref_len_; }
     SortOrder sort_order() const { return order_; }
     // BAM / BGZF SAM / bzip2 SAM: the header's inflated bytes -- where the first alignment record (line) starts in the
-    // inflated (decoded) stream
+    // inflated (decoded) stream; plain SAM: the file offset of the first alignment line
     uint64_t header_bytes() const { return header_bytes_; }
     // Q18 on a file grouped by QNAME (include/slimm_hip.h, "Q18 ON A GROUPED STREAM"): among the records read_batch /
     // read_into have handed out, some run of adjacent records with one canonical base holds SHORTENED names only -- their

@@ -123,6 +123,7 @@ SLIMM_FORWARD(int, slimm_push_bgzf_sam_blocks, (slimm_ctx* a, const uint8_t* b, 
 SLIMM_FORWARD(int, slimm_push_bzip2_sam_bytes, (slimm_ctx* a, const uint8_t* b, uint64_t c, uint32_t s, int d, uint64_t* e), (a, b, c, s, d, e))
 SLIMM_FORWARD(int, slimm_pin_host_buffer, (slimm_ctx* a, const void* b, uint64_t c), (a, b, c))
 SLIMM_FORWARD(int, slimm_host_bgzf_ranges, (const char* a, uint64_t b, uint32_t c, uint64_t* d), (a, b, c, d))
+SLIMM_FORWARD(int, slimm_host_text_ranges, (const char* a, uint64_t b, uint32_t c, uint64_t* d), (a, b, c, d))
 SLIMM_FORWARD(int, slimm_set_input_mid_file, (slimm_ctx* a, int b, int c), (a, b, c))
 SLIMM_FORWARD(int, slimm_group_stitch_ranges, (slimm_group* a), (a))
 SLIMM_FORWARD(uint64_t, slimm_record_cap, (), ())
@@ -178,7 +179,7 @@ struct Options {  // arg_options, reference src/slimm.hpp:49-87
     bool verify_grouping = false;  // --verify-grouping: count the read names that come back (slimm_check_grouping) and warn
     unsigned device_inflate = 1;   // --device-inflate K: every K-th window read in place is inflated on the device (0: none)
     unsigned window_mb = 0;        // --window-mb N: bytes per window buffer (tests make windows smaller than a record)
-    bool split_input = false;      // --split-input (with --devices): every member reads its own byte range of a grouped BAM
+    bool split_input = false;      // --split-input (with --devices): every member reads its own byte range of a grouped BAM / SAM / BGZF SAM
 };
 bool g_trace = false;              // SLIMM_TRACE=cli (or all): millisecond marks of the stages on stderr
 
@@ -865,10 +866,14 @@ struct RecordPump {
     }
 };
 
-// --split-input: every member of a group reads, inflates and decodes its own contiguous byte range of a GROUPED BAM file
-// at once -- its own pread threads, page-locked buffers and pushing thread -- and the library stitches the cuts on the
-// devices (include/slimm_hip.h, "ONE BAM FILE SPLIT BY BYTE RANGE").  The reader threads are split over the members, not
-// multiplied (a command gets 16 CPUs).  Returns SLIMM_OK or the code of what failed; *why says what.
+// --split-input: every member of a group reads, inflates and decodes its own contiguous byte range of a GROUPED file at
+// once -- its own pread threads, page-locked buffers and pushing thread -- and the library stitches the cuts on the
+// devices (include/slimm_hip.h, "ONE FILE SPLIT BY BYTE RANGE").  The file's form: BAM or SAM text in BGZF blocks -- ranges
+// of whole blocks, member 0 skips the header's inflated bytes -- or plain SAM text: ranges cut anywhere behind the header,
+// read as they lie in the file (`names`: the header's reference names, which every member's SAM decoder needs).  The
+// reader threads are split over the members, not multiplied (a command gets 16 CPUs).  Returns SLIMM_OK or the code of
+// what failed; *why says what.
+enum class SplitForm { Bam, BgzfSam, Sam };
 struct SplitBuffers {   // (page-locked for the life of the group's contexts: they outlive the group)
     struct Map {
         uint8_t* p = nullptr;
@@ -886,13 +891,17 @@ struct SplitBuffers {   // (page-locked for the life of the group's contexts: th
         return static_cast<uint8_t*>(p);
     }
 };
-int read_split(slimm_group* grp, uint32_t G, const std::string& path, uint64_t header_bytes, size_t window_cap, SplitBuffers& bufs,
-               std::string& why) {
+int read_split(slimm_group* grp, uint32_t G, const std::string& path, SplitForm form, const std::vector<std::string>& names,
+               uint64_t header_bytes, size_t window_cap, SplitBuffers& bufs, std::string& why) {
     std::vector<uint64_t> off(G + 1, 0);
-    if (header_bytes >= (1ull << 32) || slimm_host_bgzf_ranges(path.c_str(), header_bytes, G, off.data()) != SLIMM_OK) {
-        why = "the file's BGZF blocks could not be planned into ranges";
+    const bool text = form == SplitForm::Sam, sam = form != SplitForm::Bam;
+    if (text ? slimm_host_text_ranges(path.c_str(), header_bytes, G, off.data()) != SLIMM_OK
+             : (header_bytes >= (1ull << 32) || slimm_host_bgzf_ranges(path.c_str(), header_bytes, G, off.data()) != SLIMM_OK)) {
+        why = text ? "the file's text could not be planned into ranges" : "the file's BGZF blocks could not be planned into ranges";
         return SLIMM_E_INVALID;
     }
+    std::vector<const char*> name_ptrs;
+    for (const std::string& nm : names) name_ptrs.push_back(nm.c_str());
     const int fd = open(path.c_str(), O_RDONLY);
     if (fd < 0) {
         why = "could not open " + path;
@@ -927,15 +936,21 @@ int read_split(slimm_group* grp, uint32_t G, const std::string& path, uint64_t h
             M.rc = rc;
             M.err = "member " + std::to_string(i) + ": " + e;
         };
-        int rc = slimm_set_input_mid_file(ctx, i > 0 ? 1 : 0, i + 1 < G ? 1 : 0);
+        int rc = sam ? slimm_set_reference_names(ctx, name_ptrs.data()) : SLIMM_OK;
+        if (rc == SLIMM_OK) rc = slimm_set_input_mid_file(ctx, i > 0 ? 1 : 0, i + 1 < G ? 1 : 0);
         if (rc == SLIMM_OK) rc = slimm_set_input_size_hint(ctx, off[i + 1] - off[i]);
         if (rc != SLIMM_OK) return failed(rc, slimm_last_error(ctx));
         for (auto* b : M.buf) (void)slimm_pin_host_buffer(ctx, b, cap);   // (pageable memory still works)
         const uint64_t end = off[i + 1];
         // whole BGZF blocks of [at, end) into buffer w, at most `cap` bytes, by pread on the member's share of the threads:
-        // the bytes of those blocks (0: none fits), -1 on a read error
+        // the bytes of those blocks (0: none fits), -1 on a read error.  Blocks of SAM text end a push at `max_inflated`
+        // inflated bytes as well (a push is one device window at most, and text may compress 24-fold: 80 MB of blocks
+        // fill it; as RecordPump::device_window bounds one context's pushes); read_hint: what is worth reading once that
+        // bound has ended a push.  Plain text: the bytes as they lie there, cut anywhere
+        const uint64_t max_inflated = sam ? std::min<uint64_t>(10ull * cap, 1900ull << 20) : ~0ull;
+        size_t read_hint = cap;
         auto read_blocks = [&](unsigned w, uint64_t at) -> long {
-            const size_t want = static_cast<size_t>(std::min<uint64_t>(cap, end - at));
+            const size_t want = static_cast<size_t>(std::min<uint64_t>(std::min(cap, read_hint), end - at));
             if (!want) return 0;
             const unsigned nt = static_cast<unsigned>(std::max<size_t>(1, std::min<size_t>(per_member, want >> 20)));
             const size_t per = (want + nt - 1) / nt;
@@ -956,11 +971,22 @@ int read_split(slimm_group* grp, uint32_t G, const std::string& path, uint64_t h
                 });
             for (auto& t : th) t.join();
             if (!ok) return -1;
+            if (text) return static_cast<long>(want);
             size_t n = 0;
+            uint64_t inflated = 0;
             while (want - n >= 18) {
                 const uint8_t* h = M.buf[w] + n;
                 const size_t bsize = (static_cast<size_t>(h[16]) | (static_cast<size_t>(h[17]) << 8)) + 1u;
                 if (h[0] != 0x1f || h[1] != 0x8b || want - n < bsize) break;
+                const uint8_t* t = h + bsize - 4;   // (ISIZE)
+                const uint64_t isize = !sam || bsize < 28u ? 0u
+                                                           : static_cast<uint64_t>(t[0]) | (static_cast<uint64_t>(t[1]) << 8) |
+                                                                 (static_cast<uint64_t>(t[2]) << 16) | (static_cast<uint64_t>(t[3]) << 24);
+                if (n && inflated + isize > max_inflated) {
+                    read_hint = n + (n >> 2) + (1u << 16);
+                    break;
+                }
+                inflated += isize;
                 n += bsize;
             }
             return static_cast<long>(n);
@@ -985,9 +1011,15 @@ int read_split(slimm_group* grp, uint32_t G, const std::string& path, uint64_t h
                 });
             uint64_t got = 0;
             t0 = std::chrono::steady_clock::now();
-            rc = n ? slimm_push_bgzf_blocks(ctx, M.buf[w], static_cast<uint64_t>(n), pos == off[i] && i == 0 ? static_cast<uint32_t>(header_bytes) : 0u,
-                                            last ? 1 : 0, &got)
-                   : slimm_push_bam_bytes(ctx, nullptr, 0, 1, &got);   // (an empty range)
+            const uint32_t skip = pos == off[i] && i == 0 ? static_cast<uint32_t>(header_bytes) : 0u;
+            const uint64_t nb = static_cast<uint64_t>(n);
+            if (!n)   // (an empty range)
+                rc = sam ? slimm_push_sam_bytes(ctx, nullptr, 0, 1, &got) : slimm_push_bam_bytes(ctx, nullptr, 0, 1, &got);
+            else if (text)
+                rc = slimm_push_sam_bytes(ctx, M.buf[w], nb, last ? 1 : 0, &got);
+            else
+                rc = sam ? slimm_push_bgzf_sam_blocks(ctx, M.buf[w], nb, skip, last ? 1 : 0, &got)
+                         : slimm_push_bgzf_blocks(ctx, M.buf[w], nb, skip, last ? 1 : 0, &got);
             const double t = ms(t0);
             if (ahead.joinable()) ahead.join();
             M.pread_ms += next_ms;
@@ -1021,6 +1053,15 @@ int read_split(slimm_group* grp, uint32_t G, const std::string& path, uint64_t h
     const int rc = slimm_group_stitch_ranges(grp);
     if (rc != SLIMM_OK) why = slimm_group_last_error(grp);
     return rc;
+}
+
+// The files read_split takes: a regular file of BAM records, of SAM text, or of SAM text in BGZF blocks.  (A plain gzip
+// stream cannot be cut, and a bzip2 file's blocks start at bit offsets and chain from the first: those go through one member.)
+bool reads_by_byte_range(const AlignmentFile& f) {
+    return f.regular_file() && (f.is_bam() || f.compression() == Compression::None || f.compression() == Compression::Bgzf);
+}
+SplitForm split_form(const AlignmentFile& f) {
+    return f.is_bam() ? SplitForm::Bam : (f.compression() == Compression::Bgzf ? SplitForm::BgzfSam : SplitForm::Sam);
 }
 
 // One reading of a file up to its context: the file open at its first record, the choices its header and the options make,
@@ -1183,8 +1224,12 @@ std::unique_ptr<Reading> set_up(Session& S, const std::string& path, bool any_or
     // decoding starts now; the records are claimed further down, when the context exists (one context: the device decodes)
     // (a group takes a GROUPED file through member 0's device decoders and deals the records device to device afterwards:
     // slimm_group_get_profiles; any other order: the host reader deals them by key)
-    F->split_input = options.split_input && options.devices.size() > 1 && F->record_order == SLIMM_ORDER_GROUPED && bam.is_bam() &&
-                     bam.regular_file() && !options.host_decode && !options.verify_grouping && !options.packed_records;
+    F->split_input = options.split_input && options.devices.size() > 1 && F->record_order == SLIMM_ORDER_GROUPED && reads_by_byte_range(bam) &&
+                     !options.host_decode && !options.verify_grouping && !options.packed_records;
+    if (g_trace && !any_order && options.split_input && options.devices.size() > 1 && !bam.is_bam() &&
+        (bam.compression() == Compression::Gzip || bam.compression() == Compression::Bzip2))
+        fprintf(stderr, "[trace] --split-input: a %s stream is not cut by byte range; member 0 reads %s\n",
+                bam.compression() == Compression::Gzip ? "gzip" : "bzip2", path.c_str());
     if (!F->split_input)
         F->pump.reset(new RecordPump(bam, F->check_words, options.devices.size() <= 1 || F->record_order == SLIMM_ORDER_GROUPED, options));
 
@@ -1230,7 +1275,7 @@ std::unique_ptr<Reading> set_up(Session& S, const std::string& path, bool any_or
 }
 
 // What a push that found more records than one context takes leads to (the --split-input reading decides in run_group):
-// a group reading through member 0 -- HostDecode, the host reader deals them; one context of a grouped BAM -- MoreMembers,
+// a group reading through member 0 -- HostDecode, the host reader deals them; one context of a grouped BAM, SAM or BGZF SAM -- MoreMembers,
 // a group on the device reads the file by byte range; any other one context -- Fail.
 enum class OnCap { Fail, HostDecode, MoreMembers };
 
@@ -1295,8 +1340,8 @@ Outcome run_group(Session& S, Reading& F, const std::vector<int>& devs, bool spl
     bool split_read = false;
     if (split) {   // every member its own byte range (read_split); what fails there goes through member 0 after all
         std::string why;
-        const int src = read_split(grp.get(), static_cast<uint32_t>(devs.size()), F.path, F.bam.header_bytes(), RecordPump::raw_cap(),
-                                   F.split_bufs, why);
+        const int src = read_split(grp.get(), static_cast<uint32_t>(devs.size()), F.path, split_form(F.bam), F.bam.ref_names(),
+                                   F.bam.header_bytes(), RecordPump::raw_cap(), F.split_bufs, why);
         F.trace.mark("split: read + decode + stitch");
         if (src == SLIMM_E_REGROUP) return Outcome::ReadAgainAnyOrder;
         if (src != SLIMM_OK && for_cap && classify(why.c_str()) == PushError::RecordCap) return Outcome::MoreMembers;
@@ -1366,7 +1411,7 @@ Outcome run_context(Session& S, Reading& F) {
     std::cerr << "[" << F.watch.lap() << " secs]" << std::endl;
 
     std::cerr << "Analysing alignments, reads and references ....... ";
-    const bool byte_ranges = F.record_order == SLIMM_ORDER_GROUPED && F.bam.is_bam() && F.bam.regular_file();
+    const bool byte_ranges = F.record_order == SLIMM_ORDER_GROUPED && reads_by_byte_range(F.bam);
     const Outcome pushed = push_file(S, F, Target{ctx}, byte_ranges ? OnCap::MoreMembers : OnCap::Fail);
     if (pushed == Outcome::MoreMembers) {
         // more records than one context takes: contexts of a group on this one device, each its own byte range of the

@@ -320,6 +320,11 @@ void launch_sam_end_line(hipStream_t st, uint8_t* bytes, uint64_t lo, uint64_t e
 void launch_sam_decode(hipStream_t st, const uint8_t* bytes, uint64_t lo, uint64_t end, const BamPiece* pieces, const uint32_t* offs,
                        BamCarry* carry, const BamWindowResult* result, bool marked, uint64_t out_at, uint64_t* key, int32_t* ref, int32_t* pos,
                        uint16_t* flag, uint32_t* check, const SamRefEntry* table, uint32_t table_mask, const uint8_t* names);
+// a byte range that starts inside a file (split.hip): the offset of the first newline in bytes[lo, hi) -> atomicMin into
+// *out (set it to ~0 first; the bytes are read in aligned 16s: the buffer has room on both sides); the name of the line
+// at o -> *name (as the carry keeps it)
+void launch_sam_first_newline(hipStream_t st, const uint8_t* bytes, uint64_t lo, uint64_t hi, unsigned long long* out);
+void launch_sam_name_at(hipStream_t st, const uint8_t* bytes, uint64_t o, uint64_t end, BamCarry* name);
 
 // ---- bgzf_inflate.hip: BGZF blocks (DEFLATE streams of <= 64 KB) inflated on the device, a lane per block ----
 struct BgzfBlock {

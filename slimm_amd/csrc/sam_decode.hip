@@ -9,6 +9,9 @@
 //                  with '@': an error of the push, like the host reader's), and where the last of them ends.  A newline is an
 //                  exact boundary: nothing is guessed, nothing verified.
 //   k_sam_end_line the file's last window, inflated here: a last line without its newline gets one
+//   k_sam_first_newline, k_sam_name_at   a byte range of a split file that starts inside the file (split.hip): the first
+//                  newline of its first window -- the bytes through it are the head, the left member's --, and the name of
+//                  its first line, for the join with the left member's last
 //   k_bam_scan     (bam_decode.hip) lines in front of every piece, the window's totals, where its last complete line ends
 //   k_sam_decode   a WAVE per piece, a lane per line: the fields; RNAME through a hash table of the header's names (exact:
 //                  the bytes are compared); input grouped by name: QNAME compared with the line before (its canonical base:
@@ -277,25 +280,30 @@ __global__ __launch_bounds__(64) void k_sam_decode(const uint8_t* __restrict__ b
     }
 }
 
+// one wave: the name of the line at o (its canonical base, at most 255 bytes: QNAME is at most 254 characters) and whether
+// it was shortened -> *dst; the form k_split_join compares (bam_decode.hip).  The Q18 counts of *dst are the caller's
+__device__ __forceinline__ void line_name_to(const uint8_t* __restrict__ b, uint64_t o, uint64_t end, BamCarry* __restrict__ dst) {
+    const uint8_t* name;
+    uint32_t nlen, fl;
+    uint64_t unused;
+    bool is_short;
+    line_identity(b, o, end, name, nlen, fl, unused, &is_short);
+    if (nlen > 255u) nlen = 255u;
+    for (uint32_t i = threadIdx.x; i < nlen; i += 64u) dst->name[i] = name[i];
+    if (threadIdx.x == 0) {
+        dst->len = nlen;
+        dst->have = 1;
+        dst->last_short = is_short ? 1u : 0u;
+    }
+}
+
 // the window's last line's name (its canonical base) -> the carry
 __global__ __launch_bounds__(64) void k_sam_carry(const uint8_t* __restrict__ b, uint64_t end, const BamPiece* __restrict__ pieces,
                                                   const uint32_t* __restrict__ offs, const BamWindowResult* __restrict__ res,
                                                   BamCarry* __restrict__ carry) {
     const uint32_t c = res->last_piece;
     if (c == 0xffffffffu) return;
-    const uint64_t o = offs[static_cast<size_t>(c) * kBamSlots + pieces[c].count - 1u] & 0x7fffffffu;
-    const uint8_t* name;
-    uint32_t nlen, fl;
-    uint64_t unused;
-    bool is_short;
-    line_identity(b, o, end, name, nlen, fl, unused, &is_short);
-    if (nlen > 255u) nlen = 255u;   // (QNAME is at most 254 characters)
-    for (uint32_t i = threadIdx.x; i < nlen; i += 64u) carry->name[i] = name[i];
-    if (threadIdx.x == 0) {
-        carry->len = nlen;
-        carry->have = 1;
-        carry->last_short = is_short ? 1u : 0u;
-    }
+    line_name_to(b, offs[static_cast<size_t>(c) * kBamSlots + pieces[c].count - 1u] & 0x7fffffffu, end, carry);
 }
 
 // The text's last line, when its last bytes were inflated here: without its newline it ends at `end` all the same, as a
@@ -307,7 +315,47 @@ __global__ __launch_bounds__(64) void k_sam_end_line(uint8_t* __restrict__ b, ui
     *ended = open ? 1u : 0u;
 }
 
+// A range of a split file (split.hip): where its first line starts.  A lane per 16 aligned bytes of [lo, hi), the smallest
+// offset of a newline wins (-> *out: the newline's offset).  A line starts behind a newline and nowhere else: nothing is
+// guessed.  (Reads up to 15 bytes in front of lo and behind hi: the window buffer's slack and its room behind the window.)
+__global__ __launch_bounds__(256) void k_sam_first_newline(const uint8_t* __restrict__ b, uint64_t lo, uint64_t hi,
+                                                           unsigned long long* __restrict__ out) {
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * 256ull * 16ull;
+    for (uint64_t o = (lo & ~15ull) + (blockIdx.x * 256ull + threadIdx.x) * 16ull; o < hi; o += stride) {
+        if (o >= __hip_atomic_load(out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;  // (a smaller one is known)
+        const uint4 v = *reinterpret_cast<const uint4*>(b + o);
+        const uint64_t w[2] = {static_cast<uint64_t>(v.x) | (static_cast<uint64_t>(v.y) << 32),
+                               static_cast<uint64_t>(v.z) | (static_cast<uint64_t>(v.w) << 32)};
+        for (uint32_t h = 0; h < 2u; ++h) {
+            uint64_t nl = bytes_equal(w[h], '\n');
+            while (nl) {
+                const uint64_t at = o + 8u * h + (static_cast<uint32_t>(__builtin_ctzll(nl)) >> 3);
+                if (at >= lo && at < hi) {
+                    atomicMin(out, static_cast<unsigned long long>(at));
+                    return;
+                }
+                nl &= nl - 1ull;
+            }
+        }
+    }
+}
+
+// the name of the line at b[o] (its canonical base, as k_sam_carry keeps the last one)
+__global__ __launch_bounds__(64) void k_sam_name_at(const uint8_t* __restrict__ b, uint64_t o, uint64_t end, BamCarry* __restrict__ dst) {
+    line_name_to(b, o, end, dst);
+    if (threadIdx.x == 0) dst->short_starts = dst->short_to_plain = 0;
+}
+
 }  // namespace
+
+void launch_sam_first_newline(hipStream_t st, const uint8_t* bytes, uint64_t lo, uint64_t hi, unsigned long long* out) {
+    if (hi <= lo) return;
+    const uint64_t blocks = std::min<uint64_t>(1024, (hi - (lo & ~15ull) + 4095) / 4096);
+    hipLaunchKernelGGL(k_sam_first_newline, dim3(static_cast<uint32_t>(blocks)), dim3(256), 0, st, bytes, lo, hi, out);
+}
+void launch_sam_name_at(hipStream_t st, const uint8_t* bytes, uint64_t o, uint64_t end, BamCarry* name) {
+    hipLaunchKernelGGL(k_sam_name_at, dim3(1), dim3(64), 0, st, bytes, o, end, name);
+}
 
 uint32_t sam_pieces(uint64_t n_bytes) { return static_cast<uint32_t>((n_bytes + kSamPiece - 1) / kSamPiece); }
 

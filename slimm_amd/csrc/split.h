@@ -1,5 +1,5 @@
 // Internal to the library: the per-member steps of slimm_group_stitch_ranges (group.hip drives them, split.hip holds them)
-// -- one BAM file split by byte range over a group's members (include/slimm_hip.h, "ONE BAM FILE SPLIT BY BYTE RANGE").
+// -- one file (BAM, SAM, BGZF SAM) split by byte range over a group's members (include/slimm_hip.h, "ONE FILE SPLIT BY BYTE RANGE").
 // Every step finishes its own device work before it returns: the next step may run on another member's device.
 #pragma once
 #include <stdint.h>

@@ -1,9 +1,11 @@
-// One BAM file split by byte range over a group's members (include/slimm_hip.h, "ONE BAM FILE SPLIT BY BYTE RANGE"):
-// the host's plan of the ranges (slimm_host_bgzf_ranges) and the per-member steps of slimm_group_stitch_ranges (split.h;
-// group.hip runs them cut by cut).  A range that starts inside the file guesses its first record as k_bam_pieces guesses
-// a piece's (windows.hip, bam_decode.hip: k_bam_first_guess); the member on its left confirms the guess one level up, as
-// k_bam_verify confirms a piece's: its incomplete last record followed by the right member's head must be whole records
-// that end exactly where the guess begins.  The reference reads one file with one reader (src/misc.hpp:498-522).
+// One file -- BAM, SAM text or BGZF blocks of SAM text -- split by byte range over a group's members (include/slimm_hip.h,
+// "ONE FILE SPLIT BY BYTE RANGE"): the host's plan of the ranges (slimm_host_bgzf_ranges, slimm_host_text_ranges) and the
+// per-member steps of slimm_group_stitch_ranges (split.h; group.hip runs them cut by cut).  A range that starts inside
+// the file guesses its first record as k_bam_pieces guesses a piece's (windows.hip, bam_decode.hip: k_bam_first_guess);
+// the member on its left confirms the guess one level up, as k_bam_verify confirms a piece's: its incomplete last record
+// followed by the right member's head must be whole records that end exactly where the guess begins.  A range of SAM
+// text guesses nothing: its first line starts behind its first newline (sam_decode.hip: k_sam_first_newline), and the
+// left member's last line must end with the head.  The reference reads one file with one reader (src/misc.hpp:498-522).
 #include <fcntl.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -108,14 +110,26 @@ int slimm_host_bgzf_ranges(const char* path, uint64_t skip, uint32_t n, uint64_t
     return SLIMM_OK;
 }
 
+// plain text is cut anywhere: the device finds the line starts (windows.hip: guess_first_record)
+int slimm_host_text_ranges(const char* path, uint64_t skip, uint32_t n, uint64_t* offsets_out) {
+    if (!path || !n || !offsets_out) return SLIMM_E_INVALID;
+    struct stat sb;
+    if (stat(path, &sb) != 0 || !S_ISREG(sb.st_mode)) return SLIMM_E_INVALID;
+    const uint64_t size = static_cast<uint64_t>(sb.st_size);
+    if (skip > size) return SLIMM_E_INVALID;
+    for (uint32_t i = 0; i <= n; ++i)
+        offsets_out[i] = skip + static_cast<uint64_t>(static_cast<unsigned __int128>(size - skip) * i / n);
+    return SLIMM_OK;
+}
+
 }  // extern "C"
 
 namespace slimm {
 
 int split_range(slimm_ctx* c, SplitRange* out) {
     if (!c || !out) return SLIMM_E_INVALID;
-    if (c->device < 0 || !c->win.file.active || !c->win.file.closed || c->win.file.sam || c->order != SLIMM_ORDER_GROUPED)
-        return fail(c, SLIMM_E_INVALID, "a range of a split file: a GROUPED BAM range pushed to its end");
+    if (c->device < 0 || !c->win.file.active || !c->win.file.closed || c->win.file.bz2.on || c->order != SLIMM_ORDER_GROUPED)
+        return fail(c, SLIMM_E_INVALID, "a range of a split file: a GROUPED range of BAM, SAM or BGZF SAM pushed to its end");
     out->found_start = c->win.file.found_start || !c->win.announced.starts_mid;
     out->head_len = c->win.announced.starts_mid ? c->win.file.head_len : 0u;
     out->n_records = c->n_pushed;
@@ -127,7 +141,10 @@ int split_append_head(slimm_ctx* left, slimm_ctx* right, bool final, uint64_t* n
     HIP_TRY(right, hipStreamSynchronize(right->stream));   // (the head was copied aside on the right member's stream)
     const uint64_t n = right->win.announced.starts_mid ? right->win.file.head_len : 0u;
     uint64_t got = 0;
-    SLIMM_TRY(append_window(left, right->win.head_bytes.p, right->device, n, final, got));
+    // SAM: the file's last range inflated to nothing (it is empty, or holds the EOF block only), so no member has ended a
+    // last line that lacks its newline: the member that holds the line does
+    const bool end_line = left->win.file.sam && !right->win.announced.ends_mid && !right->win.file.windows && left->win.file.carry_bytes;
+    SLIMM_TRY(append_window(left, right->win.head_bytes.p, right->device, n, final, got, end_line));
     HIP_TRY(left, hipStreamSynchronize(left->stream));
     if (n_records) *n_records = got;
     return SLIMM_OK;

@@ -160,8 +160,9 @@ struct WindowPipeline {
 void push_trace_line(const char* tag, const char* fmt, va_list ap);
 void push_trace(const char* fmt, ...);
 int fetch_q18(slimm_ctx* c);   // the Q18 run counts of the device decoders so far (every window launched) -> file.q18_*
-// `n` bytes at `src` (on device src_device) as one more window behind the closed file's carry (split.hip)
-int append_window(slimm_ctx* c, const uint8_t* src, int src_device, uint64_t n, bool final, uint64_t& n_rec);
+// `n` bytes at `src` (on device src_device) as one more window behind the closed file's carry (split.hip); end_line: one
+// newline instead
+int append_window(slimm_ctx* c, const uint8_t* src, int src_device, uint64_t n, bool final, uint64_t& n_rec, bool end_line = false);
 // bzip2_decode.hip (slimm_push_bzip2_sam_bytes): the next batch of whole blocks of file.bz2.pend decoded up to their text
 // lengths (file.bz2.ready; none: the chain waits for more bytes, or the streams have ended); at `last` what is left must
 // end the streams.  Then, window by window: the text bytes of the next ready blocks that fit in `cap` (at least one

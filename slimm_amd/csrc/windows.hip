@@ -113,21 +113,30 @@ int check_inflate(slimm_ctx* c) {
 // window, as k_bam_pieces guesses a piece's; the bytes in front of it (the head, at most 16 MiB) stay on the device for the
 // member on the left, which confirms the guess (slimm_group_stitch_ranges).  No record start at all: the whole window is
 // head (a range inside one long record) -- only when it is the range's last window.  lo: where the window's records start
+//
+// SAM text: the first line starts behind the first newline, and the head is the bytes through that newline -- a whole
+// line when the cut fell on a line start; nothing is guessed, and the member on the left checks only that its last line
+// ends with the head.
 int guess_first_record(slimm_ctx* c, uint32_t b, uint64_t n_bytes, bool is_last, uint64_t end, uint64_t& lo) {
     WindowPipeline& W = c->win;
     hipStream_t st = c->stream;
     if (n_bytes) HIP_TRY(c, hipStreamWaitEvent(st, W.copied[b], 0));
     HIP_TRY(c, W.guess.ensure(1));
     HIP_TRY(c, hipMemsetAsync(W.guess.p, 0xff, sizeof(unsigned long long), st));
-    launch_bam_first_guess(st, W.bytes[b].p, lo, std::min<uint64_t>(end, lo + kBamSlack + 1u), end, c->R, W.guess.p);
+    if (W.file.sam)
+        launch_sam_first_newline(st, W.bytes[b].p, lo, std::min<uint64_t>(end, lo + kBamSlack), W.guess.p);
+    else
+        launch_bam_first_guess(st, W.bytes[b].p, lo, std::min<uint64_t>(end, lo + kBamSlack + 1u), end, c->R, W.guess.p);
     unsigned long long g = 0;
     HIP_TRY(c, hipMemcpyAsync(&g, W.guess.p, sizeof(g), hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
     W.file.found_start = g != ~0ull;
     if (!W.file.found_start) {
         if (!is_last || end - lo > kBamSlack)
-            return fail(c, SLIMM_E_SPLIT, "no record starts in the first 16 MiB of a range that starts inside the file");
+            return fail(c, SLIMM_E_SPLIT, "no %s starts in the first 16 MiB of a range that starts inside the file", W.file.sam ? "line" : "record");
         g = end;
+    } else if (W.file.sam) {
+        ++g;   // (the line starts behind the newline)
     }
     const uint64_t head = g - lo;
     HIP_TRY(c, W.head_bytes.ensure(std::max<uint64_t>(head + 64u, 4096u)));
@@ -166,16 +175,17 @@ int finish_window(slimm_ctx* c, uint64_t j, uint64_t n_bytes, bool is_last, uint
     const uint32_t b = static_cast<uint32_t>(j % kRing), nb = static_cast<uint32_t>((j + 1u) % kRing);
     uint64_t lo = kBamSlack - F.carry_bytes;
     uint64_t end = kBamSlack + n_bytes;
-    if (W.announced.starts_mid && j == 0 && !F.sam) SLIMM_TRY(guess_first_record(c, b, n_bytes, is_last, end, lo));
+    if (n_bytes) HIP_TRY(c, hipStreamWaitEvent(st, W.copied[b], 0));
+    const bool inflated_here = n_bytes && F.inflated[b];
+    // (a range that ends inside the file ends inside a line: that line is the carry, and the member on the right ends it)
+    if (F.sam && is_last && F.sam_dev_tail && !W.announced.ends_mid) SLIMM_TRY(end_last_line_on_device(c, j, b, lo, inflated_here, end));
+    if (W.announced.starts_mid && j == 0) SLIMM_TRY(guess_first_record(c, b, n_bytes, is_last, end, lo));
     const uint32_t np = window_pieces(F.sam, end - lo);
     // (with room to spare and without a hipFree: windows differ by a few pieces, and a hipFree waits for the inflate kernels
     // of the windows behind this one)
     if (W.pieces.cap < static_cast<size_t>(np) + 1) HIP_TRY(c, W.pieces.ensure_later(static_cast<size_t>(np) + (np >> 2) + 64, W.outgrown));
     if (W.offs.cap < static_cast<size_t>(np + 1) * kBamSlots)
         HIP_TRY(c, W.offs.ensure_later((static_cast<size_t>(np) + (np >> 2) + 64) * kBamSlots, W.outgrown));
-    if (n_bytes) HIP_TRY(c, hipStreamWaitEvent(st, W.copied[b], 0));
-    const bool inflated_here = n_bytes && F.inflated[b];
-    if (F.sam && is_last && F.sam_dev_tail) SLIMM_TRY(end_last_line_on_device(c, j, b, lo, inflated_here, end));
     if (inflated_here)
         HIP_TRY(c, hipMemcpyAsync(W.h_inflate_status.p, W.inflate_status.p + 4u * b, 16, hipMemcpyDeviceToHost, st));
     launch_find(c, W.bytes[b].p, lo, end);
@@ -196,9 +206,12 @@ int finish_window(slimm_ctx* c, uint64_t j, uint64_t n_bytes, bool is_last, uint
         if (c->in_check.cap < want) HIP_TRY(c, c->in_check.ensure_later(std::max<uint64_t>(want, c->in_ref.cap), W.outgrown));
     }
     launch_decode(c, W.bytes[b].p, lo, end, marked);
-    if (W.announced.starts_mid && !F.has_first && n_rec && !F.sam) {   // (the range's first record: a window's first record starts at lo)
+    if (W.announced.starts_mid && !F.has_first && n_rec) {   // (the range's first record: a window's first record starts at lo)
         HIP_TRY(c, W.first.ensure(1));
-        launch_bam_name_at(st, W.bytes[b].p, lo, W.first.p);
+        if (F.sam)
+            launch_sam_name_at(st, W.bytes[b].p, lo, end, W.first.p);
+        else
+            launch_bam_name_at(st, W.bytes[b].p, lo, W.first.p);
         F.has_first = true;
     }
     if (tail) {  // the incomplete record goes in front of the next window (whose own bytes may be on their way already)
@@ -274,8 +287,12 @@ int submit_window(slimm_ctx* c, uint64_t n_bytes, hipStream_t filled_on, bool in
 }
 
 // SAM text whose last line has no newline gets one: a line ends where its newline is.  (When the text's last bytes were
-// inflated on the device, the host has not seen them: finish_window lets the device end that line)
-bool lacks_last_newline(const File& F, bool last) { return F.sam && last && !F.sam_dev_tail && F.sam_last_byte != '\n'; }
+// inflated on the device, the host has not seen them: finish_window lets the device end that line.  A range that ends
+// inside the file -- slimm_set_input_mid_file -- ends inside a line: nothing ends it here)
+bool lacks_last_newline(const slimm_ctx* c, bool last) {
+    const File& F = c->win.file;
+    return F.sam && last && !c->win.announced.ends_mid && !F.sam_dev_tail && F.sam_last_byte != '\n';
+}
 int add_last_newline(slimm_ctx* c, uint64_t at, hipStream_t st) {   // at: bytes of the next window in front of it
     HIP_TRY(c, hipMemsetAsync(c->win.bytes[next_buffer(c->win.file)].p + kBamSlack + at, '\n', 1, st));
     c->win.file.sam_last_byte = '\n';
@@ -403,7 +420,7 @@ int push_bzip2(slimm_ctx* c, const Push& p, uint64_t& total) {
             SLIMM_TRY(finish_windows(c, Upto::Lag, false, false, total));
         }
     }
-    if (lacks_last_newline(F, p.last)) {   // (in a window of its own)
+    if (lacks_last_newline(c, p.last)) {   // (in a window of its own)
         SLIMM_TRY(window_buffer(c, 1u));
         SLIMM_TRY(add_last_newline(c, 0, st));
         SLIMM_TRY(submit_window(c, 1, st, false));
@@ -556,7 +573,7 @@ int push_plain(slimm_ctx* c, Push& p) {
         F.sam_last_byte = p.bytes[p.n_bytes - 1];
         F.sam_dev_tail = false;
     }
-    const bool add_newline = lacks_last_newline(F, p.last);
+    const bool add_newline = lacks_last_newline(c, p.last);
     SLIMM_TRY(window_buffer(c, p.n_bytes + (add_newline ? 1u : 0u)));
     const uint64_t n = p.n_bytes;
     if (n) HIP_TRY(c, hipMemcpyAsync(W.bytes[next_buffer(F)].p + kBamSlack, p.bytes, n, hipMemcpyHostToDevice, c->copy_stream));
@@ -596,7 +613,7 @@ int push_window(slimm_ctx* c, const uint8_t* bytes, uint64_t src_bytes, int form
         SLIMM_TRY(push_bzip2(c, p, total));
     else if (p.n_bytes && p.compressed)
         SLIMM_TRY(gather_blocks(c, p, total));
-    else if (p.n_bytes || (p.sam && p.last && (F.sam_last_byte != '\n' || F.sam_dev_tail)))
+    else if (p.n_bytes || (p.sam && p.last && !W.announced.ends_mid && (F.sam_last_byte != '\n' || F.sam_dev_tail)))
         SLIMM_TRY(push_plain(c, p));
     if (p.last) SLIMM_TRY(launch_gathered(c));
     // ... while the windows before are worked on: the oldest are finished -- all of them when this is the file's end
@@ -741,19 +758,24 @@ int fetch_q18(slimm_ctx* c) {
 }
 
 // slimm_group_stitch_ranges (split.hip): the head of the member on the right -- n bytes at src, on device src_device -- as one
-// more window of this member, behind the incomplete record its last window ended with.  final: the window must end with a
-// complete record; anything else means the right member guessed its first record wrong (SLIMM_E_SPLIT)
-int append_window(slimm_ctx* c, const uint8_t* src, int src_device, uint64_t n, bool final, uint64_t& n_rec) {
+// more window of this member, behind the incomplete record (SAM: line) its last window ended with.  final: the window must
+// end with a complete record; anything else means the right member guessed its first record wrong (SLIMM_E_SPLIT).
+// end_line: the window is one newline instead of the head
+int append_window(slimm_ctx* c, const uint8_t* src, int src_device, uint64_t n, bool final, uint64_t& n_rec, bool end_line) {
     WindowPipeline& W = c->win;
     File& F = W.file;
     n_rec = 0;
-    if (!F.active || !F.closed || F.head != F.windows || F.sam) return fail(c, SLIMM_E_INVALID, "a range's bytes are joined once it is pushed");
+    if (!F.active || !F.closed || F.head != F.windows) return fail(c, SLIMM_E_INVALID, "a range's bytes are joined once it is pushed");
     (void)hipSetDevice(c->device);
-    SLIMM_TRY(window_buffer(c, n));
+    SLIMM_TRY(window_buffer(c, std::max<uint64_t>(n, 1u)));
     const uint64_t j = F.windows;
     uint8_t* dst = W.bytes[next_buffer(F)].p + kBamSlack;
-    if (n && src_device == c->device) HIP_TRY(c, hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToDevice, c->stream));
-    if (n && src_device != c->device) HIP_TRY(c, hipMemcpyPeerAsync(dst, c->device, src, src_device, n, c->stream));
+    if (end_line) {   // (SAM: the newline of a last line that lacks one, when the file's last range held no byte to end it)
+        n = 1;
+        HIP_TRY(c, hipMemsetAsync(dst, '\n', 1, c->stream));
+    } else if (n && src_device == c->device) HIP_TRY(c, hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToDevice, c->stream));
+    else if (n)
+        HIP_TRY(c, hipMemcpyPeerAsync(dst, c->device, src, src_device, n, c->stream));
     SLIMM_TRY(submit_window(c, n, c->stream, false, n != 0));   // (no bytes: nothing to wait for)
     const bool starts_mid = W.announced.starts_mid;
     W.announced.starts_mid = starts_mid && F.found_start;   // (a range of no record start: its first record is in this window)
@@ -761,7 +783,9 @@ int append_window(slimm_ctx* c, const uint8_t* src, int src_device, uint64_t n, 
     W.announced.starts_mid = starts_mid;
     ++F.head;
     if (rc != SLIMM_OK) return fail(c, SLIMM_E_SPLIT, "the bytes around a cut: %s", c->err.c_str());
-    if (final && F.carry_bytes) return fail(c, SLIMM_E_SPLIT, "the record chain across a cut does not end where the next range's first record was guessed");
+    if (final && F.carry_bytes)
+        return fail(c, SLIMM_E_SPLIT, F.sam ? "the line across a cut does not end where the next range's first line starts"
+                                            : "the record chain across a cut does not end where the next range's first record was guessed");
     return SLIMM_OK;
 }
 

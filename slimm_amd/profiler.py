@@ -737,6 +737,50 @@ class SlimmGroup:
             e = min(n, s + step)
             self._check(self.L.slimm_group_push_records_marked(self.g, _p(w[s:e]), _p(rec.begin_pos[s:e]), e - s))
 
+    SPLIT_FORMS = ("bam", "sam", "bgzf_sam")
+
+    def push_split(self, data, form: str, skip: int = 0, window: int = 0):
+        """One GROUPED file split by byte range, every member its own (include/slimm_hip.h, "ONE FILE SPLIT BY BYTE RANGE").
+        `data`: the whole file -- header included -- as bytes, or its path; `form`: "bam" (BGZF blocks of BAM records), "sam"
+        (plain text) or "bgzf_sam" (BGZF blocks of SAM text); `skip`: the header's bytes (for the BGZF forms its INFLATED
+        bytes).  The ranges come from slimm_host_text_ranges / slimm_host_bgzf_ranges; member by member: the reference
+        names (SAM), slimm_set_input_mid_file, the size hint, the range pushed in windows of `window` bytes (0: one); then
+        slimm_group_stitch_ranges.  Returns (the n + 1 offsets, the records every member decoded before the stitch)."""
+        import os
+        import tempfile
+
+        assert form in self.SPLIT_FORMS, form
+        G = len(self.devices)
+        offs = (C.c_uint64 * (G + 1))()
+        plan = self.L.slimm_host_text_ranges if form == "sam" else self.L.slimm_host_bgzf_ranges
+        if isinstance(data, (str, os.PathLike)):
+            path = os.fspath(data)
+            with open(path, "rb") as f:
+                blob = f.read()
+            rc = plan(path.encode(), int(skip), G, offs)
+        else:
+            blob = bytes(data)
+            with tempfile.NamedTemporaryFile(suffix="." + form) as f:   # (the planners read a file)
+                f.write(blob)
+                f.flush()
+                rc = plan(f.name.encode(), int(skip), G, offs)
+        if rc != capi.OK:
+            raise capi.SlimmError(rc, "the file could not be planned into ranges")
+        counts = []
+        for i in range(G):
+            m = self.member(i)
+            if form != "bam":
+                m.set_reference_names(self.w.ref_names)
+            m._check(self.L.slimm_set_input_mid_file(m.ctx, 1 if i > 0 else 0, 1 if i + 1 < G else 0))
+            m._check(self.L.slimm_set_input_size_hint(m.ctx, offs[i + 1] - offs[i]))
+            part = blob[offs[i]:offs[i + 1]]
+            if form == "sam":
+                counts.append(m.push_sam_bytes(part, window=window))
+            else:
+                counts.append(m.push_bgzf_blocks(part, skip=skip if i == 0 else 0, window=window, sam=form == "bgzf_sam"))
+        self._check(self.L.slimm_group_stitch_ranges(self.g))
+        return list(offs), counts
+
     EXCHANGES = {"auto": 0, "summary": 1, "sliced": 2, "bins": 3}
 
     def set_exchange(self, mode: str):
