@@ -567,7 +567,7 @@ enum { SLIMM_EXCHANGE_AUTO = 0, SLIMM_EXCHANGE_SUMMARY = 1, SLIMM_EXCHANGE_SLICE
 int slimm_group_set_exchange(slimm_group* g, int mode);
 int slimm_group_exchange(const slimm_group* g); /* the form in effect (what AUTO resolves to) */
 int slimm_group_get_profiles(slimm_group* g, const char* path); /* path may be NULL; SLIMM_E_NO_HITS like slimm_get_profiles */
-/* ONE FILE SPLIT BY BYTE RANGE over a group (GROUPED files): every member reads, inflates and decodes its own contiguous
+/* ONE FILE SPLIT BY BYTE RANGE over a group (files GROUPED by read name or in ANY order): every member reads, inflates and decodes its own contiguous
  * range of the file at once.  Three forms of file: BAM, SAM text, and SAM text in BGZF blocks (bgzip).  (A plain gzip
  * stream cannot be cut, and a bzip2 file's blocks start at bit offsets: those go through one member.)
  *   The plan (host only, no GPU): offsets_out[0, n]; range i = [offsets_out[i], offsets_out[i + 1]), ranges may be empty.
@@ -594,7 +594,16 @@ int slimm_group_get_profiles(slimm_group* g, const char* path); /* path may be N
  * member 0 instead); the run of a read name that a cut splits moves, device to device, to the member that holds its
  * start; the Q18 counts are summed over the members (SLIMM_E_REGROUP as for one context).  slimm_group_get_profiles then
  * runs on the members' records as they are (no dealing from member 0).  This is also how ONE device takes a file of more
- * records than one context holds: a group that names the same device several times. */
+ * records than one context holds: a group that names the same device several times.
+ *   A file in ANY order is planned, announced and pushed in the same way, and slimm_group_stitch_ranges joins the cuts in the
+ * same way (SLIMM_E_SPLIT as above).  It has no runs to join and no Q18 counts; instead every member partitions the records
+ * of its range by owner -- (key & the 62 identity bits) mod n, the rule of slimm_group_push_records* -- with a stable
+ * partition on the device (slimm_partition_by_key), and member j receives stretch j of every member in member order, device
+ * to device: all records of a read on one member, in the file's order.  A member with no records, or with a range that is
+ * all head, sends and receives empty stretches.  Nothing may have been dealt through slimm_group_push_records* before.
+ *   Memory: while the records are dealt every member holds one more copy of its records (22 bytes each, the send buffers);
+ * they are released before slimm_group_stitch_ranges (or, through member 0, before phase A) goes on.  A member that receives
+ * more records than it decoded grows its record arrays to what it receives. */
 int slimm_host_bgzf_ranges(const char* path, uint64_t skip, uint32_t n, uint64_t* offsets_out);
 int slimm_host_text_ranges(const char* path, uint64_t skip, uint32_t n, uint64_t* offsets_out);
 int slimm_set_input_mid_file(slimm_ctx* ctx, int starts_mid_file, int ends_mid_file);
@@ -605,7 +614,13 @@ uint64_t slimm_record_cap(void);
  * _bgzf_blocks / _sam_bytes: the device inflates and decodes at the single-context rate) and nothing through
  * slimm_group_push_records*; slimm_group_get_profiles then deals member 0's run-marked records to the members in contiguous
  * stretches cut at qName-run starts, device to device (8 bytes per record), before phase A.  SLIMM_E_REGROUP from member 0
- * (Q18) comes back as the group's return code: such a file goes through slimm_group_push_records* in any order. */
+ * (Q18) comes back as the group's return code: such a file goes through slimm_group_push_records* in any order.
+ *   A file in ANY order reaches a group through member 0 in the same way (slimm_push_bam_bytes / _bgzf_blocks / _sam_bytes /
+ * _bgzf_sam_blocks / _bzip2_sam_bytes to slimm_group_context(g, 0), nothing through slimm_group_push_records*): when only member
+ * 0 holds records, in the four-array form, slimm_group_get_profiles partitions them by owner on the device (key mod n, the
+ * rule of slimm_group_push_records*), copies stretch i to member i device to device with its check words -- member 0 keeps
+ * stretch 0 -- and releases the send buffers (one more copy of the records, 22 bytes each) before phase A.  The records
+ * and stretch lengths do not depend on whether RCCL was loaded: the deal is copies in either case. */
 
 /* Starts the HIP runtime on `device` (what the first slimm_create of a process would otherwise pay, 0.1 - 0.3 s): for
  * hosts that call it from a thread of their own while they load their database and open their input. */
@@ -628,6 +643,14 @@ int slimm_bgzf_inflate(int device, const uint8_t* blocks, uint64_t n_bytes, uint
  * the lane-per-block kernel inflated. */
 int slimm_bgzf_inflate_with(int device, const uint8_t* blocks, uint64_t n_bytes, uint8_t* out, uint64_t out_cap, uint64_t* out_bytes,
                             double* kernel_ms, char* err, uint64_t err_cap, uint32_t how, uint32_t* lane_blocks);
+/* The stable partition of four-array records by owner, by itself (slimm_amd/csrc/deal_by_key.hip): the kernels a group of
+ * m members runs to give every read of a file in any order to one member.  Host arrays in and out, n < 2^31 records each,
+ * 1 <= m <= 255; check / check_out may be NULL.  The outputs hold the same records in m contiguous stretches, stretch o =
+ * exactly the records with (key & (2^62 - 1)) % m == o in their input order; counts_out[o] = its length.  *kernel_ms (may be
+ * null): the three kernels alone (count, scan, scatter).  Errors (-1 bad input, -2 HIP) come with a message in err[0, err_cap). */
+int slimm_partition_by_key(int device, const uint64_t* key, const int32_t* ref, const int32_t* pos, const uint16_t* flag,
+                           const uint32_t* check, uint64_t n, uint32_t m, uint64_t* key_out, int32_t* ref_out, int32_t* pos_out,
+                           uint16_t* flag_out, uint32_t* check_out, uint64_t* counts_out, double* kernel_ms, char* err, uint64_t err_cap);
 
 #ifdef __cplusplus
 }

@@ -26,6 +26,7 @@
 #include "../../include/slimm_hip.h"
 #include "force.h"
 #include "split.h"
+#include "deal_by_key.h"
 
 namespace {
 
@@ -646,6 +647,41 @@ static int deal_from_member0(slimm_group* g) {
     return SLIMM_OK;
 }
 
+// A file in no particular order: every read to ONE member, member = key mod n as deal() has it, on the devices
+// (deal_by_key.hip): every member partitions the records it holds by owner, member j takes stretch j of every member in
+// member order -- the file's order inside every member -- device to device, in the copy form whether RCCL is loaded or not
+static int deal_by_key(slimm_group* g) {
+    const uint32_t G = static_cast<uint32_t>(g->ctx.size());
+    static const bool trace = slimm::traced("cli");
+    std::vector<uint64_t> held(G, 0), own(G, 0);
+    uint32_t failed = 0;
+    const int rc = slimm::deal_by_key(g->ctx.data(), G, held.data(), own.data(), &failed);
+    if (rc != SLIMM_OK) return member_failed(g, failed, rc, "dealing the records by key");
+    if (trace)
+        for (uint32_t i = 0; i < G; ++i)
+            fprintf(stderr, "[trace] dealt by key: member %u holds %llu records (%llu of its own)\n", i,
+                    static_cast<unsigned long long>(held[i]), static_cast<unsigned long long>(own[i]));
+    return SLIMM_OK;
+}
+
+// Member 0 holds a file in ANY order it decoded itself -- four-array records with check words -- and nothing was dealt
+// through slimm_group_push_records*: the same test as deal_from_member0 makes, then deal_by_key (member 0 keeps stretch 0)
+static int deal_from_member0_any(slimm_group* g) {
+    const uint32_t G = static_cast<uint32_t>(g->ctx.size());
+    if (g->checked >= 0) return SLIMM_OK;       // (the caller dealt records itself)
+    for (uint32_t i = 0; i < G; ++i) {
+        const uint64_t* k;
+        const int32_t *r, *p;
+        const uint16_t* f;
+        uint64_t ni = 0;
+        int fi = 0;
+        GTRY(g, i, slimm_records_device(g->ctx[i], &k, &r, &p, &f, &ni, &fi));
+        if (i == 0 && (ni == 0 || fi != 0)) return SLIMM_OK;   // (nothing there, or not the four-array form: as pushed)
+        if (i && ni) return SLIMM_OK;
+    }
+    return deal_by_key(g);
+}
+
 // A file read by byte range, every member its own (include/slimm_hip.h, "ONE FILE SPLIT BY BYTE RANGE"; split.hip):
 //   1. the bytes around every cut -- the incomplete last record of the nearest member on the left that holds a record
 //      start, and the right member's head -- are decoded by that left member, and must end exactly where the right
@@ -654,9 +690,12 @@ static int deal_from_member0(slimm_group* g) {
 //      bit (and corrects the Q18 counts); then Q18 over the file, the members' counts summed
 //   3. left to right, the records in front of a member's first run start -- the run a cut split -- go device to device to
 //      the nearest member on the left that keeps records, so that a run over several members ends up in one
+// A file in ANY order has no runs: steps 2 and 3 give way to deal_by_key -- every member partitions the records of its
+// range by owner and takes its stretch of every member's, in member order
 int slimm_group_stitch_ranges(slimm_group* g) {
     if (!g) return SLIMM_E_INVALID;
-    if (g->order != SLIMM_ORDER_GROUPED) return gfail(g, SLIMM_E_INVALID, "a file split by byte range must be grouped by read name");
+    if (g->order != SLIMM_ORDER_GROUPED && g->checked >= 0)
+        return gfail(g, SLIMM_E_INVALID, "records were dealt through slimm_group_push_records*: a file is read by byte range or pushed, not both");
     const uint32_t n = static_cast<uint32_t>(g->ctx.size());
     static const bool trace = slimm::traced("cli");
     std::vector<slimm::SplitRange> r(n);
@@ -674,6 +713,12 @@ int slimm_group_stitch_ranges(slimm_group* g) {
                     static_cast<unsigned long long>(r[k].head_len), static_cast<unsigned long long>(got), left);
         left_of[k] = left;
         if (r[k].found_start) left = k;
+    }
+    if (g->order != SLIMM_ORDER_GROUPED) {
+        const int rc = n > 1 ? deal_by_key(g) : SLIMM_OK;
+        if (rc != SLIMM_OK) return rc;
+        g->stitched = true;
+        return SLIMM_OK;
     }
     uint64_t starts = 0, plain = 0;
     for (uint32_t k = 0; k < n; ++k) {
@@ -714,8 +759,8 @@ int slimm_group_get_profiles(slimm_group* g, const char* path) {
     const uint32_t n = static_cast<uint32_t>(g->ctx.size());
     int rc = flush_carry(g, g->cur);
     if (rc != SLIMM_OK) return rc;
-    if (n > 1 && g->order == SLIMM_ORDER_GROUPED && !g->stitched) {
-        rc = deal_from_member0(g);
+    if (n > 1 && !g->stitched) {
+        rc = g->order == SLIMM_ORDER_GROUPED ? deal_from_member0(g) : deal_from_member0_any(g);
         if (rc != SLIMM_OK) return rc;
     }
     if (n == 1 && !g->use_rccl) {  // (a group of one with RCCL forced goes the long way: the test of the RCCL calls)

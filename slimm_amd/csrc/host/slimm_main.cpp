@@ -179,7 +179,7 @@ struct Options {  // arg_options, reference src/slimm.hpp:49-87
     bool verify_grouping = false;  // --verify-grouping: count the read names that come back (slimm_check_grouping) and warn
     unsigned device_inflate = 1;   // --device-inflate K: every K-th window read in place is inflated on the device (0: none)
     unsigned window_mb = 0;        // --window-mb N: bytes per window buffer (tests make windows smaller than a record)
-    bool split_input = false;      // --split-input (with --devices): every member reads its own byte range of a grouped BAM / SAM / BGZF SAM
+    bool split_input = false;      // --split-input (with --devices): every member reads its own byte range of a BAM / SAM / BGZF SAM
 };
 bool g_trace = false;              // SLIMM_TRACE=cli (or all): millisecond marks of the stages on stderr
 
@@ -866,7 +866,8 @@ struct RecordPump {
     }
 };
 
-// --split-input: every member of a group reads, inflates and decodes its own contiguous byte range of a GROUPED file at
+// --split-input: every member of a group reads, inflates and decodes its own contiguous byte range of a file -- GROUPED by
+// read name or in any order (the stitch then deals the records by key) -- at
 // once -- its own pread threads, page-locked buffers and pushing thread -- and the library stitches the cuts on the
 // devices (include/slimm_hip.h, "ONE FILE SPLIT BY BYTE RANGE").  The file's form: BAM or SAM text in BGZF blocks -- ranges
 // of whole blocks, member 0 skips the header's inflated bytes -- or plain SAM text: ranges cut anywhere behind the header,
@@ -1222,16 +1223,17 @@ std::unique_ptr<Reading> set_up(Session& S, const std::string& path, bool any_or
     // (grouped streams are exact already: the reader compares the names of adjacent records)
     F->check_words = F->record_order == SLIMM_ORDER_ANY;
     // decoding starts now; the records are claimed further down, when the context exists (one context: the device decodes)
-    // (a group takes a GROUPED file through member 0's device decoders and deals the records device to device afterwards:
-    // slimm_group_get_profiles; any other order: the host reader deals them by key)
-    F->split_input = options.split_input && options.devices.size() > 1 && F->record_order == SLIMM_ORDER_GROUPED && reads_by_byte_range(bam) &&
+    // (a group takes a file through member 0's device decoders and deals the records device to device afterwards --
+    // slimm_group_get_profiles: a GROUPED file in stretches cut at qName runs, any other order by key; what the pump does
+    // not push raw -- --host-decode, pipes ... -- the host reader deals)
+    F->split_input = options.split_input && options.devices.size() > 1 && reads_by_byte_range(bam) &&
                      !options.host_decode && !options.verify_grouping && !options.packed_records;
     if (g_trace && !any_order && options.split_input && options.devices.size() > 1 && !bam.is_bam() &&
         (bam.compression() == Compression::Gzip || bam.compression() == Compression::Bzip2))
         fprintf(stderr, "[trace] --split-input: a %s stream is not cut by byte range; member 0 reads %s\n",
                 bam.compression() == Compression::Gzip ? "gzip" : "bzip2", path.c_str());
     if (!F->split_input)
-        F->pump.reset(new RecordPump(bam, F->check_words, options.devices.size() <= 1 || F->record_order == SLIMM_ORDER_GROUPED, options));
+        F->pump.reset(new RecordPump(bam, F->check_words, true, options));
 
     std::cerr << "Intializing coverages for all reference genome ... ";
     const uint32_t R = static_cast<uint32_t>(bam.ref_names().size());
@@ -1275,8 +1277,8 @@ std::unique_ptr<Reading> set_up(Session& S, const std::string& path, bool any_or
 }
 
 // What a push that found more records than one context takes leads to (the --split-input reading decides in run_group):
-// a group reading through member 0 -- HostDecode, the host reader deals them; one context of a grouped BAM, SAM or BGZF SAM -- MoreMembers,
-// a group on the device reads the file by byte range; any other one context -- Fail.
+// a group reading through member 0 -- HostDecode, the host reader deals them; one context of a BAM, SAM or BGZF SAM file, grouped
+// or in any order -- MoreMembers, a group on the device reads the file by byte range; any other one context -- Fail.
 enum class OnCap { Fail, HostDecode, MoreMembers };
 
 // The file's records through F.pump into `t`: Done, or Failed with the reason printed.  A record longer than the device
@@ -1411,7 +1413,7 @@ Outcome run_context(Session& S, Reading& F) {
     std::cerr << "[" << F.watch.lap() << " secs]" << std::endl;
 
     std::cerr << "Analysing alignments, reads and references ....... ";
-    const bool byte_ranges = F.record_order == SLIMM_ORDER_GROUPED && reads_by_byte_range(F.bam);
+    const bool byte_ranges = reads_by_byte_range(F.bam);
     const Outcome pushed = push_file(S, F, Target{ctx}, byte_ranges ? OnCap::MoreMembers : OnCap::Fail);
     if (pushed == Outcome::MoreMembers) {
         // more records than one context takes: contexts of a group on this one device, each its own byte range of the

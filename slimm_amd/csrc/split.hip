@@ -128,8 +128,8 @@ namespace slimm {
 
 int split_range(slimm_ctx* c, SplitRange* out) {
     if (!c || !out) return SLIMM_E_INVALID;
-    if (c->device < 0 || !c->win.file.active || !c->win.file.closed || c->win.file.bz2.on || c->order != SLIMM_ORDER_GROUPED)
-        return fail(c, SLIMM_E_INVALID, "a range of a split file: a GROUPED range of BAM, SAM or BGZF SAM pushed to its end");
+    if (c->device < 0 || !c->win.file.active || !c->win.file.closed || c->win.file.bz2.on)
+        return fail(c, SLIMM_E_INVALID, "a range of a split file: a range of BAM, SAM or BGZF SAM pushed to its end");
     out->found_start = c->win.file.found_start || !c->win.announced.starts_mid;
     out->head_len = c->win.announced.starts_mid ? c->win.file.head_len : 0u;
     out->n_records = c->n_pushed;

@@ -248,6 +248,13 @@ class Slimm:
         self._keepalive = (words, pos)
         self._check(self.L.slimm_set_records_device_marked(self.ctx, C.c_void_p(words.data_ptr()), C.c_void_p(pos.data_ptr()), n))
 
+    def records_held(self):
+        """slimm_records_device: (the records the context holds on the device, their form: 0 four arrays, 1 packed, 2 run-marked)."""
+        ptr = [C.c_void_p() for _ in range(4)]
+        n, form = C.c_uint64(), C.c_int()
+        self._check(self.L.slimm_records_device(self.ctx, *[C.byref(q) for q in ptr], C.byref(n), C.byref(form)))
+        return n.value, form.value
+
     def push_bam_bytes(self, data, window: int = 0) -> int:
         """slimm_push_bam_bytes: the alignment-record bytes of a BAM file (behind its header, BGZF-inflated), in windows of
         `window` bytes (0: one); the device finds the records and decodes them.  Returns the number of records."""
@@ -665,6 +672,30 @@ def host_avg_read_length(l_seq: np.ndarray, sample: int = 100000) -> int:
     return int(capi.lib().slimm_host_avg_read_length(_p(l_seq), l_seq.shape[0], sample))
 
 
+def partition_by_key(key, ref, pos, flag, check, m: int, device: int = 0):
+    """slimm_partition_by_key: the stable partition of four-array records by owner, (key & (2^62 - 1)) % m, that a group
+    of m members deals a file in any order with (slimm_amd/csrc/deal_by_key.hip).  check may be None.  Returns (key, ref,
+    pos, flag, check or None, the m stretch lengths, the kernels' milliseconds)."""
+    L = capi.lib()
+    key = np.ascontiguousarray(key, dtype=np.uint64)
+    ref = np.ascontiguousarray(ref, dtype=np.int32)
+    pos = np.ascontiguousarray(pos, dtype=np.int32)
+    flag = np.ascontiguousarray(flag, dtype=np.uint16)
+    check = None if check is None else np.ascontiguousarray(check, dtype=np.uint32)
+    n = len(key)
+    assert len(ref) == n and len(pos) == n and len(flag) == n and (check is None or len(check) == n)
+    out = [np.zeros(max(n, 1), dtype=a.dtype) for a in (key, ref, pos, flag)]
+    check_out = None if check is None else np.zeros(max(n, 1), dtype=np.uint32)
+    counts = np.zeros(m, dtype=np.uint64)
+    ms = C.c_double()
+    err = C.create_string_buffer(256)
+    rc = L.slimm_partition_by_key(device, _p(key), _p(ref), _p(pos), _p(flag), None if check is None else _p(check), n, m,
+                                  *[_p(a) for a in out], None if check_out is None else _p(check_out), _p(counts), C.byref(ms), err, 256)
+    if rc != 0:
+        raise capi.SlimmError(rc, err.value.decode())
+    return (*[a[:n] for a in out], None if check_out is None else check_out[:n], counts, ms.value)
+
+
 class SlimmGroup:
     """slimm_group_*: several GPUs in one process, used like one context (include/slimm_hip.h).  `devices` may name one
     device several times (that is how the tests run a group on a single GPU: the collectives are then copies)."""
@@ -740,12 +771,14 @@ class SlimmGroup:
     SPLIT_FORMS = ("bam", "sam", "bgzf_sam")
 
     def push_split(self, data, form: str, skip: int = 0, window: int = 0):
-        """One GROUPED file split by byte range, every member its own (include/slimm_hip.h, "ONE FILE SPLIT BY BYTE RANGE").
+        """One file split by byte range, every member its own (include/slimm_hip.h, "ONE FILE SPLIT BY BYTE RANGE"): GROUPED by
+        read name, or -- a group made with grouped=False -- in any order, in which case the stitch deals the records by key.
         `data`: the whole file -- header included -- as bytes, or its path; `form`: "bam" (BGZF blocks of BAM records), "sam"
         (plain text) or "bgzf_sam" (BGZF blocks of SAM text); `skip`: the header's bytes (for the BGZF forms its INFLATED
         bytes).  The ranges come from slimm_host_text_ranges / slimm_host_bgzf_ranges; member by member: the reference
         names (SAM), slimm_set_input_mid_file, the size hint, the range pushed in windows of `window` bytes (0: one); then
         slimm_group_stitch_ranges.  Returns (the n + 1 offsets, the records every member decoded before the stitch)."""
+        # (the planners, the announcements and the pushes are the same for both orders)
         import os
         import tempfile
 
