@@ -568,8 +568,8 @@ int slimm_group_set_exchange(slimm_group* g, int mode);
 int slimm_group_exchange(const slimm_group* g); /* the form in effect (what AUTO resolves to) */
 int slimm_group_get_profiles(slimm_group* g, const char* path); /* path may be NULL; SLIMM_E_NO_HITS like slimm_get_profiles */
 /* ONE FILE SPLIT BY BYTE RANGE over a group (files GROUPED by read name or in ANY order): every member reads, inflates and decodes its own contiguous
- * range of the file at once.  Three forms of file: BAM, SAM text, and SAM text in BGZF blocks (bgzip).  (A plain gzip
- * stream cannot be cut, and a bzip2 file's blocks start at bit offsets: those go through one member.)
+ * range of the file at once.  Four forms of file: BAM, SAM text, SAM text in BGZF blocks (bgzip), and bzip2-compressed SAM
+ * text (below: "bzip2 SAM by byte range").  (A plain gzip stream cannot be cut: it goes through one member.)
  *   The plan (host only, no GPU): offsets_out[0, n]; range i = [offsets_out[i], offsets_out[i + 1]), ranges may be empty.
  * slimm_host_bgzf_ranges -- BAM and BGZF SAM --: offsets_out[0] = 0, offsets_out[n] = the file's size; a range starts on a
  * BGZF block boundary (a header whose next three headers chain through BSIZE + 1, or whose chain reaches the EOF block or
@@ -603,7 +603,37 @@ int slimm_group_get_profiles(slimm_group* g, const char* path); /* path may be N
  * all head, sends and receives empty stretches.  Nothing may have been dealt through slimm_group_push_records* before.
  *   Memory: while the records are dealt every member holds one more copy of its records (22 bytes each, the send buffers);
  * they are released before slimm_group_stitch_ranges (or, through member 0, before phase A) goes on.  A member that receives
- * more records than it decoded grows its record arrays to what it receives. */
+ * more records than it decoded grows its record arrays to what it receives.
+ *   bzip2 SAM by byte range.  A bzip2 file's blocks start at bit offsets, and nothing in the file says where: the device
+ * finds them (their 48-bit magic at every bit offset) and trusts none.  THE RULE OF THE CUT: a block -- or an end-of-stream
+ * marker, with the next stream's header behind it -- belongs to the member in whose byte range the first bit of its magic
+ * lies.  slimm_host_bzip2_ranges cuts at plain byte offsets: offsets_out[0] = 0, offsets_out[n] = the file's size, the
+ * others divide evenly the bytes behind the block that holds decoded byte skip - 1 (the header's last byte: it decodes the
+ * file's first blocks on the host to find it; member 0 holds the whole header and pushes with that skip); SLIMM_E_INVALID
+ * for something that is no regular file, or does not start a bzip2 stream.  Every member announces its flags with
+ * slimm_set_input_mid_file AND its range's absolute file offsets with slimm_set_input_range(ctx, begin, end), and pushes
+ * -- slimm_push_bzip2_sam_bytes -- its range PLUS A SLACK behind it, slimm_bzip2_split_slack() bytes or up to the file's
+ * end, so that the block that starts inside the range can finish: no compressed byte is handed from member to member.
+ *   A range that starts inside the file starts its chain at the first candidate at or behind its first bit that decodes;
+ * candidates in front of it that do not are dropped as false magics, and an end-of-stream marker in front of it starts
+ * the chain instead.  It does not know its stream's level -- its blocks are decoded with the largest, and the largest one
+ * is remembered -- nor the combined CRC so far -- it keeps (number of blocks, partial value from 0) until its first
+ * marker.  A mismatch of that first block's CRC is SLIMM_E_SPLIT, not a verdict on the file.  A range that ends inside the
+ * file stops at the first block or marker that starts at or behind its end, at last = 1 too, and drops the rest of the
+ * slack; a block the slack does not finish is SLIMM_E_SPLIT; a range in which nothing starts decodes nothing and is an
+ * empty member.  Error messages name the file's bytes, as for one context.
+ *   slimm_group_stitch_ranges first goes left to right over the cuts on host scalars: the left chain must end exactly at
+ * the bit where the next member that holds a block starts (SLIMM_E_SPLIT otherwise); that member's blocks of its first
+ * stream must fit the level of the left chain's stream ("block longer than its stream's level allows"); and the combined
+ * CRC is linear -- c = rotl(c, 1) ^ crc per block --, so rotl^k(left's value) ^ the member's partial value must be the
+ * CRC of its first marker ("combined CRC mismatch", with the marker's byte), or is handed on to the next cut when it saw
+ * none.  The decoded text is then stitched as SAM text is: a member's text starts at a block boundary inside a line, and
+ * its head through the first newline goes to the member on its left. */
+int slimm_host_bzip2_ranges(const char* path, uint64_t skip, uint32_t n, uint64_t* offsets_out);
+/* A range's absolute file offsets [begin, end) (bzip2 SAM; before the range's first window, beside slimm_set_input_mid_file) */
+int slimm_set_input_range(slimm_ctx* ctx, uint64_t begin, uint64_t end);
+/* the bytes a member reads behind its range of a bzip2 file (slimm_amd/csrc/bzip2_block.h: kSplitSlack, from the format's bounds) */
+uint64_t slimm_bzip2_split_slack(void);
 int slimm_host_bgzf_ranges(const char* path, uint64_t skip, uint32_t n, uint64_t* offsets_out);
 int slimm_host_text_ranges(const char* path, uint64_t skip, uint32_t n, uint64_t* offsets_out);
 int slimm_set_input_mid_file(slimm_ctx* ctx, int starts_mid_file, int ends_mid_file);

@@ -26,6 +26,16 @@ constexpr uint64_t kBlockMagic = 0x314159265359ull, kEosMagic = 0x177245385090ul
 constexpr uint32_t kMaxBlock = 900000;      // RLE1 bytes of a level-9 block (the BWT string's length)
 constexpr uint32_t kMaxSelectors = 18002;   // what bzip2 writes at most (more are read and dropped, as bzip2 1.0.8 does)
 constexpr uint32_t kMaxGroups = 6, kMaxAlpha = 258, kMaxCodeLen = 23;
+// A file split by byte range (include/slimm_hip.h, "ONE FILE SPLIT BY BYTE RANGE"): a member reads this many bytes behind
+// its range, so that the block that starts in the range's last bit can finish there.  From the format's bounds: the
+// block's fixed fields (magic 48, CRC 32, randomised 1, origPtr 24, used-byte map 16 + 256, table count 3, selector count
+// 15), 2^15 - 1 selectors of at most 6 bits, 6 tables of a 5-bit start and 258 lengths that bzip2 writes in at most 19
+// two-bit steps and a stop bit each, kMaxBlock + 1 symbols (every symbol but the end of block gives a byte) of at most 20
+// bits, and an end-of-stream marker (magic 48, combined CRC 32, padding 7) with the next stream's header (32); rounded
+// up to 64 KiB.  (A table whose lengths wander up and down for longer is not what bzip2 writes: SLIMM_E_SPLIT.)
+constexpr uint64_t kSplitSlackBits = (48u + 32u + 1u + 24u + 16u + 256u + 3u + 15u) + 32767ull * 6u + 6ull * (5u + kMaxAlpha * 39ull) +
+                                     (kMaxBlock + 1ull) * 20u + (48u + 32u + 7u + 32u);
+constexpr uint64_t kSplitSlack = ((kSplitSlackBits + 7u) / 8u + 65535u) & ~65535ull;
 
 // A block's decode status; kRanOut: the bytes at hand end inside the block (more may come)
 enum Status : uint32_t {
@@ -315,6 +325,20 @@ struct Rle1 {
         return 1u;
     }
 };
+
+// the length of a block's text (RLE1 undone) from its links: the n-step walk without the bytes (the host's planner of
+// slimm_host_bzip2_ranges counts decoded bytes up to the SAM header's end)
+inline uint64_t text_length(const uint32_t* link, uint32_t n, uint32_t orig_ptr) {
+    Rle1 st;
+    uint64_t len = 0;
+    uint32_t p = orig_ptr, byte;
+    for (uint32_t k = 0; k < n; ++k) {
+        const uint32_t u = link[p];
+        len += st.step(u >> 24, byte);
+        p = u & kLinkMask;
+    }
+    return len;
+}
 
 SLIMM_BZ2_HD inline void crc_table(uint32_t* tab) {
     for (uint32_t i = 0; i < 256; ++i) {

@@ -42,6 +42,24 @@ __global__ __launch_bounds__(256) void k_bz2_find(const uint8_t* __restrict__ b,
     }
 }
 
+// A range that starts inside the file (a file split by byte range): the first end-of-stream magic whose first bit lies in
+// [bit_lo, bit_hi) -- the range's first element may be a marker, which no block decode vouches for; the stitch does
+// (split.hip: split_bz2_chains).  *first: ~0 before, the smallest such bit after
+__global__ __launch_bounds__(256) void k_bz2_first_eos(const uint8_t* __restrict__ b, uint64_t n_bytes, uint64_t bit_lo, uint64_t bit_hi,
+                                                        unsigned long long* __restrict__ first) {
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+    const uint64_t hi_byte = (bit_hi + 7u) >> 3, stop = hi_byte < n_bytes ? hi_byte : n_bytes;
+    for (uint64_t i = (bit_lo >> 3) + static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < stop; i += stride) {
+        uint64_t v = 0;   // bytes i .. i + 7, the first one highest (the buffer has kBz2Tail zeroed bytes behind n_bytes)
+        for (uint32_t k = 0; k < 8; ++k) v = (v << 8) | b[i + k];
+        for (uint32_t k = 0; k < 8; ++k) {
+            const uint64_t bit = i * 8u + k;
+            if (bit < bit_lo || bit >= bit_hi || bit + 48u > n_bytes * 8u) continue;
+            if (((v >> (16u - k)) & 0xffffffffffffull) == bz2::kEosMagic) atomicMin(first, static_cast<unsigned long long>(bit));
+        }
+    }
+}
+
 __global__ __launch_bounds__(64) void k_bz2_decode(const uint8_t* __restrict__ b, uint64_t end_bit, const unsigned long long* __restrict__ cand,
                                                     uint8_t* __restrict__ ll, uint32_t* __restrict__ hist, bz2::BlockInfo* __restrict__ info) {
     __shared__ bz2::Tables t;
@@ -170,6 +188,9 @@ double ms_since(std::chrono::steady_clock::time_point t0) {
 }
 
 #define BZ2_FAIL(fmt, ...) fail(c, SLIMM_E_INVALID, "bzip2-compressed input is not supported unless it decodes: " fmt, __VA_ARGS__)
+// a range that ends inside the file ran out of bytes: the slack behind it (bz2::kSplitSlack) did not finish its last block
+#define BZ2_SLACK_FAIL(what, at) \
+    fail(c, SLIMM_E_SPLIT, "bzip2: %s at byte %llu is not finished by the %llu bytes read behind the range", what, at, (unsigned long long)bz2::kSplitSlack)
 
 // the block magics of pend from Z.bit on, in order: the bytes not read yet go to the device first (those in front of
 // Z.bit are dropped from pend)
@@ -221,9 +242,34 @@ int bz2_find(slimm_ctx* c) {
         std::sort(Z.cand.begin(), Z.cand.end());
         Z.cand.erase(std::unique(Z.cand.begin(), Z.cand.end()), Z.cand.end());
     }
+    const WindowPipeline::Announced& A = c->win.announced;
+    if (A.has_range && A.ends_mid) {   // (blocks that start at or behind the range's end are the next member's)
+        const uint64_t lim = A.range_end > Z.base ? (A.range_end - Z.base) * 8u : 0u;
+        Z.cand.erase(std::lower_bound(Z.cand.begin(), Z.cand.end(), lim), Z.cand.end());
+    }
     Z.next_cand = 0;
     Z.found = true;
     Z.ms_find += ms_since(t0);
+    return SLIMM_OK;
+}
+
+// the first end-of-stream magic of the bytes on the device whose first bit lies in [lo, hi): *bit (~0: none)
+int bz2_first_eos(slimm_ctx* c, uint64_t lo, uint64_t hi, uint64_t* bit) {
+    WindowPipeline::Bzip2& S = c->win.bz2;
+    hipStream_t st = c->stream;
+    const uint64_t n = c->win.file.bz2.pend.size();
+    unsigned long long* d_first = reinterpret_cast<unsigned long long*>(S.count.p + 2);   // (count holds four words)
+    unsigned long long got = ~0ull;
+    *bit = ~0ull;
+    if (lo >= hi || lo + 48u > n * 8u) return SLIMM_OK;
+    HIP_TRY(c, hipMemsetAsync(d_first, 0xff, sizeof(got), st));
+    const uint64_t span = std::min<uint64_t>(n, (hi + 7u) >> 3) - (lo >> 3);
+    const uint32_t grid = static_cast<uint32_t>(std::max<uint64_t>(1u, std::min<uint64_t>((span + 255u) / 256u, 4096u)));
+    hipLaunchKernelGGL(k_bz2_first_eos, dim3(grid), dim3(256), 0, st, S.comp.p, n, lo, hi, d_first);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(&got, d_first, sizeof(got), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    *bit = got;
     return SLIMM_OK;
 }
 
@@ -256,8 +302,12 @@ int bz2_decode_batch(slimm_ctx* c, bool last) {
     WindowPipeline::File::Bzip2& Z = c->win.file.bz2;
     WindowPipeline::Bzip2& S = c->win.bz2;
     hipStream_t st = c->stream;
+    WindowPipeline::File::Bzip2::Chain& K = Z.chain;
+    const WindowPipeline::Announced& A = c->win.announced;
+    const bool starts_mid = A.has_range && A.starts_mid, ends_mid = A.has_range && A.ends_mid;
     Z.ready.clear();
     Z.ready_pos = 0;
+    if (K.ended) return SLIMM_OK;              // (a range that ends inside the file: what is left of the slack is dropped)
     if (Z.waiting && !last) return SLIMM_OK;   // (no byte has come since the chain stopped for want of them)
     SLIMM_TRY(bz2_reserve(c));
     if (!Z.found) {
@@ -270,6 +320,68 @@ int bz2_decode_batch(slimm_ctx* c, bool last) {
     std::vector<uint32_t> slots;
     std::vector<uint32_t> crcs;
     std::vector<uint64_t> ats;
+    auto abs_bit = [&](uint64_t bit) { return Z.base * 8u + bit; };
+    // the batch of candidates from `from` on decoded into slots 0 .. nb - 1
+    auto decode_from = [&](size_t from) -> int {
+        const auto t0 = std::chrono::steady_clock::now();
+        batch0 = from;
+        nb = std::min<size_t>(Z.slots, Z.cand.size() - batch0);
+        HIP_TRY(c, hipMemcpyAsync(S.d_cand.p, Z.cand.data() + batch0, nb * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_bz2_decode, dim3(static_cast<uint32_t>(nb)), dim3(64), 0, st, S.comp.p, end_bit, S.d_cand.p, S.ll.p, S.hist.p,
+                           S.info.p);
+        HIP_TRY(c, hipGetLastError());
+        hinfo.resize(nb);
+        HIP_TRY(c, hipMemcpyAsync(hinfo.data(), S.info.p, nb * sizeof(bz2::BlockInfo), hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        Z.ms_decode += ms_since(t0);
+        ++Z.batches;
+        return SLIMM_OK;
+    };
+    if (starts_mid && !K.started) {
+        // A range that starts inside the file: its chain starts at its first element -- the first candidate that decodes
+        // (those in front of it are false magics), or an end-of-stream marker in front of that one -- inside a stream of
+        // unknown level.  Nothing vouches for that start but the member on the left, whose chain must end there
+        // (SLIMM_FORCE bzip2_split_wrong_first: the first element is passed over, the chain starts at the one behind it)
+        const uint64_t range_end_bit = ends_mid ? (A.range_end > Z.base ? (A.range_end - Z.base) * 8u : 0u) : end_bit;
+        uint64_t lo = Z.bit, first = ~0ull;
+        size_t i = Z.next_cand;
+        for (int pass = forced("bzip2_split_wrong_first") ? 2 : 1; pass > 0; --pass) {
+            bool have_block = false;
+            for (; i < Z.cand.size(); ++i) {
+                if (Z.cand[i] < lo) continue;
+                if (i < batch0 || i >= batch0 + nb) SLIMM_TRY(decode_from(i));
+                const uint32_t status = hinfo[i - batch0].status;
+                if (status == bz2::kRanOut && !last) break;   // (its bytes go on with the next push: no verdict yet)
+                if (status != bz2::kOk) continue;
+                have_block = true;
+                break;
+            }
+            if (!have_block && !last) {
+                Z.waiting = true;
+                return SLIMM_OK;
+            }
+            SLIMM_TRY(bz2_first_eos(c, lo, std::min(have_block ? Z.cand[i] : end_bit, range_end_bit), &first));
+            if (have_block) first = std::min<uint64_t>(first, Z.cand[i]);
+            if (first == ~0ull) break;
+            lo = first + 1u;   // (forced: the element behind the first one)
+        }
+        const size_t next = static_cast<size_t>(std::lower_bound(Z.cand.begin(), Z.cand.end(), first) - Z.cand.begin());
+        Z.false_magics += next - Z.next_cand;
+        Z.next_cand = next;
+        K.started = true;
+        if (first == ~0ull) {   // (no block or marker starts in the range: an empty member)
+            K.ended = true;
+            K.end_bit = abs_bit(Z.bit);
+            return SLIMM_OK;
+        }
+        Z.bit = first;
+        Z.in_stream = K.first_stream = K.any = true;
+        Z.level = 9;
+        Z.combined = 0;
+        Z.streams = 1;
+        K.first_bit = abs_bit(first);
+        push_trace_bz2("the range's chain starts at bit %llu (byte %llu)", (unsigned long long)K.first_bit, at(first));
+    }
     for (;;) {
         if (!Z.in_stream) {   // a stream header, at a byte
             const uint64_t byte = Z.bit >> 3;
@@ -278,6 +390,7 @@ int bz2_decode_batch(slimm_ctx* c, bool last) {
             if (avail == 0) {
                 if (last && Z.streams == 0) return BZ2_FAIL("truncated at byte %llu", at(Z.bit));
                 Z.waiting = true;
+                K.at_file_end = last;
                 break;
             }
             if (avail < 4 && !last && memcmp(h, "BZh", avail) == 0) {
@@ -295,9 +408,16 @@ int bz2_decode_batch(slimm_ctx* c, bool last) {
             ++Z.streams;
             Z.bit += 32;
         }
+        // (a range that ends inside the file: the element -- a block, or a marker with the stream header behind it -- that
+        // starts at or behind the range's end is the next member's)
+        if (ends_mid && abs_bit(Z.bit) >= A.range_end * 8u) {
+            K.ended = true;
+            break;
+        }
         bz2::Bits br(Z.pend.data(), Z.bit, end_bit);
         uint64_t magic;
         if (!br.peek48(magic)) {
+            if (last && ends_mid) return BZ2_SLACK_FAIL("what starts", at(Z.bit));
             if (last) return BZ2_FAIL("truncated at byte %llu", at(Z.bit));
             Z.waiting = true;
             break;
@@ -305,16 +425,24 @@ int bz2_decode_batch(slimm_ctx* c, bool last) {
         if (magic == bz2::kEosMagic) {
             uint32_t v, hi, lo;
             if (!br.get(24, v) || !br.get(24, v) || !br.get(16, hi) || !br.get(16, lo)) {
+                if (last && ends_mid) return BZ2_SLACK_FAIL("the end-of-stream marker", at(Z.bit));
                 if (last) return BZ2_FAIL("truncated end-of-stream marker at byte %llu", at(Z.bit));
                 Z.waiting = true;
                 break;
             }
-            if (((hi << 16) | lo) != Z.combined) {
+            if (K.first_stream) {   // (the stream the range started in: the stitch knows what came before)
+                K.first_stream = false;
+                K.has_eos = true;
+                K.first_combined = Z.combined;
+                K.eos_crc = (hi << 16) | lo;
+                K.eos_at = at(Z.bit);
+            } else if (((hi << 16) | lo) != Z.combined) {
                 if (!slots.empty()) break;   // (the blocks in front go first: a block CRC that does not match is named as such)
                 return BZ2_FAIL("end-of-stream marker at byte %llu: combined CRC mismatch", at(Z.bit));
             }
             Z.bit = (br.pos() + 7u) & ~7ull;
             Z.in_stream = false;
+            K.any = true;
             continue;
         }
         if (magic != bz2::kBlockMagic) return BZ2_FAIL("at byte %llu: %s", at(Z.bit), bz2::status_text(bz2::kNoBlock));
@@ -325,30 +453,25 @@ int bz2_decode_batch(slimm_ctx* c, bool last) {
         }
         if (Z.next_cand >= Z.cand.size() || Z.cand[Z.next_cand] != Z.bit)
             return fail(c, SLIMM_E_INVALID, "bzip2: the block magic at byte %llu was not found by the device's scan", at(Z.bit));
-        if (Z.next_cand >= batch0 + nb) {
+        if (Z.next_cand < batch0 || Z.next_cand >= batch0 + nb) {
             if (!slots.empty()) break;
-            const auto t0 = std::chrono::steady_clock::now();
-            batch0 = Z.next_cand;
-            nb = std::min<size_t>(Z.slots, Z.cand.size() - batch0);
-            HIP_TRY(c, hipMemcpyAsync(S.d_cand.p, Z.cand.data() + batch0, nb * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(k_bz2_decode, dim3(static_cast<uint32_t>(nb)), dim3(64), 0, st, S.comp.p, end_bit, S.d_cand.p, S.ll.p, S.hist.p,
-                               S.info.p);
-            HIP_TRY(c, hipGetLastError());
-            hinfo.resize(nb);
-            HIP_TRY(c, hipMemcpyAsync(hinfo.data(), S.info.p, nb * sizeof(bz2::BlockInfo), hipMemcpyDeviceToHost, st));
-            HIP_TRY(c, hipStreamSynchronize(st));
-            Z.ms_decode += ms_since(t0);
-            ++Z.batches;
+            SLIMM_TRY(decode_from(Z.next_cand));
         }
         const uint32_t s = static_cast<uint32_t>(Z.next_cand - batch0);
         const bz2::BlockInfo& r = hinfo[s];
         if (r.status == bz2::kRanOut) {   // (the block's bytes go on with the next push)
+            if (last && ends_mid) return BZ2_SLACK_FAIL("the block", at(Z.bit));
             if (last) return BZ2_FAIL("block at byte %llu: truncated", at(Z.bit));
             Z.waiting = true;
             break;
         }
         if (r.status != bz2::kOk) return BZ2_FAIL("block at byte %llu: %s", at(Z.bit), bz2::status_text(r.status));
         if (r.n > Z.level * 100000u) return BZ2_FAIL("block at byte %llu: %s", at(Z.bit), bz2::status_text(bz2::kTooLong));
+        if (K.first_stream) {   // (level unknown: the stitch holds the largest block against the left chain's level)
+            ++K.first_blocks;
+            if (r.n > K.first_max_n) K.first_max_n = r.n, K.first_max_at = at(Z.bit);
+        }
+        K.any = true;
         slots.push_back(s);
         crcs.push_back(r.crc);
         ats.push_back(at(Z.bit));
@@ -356,6 +479,7 @@ int bz2_decode_batch(slimm_ctx* c, bool last) {
         Z.bit = r.end_bit;
         ++Z.next_cand;
     }
+    K.end_bit = abs_bit(Z.bit);
     if (slots.empty()) return SLIMM_OK;
     // the blocks of the chain: inverse BWT, text lengths
     const auto t0 = std::chrono::steady_clock::now();
@@ -376,6 +500,7 @@ int bz2_decode_batch(slimm_ctx* c, bool last) {
         b.drop = std::min<uint64_t>(Z.skip_left, b.len);
         Z.skip_left -= b.drop;
         b.at = ats[i];
+        b.unchecked = starts_mid && Z.blocks == 0 && i == 0;
         Z.ready.push_back(b);
     }
     Z.blocks += k;
@@ -428,8 +553,15 @@ int bz2_emit(slimm_ctx* c, uint8_t* dst, size_t n_blocks, uint8_t* last_byte) {
     if (off) HIP_TRY(c, hipMemcpyAsync(last_byte, dst + off - 1, 1, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
     Z.ms_emit += ms_since(t0);
-    for (uint32_t i = 0; i < k; ++i)
-        if (!ok[i]) return BZ2_FAIL("block at byte %llu: %s", static_cast<unsigned long long>(Z.ready[Z.ready_pos + i].at), bz2::status_text(bz2::kBadCrc));
+    for (uint32_t i = 0; i < k; ++i) {
+        if (ok[i]) continue;
+        const auto& b = Z.ready[Z.ready_pos + i];
+        // (nothing but this CRC says that a range's first block is one: no verdict on the file)
+        if (b.unchecked)
+            return fail(c, SLIMM_E_SPLIT, "bzip2: the first block of a range that starts inside the file, at byte %llu: %s",
+                        static_cast<unsigned long long>(b.at), bz2::status_text(bz2::kBadCrc));
+        return BZ2_FAIL("block at byte %llu: %s", static_cast<unsigned long long>(b.at), bz2::status_text(bz2::kBadCrc));
+    }
     Z.ready_pos += n_blocks;
     return SLIMM_OK;
 }

@@ -700,6 +700,12 @@ int slimm_group_stitch_ranges(slimm_group* g) {
     static const bool trace = slimm::traced("cli");
     std::vector<slimm::SplitRange> r(n);
     for (uint32_t i = 0; i < n; ++i) GTRY(g, i, slimm::split_range(g->ctx[i], &r[i]));
+    if (slimm::split_is_bzip2(g->ctx[0])) {   // (the chains of blocks first: host scalars only)
+        uint32_t bad = 0;
+        const int rc = slimm::split_bz2_chains(g->ctx.data(), n, &bad);
+        if (rc == SLIMM_E_SPLIT) return gfail(g, SLIMM_E_SPLIT, "cut in front of member %u: %s", bad, slimm_last_error(g->ctx[bad]));
+        if (rc < 0) return member_failed(g, bad, rc, "the chain of blocks across a cut");
+    }
     std::vector<uint32_t> left_of(n, 0);
     uint32_t left = 0;
     for (uint32_t k = 1; k < n; ++k) {

@@ -125,6 +125,9 @@ SLIMM_FORWARD(int, slimm_pin_host_buffer, (slimm_ctx* a, const void* b, uint64_t
 SLIMM_FORWARD(int, slimm_host_bgzf_ranges, (const char* a, uint64_t b, uint32_t c, uint64_t* d), (a, b, c, d))
 SLIMM_FORWARD(int, slimm_host_text_ranges, (const char* a, uint64_t b, uint32_t c, uint64_t* d), (a, b, c, d))
 SLIMM_FORWARD(int, slimm_set_input_mid_file, (slimm_ctx* a, int b, int c), (a, b, c))
+SLIMM_FORWARD(int, slimm_host_bzip2_ranges, (const char* a, uint64_t b, uint32_t c, uint64_t* d), (a, b, c, d))
+SLIMM_FORWARD(int, slimm_set_input_range, (slimm_ctx* a, uint64_t b, uint64_t c), (a, b, c))
+SLIMM_FORWARD(uint64_t, slimm_bzip2_split_slack, (), ())
 SLIMM_FORWARD(int, slimm_group_stitch_ranges, (slimm_group* a), (a))
 SLIMM_FORWARD(uint64_t, slimm_record_cap, (), ())
 SLIMM_FORWARD(int, slimm_shutdown, (), ())
@@ -179,7 +182,7 @@ struct Options {  // arg_options, reference src/slimm.hpp:49-87
     bool verify_grouping = false;  // --verify-grouping: count the read names that come back (slimm_check_grouping) and warn
     unsigned device_inflate = 1;   // --device-inflate K: every K-th window read in place is inflated on the device (0: none)
     unsigned window_mb = 0;        // --window-mb N: bytes per window buffer (tests make windows smaller than a record)
-    bool split_input = false;      // --split-input (with --devices): every member reads its own byte range of a BAM / SAM / BGZF SAM
+    bool split_input = false;      // --split-input (with --devices): every member reads its own byte range of a BAM / SAM / BGZF SAM / bzip2 SAM
 };
 bool g_trace = false;              // SLIMM_TRACE=cli (or all): millisecond marks of the stages on stderr
 
@@ -871,10 +874,12 @@ struct RecordPump {
 // once -- its own pread threads, page-locked buffers and pushing thread -- and the library stitches the cuts on the
 // devices (include/slimm_hip.h, "ONE FILE SPLIT BY BYTE RANGE").  The file's form: BAM or SAM text in BGZF blocks -- ranges
 // of whole blocks, member 0 skips the header's inflated bytes -- or plain SAM text: ranges cut anywhere behind the header,
-// read as they lie in the file (`names`: the header's reference names, which every member's SAM decoder needs).  The
+// read as they lie in the file (`names`: the header's reference names, which every member's SAM decoder needs) -- or bzip2
+// SAM: ranges cut at any byte behind the header's block, each read with slimm_bzip2_split_slack() bytes behind it (at most
+// to the file's end) so that its last block can finish; member 0 skips the header's decoded bytes.  The
 // reader threads are split over the members, not multiplied (a command gets 16 CPUs).  Returns SLIMM_OK or the code of
 // what failed; *why says what.
-enum class SplitForm { Bam, BgzfSam, Sam };
+enum class SplitForm { Bam, BgzfSam, Sam, Bzip2Sam };
 struct SplitBuffers {   // (page-locked for the life of the group's contexts: they outlive the group)
     struct Map {
         uint8_t* p = nullptr;
@@ -895,12 +900,17 @@ struct SplitBuffers {   // (page-locked for the life of the group's contexts: th
 int read_split(slimm_group* grp, uint32_t G, const std::string& path, SplitForm form, const std::vector<std::string>& names,
                uint64_t header_bytes, size_t window_cap, SplitBuffers& bufs, std::string& why) {
     std::vector<uint64_t> off(G + 1, 0);
-    const bool text = form == SplitForm::Sam, sam = form != SplitForm::Bam;
-    if (text ? slimm_host_text_ranges(path.c_str(), header_bytes, G, off.data()) != SLIMM_OK
-             : (header_bytes >= (1ull << 32) || slimm_host_bgzf_ranges(path.c_str(), header_bytes, G, off.data()) != SLIMM_OK)) {
-        why = text ? "the file's text could not be planned into ranges" : "the file's BGZF blocks could not be planned into ranges";
+    const bool bzip2 = form == SplitForm::Bzip2Sam;
+    const bool text = form == SplitForm::Sam || bzip2, sam = form != SplitForm::Bam;   // (text: the bytes as they lie in the file)
+    if (bzip2 ? (header_bytes >= (1ull << 32) || slimm_host_bzip2_ranges(path.c_str(), header_bytes, G, off.data()) != SLIMM_OK)
+        : text ? slimm_host_text_ranges(path.c_str(), header_bytes, G, off.data()) != SLIMM_OK
+               : (header_bytes >= (1ull << 32) || slimm_host_bgzf_ranges(path.c_str(), header_bytes, G, off.data()) != SLIMM_OK)) {
+        why = bzip2  ? "the file's bzip2 streams could not be planned into ranges"
+              : text ? "the file's text could not be planned into ranges"
+                     : "the file's BGZF blocks could not be planned into ranges";
         return SLIMM_E_INVALID;
     }
+    const uint64_t slack = bzip2 ? slimm_bzip2_split_slack() : 0u;
     std::vector<const char*> name_ptrs;
     for (const std::string& nm : names) name_ptrs.push_back(nm.c_str());
     const int fd = open(path.c_str(), O_RDONLY);
@@ -939,10 +949,12 @@ int read_split(slimm_group* grp, uint32_t G, const std::string& path, SplitForm 
         };
         int rc = sam ? slimm_set_reference_names(ctx, name_ptrs.data()) : SLIMM_OK;
         if (rc == SLIMM_OK) rc = slimm_set_input_mid_file(ctx, i > 0 ? 1 : 0, i + 1 < G ? 1 : 0);
+        if (rc == SLIMM_OK && bzip2) rc = slimm_set_input_range(ctx, off[i], off[i + 1]);
         if (rc == SLIMM_OK) rc = slimm_set_input_size_hint(ctx, off[i + 1] - off[i]);
         if (rc != SLIMM_OK) return failed(rc, slimm_last_error(ctx));
         for (auto* b : M.buf) (void)slimm_pin_host_buffer(ctx, b, cap);   // (pageable memory still works)
-        const uint64_t end = off[i + 1];
+        // (bzip2: the slack behind the range -- none behind the file's last --, at most to the file's end)
+        const uint64_t end = std::min<uint64_t>(off[G], off[i + 1] + (i + 1 < G ? slack : 0u));
         // whole BGZF blocks of [at, end) into buffer w, at most `cap` bytes, by pread on the member's share of the threads:
         // the bytes of those blocks (0: none fits), -1 on a read error.  Blocks of SAM text end a push at `max_inflated`
         // inflated bytes as well (a push is one device window at most, and text may compress 24-fold: 80 MB of blocks
@@ -1014,7 +1026,9 @@ int read_split(slimm_group* grp, uint32_t G, const std::string& path, SplitForm 
             t0 = std::chrono::steady_clock::now();
             const uint32_t skip = pos == off[i] && i == 0 ? static_cast<uint32_t>(header_bytes) : 0u;
             const uint64_t nb = static_cast<uint64_t>(n);
-            if (!n)   // (an empty range)
+            if (bzip2)
+                rc = slimm_push_bzip2_sam_bytes(ctx, n ? M.buf[w] : nullptr, nb, skip, last ? 1 : 0, &got);
+            else if (!n)   // (an empty range)
                 rc = sam ? slimm_push_sam_bytes(ctx, nullptr, 0, 1, &got) : slimm_push_bam_bytes(ctx, nullptr, 0, 1, &got);
             else if (text)
                 rc = slimm_push_sam_bytes(ctx, M.buf[w], nb, last ? 1 : 0, &got);
@@ -1056,13 +1070,16 @@ int read_split(slimm_group* grp, uint32_t G, const std::string& path, SplitForm 
     return rc;
 }
 
-// The files read_split takes: a regular file of BAM records, of SAM text, or of SAM text in BGZF blocks.  (A plain gzip
-// stream cannot be cut, and a bzip2 file's blocks start at bit offsets and chain from the first: those go through one member.)
+// The files read_split takes: a regular file of BAM records, of SAM text, of SAM text in BGZF blocks, or of bzip2 SAM.  (A
+// plain gzip stream cannot be cut: it goes through one member.)
 bool reads_by_byte_range(const AlignmentFile& f) {
-    return f.regular_file() && (f.is_bam() || f.compression() == Compression::None || f.compression() == Compression::Bgzf);
+    return f.regular_file() && (f.is_bam() || f.compression() == Compression::None || f.compression() == Compression::Bgzf ||
+                                f.compression() == Compression::Bzip2);
 }
 SplitForm split_form(const AlignmentFile& f) {
-    return f.is_bam() ? SplitForm::Bam : (f.compression() == Compression::Bgzf ? SplitForm::BgzfSam : SplitForm::Sam);
+    if (f.is_bam()) return SplitForm::Bam;
+    if (f.compression() == Compression::Bzip2) return SplitForm::Bzip2Sam;
+    return f.compression() == Compression::Bgzf ? SplitForm::BgzfSam : SplitForm::Sam;
 }
 
 // One reading of a file up to its context: the file open at its first record, the choices its header and the options make,
@@ -1228,10 +1245,8 @@ std::unique_ptr<Reading> set_up(Session& S, const std::string& path, bool any_or
     // not push raw -- --host-decode, pipes ... -- the host reader deals)
     F->split_input = options.split_input && options.devices.size() > 1 && reads_by_byte_range(bam) &&
                      !options.host_decode && !options.verify_grouping && !options.packed_records;
-    if (g_trace && !any_order && options.split_input && options.devices.size() > 1 && !bam.is_bam() &&
-        (bam.compression() == Compression::Gzip || bam.compression() == Compression::Bzip2))
-        fprintf(stderr, "[trace] --split-input: a %s stream is not cut by byte range; member 0 reads %s\n",
-                bam.compression() == Compression::Gzip ? "gzip" : "bzip2", path.c_str());
+    if (g_trace && !any_order && options.split_input && options.devices.size() > 1 && !bam.is_bam() && bam.compression() == Compression::Gzip)
+        fprintf(stderr, "[trace] --split-input: a gzip stream is not cut by byte range; member 0 reads %s\n", path.c_str());
     if (!F->split_input)
         F->pump.reset(new RecordPump(bam, F->check_words, true, options));
 
@@ -1277,7 +1292,7 @@ std::unique_ptr<Reading> set_up(Session& S, const std::string& path, bool any_or
 }
 
 // What a push that found more records than one context takes leads to (the --split-input reading decides in run_group):
-// a group reading through member 0 -- HostDecode, the host reader deals them; one context of a BAM, SAM or BGZF SAM file, grouped
+// a group reading through member 0 -- HostDecode, the host reader deals them; one context of a BAM, SAM, BGZF SAM or bzip2 SAM file, grouped
 // or in any order -- MoreMembers, a group on the device reads the file by byte range; any other one context -- Fail.
 enum class OnCap { Fail, HostDecode, MoreMembers };
 

@@ -1,11 +1,12 @@
-// One file -- BAM, SAM text or BGZF blocks of SAM text -- split by byte range over a group's members (include/slimm_hip.h,
-// "ONE FILE SPLIT BY BYTE RANGE"): the host's plan of the ranges (slimm_host_bgzf_ranges, slimm_host_text_ranges) and the
-// per-member steps of slimm_group_stitch_ranges (split.h; group.hip runs them cut by cut).  A range that starts inside
+// One file -- BAM, SAM text, BGZF blocks of SAM text or bzip2 SAM -- split by byte range over a group's members
+// (include/slimm_hip.h, "ONE FILE SPLIT BY BYTE RANGE"): the host's plan of the ranges (slimm_host_bgzf_ranges,
+// slimm_host_text_ranges, slimm_host_bzip2_ranges) and the per-member steps of slimm_group_stitch_ranges (split.h; group.hip runs them cut by cut).  A range that starts inside
 // the file guesses its first record as k_bam_pieces guesses a piece's (windows.hip, bam_decode.hip: k_bam_first_guess);
 // the member on its left confirms the guess one level up, as k_bam_verify confirms a piece's: its incomplete last record
 // followed by the right member's head must be whole records that end exactly where the guess begins.  A range of SAM
 // text guesses nothing: its first line starts behind its first newline (sam_decode.hip: k_sam_first_newline), and the
-// left member's last line must end with the head.  The reference reads one file with one reader (src/misc.hpp:498-522).
+// left member's last line must end with the head.  A range of bzip2 SAM starts at the first block of its own
+// (bzip2_decode.hip) and is text from there on; its chain of blocks is held against its neighbours' first (split_bz2_chains).  The reference reads one file with one reader (src/misc.hpp:498-522).
 #include <fcntl.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -122,14 +123,137 @@ int slimm_host_text_ranges(const char* path, uint64_t skip, uint32_t n, uint64_t
     return SLIMM_OK;
 }
 
+uint64_t slimm_bzip2_split_slack(void) { return slimm::bz2::kSplitSlack; }
+
+// bzip2 is cut at plain byte offsets: a block belongs to the range its magic's first bit lies in, and the device finds the
+// blocks (bzip2_decode.hip).  Only the SAM header is decoded here, block by block from the file's start, for the floor
+int slimm_host_bzip2_ranges(const char* path, uint64_t skip, uint32_t n, uint64_t* offsets_out) {
+    namespace bz2 = slimm::bz2;
+    if (!path || !n || !offsets_out) return SLIMM_E_INVALID;
+    File f;
+    f.fd = open(path, O_RDONLY);
+    struct stat sb;
+    if (f.fd < 0 || fstat(f.fd, &sb) != 0 || !S_ISREG(sb.st_mode)) return SLIMM_E_INVALID;
+    f.size = static_cast<uint64_t>(sb.st_size);
+    std::vector<uint8_t> in;
+    auto more = [&]() {   // the file's next bytes behind `in` (false: none left, or a read error)
+        const size_t have = in.size(), add = static_cast<size_t>(std::min<uint64_t>(f.size - have, std::max<uint64_t>(4u << 20, have)));
+        if (!add) return false;
+        in.resize(have + add);
+        return f.read(have, in.data() + have, add);
+    };
+    if (!more() || in.size() < 4 || memcmp(in.data(), "BZh", 3) != 0 || in[3] < '1' || in[3] > '9') return SLIMM_E_INVALID;
+    // no cut in front of the end of the block that holds decoded byte skip - 1: member 0 holds the whole header
+    uint64_t bit = 0, decoded = 0;
+    bool in_stream = false;
+    std::unique_ptr<bz2::Tables> t(new bz2::Tables);
+    std::vector<uint8_t> ll;
+    std::vector<uint32_t> link, counts(256), cf(256);
+    while (decoded < skip) {
+        if (!in_stream) {
+            const uint64_t at = bit >> 3;
+            if (at + 4 > in.size()) {
+                if (!more()) return SLIMM_E_INVALID;   // (the streams end in front of decoded byte `skip`)
+                continue;
+            }
+            if (memcmp(in.data() + at, "BZh", 3) != 0 || in[at + 3] < '1' || in[at + 3] > '9') return SLIMM_E_INVALID;
+            in_stream = true;
+            bit += 32;
+        }
+        bz2::Bits br(in.data(), bit, in.size() * 8u);
+        uint64_t magic;
+        uint32_t v;
+        if (!br.peek48(magic)) {
+            if (!more()) return SLIMM_E_INVALID;
+            continue;
+        }
+        if (magic == bz2::kEosMagic) {
+            if (!br.get(24, v) || !br.get(24, v) || !br.get(16, v) || !br.get(16, v)) {
+                if (!more()) return SLIMM_E_INVALID;
+                continue;
+            }
+            bit = (br.pos() + 7u) & ~7ull;
+            in_stream = false;
+            continue;
+        }
+        if (magic != bz2::kBlockMagic) return SLIMM_E_INVALID;
+        ll.resize(bz2::kMaxBlock);
+        link.resize(bz2::kMaxBlock);
+        bz2::BlockInfo info;
+        const uint32_t status = bz2::decode_block(in.data(), bit, in.size() * 8u, bz2::kMaxBlock, *t, ll.data(), counts.data(), info);
+        if (status == bz2::kRanOut && more()) continue;
+        if (status != bz2::kOk) return SLIMM_E_INVALID;
+        bz2::link_block(ll.data(), info.n, counts.data(), link.data(), cf.data());
+        decoded += bz2::text_length(link.data(), info.n, info.orig_ptr);
+        bit = info.end_bit;
+    }
+    const uint64_t floor = std::min<uint64_t>(f.size, (bit + 7u) >> 3);
+    offsets_out[0] = 0;
+    for (uint32_t i = 1; i < n; ++i)
+        offsets_out[i] = floor + static_cast<uint64_t>(static_cast<unsigned __int128>(f.size - floor) * i / n);
+    offsets_out[n] = f.size;
+    return SLIMM_OK;
+}
+
 }  // extern "C"
 
 namespace slimm {
 
+bool split_is_bzip2(const slimm_ctx* c) { return c->win.file.bz2.on; }
+
+int split_bz2_chains(slimm_ctx* const* members, uint32_t n, uint32_t* bad) {
+    auto rotl = [](uint32_t v, uint32_t k) {
+        k &= 31u;
+        return k ? (v << k) | (v >> (32u - k)) : v;
+    };
+    // the chain so far: where it ended, inside a stream of which level and combined CRC -- member 0's to begin with
+    uint32_t left = 0;
+    const WindowPipeline::File::Bzip2* L = &members[0]->win.file.bz2;
+    bool in_stream = L->in_stream, at_file_end = L->chain.at_file_end;
+    uint32_t level = L->level, combined = L->combined;
+    uint64_t end_bit = L->chain.end_bit;
+    for (uint32_t k = 1; k < n; ++k) {
+        slimm_ctx* c = members[k];
+        const WindowPipeline::File::Bzip2& Z = c->win.file.bz2;
+        const WindowPipeline::File::Bzip2::Chain& K = Z.chain;
+        if (!K.any) continue;   // (no block or marker starts in this range)
+        *bad = k;
+        if (!in_stream || end_bit != K.first_bit)
+            return fail(c, SLIMM_E_SPLIT, "bzip2: the chain of member %u ends at bit %llu%s, this range's first block was found at bit %llu", left,
+                        static_cast<unsigned long long>(end_bit), in_stream ? "" : " (behind the last stream)",
+                        static_cast<unsigned long long>(K.first_bit));
+        if (K.first_max_n > level * 100000u)
+            return fail(c, SLIMM_E_INVALID, "bzip2-compressed input is not supported unless it decodes: block at byte %llu: %s",
+                        static_cast<unsigned long long>(K.first_max_at), bz2::status_text(bz2::kTooLong));
+        if (K.has_eos) {
+            if ((rotl(combined, K.first_blocks) ^ K.first_combined) != K.eos_crc)
+                return fail(c, SLIMM_E_INVALID, "bzip2-compressed input is not supported unless it decodes: end-of-stream marker at byte %llu: combined CRC mismatch",
+                            static_cast<unsigned long long>(K.eos_at));
+            level = Z.level;
+            combined = Z.combined;
+        } else {   // (no marker in this range: the stream goes on into the next)
+            combined = rotl(combined, K.first_blocks) ^ Z.combined;
+        }
+        in_stream = Z.in_stream;
+        at_file_end = K.at_file_end;
+        end_bit = K.end_bit;
+        left = k;
+    }
+    // the last chain ended the streams at the file's end (the file's last member checks that as one context does; a member
+    // in front of it has seen every byte behind its last marker)
+    *bad = left;
+    if (left + 1 < n && !(at_file_end && !in_stream))
+        return fail(members[left], SLIMM_E_SPLIT, "bzip2: the chain of member %u ends at bit %llu, and no range behind it holds a block", left,
+                    static_cast<unsigned long long>(end_bit));
+    return SLIMM_OK;
+}
+
 int split_range(slimm_ctx* c, SplitRange* out) {
     if (!c || !out) return SLIMM_E_INVALID;
-    if (c->device < 0 || !c->win.file.active || !c->win.file.closed || c->win.file.bz2.on)
-        return fail(c, SLIMM_E_INVALID, "a range of a split file: a range of BAM, SAM or BGZF SAM pushed to its end");
+    if (c->device < 0 || !c->win.file.active || !c->win.file.closed)
+        return fail(c, SLIMM_E_INVALID, "a range of a split file: a range of BAM, SAM, BGZF SAM or bzip2 SAM pushed to its end");
+    if (c->win.file.bz2.on && !c->win.announced.has_range)
+        return fail(c, SLIMM_E_INVALID, "a range of a bzip2 file: slimm_set_input_range tells where it lies");
     out->found_start = c->win.file.found_start || !c->win.announced.starts_mid;
     out->head_len = c->win.announced.starts_mid ? c->win.file.head_len : 0u;
     out->n_records = c->n_pushed;

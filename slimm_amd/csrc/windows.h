@@ -72,6 +72,10 @@ struct WindowPipeline {
         // a byte range of a file split over a group: it starts inside the file (its first record is guessed; the bytes in
         // front, the head, wait on the device for the member on the left) and / or ends inside it (the carry stays)
         bool starts_mid = false, ends_mid = false;
+        // ... and where the range lies in the file (slimm_set_input_range; bzip2 SAM: blocks belong to the range their
+        // magic's first bit lies in, and the stitch compares absolute bit positions)
+        bool has_range = false;
+        uint64_t range_begin = 0, range_end = 0;
     } announced;
 
     // ---- this file: reset as a whole, by end_file alone -- a new member needs its initialiser and nothing else
@@ -125,11 +129,31 @@ struct WindowPipeline {
                 uint32_t slot, crc;
                 uint64_t len, drop;   // text bytes; of them the first `drop` are skipped (the header)
                 uint64_t at;          // file offset of the block (errors)
+                bool unchecked = false;   // the first block of a range that starts inside the file: a CRC mismatch is SLIMM_E_SPLIT
             };
             std::vector<Ready> ready;
             size_t ready_pos = 0;
             uint64_t blocks = 0, batches = 0, false_magics = 0;   // (SLIMM_TRACE=push; false_magics: candidates the chain passed over)
             double ms_find = 0, ms_decode = 0, ms_bwt = 0, ms_emit = 0;
+            // a byte range of a split file (Announced::has_range).  A range that starts inside the file starts its chain
+            // at its first element -- the first block candidate that decodes, or an end-of-stream marker in front of it --
+            // inside a stream whose level it does not know: until its first end-of-stream marker it keeps the largest
+            // block and the combined CRC from 0 over its blocks (`combined`), which the stitch checks against the chain on
+            // its left (split.hip: split_bz2_chains).  A range that ends inside the file stops at the first element that
+            // starts at or behind its end.  Bit positions are the file's
+            struct Chain {
+                bool started = false;        // the chain has its first element (a range from the file's start: its stream header)
+                bool ended = false;          // ... and has stopped: at the range's end, or for want of an element of its own
+                bool any = false;            // it holds an element of its own
+                bool at_file_end = false;    // it stopped behind an end-of-stream marker with no byte left
+                uint64_t first_bit = 0, end_bit = 0;
+                bool first_stream = false;   // still in the stream the range started in
+                uint32_t first_blocks = 0, first_combined = 0, first_max_n = 0;
+                uint64_t first_max_at = 0;   // file offset of the largest block of that stream
+                bool has_eos = false;        // the range's first stream ended with a marker: its combined CRC, its file offset
+                uint32_t eos_crc = 0;
+                uint64_t eos_at = 0;
+            } chain;
         } bz2;
     } file;
 

@@ -356,6 +356,8 @@ int check_push(slimm_ctx* c, Push& p) {
     if (F.active && F.bz2.on != p.bzip2)
         return fail(c, SLIMM_E_INVALID, "bzip2 SAM bytes and the other forms do not mix within a file");
     if (p.bzip2 && p.skip && F.active) return fail(c, SLIMM_E_INVALID, "skip: only in front of a file's first records");
+    if (p.bzip2 && !F.active && (c->win.announced.starts_mid || c->win.announced.ends_mid) && !c->win.announced.has_range)
+        return fail(c, SLIMM_E_INVALID, "slimm_set_input_range first: a range of a bzip2 file is cut at bits, told by where it lies in the file");
     SLIMM_TRY(trim_bgzf_push(c, p));
     if (c->device < 0) return fail(c, SLIMM_E_INVALID, "host-only context has no record stream");
     if (p.n_bytes && !p.bytes) return fail(c, SLIMM_E_INVALID, "null byte buffer");
@@ -378,6 +380,7 @@ int open_file(slimm_ctx* c, const Push& p) {
     W.file.sam = p.sam;
     W.file.bz2.on = p.bzip2;
     W.file.bz2.skip_left = p.bzip2 ? p.skip : 0u;
+    if (p.bzip2 && W.announced.has_range) W.file.bz2.base = W.announced.range_begin;   // (errors name the file's bytes)
     c->marked = marked;
     c->has_check = !marked;
     c->packed = false;
@@ -397,7 +400,7 @@ int push_bzip2(slimm_ctx* c, const Push& p, uint64_t& total) {
     WindowPipeline& W = c->win;
     File& F = W.file;
     hipStream_t st = c->stream;
-    if (p.n_bytes) {
+    if (p.n_bytes && !F.bz2.chain.ended) {   // (ended: the range's chain has stopped, these are bytes of the slack)
         F.bz2.pend.insert(F.bz2.pend.end(), p.bytes, p.bytes + p.n_bytes);
         F.bz2.found = F.bz2.waiting = false;
     }
@@ -659,6 +662,15 @@ int slimm_set_input_mid_file(slimm_ctx* c, int starts_mid_file, int ends_mid_fil
     if (c->win.file.active) return fail(c, SLIMM_E_INVALID, "slimm_set_input_mid_file: before the range's first window");
     c->win.announced.starts_mid = starts_mid_file != 0;
     c->win.announced.ends_mid = ends_mid_file != 0;
+    return SLIMM_OK;
+}
+int slimm_set_input_range(slimm_ctx* c, uint64_t begin, uint64_t end) {
+    if (!c) return SLIMM_E_INVALID;
+    if (c->win.file.active) return fail(c, SLIMM_E_INVALID, "slimm_set_input_range: before the range's first window");
+    if (begin > end) return fail(c, SLIMM_E_INVALID, "slimm_set_input_range: a range ends at or behind its start");
+    c->win.announced.has_range = true;
+    c->win.announced.range_begin = begin;
+    c->win.announced.range_end = end;
     return SLIMM_OK;
 }
 int slimm_set_input_size_hint(slimm_ctx* c, uint64_t compressed_bytes) {

@@ -768,16 +768,19 @@ class SlimmGroup:
             e = min(n, s + step)
             self._check(self.L.slimm_group_push_records_marked(self.g, _p(w[s:e]), _p(rec.begin_pos[s:e]), e - s))
 
-    SPLIT_FORMS = ("bam", "sam", "bgzf_sam")
+    SPLIT_FORMS = ("bam", "sam", "bgzf_sam", "bzip2_sam")
 
-    def push_split(self, data, form: str, skip: int = 0, window: int = 0):
+    def push_split(self, data, form: str, skip: int = 0, window: int = 0, offsets=None):
         """One file split by byte range, every member its own (include/slimm_hip.h, "ONE FILE SPLIT BY BYTE RANGE"): GROUPED by
         read name, or -- a group made with grouped=False -- in any order, in which case the stitch deals the records by key.
         `data`: the whole file -- header included -- as bytes, or its path; `form`: "bam" (BGZF blocks of BAM records), "sam"
-        (plain text) or "bgzf_sam" (BGZF blocks of SAM text); `skip`: the header's bytes (for the BGZF forms its INFLATED
-        bytes).  The ranges come from slimm_host_text_ranges / slimm_host_bgzf_ranges; member by member: the reference
-        names (SAM), slimm_set_input_mid_file, the size hint, the range pushed in windows of `window` bytes (0: one); then
-        slimm_group_stitch_ranges.  Returns (the n + 1 offsets, the records every member decoded before the stitch)."""
+        (plain text), "bgzf_sam" (BGZF blocks of SAM text) or "bzip2_sam" (bzip2-compressed SAM text); `skip`: the header's
+        bytes (for the compressed forms its INFLATED / DECODED bytes).  The ranges come from slimm_host_text_ranges /
+        slimm_host_bgzf_ranges / slimm_host_bzip2_ranges; member by member: the reference names (SAM),
+        slimm_set_input_mid_file, the size hint, the range pushed in windows of `window` bytes (0: one); then
+        slimm_group_stitch_ranges.  A bzip2 member also announces its range's file offsets (slimm_set_input_range) and
+        pushes its range plus slimm_bzip2_split_slack() bytes behind it (at most to the file's end).  `offsets`: the n + 1
+        offsets to use instead of the planner's (bzip2 is cut at any byte behind the header's block).  Returns (the n + 1 offsets, the records every member decoded before the stitch)."""
         # (the planners, the announcements and the pushes are the same for both orders)
         import os
         import tempfile
@@ -785,8 +788,12 @@ class SlimmGroup:
         assert form in self.SPLIT_FORMS, form
         G = len(self.devices)
         offs = (C.c_uint64 * (G + 1))()
-        plan = self.L.slimm_host_text_ranges if form == "sam" else self.L.slimm_host_bgzf_ranges
-        if isinstance(data, (str, os.PathLike)):
+        plan = {"sam": self.L.slimm_host_text_ranges, "bzip2_sam": self.L.slimm_host_bzip2_ranges}.get(form, self.L.slimm_host_bgzf_ranges)
+        if offsets is not None:
+            assert len(offsets) == G + 1
+            offs[:] = list(offsets)
+            blob, rc = (open(os.fspath(data), "rb").read() if isinstance(data, (str, os.PathLike)) else bytes(data)), capi.OK
+        elif isinstance(data, (str, os.PathLike)):
             path = os.fspath(data)
             with open(path, "rb") as f:
                 blob = f.read()
@@ -807,7 +814,11 @@ class SlimmGroup:
             m._check(self.L.slimm_set_input_mid_file(m.ctx, 1 if i > 0 else 0, 1 if i + 1 < G else 0))
             m._check(self.L.slimm_set_input_size_hint(m.ctx, offs[i + 1] - offs[i]))
             part = blob[offs[i]:offs[i + 1]]
-            if form == "sam":
+            if form == "bzip2_sam":
+                m._check(self.L.slimm_set_input_range(m.ctx, offs[i], offs[i + 1]))
+                part = blob[offs[i]:offs[i + 1] + self.L.slimm_bzip2_split_slack()]
+                counts.append(m.push_bzip2_sam_bytes(part, skip=skip if i == 0 else 0, window=window))
+            elif form == "sam":
                 counts.append(m.push_sam_bytes(part, window=window))
             else:
                 counts.append(m.push_bgzf_blocks(part, skip=skip if i == 0 else 0, window=window, sam=form == "bgzf_sam"))
