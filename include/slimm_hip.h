@@ -249,7 +249,12 @@ int slimm_push_bgzf_blocks(slimm_ctx* ctx, const uint8_t* blocks, uint64_t n_byt
  * each file at its first decode (it grows, never shrinks, between files; slimm_reset releases it with the rest above 4 GiB);
  * plus the compressed bytes of a round (the pushes since the last one, at most 448 MB reserved from the hint) and 8 B per
  * block magic found.  Its text windows take the ring of window buffers above, one batch's text
- * each (< 1.9 GB): within today's total of <= 17 GB per file. */
+ * each (< 1.9 GB): within today's total of <= 17 GB per file.
+ * gzip SAM (slimm_push_gzip_sam_bytes) sizes nothing before the size pass has counted a round's text: the compressed bytes
+ * of a round (the pushes since the last one), 8 B per block candidate and 24 B per chunk start, then per round 2 B per byte
+ * of text (the symbols: at most 512 MB of text a round, or one chunk alone of up to 1 GiB), 32 KiB + 72 B per chunk of the
+ * chain and 8 B per 2 KiB of text.  A round of more text is split at a chunk boundary; a single deflate block of more than
+ * 1 GiB of text is refused.  slimm_window_memory counts all of it. */
 int slimm_set_input_size_hint(slimm_ctx* ctx, uint64_t compressed_bytes);
 int slimm_window_memory(slimm_ctx* ctx, uint64_t* device_bytes);
 /* hipMemGetInfo of the context's device: bytes in use (by every process and context on it) and the device's total. */
@@ -286,6 +291,26 @@ int slimm_push_bgzf_sam_blocks(slimm_ctx* ctx, const uint8_t* blocks, uint64_t n
  * or combined CRC mismatch, origPtr out of range, a block longer than its level allows, a randomised block (never
  * written since bzip2 0.9.5: refused), bytes after the last end-of-stream marker. */
 int slimm_push_bzip2_sam_bytes(slimm_ctx* ctx, const uint8_t* bytes, uint64_t n_bytes, uint32_t skip, int last, uint64_t* n_records);
+/* GZIP-COMPRESSED SAM TEXT (`gzip x.sam`: one member, or members back to back, empty ones among them; FEXTRA, FNAME,
+ * FCOMMENT and FHCRC in any member header) inflated on the device (slimm_amd/csrc/gzip_decode.hip).  The contract is that of
+ * slimm_push_bzip2_sam_bytes: `bytes` = the file's next n_bytes, from its first byte on and in order across calls, cut
+ * anywhere (inside a member header, a block, a trailer); of the inflated text the first `skip` bytes are the header (0 in
+ * every later call); slimm_set_reference_names first; the caller's buffer is free when the call returns; what cannot be
+ * decoded yet waits for the next push; the form does not mix with the others within a file.  Pushes are gathered on the
+ * host and decoded in rounds: the device finds the headers of non-final dynamic blocks at every bit offset (candidates, none
+ * of them trusted), decodes chunks of the stream from the chosen ones in parallel -- first for their sizes, then for their
+ * text, with markers where a copy reaches in front of the chunk --, keeps of each only what the chain from the member's first
+ * block confirms, resolves the markers from the chunk in front, and checks every member's CRC32 and ISIZE.  A BGZF file is a
+ * gzip file too; callers tell it apart beforehand and give it to slimm_push_bgzf_sam_blocks.  Errors: SLIMM_E_INVALID
+ * "truncated gzip stream" (also for a cut inside the trailer) and "corrupt gzip stream (<cause>)" -- a bad code, an
+ * over-subscribed or incomplete code set, a distance beyond the member's start, a stored block whose LEN and NLEN disagree,
+ * a CRC32 or ISIZE mismatch, bytes behind the last member that start no member -- in the words of the host reader. */
+int slimm_push_gzip_sam_bytes(slimm_ctx* ctx, const uint8_t* bytes, uint64_t n_bytes, uint32_t skip, int last, uint64_t* n_records);
+/* The counters of the gzip file read last (they outlive slimm_reset, and are zeroed by the next gzip file's first push):
+ * out[0] members, [1] chunks decoded on the chain, [2] candidates found, [3] candidates and chunk starts dropped by the chain,
+ * [4] stored, [5] fixed and [6] dynamic deflate blocks, [7] back-reference bytes resolved from the window of the chunk in
+ * front, [8] rounds, [9] bytes of text, [10] compressed bytes, [11] chunk starts added by SLIMM_FORCE gzip_false_starts. */
+int slimm_get_gzip_stats(slimm_ctx* ctx, uint64_t out[12]);
 /* Page-locks a buffer of the caller (hipHostRegister) until the context is destroyed: copies out of it then run at the
  * speed of the bus instead of the runtime's own staging. */
 int slimm_pin_host_buffer(slimm_ctx* ctx, const void* buffer, uint64_t n_bytes);

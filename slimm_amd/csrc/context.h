@@ -22,6 +22,7 @@
 #include "host_profile.hpp"
 #include "force.h"
 #include "bzip2_block.h"
+#include "deflate_stream.h"
 #include "kernels.h"
 #include "read_identity.h"
 

@@ -10,6 +10,9 @@
 //   off: slimm_group_stitch_ranges must refuse the join)                             tests/test_cli_split_input.py
 //   bzip2_false_magics[=N] (block candidates that are no blocks: inside every real one, and every N bits), bzip2_round=N
 //   (bzip2 SAM decoded every N compressed bytes: blocks cut across rounds)          tests/test_gpu_bzip2_sam.py
+//   gzip_chunk=N (gzip SAM: a chunk start every N compressed bytes), gzip_round=N (decoded every N compressed bytes: blocks,
+//   headers and trailers cut across rounds), gzip_false_starts[=N] (chunk starts that start no block: inside every real
+//   one, and every N bits)                    tests/test_gpu_gzip_sam.py, tests/test_cli_gzip_sam_device.py
 //   bzip2_split_wrong_first (a mid-file member of a split bzip2 file passes over its first block or marker:
 //   slimm_group_stitch_ranges must refuse the cut)                                   tests/test_gpu_split_bzip2_sam.py
 #pragma once

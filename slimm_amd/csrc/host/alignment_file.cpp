@@ -1079,8 +1079,8 @@ long AlignmentFile::read_blocks(uint8_t* dst, size_t cap, size_t max_inflated, s
 }
 
 long AlignmentFile::read_compressed(uint8_t* dst, size_t cap) {
-    if (comp_ != Compression::Bzip2 || !fp_ || !dst) {
-        err_ = "read_compressed: a bzip2 SAM file";
+    if ((comp_ != Compression::Bzip2 && comp_ != Compression::Gzip) || bam_ || !fp_ || !dst) {
+        err_ = "read_compressed: a bzip2 or gzip SAM file";
         return -1;
     }
     const int fd = fileno(fp_);
@@ -1099,7 +1099,8 @@ long AlignmentFile::read_compressed(uint8_t* dst, size_t cap) {
     while (out < want) {
         const ssize_t got = pread(fd, dst + out, want - out, static_cast<off_t>(bz_raw_pos_ + out));
         if (got <= 0) {
-            err_ = "truncated bzip2 stream (the file shrank while it was read)";
+            err_ = comp_ == Compression::Gzip ? "truncated gzip stream (the file shrank while it was read)"
+                                              : "truncated bzip2 stream (the file shrank while it was read)";
             return -1;
         }
         out += static_cast<size_t>(got);

@@ -5,7 +5,7 @@
 // qName, flag, refID, 0-based position and sequence length.  CIGAR, MAPQ, qualities and tags are never looked at by
 // SLIMM and are skipped.  BAM = BGZF (concatenated gzip members, inflated with libdeflate when the box has it, else zlib) carrying the binary records of the
 // SAM specification; SAM = the tab-separated text form, as it is, in BGZF blocks (bgzip) or in a plain gzip stream of one
-// or more members (gzip, inflated by zlib: a deflate stream cannot be cut for threads).  Written against the SAM/BAM specification -- SeqAn's source
+// or more members (gzip, inflated here by one zlib stream; the command hands a regular file's bytes to the device instead).  Written against the SAM/BAM specification -- SeqAn's source
 // is not part of the reference checkout -- and cross-checked in tests against files produced by an independent
 // Python writer (tests/bam_io.py).
 #pragma once
@@ -88,6 +88,8 @@ public:
     // BAM / BGZF SAM / bzip2 SAM: the header's inflated bytes -- where the first alignment record (line) starts in the
     // inflated (decoded) stream; plain SAM: the file offset of the first alignment line
     uint64_t header_bytes() const { return header_bytes_; }
+    // SAM text, compressed or not: where the first alignment line starts in the text (gzip SAM: the inflated bytes in front)
+    uint64_t text_header_bytes() const { return sam_body_off_; }
     // Q18 on a file grouped by QNAME (include/slimm_hip.h, "Q18 ON A GROUPED STREAM"): among the records read_batch /
     // read_into have handed out, some run of adjacent records with one canonical base holds SHORTENED names only -- their
     // flagged namesakes may lie anywhere in the file: the file must go through the any-order path
@@ -118,9 +120,9 @@ public:
     // SAM goes through read_raw / read_blocks.)
     long read_text(uint8_t* dst, size_t cap);
     bool can_read_text() const { return !bam_ && comp_ != Compression::Bgzf && fp_ != nullptr; }
-    // bzip2 SAM: the file's bytes as they lie in it, from its first byte on, window by window (for
-    // slimm_push_bzip2_sam_bytes: the device decodes the blocks; the header's header_bytes() decoded bytes are skipped
-    // there).  Read by pread, beside whatever read_text read.  Returns the bytes written, 0 at the end, -1 + error().
+    // bzip2 and gzip SAM: the file's bytes as they lie in it, from its first byte on, window by window (for
+    // slimm_push_bzip2_sam_bytes / slimm_push_gzip_sam_bytes: the device decodes them; the header's text_header_bytes()
+    // decoded bytes are skipped there).  Read by pread, beside whatever read_text read.  Returns the bytes written, 0 at the end, -1 + error().
     long read_compressed(uint8_t* dst, size_t cap);
     bool compressed_exhausted() const { return bz_raw_pos_ >= bz_raw_size_ && bz_raw_started_; }
     bool regular_file() const;   // (read_text and the mapped reads want one; a pipe or a device goes through the buffered reads)

@@ -121,6 +121,8 @@ SLIMM_FORWARD(int, slimm_push_bam_bytes, (slimm_ctx* a, const uint8_t* b, uint64
 SLIMM_FORWARD(int, slimm_push_bgzf_blocks, (slimm_ctx* a, const uint8_t* b, uint64_t c, uint32_t s, int d, uint64_t* e), (a, b, c, s, d, e))
 SLIMM_FORWARD(int, slimm_push_bgzf_sam_blocks, (slimm_ctx* a, const uint8_t* b, uint64_t c, uint32_t s, int d, uint64_t* e), (a, b, c, s, d, e))
 SLIMM_FORWARD(int, slimm_push_bzip2_sam_bytes, (slimm_ctx* a, const uint8_t* b, uint64_t c, uint32_t s, int d, uint64_t* e), (a, b, c, s, d, e))
+SLIMM_FORWARD(int, slimm_push_gzip_sam_bytes, (slimm_ctx* a, const uint8_t* b, uint64_t c, uint32_t s, int d, uint64_t* e), (a, b, c, s, d, e))
+SLIMM_FORWARD(int, slimm_get_gzip_stats, (slimm_ctx* a, uint64_t* b), (a, b))
 SLIMM_FORWARD(int, slimm_pin_host_buffer, (slimm_ctx* a, const void* b, uint64_t c), (a, b, c))
 SLIMM_FORWARD(int, slimm_host_bgzf_ranges, (const char* a, uint64_t b, uint32_t c, uint64_t* d), (a, b, c, d))
 SLIMM_FORWARD(int, slimm_host_text_ranges, (const char* a, uint64_t b, uint32_t c, uint64_t* d), (a, b, c, d))
@@ -634,7 +636,9 @@ struct RecordPump {
     // the inflater of the device-decode mode: fills the window buffers in turn.  BGZF files -- BAM, or SAM text -- alike:
     // windows the host inflates (read_raw) and, every device_period-th of those read in place, whole blocks (read_blocks)
     void run_raw() {
-        const bool bgzf = bam.compression() == Compression::Bgzf, bzip2 = bam.compression() == Compression::Bzip2;
+        const bool bgzf = bam.compression() == Compression::Bgzf;
+        // (bzip2 and gzip SAM: the file's bytes go to the device as they lie in the file)
+        const bool bzip2 = bam.compression() == Compression::Bzip2 || gzip_on_device();
         for (unsigned w = 0;; w = (w + 1) % kRawBuffers) {
             {
                 std::unique_lock<std::mutex> g(mu);
@@ -653,11 +657,11 @@ struct RecordPump {
             // (every device_period-th of the windows read in place)
             bool compressed = false;
             long n;
-            if (bzip2) {   // bzip2 SAM: the file's bytes as they lie in it (slimm_push_bzip2_sam_bytes decodes the blocks)
+            if (bzip2) {   // bzip2 / gzip SAM: the file's bytes as they lie in it (slimm_push_bzip2_sam_bytes / _gzip_sam_bytes decode them)
                 n = bam.read_compressed(raw_buf[w].get(), raw_cap());
                 compressed = true;
                 ++raw_windows_device;
-            } else if (bam.can_read_text()) {   // SAM, plain or gzip: the text (slimm_push_sam_bytes finds and decodes the lines)
+            } else if (bam.can_read_text()) {   // SAM, plain: the text (slimm_push_sam_bytes finds and decodes the lines)
                 n = bam.read_text(raw_buf[w].get(), raw_cap());
                 ++raw_windows_device;
             } else if (device_period && bam.can_read_blocks() && (raw_windows_device + raw_windows_host) % device_period == device_period - 1u) {
@@ -681,14 +685,18 @@ struct RecordPump {
             }
         }
     }
+    // gzip SAM is inflated on the device (a header of 4 GiB of text or more: by the host reader, the push's `skip` has 32 bits)
+    bool gzip_on_device() const { return !bam.is_bam() && bam.compression() == Compression::Gzip && bam.text_header_bytes() < (1ull << 32); }
     // ... and the thread that hands them to the device, from the moment the context exists
     void push_raw(slimm_ctx* c) {
         bool pinned[kRawBuffers] = {};
         bool closed = false;  // a window went out as the file's last
         bool in_flight = false;  // the window pushed last is still being copied out of its buffer
-        const bool text = !bam.is_bam(), bzip2 = bam.compression() == Compression::Bzip2;
-        // (bzip2 SAM goes from the file's first byte: the first push skips the header's decoded bytes)
-        uint32_t skip = bzip2 ? static_cast<uint32_t>(bam.header_bytes()) : 0u;
+        bool gzip_traced = false;
+        const bool text = !bam.is_bam(), gzip = gzip_on_device(), bzip2 = bam.compression() == Compression::Bzip2 || gzip;
+        // (bzip2 and gzip SAM go from the file's first byte: the first push skips the header's decoded bytes)
+        uint32_t skip = bzip2 ? static_cast<uint32_t>(bam.text_header_bytes()) : 0u;
+        const auto push_compressed = gzip ? slimm_push_gzip_sam_bytes : slimm_push_bzip2_sam_bytes;
         if (text) {   // SAM text names its references: the header's names for the device's look-up
             std::vector<const char*> names;
             for (const std::string& nm : bam.ref_names()) names.push_back(nm.c_str());
@@ -722,18 +730,25 @@ struct RecordPump {
                 const uint8_t* p = raw_buf[w.which].get();
                 const uint64_t n = static_cast<uint64_t>(w.n);
                 const int last = w.last ? 1 : 0;
-                rc = bzip2          ? slimm_push_bzip2_sam_bytes(c, p, n, skip, last, &got)
+                rc = bzip2          ? push_compressed(c, p, n, skip, last, &got)
                      : w.compressed ? (text ? slimm_push_bgzf_sam_blocks(c, p, n, 0u, last, &got) : slimm_push_bgzf_blocks(c, p, n, 0u, last, &got))
                                     : (text ? slimm_push_sam_bytes(c, p, n, last, &got) : slimm_push_bam_bytes(c, p, n, last, &got));
                 skip = 0;
                 closed = w.last;
             } else if (!closed) {
-                rc = bzip2  ? slimm_push_bzip2_sam_bytes(c, nullptr, 0, skip, 1, &got)
+                rc = bzip2  ? push_compressed(c, nullptr, 0, skip, 1, &got)
                      : text ? slimm_push_sam_bytes(c, nullptr, 0, 1, &got)
                             : slimm_push_bam_bytes(c, nullptr, 0, 1, &got);  // (the end came without notice: an incomplete record is an error)
             }
             raw_push_ms += ms(t1, std::chrono::steady_clock::now());
             raw_records += got;
+            if (gzip && g_trace && rc >= 0 && (closed || w.n == 0) && !gzip_traced) {
+                uint64_t st[12] = {};
+                gzip_traced = true;
+                if (slimm_get_gzip_stats(c, st) == SLIMM_OK)
+                    fprintf(stderr, "[trace] gzip SAM on the device: %llu members, %llu chunks (%llu candidates dropped), %llu bytes of text\n",
+                            (unsigned long long)st[0], (unsigned long long)st[1], (unsigned long long)st[3], (unsigned long long)st[9]);
+            }
             {
                 // (a window's buffer is the library's until the NEXT push returns: its copy runs beside the work on the
                 // window before it)

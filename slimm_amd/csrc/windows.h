@@ -65,6 +65,23 @@ struct WindowPipeline {
             return n;
         }
     } bz2;
+    // gzip SAM (gzip_decode.hip), the decode scratch: the compressed bytes not decoded yet, the block candidates and chunk
+    // starts, the size pass's results, the chain's chunks, the round's text as 16-bit symbols (a byte, or a marker for a
+    // byte of the chunk in front), the chunks' last 32 768 bytes (slot 0: those of the round before), the pieces' CRCs
+    struct Gzip {
+        DevBuf<uint8_t> comp, win;
+        DevBuf<unsigned long long> d_cand;
+        DevBuf<uint32_t> count, flag;
+        DevBuf<gz::Walk> walk;
+        DevBuf<gz::Chunk> chunks;
+        DevBuf<uint16_t> sym;
+        DevBuf<uint2> piece;
+        template <typename F>
+        void each_held(F&& f) { f(comp), f(win), f(d_cand), f(flag), f(walk), f(chunks), f(sym), f(piece); }
+    } gz;
+    // the counters of the gzip file read last (slimm_get_gzip_stats): they outlive the file's state
+    enum { kGzMembers, kGzChunks, kGzCandidates, kGzDropped, kGzStored, kGzFixed, kGzDynamic, kGzResolved, kGzRounds, kGzText, kGzCompressed, kGzForced, kGzStats };
+    uint64_t gz_stats[kGzStats] = {};
 
     // ---- announced before the file's first window (slimm_set_input_size_hint, slimm_set_input_mid_file), cleared when it ends
     struct Announced {
@@ -155,6 +172,23 @@ struct WindowPipeline {
                 uint64_t eos_at = 0;
             } chain;
         } bz2;
+        // gzip SAM, the host's side: the compressed bytes not decoded yet (file offset `base` on; `bit`: the next bit to
+        // read, an exact start), where in a member that is, the member's CRC register and length so far, the decoded bytes
+        // still to skip; the block candidates found in pend as it is; the chain's chunks of the round at hand
+        struct Gzip {
+            bool on = false;
+            std::vector<uint8_t> pend;
+            uint64_t base = 0, bit = 0;
+            enum Stage { Header, Deflate, Trailer } stage = Header;
+            uint32_t crc = 0xffffffffu;
+            uint64_t len = 0;
+            uint64_t skip_left = 0;
+            std::vector<uint64_t> cand;
+            bool found = false;      // cand holds the candidates of pend as it is (and the device has pend's bytes)
+            bool waiting = false;    // nothing to decode until pend grows
+            bool carried = false;    // slot 0 of the window scratch holds the last 32 768 bytes of the text so far
+            std::vector<gz::Chunk> ready;
+        } gz;
     } file;
 
     // the buffers that grow with a file's windows: what held_bytes() counts is what end_file gives back
@@ -164,6 +198,7 @@ struct WindowPipeline {
         for (auto& sc : inflate_scratch) f(sc);
         f(pieces), f(offs);
         bz2.each_held(f);
+        gz.each_held(f);
     }
     uint64_t held_bytes() {   // device memory of the window pipeline (slimm_window_memory)
         uint64_t n = 0;
@@ -194,6 +229,15 @@ int append_window(slimm_ctx* c, const uint8_t* src, int src_device, uint64_t n, 
 int bz2_decode_batch(slimm_ctx* c, bool last);
 uint64_t bz2_window_bytes(const slimm_ctx* c, uint64_t cap, size_t* n_blocks);
 int bz2_emit(slimm_ctx* c, uint8_t* dst, size_t n_blocks, uint8_t* last_byte);
-void bz2_trace_file(const slimm_ctx* c);   // SLIMM_TRACE=push (read at every call): the file's streams, blocks, false magics, times
+void bz2_trace_file(const slimm_ctx* c);
+// gzip_decode.hip (slimm_push_gzip_sam_bytes): the member headers and trailers at file.gz.bit read on the host; then one
+// round on the device -- candidates found, chunk starts chosen, the size pass, the chain from the exact start -- which
+// leaves the chain's chunks in file.gz.ready (none: the bytes wait for more, or the members have ended); at `last` what is
+// left must end the members.  Then gz_emit: the chunks decoded, resolved and written to dst behind each other (the
+// header's bytes dropped; *n_out bytes), their members' CRC registers and lengths stepped
+int gz_round(slimm_ctx* c, bool last);
+uint64_t gz_ready_bytes(const slimm_ctx* c);   // text bytes of file.gz.ready behind what is still to skip
+int gz_emit(slimm_ctx* c, uint8_t* dst, uint64_t* n_out, uint8_t* last_byte);
+void gz_trace_file(const slimm_ctx* c);   // SLIMM_TRACE=push (read at every call): the file's streams, blocks, false magics, times
 
 }  // namespace slimm
