@@ -254,7 +254,12 @@ int slimm_push_bgzf_blocks(slimm_ctx* ctx, const uint8_t* blocks, uint64_t n_byt
  * of a round (the pushes since the last one), 8 B per block candidate and 24 B per chunk start, then per round 2 B per byte
  * of text (the symbols: at most 512 MB of text a round, or one chunk alone of up to 1 GiB), 32 KiB + 72 B per chunk of the
  * chain and 8 B per 2 KiB of text.  A round of more text is split at a chunk boundary; a single deflate block of more than
- * 1 GiB of text is refused.  slimm_window_memory counts all of it. */
+ * 1 GiB of text is refused.  slimm_window_memory counts all of it.
+ * zstd SAM (slimm_push_zstd_sam_bytes) sizes everything from the block headers and, for the text, from the decoded
+ * sequences: the compressed bytes of a round, 120 B per block, the Huffman-coded literals' bytes, 12 B per sequence, and per
+ * byte of a round's text (at most 512 MB by the blocks' bounds) 1 B + 4 B for the position it copies from, plus twice the
+ * frame's window (at most 128 MiB) of history; a frame that states a checksum also takes a page-locked host copy of the
+ * round's text, which is host memory (slimm_window_memory does not count it) and is released by slimm_reset. */
 int slimm_set_input_size_hint(slimm_ctx* ctx, uint64_t compressed_bytes);
 int slimm_window_memory(slimm_ctx* ctx, uint64_t* device_bytes);
 /* hipMemGetInfo of the context's device: bytes in use (by every process and context on it) and the device's total. */
@@ -311,6 +316,32 @@ int slimm_push_gzip_sam_bytes(slimm_ctx* ctx, const uint8_t* bytes, uint64_t n_b
  * [4] stored, [5] fixed and [6] dynamic deflate blocks, [7] back-reference bytes resolved from the window of the chunk in
  * front, [8] rounds, [9] bytes of text, [10] compressed bytes, [11] chunk starts added by SLIMM_FORCE gzip_false_starts. */
 int slimm_get_gzip_stats(slimm_ctx* ctx, uint64_t out[12]);
+/* ZSTD-COMPRESSED SAM TEXT (`zstd x.sam`; pzstd / cat: frames back to back; skippable frames among them are passed over)
+ * decoded on the device (slimm_amd/csrc/zstd_decode.hip; the format: zstd_frame.h).  The contract is that of
+ * slimm_push_gzip_sam_bytes: `bytes` = the file's next n_bytes, from its first byte on and in order across calls, cut
+ * anywhere (inside a frame header, a block header, a block, the checksum); of the decoded text the first `skip` bytes are the
+ * header (0 in every later call); slimm_set_reference_names first; the caller's buffer is free when the call returns; what
+ * cannot be decoded yet waits for the next push; the form does not mix with the others within a file, and it is refused
+ * behind slimm_set_input_mid_file ("a zstd stream is not cut by byte range").  Pushes are gathered on the host and decoded
+ * in rounds (32 MiB of compressed bytes, at most 512 MB of text by the blocks' bounds): the host walks the frame and block
+ * headers, the device decodes every compressed block's literals and sequences at once (a wave per block), builds the
+ * round's text in parallel over its bytes -- a match byte gets the position it copies from, in the round or in the
+ * frame's last window of text kept from the round before; pointer doubling resolves the chains -- and the host checks the
+ * content size and the content checksum (XXH64) of a frame that states them.  Limits: a window of more than 128 MiB is
+ * refused (as `zstd -d` does without --long), so is a dictionary id other than 0.  Errors: SLIMM_E_INVALID "zstd-compressed
+ * input is not supported unless it decodes: <where>: <cause>" in the words of the host reader -- truncation (also inside
+ * the checksum), a reserved bit or block type, bad Huffman weights, a bad FSE table description, a bitstream that does not
+ * end on its padding bit, a block larger than its maximum, a literals or sequence total that disagrees with the block, an
+ * offset beyond the frame's start or window, a content size or checksum mismatch, bytes behind the last frame that start
+ * no frame. */
+int slimm_push_zstd_sam_bytes(slimm_ctx* ctx, const uint8_t* bytes, uint64_t n_bytes, uint32_t skip, int last, uint64_t* n_records);
+/* The counters of the zstd file read last (they outlive slimm_reset, and are zeroed by the next zstd file's first push):
+ * out[0] frames, [1] skippable frames, [2] raw, [3] RLE and [4] compressed blocks, literals sections [5] Huffman-coded with
+ * a tree, [6] treeless, [7] raw or RLE, sequence tables [8] predefined, [9] of one symbol (RLE), [10] FSE-described,
+ * [11] repeated, [12] sequences, [13] match bytes copied from in front of their own block, of which [14] from the history
+ * of an earlier round, [15] rounds, [16] bytes of text, [17] compressed bytes, [18] content checksums checked, [19] the most
+ * pointer-doubling passes a round took (at most ceil(log2(its text + history)) + 1). */
+int slimm_get_zstd_stats(slimm_ctx* ctx, uint64_t out[20]);
 /* Page-locks a buffer of the caller (hipHostRegister) until the context is destroyed: copies out of it then run at the
  * speed of the bus instead of the runtime's own staging. */
 int slimm_pin_host_buffer(slimm_ctx* ctx, const void* buffer, uint64_t n_bytes);

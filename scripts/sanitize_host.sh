@@ -7,15 +7,16 @@ ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 W="${1:-/tmp/slimm_sanitize}"
 mkdir -p "$W"
 FLAGS="-std=c++17 -g -O1 -fsanitize=address,undefined -fno-omit-frame-pointer"
-g++ $FLAGS "$ROOT/tests/native/san_readers.cpp" "$ROOT/slimm_amd/csrc/host/alignment_file.cpp" \
-    "$ROOT/slimm_amd/csrc/host/sldb.cpp" -lz -lpthread -ldl -o "$W/san_readers"
+g++ $FLAGS "$ROOT/tests/native/san_readers.cpp" "$ROOT/slimm_amd/csrc/host/alignment_file.cpp" "$ROOT/slimm_amd/csrc/host/bzip2.cpp" \
+    "$ROOT/slimm_amd/csrc/host/zstd.cpp" "$ROOT/slimm_amd/csrc/host/sldb.cpp" -lz -lpthread -ldl -o "$W/san_readers"
+g++ $FLAGS "$ROOT/tests/native/san_zstd.cpp" "$ROOT/slimm_amd/csrc/host/zstd.cpp" -o "$W/san_zstd"
 g++ $FLAGS "$ROOT/tests/native/host_profile_bench.cpp" "$ROOT/slimm_amd/csrc/host_profile.cpp" -o "$W/san_profile"
 g++ $FLAGS "$ROOT/slimm_amd/csrc/host/slimm_build_main.cpp" "$ROOT/slimm_amd/csrc/host/sldb.cpp" -lz -o "$W/san_build"
 # ThreadSanitizer over the parallel BGZF inflate / record decode
 g++ -std=c++17 -g -O1 -fsanitize=thread "$ROOT/tests/native/san_readers.cpp" "$ROOT/slimm_amd/csrc/host/alignment_file.cpp" \
-    "$ROOT/slimm_amd/csrc/host/sldb.cpp" -lz -lpthread -ldl -o "$W/tsan_readers"
+    "$ROOT/slimm_amd/csrc/host/bzip2.cpp" "$ROOT/slimm_amd/csrc/host/zstd.cpp" "$ROOT/slimm_amd/csrc/host/sldb.cpp" -lz -lpthread -ldl -o "$W/tsan_readers"
 g++ -std=c++17 -g -O1 -fsanitize=thread -I"$ROOT/include" "$ROOT/slimm_amd/csrc/host/slimm_main.cpp" "$ROOT/slimm_amd/csrc/host/alignment_file.cpp" \
-    "$ROOT/slimm_amd/csrc/host/sldb.cpp" -lz -lpthread -ldl -o "$W/tsan_slimm"
+    "$ROOT/slimm_amd/csrc/host/bzip2.cpp" "$ROOT/slimm_amd/csrc/host/zstd.cpp" "$ROOT/slimm_amd/csrc/host/sldb.cpp" -lz -lpthread -ldl -o "$W/tsan_slimm"
 cd "$ROOT"
 python - "$W" <<'PY'
 import os, subprocess, sys
@@ -58,6 +59,25 @@ r = subprocess.run([f"{d}/tsan_readers", f"{d}/c3.bam", f"{d}/c4.bam", f"{d}/c2.
 print(r.stdout)
 if r.returncode or r.stderr.strip():
     bad += 1; print("THREAD SANITIZER OUTPUT:\n" + r.stderr)
+# the host zstd decoder: the committed inputs, written frames, and their truncated and bit-flipped copies
+import random
+from tests import sam_zst as Z
+rng = random.Random(3)
+zfiles = []
+blobs = [Z.golden(n) for n in sorted(os.listdir(Z.GOLDEN)) if n.endswith(".zst")]
+blobs += list(Z.written_copies(open(f"{d}/c2.sam", "rb").read()).values())
+for k, blob in enumerate(blobs):
+    copies = [blob] + [blob[:rng.randrange(1, len(blob))] for _ in range(20)]
+    for _ in range(60):
+        at = rng.randrange(len(blob))
+        copies.append(blob[:at] + bytes([blob[at] ^ (1 << rng.randrange(8))]) + blob[at + 1:])
+    for j, data in enumerate(copies):
+        open(f"{d}/z{k}_{j}.zst", "wb").write(data)
+        zfiles.append(f"{d}/z{k}_{j}.zst")
+r = subprocess.run([f"{d}/san_zstd"] + zfiles, capture_output=True, text=True)
+print(f"san_zstd: {len(zfiles)} files,", sum(1 for l in r.stdout.splitlines() if "\tok\t" in l), "decoded")
+if r.returncode or r.stderr.strip():
+    bad += 1; print("SANITIZER OUTPUT (san_zstd):\n" + r.stderr[-4000:])
 r = subprocess.run([f"{d}/san_profile"], capture_output=True, text=True)
 print(r.stdout)
 if r.returncode or r.stderr.strip():

@@ -23,6 +23,7 @@
 #include "force.h"
 #include "bzip2_block.h"
 #include "deflate_stream.h"
+#include "zstd_frame.h"
 #include "kernels.h"
 #include "read_identity.h"
 
@@ -77,8 +78,11 @@ template <typename T>
 struct PinBuf {
     T* p = nullptr;
     size_t cap = 0;
-    ~PinBuf() {
+    ~PinBuf() { release(); }
+    void release() {
         if (p) (void)hipHostFree(p);
+        p = nullptr;
+        cap = 0;
     }
     hipError_t ensure(size_t n) {
         if (n <= cap) return hipSuccess;

@@ -13,6 +13,9 @@
 //   gzip_chunk=N (gzip SAM: a chunk start every N compressed bytes), gzip_round=N (decoded every N compressed bytes: blocks,
 //   headers and trailers cut across rounds), gzip_false_starts[=N] (chunk starts that start no block: inside every real
 //   one, and every N bits)                    tests/test_gpu_gzip_sam.py, tests/test_cli_gzip_sam_device.py
+//   zstd_round=N (zstd SAM decoded every N compressed bytes: frame headers, block headers, blocks and checksums cut across
+//   rounds), zstd_round_text=N (a round's text at most, by the blocks' bounds: copies reach into the history of an earlier
+//   round)                                    tests/test_gpu_zstd_sam.py, tests/test_cli_zstd_sam_device.py
 //   bzip2_split_wrong_first (a mid-file member of a split bzip2 file passes over its first block or marker:
 //   slimm_group_stitch_ranges must refuse the cut)                                   tests/test_gpu_split_bzip2_sam.py
 #pragma once

@@ -123,6 +123,8 @@ SLIMM_FORWARD(int, slimm_push_bgzf_sam_blocks, (slimm_ctx* a, const uint8_t* b, 
 SLIMM_FORWARD(int, slimm_push_bzip2_sam_bytes, (slimm_ctx* a, const uint8_t* b, uint64_t c, uint32_t s, int d, uint64_t* e), (a, b, c, s, d, e))
 SLIMM_FORWARD(int, slimm_push_gzip_sam_bytes, (slimm_ctx* a, const uint8_t* b, uint64_t c, uint32_t s, int d, uint64_t* e), (a, b, c, s, d, e))
 SLIMM_FORWARD(int, slimm_get_gzip_stats, (slimm_ctx* a, uint64_t* b), (a, b))
+SLIMM_FORWARD(int, slimm_push_zstd_sam_bytes, (slimm_ctx* a, const uint8_t* b, uint64_t c, uint32_t s, int d, uint64_t* e), (a, b, c, s, d, e))
+SLIMM_FORWARD(int, slimm_get_zstd_stats, (slimm_ctx* a, uint64_t* b), (a, b))
 SLIMM_FORWARD(int, slimm_pin_host_buffer, (slimm_ctx* a, const void* b, uint64_t c), (a, b, c))
 SLIMM_FORWARD(int, slimm_host_bgzf_ranges, (const char* a, uint64_t b, uint32_t c, uint64_t* d), (a, b, c, d))
 SLIMM_FORWARD(int, slimm_host_text_ranges, (const char* a, uint64_t b, uint32_t c, uint64_t* d), (a, b, c, d))
@@ -387,7 +389,7 @@ int dump_raw(const Options& o) {
     const size_t cap = static_cast<size_t>(std::max(1u, o.window_mb)) << 20;
     std::vector<uint8_t> buf(cap);
     long n;
-    const bool text = f.compression() == Compression::Gzip || f.compression() == Compression::Bzip2;
+    const bool text = f.compression() == Compression::Gzip || f.compression() == Compression::Bzip2 || f.compression() == Compression::Zstd;
     while ((n = text ? f.read_text(buf.data(), cap) : f.read_raw(buf.data(), cap)) > 0) {
         std::cerr << "window\t" << n << "\t" << (f.raw_exhausted() ? "last" : "more") << "\n";
         if (fwrite(buf.data(), 1, static_cast<size_t>(n), stdout) != static_cast<size_t>(n)) return 1;
@@ -637,8 +639,8 @@ struct RecordPump {
     // windows the host inflates (read_raw) and, every device_period-th of those read in place, whole blocks (read_blocks)
     void run_raw() {
         const bool bgzf = bam.compression() == Compression::Bgzf;
-        // (bzip2 and gzip SAM: the file's bytes go to the device as they lie in the file)
-        const bool bzip2 = bam.compression() == Compression::Bzip2 || gzip_on_device();
+        // (bzip2, gzip and zstd SAM: the file's bytes go to the device as they lie in the file)
+        const bool bzip2 = bam.compression() == Compression::Bzip2 || gzip_on_device() || zstd_on_device();
         for (unsigned w = 0;; w = (w + 1) % kRawBuffers) {
             {
                 std::unique_lock<std::mutex> g(mu);
@@ -687,16 +689,17 @@ struct RecordPump {
     }
     // gzip SAM is inflated on the device (a header of 4 GiB of text or more: by the host reader, the push's `skip` has 32 bits)
     bool gzip_on_device() const { return !bam.is_bam() && bam.compression() == Compression::Gzip && bam.text_header_bytes() < (1ull << 32); }
+    bool zstd_on_device() const { return !bam.is_bam() && bam.compression() == Compression::Zstd && bam.text_header_bytes() < (1ull << 32); }   // (zstd SAM: the same)
     // ... and the thread that hands them to the device, from the moment the context exists
     void push_raw(slimm_ctx* c) {
         bool pinned[kRawBuffers] = {};
         bool closed = false;  // a window went out as the file's last
         bool in_flight = false;  // the window pushed last is still being copied out of its buffer
         bool gzip_traced = false;
-        const bool text = !bam.is_bam(), gzip = gzip_on_device(), bzip2 = bam.compression() == Compression::Bzip2 || gzip;
+        const bool text = !bam.is_bam(), gzip = gzip_on_device(), zstd = zstd_on_device(), bzip2 = bam.compression() == Compression::Bzip2 || gzip || zstd;
         // (bzip2 and gzip SAM go from the file's first byte: the first push skips the header's decoded bytes)
         uint32_t skip = bzip2 ? static_cast<uint32_t>(bam.text_header_bytes()) : 0u;
-        const auto push_compressed = gzip ? slimm_push_gzip_sam_bytes : slimm_push_bzip2_sam_bytes;
+        const auto push_compressed = zstd ? slimm_push_zstd_sam_bytes : gzip ? slimm_push_gzip_sam_bytes : slimm_push_bzip2_sam_bytes;
         if (text) {   // SAM text names its references: the header's names for the device's look-up
             std::vector<const char*> names;
             for (const std::string& nm : bam.ref_names()) names.push_back(nm.c_str());
@@ -742,6 +745,13 @@ struct RecordPump {
             }
             raw_push_ms += ms(t1, std::chrono::steady_clock::now());
             raw_records += got;
+            if (zstd && g_trace && rc >= 0 && (closed || w.n == 0) && !gzip_traced) {
+                uint64_t st[20] = {};
+                gzip_traced = true;
+                if (slimm_get_zstd_stats(c, st) == SLIMM_OK)
+                    fprintf(stderr, "[trace] zstd SAM on the device: %llu frames, %llu blocks, %llu bytes of text\n", (unsigned long long)st[0],
+                            (unsigned long long)(st[2] + st[3] + st[4]), (unsigned long long)st[16]);
+            }
             if (gzip && g_trace && rc >= 0 && (closed || w.n == 0) && !gzip_traced) {
                 uint64_t st[12] = {};
                 gzip_traced = true;
@@ -1262,6 +1272,8 @@ std::unique_ptr<Reading> set_up(Session& S, const std::string& path, bool any_or
                      !options.host_decode && !options.verify_grouping && !options.packed_records;
     if (g_trace && !any_order && options.split_input && options.devices.size() > 1 && !bam.is_bam() && bam.compression() == Compression::Gzip)
         fprintf(stderr, "[trace] --split-input: a gzip stream is not cut by byte range; member 0 reads %s\n", path.c_str());
+    if (g_trace && !any_order && options.split_input && options.devices.size() > 1 && !bam.is_bam() && bam.compression() == Compression::Zstd)
+        fprintf(stderr, "[trace] --split-input: a zstd stream is not cut by byte range; member 0 reads %s\n", path.c_str());
     if (!F->split_input)
         F->pump.reset(new RecordPump(bam, F->check_words, true, options));
 

@@ -1,0 +1,48 @@
+// zstd on the host: one serial decoder for the SAM header of a zstd-compressed SAM file, for `--host-decode`,
+// `--verify-grouping`, `--packed-records`, pipes and `--dump-records` / `--dump-raw` (the reader thread), and for the CPU
+// tests.  The format is ../zstd_frame.h, the device decoder's own source; frames back to back (pzstd, cat) are read one
+// after the other, skippable frames passed over.  No libzstd: the command does not depend on it.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <functional>
+#include <string>
+#include <vector>
+
+#include "../zstd_frame.h"
+
+namespace slimm {
+
+class ZstdReader {
+public:
+    // `source(dst, cap)`: the next compressed bytes of the file, in order (0 at its end)
+    explicit ZstdReader(std::function<size_t(uint8_t*, size_t)> source);
+    // the next decoded bytes, at most `cap`; 0 at the end of the last frame, -1 + error()
+    long read(uint8_t* dst, size_t cap);
+    // "block at byte N: <cause>", "frame at byte N: <cause>", ... (without the reader's "zstd-compressed input ..." in front)
+    const std::string& error() const { return err_; }
+    // one compressed block's content -> its text behind `text` (whose bytes from frame_lo on are the frame's so far):
+    // the serial use of zstd_frame.h, also what the tests compare the device decoder's stages with
+    static uint32_t decode_compressed(const uint8_t* content, uint32_t size, uint32_t block_max, uint64_t window, zs::Entropy& e, uint32_t rep[3],
+                                      std::vector<uint8_t>& text, size_t frame_lo);
+
+private:
+    bool next_block();   // decode the next block into out_ (false: the end, or err_)
+    bool need(size_t n); // at least n bytes at pos_ (false: the file has no more)
+    bool fail(const std::string& where, uint32_t status);
+    std::function<size_t(uint8_t*, size_t)> source_;
+    std::vector<uint8_t> in_;   // compressed bytes from file offset in_base_ on; the next to read: pos_
+    uint64_t in_base_ = 0;
+    size_t pos_ = 0;
+    bool in_eof_ = false, in_frame_ = false, done_ = false, bad_ = false;
+    uint64_t frames_ = 0, frame_at_ = 0, frame_len_ = 0;
+    zs::FrameHeader fh_{};
+    zs::Entropy entropy_;
+    uint32_t rep_[3] = {1, 4, 8};
+    zs::Xxh64 xxh_;
+    std::vector<uint8_t> text_;   // the frame's text: at least its last `window` bytes
+    size_t served_ = 0;           // ... of which [served_, size) have not been handed out
+    std::string err_;
+};
+
+}  // namespace slimm

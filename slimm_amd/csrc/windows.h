@@ -83,6 +83,24 @@ struct WindowPipeline {
     enum { kGzMembers, kGzChunks, kGzCandidates, kGzDropped, kGzStored, kGzFixed, kGzDynamic, kGzResolved, kGzRounds, kGzText, kGzCompressed, kGzForced, kGzStats };
     uint64_t gz_stats[kGzStats] = {};
 
+    // zstd SAM (zstd_decode.hip), the decode scratch: the compressed bytes of a round and what its blocks repeat of the
+    // blocks in front, the blocks' descriptors, the decoded literals and sequences, the round's text behind its history
+    // (the frame's last window of text), the position each text byte copies from, the history kept for the next round
+    struct Zstd {
+        DevBuf<uint8_t> comp, lit, text, hist;
+        DevBuf<zs::Block> blocks;
+        DevBuf<zs::Seq> seq;
+        DevBuf<uint32_t> src;
+        PinBuf<uint8_t> h_text;             // the round's text on the host, for the content checksums (released by end_file)
+        DevBuf<unsigned long long> count;   // [0] passes' "changed", [1] bad offsets, [2] first block with one, [3], [4]: stats 13, 14
+        template <typename F>
+        void each_held(F&& f) { f(comp), f(lit), f(text), f(hist), f(blocks), f(seq), f(src); }
+    } zst;
+    // the counters of the zstd file read last (slimm_get_zstd_stats): they outlive the file's state
+    enum { kZsFrames, kZsSkippable, kZsRaw, kZsRle, kZsCompressed, kZsHufTree, kZsTreeless, kZsLitPlain, kZsPredefined, kZsRleTable, kZsFseTable,
+           kZsRepeated, kZsSequences, kZsFromFront, kZsFromHistory, kZsRounds, kZsText, kZsCompressedBytes, kZsChecksums, kZsPasses, kZsStats };
+    uint64_t zs_stats[kZsStats] = {};
+
     // ---- announced before the file's first window (slimm_set_input_size_hint, slimm_set_input_mid_file), cleared when it ends
     struct Announced {
         uint64_t size_hint = 0;   // the file's compressed bytes (0 = not told): what its gathered windows are sized for
@@ -189,6 +207,40 @@ struct WindowPipeline {
             bool carried = false;    // slot 0 of the window scratch holds the last 32 768 bytes of the text so far
             std::vector<gz::Chunk> ready;
         } gz;
+        // zstd SAM, the host's side: the compressed bytes not decoded yet (file offset `base` on; `pos`: the next byte to
+        // read), where in a frame that is and what the frame's blocks hand on (the descriptions a block may repeat, the
+        // repeat offsets, the text's length and XXH64 so far), the decoded bytes still to skip, the bytes of history the
+        // device holds; the blocks and frames of the round at hand
+        struct Zstd {
+            bool on = false;
+            std::vector<uint8_t> pend;
+            uint64_t base = 0, pos = 0;
+            enum Stage { Between, Blocks, Checksum } stage = Between;
+            zs::FrameHeader fh{};
+            uint64_t frame_at = 0, frame_len = 0;
+            zs::Entropy entropy;
+            uint32_t rep[3] = {1, 4, 8};
+            zs::Xxh64 xxh{};
+            uint64_t any_frames = 0;
+            uint64_t skip_left = 0;
+            uint64_t hist_len = 0;
+            bool waiting = false;
+            struct Frame {   // a frame with blocks in the round
+                uint32_t first = 0, n = 0;   // its blocks of the round
+                bool ends = false, has_sum = false;
+                uint32_t sum = 0;
+                zs::FrameHeader fh{};
+                uint64_t at = 0, len_before = 0, text_at = 0, text_len = 0;
+                uint32_t rep[3] = {1, 4, 8};   // the repeat offsets and the XXH64 state in front of its blocks of the round
+                zs::Xxh64 xxh{};
+            };
+            std::vector<zs::Block> ready;
+            std::vector<uint64_t> ready_at;   // the blocks' file offsets (errors)
+            std::vector<Frame> frames;
+            std::vector<uint8_t> aux;
+            uint64_t text = 0;                // the round's text bytes (behind zs_round)
+            uint64_t round_hist = 0;
+        } zst;
     } file;
 
     // the buffers that grow with a file's windows: what held_bytes() counts is what end_file gives back
@@ -199,6 +251,7 @@ struct WindowPipeline {
         f(pieces), f(offs);
         bz2.each_held(f);
         gz.each_held(f);
+        zst.each_held(f);
     }
     uint64_t held_bytes() {   // device memory of the window pipeline (slimm_window_memory)
         uint64_t n = 0;
@@ -239,5 +292,16 @@ int gz_round(slimm_ctx* c, bool last);
 uint64_t gz_ready_bytes(const slimm_ctx* c);   // text bytes of file.gz.ready behind what is still to skip
 int gz_emit(slimm_ctx* c, uint8_t* dst, uint64_t* n_out, uint8_t* last_byte);
 void gz_trace_file(const slimm_ctx* c);   // SLIMM_TRACE=push (read at every call): the file's streams, blocks, false magics, times
+
+// zstd_decode.hip (slimm_push_zstd_sam_bytes): zs_round plans the whole blocks of file.zst.pend (frame and block headers
+// walked on the host), decodes their literals and sequences on the device and leaves the round's blocks, with their text
+// lengths, in file.zst.ready (none: the bytes wait for more, or the frames have ended); at `last` what is left must end the
+// frames.  Then zs_emit: the text built behind the history, resolved, and written to dst (the header's bytes dropped;
+// *n_out bytes); zs_check, behind the window's launch: the content checksums of the frames that ended
+int zs_round(slimm_ctx* c, bool last);
+uint64_t zs_ready_bytes(const slimm_ctx* c);
+int zs_emit(slimm_ctx* c, uint8_t* dst, uint64_t* n_out, uint8_t* last_byte);
+int zs_check(slimm_ctx* c);
+void zs_trace_file(const slimm_ctx* c);
 
 }  // namespace slimm

@@ -1,10 +1,10 @@
 // The window pipeline (include/slimm_hip.h: slimm_push_bam_bytes, _bgzf_blocks, _sam_bytes, _bgzf_sam_blocks, _bzip2_sam_bytes,
-// _gzip_sam_bytes): a file's bytes -- inflated BAM records, whole BGZF blocks of them, SAM text, BGZF blocks of SAM text, bzip2
-// or gzip SAM text -- cross the bus in windows; the device inflates (bgzf_tokens.hip, bgzf_inflate.hip, gzip_decode.hip) or
-// decodes (bzip2_decode.hip) them, finds the
+// _gzip_sam_bytes, _zstd_sam_bytes): a file's bytes -- inflated BAM records, whole BGZF blocks of them, SAM text, BGZF blocks of SAM
+// text, bzip2, gzip or zstd SAM text -- cross the bus in windows; the device inflates (bgzf_tokens.hip, bgzf_inflate.hip,
+// gzip_decode.hip) or decodes (bzip2_decode.hip, zstd_decode.hip) them, finds the
 // records (bam_decode.hip, sam_decode.hip) and appends them to the context's record stream.  Its state: windows.h.
 // Replaces seqan::BamFileIn + readRecord of the reference (src/misc.hpp:498-522, src/slimm.hpp:194-208).
-// A push's steps (push_window): check_push, open_file; one of four sources fills window buffers -- push_bzip2, push_gzip, gather_blocks
+// A push's steps (push_window): check_push, open_file; one of five sources fills window buffers -- push_bzip2, push_gzip, push_zstd, gather_blocks
 // (+ launch_gathered), push_plain --, each window handed over by submit_window; finish_windows; release_callers_buffer.
 // A window is copied when it is pushed and WORKED ON when the next one is pushed (or at once, when it is the last): its
 // host-to-device copy then runs beside the kernels and the host's bookkeeping of the window before it -- the copies are
@@ -56,6 +56,9 @@ int WindowPipeline::end_file(slimm_ctx* c) {
         (void)hipSetDevice(c->device);
         each_held([](auto& b) { b.release(); });
     }
+    // (zstd: the page-locked copy of a round's text, for the content checksums, goes with every file: it is no device
+    // memory, slimm_window_memory does not count it, and a file without checksums never needs it)
+    zst.h_text.release();
     return SLIMM_OK;
 }
 
@@ -301,11 +304,12 @@ int add_last_newline(slimm_ctx* c, uint64_t at, hipStream_t st) {   // at: bytes
 }
 
 // ---- a push
-enum { kFormatBam = 0, kFormatBgzf = 1, kFormatSam = 2, kFormatBgzfSam = 3, kFormatBzip2Sam = 4, kFormatGzipSam = 5 };
+enum { kFormatBam = 0, kFormatBgzf = 1, kFormatSam = 2, kFormatBgzfSam = 3, kFormatBzip2Sam = 4, kFormatGzipSam = 5, kFormatZstdSam = 6 };
 // bzip2 SAM: compressed bytes gathered on the host before their blocks are looked for and decoded (a round; the command's
 // pushes are larger, the ABI's may be of any size)
 constexpr uint64_t kBzip2Round = 32ull << 20;
 constexpr uint64_t kGzipRound = 32ull << 20;   // (gzip SAM: the same; SLIMM_FORCE gzip_round=N)
+constexpr uint64_t kZstdRound = 32ull << 20;   // (zstd SAM: the same; SLIMM_FORCE zstd_round=N)
 
 struct Push {
     const uint8_t* bytes;
@@ -317,6 +321,7 @@ struct Push {
     uint64_t inflated = 0;
     bool copy_started = false;     // this push started a copy from the caller's buffer
     bool gzip = false;             // gzip SAM: the file's bytes, inflated here
+    bool zstd = false;             // zstd SAM: the file's bytes, decoded here
 };
 
 // BGZF blocks: their descriptors; the blocks in front of the file's first record dropped, `skip` what is left of them
@@ -362,7 +367,11 @@ int check_push(slimm_ctx* c, Push& p) {
         return fail(c, SLIMM_E_INVALID, "gzip SAM bytes and the other forms do not mix within a file");
     if (p.gzip && (c->win.announced.starts_mid || c->win.announced.ends_mid))
         return fail(c, SLIMM_E_INVALID, "a gzip stream is not cut by byte range");
-    if ((p.bzip2 || p.gzip) && p.skip && F.active) return fail(c, SLIMM_E_INVALID, "skip: only in front of a file's first records");
+    if (F.active && F.zst.on != p.zstd)
+        return fail(c, SLIMM_E_INVALID, "zstd SAM bytes and the other forms do not mix within a file");
+    if (p.zstd && (c->win.announced.starts_mid || c->win.announced.ends_mid))
+        return fail(c, SLIMM_E_INVALID, "a zstd stream is not cut by byte range");
+    if ((p.bzip2 || p.gzip || p.zstd) && p.skip && F.active) return fail(c, SLIMM_E_INVALID, "skip: only in front of a file's first records");
     if (p.bzip2 && !F.active && (c->win.announced.starts_mid || c->win.announced.ends_mid) && !c->win.announced.has_range)
         return fail(c, SLIMM_E_INVALID, "slimm_set_input_range first: a range of a bzip2 file is cut at bits, told by where it lies in the file");
     SLIMM_TRY(trim_bgzf_push(c, p));
@@ -390,6 +399,9 @@ int open_file(slimm_ctx* c, const Push& p) {
     W.file.gz.on = p.gzip;
     W.file.gz.skip_left = p.gzip ? p.skip : 0u;
     if (p.gzip) std::fill(W.gz_stats, W.gz_stats + WindowPipeline::kGzStats, 0ull);
+    W.file.zst.on = p.zstd;
+    W.file.zst.skip_left = p.zstd ? p.skip : 0u;
+    if (p.zstd) std::fill(W.zs_stats, W.zs_stats + WindowPipeline::kZsStats, 0ull);
     if (p.bzip2 && W.announced.has_range) W.file.bz2.base = W.announced.range_begin;   // (errors name the file's bytes)
     c->marked = marked;
     c->has_check = !marked;
@@ -486,6 +498,52 @@ int push_gzip(slimm_ctx* c, const Push& p, uint64_t& total) {
         SLIMM_TRY(submit_window(c, 1, st, false));
     }
     if (p.last) gz_trace_file(c);
+    return SLIMM_OK;
+}
+
+// zstd: as gzip -- the bytes wait on the host until a round's worth has come (or the file ends); then round by round
+// (zstd_decode.hip) the whole blocks among them are decoded, and each round's text becomes a window of its own
+int push_zstd(slimm_ctx* c, const Push& p, uint64_t& total) {
+    WindowPipeline& W = c->win;
+    File& F = W.file;
+    File::Zstd& Z = F.zst;
+    hipStream_t st = c->stream;
+    if (p.n_bytes) {   // (what the rounds so far have read goes)
+        Z.pend.erase(Z.pend.begin(), Z.pend.begin() + static_cast<long>(Z.pos));
+        Z.base += Z.pos;
+        Z.pos = 0;
+        Z.pend.insert(Z.pend.end(), p.bytes, p.bytes + p.n_bytes);
+        Z.waiting = false;
+        W.zs_stats[WindowPipeline::kZsCompressedBytes] += p.n_bytes;
+    }
+    long round = 0;   // (SLIMM_FORCE zstd_round=N: rounds of N bytes -- tests cut headers, blocks and checksums across rounds)
+    if (!forced("zstd_round", &round) || round <= 0) round = static_cast<long>(kZstdRound);
+    const bool decode_now = p.last || Z.pend.size() - Z.pos >= static_cast<uint64_t>(round);
+    while (decode_now) {
+        const uint64_t at0 = Z.base + Z.pos;   // (the file offset read so far: zs_round drops from pend what it has read)
+        const auto stage0 = Z.stage;
+        SLIMM_TRY(zs_round(c, p.last));
+        if (!Z.ready.empty()) {
+            SLIMM_TRY(window_buffer(c, zs_ready_bytes(c) + 1u));
+            uint64_t n = 0;
+            uint8_t lb = '\n';
+            SLIMM_TRY(zs_emit(c, W.bytes[next_buffer(F)].p + kBamSlack, &n, &lb));
+            if (n) {
+                F.sam_last_byte = lb;
+                SLIMM_TRY(submit_window(c, n, st, false));
+                push_trace("window %llu: %.1f MB of text from zstd", (unsigned long long)(F.windows - 1), n / 1e6);
+            }
+            SLIMM_TRY(zs_check(c));   // (on the host, beside the window's decode)
+            if (n) SLIMM_TRY(finish_windows(c, Upto::Lag, false, false, total));
+        }
+        if (Z.waiting || (Z.base + Z.pos == at0 && Z.stage == stage0)) break;
+    }
+    if (lacks_last_newline(c, p.last)) {   // (in a window of its own)
+        SLIMM_TRY(window_buffer(c, 1u));
+        SLIMM_TRY(add_last_newline(c, 0, st));
+        SLIMM_TRY(submit_window(c, 1, st, false));
+    }
+    if (p.last) zs_trace_file(c);
     return SLIMM_OK;
 }
 
@@ -659,9 +717,11 @@ int release_callers_buffer(slimm_ctx* c, const Push& p) {
 int push_window(slimm_ctx* c, const uint8_t* bytes, uint64_t src_bytes, int format, uint32_t skip, int last, uint64_t* n_records) {
     if (!c) return SLIMM_E_INVALID;
     if (n_records) *n_records = 0;
-    const bool sam = format == kFormatSam || format == kFormatBgzfSam || format == kFormatBzip2Sam || format == kFormatGzipSam;
+    const bool sam = format == kFormatSam || format == kFormatBgzfSam || format == kFormatBzip2Sam || format == kFormatGzipSam ||
+                     format == kFormatZstdSam;
     Push p{bytes, src_bytes, src_bytes, skip, last != 0, sam, format == kFormatBzip2Sam, format == kFormatBgzf || format == kFormatBgzfSam};
     p.gzip = format == kFormatGzipSam;
+    p.zstd = format == kFormatZstdSam;
     SLIMM_TRY(check_push(c, p));
     (void)hipSetDevice(c->device);
     HIP_TRY(c, need_stream(c->copy_stream, kStreamHigh));
@@ -674,6 +734,8 @@ int push_window(slimm_ctx* c, const uint8_t* bytes, uint64_t src_bytes, int form
         SLIMM_TRY(push_bzip2(c, p, total));
     else if (p.gzip)
         SLIMM_TRY(push_gzip(c, p, total));
+    else if (p.zstd)
+        SLIMM_TRY(push_zstd(c, p, total));
     else if (p.n_bytes && p.compressed)
         SLIMM_TRY(gather_blocks(c, p, total));
     else if (p.n_bytes || (p.sam && p.last && !W.announced.ends_mid && (F.sam_last_byte != '\n' || F.sam_dev_tail)))
@@ -771,6 +833,15 @@ int slimm_push_bzip2_sam_bytes(slimm_ctx* c, const uint8_t* bytes, uint64_t n_by
 }
 int slimm_push_gzip_sam_bytes(slimm_ctx* c, const uint8_t* bytes, uint64_t n_bytes, uint32_t skip, int last, uint64_t* n_records) {
     return push_window(c, bytes, n_bytes, kFormatGzipSam, skip, last, n_records);
+}
+int slimm_push_zstd_sam_bytes(slimm_ctx* c, const uint8_t* bytes, uint64_t n_bytes, uint32_t skip, int last, uint64_t* n_records) {
+    return push_window(c, bytes, n_bytes, kFormatZstdSam, skip, last, n_records);
+}
+int slimm_get_zstd_stats(slimm_ctx* c, uint64_t out[20]) {
+    if (!c || !out) return SLIMM_E_INVALID;
+    static_assert(WindowPipeline::kZsStats == 20, "slimm_get_zstd_stats: twenty counters");
+    std::copy(c->win.zs_stats, c->win.zs_stats + WindowPipeline::kZsStats, out);
+    return SLIMM_OK;
 }
 int slimm_get_gzip_stats(slimm_ctx* c, uint64_t out[12]) {
     if (!c || !out) return SLIMM_E_INVALID;

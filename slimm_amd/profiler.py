@@ -343,6 +343,36 @@ class Slimm:
         self._check(self.L.slimm_get_gzip_stats(self.ctx, out))
         return dict(zip(self.GZIP_STATS, [int(v) for v in out]))
 
+    def push_zstd_sam_bytes(self, blob, skip: int = 0, window: int = 0, cuts=None, empty_last: bool = False) -> int:
+        """slimm_push_zstd_sam_bytes: a zstd-compressed SAM file's bytes from its first byte on, of whose decoded text the
+        first `skip` bytes are the header (set_reference_names first); the arguments are those of push_bzip2_sam_bytes.  The
+        host walks the frames and blocks, the device decodes the blocks, builds the text, finds the lines and decodes them.
+        Returns the number of records."""
+        buf = np.frombuffer(blob, dtype=np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob, dtype=np.uint8)
+        n = buf.shape[0]
+        if cuts is None:
+            step = window or max(n, 1)
+            cuts = list(range(step, n, step))
+        bounds = [0] + sorted(c for c in set(cuts) if 0 < c < n) + [n]
+        pieces = [(a, b) for a, b in zip(bounds, bounds[1:]) if b > a] + ([(n, n)] if empty_last or n == 0 else [])
+        total, got = 0, C.c_uint64()
+        for k, (a, b) in enumerate(pieces):
+            piece = np.ascontiguousarray(buf[a:b])
+            self._check(self.L.slimm_push_zstd_sam_bytes(self.ctx, _p(piece) if piece.size else None, b - a, skip if k == 0 else 0,
+                                                         1 if k == len(pieces) - 1 else 0, C.byref(got)))
+            total += got.value
+        return total
+
+    ZSTD_STATS = ("frames", "skippable", "raw_blocks", "rle_blocks", "compressed_blocks", "huffman_trees", "treeless", "plain_literals",
+                  "predefined", "rle_tables", "fse_tables", "repeated", "sequences", "front_bytes", "history_bytes", "rounds",
+                  "text_bytes", "compressed_bytes", "checksums", "passes")
+
+    def zstd_stats(self) -> dict:
+        """slimm_get_zstd_stats: the counters of the zstd file read last."""
+        out = (C.c_uint64 * 20)()
+        self._check(self.L.slimm_get_zstd_stats(self.ctx, out))
+        return dict(zip(self.ZSTD_STATS, [int(v) for v in out]))
+
     def push_bgzf_blocks(self, blob, skip: int = 0, window: int = 0, host_every: int = 0, sam: bool = False) -> int:
         """slimm_push_bgzf_blocks: whole BGZF blocks of a BAM file (compressed), the first of which holds the first alignment
         record `skip` inflated bytes in; windows of about `window` compressed bytes (0: one), cut at block boundaries.  The
