@@ -565,10 +565,43 @@ constexpr uint32_t kFcRing = 128;                  // (a power of two; at most 6
 constexpr uint32_t kFcReads = kSlotRecs + 8;       // reads of a slot: its records' runs START in it; the last run may add two
 constexpr uint32_t kFcBatch = 4;                   // chunks of 64 targets per trip of a wave
 
+// Everything k_filter_compact is given, as ONE kernel argument: it starts at byte 0 of the kernel's argument segment, and
+// what only the rare paths need -- the pair set and the counters (quirk Q4, the redo list), taxon_flat -- is read from
+// there WHERE IT IS USED (kernarg_now) instead of living in scalar registers through the hot loops: with launch bounds of
+// 8 waves per SIMD the kernel has 78 of them, and with every argument held from the kernel's start it spilled 29 into the
+// lanes of a vector register, reloaded per batch, per chunk and per window.  (With the argument segment's address pinned
+// in the rare blocks the compiler also reads the window path's fields -- rows, marks, taxon_base -- where the windows are.)
 template <typename Rows>
-__device__ __forceinline__ void compact_window(const Rows& rows, const FilterOut& out, uint32_t lane, uint32_t X, uint64_t Hc,
+struct FilterKernArgs {
+    const uint32_t* tgt_ref;
+    const uint32_t* tgt_gbin;
+    const uint4* slots;
+    const uint32_t* valid_bits;
+    uint32_t* redo;
+    uint32_t nslots;
+    Rows rows;
+    FilterOut out;
+};
+template <typename T, typename Args>
+__device__ __forceinline__ T kernarg_now(const Args& args, size_t offset) {
+    T v;
+#if defined(__HIP_DEVICE_COMPILE__)
+    const __attribute__((address_space(4))) char* p =
+        (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));   // (the read stays here: an empty statement the compiler cannot move)
+    __builtin_memcpy(&v, p + offset, sizeof(T));
+#else
+    memcpy(&v, reinterpret_cast<const char*>(&args) + offset, sizeof(T));
+#endif
+    return v;
+}
+
+template <typename Rows>
+__device__ __forceinline__ void compact_window(const FilterKernArgs<Rows>& ka, uint32_t lane, uint32_t X, uint64_t Hc,
                                                uint32_t cref, uint32_t cg, uint32_t cr, const typename Rows::Row& row,
                                                uint32_t* __restrict__ s_sel) {
+    const Rows& rows = ka.rows;
+    const FilterOut& out = ka.out;
     const uint64_t PR = k_below(X);
     const uint64_t H = Hc & PR;                                    // (bit 0 is set)
     const uint64_t stops = (H >> 1) | (1ull << (X - 1u));          // the last entry of every read
@@ -601,7 +634,9 @@ __device__ __forceinline__ void compact_window(const Rows& rows, const FilterOut
         if (k_bit(OW & ~Q4)) s_sel[cr] = out.taxon_base + rows.taxon_index(lv & 7u, Rows::field(row, lv & 7u));
         const uint32_t lv_read = __builtin_amdgcn_ds_bpermute(fvl << 2, lv);
         if (k_bit(PR & ~single) && lv_read < 8u) out.marks[cref * kMarkBytes + lv_read] = 1;  // plain, idempotent byte store
-        if (Q4) {
+        if (__builtin_expect(Q4 != 0ull, 0)) {
+            const Rows rows_q = kernarg_now<Rows>(ka, offsetof(FilterKernArgs<Rows>, rows));
+            const FilterOut out_q = kernarg_now<FilterOut>(ka, offsetof(FilterKernArgs<Rows>, out));
             uint32_t f[8];
             Rows::fields(row, f);
             uint64_t todo = Q4;
@@ -614,65 +649,103 @@ __device__ __forceinline__ void compact_window(const Rows& rows, const FilterOut
                 ReadAcc acc;
                 read_clear(acc);
                 read_max(acc, Vs, cref, f[7]);
-                const uint32_t index = rows.taxon_index(7u, acc.max_f7);
-                const uint32_t taxon = rows.taxon_at(index);
-                read_children(out, k_bit(Vs), cref, 8u, taxon);
+                const uint32_t index = rows_q.taxon_index(7u, acc.max_f7);
+                const uint32_t taxon = rows_q.taxon_at(index);
+                read_children(out_q, k_bit(Vs), cref, 8u, taxon);
                 const uint32_t rl = static_cast<uint32_t>(__builtin_amdgcn_readlane(cr, o));
-                if (lane == 0u) s_sel[rl] = out.taxon_base + index;
+                if (lane == 0u) s_sel[rl] = out_q.taxon_base + index;
             }
         }
     }
 }
 
 template <typename Rows>
-__global__ __launch_bounds__(64, 8) void k_filter_compact(const uint32_t* __restrict__ tgt_ref, const uint32_t* __restrict__ tgt_gbin,
-                                                          const uint4* __restrict__ slots, uint32_t nslots,
-                                                          const uint32_t* __restrict__ valid_bits, uint32_t* __restrict__ redo,
-                                                          const Rows rows, const FilterOut out) {
+__global__ __launch_bounds__(64, 8) void k_filter_compact(const FilterKernArgs<Rows> ka) {
+    const uint32_t* __restrict__ const tgt_ref = ka.tgt_ref;
+    const uint32_t* __restrict__ const tgt_gbin = ka.tgt_gbin;
+    const uint32_t* __restrict__ const valid_bits = ka.valid_bits;
     __shared__ uint32_t s_ref[kFcRing], s_g[kFcRing], s_r[kFcRing];
-    __shared__ uint32_t s_sel[kFcReads];
+    __shared__ __attribute__((aligned(16))) uint32_t s_sel[kFcReads];
+    static_assert(kFcReads % 4u == 0u, "the selectors are prefilled four at a time");
     const uint32_t lane = lane_id();
-    for (uint32_t r = lane; r < kFcReads; r += 64u) s_sel[r] = 0xffffffffu;
+    const uint32_t slot = blockIdx.x;   // one workgroup, one slot (launch_filter)
+    if (slot >= ka.nslots) return;
+    const uint4 d = ka.slots[slot];
+    const uint32_t rb = ka.out.rbase[slot] + ka.out.bbase[slot >> 10];
+    const uint32_t t0 = d.x, tend = d.x + d.y;
+    bool whole_reads_walk = d.z > kFcReads;   // (cannot happen with kSlotRecs records per slot; the walk takes anything)
+    // "nothing" for the slot's reads (rounded up to the 16 bytes of a store), not for the most a slot may hold
+    if (!whole_reads_walk)
+        for (uint32_t r = 4u * lane; r < d.z; r += 256u) *reinterpret_cast<uint4*>(&s_sel[r]) = make_uint4(~0u, ~0u, ~0u, ~0u);
     __builtin_amdgcn_wave_barrier();
-    for (uint32_t slot = blockIdx.x; slot < nslots; slot += gridDim.x) {
-        const uint4 d = slots[slot];
-        const uint32_t rb = out.rbase[slot] + out.bbase[slot >> 10];
-        const uint32_t t0 = d.x, tend = d.x + d.y;
-        bool whole_reads_walk = d.z > kFcReads;   // (cannot happen with kSlotRecs records per slot; the walk takes anything)
-        uint32_t rcount = 0, ccount = 0, cdone = 0;
-        // kFcBatch chunks of 64 targets per trip: their words were asked for a trip ahead, their bitmap words are asked for
-        // together -- one dependent round trip per 256 targets (with one chunk per trip the kernel waited for that gather:
-        // 2.15 ms at 1 B records, 12 % under the window-by-window kernel)
-        uint32_t wn[kFcBatch], gn[kFcBatch];
-        auto ask = [&](uint32_t t) {
+    uint32_t rcount = 0, ccount = 0, cdone = 0;
+    // kFcBatch chunks of 64 targets per trip: their words were asked for a trip ahead, their bitmap words are asked for
+    // together -- one dependent round trip per 256 targets (with one chunk per trip the kernel waited for that gather:
+    // 2.15 ms at 1 B records, 12 % under the window-by-window kernel)
+    uint32_t wn[kFcBatch], gn[kFcBatch];
+    auto ask = [&](uint32_t t) {
+        if (t + 64u * kFcBatch <= tend) {   // a full batch: one base per array, the chunks at constant offsets
+            const uint32_t *pr = tgt_ref + t, *pg = tgt_gbin + t;
+#pragma unroll
+            for (uint32_t u = 0; u < kFcBatch; ++u) {
+                wn[u] = pr[lane + 64u * u];
+                gn[u] = pg[lane + 64u * u];
+            }
+            __builtin_amdgcn_sched_barrier(0);   // (keeps the two forms apart: merged, the loads' addresses would be per-lane selects)
+        } else {
 #pragma unroll
             for (uint32_t u = 0; u < kFcBatch; ++u) {
                 const uint32_t i = min(t + 64u * u + lane, tend - 1u);   // (lanes behind the slot's end: its last target, not used)
                 wn[u] = tgt_ref[i];
                 gn[u] = tgt_gbin[i];
             }
-        };
-        if (!whole_reads_walk && t0 < tend) ask(t0);
-        for (uint32_t t = t0; t < tend && !whole_reads_walk; t += 64u * kFcBatch) {
-            uint32_t w[kFcBatch], g[kFcBatch], bits[kFcBatch];
+        }
+    };
+    if (!whole_reads_walk && t0 < tend) ask(t0);
+    for (uint32_t t = t0; t < tend && !whole_reads_walk; t += 64u * kFcBatch) {
+        uint32_t w[kFcBatch], g[kFcBatch], bits[kFcBatch];
 #pragma unroll
-            for (uint32_t u = 0; u < kFcBatch; ++u) {
-                w[u] = wn[u];
-                g[u] = gn[u];
-            }
-            __builtin_amdgcn_sched_barrier(0);
+        for (uint32_t u = 0; u < kFcBatch; ++u) {
+            w[u] = wn[u];
+            g[u] = gn[u];
+        }
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (uint32_t u = 0; u < kFcBatch; ++u) bits[u] = valid_bits[(w[u] & 0x7fffffffu) >> 5];
-            __builtin_amdgcn_sched_barrier(0);
-            if (t + 64u * kFcBatch < tend) ask(t + 64u * kFcBatch);
-            __builtin_amdgcn_sched_barrier(0);
-            // (one chunk after the other through ONE copy of the code below: the chunk's words picked out of the batch's
-            // registers by a few selects -- unrolled, the window code would stand in the kernel kFcBatch times)
+        for (uint32_t u = 0; u < kFcBatch; ++u) bits[u] = valid_bits[(w[u] & 0x7fffffffu) >> 5];
+        __builtin_amdgcn_sched_barrier(0);
+        if (t + 64u * kFcBatch < tend) ask(t + 64u * kFcBatch);
+        __builtin_amdgcn_sched_barrier(0);
+        // Only a slot's last batch can be partial: a full one needs no "is this lane's target the slot's" and appends each
+        // chunk straight from its own registers (one copy of the cheap append per chunk position); the partial one picks the
+        // chunk's words out of the batch's registers by a few selects.  The drain below -- the window code -- stands in the
+        // kernel ONCE, behind all of them: unrolled with the chunks it would stand there kFcBatch times.
+        const bool full = t + 64u * kFcBatch <= tend;
+        const uint32_t nchunks = full ? kFcBatch : (tend - t + 63u) >> 6;
 #pragma unroll 1
-            for (uint32_t u = 0; u < kFcBatch; ++u) {
-                const uint32_t tu = t + 64u * u;
-                if (tu >= tend) break;
-                uint32_t wu = w[0], gu = g[0], bu = bits[0];
+        for (uint32_t u = 0; u < nchunks; ++u) {
+            const uint32_t tu = t + 64u * u;
+            uint32_t wu, gu;
+            uint64_t H, VB;
+            // (the word is pinned where the chunk is picked: what depends only on the batch's registers is otherwise computed
+            // for all of the batch's chunks in front of this loop, and the selects come back)
+            auto pick = [&](uint32_t wk, uint32_t gk, uint32_t bk) {
+                SLIMM_PIN_VGPR(wk);
+                wu = wk;
+                gu = gk;
+                H = k_ballot((wk >> 31) != 0u);
+                VB = k_ballot(((bk >> (wk & 31u)) & 1u) != 0u);
+            };
+            if (full) {
+                if (u < 2u) {
+                    if (u == 0u) pick(w[0], g[0], bits[0]);
+                    else pick(w[1], g[1], bits[1]);
+                } else {
+                    if (u == 2u) pick(w[2], g[2], bits[2]);
+                    else pick(w[3], g[3], bits[3]);
+                }
+            } else {
+                uint32_t bu = bits[0];
+                wu = w[0], gu = g[0];
 #pragma unroll
                 for (uint32_t k = 1; k < kFcBatch; ++k) {
                     wu = u == k ? w[k] : wu;
@@ -680,53 +753,52 @@ __global__ __launch_bounds__(64, 8) void k_filter_compact(const uint32_t* __rest
                     bu = u == k ? bits[k] : bu;
                 }
                 const bool live = tu + lane < tend;
-                const uint32_t ref = wu & 0x7fffffffu;
-                const bool valid = live && ((bu >> (ref & 31u)) & 1u) != 0u;
-                const bool head = live && (wu >> 31) != 0u;
-                const uint64_t H = k_ballot(head), VB = k_ballot(valid);
-                if (valid) {
-                    const uint32_t p = (ccount + mask_rank(VB)) & (kFcRing - 1u);
-                    s_ref[p] = ref;
-                    s_g[p] = gu;
-                    s_r[p] = rcount + mask_rank(H) + (head ? 1u : 0u) - 1u;
-                }
-                rcount += static_cast<uint32_t>(__popcll(H));
-                ccount += static_cast<uint32_t>(__popcll(VB));
-                const bool last = tu + 64u >= tend;
-                while (ccount - cdone >= 64u || (last && ccount != cdone)) {
-                    __builtin_amdgcn_wave_barrier();   // (the ring's words: written above, read here)
-                    const uint32_t n_live = min(64u, ccount - cdone);
-                    const uint32_t e = (cdone + lane) & (kFcRing - 1u);
-                    const uint32_t cref = lane < n_live ? s_ref[e] : 0u;
-                    const uint32_t cg = s_g[e], cr = lane < n_live ? s_r[e] : 0xffffffffu;
-                    typename Rows::Row row = rows.load(cref);
-                    const uint32_t before = __builtin_amdgcn_update_dpp(0xffffffffu, cr, 0x138, 0xf, 0xf, false);   // wave_shr:1 (lane 0: none)
-                    const uint64_t Hc = k_ballot(lane < n_live && (lane == 0u || cr != before));
-                    // whole reads only: the last read of a full window may go on in the entries to come
-                    const bool final_window = last && ccount - cdone <= 64u;
-                    const uint32_t X = final_window ? n_live : 63u - static_cast<uint32_t>(__builtin_clzll(Hc));
-                    __builtin_amdgcn_wave_barrier();   // (every lane has read its entry before the ring is written again)
-                    if (X == 0u) {   // 64 valid targets of one read (or more): the slot goes through the walk that takes any length
-                        whole_reads_walk = true;
-                        break;
-                    }
-                    compact_window(rows, out, lane, X, Hc, cref, cg, cr, row, s_sel);
-                    cdone += X;
-                }
-                if (whole_reads_walk) break;
+                H = k_ballot(live && (wu >> 31) != 0u);
+                VB = k_ballot(live && ((bu >> (wu & 31u)) & 1u) != 0u);
             }
-        }
-        __builtin_amdgcn_wave_barrier();
-        if (whole_reads_walk) {   // (rare: left to k_filter_walk, a kernel of its own -- inlined, its registers would be this kernel's)
-            if (lane == 0u) redo[atomicAdd(&out.counters[CNT_REDO], 1u)] = slot;
-            for (uint32_t r = lane; r < kFcReads; r += 64u) s_sel[r] = 0xffffffffu;
-        } else {
-            for (uint32_t r = lane; r < d.z; r += 64u) {   // the slot's selectors, reads without a valid target included
-                out.sel[rb + r] = s_sel[r];
-                s_sel[r] = 0xffffffffu;
+            // every valid target gets its place in the ring and the number of its read among the slot's
+            if (k_bit(VB)) {
+                const uint32_t p = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(VB >> 32),
+                                                             __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(VB), ccount)) & (kFcRing - 1u);
+                s_ref[p] = wu & 0x7fffffffu;
+                s_g[p] = gu;
+                // (the read's number: the heads up to and including this lane, less one)
+                s_r[p] = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(H >> 32),
+                                                   __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(H), rcount - 1u)) + (k_bit(H) ? 1u : 0u);
             }
+            rcount += static_cast<uint32_t>(__popcll(H));
+            ccount += static_cast<uint32_t>(__popcll(VB));
+            const bool last = tu + 64u >= tend;
+            while (ccount - cdone >= 64u || (last && ccount != cdone)) {
+                __builtin_amdgcn_wave_barrier();   // (the ring's words: written above, read here)
+                const uint32_t n_live = min(64u, ccount - cdone);
+                const uint32_t e = (cdone + lane) & (kFcRing - 1u);
+                const uint32_t cref = lane < n_live ? s_ref[e] : 0u;
+                const uint32_t cg = s_g[e], cr = lane < n_live ? s_r[e] : 0xffffffffu;
+                typename Rows::Row row = ka.rows.load(cref);
+                const uint32_t before = __builtin_amdgcn_update_dpp(0xffffffffu, cr, 0x138, 0xf, 0xf, false);   // wave_shr:1 (lane 0: none)
+                const uint64_t Hc = k_ballot(lane < n_live && (lane == 0u || cr != before));
+                // whole reads only: the last read of a full window may go on in the entries to come
+                const bool final_window = last && ccount - cdone <= 64u;
+                const uint32_t X = final_window ? n_live : 63u - static_cast<uint32_t>(__builtin_clzll(Hc));
+                __builtin_amdgcn_wave_barrier();   // (every lane has read its entry before the ring is written again)
+                if (__builtin_expect(X == 0u, 0)) {   // 64 valid targets of one read (or more): the slot goes through the walk that takes any length
+                    whole_reads_walk = true;
+                    break;
+                }
+                compact_window(ka, lane, X, Hc, cref, cg, cr, row, s_sel);
+                cdone += X;
+            }
+            if (__builtin_expect(whole_reads_walk, 0)) break;
         }
-        __builtin_amdgcn_wave_barrier();
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (__builtin_expect(whole_reads_walk, 0)) {   // (rare: left to k_filter_walk, a kernel of its own -- inlined, its registers would be this kernel's)
+        uint32_t* const redo = kernarg_now<uint32_t*>(ka, offsetof(FilterKernArgs<Rows>, redo));
+        uint32_t* const counters = kernarg_now<uint32_t*>(ka, offsetof(FilterKernArgs<Rows>, out.counters));
+        if (lane == 0u) redo[atomicAdd(&counters[CNT_REDO], 1u)] = slot;
+    } else {
+        for (uint32_t r = lane; r < d.z; r += 64u) ka.out.sel[rb + r] = s_sel[r];   // the slot's selectors, reads without a valid target included
     }
 }
 
@@ -961,15 +1033,15 @@ void launch_filter(hipStream_t st, const FilterArgs& a, hipEvent_t t0, hipEvent_
         r.rows = reinterpret_cast<const uint4*>(a.rows16);
         r.taxon_flat = a.taxon_flat;
         r.shift = a.taxon_shift;
-        hipExtLaunchKernelGGL(k_filter_compact<Rows16>, dim3(grid), dim3(64), 0, st, t0, t1, 0, a.tgt_ref, a.tgt_gbin, a.slots, a.nslots,
-                              a.valid_bits, a.redo, r, out);
+        const FilterKernArgs<Rows16> ka{a.tgt_ref, a.tgt_gbin, a.slots, a.valid_bits, a.redo, a.nslots, r, out};
+        hipExtLaunchKernelGGL(k_filter_compact<Rows16>, dim3(grid), dim3(64), 0, st, t0, t1, 0, ka);
         hipLaunchKernelGGL(k_filter_walk<Rows16>, dim3(std::min(a.nslots, 256u)), dim3(64), 0, st, a.tgt_ref, a.tgt_gbin, a.slots, a.redo, r, out);
     } else {
         Rows32 r;
         r.lin4 = reinterpret_cast<const uint4*>(a.lin_dense);
         r.valid_of = a.valid;
-        hipExtLaunchKernelGGL(k_filter_compact<Rows32>, dim3(grid), dim3(64), 0, st, t0, t1, 0, a.tgt_ref, a.tgt_gbin, a.slots, a.nslots,
-                              a.valid_bits, a.redo, r, out);
+        const FilterKernArgs<Rows32> ka{a.tgt_ref, a.tgt_gbin, a.slots, a.valid_bits, a.redo, a.nslots, r, out};
+        hipExtLaunchKernelGGL(k_filter_compact<Rows32>, dim3(grid), dim3(64), 0, st, t0, t1, 0, ka);
         hipLaunchKernelGGL(k_filter_walk<Rows32>, dim3(std::min(a.nslots, 256u)), dim3(64), 0, st, a.tgt_ref, a.tgt_gbin, a.slots, a.redo, r, out);
     }
 }
