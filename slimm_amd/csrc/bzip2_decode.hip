@@ -192,63 +192,45 @@ double ms_since(std::chrono::steady_clock::time_point t0) {
 #define BZ2_SLACK_FAIL(what, at) \
     fail(c, SLIMM_E_SPLIT, "bzip2: %s at byte %llu is not finished by the %llu bytes read behind the range", what, at, (unsigned long long)bz2::kSplitSlack)
 
-// the block magics of pend from Z.bit on, in order: the bytes not read yet go to the device first (those in front of
-// Z.bit are dropped from pend)
+// the block magics of pend from T.bit on, in order: the bytes go to the device first
 int bz2_find(slimm_ctx* c) {
     WindowPipeline::File::Bzip2& Z = c->win.file.bz2;
+    WindowPipeline::File::Stream& T = c->win.file.stream;
     WindowPipeline::Bzip2& S = c->win.bz2;
     hipStream_t st = c->stream;
     const auto t0 = std::chrono::steady_clock::now();
-    const size_t drop = static_cast<size_t>(Z.bit >> 3);
-    if (drop) {
-        Z.pend.erase(Z.pend.begin(), Z.pend.begin() + static_cast<long>(drop));
-        Z.base += drop;
-        Z.bit -= drop * 8u;
-    }
-    const uint64_t n = Z.pend.size();
-    if (S.comp.cap < n + kBz2Tail) HIP_TRY(c, S.comp.ensure_later(n + (n >> 3) + kBz2Tail, c->win.outgrown));
-    if (n) HIP_TRY(c, hipMemcpyAsync(S.comp.p, Z.pend.data(), n, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemsetAsync(S.comp.p + n, 0, kBz2Tail, st));
+    const uint64_t n = T.pend.size();
+    SLIMM_TRY(stream_upload(c, S.comp, kBz2Tail));
     HIP_TRY(c, S.count.ensure(4));
-    uint32_t cap = static_cast<uint32_t>(std::min<uint64_t>(n / 64u + 256u, 1u << 26));
-    for (;;) {
-        if (S.d_cand.cap < cap) HIP_TRY(c, S.d_cand.ensure_later(cap, c->win.outgrown));
-        HIP_TRY(c, hipMemsetAsync(S.count.p, 0, 4, st));
-        const uint64_t span = n > (Z.bit >> 3) ? n - (Z.bit >> 3) : 0;
+    uint32_t got = 0;
+    // (more magics than room: blocks of a few bytes each, pbzip2 on a tiny input)
+    SLIMM_TRY(stream_candidates(c, S.d_cand, S.count, static_cast<uint32_t>(std::min<uint64_t>(n / 64u + 256u, 1u << 26)), [&](uint32_t cap) {
+        const uint64_t span = n > (T.bit >> 3) ? n - (T.bit >> 3) : 0;
         const uint32_t grid = static_cast<uint32_t>(std::max<uint64_t>(1u, std::min<uint64_t>((span + 255u) / 256u, 4096u)));
-        if (span) hipLaunchKernelGGL(k_bz2_find, dim3(grid), dim3(256), 0, st, S.comp.p, n, Z.bit, n * 8u, S.d_cand.p, S.count.p, cap);
-        HIP_TRY(c, hipGetLastError());
-        uint32_t got = 0;
-        HIP_TRY(c, hipMemcpyAsync(&got, S.count.p, 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(c, hipStreamSynchronize(st));
-        if (got > cap) {   // (more magics than room: blocks of a few bytes each, pbzip2 on a tiny input)
-            cap = got + (got >> 2) + 256u;
-            continue;
-        }
-        Z.cand.resize(got);
-        if (got) HIP_TRY(c, hipMemcpy(Z.cand.data(), S.d_cand.p, got * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        break;
-    }
-    std::sort(Z.cand.begin(), Z.cand.end());
+        if (span) hipLaunchKernelGGL(k_bz2_find, dim3(grid), dim3(256), 0, st, S.comp.p, n, T.bit, n * 8u, S.d_cand.p, S.count.p, cap);
+    }, &got));
+    T.cand.resize(got);
+    if (got) HIP_TRY(c, hipMemcpy(T.cand.data(), S.d_cand.p, got * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    std::sort(T.cand.begin(), T.cand.end());
     long every = 0;
     if (forced("bzip2_false_magics", &every)) {
         // (tests: candidates that are no blocks -- a few bits into every real one, and every `every` bits, 4096 by default
         // -- must be decoded and dropped without changing anything)
         const uint64_t step = every > 1 ? static_cast<uint64_t>(every) : 4096u;
         std::vector<uint64_t> extra;
-        for (uint64_t b : Z.cand) extra.push_back(b + 13u);
-        for (uint64_t b = Z.bit + 5u; b + 48u <= n * 8u; b += step) extra.push_back(b);
-        Z.cand.insert(Z.cand.end(), extra.begin(), extra.end());
-        std::sort(Z.cand.begin(), Z.cand.end());
-        Z.cand.erase(std::unique(Z.cand.begin(), Z.cand.end()), Z.cand.end());
+        for (uint64_t b : T.cand) extra.push_back(b + 13u);
+        for (uint64_t b = T.bit + 5u; b + 48u <= n * 8u; b += step) extra.push_back(b);
+        T.cand.insert(T.cand.end(), extra.begin(), extra.end());
+        std::sort(T.cand.begin(), T.cand.end());
+        T.cand.erase(std::unique(T.cand.begin(), T.cand.end()), T.cand.end());
     }
     const WindowPipeline::Announced& A = c->win.announced;
     if (A.has_range && A.ends_mid) {   // (blocks that start at or behind the range's end are the next member's)
-        const uint64_t lim = A.range_end > Z.base ? (A.range_end - Z.base) * 8u : 0u;
-        Z.cand.erase(std::lower_bound(Z.cand.begin(), Z.cand.end(), lim), Z.cand.end());
+        const uint64_t lim = A.range_end > T.base ? (A.range_end - T.base) * 8u : 0u;
+        T.cand.erase(std::lower_bound(T.cand.begin(), T.cand.end(), lim), T.cand.end());
     }
     Z.next_cand = 0;
-    Z.found = true;
+    T.found = true;
     Z.ms_find += ms_since(t0);
     return SLIMM_OK;
 }
@@ -257,7 +239,7 @@ int bz2_find(slimm_ctx* c) {
 int bz2_first_eos(slimm_ctx* c, uint64_t lo, uint64_t hi, uint64_t* bit) {
     WindowPipeline::Bzip2& S = c->win.bz2;
     hipStream_t st = c->stream;
-    const uint64_t n = c->win.file.bz2.pend.size();
+    const uint64_t n = c->win.file.stream.pend.size();
     unsigned long long* d_first = reinterpret_cast<unsigned long long*>(S.count.p + 2);   // (count holds four words)
     unsigned long long got = ~0ull;
     *bit = ~0ull;
@@ -300,6 +282,7 @@ int bz2_reserve(slimm_ctx* c) {
 
 int bz2_decode_batch(slimm_ctx* c, bool last) {
     WindowPipeline::File::Bzip2& Z = c->win.file.bz2;
+    WindowPipeline::File::Stream& T = c->win.file.stream;
     WindowPipeline::Bzip2& S = c->win.bz2;
     hipStream_t st = c->stream;
     WindowPipeline::File::Bzip2::Chain& K = Z.chain;
@@ -308,25 +291,25 @@ int bz2_decode_batch(slimm_ctx* c, bool last) {
     Z.ready.clear();
     Z.ready_pos = 0;
     if (K.ended) return SLIMM_OK;              // (a range that ends inside the file: what is left of the slack is dropped)
-    if (Z.waiting && !last) return SLIMM_OK;   // (no byte has come since the chain stopped for want of them)
+    if (T.waiting && !last) return SLIMM_OK;   // (no byte has come since the chain stopped for want of them)
     SLIMM_TRY(bz2_reserve(c));
-    if (!Z.found) {
+    if (!T.found) {
         SLIMM_TRY(bz2_find(c));
     }
-    const uint64_t end_bit = Z.pend.size() * 8u;
-    auto at = [&](uint64_t bit) { return static_cast<unsigned long long>(Z.base + (bit >> 3)); };
+    const uint64_t end_bit = T.pend.size() * 8u;
+    auto at = [&](uint64_t bit) { return static_cast<unsigned long long>(T.base + (bit >> 3)); };
     std::vector<bz2::BlockInfo> hinfo;
     size_t batch0 = 0, nb = 0;   // the batch: candidates [batch0, batch0 + nb) in slots 0 .. nb - 1
     std::vector<uint32_t> slots;
     std::vector<uint32_t> crcs;
     std::vector<uint64_t> ats;
-    auto abs_bit = [&](uint64_t bit) { return Z.base * 8u + bit; };
+    auto abs_bit = [&](uint64_t bit) { return T.base * 8u + bit; };
     // the batch of candidates from `from` on decoded into slots 0 .. nb - 1
     auto decode_from = [&](size_t from) -> int {
         const auto t0 = std::chrono::steady_clock::now();
         batch0 = from;
-        nb = std::min<size_t>(Z.slots, Z.cand.size() - batch0);
-        HIP_TRY(c, hipMemcpyAsync(S.d_cand.p, Z.cand.data() + batch0, nb * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        nb = std::min<size_t>(Z.slots, T.cand.size() - batch0);
+        HIP_TRY(c, hipMemcpyAsync(S.d_cand.p, T.cand.data() + batch0, nb * sizeof(uint64_t), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_bz2_decode, dim3(static_cast<uint32_t>(nb)), dim3(64), 0, st, S.comp.p, end_bit, S.d_cand.p, S.ll.p, S.hist.p,
                            S.info.p);
         HIP_TRY(c, hipGetLastError());
@@ -342,13 +325,13 @@ int bz2_decode_batch(slimm_ctx* c, bool last) {
         // (those in front of it are false magics), or an end-of-stream marker in front of that one -- inside a stream of
         // unknown level.  Nothing vouches for that start but the member on the left, whose chain must end there
         // (SLIMM_FORCE bzip2_split_wrong_first: the first element is passed over, the chain starts at the one behind it)
-        const uint64_t range_end_bit = ends_mid ? (A.range_end > Z.base ? (A.range_end - Z.base) * 8u : 0u) : end_bit;
-        uint64_t lo = Z.bit, first = ~0ull;
+        const uint64_t range_end_bit = ends_mid ? (A.range_end > T.base ? (A.range_end - T.base) * 8u : 0u) : end_bit;
+        uint64_t lo = T.bit, first = ~0ull;
         size_t i = Z.next_cand;
         for (int pass = forced("bzip2_split_wrong_first") ? 2 : 1; pass > 0; --pass) {
             bool have_block = false;
-            for (; i < Z.cand.size(); ++i) {
-                if (Z.cand[i] < lo) continue;
+            for (; i < T.cand.size(); ++i) {
+                if (T.cand[i] < lo) continue;
                 if (i < batch0 || i >= batch0 + nb) SLIMM_TRY(decode_from(i));
                 const uint32_t status = hinfo[i - batch0].status;
                 if (status == bz2::kRanOut && !last) break;   // (its bytes go on with the next push: no verdict yet)
@@ -357,24 +340,24 @@ int bz2_decode_batch(slimm_ctx* c, bool last) {
                 break;
             }
             if (!have_block && !last) {
-                Z.waiting = true;
+                T.waiting = true;
                 return SLIMM_OK;
             }
-            SLIMM_TRY(bz2_first_eos(c, lo, std::min(have_block ? Z.cand[i] : end_bit, range_end_bit), &first));
-            if (have_block) first = std::min<uint64_t>(first, Z.cand[i]);
+            SLIMM_TRY(bz2_first_eos(c, lo, std::min(have_block ? T.cand[i] : end_bit, range_end_bit), &first));
+            if (have_block) first = std::min<uint64_t>(first, T.cand[i]);
             if (first == ~0ull) break;
             lo = first + 1u;   // (forced: the element behind the first one)
         }
-        const size_t next = static_cast<size_t>(std::lower_bound(Z.cand.begin(), Z.cand.end(), first) - Z.cand.begin());
+        const size_t next = static_cast<size_t>(std::lower_bound(T.cand.begin(), T.cand.end(), first) - T.cand.begin());
         Z.false_magics += next - Z.next_cand;
         Z.next_cand = next;
         K.started = true;
         if (first == ~0ull) {   // (no block or marker starts in the range: an empty member)
             K.ended = true;
-            K.end_bit = abs_bit(Z.bit);
+            K.end_bit = abs_bit(T.bit);
             return SLIMM_OK;
         }
-        Z.bit = first;
+        T.bit = first;
         Z.in_stream = K.first_stream = K.any = true;
         Z.level = 9;
         Z.combined = 0;
@@ -384,50 +367,50 @@ int bz2_decode_batch(slimm_ctx* c, bool last) {
     }
     for (;;) {
         if (!Z.in_stream) {   // a stream header, at a byte
-            const uint64_t byte = Z.bit >> 3;
-            const uint64_t avail = Z.pend.size() - byte;
-            const uint8_t* h = Z.pend.data() + byte;
+            const uint64_t byte = T.bit >> 3;
+            const uint64_t avail = T.pend.size() - byte;
+            const uint8_t* h = T.pend.data() + byte;
             if (avail == 0) {
-                if (last && Z.streams == 0) return BZ2_FAIL("truncated at byte %llu", at(Z.bit));
-                Z.waiting = true;
+                if (last && Z.streams == 0) return BZ2_FAIL("truncated at byte %llu", at(T.bit));
+                T.waiting = true;
                 K.at_file_end = last;
                 break;
             }
             if (avail < 4 && !last && memcmp(h, "BZh", avail) == 0) {
-                Z.waiting = true;
+                T.waiting = true;
                 break;
             }
             if (avail < 4 || memcmp(h, "BZh", 3) != 0 || h[3] < '1' || h[3] > '9') {
-                if (avail < 4 && memcmp(h, "BZh", avail) == 0) return BZ2_FAIL("truncated stream header at byte %llu", at(Z.bit));
-                if (Z.streams) return BZ2_FAIL("bytes after the last end-of-stream marker, at byte %llu", at(Z.bit));
+                if (avail < 4 && memcmp(h, "BZh", avail) == 0) return BZ2_FAIL("truncated stream header at byte %llu", at(T.bit));
+                if (Z.streams) return BZ2_FAIL("bytes after the last end-of-stream marker, at byte %llu", at(T.bit));
                 return BZ2_FAIL("not a bzip2 stream%s", "");
             }
             Z.level = static_cast<uint32_t>(h[3] - '0');
             Z.combined = 0;
             Z.in_stream = true;
             ++Z.streams;
-            Z.bit += 32;
+            T.bit += 32;
         }
         // (a range that ends inside the file: the element -- a block, or a marker with the stream header behind it -- that
         // starts at or behind the range's end is the next member's)
-        if (ends_mid && abs_bit(Z.bit) >= A.range_end * 8u) {
+        if (ends_mid && abs_bit(T.bit) >= A.range_end * 8u) {
             K.ended = true;
             break;
         }
-        bz2::Bits br(Z.pend.data(), Z.bit, end_bit);
+        bz2::Bits br(T.pend.data(), T.bit, end_bit);
         uint64_t magic;
         if (!br.peek48(magic)) {
-            if (last && ends_mid) return BZ2_SLACK_FAIL("what starts", at(Z.bit));
-            if (last) return BZ2_FAIL("truncated at byte %llu", at(Z.bit));
-            Z.waiting = true;
+            if (last && ends_mid) return BZ2_SLACK_FAIL("what starts", at(T.bit));
+            if (last) return BZ2_FAIL("truncated at byte %llu", at(T.bit));
+            T.waiting = true;
             break;
         }
         if (magic == bz2::kEosMagic) {
             uint32_t v, hi, lo;
             if (!br.get(24, v) || !br.get(24, v) || !br.get(16, hi) || !br.get(16, lo)) {
-                if (last && ends_mid) return BZ2_SLACK_FAIL("the end-of-stream marker", at(Z.bit));
-                if (last) return BZ2_FAIL("truncated end-of-stream marker at byte %llu", at(Z.bit));
-                Z.waiting = true;
+                if (last && ends_mid) return BZ2_SLACK_FAIL("the end-of-stream marker", at(T.bit));
+                if (last) return BZ2_FAIL("truncated end-of-stream marker at byte %llu", at(T.bit));
+                T.waiting = true;
                 break;
             }
             if (K.first_stream) {   // (the stream the range started in: the stitch knows what came before)
@@ -435,24 +418,24 @@ int bz2_decode_batch(slimm_ctx* c, bool last) {
                 K.has_eos = true;
                 K.first_combined = Z.combined;
                 K.eos_crc = (hi << 16) | lo;
-                K.eos_at = at(Z.bit);
+                K.eos_at = at(T.bit);
             } else if (((hi << 16) | lo) != Z.combined) {
                 if (!slots.empty()) break;   // (the blocks in front go first: a block CRC that does not match is named as such)
-                return BZ2_FAIL("end-of-stream marker at byte %llu: combined CRC mismatch", at(Z.bit));
+                return BZ2_FAIL("end-of-stream marker at byte %llu: combined CRC mismatch", at(T.bit));
             }
-            Z.bit = (br.pos() + 7u) & ~7ull;
+            T.bit = (br.pos() + 7u) & ~7ull;
             Z.in_stream = false;
             K.any = true;
             continue;
         }
-        if (magic != bz2::kBlockMagic) return BZ2_FAIL("at byte %llu: %s", at(Z.bit), bz2::status_text(bz2::kNoBlock));
+        if (magic != bz2::kBlockMagic) return BZ2_FAIL("at byte %llu: %s", at(T.bit), bz2::status_text(bz2::kNoBlock));
         // a block: decoded in the batch at hand, or first in a new batch (once the blocks of this one are through)
-        while (Z.next_cand < Z.cand.size() && Z.cand[Z.next_cand] < Z.bit) {   // (magics inside the blocks in front: no blocks)
+        while (Z.next_cand < T.cand.size() && T.cand[Z.next_cand] < T.bit) {   // (magics inside the blocks in front: no blocks)
             ++Z.next_cand;
             ++Z.false_magics;
         }
-        if (Z.next_cand >= Z.cand.size() || Z.cand[Z.next_cand] != Z.bit)
-            return fail(c, SLIMM_E_INVALID, "bzip2: the block magic at byte %llu was not found by the device's scan", at(Z.bit));
+        if (Z.next_cand >= T.cand.size() || T.cand[Z.next_cand] != T.bit)
+            return fail(c, SLIMM_E_INVALID, "bzip2: the block magic at byte %llu was not found by the device's scan", at(T.bit));
         if (Z.next_cand < batch0 || Z.next_cand >= batch0 + nb) {
             if (!slots.empty()) break;
             SLIMM_TRY(decode_from(Z.next_cand));
@@ -460,26 +443,26 @@ int bz2_decode_batch(slimm_ctx* c, bool last) {
         const uint32_t s = static_cast<uint32_t>(Z.next_cand - batch0);
         const bz2::BlockInfo& r = hinfo[s];
         if (r.status == bz2::kRanOut) {   // (the block's bytes go on with the next push)
-            if (last && ends_mid) return BZ2_SLACK_FAIL("the block", at(Z.bit));
-            if (last) return BZ2_FAIL("block at byte %llu: truncated", at(Z.bit));
-            Z.waiting = true;
+            if (last && ends_mid) return BZ2_SLACK_FAIL("the block", at(T.bit));
+            if (last) return BZ2_FAIL("block at byte %llu: truncated", at(T.bit));
+            T.waiting = true;
             break;
         }
-        if (r.status != bz2::kOk) return BZ2_FAIL("block at byte %llu: %s", at(Z.bit), bz2::status_text(r.status));
-        if (r.n > Z.level * 100000u) return BZ2_FAIL("block at byte %llu: %s", at(Z.bit), bz2::status_text(bz2::kTooLong));
+        if (r.status != bz2::kOk) return BZ2_FAIL("block at byte %llu: %s", at(T.bit), bz2::status_text(r.status));
+        if (r.n > Z.level * 100000u) return BZ2_FAIL("block at byte %llu: %s", at(T.bit), bz2::status_text(bz2::kTooLong));
         if (K.first_stream) {   // (level unknown: the stitch holds the largest block against the left chain's level)
             ++K.first_blocks;
-            if (r.n > K.first_max_n) K.first_max_n = r.n, K.first_max_at = at(Z.bit);
+            if (r.n > K.first_max_n) K.first_max_n = r.n, K.first_max_at = at(T.bit);
         }
         K.any = true;
         slots.push_back(s);
         crcs.push_back(r.crc);
-        ats.push_back(at(Z.bit));
+        ats.push_back(at(T.bit));
         Z.combined = ((Z.combined << 1) | (Z.combined >> 31)) ^ r.crc;
-        Z.bit = r.end_bit;
+        T.bit = r.end_bit;
         ++Z.next_cand;
     }
-    K.end_bit = abs_bit(Z.bit);
+    K.end_bit = abs_bit(T.bit);
     if (slots.empty()) return SLIMM_OK;
     // the blocks of the chain: inverse BWT, text lengths
     const auto t0 = std::chrono::steady_clock::now();
@@ -497,8 +480,7 @@ int bz2_decode_batch(slimm_ctx* c, bool last) {
         b.slot = slots[i];
         b.crc = crcs[i];
         b.len = len[i];
-        b.drop = std::min<uint64_t>(Z.skip_left, b.len);
-        Z.skip_left -= b.drop;
+        b.drop = T.skip_of(b.len);
         b.at = ats[i];
         b.unchecked = starts_mid && Z.blocks == 0 && i == 0;
         Z.ready.push_back(b);
@@ -515,6 +497,8 @@ void bz2_trace_file(const slimm_ctx* c) {
             (unsigned long long)Z.batches, (unsigned long long)Z.false_magics, Z.ms_find, Z.ms_decode, Z.ms_bwt, Z.ms_emit);
 }
 
+namespace {
+// the text bytes of the next ready blocks that fit in `cap` (at least one block)
 uint64_t bz2_window_bytes(const slimm_ctx* c, uint64_t cap, size_t* n_blocks) {
     const WindowPipeline::File::Bzip2& Z = c->win.file.bz2;
     uint64_t n = 0;
@@ -527,9 +511,18 @@ uint64_t bz2_window_bytes(const slimm_ctx* c, uint64_t cap, size_t* n_blocks) {
     *n_blocks = i - Z.ready_pos;
     return n;
 }
+}  // namespace
 
-int bz2_emit(slimm_ctx* c, uint8_t* dst, size_t n_blocks, uint8_t* last_byte) {
+bool bz2_next_window(const slimm_ctx* c, uint64_t cap, uint64_t* n) {
+    size_t n_blocks = 0;
+    *n = bz2_window_bytes(c, cap, &n_blocks);
+    return n_blocks != 0;
+}
+
+int bz2_emit(slimm_ctx* c, uint8_t* dst, uint64_t cap, uint64_t* n_out, uint8_t* last_byte) {
     WindowPipeline::File::Bzip2& Z = c->win.file.bz2;
+    size_t n_blocks = 0;
+    *n_out = bz2_window_bytes(c, cap, &n_blocks);
     WindowPipeline::Bzip2& S = c->win.bz2;
     hipStream_t st = c->stream;
     const auto t0 = std::chrono::steady_clock::now();

@@ -200,135 +200,124 @@ void push_trace_gz(const char* fmt, ...) {   // "[push gzip] ..."
 #define GZ_CORRUPT(fmt, ...) fail(c, SLIMM_E_INVALID, "corrupt gzip stream (" fmt ")", __VA_ARGS__)
 #define GZ_TRUNCATED() fail(c, SLIMM_E_INVALID, "truncated gzip stream")
 
-// the block candidates of pend from Z.bit on, in order; the bytes go to the device first
+// the block candidates of pend from T.bit on, in order; the bytes go to the device first
 int gz_find(slimm_ctx* c) {
     WindowPipeline& W = c->win;
-    WindowPipeline::File::Gzip& Z = W.file.gz;
+    WindowPipeline::File::Stream& T = W.file.stream;
     WindowPipeline::Gzip& S = W.gz;
     hipStream_t st = c->stream;
-    const uint64_t n = Z.pend.size();
-    if (S.comp.cap < n + kGzTail) HIP_TRY(c, S.comp.ensure_later(n + (n >> 3) + kGzTail, W.outgrown));
-    if (n) HIP_TRY(c, hipMemcpyAsync(S.comp.p, Z.pend.data(), n, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemsetAsync(S.comp.p + n, 0, kGzTail, st));
+    const uint64_t n = T.pend.size();
+    SLIMM_TRY(stream_upload(c, S.comp, kGzTail));
     HIP_TRY(c, S.count.ensure(4));
-    Z.cand.clear();
-    const uint64_t bits = n * 8u > Z.bit ? n * 8u - Z.bit : 0u;
-    uint32_t cap = static_cast<uint32_t>(std::min<uint64_t>(bits / 256u + 1024u, 1u << 27));
-    std::vector<uint64_t> pre;
-    for (; bits;) {
-        if (S.d_cand.cap < cap) HIP_TRY(c, S.d_cand.ensure_later(cap, W.outgrown));
-        HIP_TRY(c, hipMemsetAsync(S.count.p, 0, 4, st));
-        const uint32_t grid = static_cast<uint32_t>(std::max<uint64_t>(1u, std::min<uint64_t>((bits + 255u) / 256u, 8192u)));
-        hipLaunchKernelGGL(k_gz_find, dim3(grid), dim3(256), 0, st, S.comp.p, n, Z.bit, S.d_cand.p, S.count.p, cap);
-        HIP_TRY(c, hipGetLastError());
-        uint32_t got = 0;
-        HIP_TRY(c, hipMemcpyAsync(&got, S.count.p, 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(c, hipStreamSynchronize(st));
-        if (got > cap) {   // (more than room: again, with room)
-            cap = got + (got >> 2) + 256u;
-            continue;
-        }
-        if (!got) break;
+    T.cand.clear();
+    const uint64_t bits = n * 8u > T.bit ? n * 8u - T.bit : 0u;
+    uint32_t got = 0;
+    if (bits)
+        SLIMM_TRY(stream_candidates(c, S.d_cand, S.count, static_cast<uint32_t>(std::min<uint64_t>(bits / 256u + 1024u, 1u << 27)), [&](uint32_t cap) {
+            const uint32_t grid = static_cast<uint32_t>(std::max<uint64_t>(1u, std::min<uint64_t>((bits + 255u) / 256u, 8192u)));
+            hipLaunchKernelGGL(k_gz_find, dim3(grid), dim3(256), 0, st, S.comp.p, n, T.bit, S.d_cand.p, S.count.p, cap);
+        }, &got));
+    if (got) {
         if (S.flag.cap < got) HIP_TRY(c, S.flag.ensure_later(got + (got >> 2), W.outgrown));
         hipLaunchKernelGGL(k_gz_check, dim3(got), dim3(64), 0, st, S.comp.p, n, S.d_cand.p, got, S.flag.p);
         HIP_TRY(c, hipGetLastError());
-        pre.resize(got);
+        std::vector<uint64_t> pre(got);
         std::vector<uint32_t> ok(got);
         HIP_TRY(c, hipMemcpyAsync(pre.data(), S.d_cand.p, got * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
         HIP_TRY(c, hipMemcpyAsync(ok.data(), S.flag.p, got * 4u, hipMemcpyDeviceToHost, st));
         HIP_TRY(c, hipStreamSynchronize(st));
         for (uint32_t i = 0; i < got; ++i)
-            if (ok[i]) Z.cand.push_back(pre[i]);
-        break;
+            if (ok[i]) T.cand.push_back(pre[i]);
     }
-    std::sort(Z.cand.begin(), Z.cand.end());
-    W.gz_stats[WindowPipeline::kGzCandidates] += Z.cand.size();
-    Z.found = true;
+    std::sort(T.cand.begin(), T.cand.end());
+    W.gz_stats[WindowPipeline::kGzCandidates] += T.cand.size();
+    T.found = true;
     return SLIMM_OK;
 }
 
 }  // namespace
 
-uint64_t gz_ready_bytes(const slimm_ctx* c) {
-    const WindowPipeline::File::Gzip& Z = c->win.file.gz;
-    uint64_t n = 0;
-    for (const gz::Chunk& k : Z.ready) n += k.len;
-    return n - std::min(n, Z.skip_left);
+bool gz_next_window(const slimm_ctx* c, uint64_t, uint64_t* n) {   // (a round's text is one window: kRoundText)
+    uint64_t text = 0;
+    for (const gz::Chunk& k : c->win.file.gz.ready) text += k.len;
+    *n = text - std::min(text, c->win.file.stream.skip_left);
+    return !c->win.file.gz.ready.empty();
 }
 
 int gz_round(slimm_ctx* c, bool last) {
     WindowPipeline& W = c->win;
     WindowPipeline::File::Gzip& Z = W.file.gz;
+    WindowPipeline::File::Stream& T = W.file.stream;
     WindowPipeline::Gzip& S = W.gz;
     hipStream_t st = c->stream;
     uint64_t* stats = W.gz_stats;
     Z.ready.clear();
-    if (Z.waiting && !last) return SLIMM_OK;
+    if (T.waiting && !last) return SLIMM_OK;
     // the candidates in [from, to) of the bytes at hand lie in a trailer or a member header: passed over
     auto pass_over = [&](uint64_t from, uint64_t to) {
-        if (!Z.found) return;
-        stats[WindowPipeline::kGzDropped] += static_cast<uint64_t>(std::lower_bound(Z.cand.begin(), Z.cand.end(), to) -
-                                                                   std::lower_bound(Z.cand.begin(), Z.cand.end(), from));
+        if (!T.found) return;
+        stats[WindowPipeline::kGzDropped] += static_cast<uint64_t>(std::lower_bound(T.cand.begin(), T.cand.end(), to) -
+                                                                   std::lower_bound(T.cand.begin(), T.cand.end(), from));
     };
     // ---- between the deflate streams, on the host: a trailer, a member header
     while (Z.stage != Stage::Deflate) {
-        const uint64_t byte = (Z.bit + 7u) >> 3, avail = Z.pend.size() - std::min<uint64_t>(byte, Z.pend.size());
-        const uint8_t* p = Z.pend.data() + byte;
+        const uint64_t byte = (T.bit + 7u) >> 3, avail = T.pend.size() - std::min<uint64_t>(byte, T.pend.size());
+        const uint8_t* p = T.pend.data() + byte;
         if (Z.stage == Stage::Trailer) {
             if (avail < 8) {
                 if (last) return GZ_TRUNCATED();
-                Z.waiting = true;
+                T.waiting = true;
                 return SLIMM_OK;
             }
             const uint32_t crc = p[0] | (p[1] << 8) | (p[2] << 16) | (static_cast<uint32_t>(p[3]) << 24);
             const uint32_t isize = p[4] | (p[5] << 8) | (p[6] << 16) | (static_cast<uint32_t>(p[7]) << 24);
             if (crc != ~Z.crc) return GZ_CORRUPT("%s", gz::status_text(gz::kBadCrc));
             if (isize != static_cast<uint32_t>(Z.len)) return GZ_CORRUPT("%s", gz::status_text(gz::kBadLength));
-            pass_over(Z.bit, (byte + 8u) * 8u);
-            Z.bit = (byte + 8u) * 8u;
+            pass_over(T.bit, (byte + 8u) * 8u);
+            T.bit = (byte + 8u) * 8u;
             Z.stage = Stage::Header;
             ++stats[WindowPipeline::kGzMembers];
             continue;
         }
         if (avail == 0) {   // the file is used up between two members
             if (last && stats[WindowPipeline::kGzMembers] == 0) return GZ_TRUNCATED();
-            Z.waiting = true;
+            T.waiting = true;
             return SLIMM_OK;
         }
         const long h = gz::member_header(p, avail);
         if (h < 0) return GZ_CORRUPT("%s", "incorrect header check");
         if (h == 0) {
             if (last) return GZ_TRUNCATED();
-            Z.waiting = true;
+            T.waiting = true;
             return SLIMM_OK;
         }
-        pass_over(Z.bit, (byte + static_cast<uint64_t>(h)) * 8u);
-        Z.bit = (byte + static_cast<uint64_t>(h)) * 8u;
+        pass_over(T.bit, (byte + static_cast<uint64_t>(h)) * 8u);
+        T.bit = (byte + static_cast<uint64_t>(h)) * 8u;
         Z.stage = Stage::Deflate;
         Z.crc = 0xffffffffu;
         Z.len = 0;
     }
     // ---- a round on the device: candidates, chunk starts, the size pass
-    if (!Z.found) SLIMM_TRY(gz_find(c));
-    const uint64_t n_bytes = Z.pend.size(), end_bit = n_bytes * 8u;
+    if (!T.found) SLIMM_TRY(gz_find(c));
+    const uint64_t n_bytes = T.pend.size(), end_bit = n_bytes * 8u;
     long chunk = 0, every = 0;
     if (!forced("gzip_chunk", &chunk) || chunk <= 0) chunk = static_cast<long>(kGzipChunk);
-    std::vector<uint64_t> starts{Z.bit};
+    std::vector<uint64_t> starts{T.bit};
     const uint64_t cb = static_cast<uint64_t>(chunk) * 8u;
-    for (uint64_t target = Z.bit + cb;;) {   // (the first candidate at or behind every cb bits)
-        const auto it = std::lower_bound(Z.cand.begin(), Z.cand.end(), target);
-        if (it == Z.cand.end()) break;
+    for (uint64_t target = T.bit + cb;;) {   // (the first candidate at or behind every cb bits)
+        const auto it = std::lower_bound(T.cand.begin(), T.cand.end(), target);
+        if (it == T.cand.end()) break;
         starts.push_back(*it);
-        target = Z.bit + ((*it - Z.bit) / cb + 1u) * cb;
+        target = T.bit + ((*it - T.bit) / cb + 1u) * cb;
     }
     if (forced("gzip_false_starts", &every)) {
         // (tests: chunk starts that start no block -- a few bits into every candidate, and every `every` bits, 4096 by
         // default -- must be walked and dropped without changing anything)
         const uint64_t step = every > 1 ? static_cast<uint64_t>(every) : 4096u;
         const size_t before = starts.size();
-        for (auto it = std::upper_bound(Z.cand.begin(), Z.cand.end(), Z.bit); it != Z.cand.end(); ++it)
+        for (auto it = std::upper_bound(T.cand.begin(), T.cand.end(), T.bit); it != T.cand.end(); ++it)
             if (*it + 13u < end_bit) starts.push_back(*it + 13u);
-        for (uint64_t b = Z.bit + 5u; b + 3u <= end_bit; b += step) starts.push_back(b);
+        for (uint64_t b = T.bit + 5u; b + 3u <= end_bit; b += step) starts.push_back(b);
         stats[WindowPipeline::kGzForced] += starts.size() - before;
     }
     std::sort(starts.begin(), starts.end());
@@ -344,7 +333,7 @@ int gz_round(slimm_ctx* c, bool last) {
     HIP_TRY(c, hipStreamSynchronize(st));
     ++stats[WindowPipeline::kGzRounds];
     // ---- the chain
-    uint64_t cur = Z.bit, text = 0, member_len = Z.len;
+    uint64_t cur = T.bit, text = 0, member_len = Z.len;
     size_t i = 0;
     uint32_t pieces = 0;
     bool final = false;
@@ -368,7 +357,7 @@ int gz_round(slimm_ctx* c, bool last) {
         }
         if (w.status == gz::kRanOut) {
             if (last) return GZ_TRUNCATED();
-            Z.waiting = true;
+            T.waiting = true;
             break;
         }
         if (w.final) {
@@ -384,12 +373,12 @@ int gz_round(slimm_ctx* c, bool last) {
     for (const gz::Chunk& k : Z.ready) chained += std::binary_search(starts.begin(), starts.end(), k.start_bit) ? 1u : 0u;
     stats[WindowPipeline::kGzDropped] += static_cast<uint64_t>(std::lower_bound(starts.begin(), starts.end(), cur) - starts.begin()) - chained;
     stats[WindowPipeline::kGzChunks] += Z.ready.size();
-    Z.bit = cur;
+    T.bit = cur;
     if (final) Z.stage = Stage::Trailer;
     return SLIMM_OK;
 }
 
-int gz_emit(slimm_ctx* c, uint8_t* dst, uint64_t* n_out, uint8_t* last_byte) {
+int gz_emit(slimm_ctx* c, uint8_t* dst, uint64_t, uint64_t* n_out, uint8_t* last_byte) {
     WindowPipeline& W = c->win;
     WindowPipeline::File::Gzip& Z = W.file.gz;
     WindowPipeline::Gzip& S = W.gz;
@@ -401,7 +390,7 @@ int gz_emit(slimm_ctx* c, uint8_t* dst, uint64_t* n_out, uint8_t* last_byte) {
     uint64_t text = 0;
     for (const gz::Chunk& k : Z.ready) text += k.len;
     const uint32_t pieces = Z.ready.back().piece0 + static_cast<uint32_t>((Z.ready.back().len + gz::kPiece - 1u) / gz::kPiece);
-    const uint64_t drop = std::min(text, Z.skip_left);
+    const uint64_t drop = W.file.stream.skip_of(text);
     if (S.chunks.cap < n) HIP_TRY(c, S.chunks.ensure_later(n + (n >> 2) + 64u, W.outgrown));
     if (S.sym.cap < text + 1u) HIP_TRY(c, S.sym.ensure_later(text + (text >> 3) + 1u, W.outgrown));
     if (S.piece.cap < pieces + 1u) HIP_TRY(c, S.piece.ensure_later(pieces + (pieces >> 3) + 1u, W.outgrown));
@@ -414,7 +403,7 @@ int gz_emit(slimm_ctx* c, uint8_t* dst, uint64_t* n_out, uint8_t* last_byte) {
     }
     if (!Z.carried) HIP_TRY(c, hipMemsetAsync(S.win.p, 0, gz::kWindow, st));
     HIP_TRY(c, hipMemcpyAsync(S.chunks.p, Z.ready.data(), n * sizeof(gz::Chunk), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_gz_decode, dim3(n), dim3(64), 0, st, S.comp.p, Z.pend.size(), S.chunks.p, n, S.sym.p);
+    hipLaunchKernelGGL(k_gz_decode, dim3(n), dim3(64), 0, st, S.comp.p, W.file.stream.pend.size(), S.chunks.p, n, S.sym.p);
     hipLaunchKernelGGL(k_gz_windows, dim3(1), dim3(1024), 0, st, S.chunks.p, n, S.sym.p, S.win.p);
     if (pieces)
         hipLaunchKernelGGL(k_gz_resolve, dim3((pieces + 255u) / 256u), dim3(256), 0, st, S.chunks.p, n, pieces, S.sym.p, S.win.p, drop, dst, S.piece.p);
@@ -436,7 +425,6 @@ int gz_emit(slimm_ctx* c, uint8_t* dst, uint64_t* n_out, uint8_t* last_byte) {
         stats[WindowPipeline::kGzDynamic] += k.kinds[2];
         stats[WindowPipeline::kGzResolved] += k.markers;
     }
-    Z.skip_left -= drop;
     stats[WindowPipeline::kGzText] += text;
     *n_out = text - drop;
     push_trace_gz("round %llu: %u chunks -> %.1f MB of text", (unsigned long long)stats[WindowPipeline::kGzRounds], n, text / 1e6);

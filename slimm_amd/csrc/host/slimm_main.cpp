@@ -639,8 +639,7 @@ struct RecordPump {
     // windows the host inflates (read_raw) and, every device_period-th of those read in place, whole blocks (read_blocks)
     void run_raw() {
         const bool bgzf = bam.compression() == Compression::Bgzf;
-        // (bzip2, gzip and zstd SAM: the file's bytes go to the device as they lie in the file)
-        const bool bzip2 = bam.compression() == Compression::Bzip2 || gzip_on_device() || zstd_on_device();
+        const bool streamed = streamed_sam();
         for (unsigned w = 0;; w = (w + 1) % kRawBuffers) {
             {
                 std::unique_lock<std::mutex> g(mu);
@@ -659,7 +658,7 @@ struct RecordPump {
             // (every device_period-th of the windows read in place)
             bool compressed = false;
             long n;
-            if (bzip2) {   // bzip2 / gzip SAM: the file's bytes as they lie in it (slimm_push_bzip2_sam_bytes / _gzip_sam_bytes decode them)
+            if (streamed) {   // the file's bytes as they lie in it (slimm_push_bzip2_sam_bytes / _gzip_sam_bytes / _zstd_sam_bytes decode them)
                 n = bam.read_compressed(raw_buf[w].get(), raw_cap());
                 compressed = true;
                 ++raw_windows_device;
@@ -678,7 +677,7 @@ struct RecordPump {
             decode_ms += ms(t1, std::chrono::steady_clock::now());
             {
                 std::lock_guard<std::mutex> g(mu);
-                raw_ready.push_back(RawWindow{w, n, n > 0 && ((bgzf && bam.raw_exhausted()) || (bzip2 && bam.compressed_exhausted())), compressed});
+                raw_ready.push_back(RawWindow{w, n, n > 0 && ((bgzf && bam.raw_exhausted()) || (streamed && bam.compressed_exhausted())), compressed});
             }
             cv.notify_all();
             if (n <= 0) {
@@ -687,19 +686,20 @@ struct RecordPump {
             }
         }
     }
-    // gzip SAM is inflated on the device (a header of 4 GiB of text or more: by the host reader, the push's `skip` has 32 bits)
-    bool gzip_on_device() const { return !bam.is_bam() && bam.compression() == Compression::Gzip && bam.text_header_bytes() < (1ull << 32); }
-    bool zstd_on_device() const { return !bam.is_bam() && bam.compression() == Compression::Zstd && bam.text_header_bytes() < (1ull << 32); }   // (zstd SAM: the same)
+    // gzip and zstd SAM are decoded on the device (a header of 4 GiB of text or more: by the host reader, the push's `skip` has 32 bits)
+    bool on_device(Compression k) const { return !bam.is_bam() && bam.compression() == k && bam.text_header_bytes() < (1ull << 32); }
+    // bzip2, gzip and zstd SAM: the file's bytes go to the device as they lie in the file
+    bool streamed_sam() const { return bam.compression() == Compression::Bzip2 || on_device(Compression::Gzip) || on_device(Compression::Zstd); }
     // ... and the thread that hands them to the device, from the moment the context exists
     void push_raw(slimm_ctx* c) {
         bool pinned[kRawBuffers] = {};
         bool closed = false;  // a window went out as the file's last
         bool in_flight = false;  // the window pushed last is still being copied out of its buffer
-        bool gzip_traced = false;
-        const bool text = !bam.is_bam(), gzip = gzip_on_device(), zstd = zstd_on_device(), bzip2 = bam.compression() == Compression::Bzip2 || gzip || zstd;
-        // (bzip2 and gzip SAM go from the file's first byte: the first push skips the header's decoded bytes)
-        uint32_t skip = bzip2 ? static_cast<uint32_t>(bam.text_header_bytes()) : 0u;
-        const auto push_compressed = zstd ? slimm_push_zstd_sam_bytes : gzip ? slimm_push_gzip_sam_bytes : slimm_push_bzip2_sam_bytes;
+        bool end_traced = false;
+        const bool text = !bam.is_bam(), gzip = on_device(Compression::Gzip), zstd = on_device(Compression::Zstd), streamed = streamed_sam();
+        // (a streamed file goes from its first byte: the first push skips the header's decoded bytes)
+        uint32_t skip = streamed ? static_cast<uint32_t>(bam.text_header_bytes()) : 0u;
+        const auto push_streamed = zstd ? slimm_push_zstd_sam_bytes : gzip ? slimm_push_gzip_sam_bytes : slimm_push_bzip2_sam_bytes;
         if (text) {   // SAM text names its references: the header's names for the device's look-up
             std::vector<const char*> names;
             for (const std::string& nm : bam.ref_names()) names.push_back(nm.c_str());
@@ -733,29 +733,25 @@ struct RecordPump {
                 const uint8_t* p = raw_buf[w.which].get();
                 const uint64_t n = static_cast<uint64_t>(w.n);
                 const int last = w.last ? 1 : 0;
-                rc = bzip2          ? push_compressed(c, p, n, skip, last, &got)
+                rc = streamed       ? push_streamed(c, p, n, skip, last, &got)
                      : w.compressed ? (text ? slimm_push_bgzf_sam_blocks(c, p, n, 0u, last, &got) : slimm_push_bgzf_blocks(c, p, n, 0u, last, &got))
                                     : (text ? slimm_push_sam_bytes(c, p, n, last, &got) : slimm_push_bam_bytes(c, p, n, last, &got));
                 skip = 0;
                 closed = w.last;
             } else if (!closed) {
-                rc = bzip2  ? push_compressed(c, nullptr, 0, skip, 1, &got)
+                rc = streamed ? push_streamed(c, nullptr, 0, skip, 1, &got)
                      : text ? slimm_push_sam_bytes(c, nullptr, 0, 1, &got)
                             : slimm_push_bam_bytes(c, nullptr, 0, 1, &got);  // (the end came without notice: an incomplete record is an error)
             }
             raw_push_ms += ms(t1, std::chrono::steady_clock::now());
             raw_records += got;
-            if (zstd && g_trace && rc >= 0 && (closed || w.n == 0) && !gzip_traced) {
+            if ((gzip || zstd) && g_trace && rc >= 0 && (closed || w.n == 0) && !end_traced) {   // (the file's end: what the device decoded)
                 uint64_t st[20] = {};
-                gzip_traced = true;
-                if (slimm_get_zstd_stats(c, st) == SLIMM_OK)
+                end_traced = true;
+                if (zstd && slimm_get_zstd_stats(c, st) == SLIMM_OK)
                     fprintf(stderr, "[trace] zstd SAM on the device: %llu frames, %llu blocks, %llu bytes of text\n", (unsigned long long)st[0],
                             (unsigned long long)(st[2] + st[3] + st[4]), (unsigned long long)st[16]);
-            }
-            if (gzip && g_trace && rc >= 0 && (closed || w.n == 0) && !gzip_traced) {
-                uint64_t st[12] = {};
-                gzip_traced = true;
-                if (slimm_get_gzip_stats(c, st) == SLIMM_OK)
+                if (gzip && slimm_get_gzip_stats(c, st) == SLIMM_OK)
                     fprintf(stderr, "[trace] gzip SAM on the device: %llu members, %llu chunks (%llu candidates dropped), %llu bytes of text\n",
                             (unsigned long long)st[0], (unsigned long long)st[1], (unsigned long long)st[3], (unsigned long long)st[9]);
             }

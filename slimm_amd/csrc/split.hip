@@ -199,7 +199,7 @@ int slimm_host_bzip2_ranges(const char* path, uint64_t skip, uint32_t n, uint64_
 
 namespace slimm {
 
-bool split_is_bzip2(const slimm_ctx* c) { return c->win.file.bz2.on; }
+bool split_is_bzip2(const slimm_ctx* c) { return c->win.file.stream.codec == WindowPipeline::File::Codec::Bzip2; }
 
 int split_bz2_chains(slimm_ctx* const* members, uint32_t n, uint32_t* bad) {
     auto rotl = [](uint32_t v, uint32_t k) {
@@ -252,7 +252,7 @@ int split_range(slimm_ctx* c, SplitRange* out) {
     if (!c || !out) return SLIMM_E_INVALID;
     if (c->device < 0 || !c->win.file.active || !c->win.file.closed)
         return fail(c, SLIMM_E_INVALID, "a range of a split file: a range of BAM, SAM, BGZF SAM or bzip2 SAM pushed to its end");
-    if (c->win.file.bz2.on && !c->win.announced.has_range)
+    if (split_is_bzip2(c) && !c->win.announced.has_range)
         return fail(c, SLIMM_E_INVALID, "a range of a bzip2 file: slimm_set_input_range tells where it lies");
     out->found_start = c->win.file.found_start || !c->win.announced.starts_mid;
     out->head_len = c->win.announced.starts_mid ? c->win.file.head_len : 0u;

@@ -1,4 +1,4 @@
-// The window pipeline's state (windows.hip; bzip2_decode.hip and split.hip work on it too), in three parts by how long they
+// The window pipeline's state (windows.hip; the streamed codecs' decoders and split.hip work on it too), in three parts by how long they
 // live: what the context keeps (buffers, streams, events), what the caller announces for the next file, and the file's own
 // state, which is reset in one place.  Included by context.h (DevBuf, PinBuf).
 #pragma once
@@ -144,21 +144,41 @@ struct WindowPipeline {
         bool found_start = false;   // a range that starts inside the file: its first window holds a record start (false: all head)
         bool has_first = false;     // `first` holds the name of the range's first record (decoded in any window)
         uint64_t head_len = 0;
-        // bzip2 SAM, the host's side: the compressed bytes not decoded yet (file offset `base` on; the next bit to read),
-        // the stream being read (its level, combined CRC so far), the decoded bytes still to skip; the block magics found
-        // in them (bit offsets into pend, in order) and the next one to look at; the blocks of the last batch decoded and
-        // not yet written into a window
-        struct Bzip2 {
-            bool on = false;
+        // a streamed codec's SAM (bzip2, gzip, zstd: the file's bytes as they lie in it, decoded here), what every codec
+        // keeps on the host: the compressed bytes not decoded yet (file offset `base` on; `bit`: the next bit to read --
+        // zstd reads at bytes), the decoded bytes still to skip (the header)
+        enum class Codec : uint8_t { None, Bzip2, Gzip, Zstd };
+        struct Stream {
+            Codec codec = Codec::None;
             std::vector<uint8_t> pend;
             uint64_t base = 0, bit = 0;
+            uint64_t skip_left = 0;
+            bool waiting = false;   // the codec stopped for want of bytes: nothing to decode until pend grows
+            // bzip2, gzip: the block candidates found in pend (bit offsets, in order); found: cand holds those of pend as
+            // it is, and the device has pend's bytes (zstd sends a round's bytes with every round: never set)
+            std::vector<uint64_t> cand;
+            bool found = false;
+            // What the rounds so far have read goes; the bit to read next stays in the first byte.  Once per round, at its
+            // start, and only while the device does not hold pend (windows.hip: push_stream)
+            void drop_read() {
+                const size_t drop = static_cast<size_t>(bit >> 3);
+                pend.erase(pend.begin(), pend.begin() + static_cast<long>(drop));
+                base += drop;
+                bit -= drop * 8u;
+            }
+            // the decoded bytes of `text` that are still header: skipped, and counted off
+            uint64_t skip_of(uint64_t text) {
+                const uint64_t drop = std::min(text, skip_left);
+                skip_left -= drop;
+                return drop;
+            }
+        } stream;
+        // bzip2 SAM, the host's side: the stream being read (its level, combined CRC so far), the next candidate to look
+        // at; the blocks of the last batch decoded and not yet written into a window
+        struct Bzip2 {
             bool in_stream = false;
             uint32_t level = 0, combined = 0, streams = 0;
-            uint64_t skip_left = 0;
-            std::vector<uint64_t> cand;
             size_t next_cand = 0;
-            bool found = false;     // cand holds the magics of pend as it is
-            bool waiting = false;   // the chain stopped for want of bytes: nothing to decode until pend grows
             uint32_t slots = 0;     // blocks a batch decodes at most (the scratch holds that many; sized per file: bz2_reserve)
             struct Ready {
                 uint32_t slot, crc;
@@ -190,31 +210,19 @@ struct WindowPipeline {
                 uint64_t eos_at = 0;
             } chain;
         } bz2;
-        // gzip SAM, the host's side: the compressed bytes not decoded yet (file offset `base` on; `bit`: the next bit to
-        // read, an exact start), where in a member that is, the member's CRC register and length so far, the decoded bytes
-        // still to skip; the block candidates found in pend as it is; the chain's chunks of the round at hand
+        // gzip SAM, the host's side: where in a member stream.bit (an exact start) is, the member's CRC register and length
+        // so far; the chain's chunks of the round at hand
         struct Gzip {
-            bool on = false;
-            std::vector<uint8_t> pend;
-            uint64_t base = 0, bit = 0;
             enum Stage { Header, Deflate, Trailer } stage = Header;
             uint32_t crc = 0xffffffffu;
             uint64_t len = 0;
-            uint64_t skip_left = 0;
-            std::vector<uint64_t> cand;
-            bool found = false;      // cand holds the candidates of pend as it is (and the device has pend's bytes)
-            bool waiting = false;    // nothing to decode until pend grows
             bool carried = false;    // slot 0 of the window scratch holds the last 32 768 bytes of the text so far
             std::vector<gz::Chunk> ready;
         } gz;
-        // zstd SAM, the host's side: the compressed bytes not decoded yet (file offset `base` on; `pos`: the next byte to
-        // read), where in a frame that is and what the frame's blocks hand on (the descriptions a block may repeat, the
-        // repeat offsets, the text's length and XXH64 so far), the decoded bytes still to skip, the bytes of history the
-        // device holds; the blocks and frames of the round at hand
+        // zstd SAM, the host's side: where in a frame stream.bit is and what the frame's blocks hand on (the descriptions a
+        // block may repeat, the repeat offsets, the text's length and XXH64 so far), the bytes of history the device holds;
+        // the blocks and frames of the round at hand
         struct Zstd {
-            bool on = false;
-            std::vector<uint8_t> pend;
-            uint64_t base = 0, pos = 0;
             enum Stage { Between, Blocks, Checksum } stage = Between;
             zs::FrameHeader fh{};
             uint64_t frame_at = 0, frame_len = 0;
@@ -222,9 +230,7 @@ struct WindowPipeline {
             uint32_t rep[3] = {1, 4, 8};
             zs::Xxh64 xxh{};
             uint64_t any_frames = 0;
-            uint64_t skip_left = 0;
             uint64_t hist_len = 0;
-            bool waiting = false;
             struct Frame {   // a frame with blocks in the round
                 uint32_t first = 0, n = 0;   // its blocks of the round
                 bool ends = false, has_sum = false;
@@ -275,33 +281,41 @@ int fetch_q18(slimm_ctx* c);   // the Q18 run counts of the device decoders so f
 // `n` bytes at `src` (on device src_device) as one more window behind the closed file's carry (split.hip); end_line: one
 // newline instead
 int append_window(slimm_ctx* c, const uint8_t* src, int src_device, uint64_t n, bool final, uint64_t& n_rec, bool end_line = false);
-// bzip2_decode.hip (slimm_push_bzip2_sam_bytes): the next batch of whole blocks of file.bz2.pend decoded up to their text
-// lengths (file.bz2.ready; none: the chain waits for more bytes, or the streams have ended); at `last` what is left must
-// end the streams.  Then, window by window: the text bytes of the next ready blocks that fit in `cap` (at least one
-// block), and those written to dst on the context's stream, their CRCs checked, *last_byte = the text's last byte
+// What a streamed codec supplies to the pipeline (windows.hip: kCodecs, push_stream), all on file.stream and the codec's own
+// state.  round: what can be decoded of stream.pend, up to its text lengths; at `last` what is left must end the streams
+// (nothing ready: the bytes wait for more -- stream.waiting --, or the streams have ended).  next_window: is anything
+// ready, and *n the text bytes of the next window, at most `cap` where a round's text is cut into several (and at least
+// one block).  emit: those written to dst on the context's stream behind what is still to skip of the header (*n_out
+// bytes, *last_byte the last of them), their checksums checked.  trace_file: SLIMM_TRACE=push, the file's counters.
+//
+// bzip2_decode.hip (slimm_push_bzip2_sam_bytes): a round is the next batch of whole blocks, found by their magics and chained
+// from the stream header on; a batch's text is cut into windows block by block
 int bz2_decode_batch(slimm_ctx* c, bool last);
-uint64_t bz2_window_bytes(const slimm_ctx* c, uint64_t cap, size_t* n_blocks);
-int bz2_emit(slimm_ctx* c, uint8_t* dst, size_t n_blocks, uint8_t* last_byte);
+bool bz2_next_window(const slimm_ctx* c, uint64_t cap, uint64_t* n);
+int bz2_emit(slimm_ctx* c, uint8_t* dst, uint64_t cap, uint64_t* n_out, uint8_t* last_byte);
 void bz2_trace_file(const slimm_ctx* c);
-// gzip_decode.hip (slimm_push_gzip_sam_bytes): the member headers and trailers at file.gz.bit read on the host; then one
+// gzip_decode.hip (slimm_push_gzip_sam_bytes): the member headers and trailers at stream.bit read on the host; then one
 // round on the device -- candidates found, chunk starts chosen, the size pass, the chain from the exact start -- which
-// leaves the chain's chunks in file.gz.ready (none: the bytes wait for more, or the members have ended); at `last` what is
-// left must end the members.  Then gz_emit: the chunks decoded, resolved and written to dst behind each other (the
-// header's bytes dropped; *n_out bytes), their members' CRC registers and lengths stepped
+// leaves the chain's chunks in file.gz.ready.  gz_emit: the chunks decoded, resolved and written behind each other, their
+// members' CRC registers and lengths stepped
 int gz_round(slimm_ctx* c, bool last);
-uint64_t gz_ready_bytes(const slimm_ctx* c);   // text bytes of file.gz.ready behind what is still to skip
-int gz_emit(slimm_ctx* c, uint8_t* dst, uint64_t* n_out, uint8_t* last_byte);
-void gz_trace_file(const slimm_ctx* c);   // SLIMM_TRACE=push (read at every call): the file's streams, blocks, false magics, times
-
-// zstd_decode.hip (slimm_push_zstd_sam_bytes): zs_round plans the whole blocks of file.zst.pend (frame and block headers
+bool gz_next_window(const slimm_ctx* c, uint64_t cap, uint64_t* n);
+int gz_emit(slimm_ctx* c, uint8_t* dst, uint64_t cap, uint64_t* n_out, uint8_t* last_byte);
+void gz_trace_file(const slimm_ctx* c);
+// zstd_decode.hip (slimm_push_zstd_sam_bytes): zs_round plans the whole blocks of stream.pend (frame and block headers
 // walked on the host), decodes their literals and sequences on the device and leaves the round's blocks, with their text
-// lengths, in file.zst.ready (none: the bytes wait for more, or the frames have ended); at `last` what is left must end the
-// frames.  Then zs_emit: the text built behind the history, resolved, and written to dst (the header's bytes dropped;
-// *n_out bytes); zs_check, behind the window's launch: the content checksums of the frames that ended
+// lengths, in file.zst.ready.  zs_emit: the text built behind the history, resolved, and written to dst; zs_check, behind
+// the window's launch: the content checksums of the frames that ended
 int zs_round(slimm_ctx* c, bool last);
-uint64_t zs_ready_bytes(const slimm_ctx* c);
-int zs_emit(slimm_ctx* c, uint8_t* dst, uint64_t* n_out, uint8_t* last_byte);
+bool zs_next_window(const slimm_ctx* c, uint64_t cap, uint64_t* n);
+int zs_emit(slimm_ctx* c, uint8_t* dst, uint64_t cap, uint64_t* n_out, uint8_t* last_byte);
 int zs_check(slimm_ctx* c);
 void zs_trace_file(const slimm_ctx* c);
+// the decoders' shared steps (windows.hip).  stream.pend to the device, into `comp` with `tail` zeroed bytes behind it.
+// The candidates a find kernel left at d_cand, counted at count[0]: `launch(cap)` runs it with room for cap of them, again
+// with more room when there were more; *got of them are there (and the stream is idle)
+int stream_upload(slimm_ctx* c, DevBuf<uint8_t>& comp, uint64_t tail);
+int stream_candidates(slimm_ctx* c, DevBuf<unsigned long long>& d_cand, DevBuf<uint32_t>& count, uint32_t cap, const std::function<void(uint32_t)>& launch,
+                      uint32_t* got);
 
 }  // namespace slimm

@@ -1,11 +1,12 @@
 // The window pipeline (include/slimm_hip.h: slimm_push_bam_bytes, _bgzf_blocks, _sam_bytes, _bgzf_sam_blocks, _bzip2_sam_bytes,
 // _gzip_sam_bytes, _zstd_sam_bytes): a file's bytes -- inflated BAM records, whole BGZF blocks of them, SAM text, BGZF blocks of SAM
-// text, bzip2, gzip or zstd SAM text -- cross the bus in windows; the device inflates (bgzf_tokens.hip, bgzf_inflate.hip,
-// gzip_decode.hip) or decodes (bzip2_decode.hip, zstd_decode.hip) them, finds the
+// text, SAM text in a streamed codec (bzip2, gzip, zstd) -- cross the bus in windows; the device inflates (bgzf_tokens.hip,
+// bgzf_inflate.hip) or decodes (the codecs: bzip2_decode.hip, gzip_decode.hip, zstd_decode.hip) them, finds the
 // records (bam_decode.hip, sam_decode.hip) and appends them to the context's record stream.  Its state: windows.h.
 // Replaces seqan::BamFileIn + readRecord of the reference (src/misc.hpp:498-522, src/slimm.hpp:194-208).
-// A push's steps (push_window): check_push, open_file; one of five sources fills window buffers -- push_bzip2, push_gzip, push_zstd, gather_blocks
-// (+ launch_gathered), push_plain --, each window handed over by submit_window; finish_windows; release_callers_buffer.
+// A push's steps (push_window): check_push, open_file; one of three sources fills window buffers -- push_stream (a streamed
+// codec: kCodecs says what each supplies), gather_blocks (+ launch_gathered), push_plain --, each window handed over by
+// submit_window; finish_windows; release_callers_buffer.
 // A window is copied when it is pushed and WORKED ON when the next one is pushed (or at once, when it is the last): its
 // host-to-device copy then runs beside the kernels and the host's bookkeeping of the window before it -- the copies are
 // what bounds this path (192 MB at 54 GB/s: 3.6 ms; kernels + one synchronisation per window: 0.8 ms).
@@ -49,7 +50,7 @@ int WindowPipeline::end_file(slimm_ctx* c) {
         if (c->copy_stream) HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
     }
     free_outgrown();
-    // (bzip2 SAM: the next file sizes its own decode scratch; what the host held of this one's bytes goes)
+    // (a streamed codec: the next file sizes its own decode scratch; what the host held of this one's bytes goes)
     file = File{};
     announced = Announced{};
     if (held_bytes() > kWindowKeepAcrossFiles) {   // (a large file's windows: the next file sizes its own)
@@ -82,6 +83,7 @@ void WindowPipeline::destroy() {
 namespace {
 
 using File = WindowPipeline::File;
+using Codec = File::Codec;
 constexpr uint32_t kRing = WindowPipeline::kWindowRing;
 
 // ---- a window is finished.  First, what differs between a window of BAM records and one of SAM lines
@@ -305,23 +307,52 @@ int add_last_newline(slimm_ctx* c, uint64_t at, hipStream_t st) {   // at: bytes
 
 // ---- a push
 enum { kFormatBam = 0, kFormatBgzf = 1, kFormatSam = 2, kFormatBgzfSam = 3, kFormatBzip2Sam = 4, kFormatGzipSam = 5, kFormatZstdSam = 6 };
-// bzip2 SAM: compressed bytes gathered on the host before their blocks are looked for and decoded (a round; the command's
-// pushes are larger, the ABI's may be of any size)
-constexpr uint64_t kBzip2Round = 32ull << 20;
-constexpr uint64_t kGzipRound = 32ull << 20;   // (gzip SAM: the same; SLIMM_FORCE gzip_round=N)
-constexpr uint64_t kZstdRound = 32ull << 20;   // (zstd SAM: the same; SLIMM_FORCE zstd_round=N)
+
+// What a streamed codec supplies (windows.h: the hooks' contracts), by File::Codec
+struct StreamCodec {
+    const char* name;        // traces and error texts
+    // compressed bytes gathered on the host before a round looks at them (the command's pushes are larger, the ABI's may be
+    // of any size); SLIMM_FORCE <round_key>=N: rounds of N bytes -- tests cut blocks, headers and trailers across rounds
+    const char* round_key;
+    uint64_t round_bytes;
+    bool cut_by_range;       // a byte range of a split file may cut it (slimm_set_input_mid_file)
+    int (*round)(slimm_ctx*, bool last);
+    bool (*next_window)(const slimm_ctx*, uint64_t cap, uint64_t* n);
+    int (*emit)(slimm_ctx*, uint8_t* dst, uint64_t cap, uint64_t* n_out, uint8_t* last_byte);
+    int (*behind_submit)(slimm_ctx*);   // on the host, beside the window's decode -- also behind a round of no text (or null)
+    void (*trace_file)(const slimm_ctx*);
+    // where between its streams the codec is: a push's rounds go on while the file offset or this moves, and stop when the
+    // codec waits for bytes (null: they go on while a round leaves something ready)
+    int (*stage)(const File&);
+    bool (*ended)(const File&);   // the codec has stopped for good: bytes pushed now are dropped (or null)
+    // its counters (they outlive the file: slimm_get_*_stats), how many, and which of them counts the compressed bytes
+    uint64_t* (*stats)(WindowPipeline&);
+    size_t n_stats, stat_compressed;
+};
+const StreamCodec kCodecs[] = {
+    {},
+    // (ended: the range's chain has stopped, what comes now are bytes of the slack)
+    {"bzip2", "bzip2_round", 32ull << 20, true, bz2_decode_batch, bz2_next_window, bz2_emit, nullptr, bz2_trace_file, nullptr,
+     [](const File& F) { return F.bz2.chain.ended; }, nullptr, 0, 0},
+    {"gzip", "gzip_round", 32ull << 20, false, gz_round, gz_next_window, gz_emit, nullptr, gz_trace_file,
+     [](const File& F) { return static_cast<int>(F.gz.stage); }, nullptr, [](WindowPipeline& W) { return W.gz_stats; },
+     WindowPipeline::kGzStats, WindowPipeline::kGzCompressed},
+    {"zstd", "zstd_round", 32ull << 20, false, zs_round, zs_next_window, zs_emit, zs_check, zs_trace_file,
+     [](const File& F) { return static_cast<int>(F.zst.stage); }, nullptr, [](WindowPipeline& W) { return W.zs_stats; },
+     WindowPipeline::kZsStats, WindowPipeline::kZsCompressedBytes},
+};
+const StreamCodec& codec_of(Codec k) { return kCodecs[static_cast<size_t>(k)]; }
 
 struct Push {
     const uint8_t* bytes;
     uint64_t src_bytes, n_bytes;   // what crosses the bus; the push's record bytes (text bytes)
-    uint32_t skip;                 // inflated (bzip2: decoded) bytes in front of the file's first record
-    bool last, sam, bzip2;
+    uint32_t skip;                 // inflated (a streamed codec: decoded) bytes in front of the file's first record
+    bool last, sam;
+    Codec codec;                   // a streamed codec's SAM: the file's bytes, decoded here
     bool compressed;               // BGZF blocks to inflate here: their descriptors, their inflated bytes
     std::vector<BgzfBlock> blocks = {};
     uint64_t inflated = 0;
     bool copy_started = false;     // this push started a copy from the caller's buffer
-    bool gzip = false;             // gzip SAM: the file's bytes, inflated here
-    bool zstd = false;             // zstd SAM: the file's bytes, decoded here
 };
 
 // BGZF blocks: their descriptors; the blocks in front of the file's first record dropped, `skip` what is left of them
@@ -361,19 +392,15 @@ int check_push(slimm_ctx* c, Push& p) {
     const File& F = c->win.file;
     if (p.sam && !c->win.sam_mask) return fail(c, SLIMM_E_INVALID, "slimm_set_reference_names first: SAM text names its references");
     if (F.active && F.sam != p.sam) return fail(c, SLIMM_E_INVALID, "SAM text and BAM bytes do not mix within a file");
-    if (F.active && F.bz2.on != p.bzip2)
-        return fail(c, SLIMM_E_INVALID, "bzip2 SAM bytes and the other forms do not mix within a file");
-    if (F.active && F.gz.on != p.gzip)
-        return fail(c, SLIMM_E_INVALID, "gzip SAM bytes and the other forms do not mix within a file");
-    if (p.gzip && (c->win.announced.starts_mid || c->win.announced.ends_mid))
-        return fail(c, SLIMM_E_INVALID, "a gzip stream is not cut by byte range");
-    if (F.active && F.zst.on != p.zstd)
-        return fail(c, SLIMM_E_INVALID, "zstd SAM bytes and the other forms do not mix within a file");
-    if (p.zstd && (c->win.announced.starts_mid || c->win.announced.ends_mid))
-        return fail(c, SLIMM_E_INVALID, "a zstd stream is not cut by byte range");
-    if ((p.bzip2 || p.gzip || p.zstd) && p.skip && F.active) return fail(c, SLIMM_E_INVALID, "skip: only in front of a file's first records");
-    if (p.bzip2 && !F.active && (c->win.announced.starts_mid || c->win.announced.ends_mid) && !c->win.announced.has_range)
-        return fail(c, SLIMM_E_INVALID, "slimm_set_input_range first: a range of a bzip2 file is cut at bits, told by where it lies in the file");
+    const Codec mine = F.stream.codec, named = mine == Codec::None ? p.codec : p.codec == Codec::None ? mine : std::min(mine, p.codec);
+    const StreamCodec& K = codec_of(p.codec);
+    const bool mid = c->win.announced.starts_mid || c->win.announced.ends_mid;
+    if (F.active && mine != p.codec)   // (two codecs: the text names the first of them in Codec's order)
+        return fail(c, SLIMM_E_INVALID, "%s SAM bytes and the other forms do not mix within a file", codec_of(named).name);
+    if (K.name && !K.cut_by_range && mid) return fail(c, SLIMM_E_INVALID, "a %s stream is not cut by byte range", K.name);
+    if (K.name && p.skip && F.active) return fail(c, SLIMM_E_INVALID, "skip: only in front of a file's first records");
+    if (K.name && K.cut_by_range && !F.active && mid && !c->win.announced.has_range)
+        return fail(c, SLIMM_E_INVALID, "slimm_set_input_range first: a range of a %s file is cut at bits, told by where it lies in the file", K.name);
     SLIMM_TRY(trim_bgzf_push(c, p));
     if (c->device < 0) return fail(c, SLIMM_E_INVALID, "host-only context has no record stream");
     if (p.n_bytes && !p.bytes) return fail(c, SLIMM_E_INVALID, "null byte buffer");
@@ -394,15 +421,11 @@ int open_file(slimm_ctx* c, const Push& p) {
     const bool marked = c->order == SLIMM_ORDER_GROUPED;
     W.file.active = true;
     W.file.sam = p.sam;
-    W.file.bz2.on = p.bzip2;
-    W.file.bz2.skip_left = p.bzip2 ? p.skip : 0u;
-    W.file.gz.on = p.gzip;
-    W.file.gz.skip_left = p.gzip ? p.skip : 0u;
-    if (p.gzip) std::fill(W.gz_stats, W.gz_stats + WindowPipeline::kGzStats, 0ull);
-    W.file.zst.on = p.zstd;
-    W.file.zst.skip_left = p.zstd ? p.skip : 0u;
-    if (p.zstd) std::fill(W.zs_stats, W.zs_stats + WindowPipeline::kZsStats, 0ull);
-    if (p.bzip2 && W.announced.has_range) W.file.bz2.base = W.announced.range_begin;   // (errors name the file's bytes)
+    const StreamCodec& K = codec_of(p.codec);
+    W.file.stream.codec = p.codec;
+    W.file.stream.skip_left = K.name ? p.skip : 0u;
+    if (K.stats) std::fill(K.stats(W), K.stats(W) + K.n_stats, 0ull);
+    if (K.cut_by_range && W.announced.has_range) W.file.stream.base = W.announced.range_begin;   // (errors name the file's bytes)
     c->marked = marked;
     c->has_check = !marked;
     c->packed = false;
@@ -416,134 +439,52 @@ int open_file(slimm_ctx* c, const Push& p) {
     return SLIMM_OK;
 }
 
-// bzip2: the bytes wait on the host until a round's worth has come (or the file ends); then the blocks are decoded batch by
-// batch (bzip2_decode.hip), and each batch's text becomes windows of its own
-int push_bzip2(slimm_ctx* c, const Push& p, uint64_t& total) {
+// A streamed codec: the bytes wait on the host until a round's worth has come (or the file ends); then round by round what
+// can be decoded of them is (the codec's decoder), and each round's text becomes a window of its own -- or several, where
+// the codec cuts it (bzip2: a batch of blocks)
+int push_stream(slimm_ctx* c, const Push& p, uint64_t& total) {
     WindowPipeline& W = c->win;
     File& F = W.file;
+    File::Stream& S = F.stream;
+    const StreamCodec& K = codec_of(p.codec);
     hipStream_t st = c->stream;
-    if (p.n_bytes && !F.bz2.chain.ended) {   // (ended: the range's chain has stopped, these are bytes of the slack)
-        F.bz2.pend.insert(F.bz2.pend.end(), p.bytes, p.bytes + p.n_bytes);
-        F.bz2.found = F.bz2.waiting = false;
+    if (p.n_bytes && !(K.ended && K.ended(F))) {
+        S.pend.insert(S.pend.end(), p.bytes, p.bytes + p.n_bytes);
+        S.found = S.waiting = false;
+        if (K.stats) K.stats(W)[K.stat_compressed] += p.n_bytes;
     }
-    long round = 0;   // (SLIMM_FORCE bzip2_round=N: rounds of N bytes -- tests cut blocks across rounds with small files)
-    if (!forced("bzip2_round", &round) || round <= 0) round = static_cast<long>(kBzip2Round);
-    const bool decode_now = p.last || F.bz2.pend.size() - (F.bz2.bit >> 3) >= static_cast<uint64_t>(round);
+    long round = 0;
+    if (!forced(K.round_key, &round) || round <= 0) round = static_cast<long>(K.round_bytes);
+    const bool decode_now = p.last || S.pend.size() - (S.bit >> 3) >= static_cast<uint64_t>(round);
     while (decode_now) {
-        SLIMM_TRY(bz2_decode_batch(c, p.last));
-        if (F.bz2.ready.empty()) break;
-        while (F.bz2.ready_pos < F.bz2.ready.size()) {
-            size_t nblk = 0;
-            const uint64_t n = bz2_window_bytes(c, WindowPipeline::kWindowGather, &nblk);
+        // (the one moment the bytes read so far go: a round's start, unless the device holds pend as it is and the round
+        // goes on in those bytes)
+        if (!S.found) S.drop_read();
+        const uint64_t at0 = S.base * 8u + S.bit;
+        const int stage0 = K.stage ? K.stage(F) : 0;
+        SLIMM_TRY(K.round(c, p.last));
+        uint64_t n = 0;
+        bool any = false;
+        for (; K.next_window(c, WindowPipeline::kWindowGather, &n); any = true) {
             SLIMM_TRY(window_buffer(c, n + 1u));
             uint8_t lb = '\n';
-            SLIMM_TRY(bz2_emit(c, W.bytes[next_buffer(F)].p + kBamSlack, nblk, &lb));
-            if (!n) continue;   // (blocks of header only)
-            F.sam_last_byte = lb;
-            SLIMM_TRY(submit_window(c, n, st, false));
-            push_trace("window %llu: %zu bzip2 blocks -> %.1f MB of text", (unsigned long long)(F.windows - 1), nblk, n / 1e6);
-            SLIMM_TRY(finish_windows(c, Upto::Lag, false, false, total));
-        }
-    }
-    if (lacks_last_newline(c, p.last)) {   // (in a window of its own)
-        SLIMM_TRY(window_buffer(c, 1u));
-        SLIMM_TRY(add_last_newline(c, 0, st));
-        SLIMM_TRY(submit_window(c, 1, st, false));
-    }
-    if (p.last) bz2_trace_file(c);
-    return SLIMM_OK;
-}
-
-// gzip: as bzip2 -- the bytes wait on the host until a round's worth has come (or the file ends); then round by round
-// (gzip_decode.hip) what can be decoded of them is, and each round's text becomes a window of its own
-int push_gzip(slimm_ctx* c, const Push& p, uint64_t& total) {
-    WindowPipeline& W = c->win;
-    File& F = W.file;
-    File::Gzip& Z = F.gz;
-    hipStream_t st = c->stream;
-    if (p.n_bytes) {   // (what the rounds so far have read goes; the bit to read next stays in the first byte)
-        const size_t drop = static_cast<size_t>(Z.bit >> 3);
-        Z.pend.erase(Z.pend.begin(), Z.pend.begin() + static_cast<long>(drop));
-        Z.base += drop;
-        Z.bit -= drop * 8u;
-        Z.pend.insert(Z.pend.end(), p.bytes, p.bytes + p.n_bytes);
-        Z.found = Z.waiting = false;
-        W.gz_stats[WindowPipeline::kGzCompressed] += p.n_bytes;
-    }
-    long round = 0;   // (SLIMM_FORCE gzip_round=N: rounds of N bytes -- tests cut blocks, headers and trailers across rounds)
-    if (!forced("gzip_round", &round) || round <= 0) round = static_cast<long>(kGzipRound);
-    const bool decode_now = p.last || Z.pend.size() - (Z.bit >> 3) >= static_cast<uint64_t>(round);
-    while (decode_now) {
-        const uint64_t bit0 = Z.bit;
-        const auto stage0 = Z.stage;
-        SLIMM_TRY(gz_round(c, p.last));
-        if (!Z.ready.empty()) {
-            const uint64_t room = gz_ready_bytes(c);
-            SLIMM_TRY(window_buffer(c, room + 1u));
-            uint64_t n = 0;
-            uint8_t lb = '\n';
-            SLIMM_TRY(gz_emit(c, W.bytes[next_buffer(F)].p + kBamSlack, &n, &lb));
-            if (n) {
+            SLIMM_TRY(K.emit(c, W.bytes[next_buffer(F)].p + kBamSlack, WindowPipeline::kWindowGather, &n, &lb));
+            if (n) {   // (none: a round of header only)
                 F.sam_last_byte = lb;
                 SLIMM_TRY(submit_window(c, n, st, false));
-                push_trace("window %llu: %.1f MB of text from gzip", (unsigned long long)(F.windows - 1), n / 1e6);
-                SLIMM_TRY(finish_windows(c, Upto::Lag, false, false, total));
+                push_trace("window %llu: %.1f MB of text from %s", (unsigned long long)(F.windows - 1), n / 1e6, K.name);
             }
-        }
-        if (Z.waiting || (Z.bit == bit0 && Z.stage == stage0)) break;
-    }
-    if (lacks_last_newline(c, p.last)) {   // (in a window of its own)
-        SLIMM_TRY(window_buffer(c, 1u));
-        SLIMM_TRY(add_last_newline(c, 0, st));
-        SLIMM_TRY(submit_window(c, 1, st, false));
-    }
-    if (p.last) gz_trace_file(c);
-    return SLIMM_OK;
-}
-
-// zstd: as gzip -- the bytes wait on the host until a round's worth has come (or the file ends); then round by round
-// (zstd_decode.hip) the whole blocks among them are decoded, and each round's text becomes a window of its own
-int push_zstd(slimm_ctx* c, const Push& p, uint64_t& total) {
-    WindowPipeline& W = c->win;
-    File& F = W.file;
-    File::Zstd& Z = F.zst;
-    hipStream_t st = c->stream;
-    if (p.n_bytes) {   // (what the rounds so far have read goes)
-        Z.pend.erase(Z.pend.begin(), Z.pend.begin() + static_cast<long>(Z.pos));
-        Z.base += Z.pos;
-        Z.pos = 0;
-        Z.pend.insert(Z.pend.end(), p.bytes, p.bytes + p.n_bytes);
-        Z.waiting = false;
-        W.zs_stats[WindowPipeline::kZsCompressedBytes] += p.n_bytes;
-    }
-    long round = 0;   // (SLIMM_FORCE zstd_round=N: rounds of N bytes -- tests cut headers, blocks and checksums across rounds)
-    if (!forced("zstd_round", &round) || round <= 0) round = static_cast<long>(kZstdRound);
-    const bool decode_now = p.last || Z.pend.size() - Z.pos >= static_cast<uint64_t>(round);
-    while (decode_now) {
-        const uint64_t at0 = Z.base + Z.pos;   // (the file offset read so far: zs_round drops from pend what it has read)
-        const auto stage0 = Z.stage;
-        SLIMM_TRY(zs_round(c, p.last));
-        if (!Z.ready.empty()) {
-            SLIMM_TRY(window_buffer(c, zs_ready_bytes(c) + 1u));
-            uint64_t n = 0;
-            uint8_t lb = '\n';
-            SLIMM_TRY(zs_emit(c, W.bytes[next_buffer(F)].p + kBamSlack, &n, &lb));
-            if (n) {
-                F.sam_last_byte = lb;
-                SLIMM_TRY(submit_window(c, n, st, false));
-                push_trace("window %llu: %.1f MB of text from zstd", (unsigned long long)(F.windows - 1), n / 1e6);
-            }
-            SLIMM_TRY(zs_check(c));   // (on the host, beside the window's decode)
+            if (K.behind_submit) SLIMM_TRY(K.behind_submit(c));
             if (n) SLIMM_TRY(finish_windows(c, Upto::Lag, false, false, total));
         }
-        if (Z.waiting || (Z.base + Z.pos == at0 && Z.stage == stage0)) break;
+        if (K.stage ? S.waiting || (S.base * 8u + S.bit == at0 && K.stage(F) == stage0) : !any) break;
     }
     if (lacks_last_newline(c, p.last)) {   // (in a window of its own)
         SLIMM_TRY(window_buffer(c, 1u));
         SLIMM_TRY(add_last_newline(c, 0, st));
         SLIMM_TRY(submit_window(c, 1, st, false));
     }
-    if (p.last) zs_trace_file(c);
+    if (p.last) K.trace_file(c);
     return SLIMM_OK;
 }
 
@@ -712,16 +653,14 @@ int release_callers_buffer(slimm_ctx* c, const Push& p) {
     return SLIMM_OK;
 }
 
-// A window of a file's bytes in one of the five forms: record bytes (`bytes` are BAM records or SAM text), whole BGZF blocks
-// of them (the first `skip` inflated bytes are not records), bzip2-compressed SAM text.
+// A window of a file's bytes in one of the seven forms: record bytes (`bytes` are BAM records or SAM text), whole BGZF blocks
+// of them (the first `skip` inflated bytes are not records), SAM text in a streamed codec.
 int push_window(slimm_ctx* c, const uint8_t* bytes, uint64_t src_bytes, int format, uint32_t skip, int last, uint64_t* n_records) {
     if (!c) return SLIMM_E_INVALID;
     if (n_records) *n_records = 0;
-    const bool sam = format == kFormatSam || format == kFormatBgzfSam || format == kFormatBzip2Sam || format == kFormatGzipSam ||
-                     format == kFormatZstdSam;
-    Push p{bytes, src_bytes, src_bytes, skip, last != 0, sam, format == kFormatBzip2Sam, format == kFormatBgzf || format == kFormatBgzfSam};
-    p.gzip = format == kFormatGzipSam;
-    p.zstd = format == kFormatZstdSam;
+    const Codec codec = format == kFormatBzip2Sam ? Codec::Bzip2 : format == kFormatGzipSam ? Codec::Gzip : format == kFormatZstdSam ? Codec::Zstd : Codec::None;
+    const bool sam = format == kFormatSam || format == kFormatBgzfSam || codec != Codec::None;
+    Push p{bytes, src_bytes, src_bytes, skip, last != 0, sam, codec, format == kFormatBgzf || format == kFormatBgzfSam};
     SLIMM_TRY(check_push(c, p));
     (void)hipSetDevice(c->device);
     HIP_TRY(c, need_stream(c->copy_stream, kStreamHigh));
@@ -730,12 +669,8 @@ int push_window(slimm_ctx* c, const uint8_t* bytes, uint64_t src_bytes, int form
     File& F = W.file;
     uint64_t total = 0;
     push_trace("push: %.0f MB %s -> %.0f MB%s", p.src_bytes / 1e6, p.compressed ? "of blocks" : "inflated", p.n_bytes / 1e6, p.last ? " (last)" : "");
-    if (p.bzip2)
-        SLIMM_TRY(push_bzip2(c, p, total));
-    else if (p.gzip)
-        SLIMM_TRY(push_gzip(c, p, total));
-    else if (p.zstd)
-        SLIMM_TRY(push_zstd(c, p, total));
+    if (p.codec != Codec::None)
+        SLIMM_TRY(push_stream(c, p, total));
     else if (p.n_bytes && p.compressed)
         SLIMM_TRY(gather_blocks(c, p, total));
     else if (p.n_bytes || (p.sam && p.last && !W.announced.ends_mid && (F.sam_last_byte != '\n' || F.sam_dev_tail)))
@@ -896,6 +831,28 @@ int slimm_set_reference_names(slimm_ctx* c, const char* const* names) {
 }  // extern "C"
 
 namespace slimm {
+
+int stream_upload(slimm_ctx* c, DevBuf<uint8_t>& comp, uint64_t tail) {
+    const std::vector<uint8_t>& pend = c->win.file.stream.pend;
+    const uint64_t n = pend.size();
+    if (comp.cap < n + tail) HIP_TRY(c, comp.ensure_later(n + (n >> 3) + tail, c->win.outgrown));
+    if (n) HIP_TRY(c, hipMemcpyAsync(comp.p, pend.data(), n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(comp.p + n, 0, tail, c->stream));
+    return SLIMM_OK;
+}
+
+int stream_candidates(slimm_ctx* c, DevBuf<unsigned long long>& d_cand, DevBuf<uint32_t>& count, uint32_t cap, const std::function<void(uint32_t)>& launch,
+                      uint32_t* got) {
+    for (;; cap = *got + (*got >> 2) + 256u) {   // (more than room: again, with room)
+        if (d_cand.cap < cap) HIP_TRY(c, d_cand.ensure_later(cap, c->win.outgrown));
+        HIP_TRY(c, hipMemsetAsync(count.p, 0, 4, c->stream));
+        launch(cap);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(got, count.p, 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (*got <= cap) return SLIMM_OK;
+    }
+}
 
 int fetch_q18(slimm_ctx* c) {
     WindowPipeline& W = c->win;

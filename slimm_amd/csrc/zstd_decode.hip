@@ -183,72 +183,76 @@ uint32_t grid_for(uint64_t n) { return static_cast<uint32_t>(std::max<uint64_t>(
 
 }  // namespace
 
-uint64_t zs_ready_bytes(const slimm_ctx* c) {
+bool zs_next_window(const slimm_ctx* c, uint64_t, uint64_t* n) {   // (a round's text is one window: kZsRoundText)
     const ZF& Z = c->win.file.zst;
-    return Z.text - std::min(Z.text, Z.skip_left);
+    *n = Z.text - std::min(Z.text, c->win.file.stream.skip_left);
+    return !Z.ready.empty();
 }
 
 int zs_round(slimm_ctx* c, bool last) {
     WindowPipeline& W = c->win;
     ZF& Z = W.file.zst;
+    WindowPipeline::File::Stream& T = W.file.stream;
     WindowPipeline::Zstd& S = W.zst;
     hipStream_t st = c->stream;
     uint64_t* stats = W.zs_stats;
     Z.ready.clear(), Z.ready_at.clear(), Z.frames.clear(), Z.aux.clear();
     Z.text = 0;
-    if (Z.waiting && !last) return SLIMM_OK;
-    Z.waiting = false;   // (at the file's end what waited for bytes is looked at again: it ends the frames, or is truncated)
-    if (Z.pos) {   // (what the rounds so far have read goes: a round copies to the device only what is still to decode)
-        Z.pend.erase(Z.pend.begin(), Z.pend.begin() + static_cast<long>(Z.pos));
-        Z.base += Z.pos;
-        Z.pos = 0;
-    }
+    if (T.waiting && !last) return SLIMM_OK;
+    T.waiting = false;   // (at the file's end what waited for bytes is looked at again: it ends the frames, or is truncated)
+    // (what the rounds so far have read is gone: a round copies to the device only what is still to decode.  zstd reads at
+    // bytes: `pos` is the stream's bit, put back however the round ends)
+    uint64_t pos = T.bit >> 3;
+    struct PutBack {
+        uint64_t &bit, &pos;
+        ~PutBack() { bit = pos * 8u; }
+    } put_back{T.bit, pos};
     long cap_text = 0;
     if (!forced("zstd_round_text", &cap_text) || cap_text <= 0) cap_text = static_cast<long>(kZsRoundText);
-    auto at = [&](uint64_t pos) { return std::to_string(Z.base + pos); };
+    auto at = [&](uint64_t byte) { return std::to_string(T.base + byte); };
     // what a stage lacks: more bytes may come, or the file ends inside it
     auto wait_or = [&](const std::string& where) {
         if (last) return zs_fail(c, where, zs::kRanOut);
-        Z.waiting = true;
+        T.waiting = true;
         return static_cast<int>(SLIMM_OK);
     };
     // ---- the plan
-    const uint64_t n_bytes = Z.pend.size(), aux_base = n_bytes + zs::kPad;
-    const uint8_t* p = Z.pend.data();
+    const uint64_t n_bytes = T.pend.size(), aux_base = n_bytes + zs::kPad;
+    const uint8_t* p = T.pend.data();
     uint64_t bound = 0, lit_bytes = 0, n_seq_slots = 0;
     bool full = false;
-    while (!full && !Z.waiting) {
-        const uint64_t avail = n_bytes - Z.pos;
+    while (!full && !T.waiting) {
+        const uint64_t avail = n_bytes - pos;
         if (Z.stage == Stage::Between) {
             if (avail == 0 && (Z.any_frames > 0 || !last)) {
-                Z.waiting = true;   // (the file may end here)
+                T.waiting = true;   // (the file may end here)
                 break;
             }
             if (avail < 4u) {
-                if (last) return zs_fail(c, "at byte " + at(Z.pos), Z.any_frames == 0 || zs::magic_prefix(p + Z.pos, avail) ? zs::kRanOut : zs::kNoFrame);
-                Z.waiting = true;
+                if (last) return zs_fail(c, "at byte " + at(pos), Z.any_frames == 0 || zs::magic_prefix(p + pos, avail) ? zs::kRanOut : zs::kNoFrame);
+                T.waiting = true;
                 break;
             }
-            const uint32_t magic = zs::le32(p + Z.pos);
+            const uint32_t magic = zs::le32(p + pos);
             if ((magic & 0xfffffff0u) == zs::kSkippable) {
-                if (avail < 8u || avail < 8ull + zs::le32(p + Z.pos + 4)) {
-                    SLIMM_TRY(wait_or("skippable frame at byte " + at(Z.pos)));
+                if (avail < 8u || avail < 8ull + zs::le32(p + pos + 4)) {
+                    SLIMM_TRY(wait_or("skippable frame at byte " + at(pos)));
                     break;
                 }
-                Z.pos += 8ull + zs::le32(p + Z.pos + 4);
+                pos += 8ull + zs::le32(p + pos + 4);
                 ++Z.any_frames;
                 ++stats[WindowPipeline::kZsSkippable];
                 continue;
             }
-            if (magic != zs::kMagic) return zs_fail(c, "at byte " + at(Z.pos), Z.any_frames ? zs::kNoFrame : zs::kRanOut);
-            const uint32_t hs = zs::frame_header(p + Z.pos, avail, Z.fh);
+            if (magic != zs::kMagic) return zs_fail(c, "at byte " + at(pos), Z.any_frames ? zs::kNoFrame : zs::kRanOut);
+            const uint32_t hs = zs::frame_header(p + pos, avail, Z.fh);
             if (hs == zs::kRanOut) {
-                SLIMM_TRY(wait_or("frame header at byte " + at(Z.pos)));
+                SLIMM_TRY(wait_or("frame header at byte " + at(pos)));
                 break;
             }
-            if (hs != zs::kOk) return zs_fail(c, "frame header at byte " + at(Z.pos), hs);
-            Z.frame_at = Z.base + Z.pos;
-            Z.pos += Z.fh.bytes;
+            if (hs != zs::kOk) return zs_fail(c, "frame header at byte " + at(pos), hs);
+            Z.frame_at = T.base + pos;
+            pos += Z.fh.bytes;
             Z.stage = Stage::Blocks;
             Z.frame_len = 0;
             Z.entropy.reset();
@@ -261,10 +265,10 @@ int zs_round(slimm_ctx* c, bool last) {
         }
         if (Z.stage == Stage::Checksum) {
             if (avail < 4u) {
-                SLIMM_TRY(wait_or("checksum at byte " + at(Z.pos)));
+                SLIMM_TRY(wait_or("checksum at byte " + at(pos)));
                 break;
             }
-            const uint32_t sum = zs::le32(p + Z.pos);
+            const uint32_t sum = zs::le32(p + pos);
             if (!Z.frames.empty() && Z.frames.back().ends) {   // (its last blocks are of this round: zs_check compares)
                 Z.frames.back().has_sum = true;
                 Z.frames.back().sum = sum;
@@ -272,17 +276,17 @@ int zs_round(slimm_ctx* c, bool last) {
                 if (sum != static_cast<uint32_t>(Z.xxh.digest())) return zs_fail(c, "frame at byte " + std::to_string(Z.frame_at), zs::kBadChecksum);
                 ++stats[WindowPipeline::kZsChecksums];
             }
-            Z.pos += 4u;
+            pos += 4u;
             Z.stage = Stage::Between;
             continue;
         }
         // a block
         if (avail < 3u) {
-            SLIMM_TRY(wait_or("block header at byte " + at(Z.pos)));
+            SLIMM_TRY(wait_or("block header at byte " + at(pos)));
             break;
         }
-        const uint32_t h = zs::le24(p + Z.pos), type = (h >> 1) & 3u, size = h >> 3;
-        const std::string where = "block at byte " + at(Z.pos);
+        const uint32_t h = zs::le24(p + pos), type = (h >> 1) & 3u, size = h >> 3;
+        const std::string where = "block at byte " + at(pos);
         if (type == 3u) return zs_fail(c, where, zs::kReservedBlock);
         if (size > Z.fh.block_max) return zs_fail(c, where, zs::kBlockTooLarge);
         const uint64_t content = type == zs::kRleBlock ? 1u : size;
@@ -296,7 +300,7 @@ int zs_round(slimm_ctx* c, bool last) {
             break;
         }
         zs::Block b{};
-        b.at = Z.pos + 3u, b.size = static_cast<uint32_t>(content), b.type = type, b.max = Z.fh.block_max, b.regen = size;
+        b.at = pos + 3u, b.size = static_cast<uint32_t>(content), b.type = type, b.max = Z.fh.block_max, b.regen = size;
         b.window = static_cast<uint32_t>(Z.fh.window);
         b.status = zs::kOk;
         b.rep[0] = zs::sym(0), b.rep[1] = zs::sym(1), b.rep[2] = zs::sym(2);
@@ -320,9 +324,9 @@ int zs_round(slimm_ctx* c, bool last) {
         b.frame = static_cast<uint32_t>(Z.frames.size() - 1u);
         ++Z.frames.back().n;
         Z.ready.push_back(b);
-        Z.ready_at.push_back(Z.base + Z.pos);
+        Z.ready_at.push_back(T.base + pos);
         bound += most;
-        Z.pos += 3u + content;
+        pos += 3u + content;
         if (h & 1u) {
             Z.frames.back().ends = true;
             Z.stage = Z.fh.has_checksum ? Stage::Checksum : Stage::Between;
@@ -337,8 +341,7 @@ int zs_round(slimm_ctx* c, bool last) {
     if (S.lit.cap < lit_bytes + 1u) HIP_TRY(c, S.lit.ensure_later(lit_bytes + (lit_bytes >> 3) + 1u, W.outgrown));
     if (S.seq.cap < n_seq_slots + 1u) HIP_TRY(c, S.seq.ensure_later(n_seq_slots + (n_seq_slots >> 3) + 1u, W.outgrown));
     HIP_TRY(c, S.count.ensure(8));
-    HIP_TRY(c, hipMemcpyAsync(S.comp.p, p, n_bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemsetAsync(S.comp.p + n_bytes, 0, zs::kPad, st));
+    SLIMM_TRY(stream_upload(c, S.comp, zs::kPad));   // (room for it and for aux: above)
     if (!Z.aux.empty()) HIP_TRY(c, hipMemcpyAsync(S.comp.p + aux_base, Z.aux.data(), Z.aux.size(), hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipMemsetAsync(S.comp.p + aux_base + Z.aux.size(), 0, zs::kPad, st));
     HIP_TRY(c, hipMemcpyAsync(S.blocks.p, Z.ready.data(), nb * sizeof(zs::Block), hipMemcpyHostToDevice, st));
@@ -387,7 +390,7 @@ int zs_round(slimm_ctx* c, bool last) {
     return SLIMM_OK;
 }
 
-int zs_emit(slimm_ctx* c, uint8_t* dst, uint64_t* n_out, uint8_t* last_byte) {
+int zs_emit(slimm_ctx* c, uint8_t* dst, uint64_t, uint64_t* n_out, uint8_t* last_byte) {
     WindowPipeline& W = c->win;
     ZF& Z = W.file.zst;
     WindowPipeline::Zstd& S = W.zst;
@@ -397,7 +400,7 @@ int zs_emit(slimm_ctx* c, uint8_t* dst, uint64_t* n_out, uint8_t* last_byte) {
     const uint64_t text = Z.text, H = Z.hist_len;
     *n_out = 0;
     if (!nb) return SLIMM_OK;
-    const uint64_t drop = std::min(text, Z.skip_left);
+    const uint64_t drop = W.file.stream.skip_of(text);
     if (S.text.cap < H + text + 1u) HIP_TRY(c, S.text.ensure_later(H + text + (text >> 3) + 1u, W.outgrown));
     if (S.src.cap < text + 1u) HIP_TRY(c, S.src.ensure_later(text + (text >> 3) + 1u, W.outgrown));
     if (H) HIP_TRY(c, hipMemcpyAsync(S.text.p, S.hist.p, H, hipMemcpyDeviceToDevice, st));
@@ -455,7 +458,6 @@ int zs_emit(slimm_ctx* c, uint8_t* dst, uint64_t* n_out, uint8_t* last_byte) {
     stats[WindowPipeline::kZsPasses] = std::max<uint64_t>(stats[WindowPipeline::kZsPasses], passes);
     stats[WindowPipeline::kZsText] += text;
     Z.hist_len = keep;
-    Z.skip_left -= drop;
     *n_out = text - drop;
     push_trace_zs("round %llu: %u blocks -> %.1f MB of text, %u passes", (unsigned long long)stats[WindowPipeline::kZsRounds], nb, text / 1e6, passes);
     return SLIMM_OK;

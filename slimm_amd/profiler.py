@@ -294,11 +294,8 @@ class Slimm:
             total += got.value
         return total
 
-    def push_bzip2_sam_bytes(self, blob, skip: int = 0, window: int = 0, cuts=None, empty_last: bool = False) -> int:
-        """slimm_push_bzip2_sam_bytes: a bzip2-compressed SAM file's bytes from its first byte on, of whose decoded text the
-        first `skip` bytes are the header (set_reference_names first); pushed in windows of `window` bytes (0: one), or cut
-        at the offsets `cuts` -- anywhere, inside blocks and magics.  empty_last: the last push carries no byte.  The device
-        decodes the blocks, finds the lines and decodes them.  Returns the number of records."""
+    def _push_streamed_sam_bytes(self, push, blob, skip, window, cuts, empty_last) -> int:
+        """The cut-and-push loop of push_bzip2_sam_bytes, _gzip_ and _zstd_: `push` is the codec's entry point."""
         buf = np.frombuffer(blob, dtype=np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob, dtype=np.uint8)
         n = buf.shape[0]
         if cuts is None:
@@ -309,30 +306,24 @@ class Slimm:
         total, got = 0, C.c_uint64()
         for k, (a, b) in enumerate(pieces):
             piece = np.ascontiguousarray(buf[a:b])
-            self._check(self.L.slimm_push_bzip2_sam_bytes(self.ctx, _p(piece) if piece.size else None, b - a, skip if k == 0 else 0,
-                                                          1 if k == len(pieces) - 1 else 0, C.byref(got)))
+            self._check(push(self.ctx, _p(piece) if piece.size else None, b - a, skip if k == 0 else 0,
+                             1 if k == len(pieces) - 1 else 0, C.byref(got)))
             total += got.value
         return total
+
+    def push_bzip2_sam_bytes(self, blob, skip: int = 0, window: int = 0, cuts=None, empty_last: bool = False) -> int:
+        """slimm_push_bzip2_sam_bytes: a bzip2-compressed SAM file's bytes from its first byte on, of whose decoded text the
+        first `skip` bytes are the header (set_reference_names first); pushed in windows of `window` bytes (0: one), or cut
+        at the offsets `cuts` -- anywhere, inside blocks and magics.  empty_last: the last push carries no byte.  The device
+        decodes the blocks, finds the lines and decodes them.  Returns the number of records."""
+        return self._push_streamed_sam_bytes(self.L.slimm_push_bzip2_sam_bytes, blob, skip, window, cuts, empty_last)
 
     def push_gzip_sam_bytes(self, blob, skip: int = 0, window: int = 0, cuts=None, empty_last: bool = False) -> int:
         """slimm_push_gzip_sam_bytes: a gzip-compressed SAM file's bytes from its first byte on, of whose inflated text the
         first `skip` bytes are the header (set_reference_names first); the arguments are those of push_bzip2_sam_bytes.  The
         device finds chunk starts, inflates the chunks, checks the members, finds the lines and decodes them.  Returns the
         number of records."""
-        buf = np.frombuffer(blob, dtype=np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob, dtype=np.uint8)
-        n = buf.shape[0]
-        if cuts is None:
-            step = window or max(n, 1)
-            cuts = list(range(step, n, step))
-        bounds = [0] + sorted(c for c in set(cuts) if 0 < c < n) + [n]
-        pieces = [(a, b) for a, b in zip(bounds, bounds[1:]) if b > a] + ([(n, n)] if empty_last or n == 0 else [])
-        total, got = 0, C.c_uint64()
-        for k, (a, b) in enumerate(pieces):
-            piece = np.ascontiguousarray(buf[a:b])
-            self._check(self.L.slimm_push_gzip_sam_bytes(self.ctx, _p(piece) if piece.size else None, b - a, skip if k == 0 else 0,
-                                                         1 if k == len(pieces) - 1 else 0, C.byref(got)))
-            total += got.value
-        return total
+        return self._push_streamed_sam_bytes(self.L.slimm_push_gzip_sam_bytes, blob, skip, window, cuts, empty_last)
 
     GZIP_STATS = ("members", "chunks", "candidates", "dropped", "stored_blocks", "fixed_blocks", "dynamic_blocks", "resolved_bytes",
                   "rounds", "text_bytes", "compressed_bytes", "forced_starts")
@@ -348,20 +339,7 @@ class Slimm:
         first `skip` bytes are the header (set_reference_names first); the arguments are those of push_bzip2_sam_bytes.  The
         host walks the frames and blocks, the device decodes the blocks, builds the text, finds the lines and decodes them.
         Returns the number of records."""
-        buf = np.frombuffer(blob, dtype=np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob, dtype=np.uint8)
-        n = buf.shape[0]
-        if cuts is None:
-            step = window or max(n, 1)
-            cuts = list(range(step, n, step))
-        bounds = [0] + sorted(c for c in set(cuts) if 0 < c < n) + [n]
-        pieces = [(a, b) for a, b in zip(bounds, bounds[1:]) if b > a] + ([(n, n)] if empty_last or n == 0 else [])
-        total, got = 0, C.c_uint64()
-        for k, (a, b) in enumerate(pieces):
-            piece = np.ascontiguousarray(buf[a:b])
-            self._check(self.L.slimm_push_zstd_sam_bytes(self.ctx, _p(piece) if piece.size else None, b - a, skip if k == 0 else 0,
-                                                         1 if k == len(pieces) - 1 else 0, C.byref(got)))
-            total += got.value
-        return total
+        return self._push_streamed_sam_bytes(self.L.slimm_push_zstd_sam_bytes, blob, skip, window, cuts, empty_last)
 
     ZSTD_STATS = ("frames", "skippable", "raw_blocks", "rle_blocks", "compressed_blocks", "huffman_trees", "treeless", "plain_literals",
                   "predefined", "rle_tables", "fse_tables", "repeated", "sequences", "front_bytes", "history_bytes", "rounds",
