@@ -473,6 +473,33 @@ int slimm_install_merged_partials(slimm_ctx* ctx, uint32_t* total_pairs);
 /* ---- phase C(2,3): the propagation part of slimm::get_reads_lca_count() (src/slimm.hpp:560-610). */
 int slimm_get_reads_lca_count(slimm_ctx* ctx);
 
+/* THE ORDER OF THE PROPAGATION (quirk Q17).  Step 2 (src/slimm.hpp:560-586) hands the read count and the children of every
+ * directly counted taxon up the lineage of that taxon's smallest child AT THE MOMENT IT IS WALKED, and the reference walks
+ * an unordered_map: where an earlier climb can hand a later taxon a smaller child of another lineage -- databases with
+ * lineage holes, taxid 0 in a rank slot, once some multi-mapped read's LCA is taxid 0 -- the reference's own counts depend
+ * on its hash table's bucket order and cannot be reproduced from the input.
+ *   WHICH WALK THE LIBRARY TAKES: the directly counted taxa by rank, lowest (strain) first -- a taxid the database does
+ * not name, taxid 0 among them, counts as a strain (Q6) --, and ascending taxid within a rank (SLIMM_WALK_DEFAULT);
+ * SLIMM_WALK_REVERSED is its exact reverse.  slimm_set_propagation_priority puts the listed taxids that are directly
+ * counted in front, in the listed order (ids that are unknown or not counted are ignored, a repeated id counts once; n = 0
+ * clears the list); the rest follow in the chosen walk.  Both are settings of the context like its configuration: they
+ * hold for every later slimm_get_reads_lca_count and survive slimm_reset.  For a group set them on
+ * slimm_group_context(g, 0), the member that propagates, and read the verdict there.
+ *   slimm_get_reads_lca_count also decides whether the walk matters for THIS file, over every walk and whichever was
+ * taken; slimm_get_propagation_order reports it until the context's next propagation or reset (an error before any):
+ *   SLIMM_PROPAGATION_INDEPENDENT  every order of the walk gives the same counts and the same children (proved);
+ *   SLIMM_PROPAGATION_DEPENDENT    two concrete walks were run and their step-2 results differ;
+ *   SLIMM_PROPAGATION_UNDECIDED    neither: not proved independent, and the walks tried (default, reversed, each taxon
+ *                                  below -- at most 16 of them -- first and last) agree.
+ * and for the last two the taxa involved, as taxids in ascending order: the directly counted taxa that can receive
+ * children from another counted taxon's climb before their own walk when that can change the lineage they climb or where
+ * those children travel.  taxid may be NULL to ask for the count (*n_taxa); otherwise cap entries are available. */
+enum { SLIMM_PROPAGATION_INDEPENDENT = 0, SLIMM_PROPAGATION_DEPENDENT = 1, SLIMM_PROPAGATION_UNDECIDED = 2 };
+enum { SLIMM_WALK_DEFAULT = 0, SLIMM_WALK_REVERSED = 1 };
+int slimm_get_propagation_order(slimm_ctx* ctx, int* verdict, uint32_t* taxid, uint32_t cap, uint32_t* n_taxa);
+int slimm_set_propagation_walk(slimm_ctx* ctx, int walk);
+int slimm_set_propagation_priority(slimm_ctx* ctx, const uint32_t* taxid, uint32_t n);
+
 /* The per-file body of slimm::get_profiles() (src/slimm.hpp:447-489) on one GPU in one call:
  * slimm_analyze_alignments, slimm_finish_coverage, slimm_filter_alignments, slimm_get_reads_lca_count and, when path is
  * not NULL, slimm_write_abundance_file.  Returns SLIMM_E_NO_HITS (nothing written) when no record is mapped. */
@@ -592,7 +619,8 @@ int slimm_shutdown(void);
  * created; without it, or when one device is named several times, the same collectives are device-to-device copies and
  * a summing kernel) -- and writes the profile from member 0.  cfg->device is ignored; results (slimm_get_stats,
  * slimm_get_ref_columns, ...) are read from slimm_group_context(g, 0), whose per-reference columns, scalars and
- * per-taxon counts are the merged ones.  The coverage arrays stay per-member partial sums. */
+ * per-taxon counts are the merged ones.  The coverage arrays stay per-member partial sums.  Member 0 is also the one
+ * that propagates: slimm_set_propagation_walk / _priority are set on it and slimm_get_propagation_order is read from it. */
 typedef struct slimm_group slimm_group;
 int slimm_group_create(const slimm_config* cfg, const int* devices, uint32_t n_devices, slimm_group** out);
 void slimm_group_destroy(slimm_group* g);

@@ -26,6 +26,12 @@ E_NO_HITS = 1
 ORDER_GROUPED = 0
 ORDER_ANY = 1
 
+PROPAGATION_INDEPENDENT = 0
+PROPAGATION_DEPENDENT = 1
+PROPAGATION_UNDECIDED = 2
+WALK_DEFAULT = 0
+WALK_REVERSED = 1
+
 
 class SlimmError(RuntimeError):
     def __init__(self, code: int, msg: str):
@@ -136,6 +142,9 @@ SYMBOLS = [
     ("slimm_partials_buffer", C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_uint64)]),
     ("slimm_install_merged_partials", C.c_int, [_P, C.POINTER(C.c_uint32)]),
     ("slimm_get_reads_lca_count", C.c_int, [_P]),
+    ("slimm_get_propagation_order", C.c_int, [_P, C.POINTER(C.c_int), _P, C.c_uint32, C.POINTER(C.c_uint32)]),
+    ("slimm_set_propagation_walk", C.c_int, [_P, C.c_int]),
+    ("slimm_set_propagation_priority", C.c_int, [_P, _P, C.c_uint32]),
     ("slimm_get_profiles", C.c_int, [_P, C.c_char_p]),
     ("slimm_write_abundance", C.c_int, [_P, C.POINTER(C.c_char_p), C.POINTER(C.c_uint64)]),
     ("slimm_write_abundance_file", C.c_int, [_P, C.c_char_p]),

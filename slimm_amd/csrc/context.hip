@@ -1256,6 +1256,31 @@ int slimm_get_reads_lca_count(slimm_ctx* c) {
     return SLIMM_OK;
 }
 
+int slimm_get_propagation_order(slimm_ctx* c, int* verdict, uint32_t* taxid, uint32_t cap, uint32_t* n_taxa) {
+    if (!c || !verdict || !n_taxa) return SLIMM_E_INVALID;
+    if (!c->counted) return fail(c, SLIMM_E_INVALID, "call slimm_get_reads_lca_count first");
+    const std::vector<uint32_t>& t = c->host->order_taxa();
+    *verdict = c->host->order_verdict();
+    *n_taxa = static_cast<uint32_t>(t.size());
+    if (!taxid) return SLIMM_OK;
+    if (cap < t.size()) return fail(c, SLIMM_E_INVALID, "slimm_get_propagation_order: %zu taxa, room for %u", t.size(), cap);
+    if (!t.empty()) memcpy(taxid, t.data(), t.size() * 4);
+    return SLIMM_OK;
+}
+
+int slimm_set_propagation_walk(slimm_ctx* c, int walk) {
+    if (!c) return SLIMM_E_INVALID;
+    if (walk != SLIMM_WALK_DEFAULT && walk != SLIMM_WALK_REVERSED) return fail(c, SLIMM_E_INVALID, "unknown walk %d", walk);
+    c->host->set_walk(walk);
+    return SLIMM_OK;
+}
+
+int slimm_set_propagation_priority(slimm_ctx* c, const uint32_t* taxid, uint32_t n) {
+    if (!c || (n && !taxid)) return SLIMM_E_INVALID;
+    c->host->set_walk_priority(taxid, n);
+    return SLIMM_OK;
+}
+
 int slimm_get_profiles(slimm_ctx* c, const char* path) {  // src/slimm.hpp:447-489, one file on one GPU
     SLIMM_TRY(slimm_analyze_alignments(c));
     SLIMM_TRY(slimm_finish_coverage(c));  // SLIMM_E_NO_HITS: "[WARNING] No mapped reads found" (:451-455), nothing written

@@ -142,6 +142,8 @@ SLIMM_FORWARD(int, slimm_analyze_alignments, (slimm_ctx* a), (a))
 SLIMM_FORWARD(int, slimm_finish_coverage, (slimm_ctx* a), (a))
 SLIMM_FORWARD(int, slimm_filter_alignments, (slimm_ctx* a), (a))
 SLIMM_FORWARD(int, slimm_get_reads_lca_count, (slimm_ctx* a), (a))
+SLIMM_FORWARD(int, slimm_get_propagation_order, (slimm_ctx* a, int* b, uint32_t* c, uint32_t d, uint32_t* e), (a, b, c, d, e))
+SLIMM_FORWARD(int, slimm_set_propagation_walk, (slimm_ctx* a, int b), (a, b))
 SLIMM_FORWARD(int, slimm_write_abundance_file, (slimm_ctx* a, const char* b), (a, b))
 SLIMM_FORWARD(int, slimm_get_stats, (slimm_ctx* a, slimm_stats* b), (a, b))
 SLIMM_FORWARD(int, slimm_get_ref_columns, (slimm_ctx* a, slimm_ref_columns* b), (a, b))
@@ -186,6 +188,7 @@ struct Options {  // arg_options, reference src/slimm.hpp:49-87
     bool verify_grouping = false;  // --verify-grouping: count the read names that come back (slimm_check_grouping) and warn
     unsigned device_inflate = 1;   // --device-inflate K: every K-th window read in place is inflated on the device (0: none)
     unsigned window_mb = 0;        // --window-mb N: bytes per window buffer (tests make windows smaller than a record)
+    int propagation_walk = SLIMM_WALK_DEFAULT;  // --propagation-walk default|reversed (include/slimm_hip.h, "THE ORDER OF THE PROPAGATION")
     bool split_input = false;      // --split-input (with --devices): every member reads its own byte range of a BAM / SAM / BGZF SAM / bzip2 SAM
 };
 bool g_trace = false;              // SLIMM_TRACE=cli (or all): millisecond marks of the stages on stderr
@@ -253,7 +256,10 @@ void usage() {
                  "  -v,  --verbose\n"
                  "       --device N | --devices N,M,... [--split-input] | --query-grouped | --any-order | --dump-records | --dump-raw\n"
                  "       --host-decode | --packed-records | --verify-grouping | --device-inflate K | --window-mb N |\n"
-                 "       --decode-threads N | --no-mmap     (SLIMM_TRACE=cli: stage marks on stderr)\n";
+                 "       --decode-threads N | --no-mmap     (SLIMM_TRACE=cli: stage marks on stderr)\n"
+                 "       --propagation-walk default|reversed   order in which the directly counted taxa hand their read counts up\n"
+                 "                                     (default: lower ranks first, then ascending taxid; a [WARNING] names\n"
+                 "                                     the taxa when a file's counts depend on it)\n";
 }
 
 // 0 ok, 1 error, 2 help
@@ -325,6 +331,13 @@ int parse(int argc, char** argv, Options& o) {
             if (!o.devices.empty()) o.device = o.devices[0];
         } else if (a == "--split-input") {
             o.split_input = true;
+        } else if (a == "--propagation-walk") {
+            if (!value(v)) return 1;
+            if (v != "default" && v != "reversed") {
+                std::cerr << "slimm: propagation-walk must be default or reversed\n";
+                return 1;
+            }
+            o.propagation_walk = v == "reversed" ? SLIMM_WALK_REVERSED : SLIMM_WALK_DEFAULT;
         } else if (a == "--device") {
             if (!value(v)) return 1;
             o.device = atoi(v.c_str());
@@ -1353,6 +1366,26 @@ Outcome push_file(Session& S, Reading& F, Target t, OnCap on_cap) {
     return Outcome::Done;
 }
 
+// Q17: one line per file whose propagated read counts depend on the order of the walk, or could not be shown not to
+// (slimm_get_propagation_order on the context that propagated).  The profile is written either way.
+void warn_propagation_order(slimm_ctx* ctx, const std::string& path, int walk) {
+    int verdict = SLIMM_PROPAGATION_INDEPENDENT;
+    uint32_t n = 0;
+    if (slimm_get_propagation_order(ctx, &verdict, nullptr, 0, &n) != SLIMM_OK || verdict == SLIMM_PROPAGATION_INDEPENDENT) return;
+    std::vector<uint32_t> taxa(std::max<uint32_t>(n, 1u));
+    if (slimm_get_propagation_order(ctx, &verdict, taxa.data(), n, &n) != SLIMM_OK) return;
+    const uint32_t shown = std::min<uint32_t>(n, 12u);
+    std::ostringstream line;
+    line << "[WARNING] " << get_file_name(path) << ": the propagated read counts "
+         << (verdict == SLIMM_PROPAGATION_DEPENDENT ? "depend on the order in which the directly counted taxa are walked"
+                                                    : "could not be shown independent of the order in which the directly counted taxa are walked")
+         << " (lineage holes; the " << (walk == SLIMM_WALK_REVERSED ? "reversed" : "default") << " walk was taken, see --propagation-walk); taxid"
+         << (n == 1 ? "" : "s") << " involved:";
+    for (uint32_t k = 0; k < shown; ++k) line << ' ' << taxa[k];
+    if (n > shown) line << " and " << n - shown << " more";
+    std::cerr << line.str() << std::endl;
+}
+
 // ---- several GPUs, one process (--devices), or members of a group on ONE device for a file of more records than one
 // context takes (for_cap): the group deals the records to its members by read and runs the phases with the two RCCL
 // exchanges in between (slimm_amd/csrc/group.hip); the profile comes from member 0
@@ -1373,6 +1406,7 @@ Outcome run_group(Session& S, Reading& F, const std::vector<int>& devs, bool spl
         (void)slimm_keep_bins(slimm_group_context(grp.get(), i), want_arrays ? 1 : 0);
     }
     slimm_ctx* c0 = slimm_group_context(grp.get(), 0);
+    (void)slimm_set_propagation_walk(c0, options.propagation_walk);   // (member 0 propagates)
     F.trace.mark("lineage table + slimm_group_create");
     std::cerr << "[" << F.watch.lap() << " secs]" << std::endl;
     std::cerr << "Analysing alignments on " << devs.size() << " devices ("
@@ -1418,6 +1452,7 @@ Outcome run_group(Session& S, Reading& F, const std::vector<int>& devs, bool spl
         std::cerr << "[WARNING] No mapped reads found in BAM file!" << std::endl;
         return Outcome::Done;
     }
+    warn_propagation_order(c0, F.path, options.propagation_walk);
     if (options.min_reads == 0) options.min_reads = st.min_reads;
     if (options.verbose) {
         std::cerr << "  " << st.hits_count << " records processed." << std::endl;
@@ -1445,6 +1480,7 @@ Outcome run_context(Session& S, Reading& F) {
     CtxPtr owned(created, slimm_destroy);
     slimm_ctx* ctx = owned.get();
     CHECK(ctx, slimm_set_cutoff_cache(ctx, S.cc_cache, S.ucc_cache));
+    CHECK(ctx, slimm_set_propagation_walk(ctx, options.propagation_walk));
     set_size_hint(ctx, F.path);
     slimm_keep_bins(ctx, (options.raw_output || options.coverage_output) ? 1 : 0);  // (only -ro / -co read the arrays back)
     F.trace.mark("lineage table + slimm_create");
@@ -1529,6 +1565,7 @@ Outcome run_context(Session& S, Reading& F) {
     std::cerr << "Assigning reads to Least Common Ancestor (LCA) ... ";
     CHECK(ctx, slimm_get_reads_lca_count(ctx));
     std::cerr << "[" << F.watch.lap() << " secs]" << std::endl;
+    warn_propagation_order(ctx, F.path, options.propagation_walk);
 
     std::cerr << "Writing taxnomic profile(s) ...................... ";
     CHECK(ctx, slimm_write_abundance_file(ctx, get_tsv_file_name(options.output_prefix, F.path, "_profile").c_str()));

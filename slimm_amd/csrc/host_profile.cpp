@@ -139,6 +139,24 @@ HostProfile::HostProfile(const HostConfig& cfg) : cfg_(cfg) {
     }
     lvl_off_[8] = static_cast<uint32_t>(lvl_taxon_.size());
 
+    // references whose lineages agree at levels 1..7 (all that a climb can read) share a class: decide_order()
+    {
+        std::vector<uint32_t> by_row(R);
+        std::iota(by_row.begin(), by_row.end(), 0u);
+        auto row = [&](uint32_t r) { return &lin_dense_[static_cast<size_t>(r) * 8 + 1]; };
+        std::sort(by_row.begin(), by_row.end(), [&](uint32_t a, uint32_t b) {
+            const int c = memcmp(row(a), row(b), 7 * sizeof(uint32_t));
+            return c != 0 ? c < 0 : a < b;
+        });
+        class_of_ref_.assign(R, 0);
+        uint32_t cls = 0;
+        for (uint32_t k = 0; k < R; ++k) {
+            if (k && memcmp(row(by_row[k]), row(by_row[k - 1]), 7 * sizeof(uint32_t)) != 0) ++cls;
+            class_of_ref_[by_row[k]] = cls;
+        }
+    }
+    slot_of_.assign(n_taxa_dense(), 0xffffffffu);
+
     // db.taxid__name: absent taxid reads as (strain_lv, "") -- the reference's operator[] default (Q6)
     std::unordered_map<uint32_t, uint32_t> pos;
     pos.reserve(cfg_.tax_id.size() * 2);
@@ -439,9 +457,35 @@ void HostProfile::propagate() {
     }
 
     // Step 2 (:560-586): every taxon with direct hits hands its count (snapshot value) and its children (live) to the
-    // ranks above its own along the lineage of its smallest child.  The reference walks an unordered_map; any order
-    // gives the same result in a consistent tree.  Here: lower ranks first, then ascending taxid.
+    // ranks above its own along the lineage of its smallest child AT THE MOMENT IT IS WALKED.  The reference walks an
+    // unordered_map.  The order matters when an earlier climb can hand a later taxon a smaller child of another lineage, or
+    // children that the later taxon carries to places the earlier one does not reach -- which lineage holes (taxid 0 in
+    // a rank slot) make possible.  decide_order() says whether it can matter here.  The default walk: lower
+    // ranks first, then ascending taxid; set_walk / set_walk_priority choose another.
     std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return rank_d_[a] < rank_d_[b]; });
+    decide_order(order);
+    if (walk_ != kWalkDefault || !priority_.empty()) {
+        std::vector<uint32_t>& walk = walk_scratch_;
+        walk.clear();
+        for (uint32_t id : priority_) {  // the listed taxa that are directly counted, each once
+            const auto it = std::lower_bound(dense_taxid_.begin(), dense_taxid_.end(), id);
+            if (it == dense_taxid_.end() || *it != id) continue;
+            const uint32_t t = static_cast<uint32_t>(it - dense_taxid_.begin());
+            if (!lca_count_[t] || slot_of_[t] != 0xffffffffu) continue;
+            slot_of_[t] = 0;
+            walk.push_back(t);
+        }
+        const size_t n_first = walk.size();
+        if (walk_ == kWalkReversed) {
+            for (size_t k = order.size(); k-- > 0;)
+                if (slot_of_[order[k]] == 0xffffffffu) walk.push_back(order[k]);
+        } else {
+            for (uint32_t t : order)
+                if (slot_of_[t] == 0xffffffffu) walk.push_back(t);
+        }
+        for (size_t k = 0; k < n_first; ++k) slot_of_[walk[k]] = 0xffffffffu;
+        order.swap(walk);
+    }
     std::vector<uint32_t> ids;
     for (uint32_t t : order) {
         uint32_t rnk = rank_d_[t];
@@ -480,6 +524,208 @@ void HostProfile::propagate() {
     });
     have_counts = true;
     profile_ready_ = false;
+}
+
+// Whether the result of step 2 depends on the order of its walk (DESIGN.md section 2 has the argument in full).
+//
+// For every counted taxon t, poss_[t] over-approximates the references kids_[t] can hold when t is walked: its own
+// children and, transitively, those of every counted taxon s one of whose possible climbs passes through t.  A
+// reference can be t's smallest child only if it is no larger than t's smallest OWN child (always there); such
+// references are t's candidates, their lineages above t's rank its possible climbs.  References whose lineages agree
+// at levels 1..7 are kept as one entry with the smallest of them: only that one can decide a candidate.
+//   INDEPENDENT when, for every t, (a) all candidates have the same lineage above t's rank -- every walk climbs the
+// same slots with the same count --, and (b) for every edge s -> t, {t} + t's climb is a subset of {s} + s's climb --
+// whatever t carries upwards for s, s delivers there itself (or it is s's own set).  By induction over the walk every
+// kids_[u] then ends as own(u) + the own children of every s whose climb reaches u, in any order.
+//   Otherwise the taxa that break (a) or (b) are suspects; a handful of concrete walks on sparse containers (default,
+// reversed, each suspect first and last) either differ -- DEPENDENT, proved by two witnesses -- or leave it UNDECIDED.
+void HostProfile::decide_order(const std::vector<uint32_t>& walk) {
+    order_verdict_ = kOrderIndependent;
+    order_taxa_.clear();
+    const uint32_t n = static_cast<uint32_t>(walk.size());
+    if (n < 2) return;  // one counted taxon: one walk
+    const uint32_t none = 0xffffffffu;
+    auto own_min = [&](uint32_t i) { return kids_[walk[i]].items.empty() ? none : kids_[walk[i]].mn; };
+    auto climb_of = [&](uint32_t ref) { return &lin_dense_[static_cast<size_t>(ref) * 8]; };
+    // Nothing can arrive anywhere unless some taxon's climb from its smallest OWN child meets another counted taxon: the
+    // usual end for a file whose multi-mapped reads stay inside their species.
+    bool any_edge = false;
+    for (uint32_t i = 0; i < n && !any_edge; ++i) {
+        if (own_min(i) == none) continue;
+        const uint32_t* lin = climb_of(own_min(i));
+        for (uint32_t j = rank_d_[walk[i]] + 1; j < kLineageLen; ++j) any_edge |= lca_count_[lin[j]] != 0 && lin[j] != walk[i];
+    }
+    if (!any_edge) return;
+    for (uint32_t i = 0; i < n; ++i) slot_of_[walk[i]] = i;
+    if (poss_.size() < n) poss_.resize(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        std::vector<ClassMin>& q = poss_[i];
+        q.clear();
+        const std::vector<uint32_t>& own = kids_[walk[i]].items;
+        for (uint32_t r : own) q.push_back({class_of_ref_[r], r});
+        if (own.size() < 2) continue;
+        std::sort(q.begin(), q.end(), [](const ClassMin& a, const ClassMin& b) { return a.cls != b.cls ? a.cls < b.cls : a.ref < b.ref; });
+        q.erase(std::unique(q.begin(), q.end(), [](const ClassMin& a, const ClassMin& b) { return a.cls == b.cls; }), q.end());
+    }
+
+    // the fixpoint: poss_[k] takes in poss_[i] for every counted k != i on a possible climb of i
+    std::vector<ClassMin> merged;
+    auto merge_into = [&](std::vector<ClassMin>& a, const std::vector<ClassMin>& b) {
+        merged.clear();
+        bool changed = false;
+        size_t x = 0, y = 0;
+        while (x < a.size() || y < b.size()) {
+            if (y == b.size() || (x < a.size() && a[x].cls < b[y].cls)) {
+                merged.push_back(a[x++]);
+            } else if (x == a.size() || b[y].cls < a[x].cls) {
+                merged.push_back(b[y++]);
+                changed = true;
+            } else {
+                changed |= b[y].ref < a[x].ref;
+                merged.push_back({a[x].cls, std::min(a[x].ref, b[y].ref)});
+                ++x;
+                ++y;
+            }
+        }
+        if (changed) a.swap(merged);
+        return changed;
+    };
+    std::vector<uint32_t> todo(n);
+    std::vector<uint8_t> queued(n, 1), has_in(n, 0);
+    // An edge i -> k delivers nothing when nothing arrives at i and k's own children include i's: then it is no edge.
+    auto absorbed = [&](uint32_t i, uint32_t k) {
+        if (has_in[i]) return false;
+        RefSet &a = kids_[walk[i]], &b = kids_[walk[k]];
+        a.materialise();
+        b.materialise();
+        return std::includes(b.items.begin(), b.items.end(), a.items.begin(), a.items.end());
+    };
+    for (uint32_t i = 0; i < n; ++i) todo[i] = n - 1 - i;  // (a stack: the default walk's first taxon on top)
+    while (!todo.empty()) {
+        const uint32_t i = todo.back();
+        todo.pop_back();
+        queued[i] = 0;
+        const uint32_t rnk = rank_d_[walk[i]], mn = own_min(i);
+        for (size_t e = 0; e < poss_[i].size(); ++e) {
+            if (poss_[i][e].ref > mn) continue;
+            const uint32_t* lin = climb_of(poss_[i][e].ref);
+            for (uint32_t j = rnk + 1; j < kLineageLen; ++j) {
+                const uint32_t k = slot_of_[lin[j]];
+                if (k == none || k == i || absorbed(i, k)) continue;
+                const bool first = !has_in[k];  // (its own edges may have been taken for absorbed ones: once more)
+                has_in[k] = 1;
+                if ((merge_into(poss_[k], poss_[i]) || first) && !queued[k]) {
+                    queued[k] = 1;
+                    todo.push_back(k);
+                }
+            }
+        }
+    }
+
+    std::vector<uint8_t> suspect(n, 0);
+    for (uint32_t i = 0; i < n; ++i) {  // (a): one lineage above the rank among the candidates
+        if (!has_in[i]) continue;        // (nothing arrives: its smallest own child decides, whatever the walk)
+        const uint32_t rnk = rank_d_[walk[i]], mn = own_min(i);
+        if (mn == none) suspect[i] = 1;  // walked only if something has arrived
+        const uint32_t* first = nullptr;
+        for (const ClassMin& e : poss_[i]) {
+            if (e.ref > mn) continue;
+            const uint32_t* lin = climb_of(e.ref);
+            if (!first) first = lin;
+            for (uint32_t j = rnk + 1; j < kLineageLen; ++j)
+                if (lin[j] != first[j]) suspect[i] = 1;
+        }
+    }
+    for (uint32_t i = 0; i < n; ++i) {  // (b): over every possible climb of s = walk[i] and every counted k on it
+        const uint32_t s = walk[i], rnk = rank_d_[s], mn = own_min(i);
+        for (const ClassMin& e : poss_[i]) {
+            if (e.ref > mn) continue;
+            const uint32_t* ls = climb_of(e.ref);
+            for (uint32_t j = rnk + 1; j < kLineageLen; ++j) {
+                const uint32_t k = slot_of_[ls[j]];
+                if (k == none || k == i || suspect[k] || absorbed(i, k)) continue;
+                const uint32_t rk = rank_d_[walk[k]], mk = own_min(k);
+                if (rk + 1 >= kLineageLen) continue;  // (k climbs nowhere)
+                for (const ClassMin& f : poss_[k]) {
+                    if (f.ref > mk) continue;
+                    const uint32_t* lt = climb_of(f.ref);
+                    if (rk >= rnk && std::equal(lt + rk + 1, lt + kLineageLen, ls + rk + 1)) continue;  // (the tail of s's climb)
+                    for (uint32_t a = rk + 1; a < kLineageLen && !suspect[k]; ++a) {
+                        bool found = lt[a] == s || lt[a] == walk[k];
+                        for (uint32_t b = rnk + 1; b < kLineageLen && !found; ++b) found = ls[b] == lt[a];
+                        if (!found) suspect[k] = 1;
+                    }
+                }
+            }
+        }
+    }
+    for (uint32_t i = 0; i < n; ++i) slot_of_[walk[i]] = none;
+    std::vector<uint32_t> sus;
+    for (uint32_t i = 0; i < n; ++i)
+        if (suspect[i]) sus.push_back(walk[i]);
+    if (sus.empty()) return;
+    std::sort(sus.begin(), sus.end());
+    for (uint32_t t : sus) order_taxa_.push_back(dense_taxid_[t]);  // (dense indices ascend with the taxids)
+
+    // witnesses: stop at the first walk that differs from the default one
+    order_verdict_ = kOrderUndecided;
+    const Step2Result base = simulate_step2(walk);
+    std::vector<uint32_t> w(walk.rbegin(), walk.rend());
+    if (!(simulate_step2(w) == base)) {
+        order_verdict_ = kOrderDependent;
+        return;
+    }
+    const size_t tried = std::min<size_t>(sus.size(), 16);  // (a bound on the work, not on the verdict's soundness)
+    for (size_t k = 0; k < tried; ++k) {
+        for (int last = 0; last < 2; ++last) {
+            w.clear();
+            if (!last) w.push_back(sus[k]);
+            for (uint32_t t : walk)
+                if (t != sus[k]) w.push_back(t);
+            if (last) w.push_back(sus[k]);
+            if (!(simulate_step2(w) == base)) {
+                order_verdict_ = kOrderDependent;
+                return;
+            }
+        }
+    }
+}
+
+// Step 2 as propagate() does it, for one walk, on containers of their own (the state before step 2 is left alone).
+HostProfile::Step2Result HostProfile::simulate_step2(const std::vector<uint32_t>& walk) const {
+    std::unordered_map<uint32_t, uint32_t> count;
+    std::unordered_map<uint32_t, std::vector<uint32_t>> kids;  // sorted, unique
+    for (uint32_t t : touched_) {
+        if (lca_count_[t]) count[t] = lca_count_[t];
+        if (!kids_[t].present) continue;
+        std::vector<uint32_t>& k = kids[t];
+        k = kids_[t].items;
+        std::sort(k.begin(), k.end());
+        k.erase(std::unique(k.begin(), k.end()), k.end());
+    }
+    std::vector<uint32_t> ids, tmp;
+    for (uint32_t t : walk) {
+        const auto it = kids.find(t);
+        if (it == kids.end() || it->second.empty()) continue;
+        ids = it->second;
+        const uint32_t* lin = &lin_dense_[static_cast<size_t>(ids[0]) * 8];
+        for (uint32_t j = rank_d_[t] + 1; j < kLineageLen; ++j) {
+            const uint32_t u = lin[j];
+            count[u] += lca_count_[t];
+            if (u == t) continue;
+            std::vector<uint32_t>& k = kids[u];
+            tmp.resize(k.size() + ids.size());
+            tmp.erase(std::set_union(k.begin(), k.end(), ids.begin(), ids.end(), tmp.begin()), tmp.end());
+            k.swap(tmp);
+        }
+    }
+    Step2Result r;
+    for (const auto& c : count) r.count.push_back((static_cast<uint64_t>(c.first) << 32) | c.second);
+    for (const auto& k : kids)
+        for (uint32_t ref : k.second) r.kids.push_back((static_cast<uint64_t>(k.first) << 32) | ref);
+    std::sort(r.count.begin(), r.count.end());
+    std::sort(r.kids.begin(), r.kids.end());
+    return r;
 }
 
 void HostProfile::taxon_counts(int stage, std::vector<uint32_t>& taxid, std::vector<uint32_t>& count) {

@@ -101,6 +101,17 @@ public:
     const std::vector<uint64_t>& pairs() const { return pairs_; }
     // a12 steps 2,3
     void propagate();
+    // The order in which step 2 walks the directly counted taxa, and whether it matters.
+    // Settings of the object, like its configuration: reset() keeps them.  walk 0: lower ranks first, then ascending
+    // taxid; 1: the exact reverse.  The listed taxids that are directly counted are walked first, in the listed order.
+    enum { kWalkDefault = 0, kWalkReversed = 1 };
+    enum { kOrderIndependent = 0, kOrderDependent = 1, kOrderUndecided = 2 };
+    void set_walk(int walk) { walk_ = walk; }
+    void set_walk_priority(const uint32_t* taxid, uint32_t n) { priority_.assign(taxid, taxid + n); }
+    // valid after propagate(): the verdict over EVERY walk (not only the one taken), and for a verdict other than
+    // independent the counted taxa whose walk position can matter, as original taxids, ascending
+    int order_verdict() const { return order_verdict_; }
+    const std::vector<uint32_t>& order_taxa() const { return order_taxa_; }
     // a13
     const std::string& write_abundance();
 
@@ -164,6 +175,24 @@ private:
     std::vector<uint32_t> pa_rd_, sum_rd_, order_scratch_, parents_scratch_;
     std::vector<uint8_t> pa_seen_;
     std::vector<uint32_t> touched_;       // taxa whose count / children entry exists (cleared cheaply on the next file)
+    // order of step 2
+    struct ClassMin {  // a lineage (levels 1..7) among the references a taxon may hold when walked, and the smallest of them
+        uint32_t cls, ref;
+    };
+    struct Step2Result {  // step 2 of one walk on sparse containers: (taxon, count) and (taxon << 32 | reference), sorted
+        std::vector<uint64_t> count, kids;
+        bool operator==(const Step2Result& o) const { return count == o.count && kids == o.kids; }
+    };
+    void decide_order(const std::vector<uint32_t>& default_walk);
+    Step2Result simulate_step2(const std::vector<uint32_t>& walk) const;
+    int walk_ = kWalkDefault;
+    std::vector<uint32_t> priority_;      // taxids
+    int order_verdict_ = kOrderIndependent;
+    std::vector<uint32_t> order_taxa_;
+    std::vector<uint32_t> class_of_ref_;  // [R] equal for references whose lineages agree at levels 1..7
+    std::vector<uint32_t> slot_of_;       // [T] position among the counted taxa, ~0 outside decide_order / propagate
+    std::vector<std::vector<ClassMin>> poss_;
+    std::vector<uint32_t> walk_scratch_;
     std::string profile_;
     bool profile_ready_ = false;
     bool abundance_ready_ = false;

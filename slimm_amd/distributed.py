@@ -300,7 +300,9 @@ def sharded_profile_begin(engine, device: Optional[torch.device] = None, group=N
 
 def sharded_profile_end(engine, path: Optional[str] = None, group=None, phase_times: Optional[dict] = None):
     """The host's end of `sharded_profile`: the propagation of the LCA counts (src/slimm.hpp:560-610) and the profile
-    (`write_abundance`, :733-843; rank 0 writes the file).  No device work, no collective."""
+    (`write_abundance`, :733-843; rank 0 writes the file).  No device work, no collective.  Every rank propagates the
+    same merged partial results, so `engine.propagation_order()` afterwards is on every rank the verdict one context
+    would give on all the records; `engine.set_propagation_walk` before it chooses the walk (the same on every rank)."""
     import time
     t = time.perf_counter()
     engine.get_reads_lca_count()

@@ -607,6 +607,24 @@ class Slimm:
     def get_reads_lca_count(self):
         self._check(self.L.slimm_get_reads_lca_count(self.ctx))
 
+    def set_propagation_walk(self, walk: int = capi.WALK_DEFAULT, first=()):
+        """The order in which step 2 of the propagation walks the directly counted taxa (include/slimm_hip.h, "THE ORDER OF
+        THE PROPAGATION"): capi.WALK_DEFAULT (lower ranks first, then ascending taxid) or capi.WALK_REVERSED, behind the
+        directly counted taxids of `first` in the order given.  A setting of the context: it survives reset()."""
+        self._check(self.L.slimm_set_propagation_walk(self.ctx, int(walk)))
+        ids = np.ascontiguousarray(list(first), dtype=np.uint32)
+        self._check(self.L.slimm_set_propagation_priority(self.ctx, _p(ids) if ids.size else None, int(ids.size)))
+
+    def propagation_order(self) -> Tuple[int, List[int]]:
+        """(verdict, taxids) of the last get_reads_lca_count -- on whichever path the partial results arrived, one context
+        or a merge over ranks: capi.PROPAGATION_INDEPENDENT / _DEPENDENT / _UNDECIDED and the taxa involved, ascending."""
+        verdict = C.c_int()
+        n = C.c_uint32()
+        self._check(self.L.slimm_get_propagation_order(self.ctx, C.byref(verdict), None, 0, C.byref(n)))
+        ids = np.zeros(max(n.value, 1), dtype=np.uint32)
+        self._check(self.L.slimm_get_propagation_order(self.ctx, C.byref(verdict), _p(ids), n.value, C.byref(n)))
+        return int(verdict.value), ids[:n.value].tolist()
+
     def write_abundance(self, path: Optional[str] = None) -> str:
         if path is not None:
             self._check(self.L.slimm_write_abundance_file(self.ctx, path.encode()))
@@ -873,6 +891,14 @@ class SlimmGroup:
     def exchange(self) -> str:
         k = self.L.slimm_group_exchange(self.g)
         return next(n for n, v in self.EXCHANGES.items() if v == k)
+
+    def set_propagation_walk(self, walk: int = capi.WALK_DEFAULT, first=()):
+        """Slimm.set_propagation_walk on member 0, the member that propagates."""
+        self.member(0).set_propagation_walk(walk, first)
+
+    def propagation_order(self):
+        """Slimm.propagation_order of member 0 (after get_profiles)."""
+        return self.member(0).propagation_order()
 
     def get_profiles(self, path: Optional[str] = None) -> bool:
         """False when no record is mapped (the reference's early return)."""
