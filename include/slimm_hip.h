@@ -321,8 +321,10 @@ int slimm_get_gzip_stats(slimm_ctx* ctx, uint64_t out[12]);
  * slimm_push_gzip_sam_bytes: `bytes` = the file's next n_bytes, from its first byte on and in order across calls, cut
  * anywhere (inside a frame header, a block header, a block, the checksum); of the decoded text the first `skip` bytes are the
  * header (0 in every later call); slimm_set_reference_names first; the caller's buffer is free when the call returns; what
- * cannot be decoded yet waits for the next push; the form does not mix with the others within a file, and it is refused
- * behind slimm_set_input_mid_file ("a zstd stream is not cut by byte range").  Pushes are gathered on the host and decoded
+ * cannot be decoded yet waits for the next push; the form does not mix with the others within a file.  Behind
+ * slimm_set_input_mid_file it is a byte range of a split file, taken only when slimm_set_input_range has told where the
+ * range lies (below: "zstd SAM by byte range"); without that it is refused ("a zstd stream is not cut by byte range unless
+ * its range is announced (slimm_set_input_range) and starts at a frame").  Pushes are gathered on the host and decoded
  * in rounds (32 MiB of compressed bytes, at most 512 MB of text by the blocks' bounds): the host walks the frame and block
  * headers, the device decodes every compressed block's literals and sequences at once (a wave per block), builds the
  * round's text in parallel over its bytes -- a match byte gets the position it copies from, in the round or in the
@@ -652,8 +654,9 @@ int slimm_group_set_exchange(slimm_group* g, int mode);
 int slimm_group_exchange(const slimm_group* g); /* the form in effect (what AUTO resolves to) */
 int slimm_group_get_profiles(slimm_group* g, const char* path); /* path may be NULL; SLIMM_E_NO_HITS like slimm_get_profiles */
 /* ONE FILE SPLIT BY BYTE RANGE over a group (files GROUPED by read name or in ANY order): every member reads, inflates and decodes its own contiguous
- * range of the file at once.  Four forms of file: BAM, SAM text, SAM text in BGZF blocks (bgzip), and bzip2-compressed SAM
- * text (below: "bzip2 SAM by byte range").  (A plain gzip stream cannot be cut: it goes through one member.)
+ * range of the file at once.  Five forms of file: BAM, SAM text, SAM text in BGZF blocks (bgzip), bzip2-compressed SAM
+ * text (below: "bzip2 SAM by byte range") and zstd-compressed SAM text of several frames (below: "zstd SAM by byte range").
+ * (A plain gzip stream and a zstd file of one frame cannot be cut: they go through one member.)
  *   The plan (host only, no GPU): offsets_out[0, n]; range i = [offsets_out[i], offsets_out[i + 1]), ranges may be empty.
  * slimm_host_bgzf_ranges -- BAM and BGZF SAM --: offsets_out[0] = 0, offsets_out[n] = the file's size; a range starts on a
  * BGZF block boundary (a header whose next three headers chain through BSIZE + 1, or whose chain reaches the EOF block or
@@ -712,9 +715,39 @@ int slimm_group_get_profiles(slimm_group* g, const char* path); /* path may be N
  * CRC is linear -- c = rotl(c, 1) ^ crc per block --, so rotl^k(left's value) ^ the member's partial value must be the
  * CRC of its first marker ("combined CRC mismatch", with the marker's byte), or is handed on to the next cut when it saw
  * none.  The decoded text is then stitched as SAM text is: a member's text starts at a block boundary inside a line, and
- * its head through the first newline goes to the member on its left. */
+ * its head through the first newline goes to the member on its left.
+ *   zstd SAM by byte range.  A zstd file is cut where a frame -- or a skippable frame -- starts, and nowhere else: frames
+ * are byte-aligned, start with a magic and are independent of each other (window, repeat offsets and entropy tables start
+ * afresh at a frame header), which is what pzstd, the seekable format and `cat a.zst b.zst` write.  A single frame cannot be
+ * cut: its copies reach back through the whole window.  slimm_host_zstd_ranges: offsets_out[0] = 0, offsets_out[n] = the
+ * file's size, every other offset the first byte of a frame or of a skippable frame, or the file's size.  No cut lies in
+ * front of the end of the frame that holds decoded byte skip - 1 (the header's frames are decoded on the host; member 0
+ * holds the whole header and pushes with that skip).  Cut i is the earliest start at or behind first + i * (size - first) /
+ * n that passes these checks: the frame header parses (reserved bit, window of at most 128 MiB, dictionary id 0), the block
+ * chain reaches a last block with no block of the reserved type and none above the frame's block maximum, a stated
+ * checksum fits in the file, and behind it the file ends or a frame's or skippable frame's magic stands (a skippable
+ * frame: its length fits, and the same holds behind it).  The search gives up 64 MiB behind its target (a design constant
+ * that bounds the planner's reading; SLIMM_FORCE zstd_cut_search=N): the cut is then the next one found, or the file's
+ * size, and the range in between is empty -- so a file of one frame has every cut at its size.  SLIMM_E_INVALID for a skip
+ * of 2^32 or more, for a path that is no regular file, and when the header's frames do not decode.  The planner trusts
+ * nothing it cannot walk; the members and the stitch check the rest.
+ *   Every member announces its flags with slimm_set_input_mid_file AND its range with slimm_set_input_range(ctx, begin,
+ * end), and pushes -- slimm_push_zstd_sam_bytes, skip for member 0 only -- exactly its range: there is no slack.  A range
+ * that starts inside the file whose first bytes start no frame is SLIMM_E_SPLIT; so is a range that ends inside the file
+ * and at last = 1 does not stand between frames with every byte read ("the range does not end at a frame boundary": a
+ * frame or block that runs past the range).  The file's last member keeps the truncation errors of one context.  Nothing
+ * in front of the range exists for the member; content sizes and checksums are checked by the member that owns the
+ * frame, and error messages name the file's bytes.  An empty range, or one of skippable and empty frames only, decodes no
+ * text and is an empty member.  slimm_get_zstd_stats stays per context: the members' counters sum to the file's.
+ *   slimm_group_stitch_ranges first checks on host scalars, left to right, that every member's decoder stopped between
+ * frames exactly at its range's end (SLIMM_E_SPLIT names the member); the text is then stitched as SAM text is.
+ * slimm_zstd_split_floor(): the least bytes per member -- (size - first cut) / members -- at which the command cuts a
+ * zstd file for --split-input: the codec's round size, 32 MiB (a member with less decodes its range in one round, and no
+ * gain from that has been measured: a stated default, not a measurement; SLIMM_FORCE zstd_split_floor=N). */
+int slimm_host_zstd_ranges(const char* path, uint64_t skip, uint32_t n, uint64_t* offsets_out);
+uint64_t slimm_zstd_split_floor(void);
 int slimm_host_bzip2_ranges(const char* path, uint64_t skip, uint32_t n, uint64_t* offsets_out);
-/* A range's absolute file offsets [begin, end) (bzip2 SAM; before the range's first window, beside slimm_set_input_mid_file) */
+/* A range's absolute file offsets [begin, end) (bzip2 SAM, zstd SAM; before the range's first window, beside slimm_set_input_mid_file) */
 int slimm_set_input_range(slimm_ctx* ctx, uint64_t begin, uint64_t end);
 /* the bytes a member reads behind its range of a bzip2 file (slimm_amd/csrc/bzip2_block.h: kSplitSlack, from the format's bounds) */
 uint64_t slimm_bzip2_split_slack(void);

@@ -196,6 +196,8 @@ SYMBOLS = [
     ("slimm_host_bzip2_ranges", C.c_int, [C.c_char_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]),
     ("slimm_set_input_range", C.c_int, [_P, C.c_uint64, C.c_uint64]),
     ("slimm_bzip2_split_slack", C.c_uint64, []),
+    ("slimm_host_zstd_ranges", C.c_int, [C.c_char_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]),
+    ("slimm_zstd_split_floor", C.c_uint64, []),
     ("slimm_group_stitch_ranges", C.c_int, [_P]),
     ("slimm_record_cap", C.c_uint64, []),
     ("slimm_shutdown", C.c_int, []),

@@ -18,6 +18,10 @@
 //   round)                                    tests/test_gpu_zstd_sam.py, tests/test_cli_zstd_sam_device.py
 //   bzip2_split_wrong_first (a mid-file member of a split bzip2 file passes over its first block or marker:
 //   slimm_group_stitch_ranges must refuse the cut)                                   tests/test_gpu_split_bzip2_sam.py
+//   zstd_split_floor=N (the least bytes per member at which the command cuts a zstd file for --split-input: 32 MiB unless
+//   told), zstd_cut_search=N (slimm_host_zstd_ranges gives a cut up N bytes behind its target: 64 MiB unless told),
+//   zstd_split_wrong_cut (the planner's second cut -- of two members: its only one -- lands one byte late, where no frame
+//   starts: the members or the stitch must refuse it)   tests/test_gpu_split_zstd_sam.py, tests/test_cli_split_input_zstd.py
 #pragma once
 #include <cstdlib>
 #include <cstring>

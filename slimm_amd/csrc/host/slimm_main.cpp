@@ -132,6 +132,8 @@ SLIMM_FORWARD(int, slimm_set_input_mid_file, (slimm_ctx* a, int b, int c), (a, b
 SLIMM_FORWARD(int, slimm_host_bzip2_ranges, (const char* a, uint64_t b, uint32_t c, uint64_t* d), (a, b, c, d))
 SLIMM_FORWARD(int, slimm_set_input_range, (slimm_ctx* a, uint64_t b, uint64_t c), (a, b, c))
 SLIMM_FORWARD(uint64_t, slimm_bzip2_split_slack, (), ())
+SLIMM_FORWARD(int, slimm_host_zstd_ranges, (const char* a, uint64_t b, uint32_t c, uint64_t* d), (a, b, c, d))
+SLIMM_FORWARD(uint64_t, slimm_zstd_split_floor, (), ())
 SLIMM_FORWARD(int, slimm_group_stitch_ranges, (slimm_group* a), (a))
 SLIMM_FORWARD(uint64_t, slimm_record_cap, (), ())
 SLIMM_FORWARD(int, slimm_shutdown, (), ())
@@ -165,6 +167,7 @@ SLIMM_FORWARD(int, slimm_group_get_profiles, (slimm_group* a, const char* b), (a
 SLIMM_FORWARD(int, slimm_group_reset, (slimm_group* a), (a))
 #include "accession.hpp"
 #include "alignment_file.hpp"
+#include "zstd.hpp"
 #include "sldb.hpp"
 
 namespace {
@@ -910,10 +913,11 @@ struct RecordPump {
 // of whole blocks, member 0 skips the header's inflated bytes -- or plain SAM text: ranges cut anywhere behind the header,
 // read as they lie in the file (`names`: the header's reference names, which every member's SAM decoder needs) -- or bzip2
 // SAM: ranges cut at any byte behind the header's block, each read with slimm_bzip2_split_slack() bytes behind it (at most
-// to the file's end) so that its last block can finish; member 0 skips the header's decoded bytes.  The
+// to the file's end) so that its last block can finish; member 0 skips the header's decoded bytes -- or zstd SAM: ranges
+// cut where frames start (slimm_host_zstd_ranges), each announced and read exactly, without slack.  The
 // reader threads are split over the members, not multiplied (a command gets 16 CPUs).  Returns SLIMM_OK or the code of
 // what failed; *why says what.
-enum class SplitForm { Bam, BgzfSam, Sam, Bzip2Sam };
+enum class SplitForm { Bam, BgzfSam, Sam, Bzip2Sam, ZstdSam };
 struct SplitBuffers {   // (page-locked for the life of the group's contexts: they outlive the group)
     struct Map {
         uint8_t* p = nullptr;
@@ -934,12 +938,14 @@ struct SplitBuffers {   // (page-locked for the life of the group's contexts: th
 int read_split(slimm_group* grp, uint32_t G, const std::string& path, SplitForm form, const std::vector<std::string>& names,
                uint64_t header_bytes, size_t window_cap, SplitBuffers& bufs, std::string& why) {
     std::vector<uint64_t> off(G + 1, 0);
-    const bool bzip2 = form == SplitForm::Bzip2Sam;
-    const bool text = form == SplitForm::Sam || bzip2, sam = form != SplitForm::Bam;   // (text: the bytes as they lie in the file)
-    if (bzip2 ? (header_bytes >= (1ull << 32) || slimm_host_bzip2_ranges(path.c_str(), header_bytes, G, off.data()) != SLIMM_OK)
+    const bool bzip2 = form == SplitForm::Bzip2Sam, zstd = form == SplitForm::ZstdSam;
+    const bool text = form == SplitForm::Sam || bzip2 || zstd, sam = form != SplitForm::Bam;   // (text: the bytes as they lie in the file)
+    if (zstd    ? slimm_host_zstd_ranges(path.c_str(), header_bytes, G, off.data()) != SLIMM_OK
+        : bzip2 ? (header_bytes >= (1ull << 32) || slimm_host_bzip2_ranges(path.c_str(), header_bytes, G, off.data()) != SLIMM_OK)
         : text ? slimm_host_text_ranges(path.c_str(), header_bytes, G, off.data()) != SLIMM_OK
                : (header_bytes >= (1ull << 32) || slimm_host_bgzf_ranges(path.c_str(), header_bytes, G, off.data()) != SLIMM_OK)) {
-        why = bzip2  ? "the file's bzip2 streams could not be planned into ranges"
+        why = zstd   ? "the file's zstd frames could not be planned into ranges"
+              : bzip2 ? "the file's bzip2 streams could not be planned into ranges"
               : text ? "the file's text could not be planned into ranges"
                      : "the file's BGZF blocks could not be planned into ranges";
         return SLIMM_E_INVALID;
@@ -983,7 +989,7 @@ int read_split(slimm_group* grp, uint32_t G, const std::string& path, SplitForm 
         };
         int rc = sam ? slimm_set_reference_names(ctx, name_ptrs.data()) : SLIMM_OK;
         if (rc == SLIMM_OK) rc = slimm_set_input_mid_file(ctx, i > 0 ? 1 : 0, i + 1 < G ? 1 : 0);
-        if (rc == SLIMM_OK && bzip2) rc = slimm_set_input_range(ctx, off[i], off[i + 1]);
+        if (rc == SLIMM_OK && (bzip2 || zstd)) rc = slimm_set_input_range(ctx, off[i], off[i + 1]);
         if (rc == SLIMM_OK) rc = slimm_set_input_size_hint(ctx, off[i + 1] - off[i]);
         if (rc != SLIMM_OK) return failed(rc, slimm_last_error(ctx));
         for (auto* b : M.buf) (void)slimm_pin_host_buffer(ctx, b, cap);   // (pageable memory still works)
@@ -1062,6 +1068,8 @@ int read_split(slimm_group* grp, uint32_t G, const std::string& path, SplitForm 
             const uint64_t nb = static_cast<uint64_t>(n);
             if (bzip2)
                 rc = slimm_push_bzip2_sam_bytes(ctx, n ? M.buf[w] : nullptr, nb, skip, last ? 1 : 0, &got);
+            else if (zstd)
+                rc = slimm_push_zstd_sam_bytes(ctx, n ? M.buf[w] : nullptr, nb, skip, last ? 1 : 0, &got);
             else if (!n)   // (an empty range)
                 rc = sam ? slimm_push_sam_bytes(ctx, nullptr, 0, 1, &got) : slimm_push_bam_bytes(ctx, nullptr, 0, 1, &got);
             else if (text)
@@ -1101,17 +1109,57 @@ int read_split(slimm_group* grp, uint32_t G, const std::string& path, SplitForm 
         }
     const int rc = slimm_group_stitch_ranges(grp);
     if (rc != SLIMM_OK) why = slimm_group_last_error(grp);
+    if (zstd && g_trace && rc == SLIMM_OK) {   // (the members' counters summed: the whole file's)
+        uint64_t frames = 0, blocks = 0, text_bytes = 0;
+        for (uint32_t i = 0; i < G; ++i) {
+            uint64_t st[20] = {};
+            if (slimm_get_zstd_stats(slimm_group_context(grp, i), st) != SLIMM_OK) continue;
+            frames += st[0], blocks += st[2] + st[3] + st[4], text_bytes += st[16];
+        }
+        fprintf(stderr, "[trace] zstd SAM on the device: %llu frames, %llu blocks, %llu bytes of text\n", (unsigned long long)frames,
+                (unsigned long long)blocks, (unsigned long long)text_bytes);
+    }
     return rc;
 }
 
-// The files read_split takes: a regular file of BAM records, of SAM text, of SAM text in BGZF blocks, or of bzip2 SAM.  (A
-// plain gzip stream cannot be cut: it goes through one member.)
+// The files read_split takes whatever they hold: a regular file of BAM records, of SAM text, of SAM text in BGZF blocks, or
+// of bzip2 SAM.  (A plain gzip stream cannot be cut: it goes through one member.  zstd SAM: zstd_reads_by_byte_range.)
 bool reads_by_byte_range(const AlignmentFile& f) {
     return f.regular_file() && (f.is_bam() || f.compression() == Compression::None || f.compression() == Compression::Bgzf ||
                                 f.compression() == Compression::Bzip2);
 }
+// zstd SAM is cut where frames start and nowhere else (slimm_host_zstd_ranges): read_split takes a regular file whose plan
+// for G members has at least two ranges that are not empty -- a file of one frame has none -- and, with_floor, whose
+// members get slimm_zstd_split_floor() bytes each or more: (the file's size - the first legal cut) / G (the cap's re-read
+// does not ask: it has no other way).  The floor is a stated default, the codec's round size, not a measurement
+bool zstd_reads_by_byte_range(const AlignmentFile& f, const std::string& path, uint32_t G, bool with_floor) {
+    if (f.is_bam() || f.compression() != Compression::Zstd || !f.regular_file() || f.header_bytes() >= (1ull << 32) || G < 2u) return false;
+    std::vector<uint64_t> off(G + 1u, 0);
+    if (slimm_host_zstd_ranges(path.c_str(), f.header_bytes(), G, off.data()) != SLIMM_OK) return false;
+    uint32_t filled = 0;
+    for (uint32_t i = 0; i < G; ++i) filled += off[i + 1] > off[i] ? 1u : 0u;
+    if (filled < 2u) return false;
+    if (!with_floor) return true;
+    const int fd = open(path.c_str(), O_RDONLY);
+    if (fd < 0) return false;
+    const uint64_t size = off[G];
+    uint64_t first = 0;
+    const bool ok = zstd_header_end(
+        [&](uint64_t at, uint8_t* dst, size_t n) {
+            for (; n;) {
+                const ssize_t k = pread(fd, dst, n, static_cast<off_t>(at));
+                if (k <= 0) return false;
+                dst += k, at += static_cast<uint64_t>(k), n -= static_cast<size_t>(k);
+            }
+            return true;
+        },
+        size, f.header_bytes(), &first);
+    close(fd);
+    return ok && first <= size && (size - first) / G >= slimm_zstd_split_floor();
+}
 SplitForm split_form(const AlignmentFile& f) {
     if (f.is_bam()) return SplitForm::Bam;
+    if (f.compression() == Compression::Zstd) return SplitForm::ZstdSam;
     if (f.compression() == Compression::Bzip2) return SplitForm::Bzip2Sam;
     return f.compression() == Compression::Bgzf ? SplitForm::BgzfSam : SplitForm::Sam;
 }
@@ -1277,11 +1325,12 @@ std::unique_ptr<Reading> set_up(Session& S, const std::string& path, bool any_or
     // (a group takes a file through member 0's device decoders and deals the records device to device afterwards --
     // slimm_group_get_profiles: a GROUPED file in stretches cut at qName runs, any other order by key; what the pump does
     // not push raw -- --host-decode, pipes ... -- the host reader deals)
-    F->split_input = options.split_input && options.devices.size() > 1 && reads_by_byte_range(bam) &&
-                     !options.host_decode && !options.verify_grouping && !options.packed_records;
+    const bool may_split = options.split_input && options.devices.size() > 1 && !options.host_decode && !options.verify_grouping && !options.packed_records;
+    F->split_input = may_split && (reads_by_byte_range(bam) || zstd_reads_by_byte_range(bam, path, static_cast<uint32_t>(options.devices.size()), true));
     if (g_trace && !any_order && options.split_input && options.devices.size() > 1 && !bam.is_bam() && bam.compression() == Compression::Gzip)
         fprintf(stderr, "[trace] --split-input: a gzip stream is not cut by byte range; member 0 reads %s\n", path.c_str());
-    if (g_trace && !any_order && options.split_input && options.devices.size() > 1 && !bam.is_bam() && bam.compression() == Compression::Zstd)
+    // (a zstd file of one frame, or one whose members would get less than the floor; or the host decoders were asked for)
+    if (g_trace && !any_order && !F->split_input && options.split_input && options.devices.size() > 1 && !bam.is_bam() && bam.compression() == Compression::Zstd)
         fprintf(stderr, "[trace] --split-input: a zstd stream is not cut by byte range; member 0 reads %s\n", path.c_str());
     if (!F->split_input)
         F->pump.reset(new RecordPump(bam, F->check_words, true, options));
@@ -1487,8 +1536,15 @@ Outcome run_context(Session& S, Reading& F) {
     std::cerr << "[" << F.watch.lap() << " secs]" << std::endl;
 
     std::cerr << "Analysing alignments, reads and references ....... ";
-    const bool byte_ranges = reads_by_byte_range(F.bam);
+    // (zstd SAM: whether the file can be cut is asked only once the cap is met -- the plan reads the file; the floor is not
+    // consulted here.  A file of one frame cannot be cut and ends at the cap, as it did)
+    const bool zstd_file = !F.bam.is_bam() && F.bam.compression() == Compression::Zstd && F.bam.regular_file();
+    const bool byte_ranges = reads_by_byte_range(F.bam) || zstd_file;
     const Outcome pushed = push_file(S, F, Target{ctx}, byte_ranges ? OnCap::MoreMembers : OnCap::Fail);
+    if (pushed == Outcome::MoreMembers && zstd_file && !zstd_reads_by_byte_range(F.bam, F.path, 2u, false)) {
+        std::cerr << "slimm: pushing records: " << slimm_last_error(ctx) << "\n";
+        return Outcome::Failed;
+    }
     if (pushed == Outcome::MoreMembers) {
         // more records than one context takes: contexts of a group on this one device, each its own byte range of the
         // file (read_split) -- twice as many until each range fits

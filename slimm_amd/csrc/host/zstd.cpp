@@ -190,4 +190,24 @@ long ZstdReader::read(uint8_t* dst, size_t cap) {
     return static_cast<long>(out);
 }
 
+bool zstd_header_end(const std::function<bool(uint64_t, uint8_t*, size_t)>& read, uint64_t size, uint64_t skip, uint64_t* end) {
+    *end = 0;
+    if (!skip) return true;
+    uint64_t fed = 0;
+    ZstdReader r([&](uint8_t* d, size_t cap) -> size_t {
+        const size_t k = static_cast<size_t>(std::min<uint64_t>(cap, size - fed));
+        if (!k || !read(fed, d, k)) return 0;
+        fed += k;
+        return k;
+    });
+    std::vector<uint8_t> buf(1u << 20);
+    for (uint64_t left = skip; left;) {
+        const long got = r.read(buf.data(), static_cast<size_t>(std::min<uint64_t>(left, buf.size())));
+        if (got <= 0) return false;
+        left -= static_cast<uint64_t>(got);
+    }
+    *end = r.file_pos();
+    return !r.in_frame() || zs::walk_blocks(read, size, *end, r.frame().block_max, r.frame().has_checksum, end);
+}
+
 }  // namespace slimm

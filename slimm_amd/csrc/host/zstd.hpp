@@ -21,6 +21,11 @@ public:
     long read(uint8_t* dst, size_t cap);
     // "block at byte N: <cause>", "frame at byte N: <cause>", ... (without the reader's "zstd-compressed input ..." in front)
     const std::string& error() const { return err_; }
+    // where the reader stands: the file offset behind the last block it decoded (its checksum included), whether a frame
+    // goes on there, and that frame's header (the split planner walks on from here: split.hip)
+    uint64_t file_pos() const { return in_base_ + pos_; }
+    bool in_frame() const { return in_frame_; }
+    const zs::FrameHeader& frame() const { return fh_; }
     // one compressed block's content -> its text behind `text` (whose bytes from frame_lo on are the frame's so far):
     // the serial use of zstd_frame.h, also what the tests compare the device decoder's stages with
     static uint32_t decode_compressed(const uint8_t* content, uint32_t size, uint32_t block_max, uint64_t window, zs::Entropy& e, uint32_t rep[3],
@@ -44,5 +49,11 @@ private:
     size_t served_ = 0;           // ... of which [served_, size) have not been handed out
     std::string err_;
 };
+
+// A file of `size` bytes seen through read(offset, dst, n) (false: a read error): *end = the first byte behind the frame
+// that holds decoded byte skip - 1 -- the first place where a file split by byte range may be cut, since the first range
+// holds the whole SAM header (0 for skip = 0).  The frames up to there are decoded, the last one's block chain is walked to
+// its end.  false: they do not decode, or end in front of decoded byte `skip`
+bool zstd_header_end(const std::function<bool(uint64_t, uint8_t*, size_t)>& read, uint64_t size, uint64_t skip, uint64_t* end);
 
 }  // namespace slimm

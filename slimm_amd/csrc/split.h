@@ -1,5 +1,5 @@
 // Internal to the library: the per-member steps of slimm_group_stitch_ranges (group.hip drives them, split.hip holds them)
-// -- one file (BAM, SAM, BGZF SAM, bzip2 SAM) split by byte range over a group's members (include/slimm_hip.h, "ONE FILE SPLIT BY BYTE RANGE").
+// -- one file (BAM, SAM, BGZF SAM, bzip2 SAM, zstd SAM) split by byte range over a group's members (include/slimm_hip.h, "ONE FILE SPLIT BY BYTE RANGE").
 // Every step finishes its own device work before it returns: the next step may run on another member's device.
 #pragma once
 #include <stdint.h>
@@ -19,6 +19,10 @@ int split_range(slimm_ctx* c, SplitRange* out);
 // level, and the combined CRC of a stream over a cut is its marker's.  SLIMM_OK, or the code with the message on member *bad
 bool split_is_bzip2(const slimm_ctx* c);
 int split_bz2_chains(slimm_ctx* const* members, uint32_t n, uint32_t* bad);
+// zstd SAM: left to right on host scalars, every member's decoder stands between frames at its range's end with every byte of
+// the range read.  SLIMM_OK, or SLIMM_E_SPLIT with the message on member *bad
+bool split_is_zstd(const slimm_ctx* c);
+int split_zstd_ends(slimm_ctx* const* members, uint32_t n, uint32_t* bad);
 // the head of `right` as one more window of `left` (final: it must end with a complete record, else SLIMM_E_SPLIT)
 int split_append_head(slimm_ctx* left, slimm_ctx* right, bool final, uint64_t* n_records);
 // `right`'s first record against the last record of `left` (its carry): the same name clears the run-start bit and

@@ -1,18 +1,20 @@
-// One file -- BAM, SAM text, BGZF blocks of SAM text or bzip2 SAM -- split by byte range over a group's members
+// One file -- BAM, SAM text, BGZF blocks of SAM text, bzip2 SAM or zstd SAM -- split by byte range over a group's members
 // (include/slimm_hip.h, "ONE FILE SPLIT BY BYTE RANGE"): the host's plan of the ranges (slimm_host_bgzf_ranges,
-// slimm_host_text_ranges, slimm_host_bzip2_ranges) and the per-member steps of slimm_group_stitch_ranges (split.h; group.hip runs them cut by cut).  A range that starts inside
+// slimm_host_text_ranges, slimm_host_bzip2_ranges, slimm_host_zstd_ranges) and the per-member steps of slimm_group_stitch_ranges (split.h; group.hip runs them cut by cut).  A range that starts inside
 // the file guesses its first record as k_bam_pieces guesses a piece's (windows.hip, bam_decode.hip: k_bam_first_guess);
 // the member on its left confirms the guess one level up, as k_bam_verify confirms a piece's: its incomplete last record
 // followed by the right member's head must be whole records that end exactly where the guess begins.  A range of SAM
 // text guesses nothing: its first line starts behind its first newline (sam_decode.hip: k_sam_first_newline), and the
 // left member's last line must end with the head.  A range of bzip2 SAM starts at the first block of its own
-// (bzip2_decode.hip) and is text from there on; its chain of blocks is held against its neighbours' first (split_bz2_chains).  The reference reads one file with one reader (src/misc.hpp:498-522).
+// (bzip2_decode.hip) and is text from there on; its chain of blocks is held against its neighbours' first (split_bz2_chains).  A range of zstd SAM starts and ends where frames do
+// (zstd_decode.hip) and is text in between; that every member's frames ended at its range's end is checked first (split_zstd_ends).  The reference reads one file with one reader (src/misc.hpp:498-522).
 #include <fcntl.h>
 #include <sys/stat.h>
 #include <unistd.h>
 
 #include "context.h"
 #include "split.h"
+#include "host/zstd.cpp"   // (the host's serial zstd decoder, for the header's frames: the library holds no other copy of it)
 
 namespace {
 
@@ -195,6 +197,76 @@ int slimm_host_bzip2_ranges(const char* path, uint64_t skip, uint32_t n, uint64_
     return SLIMM_OK;
 }
 
+
+// zstd is cut where a frame -- or a skippable frame -- starts, and nowhere else: frames are independent of each other (the
+// window, the repeat offsets and the entropy tables start afresh at a frame header), and a frame cannot be entered in its
+// middle.  The header's frames are decoded here (host/zstd.cpp) for the first legal cut; a cut is the first start at or
+// behind its even share that zs::cut_candidate accepts (zstd_frame.h: the frame header parses, the block chain reaches the
+// frame's end, a magic or the file's end stands behind it).  What the walk cannot see -- the blocks' contents -- the members
+// and the stitch check.  The search for a cut gives up kZstdCutSearch bytes behind its target (SLIMM_FORCE zstd_cut_search=N):
+// the cut is then the next one found, or the file's size, and the range in between is empty -- a file of one frame has all
+// its cuts at its size, and member 0 reads it
+constexpr uint64_t kZstdCutSearch = 64ull << 20;
+int slimm_host_zstd_ranges(const char* path, uint64_t skip, uint32_t n, uint64_t* offsets_out) {
+    namespace zs = slimm::zs;
+    if (!path || !n || !offsets_out || skip >= (1ull << 32)) return SLIMM_E_INVALID;
+    File f;
+    struct stat sb;
+    if (stat(path, &sb) != 0 || !S_ISREG(sb.st_mode)) return SLIMM_E_INVALID;   // (asked before it is opened: opening a FIFO waits for its writer)
+    f.fd = open(path, O_RDONLY);
+    if (f.fd < 0 || fstat(f.fd, &sb) != 0 || !S_ISREG(sb.st_mode)) return SLIMM_E_INVALID;
+    f.size = static_cast<uint64_t>(sb.st_size);
+    auto read = [&](uint64_t off, uint8_t* dst, size_t k) { return off <= f.size && k <= f.size - off && f.read(off, dst, k); };
+    // no cut in front of the end of the frame that holds decoded byte skip - 1: member 0 holds the whole header
+    uint64_t first = 0;
+    if (!slimm::zstd_header_end(read, f.size, skip, &first)) return SLIMM_E_INVALID;
+    long v = 0;
+    const uint64_t search = slimm::forced("zstd_cut_search", &v) && v > 0 ? static_cast<uint64_t>(v) : kZstdCutSearch;
+    constexpr uint64_t kNone = ~0ull;
+    std::vector<uint8_t> buf(1u << 20);
+    // the first start at or behind t that is a cut, looked for in [t, t + search)
+    auto cut_at = [&](uint64_t t) -> uint64_t {
+        if (t >= f.size) return f.size;
+        const uint64_t stop = std::min(f.size, t + search);
+        for (uint64_t at = t; at < stop;) {
+            const size_t k = static_cast<size_t>(std::min<uint64_t>(buf.size(), f.size - at));
+            if (!f.read(at, buf.data(), k)) return kNone;
+            for (size_t i = 0; i + 4u <= k && at + i < stop; ++i) {
+                const uint8_t b = buf[i];
+                if (b != 0x28u && (b & 0xf0u) != 0x50u) continue;
+                const uint32_t magic = zs::le32(&buf[i]);
+                uint64_t end = 0;
+                if ((magic == zs::kMagic || (magic & 0xfffffff0u) == zs::kSkippable) && zs::cut_candidate(read, f.size, at + i, &end)) return at + i;
+            }
+            if (k < 4u) break;
+            at += k - 3u;
+        }
+        return kNone;
+    };
+    offsets_out[0] = 0;
+    offsets_out[n] = f.size;
+    for (uint32_t i = 1; i < n; ++i) offsets_out[i] = cut_at(first + static_cast<uint64_t>(static_cast<unsigned __int128>(f.size - first) * i / n));
+    for (uint32_t i = n; i-- > 1;)
+        if (offsets_out[i] == kNone) offsets_out[i] = offsets_out[i + 1];
+    for (uint32_t i = 1; i < n; ++i) offsets_out[i] = std::max(offsets_out[i], offsets_out[i - 1]);
+    // (SLIMM_FORCE zstd_split_wrong_cut: the second cut -- the first of two members -- lands one byte late, where no frame
+    // starts: the members, or the stitch, must refuse it)
+    if (n > 1 && slimm::forced("zstd_split_wrong_cut")) {
+        for (uint32_t i = std::min(2u, n - 1u); i >= 1u; --i) {
+            const uint64_t was = offsets_out[i];
+            if (was >= f.size || was == 0) continue;
+            for (uint32_t j = i; j < n && offsets_out[j] == was; ++j) ++offsets_out[j];
+            break;
+        }
+    }
+    return SLIMM_OK;
+}
+
+uint64_t slimm_zstd_split_floor(void) {
+    long v = 0;
+    return slimm::forced("zstd_split_floor", &v) && v >= 0 ? static_cast<uint64_t>(v) : slimm::kZstdRoundBytes;
+}
+
 }  // extern "C"
 
 namespace slimm {
@@ -248,10 +320,28 @@ int split_bz2_chains(slimm_ctx* const* members, uint32_t n, uint32_t* bad) {
     return SLIMM_OK;
 }
 
+bool split_is_zstd(const slimm_ctx* c) { return c->win.file.stream.codec == WindowPipeline::File::Codec::Zstd; }
+
+int split_zstd_ends(slimm_ctx* const* members, uint32_t n, uint32_t* bad) {
+    for (uint32_t k = 0; k < n; ++k) {
+        slimm_ctx* c = members[k];
+        const WindowPipeline::Announced& A = c->win.announced;
+        const WindowPipeline::File::Stream& T = c->win.file.stream;
+        const uint64_t at = T.base + (T.bit >> 3);   // (the file's byte its decoder stands at)
+        *bad = k;
+        if (!split_is_zstd(c) || !A.has_range)
+            return fail(c, SLIMM_E_INVALID, "a range of a zstd file: slimm_set_input_range tells where it lies");
+        if (c->win.file.zst.stage != WindowPipeline::File::Zstd::Between || at != A.range_end || T.pend.size() != (T.bit >> 3))
+            return fail(c, SLIMM_E_SPLIT, "zstd: the frames of member %u end at byte %llu, its range at byte %llu: the range does not end at a frame boundary", k,
+                        static_cast<unsigned long long>(at), static_cast<unsigned long long>(A.range_end));
+    }
+    return SLIMM_OK;
+}
+
 int split_range(slimm_ctx* c, SplitRange* out) {
     if (!c || !out) return SLIMM_E_INVALID;
     if (c->device < 0 || !c->win.file.active || !c->win.file.closed)
-        return fail(c, SLIMM_E_INVALID, "a range of a split file: a range of BAM, SAM, BGZF SAM or bzip2 SAM pushed to its end");
+        return fail(c, SLIMM_E_INVALID, "a range of a split file: a range of BAM, SAM, BGZF SAM, bzip2 SAM or zstd SAM pushed to its end");
     if (split_is_bzip2(c) && !c->win.announced.has_range)
         return fail(c, SLIMM_E_INVALID, "a range of a bzip2 file: slimm_set_input_range tells where it lies");
     out->found_start = c->win.file.found_start || !c->win.announced.starts_mid;

@@ -306,6 +306,10 @@ void gz_trace_file(const slimm_ctx* c);
 // walked on the host), decodes their literals and sequences on the device and leaves the round's blocks, with their text
 // lengths, in file.zst.ready.  zs_emit: the text built behind the history, resolved, and written to dst; zs_check, behind
 // the window's launch: the content checksums of the frames that ended
+// (A byte range of a split file -- Announced::has_range --: the range starts at a frame and ends between frames, both
+// SLIMM_E_SPLIT otherwise; nothing in front of the range exists for it, and an empty range, or one of skippable frames only,
+// decodes no text)
+constexpr uint64_t kZstdRoundBytes = 32ull << 20;   // compressed bytes gathered for a round; also the least a member's range of a split file is worth (slimm_zstd_split_floor)
 int zs_round(slimm_ctx* c, bool last);
 bool zs_next_window(const slimm_ctx* c, uint64_t cap, uint64_t* n);
 int zs_emit(slimm_ctx* c, uint8_t* dst, uint64_t cap, uint64_t* n_out, uint8_t* last_byte);

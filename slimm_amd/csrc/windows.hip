@@ -316,6 +316,7 @@ struct StreamCodec {
     const char* round_key;
     uint64_t round_bytes;
     bool cut_by_range;       // a byte range of a split file may cut it (slimm_set_input_mid_file)
+    bool cut_at_frames;      // ... only where the caller's plan found a frame start: not without slimm_set_input_range
     int (*round)(slimm_ctx*, bool last);
     bool (*next_window)(const slimm_ctx*, uint64_t cap, uint64_t* n);
     int (*emit)(slimm_ctx*, uint8_t* dst, uint64_t cap, uint64_t* n_out, uint8_t* last_byte);
@@ -332,12 +333,12 @@ struct StreamCodec {
 const StreamCodec kCodecs[] = {
     {},
     // (ended: the range's chain has stopped, what comes now are bytes of the slack)
-    {"bzip2", "bzip2_round", 32ull << 20, true, bz2_decode_batch, bz2_next_window, bz2_emit, nullptr, bz2_trace_file, nullptr,
+    {"bzip2", "bzip2_round", 32ull << 20, true, false, bz2_decode_batch, bz2_next_window, bz2_emit, nullptr, bz2_trace_file, nullptr,
      [](const File& F) { return F.bz2.chain.ended; }, nullptr, 0, 0},
-    {"gzip", "gzip_round", 32ull << 20, false, gz_round, gz_next_window, gz_emit, nullptr, gz_trace_file,
+    {"gzip", "gzip_round", 32ull << 20, false, false, gz_round, gz_next_window, gz_emit, nullptr, gz_trace_file,
      [](const File& F) { return static_cast<int>(F.gz.stage); }, nullptr, [](WindowPipeline& W) { return W.gz_stats; },
      WindowPipeline::kGzStats, WindowPipeline::kGzCompressed},
-    {"zstd", "zstd_round", 32ull << 20, false, zs_round, zs_next_window, zs_emit, zs_check, zs_trace_file,
+    {"zstd", "zstd_round", kZstdRoundBytes, true, true, zs_round, zs_next_window, zs_emit, zs_check, zs_trace_file,
      [](const File& F) { return static_cast<int>(F.zst.stage); }, nullptr, [](WindowPipeline& W) { return W.zs_stats; },
      WindowPipeline::kZsStats, WindowPipeline::kZsCompressedBytes},
 };
@@ -398,6 +399,8 @@ int check_push(slimm_ctx* c, Push& p) {
     if (F.active && mine != p.codec)   // (two codecs: the text names the first of them in Codec's order)
         return fail(c, SLIMM_E_INVALID, "%s SAM bytes and the other forms do not mix within a file", codec_of(named).name);
     if (K.name && !K.cut_by_range && mid) return fail(c, SLIMM_E_INVALID, "a %s stream is not cut by byte range", K.name);
+    if (K.name && K.cut_at_frames && mid && !c->win.announced.has_range)
+        return fail(c, SLIMM_E_INVALID, "a %s stream is not cut by byte range unless its range is announced (slimm_set_input_range) and starts at a frame", K.name);
     if (K.name && p.skip && F.active) return fail(c, SLIMM_E_INVALID, "skip: only in front of a file's first records");
     if (K.name && K.cut_by_range && !F.active && mid && !c->win.announced.has_range)
         return fail(c, SLIMM_E_INVALID, "slimm_set_input_range first: a range of a %s file is cut at bits, told by where it lies in the file", K.name);

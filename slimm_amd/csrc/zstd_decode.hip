@@ -210,8 +210,20 @@ int zs_round(slimm_ctx* c, bool last) {
     long cap_text = 0;
     if (!forced("zstd_round_text", &cap_text) || cap_text <= 0) cap_text = static_cast<long>(kZsRoundText);
     auto at = [&](uint64_t byte) { return std::to_string(T.base + byte); };
+    // a byte range of a split file (check_push: its range is announced).  It starts at a frame and ends between frames, or
+    // the cut is refused -- SLIMM_E_SPLIT, no verdict on the file: the caller reads it through one context
+    const WindowPipeline::Announced& A = W.announced;
+    const bool starts_mid = A.has_range && A.starts_mid, ends_mid = A.has_range && A.ends_mid;
+    auto no_start = [&](uint64_t byte) {
+        return fail(c, SLIMM_E_SPLIT, "zstd: the range starts at byte %s, where no frame starts", at(byte).c_str());
+    };
+    auto no_end = [&](const std::string& where) {
+        return fail(c, SLIMM_E_SPLIT, "zstd: %s runs past byte %llu: the range does not end at a frame boundary", where.c_str(),
+                    static_cast<unsigned long long>(A.range_end));
+    };
     // what a stage lacks: more bytes may come, or the file ends inside it
     auto wait_or = [&](const std::string& where) {
+        if (last && ends_mid) return no_end(where);
         if (last) return zs_fail(c, where, zs::kRanOut);
         T.waiting = true;
         return static_cast<int>(SLIMM_OK);
@@ -224,11 +236,13 @@ int zs_round(slimm_ctx* c, bool last) {
     while (!full && !T.waiting) {
         const uint64_t avail = n_bytes - pos;
         if (Z.stage == Stage::Between) {
-            if (avail == 0 && (Z.any_frames > 0 || !last)) {
-                T.waiting = true;   // (the file may end here)
+            if (avail == 0 && (Z.any_frames > 0 || !last || starts_mid || ends_mid)) {
+                T.waiting = true;   // (the file may end here; a range may be empty)
                 break;
             }
             if (avail < 4u) {
+                if (last && ends_mid) return no_end("what starts at byte " + at(pos));
+                if (last && starts_mid && Z.any_frames == 0) return no_start(pos);
                 if (last) return zs_fail(c, "at byte " + at(pos), Z.any_frames == 0 || zs::magic_prefix(p + pos, avail) ? zs::kRanOut : zs::kNoFrame);
                 T.waiting = true;
                 break;
@@ -244,12 +258,14 @@ int zs_round(slimm_ctx* c, bool last) {
                 ++stats[WindowPipeline::kZsSkippable];
                 continue;
             }
+            if (magic != zs::kMagic && starts_mid && Z.any_frames == 0) return no_start(pos);
             if (magic != zs::kMagic) return zs_fail(c, "at byte " + at(pos), Z.any_frames ? zs::kNoFrame : zs::kRanOut);
             const uint32_t hs = zs::frame_header(p + pos, avail, Z.fh);
             if (hs == zs::kRanOut) {
                 SLIMM_TRY(wait_or("frame header at byte " + at(pos)));
                 break;
             }
+            if (hs != zs::kOk && starts_mid && Z.any_frames == 0) return no_start(pos);   // (the magic's bytes, inside some frame)
             if (hs != zs::kOk) return zs_fail(c, "frame header at byte " + at(pos), hs);
             Z.frame_at = T.base + pos;
             pos += Z.fh.bytes;

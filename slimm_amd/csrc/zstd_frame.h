@@ -708,5 +708,64 @@ SLIMM_ZS_HD inline uint32_t literal_streams(const uint8_t* base, const Block& b,
     return kOk;
 }
 
+// ---- where a file of frames may be cut (split.hip: slimm_host_zstd_ranges), on the host.  The file is seen through
+// read(offset, dst, n) -> bool (false: a read error, or bytes behind `size`): a frame's content is never loaded, only the
+// 3 bytes of every block header.
+// The block chain from the block header at `at`: every block of a type that exists and no larger than block_max, up to a
+// last block, a stated checksum behind it, all within `size`.  *end: the first byte behind the frame
+template <typename Read>
+inline bool walk_blocks(Read&& read, uint64_t size, uint64_t at, uint32_t block_max, bool has_checksum, uint64_t* end) {
+    for (;;) {   // (every turn moves at least 3 bytes on: it ends at `size` at the latest)
+        uint8_t b[3];
+        if (at > size || size - at < 3u || !read(at, b, 3)) return false;
+        const uint32_t h = le24(b), type = (h >> 1) & 3u, len = h >> 3;
+        if (type == 3u || len > block_max) return false;
+        const uint64_t content = type == kRleBlock ? 1u : len;
+        at += 3u;
+        if (size - at < content) return false;
+        at += content;
+        if (h & 1u) break;
+    }
+    if (has_checksum) {
+        if (size - at < 4u) return false;
+        at += 4u;
+    }
+    *end = at;
+    return true;
+}
+// Is `at` the file's end, or do a frame's or a skippable frame's magic bytes stand there?
+template <typename Read>
+inline bool frame_may_start(Read&& read, uint64_t size, uint64_t at) {
+    if (at == size) return true;
+    uint8_t m[4];
+    if (at > size || size - at < 4u || !read(at, m, 4)) return false;
+    const uint32_t magic = le32(m);
+    return magic == kMagic || (magic & 0xfffffff0u) == kSkippable;
+}
+// May the file be cut in front of byte `at`?  A frame starts there whose header parses (frame_header: reserved bit, window,
+// dictionary) and whose block chain reaches a last block and a stated checksum inside the file, or a skippable frame
+// whose length fits; and behind it the file ends, or the next magic stands.  *end: the first byte behind what starts at `at`
+template <typename Read>
+inline bool cut_candidate(Read&& read, uint64_t size, uint64_t at, uint64_t* end) {
+    uint8_t h[18];   // (a frame header is at most 4 + 1 + 1 + 4 + 8 bytes)
+    if (at >= size || size - at < 8u) return false;   // (the smallest frame: magic, descriptor, one empty block)
+    const uint64_t n = size - at < sizeof(h) ? size - at : sizeof(h);
+    if (!read(at, h, static_cast<size_t>(n))) return false;
+    const uint32_t magic = le32(h);
+    uint64_t e = 0;
+    if ((magic & 0xfffffff0u) == kSkippable) {
+        const uint64_t len = le32(h + 4);
+        if (size - at - 8u < len) return false;
+        e = at + 8u + len;
+    } else {
+        FrameHeader fh;
+        if (magic != kMagic || frame_header(h, n, fh) != kOk) return false;
+        if (!walk_blocks(read, size, at + fh.bytes, fh.block_max, fh.has_checksum, &e)) return false;
+    }
+    if (!frame_may_start(read, size, e)) return false;
+    *end = e;
+    return true;
+}
+
 }  // namespace zs
 }  // namespace slimm
