@@ -17,6 +17,11 @@ g++ -std=c++17 -g -O1 -fsanitize=thread "$ROOT/tests/native/san_readers.cpp" "$R
     "$ROOT/slimm_amd/csrc/host/bzip2.cpp" "$ROOT/slimm_amd/csrc/host/zstd.cpp" "$ROOT/slimm_amd/csrc/host/sldb.cpp" -lz -lpthread -ldl -o "$W/tsan_readers"
 g++ -std=c++17 -g -O1 -fsanitize=thread -I"$ROOT/include" "$ROOT/slimm_amd/csrc/host/slimm_main.cpp" "$ROOT/slimm_amd/csrc/host/alignment_file.cpp" \
     "$ROOT/slimm_amd/csrc/host/bzip2.cpp" "$ROOT/slimm_amd/csrc/host/zstd.cpp" "$ROOT/slimm_amd/csrc/host/sldb.cpp" -lz -lpthread -ldl -o "$W/tsan_slimm"
+# the host emulator for a command whose threads drive several contexts at once (tests/native/emu_one_launch.cpp)
+if [ -e "$ROOT/tests/native/libslimm_emu.so" ]; then
+    g++ -std=c++17 -g -O1 -shared -fPIC -I"$ROOT/tests/native/hip_emu" "$ROOT/tests/native/emu_one_launch.cpp" -L"$ROOT/tests/native" \
+        -Wl,--no-as-needed -lslimm_emu -Wl,-rpath,"$ROOT/tests/native" -ldl -o "$W/libslimm_emu_mt.so"
+fi
 cd "$ROOT"
 python - "$W" <<'PY'
 import os, subprocess, sys
@@ -119,6 +124,21 @@ if os.path.exists(emu) and os.path.exists(f"{d}/tsan_slimm"):
                                text=True, errors="replace", env=dict(os.environ, SLIMM_HIP_LIB=emu))
             if r.returncode or "ThreadSanitizer" in r.stderr:
                 bad += 1; print("SANITIZER OUTPUT (slimm under TSan):\n" + r.stderr[-4000:])
+    # --file-per-device: three slot threads over a directory of six files (the config-1 records in six parts, SAM and BAM),
+    # each with its own reader, pump and context; the blocks of the log and the shared database are what they meet at.  The
+    # emulator runs one kernel at a time: libslimm_emu_mt.so (built above) takes the launches of all threads in turn
+    import numpy as np
+    w = cases[2]
+    os.makedirs(f"{d}/fpd_in", exist_ok=True)
+    os.makedirs(f"{d}/fpd_out", exist_ok=True)
+    cuts = [int(len(w.records) * c) for c in (0.0, 0.10, 0.25, 0.45, 0.60, 0.82, 1.0)]
+    for k in range(6):
+        (write_sam if k % 2 == 0 else write_bam)(f"{d}/fpd_in/s{k}.{'sam' if k % 2 == 0 else 'bam'}", w.ref_names, w.ref_len,
+                                                 w.records.take(np.arange(cuts[k], cuts[k + 1])), read_len=w.avg_read_len)
+    r = subprocess.run([f"{d}/tsan_slimm", "-d", "--devices", "0,0,0", "--file-per-device", "-ro", "-co", "-v", "-o", f"{d}/fpd_out/", f"{d}/c2.sldb",
+                        f"{d}/fpd_in"], capture_output=True, text=True, errors="replace", env=dict(os.environ, SLIMM_HIP_LIB=f"{d}/libslimm_emu_mt.so", SLIMM_TRACE="cli"))
+    if r.returncode or "ThreadSanitizer" in r.stderr or "5 handed to 3 slots" not in r.stderr:
+        bad += 1; print("SANITIZER OUTPUT (slimm --file-per-device under TSan):\n" + r.stderr[-4000:])
     print("slimm (command, emulated device) under ThreadSanitizer: done")
 print("sanitizer findings:", bad)
 sys.exit(1 if bad else 0)

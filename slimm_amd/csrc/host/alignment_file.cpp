@@ -160,10 +160,28 @@ AlignmentFile::Settings& AlignmentFile::settings() {
     return s;
 }
 
+// as many threads as the process may keep busy: the logical CPUs, or the cgroup's CPU quota when that is less (a
+// container on a 256-thread host may be held to 16 cores' worth; twice the quota keeps them fed across the
+// stages' short waits); 64 at the most
+unsigned AlignmentFile::default_threads() {
+    unsigned hw = std::thread::hardware_concurrency();
+    hw = hw ? hw : 1u;
+    if (FILE* q = fopen("/sys/fs/cgroup/cpu.max", "r")) {
+        char quota[32] = {0};
+        unsigned long period = 0;
+        if (fscanf(q, "%31s %lu", quota, &period) == 2 && strcmp(quota, "max") != 0 && period > 0) {
+            const unsigned long cores = (strtoul(quota, nullptr, 10) + period - 1) / period;
+            if (cores > 0) hw = std::min<unsigned>(hw, static_cast<unsigned>(2 * cores));
+        }
+        fclose(q);
+    }
+    return std::max(1u, std::min(hw, 64u));
+}
+
 void AlignmentFile::close() {
     if (fp_ && settings().trace && (ms_read_ + ms_inflate_ + ms_find_ + ms_decode_) > 0 && n_windows_ > 1)
-        fprintf(stderr, "[trace] reader: read + parse blocks %.1f ms, inflate %.1f ms, record starts %.1f ms, decode + hash %.1f ms, "
-                        "name check %.1f ms; %u windows, waited %.1f ms for the prefetch thread (%u threads, inflate by %s)\n", ms_read_, ms_inflate_, ms_find_,
+        fprintf(stderr, "%sreader: read + parse blocks %.1f ms, inflate %.1f ms, record starts %.1f ms, decode + hash %.1f ms, "
+                        "name check %.1f ms; %u windows, waited %.1f ms for the prefetch thread (%u threads, inflate by %s)\n", trace_head_.c_str(), ms_read_, ms_inflate_, ms_find_,
                 ms_decode_, ms_names_, n_windows_, ms_wait_, threads_, inflate_backend());
     ms_read_ = ms_inflate_ = ms_find_ = ms_decode_ = ms_names_ = ms_wait_ = 0;
     n_windows_ = 0;
@@ -198,24 +216,7 @@ bool AlignmentFile::open(const std::string& path) {
     have_last_ = false;
     last_short_ = false;
     q18_short_starts_ = q18_short_to_plain_ = 0;
-    {
-        // as many threads as the process may keep busy: the logical CPUs, or the cgroup's CPU quota when that is less (a
-        // container on a 256-thread host may be held to 16 cores' worth; twice the quota keeps them fed across the
-        // stages' short waits)
-        const unsigned asked = settings().threads;
-        unsigned hw = std::thread::hardware_concurrency();
-        hw = hw ? hw : 1u;
-        if (FILE* q = fopen("/sys/fs/cgroup/cpu.max", "r")) {
-            char quota[32] = {0};
-            unsigned long period = 0;
-            if (fscanf(q, "%31s %lu", quota, &period) == 2 && strcmp(quota, "max") != 0 && period > 0) {
-                const unsigned long cores = (strtoul(quota, nullptr, 10) + period - 1) / period;
-                if (cores > 0) hw = std::min<unsigned>(hw, static_cast<unsigned>(2 * cores));
-            }
-            fclose(q);
-        }
-        threads_ = asked ? asked : std::max(1u, std::min(hw, 64u));
-    }
+    threads_ = settings().threads ? settings().threads : default_threads();
     workers_.reset(new Workers(threads_));
     inflaters_.reset(new Workers(threads_));  // (the prefetch thread's own: its jobs run beside the decode jobs)
     file_eof_ = false;

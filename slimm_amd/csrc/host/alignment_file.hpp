@@ -75,6 +75,10 @@ public:
         bool no_mmap = false, trace = false;
     };
     static Settings& settings();
+    // what threads = 0 comes to (the command's --file-per-device divides it among the files open at once)
+    static unsigned default_threads();
+    // what the reader's trace line starts with (the command's --file-per-device puts the file's index there)
+    void set_trace_head(const std::string& head) { trace_head_ = head; }
     // false + error() on failure (reference: "Could not open <path>!", src/misc.hpp:500-504)
     bool open(const std::string& path);
     void close();
@@ -229,6 +233,7 @@ private:
     };
     std::vector<Block> blocks_;
     unsigned threads_ = 1;
+    std::string trace_head_ = "[trace] ";
     double ms_read_ = 0, ms_inflate_ = 0, ms_find_ = 0, ms_decode_ = 0, ms_names_ = 0, ms_wait_ = 0;  // SLIMM_TRACE=cli
     unsigned n_windows_ = 0;
     class Workers;  // the decode threads, started once per file

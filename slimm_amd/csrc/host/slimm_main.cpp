@@ -3,7 +3,8 @@
 // Same options, defaults and output files as the reference; the per-file driver follows slimm::get_profiles()
 // (reference src/slimm.hpp:395-496) step for step, with the three hot phases running on the MI355X through
 // include/slimm_hip.h.  Extra options (no reference counterpart): --device N, --query-grouped, --any-order,
-// --dump-records (decode only, for reader tests on machines without a GPU).
+// --dump-records (decode only, for reader tests on machines without a GPU), --devices with --split-input (one file over
+// several devices) or with --file-per-device (the files of a directory side by side, one per listed device).
 #include <dirent.h>
 #include <fcntl.h>
 #include <sys/stat.h>
@@ -26,6 +27,7 @@
 #include <memory>
 #include <mutex>
 #include <numeric>
+#include <shared_mutex>
 #include <sstream>
 #include <string>
 #include <thread>
@@ -193,6 +195,10 @@ struct Options {  // arg_options, reference src/slimm.hpp:49-87
     unsigned window_mb = 0;        // --window-mb N: bytes per window buffer (tests make windows smaller than a record)
     int propagation_walk = SLIMM_WALK_DEFAULT;  // --propagation-walk default|reversed (include/slimm_hip.h, "THE ORDER OF THE PROPAGATION")
     bool split_input = false;      // --split-input (with --devices): every member reads its own byte range of a BAM / SAM / BGZF SAM / bzip2 SAM
+    // --file-per-device (with --devices): the listed devices are SLOTS that take whole files, one at a time, each through one
+    // context on its device (run_file_per_device); parse() moves the list here and leaves `devices` empty: no group
+    bool file_per_device = false;
+    std::vector<int> slots;
 };
 bool g_trace = false;              // SLIMM_TRACE=cli (or all): millisecond marks of the stages on stderr
 
@@ -258,6 +264,8 @@ void usage() {
                  "  -co, --coverage-output        write raw coverage statistics\n"
                  "  -v,  --verbose\n"
                  "       --device N | --devices N,M,... [--split-input] | --query-grouped | --any-order | --dump-records | --dump-raw\n"
+                 "       --devices N,M,... --file-per-device   every listed device (one may be listed twice) is a slot that takes whole\n"
+                 "                                     files of a directory, one at a time; the outputs are those of --device N\n"
                  "       --host-decode | --packed-records | --verify-grouping | --device-inflate K | --window-mb N |\n"
                  "       --decode-threads N | --no-mmap     (SLIMM_TRACE=cli: stage marks on stderr)\n"
                  "       --propagation-walk default|reversed   order in which the directly counted taxa hand their read counts up\n"
@@ -334,6 +342,8 @@ int parse(int argc, char** argv, Options& o) {
             if (!o.devices.empty()) o.device = o.devices[0];
         } else if (a == "--split-input") {
             o.split_input = true;
+        } else if (a == "--file-per-device") {
+            o.file_per_device = true;
         } else if (a == "--propagation-walk") {
             if (!value(v)) return 1;
             if (v != "default" && v != "reversed") {
@@ -375,6 +385,19 @@ int parse(int argc, char** argv, Options& o) {
         } else {
             pos.push_back(a);
         }
+    }
+    if (o.file_per_device) {
+        if (o.devices.empty()) {
+            std::cerr << "slimm: --file-per-device needs --devices a,b,...: one slot per entry, each takes whole files\n";
+            return 1;
+        }
+        if (o.split_input) {
+            std::cerr << "slimm: --file-per-device and --split-input exclude each other: whole files on separate devices, or one file "
+                         "over a group's members\n";
+            return 1;
+        }
+        o.slots.swap(o.devices);
+        o.device = o.slots[0];
     }
     if (o.dump_records && pos.size() == 1) {
         o.input_path = pos[0];
@@ -442,12 +465,41 @@ int dump_records(const Options& o) {
     return 0;
 }
 
-struct Session {  // what the one `slimm` object of the reference keeps across files
-    Options options;
+// What every file of a run reads: filled by main() before the first file, read-only from then on -- but for the zero lineages
+// that set_up adds to db.ac_taxid (Q13), under db_mu: --file-per-device sets files up side by side.
+struct Shared {
     SlimmDatabase db;
+    std::shared_mutex db_mu;
     std::vector<std::string> input_paths;
+};
+
+// Where a file's stderr lines go: to std::cerr as they come, or -- --file-per-device -- into a block that is printed whole once
+// the blocks of the files before it are out.  Only the thread that runs the file's stages writes here.  The [trace] marks go
+// to stderr at once either way, from several threads; `head` starts them and names the file where files run side by side.
+struct FileLog {
+    bool collect = false;
+    std::ostringstream block;
+    std::string head = "[trace] ";
+    std::ostream& out() { return collect ? static_cast<std::ostream&>(block) : std::cerr; }
+};
+
+// What the one `slimm` object of the reference keeps across files (Q8): the values that a file sets for the files behind it.
+// A slot of --file-per-device works on a copy of its own, taken once no file can change them any more (settled).
+struct Session {
+    Options options;   // (bin_width and min_reads: 0 until a file sets them)
     float cc_cache = 0.0f, ucc_cache = 0.0f;  // src/slimm.hpp:155-156: never cleared by reset() (Q8)
     uint32_t total_hits = 0;
+    Shared* shared = nullptr;
+    FileLog* log = nullptr;   // the file at hand
+    std::ostream& err() const { return log->out(); }
+    const char* trace_head() const { return log->head.c_str(); }
+    // No file behind this point changes a carried value, and none reads one that another file wrote: set_up takes the bin
+    // width from a file only while it is 0, the library derives min_reads only while it is 0 (HostProfile::set_coverage_strided)
+    // and computes a cut-off only while its cache is 0.0 and the quantile below 1.0 (HostProfile::coverage_cut_off,
+    // uniq_coverage_cut_off); what slimm_get_cutoff_cache hands back is then what slimm_set_cutoff_cache was given.
+    bool settled() const {
+        return options.bin_width != 0 && options.min_reads != 0 && (options.cov_cut_off >= 1.0f || (cc_cache != 0.0f && ucc_cache != 0.0f));
+    }
 };
 
 // What one reading of a file comes to
@@ -461,7 +513,7 @@ enum class Outcome {
 #define CHECK(ctx, call)                                                            \
     do {                                                                            \
         if ((call) < 0) {                                                           \
-            std::cerr << "slimm: " << #call << ": " << slimm_last_error(ctx) << "\n"; \
+            S.err() << "slimm: " << #call << ": " << slimm_last_error(ctx) << "\n";  \
             return Outcome::Failed;                                                 \
         }                                                                           \
     } while (0)
@@ -477,10 +529,10 @@ void set_size_hint(slimm_ctx* ctx, const std::string& path) {
 }
 
 // the file from its first record again; false after printing why it could not be opened
-bool reopen(AlignmentFile& bam, const std::string& path) {
+bool reopen(AlignmentFile& bam, const std::string& path, std::ostream& err) {
     bam.close();
     if (bam.open(path)) return true;
-    std::cerr << bam.error() << "\n";
+    err << bam.error() << "\n";
     return false;
 }
 
@@ -503,18 +555,19 @@ float depth_of(const uint32_t* bins, uint32_t n, uint32_t nz) {  // reference_co
 // SLIMM_TRACE=cli: millisecond marks of the per-file stages on stderr (the reference's own timer prints whole seconds)
 struct Trace {
     bool on = g_trace;
+    std::string head = "[trace] ";   // (FileLog::head)
     std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
     void mark(const char* what) {
         if (!on) return;
         auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[trace] %-34s %9.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t).count());
+        fprintf(stderr, "%s%-34s %9.2f ms\n", head.c_str(), what, std::chrono::duration<double, std::milli>(now - t).count());
         t = now;
     }
 };
 
 // SLIMM_TRACE=cli: what the file's end holds -- device memory in use (hipMemGetInfo: everything on the device), the window
 // pipeline's share of it, and the process's peak resident set
-void trace_memory(slimm_ctx* ctx) {
+void trace_memory(slimm_ctx* ctx, const char* head) {
     uint64_t used = 0, total = 0, win = 0;
     (void)slimm_device_memory(ctx, &used, &total);
     (void)slimm_window_memory(ctx, &win);
@@ -525,7 +578,7 @@ void trace_memory(slimm_ctx* ctx) {
             if (sscanf(line, "VmHWM: %ld kB", &hwm_kb) == 1) break;
         fclose(f);
     }
-    fprintf(stderr, "[trace] device memory in use %.2f GB of %.0f GB (window pipeline %.2f GB); host peak resident set %.2f GB\n", used / 1e9,
+    fprintf(stderr, "%sdevice memory in use %.2f GB of %.0f GB (window pipeline %.2f GB); host peak resident set %.2f GB\n", head, used / 1e9,
             total / 1e9, win / 1e9, hwm_kb / 1e6);
 }
 
@@ -588,6 +641,7 @@ struct RecordPump {
     // record boundaries, reads the fields and compares / hashes the names (slimm_amd/csrc/bam_decode.hip).  The host
     // walked every inflated byte three times for that.  --host-decode keeps the host decoder.
     const bool raw;
+    const std::string head;   // what the [trace] lines start with (FileLog::head)
     // bytes per window buffer (--window-mb: tests make windows smaller than a record)
     static size_t& raw_cap_setting() {
         static size_t cap = 192u << 20;
@@ -631,11 +685,12 @@ struct RecordPump {
     uint64_t raw_records = 0;
     double raw_push_ms = 0;
 
-    RecordPump(AlignmentFile& f, bool check_words, bool device_decode, const Options& o)
+    RecordPump(AlignmentFile& f, bool check_words, bool device_decode, const Options& o, const std::string& trace_head)
         : bam(f), want_check(check_words),
           marked(!check_words && !o.verify_grouping && !o.packed_records),
           // (SAM text from anything but a regular file -- a pipe -- goes through the host decoder's buffered reads)
-          raw(device_decode && !o.verify_grouping && !o.packed_records && !o.host_decode && (f.is_bam() || f.regular_file())) {
+          raw(device_decode && !o.verify_grouping && !o.packed_records && !o.host_decode && (f.is_bam() || f.regular_file())),
+          head(trace_head) {
         device_period = o.device_inflate;
         device_window = std::min<size_t>(10 * raw_cap(), 1900u << 20);
         th = std::thread([this] { raw ? run_raw() : run(); });  // (in the body: every member is initialised by now)
@@ -765,11 +820,11 @@ struct RecordPump {
                 uint64_t st[20] = {};
                 end_traced = true;
                 if (zstd && slimm_get_zstd_stats(c, st) == SLIMM_OK)
-                    fprintf(stderr, "[trace] zstd SAM on the device: %llu frames, %llu blocks, %llu bytes of text\n", (unsigned long long)st[0],
+                    fprintf(stderr, "%szstd SAM on the device: %llu frames, %llu blocks, %llu bytes of text\n", head.c_str(), (unsigned long long)st[0],
                             (unsigned long long)(st[2] + st[3] + st[4]), (unsigned long long)st[16]);
                 if (gzip && slimm_get_gzip_stats(c, st) == SLIMM_OK)
-                    fprintf(stderr, "[trace] gzip SAM on the device: %llu members, %llu chunks (%llu candidates dropped), %llu bytes of text\n",
-                            (unsigned long long)st[0], (unsigned long long)st[1], (unsigned long long)st[3], (unsigned long long)st[9]);
+                    fprintf(stderr, "%sgzip SAM on the device: %llu members, %llu chunks (%llu candidates dropped), %llu bytes of text\n",
+                            head.c_str(), (unsigned long long)st[0], (unsigned long long)st[1], (unsigned long long)st[3], (unsigned long long)st[9]);
             }
             {
                 // (a window's buffer is the library's until the NEXT push returns: its copy runs beside the work on the
@@ -891,17 +946,17 @@ struct RecordPump {
     void report(bool group) const {
         if (group) {
             if (raw)
-                fprintf(stderr, "[trace] device decode on member 0: slimm_push_bam_bytes %.2f ms for %llu records, pusher waited %.2f ms for windows\n",
-                        raw_push_ms, static_cast<unsigned long long>(raw_records), wait_ms);
+                fprintf(stderr, "%sdevice decode on member 0: slimm_push_bam_bytes %.2f ms for %llu records, pusher waited %.2f ms for windows\n",
+                        head.c_str(), raw_push_ms, static_cast<unsigned long long>(raw_records), wait_ms);
         } else if (raw) {
-            fprintf(stderr, "[trace] device decode: inflate %.2f ms (on its own thread, from the moment the file was open), "
+            fprintf(stderr, "%sdevice decode: inflate %.2f ms (on its own thread, from the moment the file was open), "
                             "slimm_push_bam_bytes %.2f ms for %llu records, pusher waited %.2f ms for windows; of the windows read in "
                             "place %llu were inflated on the host, %llu on the device\n",
-                    decode_ms, raw_push_ms, static_cast<unsigned long long>(raw_records), wait_ms,
+                    head.c_str(), decode_ms, raw_push_ms, static_cast<unsigned long long>(raw_records), wait_ms,
                     static_cast<unsigned long long>(raw_windows_host), static_cast<unsigned long long>(raw_windows_device));
         } else {
-            fprintf(stderr, "[trace] decode %.2f ms (on its own thread, from the moment the file was open), waiting for staging sets %.2f ms\n",
-                    decode_ms, wait_ms);
+            fprintf(stderr, "%sdecode %.2f ms (on its own thread, from the moment the file was open), waiting for staging sets %.2f ms\n",
+                    head.c_str(), decode_ms, wait_ms);
         }
     }
 };
@@ -936,7 +991,7 @@ struct SplitBuffers {   // (page-locked for the life of the group's contexts: th
     }
 };
 int read_split(slimm_group* grp, uint32_t G, const std::string& path, SplitForm form, const std::vector<std::string>& names,
-               uint64_t header_bytes, size_t window_cap, SplitBuffers& bufs, std::string& why) {
+               uint64_t header_bytes, size_t window_cap, SplitBuffers& bufs, const char* head, std::string& why) {
     std::vector<uint64_t> off(G + 1, 0);
     const bool bzip2 = form == SplitForm::Bzip2Sam, zstd = form == SplitForm::ZstdSam;
     const bool text = form == SplitForm::Sam || bzip2 || zstd, sam = form != SplitForm::Bam;   // (text: the bytes as they lie in the file)
@@ -1098,7 +1153,7 @@ int read_split(slimm_group* grp, uint32_t G, const std::string& path, SplitForm 
     close(fd);
     for (uint32_t i = 0; i < G; ++i) {
         if (g_trace)
-            fprintf(stderr, "[trace] split member %u: bytes [%llu, %llu) of %llu, %llu records, pread %.2f ms, push %.2f ms, last push (wait) %.2f ms\n", i,
+            fprintf(stderr, "%ssplit member %u: bytes [%llu, %llu) of %llu, %llu records, pread %.2f ms, push %.2f ms, last push (wait) %.2f ms\n", head, i,
                     static_cast<unsigned long long>(off[i]), static_cast<unsigned long long>(off[i + 1]), static_cast<unsigned long long>(off[G]),
                     static_cast<unsigned long long>(m[i].records), m[i].pread_ms, m[i].push_ms, m[i].last_ms);
     }
@@ -1116,7 +1171,7 @@ int read_split(slimm_group* grp, uint32_t G, const std::string& path, SplitForm 
             if (slimm_get_zstd_stats(slimm_group_context(grp, i), st) != SLIMM_OK) continue;
             frames += st[0], blocks += st[2] + st[3] + st[4], text_bytes += st[16];
         }
-        fprintf(stderr, "[trace] zstd SAM on the device: %llu frames, %llu blocks, %llu bytes of text\n", (unsigned long long)frames,
+        fprintf(stderr, "%szstd SAM on the device: %llu frames, %llu blocks, %llu bytes of text\n", head, (unsigned long long)frames,
                 (unsigned long long)blocks, (unsigned long long)text_bytes);
     }
     return rc;
@@ -1215,11 +1270,11 @@ Outcome write_raw_and_coverage(Session& S, Reading& F, slimm_ctx* ctx, bool glob
         }
     }
     auto name_of = [&](uint32_t taxid) -> std::string {
-        auto it = S.db.taxid_name.find(taxid);
-        return it == S.db.taxid_name.end() ? std::string() : it->second.second;
+        auto it = S.shared->db.taxid_name.find(taxid);
+        return it == S.shared->db.taxid_name.end() ? std::string() : it->second.second;
     };
     if (options.raw_output) {  // write_raw_stat :883-943
-        std::cerr << "Writing features to a file ....................... ";
+        S.err() << "Writing features to a file ....................... ";
         std::ofstream o(get_tsv_file_name(options.output_prefix, F.path, "_raw"));
         o << "accesion\ttaxaid\tname\treads_count\tabundance\tuniq1_abundance\tuniq2_abundance\tgenome_length\t"
              "uniq1_reads_count\tuniq2_reads_count\tbins_count\tbins_count(>0)\tuniq1_bins_count(>0)\t"
@@ -1237,10 +1292,10 @@ Outcome write_raw_and_coverage(Session& S, Reading& F, slimm_ctx* ctx, bool glob
               << float(nzu2[i]) / nb << "\n";
             off += nb;
         }
-        std::cerr << "[" << F.watch.lap() << " secs]" << std::endl;
+        S.err() << "[" << F.watch.lap() << " secs]" << std::endl;
     }
     if (options.coverage_output) {  // write_coverage :846-881
-        std::cerr << "Writing coverage profiles to a file ....................... ";
+        S.err() << "Writing coverage profiles to a file ....................... ";
         std::ofstream a(get_tsv_file_name(options.output_prefix, F.path, "_coverage"));
         std::ofstream b(get_tsv_file_name(options.output_prefix, F.path, "_uniq_coverage"));
         std::ofstream c(get_tsv_file_name(options.output_prefix, F.path, "_uniq_coverage2"));
@@ -1268,7 +1323,7 @@ Outcome write_raw_and_coverage(Session& S, Reading& F, slimm_ctx* ctx, bool glob
             }
             off += nb;
         }
-        std::cerr << "[" << F.watch.lap() << " secs]" << std::endl;
+        S.err() << "[" << F.watch.lap() << " secs]" << std::endl;
     }
 
     return Outcome::Done;
@@ -1297,21 +1352,23 @@ std::unique_ptr<Reading> set_up(Session& S, const std::string& path, bool any_or
     Options& options = S.options;
     std::unique_ptr<Reading> F(new Reading);
     F->path = path;
+    F->trace.head = S.log->head;
     AlignmentFile& bam = F->bam;
+    bam.set_trace_head(S.log->head);
     end = Outcome::Done;
     if (!bam.open(path)) {  // src/misc.hpp:500-504: message, skip the file
-        std::cerr << bam.error() << "\n";
+        S.err() << bam.error() << "\n";
         return nullptr;
     }
     const uint32_t avg_read_length = average_read_length(bam);
     if (avg_read_length == 0) {
-        std::cerr << "[ERROR] no record with a sequence in " << path << " (the reference divides by zero here)\n";
+        S.err() << "[ERROR] no record with a sequence in " << path << " (the reference divides by zero here)\n";
         end = Outcome::Failed;
         return nullptr;
     }
     if (options.bin_width == 0) options.bin_width = avg_read_length;  // :412-413, persists across files
     F->trace.mark("open + read-length sample");
-    if (!reopen(bam, path)) return nullptr;
+    if (!reopen(bam, path, S.err())) return nullptr;
     // only a header that promises name grouping is trusted; anything else is sorted on the device
     F->record_order = any_order ? SLIMM_ORDER_ANY
                       : options.order >= 0
@@ -1328,30 +1385,42 @@ std::unique_ptr<Reading> set_up(Session& S, const std::string& path, bool any_or
     const bool may_split = options.split_input && options.devices.size() > 1 && !options.host_decode && !options.verify_grouping && !options.packed_records;
     F->split_input = may_split && (reads_by_byte_range(bam) || zstd_reads_by_byte_range(bam, path, static_cast<uint32_t>(options.devices.size()), true));
     if (g_trace && !any_order && options.split_input && options.devices.size() > 1 && !bam.is_bam() && bam.compression() == Compression::Gzip)
-        fprintf(stderr, "[trace] --split-input: a gzip stream is not cut by byte range; member 0 reads %s\n", path.c_str());
+        fprintf(stderr, "%s--split-input: a gzip stream is not cut by byte range; member 0 reads %s\n", S.trace_head(), path.c_str());
     // (a zstd file of one frame, or one whose members would get less than the floor; or the host decoders were asked for)
     if (g_trace && !any_order && !F->split_input && options.split_input && options.devices.size() > 1 && !bam.is_bam() && bam.compression() == Compression::Zstd)
-        fprintf(stderr, "[trace] --split-input: a zstd stream is not cut by byte range; member 0 reads %s\n", path.c_str());
+        fprintf(stderr, "%s--split-input: a zstd stream is not cut by byte range; member 0 reads %s\n", S.trace_head(), path.c_str());
     if (!F->split_input)
-        F->pump.reset(new RecordPump(bam, F->check_words, true, options));
+        F->pump.reset(new RecordPump(bam, F->check_words, true, options, S.log->head));
 
-    std::cerr << "Intializing coverages for all reference genome ... ";
+    S.err() << "Intializing coverages for all reference genome ... ";
     const uint32_t R = static_cast<uint32_t>(bam.ref_names().size());
     F->accession.resize(R);
     F->taxa_id.assign(R, 0);
     F->lineage.assign(static_cast<size_t>(R) * 8, 0);
-    for (uint32_t i = 0; i < R; ++i) {  // :430-445
-        F->accession[i] = get_accession_id(bam.ref_names()[i]);
-        auto it = S.db.ac_taxid.find(F->accession[i]);
-        if (it != S.db.ac_taxid.end()) {
-            F->taxa_id[i] = it->second.empty() ? 0 : it->second[0];
-            for (size_t k = 0; k < 8 && k < it->second.size(); ++k) F->lineage[static_cast<size_t>(i) * 8 + k] = it->second[k];
-        } else {
-            S.db.ac_taxid[F->accession[i]] = std::vector<uint32_t>(8, 0);  // Q13
+    SlimmDatabase& db = S.shared->db;
+    std::vector<uint32_t> unknown;
+    {   // :430-445
+        std::shared_lock<std::shared_mutex> g(S.shared->db_mu);
+        for (uint32_t i = 0; i < R; ++i) {
+            F->accession[i] = get_accession_id(bam.ref_names()[i]);
+            auto it = db.ac_taxid.find(F->accession[i]);
+            if (it != db.ac_taxid.end()) {
+                F->taxa_id[i] = it->second.empty() ? 0 : it->second[0];
+                for (size_t k = 0; k < 8 && k < it->second.size(); ++k) F->lineage[static_cast<size_t>(i) * 8 + k] = it->second[k];
+            } else {
+                unknown.push_back(i);
+            }
         }
     }
-    F->tax_id.reserve(S.db.taxid_name.size());
-    for (auto& kv : S.db.taxid_name) {
+    if (!unknown.empty()) {
+        // Q13: an unknown accession gets a zero lineage in the database.  Whoever looks it up later -- this file, for a name its
+        // header holds twice, or another one -- reads the zeros it would have got for a missing entry, so it does not matter who
+        // inserts first; the writers only may not meet the readers above
+        std::unique_lock<std::shared_mutex> g(S.shared->db_mu);
+        for (uint32_t i : unknown) db.ac_taxid.emplace(F->accession[i], std::vector<uint32_t>(8, 0));
+    }
+    F->tax_id.reserve(db.taxid_name.size());
+    for (auto& kv : db.taxid_name) {
         F->tax_id.push_back(kv.first);
         F->tax_rank.push_back(kv.second.first);
         F->tax_name.push_back(kv.second.second.c_str());
@@ -1393,23 +1462,23 @@ Outcome push_file(Session& S, Reading& F, Target t, OnCap on_cap) {
     const PushError why = ok || !pump.raw || read_rc < 0 ? PushError::Other : classify(slimm_last_error(t.ctx));
     if (why == PushError::RecordCap && on_cap == OnCap::MoreMembers) return Outcome::MoreMembers;
     if (why == PushError::HostDecode || (why == PushError::RecordCap && on_cap == OnCap::HostDecode)) {
-        std::cerr << "(" << slimm_last_error(t.ctx) << ": decoding on the host) ";
+        S.err() << "(" << slimm_last_error(t.ctx) << ": decoding on the host) ";
         if (t.reset() != SLIMM_OK) {
-            std::cerr << "slimm: " << (t.group ? "" : "slimm_reset(ctx): ") << t.error() << "\n";
+            S.err() << "slimm: " << (t.group ? "" : "slimm_reset(ctx): ") << t.error() << "\n";
             return Outcome::Failed;
         }
-        if (!reopen(F.bam, F.path)) return Outcome::Failed;
-        RecordPump again(F.bam, F.check_words, false, S.options);
+        if (!reopen(F.bam, F.path, S.err())) return Outcome::Failed;
+        RecordPump again(F.bam, F.check_words, false, S.options, S.log->head);
         ok = again.drain(t);
         read_rc = again.read_rc;
     }
     if (t.group) F.trace.mark("rest of read + decode + push");
     if (!ok) {   // (a pump that fed the device decoders: their context's message, after the host decoder's pass too)
-        std::cerr << (t.group ? "" : "slimm: ") << "pushing records: " << (pump.raw ? slimm_last_error(t.ctx) : t.error()) << "\n";
+        S.err() << (t.group ? "" : "slimm: ") << "pushing records: " << (pump.raw ? slimm_last_error(t.ctx) : t.error()) << "\n";
         return Outcome::Failed;
     }
     if (read_rc < 0) {
-        std::cerr << F.bam.error() << "\n";
+        S.err() << F.bam.error() << "\n";
         return Outcome::Failed;
     }
     return Outcome::Done;
@@ -1417,7 +1486,7 @@ Outcome push_file(Session& S, Reading& F, Target t, OnCap on_cap) {
 
 // Q17: one line per file whose propagated read counts depend on the order of the walk, or could not be shown not to
 // (slimm_get_propagation_order on the context that propagated).  The profile is written either way.
-void warn_propagation_order(slimm_ctx* ctx, const std::string& path, int walk) {
+void warn_propagation_order(slimm_ctx* ctx, const std::string& path, int walk, std::ostream& err) {
     int verdict = SLIMM_PROPAGATION_INDEPENDENT;
     uint32_t n = 0;
     if (slimm_get_propagation_order(ctx, &verdict, nullptr, 0, &n) != SLIMM_OK || verdict == SLIMM_PROPAGATION_INDEPENDENT) return;
@@ -1432,7 +1501,7 @@ void warn_propagation_order(slimm_ctx* ctx, const std::string& path, int walk) {
          << (n == 1 ? "" : "s") << " involved:";
     for (uint32_t k = 0; k < shown; ++k) line << ' ' << taxa[k];
     if (n > shown) line << " and " << n - shown << " more";
-    std::cerr << line.str() << std::endl;
+    err << line.str() << std::endl;
 }
 
 // ---- several GPUs, one process (--devices), or members of a group on ONE device for a file of more records than one
@@ -1441,9 +1510,14 @@ void warn_propagation_order(slimm_ctx* ctx, const std::string& path, int walk) {
 Outcome run_group(Session& S, Reading& F, const std::vector<int>& devs, bool split, bool for_cap) {
     Options& options = S.options;
     slimm_group* created = nullptr;
-    if (slimm_group_create(&F.cfg, devs.data(), static_cast<uint32_t>(devs.size()), &created) != SLIMM_OK) {
-        std::cerr << "slimm: " << slimm_group_last_error(nullptr) << "\n";
-        return Outcome::Failed;
+    {   // (a failed slimm_group_create leaves its message in one string of the process: one at a time, for the slots of
+        // --file-per-device, whose files may each meet the record cap)
+        static std::mutex create_mu;
+        std::lock_guard<std::mutex> g(create_mu);
+        if (slimm_group_create(&F.cfg, devs.data(), static_cast<uint32_t>(devs.size()), &created) != SLIMM_OK) {
+            S.err() << "slimm: " << slimm_group_last_error(nullptr) << "\n";
+            return Outcome::Failed;
+        }
     }
     const GroupPtr grp(created, slimm_group_destroy);
     const bool want_arrays = options.raw_output || options.coverage_output;
@@ -1457,29 +1531,29 @@ Outcome run_group(Session& S, Reading& F, const std::vector<int>& devs, bool spl
     slimm_ctx* c0 = slimm_group_context(grp.get(), 0);
     (void)slimm_set_propagation_walk(c0, options.propagation_walk);   // (member 0 propagates)
     F.trace.mark("lineage table + slimm_group_create");
-    std::cerr << "[" << F.watch.lap() << " secs]" << std::endl;
-    std::cerr << "Analysing alignments on " << devs.size() << " devices ("
+    S.err() << "[" << F.watch.lap() << " secs]" << std::endl;
+    S.err() << "Analysing alignments on " << devs.size() << " devices ("
               << (slimm_group_uses_rccl(grp.get()) ? "RCCL" : "copy") << " collectives) ... ";
     bool split_read = false;
     if (split) {   // every member its own byte range (read_split); what fails there goes through member 0 after all
         std::string why;
         const int src = read_split(grp.get(), static_cast<uint32_t>(devs.size()), F.path, split_form(F.bam), F.bam.ref_names(),
-                                   F.bam.header_bytes(), RecordPump::raw_cap(), F.split_bufs, why);
+                                   F.bam.header_bytes(), RecordPump::raw_cap(), F.split_bufs, S.trace_head(), why);
         F.trace.mark("split: read + decode + stitch");
         if (src == SLIMM_E_REGROUP) return Outcome::ReadAgainAnyOrder;
         if (src != SLIMM_OK && for_cap && classify(why.c_str()) == PushError::RecordCap) return Outcome::MoreMembers;
         if (src != SLIMM_OK) {
-            std::cerr << "(split input: " << why << "; reading the file through member 0) ";
+            S.err() << "(split input: " << why << "; reading the file through member 0) ";
             if (slimm_group_reset(grp.get()) != SLIMM_OK) {
-                std::cerr << "slimm: " << slimm_group_last_error(grp.get()) << "\n";
+                S.err() << "slimm: " << slimm_group_last_error(grp.get()) << "\n";
                 return Outcome::Failed;
             }
-            if (!reopen(F.bam, F.path)) return Outcome::Failed;
+            if (!reopen(F.bam, F.path, S.err())) return Outcome::Failed;
         }
         split_read = src == SLIMM_OK;
     }
     if (!split_read) {   // member 0 reads the whole file
-        if (!F.pump) F.pump.reset(new RecordPump(F.bam, F.check_words, true, options));
+        if (!F.pump) F.pump.reset(new RecordPump(F.bam, F.check_words, true, options, S.log->head));
         if (F.pump->raw) set_size_hint(c0, F.path);   // (what member 0 sizes its window buffers by)
         const Outcome pushed = push_file(S, F, Target{c0, grp.get()}, OnCap::HostDecode);
         if (pushed != Outcome::Done) return pushed;
@@ -1488,33 +1562,33 @@ Outcome run_group(Session& S, Reading& F, const std::vector<int>& devs, bool spl
     const int grc = slimm_group_get_profiles(grp.get(), get_tsv_file_name(options.output_prefix, F.path, "_profile").c_str());
     if (grc == SLIMM_E_REGROUP) return Outcome::ReadAgainAnyOrder;   // (member 0's decoders counted a run of shortened names only: Q18)
     if (grc < 0) {
-        std::cerr << "slimm: " << slimm_group_last_error(grp.get()) << "\n";
+        S.err() << "slimm: " << slimm_group_last_error(grp.get()) << "\n";
         return Outcome::Failed;
     }
     F.trace.mark("phases + exchanges + profile");
-    if (F.trace.on) trace_memory(c0);
-    std::cerr << "[" << F.watch.lap() << " secs]" << std::endl;
+    if (F.trace.on) trace_memory(c0, S.trace_head());
+    S.err() << "[" << F.watch.lap() << " secs]" << std::endl;
     slimm_stats st;
     slimm_get_stats(c0, &st);
     S.total_hits += st.hits_count;
     if (grc == SLIMM_E_NO_HITS) {
-        std::cerr << "[WARNING] No mapped reads found in BAM file!" << std::endl;
+        S.err() << "[WARNING] No mapped reads found in BAM file!" << std::endl;
         return Outcome::Done;
     }
-    warn_propagation_order(c0, F.path, options.propagation_walk);
+    warn_propagation_order(c0, F.path, options.propagation_walk, S.err());
     if (options.min_reads == 0) options.min_reads = st.min_reads;
     if (options.verbose) {
-        std::cerr << "  " << st.hits_count << " records processed." << std::endl;
-        std::cerr << "    " << st.matches_count << " matching reads" << std::endl;
-        std::cerr << "    " << st.uniq_matches_count << " uniquily matching reads" << std::endl;
-        std::cerr << "  references with reads = " << st.reference_count << std::endl;
-        std::cerr << "  " << st.n_valid << " passed the threshould coverage.\n";
-        std::cerr << "  uniquily matching reads increased from " << st.uniq_matches_count << " to " << st.uniq_matches_count2 << "\n";
-        std::cerr << std::setw(4) << st.profile_count << std::setw(15) << (options.rank) << " (" << st.profile_failed
+        S.err() << "  " << st.hits_count << " records processed." << std::endl;
+        S.err() << "    " << st.matches_count << " matching reads" << std::endl;
+        S.err() << "    " << st.uniq_matches_count << " uniquily matching reads" << std::endl;
+        S.err() << "  references with reads = " << st.reference_count << std::endl;
+        S.err() << "  " << st.n_valid << " passed the threshould coverage.\n";
+        S.err() << "  uniquily matching reads increased from " << st.uniq_matches_count << " to " << st.uniq_matches_count2 << "\n";
+        S.err() << std::setw(4) << st.profile_count << std::setw(15) << (options.rank) << " (" << st.profile_failed
                   << " bellow cutoff i.e. " << options.abundance_cut_off << ")\n";
     }
     if (want_arrays && write_raw_and_coverage(S, F, c0, true) != Outcome::Done) return Outcome::Failed;
-    std::cerr << "[Done!] File took " << F.watch.elapsed() << " secs to process.\n";
+    S.err() << "[Done!] File took " << F.watch.elapsed() << " secs to process.\n";
     (void)slimm_get_cutoff_cache(c0, &S.cc_cache, &S.ucc_cache);
     return Outcome::Done;
 }
@@ -1523,7 +1597,7 @@ Outcome run_context(Session& S, Reading& F) {
     Options& options = S.options;
     slimm_ctx* created = nullptr;
     if (slimm_create(&F.cfg, &created) != SLIMM_OK) {
-        std::cerr << "slimm: " << slimm_last_error(nullptr) << "\n";
+        S.err() << "slimm: " << slimm_last_error(nullptr) << "\n";
         return Outcome::Failed;
     }
     CtxPtr owned(created, slimm_destroy);
@@ -1533,22 +1607,22 @@ Outcome run_context(Session& S, Reading& F) {
     set_size_hint(ctx, F.path);
     slimm_keep_bins(ctx, (options.raw_output || options.coverage_output) ? 1 : 0);  // (only -ro / -co read the arrays back)
     F.trace.mark("lineage table + slimm_create");
-    std::cerr << "[" << F.watch.lap() << " secs]" << std::endl;
+    S.err() << "[" << F.watch.lap() << " secs]" << std::endl;
 
-    std::cerr << "Analysing alignments, reads and references ....... ";
+    S.err() << "Analysing alignments, reads and references ....... ";
     // (zstd SAM: whether the file can be cut is asked only once the cap is met -- the plan reads the file; the floor is not
     // consulted here.  A file of one frame cannot be cut and ends at the cap, as it did)
     const bool zstd_file = !F.bam.is_bam() && F.bam.compression() == Compression::Zstd && F.bam.regular_file();
     const bool byte_ranges = reads_by_byte_range(F.bam) || zstd_file;
     const Outcome pushed = push_file(S, F, Target{ctx}, byte_ranges ? OnCap::MoreMembers : OnCap::Fail);
     if (pushed == Outcome::MoreMembers && zstd_file && !zstd_reads_by_byte_range(F.bam, F.path, 2u, false)) {
-        std::cerr << "slimm: pushing records: " << slimm_last_error(ctx) << "\n";
+        S.err() << "slimm: pushing records: " << slimm_last_error(ctx) << "\n";
         return Outcome::Failed;
     }
     if (pushed == Outcome::MoreMembers) {
         // more records than one context takes: contexts of a group on this one device, each its own byte range of the
         // file (read_split) -- twice as many until each range fits
-        std::cerr << "(" << slimm_last_error(ctx) << ": reading the file by byte range into several contexts of device " << options.device
+        S.err() << "(" << slimm_last_error(ctx) << ": reading the file by byte range into several contexts of device " << options.device
                   << ") ";
         const uint64_t records = F.pump->raw_records;
         owned.reset();
@@ -1556,11 +1630,11 @@ Outcome run_context(Session& S, Reading& F) {
         const uint64_t cap = slimm_record_cap();
         uint32_t G = std::max<uint32_t>(2u, static_cast<uint32_t>(std::min<uint64_t>(64u, 2u * (records + cap - 1) / cap)));
         for (; G <= 128u; G *= 2u) {
-            if (!reopen(F.bam, F.path)) return Outcome::Failed;
+            if (!reopen(F.bam, F.path, S.err())) return Outcome::Failed;
             const Outcome r = run_group(S, F, std::vector<int>(G, options.device), true, true);
             if (r != Outcome::MoreMembers) return r;
         }
-        std::cerr << "slimm: more records than " << G / 2 << " contexts take\n";
+        S.err() << "slimm: more records than " << G / 2 << " contexts take\n";
         return Outcome::Failed;
     }
     if (pushed != Outcome::Done) return pushed;
@@ -1570,7 +1644,7 @@ Outcome run_context(Session& S, Reading& F) {
         uint64_t split = 0;
         CHECK(ctx, slimm_check_grouping(ctx, &split));
         if (split)
-            std::cerr << "\n[WARNING] " << split << " read name run(s) repeat a name seen earlier in " << get_file_name(F.path)
+            S.err() << "\n[WARNING] " << split << " read name run(s) repeat a name seen earlier in " << get_file_name(F.path)
                       << ": the file is NOT grouped by read name although it is declared so; run with --any-order\n";
     }
     // (the device decoders count inside the library: SLIMM_E_REGROUP; the host decoder counts in the reader)
@@ -1578,63 +1652,63 @@ Outcome run_context(Session& S, Reading& F) {
     const int arc = slimm_analyze_alignments(ctx);
     if (arc == SLIMM_E_REGROUP) return Outcome::ReadAgainAnyOrder;
     if (arc < 0) {
-        std::cerr << "slimm: slimm_analyze_alignments(ctx): " << slimm_last_error(ctx) << "\n";
+        S.err() << "slimm: slimm_analyze_alignments(ctx): " << slimm_last_error(ctx) << "\n";
         return Outcome::Failed;
     }
     const int rc = slimm_finish_coverage(ctx);
     if (rc < 0) {
-        std::cerr << "slimm: " << slimm_last_error(ctx) << "\n";
+        S.err() << "slimm: " << slimm_last_error(ctx) << "\n";
         return Outcome::Failed;
     }
     F.trace.mark("analyze_alignments + finish_coverage");
-    std::cerr << "[" << F.watch.lap() << " secs]" << std::endl;
+    S.err() << "[" << F.watch.lap() << " secs]" << std::endl;
     slimm_stats st;
     slimm_get_stats(ctx, &st);
     S.total_hits += st.hits_count;
     if (rc == SLIMM_E_NO_HITS) {
-        std::cerr << "[WARNING] No mapped reads found in BAM file!" << std::endl;
+        S.err() << "[WARNING] No mapped reads found in BAM file!" << std::endl;
         return Outcome::Done;
     }
     if (options.min_reads == 0) options.min_reads = st.min_reads;  // :458-459, persists across files
     if (options.verbose) {                                         // print_matches_stat :621-630
-        std::cerr << "  " << st.hits_count << " records processed." << std::endl;
-        std::cerr << "    " << st.matches_count << " matching reads" << std::endl;
-        std::cerr << "    " << st.uniq_matches_count << " uniquily matching reads" << std::endl;
-        std::cerr << "  references with reads = " << st.reference_count << std::endl;
-        std::cerr << "  expected bins coverage = " << st.expected_coverage << std::endl;
-        std::cerr << "  bins coverage cut-off = " << st.coverage_cut_off << " (" << options.cov_cut_off << " quantile)\n";
-        std::cerr << "  uniq bins coverage cut-off = " << st.uniq_coverage_cut_off << " (" << options.cov_cut_off << " quantile)\n\n";
+        S.err() << "  " << st.hits_count << " records processed." << std::endl;
+        S.err() << "    " << st.matches_count << " matching reads" << std::endl;
+        S.err() << "    " << st.uniq_matches_count << " uniquily matching reads" << std::endl;
+        S.err() << "  references with reads = " << st.reference_count << std::endl;
+        S.err() << "  expected bins coverage = " << st.expected_coverage << std::endl;
+        S.err() << "  bins coverage cut-off = " << st.coverage_cut_off << " (" << options.cov_cut_off << " quantile)\n";
+        S.err() << "  uniq bins coverage cut-off = " << st.uniq_coverage_cut_off << " (" << options.cov_cut_off << " quantile)\n\n";
     }
 
-    std::cerr << "Filtering unlikely sequences ..................... ";
+    S.err() << "Filtering unlikely sequences ..................... ";
     CHECK(ctx, slimm_filter_alignments(ctx));
-    std::cerr << "[" << F.watch.lap() << " secs]" << std::endl;
+    S.err() << "[" << F.watch.lap() << " secs]" << std::endl;
     slimm_get_stats(ctx, &st);
     if (options.verbose) {  // print_filter_stat :613-619
-        std::cerr << "  " << st.n_valid << " passed the threshould coverage.\n";
-        std::cerr << "  " << st.failed_by_cov << " ref's couldn't pass the coverage threshould.\n";
-        std::cerr << "  " << st.failed_by_uniq_cov << " ref's couldn't pass the uniq coverage threshould.\n";
-        std::cerr << "  uniquily matching reads increased from " << st.uniq_matches_count << " to " << st.uniq_matches_count2 << "\n\n";
+        S.err() << "  " << st.n_valid << " passed the threshould coverage.\n";
+        S.err() << "  " << st.failed_by_cov << " ref's couldn't pass the coverage threshould.\n";
+        S.err() << "  " << st.failed_by_uniq_cov << " ref's couldn't pass the uniq coverage threshould.\n";
+        S.err() << "  uniquily matching reads increased from " << st.uniq_matches_count << " to " << st.uniq_matches_count2 << "\n\n";
     }
 
     if ((options.raw_output || options.coverage_output) && write_raw_and_coverage(S, F, ctx, false) != Outcome::Done) return Outcome::Failed;
-    std::cerr << "Assigning reads to Least Common Ancestor (LCA) ... ";
+    S.err() << "Assigning reads to Least Common Ancestor (LCA) ... ";
     CHECK(ctx, slimm_get_reads_lca_count(ctx));
-    std::cerr << "[" << F.watch.lap() << " secs]" << std::endl;
-    warn_propagation_order(ctx, F.path, options.propagation_walk);
+    S.err() << "[" << F.watch.lap() << " secs]" << std::endl;
+    warn_propagation_order(ctx, F.path, options.propagation_walk, S.err());
 
-    std::cerr << "Writing taxnomic profile(s) ...................... ";
+    S.err() << "Writing taxnomic profile(s) ...................... ";
     CHECK(ctx, slimm_write_abundance_file(ctx, get_tsv_file_name(options.output_prefix, F.path, "_profile").c_str()));
     if (options.verbose) {
         slimm_get_stats(ctx, &st);
-        std::cerr << "\n" << std::setw(4) << st.profile_count << std::setw(15) << (options.rank) << " (" << st.profile_failed
+        S.err() << "\n" << std::setw(4) << st.profile_count << std::setw(15) << (options.rank) << " (" << st.profile_failed
                   << " bellow cutoff i.e. " << options.abundance_cut_off << ")";
-        std::cerr << "\n.................................................. ";
+        S.err() << "\n.................................................. ";
     }
-    std::cerr << "[" << F.watch.lap() << " secs]" << std::endl;
+    S.err() << "[" << F.watch.lap() << " secs]" << std::endl;
     F.trace.mark("filter + LCA + outputs");
-    if (F.trace.on) trace_memory(ctx);
-    std::cerr << "[Done!] File took " << F.watch.elapsed() << " secs to process.\n";
+    if (F.trace.on) trace_memory(ctx, S.trace_head());
+    S.err() << "[Done!] File took " << F.watch.elapsed() << " secs to process.\n";
     CHECK(ctx, slimm_get_cutoff_cache(ctx, &S.cc_cache, &S.ucc_cache));
     owned.reset();
     F.trace.mark("slimm_destroy");
@@ -1643,8 +1717,8 @@ Outcome run_context(Session& S, Reading& F) {
 
 // slimm::get_profiles() for one file (src/slimm.hpp:395-496)
 bool get_profiles(Session& S, size_t file_index) {
-    const std::string& path = S.input_paths[file_index];
-    std::cerr << "\nReading " << file_index + 1 << " of " << S.input_paths.size() << " files ... (" << get_file_name(path) << ")\n"
+    const std::string& path = S.shared->input_paths[file_index];
+    S.err() << "\nReading " << file_index + 1 << " of " << S.shared->input_paths.size() << " files ... (" << get_file_name(path) << ")\n"
               << "=================================================================\n";
     auto read = [&](bool any_order) {   // one reading of the file, through a group (--devices) or one context
         Outcome end;
@@ -1659,11 +1733,100 @@ bool get_profiles(Session& S, size_t file_index) {
         // (src/slimm.hpp:204-211).  The readers count the runs of such shortened names that stand apart from their
         // namesakes; a file that has one is read again, in any order (a fresh context of the same process: the HIP runtime
         // and the page cache are warm).  The any-order path never asks for it.
-        std::cerr << "\n(read names ending in .1 / .2 without a mate flag, apart from the flagged records of the shortened name: "
+        S.err() << "\n(read names ending in .1 / .2 without a mate flag, apart from the flagged records of the shortened name: "
                      "reading " << get_file_name(path) << " again as a file in no particular order)\n";
         r = read(true);
     }
     return r == Outcome::Done;
+}
+
+// --file-per-device: the files of S.shared->input_paths, in that order, through the slots of S.options.slots; false when a
+// file failed (the sequential run's status 1).  Two steps.  (1) The files are read in turn in slot 0 -- S itself, carrying
+// its values from file to file exactly as main()'s loop does -- until those values are settled (Session::settled): up to
+// there a file's result depends on the files before it.  (2) The rest is handed, in list order, to whichever slot is free;
+// a slot is a thread with a copy of the settled values and its own device, and reads a file as --device N does -- the device
+// decoders and their fallbacks, the any-order re-read, the re-read by byte range into several contexts of ITS device at the
+// record cap.  No group spans slots.  If the values never settle -- a directory of files without mapped reads -- step 1 takes
+// every file.  Every output file is byte for byte the sequential run's.
+// A file's stderr lines are collected (FileLog) and printed as one block, the blocks in list order: a finished block waits
+// for those before it.  The first failing file in list order has the last block printed; once a failure is known no new file
+// starts, the running ones finish (so outputs of files behind the failing one may exist).
+bool run_file_per_device(Session& S) {
+    const std::vector<std::string>& paths = S.shared->input_paths;
+    const size_t n = paths.size(), n_slots = S.options.slots.size();
+    struct Board {
+        std::mutex mu;
+        std::vector<std::string> block;   // of the finished files not printed yet
+        std::vector<int> state;           // 0: not finished, 1: done, 2: failed
+        size_t printed = 0;               // blocks [0, printed) are out
+        bool closed = false;              // ... the last of them a failed file's: nothing follows it
+        size_t next = 0;                  // the next file to hand out
+        bool failure = false;             // a file failed: no new one starts
+        uint32_t hits = 0;                // (total_hits: a sum modulo 2^32, whatever the order)
+    } board;
+    board.block.resize(n);
+    board.state.assign(n, 0);
+    auto one_file = [&](Session& mine, size_t k, size_t slot) {
+        FileLog log;
+        log.collect = true;
+        log.head = "[trace] file " + std::to_string(k + 1) + ": ";
+        FileLog* const before = mine.log;
+        mine.log = &log;
+        if (g_trace)
+            fprintf(stderr, "[trace] file-per-device: file %zu (%s) in slot %zu on device %d\n", k + 1, get_file_name(paths[k]).c_str(), slot,
+                    mine.options.device);
+        Trace trace;
+        trace.head = log.head;
+        const bool ok = get_profiles(mine, k);
+        trace.mark("get_profiles + its buffers released");
+        mine.log = before;
+        std::lock_guard<std::mutex> g(board.mu);
+        board.block[k] = log.block.str();
+        board.state[k] = ok ? 1 : 2;
+        if (!ok) board.failure = true;
+        for (; !board.closed && board.printed < n && board.state[board.printed]; ++board.printed) {
+            // (one call: stderr is not buffered, so the block goes out whole, between the [trace] lines of other threads)
+            fwrite(board.block[board.printed].data(), 1, board.block[board.printed].size(), stderr);
+            std::string().swap(board.block[board.printed]);
+            board.closed = board.state[board.printed] == 2;
+        }
+        return ok;
+    };
+    size_t in_turn = 0;
+    for (; in_turn < n && !S.settled(); ++in_turn)
+        if (!one_file(S, in_turn, 0)) return false;
+    if (g_trace)
+        fprintf(stderr, "[trace] file-per-device: %zu of %zu files read in turn before the carried values settled; %zu handed to %zu slots\n",
+                in_turn, n, n - in_turn, n_slots);
+    board.next = in_turn;
+    std::vector<std::thread> slots;
+    for (size_t j = 0; j < std::min(n_slots, n - in_turn); ++j)
+        slots.emplace_back([&, j] {
+            Session mine = S;   // (its own copy of the options: the re-read at the record cap asks them for the device)
+            mine.options.device = S.options.slots[j];
+            mine.total_hits = 0;
+            for (;;) {
+                size_t k;
+                {
+                    std::lock_guard<std::mutex> g(board.mu);
+                    if (board.failure || board.next >= n) break;
+                    k = board.next++;
+                }
+                if (!one_file(mine, k, j)) break;
+                if (mine.options.bin_width != S.options.bin_width || mine.options.min_reads != S.options.min_reads ||
+                    mine.cc_cache != S.cc_cache || mine.ucc_cache != S.ucc_cache) {   // (what settled() rules out)
+                    std::lock_guard<std::mutex> g(board.mu);
+                    std::cerr << "slimm: " << get_file_name(paths[k]) << " changed a value carried from file to file after those had settled\n";
+                    board.failure = true;
+                    break;
+                }
+            }
+            std::lock_guard<std::mutex> g(board.mu);
+            board.hits += mine.total_hits;
+        });
+    for (std::thread& t : slots) t.join();
+    S.total_hits += board.hits;
+    return !board.failure;
 }
 
 }  // namespace
@@ -1685,7 +1848,11 @@ int main(int argc, char** argv) {
         clock_gettime(CLOCK_REALTIME, &now);
         fprintf(stderr, "[trace] main() entered at %.6f (epoch seconds)\n", now.tv_sec + now.tv_nsec * 1e-9);
     }
+    Shared shared;
+    FileLog direct;
     Session S;
+    S.shared = &shared;
+    S.log = &direct;
     int pr = parse(argc, argv, S.options);
     if (pr == 2) return 0;
     if (pr != 0) return 1;
@@ -1697,22 +1864,22 @@ int main(int argc, char** argv) {
         ~WarmUp() {
             if (t.joinable()) t.join();
         }
-    } warm_up{std::thread([devices = S.options.devices.size() > 1 ? S.options.devices : std::vector<int>{S.options.device}] { lazy::load(devices); })};
+    } warm_up{std::thread([devices = S.options.file_per_device ? S.options.slots : S.options.devices.size() > 1 ? S.options.devices : std::vector<int>{S.options.device}] { lazy::load(devices); })};
     Lap watch;
     // slimm::slimm(): collect_bam_files + load_slimm_database (src/slimm.hpp:96-101, 306-326)
     if (S.options.is_directory) {
-        S.input_paths = get_bam_files_in_directory(S.options.input_path);
+        shared.input_paths = get_bam_files_in_directory(S.options.input_path);
         if (S.options.verbose)
-            std::cerr << S.input_paths.size() << " SAM/BAM Files found under the directory: " << S.options.input_path << "!\n";
+            std::cerr << shared.input_paths.size() << " SAM/BAM Files found under the directory: " << S.options.input_path << "!\n";
     } else if (access(S.options.input_path.c_str(), 0) == 0) {
-        S.input_paths.push_back(S.options.input_path);
+        shared.input_paths.push_back(S.options.input_path);
     } else {
         std::cerr << S.options.input_path << " is not a file use -d option for a directory.\n";
         return 1;
     }
     std::string err;
     Trace trace;
-    if (!load_slimm_database(S.options.database_path, S.db, err)) {
+    if (!load_slimm_database(S.options.database_path, shared.db, err)) {
         std::cerr << "slimm: " << err << "\n";
         return 1;
     }
@@ -1755,9 +1922,16 @@ int main(int argc, char** argv) {
         std::cerr.flush();
         fflush(nullptr);
     };
-    for (size_t n = 0; n < S.input_paths.size(); ++n) {
-        if (!get_profiles(S, n)) return 1;
-        trace.mark("get_profiles + its buffers released");
+    if (S.options.file_per_device) {
+        // (up to 64 decode threads a file by default: shared among the files open at once; --decode-threads N is per file)
+        const unsigned at_once = static_cast<unsigned>(std::max<size_t>(1, std::min(S.options.slots.size(), shared.input_paths.size())));
+        if (AlignmentFile::settings().threads == 0) AlignmentFile::settings().threads = std::max(1u, AlignmentFile::default_threads() / at_once);
+        if (!run_file_per_device(S)) return 1;
+    } else {
+        for (size_t n = 0; n < shared.input_paths.size(); ++n) {
+            if (!get_profiles(S, n)) return 1;
+            trace.mark("get_profiles + its buffers released");
+        }
     }
     closing_lines();
     return 0;
