@@ -194,7 +194,7 @@ struct Options {  // arg_options, reference src/slimm.hpp:49-87
     unsigned device_inflate = 1;   // --device-inflate K: every K-th window read in place is inflated on the device (0: none)
     unsigned window_mb = 0;        // --window-mb N: bytes per window buffer (tests make windows smaller than a record)
     int propagation_walk = SLIMM_WALK_DEFAULT;  // --propagation-walk default|reversed (include/slimm_hip.h, "THE ORDER OF THE PROPAGATION")
-    bool split_input = false;      // --split-input (with --devices): every member reads its own byte range of a BAM / SAM / BGZF SAM / bzip2 SAM
+    bool split_input = false;      // --split-input (with --devices): every member reads its own byte range of the file, where its form is cut (kForms)
     // --file-per-device (with --devices): the listed devices are SLOTS that take whole files, one at a time, each through one
     // context on its device (run_file_per_device); parse() moves the list here and leaves `devices` empty: no group
     bool file_per_device = false;
@@ -602,6 +602,130 @@ struct Target {
     const char* error() const { return group ? slimm_group_last_error(group) : slimm_last_error(ctx); }
 };
 
+// THE FORMS OF AN INPUT FILE: one row per form says what the command's two readers of file bytes -- RecordPump's raw windows
+// and read_split -- need to know of it.  A new form is a row.
+struct InputForm {
+    const char* name;   // in the [trace] lines (a streamed codec's: "a <name> stream", "<name> SAM on the device")
+    bool sam;           // SAM text: the decoder wants the header's reference names first (slimm_set_reference_names)
+    // Which AlignmentFile path supplies the pump's bytes.  Bgzf: read_blocks -- whole blocks, the device inflates them -- every
+    // device_period-th window, else read_raw; `last` from raw_exhausted().  Text: read_text.  Streamed: read_compressed, the
+    // file's bytes from its first on; the first push skips text_header_bytes() decoded bytes, `last` from compressed_exhausted()
+    enum Read { Bgzf, Text, Streamed } read;
+    // (ctx, bytes, n, skip, last, &got): a window of those bytes -- and the empty final push, (nullptr, 0, skip, 1), when the end
+    // came without notice or a range is empty.  push_blocks: whole BGZF blocks as they lie in the file
+    using Push = int (*)(slimm_ctx*, const uint8_t*, uint64_t, uint32_t, int, uint64_t*);
+    Push push, push_blocks = nullptr;
+    // --split-input and the re-read at the record cap: the planner of the members' byte ranges (none: the form is never cut),
+    // and what read_split says it plans: "the file's <planned> could not be planned into ranges"
+    int (*plan)(const char* path, uint64_t header_bytes, uint32_t n, uint64_t* offsets) = nullptr;
+    const char* planned = nullptr;
+    bool header_32bit = true;          // ... only with a header of fewer than 2^32 inflated bytes (member 0's `skip`)
+    bool wide_header_by_host = false;  // the pump: a header of 2^32 text bytes or more goes through the host reader (pushed_as)
+    uint64_t (*slack)() = nullptr;     // bytes a member reads behind its range, at most to the file's end (none: 0)
+    bool announce_range = false;       // the members are told their ranges (slimm_set_input_range)
+    // what else must hold for a regular file of this form to be cut over G members (none: nothing)
+    bool (*may_cut)(const AlignmentFile& f, const std::string& path, uint32_t G, bool with_floor) = nullptr;
+    // SLIMM_TRACE=cli, at the file's end: what the device decoded, the counters of the n contexts summed (none: no line)
+    void (*end_line)(const char* head, slimm_ctx* const* ctx, uint32_t n) = nullptr;
+};
+int push_sam_text(slimm_ctx* c, const uint8_t* p, uint64_t n, uint32_t, int last, uint64_t* got) { return slimm_push_sam_bytes(c, p, n, last, got); }
+int push_bam_records(slimm_ctx* c, const uint8_t* p, uint64_t n, uint32_t, int last, uint64_t* got) { return slimm_push_bam_bytes(c, p, n, last, got); }
+
+// bytes [at, at + n) of the file into dst; false on a read error or a short file
+bool pread_all(int fd, uint8_t* dst, uint64_t at, size_t n) {
+    for (; n;) {
+        const ssize_t k = pread(fd, dst, n, static_cast<off_t>(at));
+        if (k <= 0) return false;
+        dst += k, at += static_cast<uint64_t>(k), n -= static_cast<size_t>(k);
+    }
+    return true;
+}
+void gzip_end_line(const char* head, slimm_ctx* const* ctx, uint32_t n) {
+    uint64_t members = 0, chunks = 0, dropped = 0, text = 0, told = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        uint64_t st[20] = {};
+        if (slimm_get_gzip_stats(ctx[i], st) == SLIMM_OK) ++told, members += st[0], chunks += st[1], dropped += st[3], text += st[9];
+    }
+    if (told) fprintf(stderr, "%sgzip SAM on the device: %llu members, %llu chunks (%llu candidates dropped), %llu bytes of text\n", head,
+            (unsigned long long)members, (unsigned long long)chunks, (unsigned long long)dropped, (unsigned long long)text);
+}
+void zstd_end_line(const char* head, slimm_ctx* const* ctx, uint32_t n) {
+    uint64_t frames = 0, blocks = 0, text = 0, told = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        uint64_t st[20] = {};
+        if (slimm_get_zstd_stats(ctx[i], st) == SLIMM_OK) ++told, frames += st[0], blocks += st[2] + st[3] + st[4], text += st[16];
+    }
+    if (told) fprintf(stderr, "%szstd SAM on the device: %llu frames, %llu blocks, %llu bytes of text\n", head, (unsigned long long)frames,
+            (unsigned long long)blocks, (unsigned long long)text);
+}
+// zstd SAM is cut where frames start and nowhere else (slimm_host_zstd_ranges): read_split takes a file whose plan for G
+// members has at least two ranges that are not empty -- a file of one frame has none -- and, with_floor, whose members get
+// slimm_zstd_split_floor() bytes each or more: (the file's size - the first legal cut) / G (the cap's re-read does not ask:
+// it has no other way).  The floor is a stated default, the codec's round size, not a measurement
+bool zstd_may_cut(const AlignmentFile& f, const std::string& path, uint32_t G, bool with_floor) {
+    if (G < 2u) return false;
+    std::vector<uint64_t> off(G + 1u, 0);
+    if (slimm_host_zstd_ranges(path.c_str(), f.header_bytes(), G, off.data()) != SLIMM_OK) return false;
+    uint32_t filled = 0;
+    for (uint32_t i = 0; i < G; ++i) filled += off[i + 1] > off[i] ? 1u : 0u;
+    if (filled < 2u) return false;
+    if (!with_floor) return true;
+    const int fd = open(path.c_str(), O_RDONLY);
+    if (fd < 0) return false;
+    const uint64_t size = off[G];
+    uint64_t first = 0;
+    const bool ok = zstd_header_end([&](uint64_t at, uint8_t* dst, size_t n) { return pread_all(fd, dst, at, n); }, size, f.header_bytes(), &first);
+    close(fd);
+    return ok && first <= size && (size - first) / G >= slimm_zstd_split_floor();
+}
+
+enum { kBam, kBgzfSam, kSam, kBzip2Sam, kGzipSam, kZstdSam };
+const InputForm kForms[] = {
+    {.name = "BAM", .sam = false, .read = InputForm::Bgzf, .push = push_bam_records, .push_blocks = slimm_push_bgzf_blocks,
+     .plan = slimm_host_bgzf_ranges, .planned = "BGZF blocks"},
+    {.name = "BGZF SAM", .sam = true, .read = InputForm::Bgzf, .push = push_sam_text, .push_blocks = slimm_push_bgzf_sam_blocks,
+     .plan = slimm_host_bgzf_ranges, .planned = "BGZF blocks"},
+    {.name = "SAM", .sam = true, .read = InputForm::Text, .push = push_sam_text, .plan = slimm_host_text_ranges, .planned = "text", .header_32bit = false},
+    {.name = "bzip2", .sam = true, .read = InputForm::Streamed, .push = slimm_push_bzip2_sam_bytes, .plan = slimm_host_bzip2_ranges,
+     .planned = "bzip2 streams", .slack = slimm_bzip2_split_slack, .announce_range = true},
+    {.name = "gzip", .sam = true, .read = InputForm::Streamed, .push = slimm_push_gzip_sam_bytes, .planned = "gzip stream",
+     .wide_header_by_host = true, .end_line = gzip_end_line},
+    {.name = "zstd", .sam = true, .read = InputForm::Streamed, .push = slimm_push_zstd_sam_bytes, .plan = slimm_host_zstd_ranges,
+     .planned = "zstd frames", .wide_header_by_host = true, .announce_range = true, .may_cut = zstd_may_cut, .end_line = zstd_end_line},
+};
+const InputForm& form_of(const AlignmentFile& f) {
+    if (f.is_bam()) return kForms[kBam];
+    switch (f.compression()) {
+        case Compression::Bgzf: return kForms[kBgzfSam];
+        case Compression::Bzip2: return kForms[kBzip2Sam];
+        case Compression::Gzip: return kForms[kGzipSam];
+        case Compression::Zstd: return kForms[kZstdSam];
+        default: return kForms[kSam];
+    }
+}
+// What RecordPump's raw windows push a file as: its own form -- but where the row says so (gzip, zstd) a header of 2^32 text
+// bytes or more goes through the host reader (the push's `skip` has 32 bits): read_text decodes it, and the text is plain SAM's
+const InputForm& pushed_as(const AlignmentFile& f) {
+    const InputForm& form = form_of(f);
+    return form.wide_header_by_host && f.text_header_bytes() >= (1ull << 32) ? kForms[kSam] : form;
+}
+// ... and whether it has raw windows at all: SAM text from anything but a regular file -- a pipe -- goes through the host
+// decoder's buffered reads
+bool has_raw_windows(const AlignmentFile& f) { return f.is_bam() || f.regular_file(); }
+// The files read_split takes: regular files of a form that has a planner, where the form's own condition holds
+bool cut_by_byte_range(const AlignmentFile& f, const std::string& path, uint32_t G, bool with_floor) {
+    const InputForm& form = form_of(f);
+    return f.regular_file() && form.plan && (!form.may_cut || form.may_cut(f, path, G, with_floor));
+}
+// One window of a file's bytes to the device decoder of its form; n = 0: the empty final push
+int push_window(const InputForm& form, slimm_ctx* ctx, const uint8_t* bytes, uint64_t n, bool compressed, uint32_t skip, bool last, uint64_t* got) {
+    if (!n) return form.push(ctx, nullptr, 0, skip, 1, got);
+    return (compressed && form.push_blocks ? form.push_blocks : form.push)(ctx, bytes, n, skip, last ? 1 : 0, got);
+}
+// A push is one device window at most: what its bytes may inflate to, for a window buffer of `cap` bytes (SAM text in BGZF
+// blocks may compress 24-fold: 80 MB of blocks fill it)
+size_t max_inflated_per_push(size_t cap) { return std::min<size_t>(10 * cap, 1900u << 20); }
+
 // The record stream of one file, decoded on a thread of its own from the moment the file is open: while the main thread
 // builds the lineage table and creates the context (the HIP runtime's start-up included), batches pile up in host
 // memory; once the context exists they are pushed in order and the decoder switches to the context's page-locked
@@ -641,6 +765,7 @@ struct RecordPump {
     // record boundaries, reads the fields and compares / hashes the names (slimm_amd/csrc/bam_decode.hip).  The host
     // walked every inflated byte three times for that.  --host-decode keeps the host decoder.
     const bool raw;
+    const InputForm& form;    // what the raw windows are read and pushed as
     const std::string head;   // what the [trace] lines start with (FileLog::head)
     // bytes per window buffer (--window-mb: tests make windows smaller than a record)
     static size_t& raw_cap_setting() {
@@ -688,11 +813,10 @@ struct RecordPump {
     RecordPump(AlignmentFile& f, bool check_words, bool device_decode, const Options& o, const std::string& trace_head)
         : bam(f), want_check(check_words),
           marked(!check_words && !o.verify_grouping && !o.packed_records),
-          // (SAM text from anything but a regular file -- a pipe -- goes through the host decoder's buffered reads)
-          raw(device_decode && !o.verify_grouping && !o.packed_records && !o.host_decode && (f.is_bam() || f.regular_file())),
-          head(trace_head) {
+          raw(device_decode && !o.verify_grouping && !o.packed_records && !o.host_decode && has_raw_windows(f)),
+          form(pushed_as(f)), head(trace_head) {
         device_period = o.device_inflate;
-        device_window = std::min<size_t>(10 * raw_cap(), 1900u << 20);
+        device_window = max_inflated_per_push(raw_cap());
         th = std::thread([this] { raw ? run_raw() : run(); });  // (in the body: every member is initialised by now)
     }
     ~RecordPump() {
@@ -709,8 +833,6 @@ struct RecordPump {
     // the inflater of the device-decode mode: fills the window buffers in turn.  BGZF files -- BAM, or SAM text -- alike:
     // windows the host inflates (read_raw) and, every device_period-th of those read in place, whole blocks (read_blocks)
     void run_raw() {
-        const bool bgzf = bam.compression() == Compression::Bgzf;
-        const bool streamed = streamed_sam();
         for (unsigned w = 0;; w = (w + 1) % kRawBuffers) {
             {
                 std::unique_lock<std::mutex> g(mu);
@@ -729,11 +851,11 @@ struct RecordPump {
             // (every device_period-th of the windows read in place)
             bool compressed = false;
             long n;
-            if (streamed) {   // the file's bytes as they lie in it (slimm_push_bzip2_sam_bytes / _gzip_sam_bytes / _zstd_sam_bytes decode them)
+            if (form.read == InputForm::Streamed) {   // the file's bytes as they lie in it (the codec's push decodes them)
                 n = bam.read_compressed(raw_buf[w].get(), raw_cap());
                 compressed = true;
                 ++raw_windows_device;
-            } else if (bam.can_read_text()) {   // SAM, plain: the text (slimm_push_sam_bytes finds and decodes the lines)
+            } else if (form.read == InputForm::Text) {   // SAM, plain: the text (slimm_push_sam_bytes finds and decodes the lines)
                 n = bam.read_text(raw_buf[w].get(), raw_cap());
                 ++raw_windows_device;
             } else if (device_period && bam.can_read_blocks() && (raw_windows_device + raw_windows_host) % device_period == device_period - 1u) {
@@ -748,7 +870,7 @@ struct RecordPump {
             decode_ms += ms(t1, std::chrono::steady_clock::now());
             {
                 std::lock_guard<std::mutex> g(mu);
-                raw_ready.push_back(RawWindow{w, n, n > 0 && ((bgzf && bam.raw_exhausted()) || (streamed && bam.compressed_exhausted())), compressed});
+                raw_ready.push_back(RawWindow{w, n, n > 0 && (form.read == InputForm::Streamed ? bam.compressed_exhausted() : form.read == InputForm::Bgzf && bam.raw_exhausted()), compressed});
             }
             cv.notify_all();
             if (n <= 0) {
@@ -757,21 +879,15 @@ struct RecordPump {
             }
         }
     }
-    // gzip and zstd SAM are decoded on the device (a header of 4 GiB of text or more: by the host reader, the push's `skip` has 32 bits)
-    bool on_device(Compression k) const { return !bam.is_bam() && bam.compression() == k && bam.text_header_bytes() < (1ull << 32); }
-    // bzip2, gzip and zstd SAM: the file's bytes go to the device as they lie in the file
-    bool streamed_sam() const { return bam.compression() == Compression::Bzip2 || on_device(Compression::Gzip) || on_device(Compression::Zstd); }
     // ... and the thread that hands them to the device, from the moment the context exists
     void push_raw(slimm_ctx* c) {
         bool pinned[kRawBuffers] = {};
         bool closed = false;  // a window went out as the file's last
         bool in_flight = false;  // the window pushed last is still being copied out of its buffer
         bool end_traced = false;
-        const bool text = !bam.is_bam(), gzip = on_device(Compression::Gzip), zstd = on_device(Compression::Zstd), streamed = streamed_sam();
         // (a streamed file goes from its first byte: the first push skips the header's decoded bytes)
-        uint32_t skip = streamed ? static_cast<uint32_t>(bam.text_header_bytes()) : 0u;
-        const auto push_streamed = zstd ? slimm_push_zstd_sam_bytes : gzip ? slimm_push_gzip_sam_bytes : slimm_push_bzip2_sam_bytes;
-        if (text) {   // SAM text names its references: the header's names for the device's look-up
+        uint32_t skip = form.read == InputForm::Streamed ? static_cast<uint32_t>(bam.text_header_bytes()) : 0u;
+        if (form.sam) {   // SAM text names its references: the header's names for the device's look-up
             std::vector<const char*> names;
             for (const std::string& nm : bam.ref_names()) names.push_back(nm.c_str());
             if (slimm_set_reference_names(c, names.data()) != SLIMM_OK) {
@@ -801,30 +917,17 @@ struct RecordPump {
                     (void)slimm_pin_host_buffer(c, raw_buf[w.which].get(), raw_cap());  // (pageable memory still works)
                     pinned[w.which] = true;
                 }
-                const uint8_t* p = raw_buf[w.which].get();
-                const uint64_t n = static_cast<uint64_t>(w.n);
-                const int last = w.last ? 1 : 0;
-                rc = streamed       ? push_streamed(c, p, n, skip, last, &got)
-                     : w.compressed ? (text ? slimm_push_bgzf_sam_blocks(c, p, n, 0u, last, &got) : slimm_push_bgzf_blocks(c, p, n, 0u, last, &got))
-                                    : (text ? slimm_push_sam_bytes(c, p, n, last, &got) : slimm_push_bam_bytes(c, p, n, last, &got));
+                rc = push_window(form, c, raw_buf[w.which].get(), static_cast<uint64_t>(w.n), w.compressed, skip, w.last, &got);
                 skip = 0;
                 closed = w.last;
             } else if (!closed) {
-                rc = streamed ? push_streamed(c, nullptr, 0, skip, 1, &got)
-                     : text ? slimm_push_sam_bytes(c, nullptr, 0, 1, &got)
-                            : slimm_push_bam_bytes(c, nullptr, 0, 1, &got);  // (the end came without notice: an incomplete record is an error)
+                rc = push_window(form, c, nullptr, 0, false, skip, true, &got);  // (the end came without notice: an incomplete record is an error)
             }
             raw_push_ms += ms(t1, std::chrono::steady_clock::now());
             raw_records += got;
-            if ((gzip || zstd) && g_trace && rc >= 0 && (closed || w.n == 0) && !end_traced) {   // (the file's end: what the device decoded)
-                uint64_t st[20] = {};
+            if (form.end_line && g_trace && rc >= 0 && (closed || w.n == 0) && !end_traced) {   // (the file's end: what the device decoded)
                 end_traced = true;
-                if (zstd && slimm_get_zstd_stats(c, st) == SLIMM_OK)
-                    fprintf(stderr, "%szstd SAM on the device: %llu frames, %llu blocks, %llu bytes of text\n", head.c_str(), (unsigned long long)st[0],
-                            (unsigned long long)(st[2] + st[3] + st[4]), (unsigned long long)st[16]);
-                if (gzip && slimm_get_gzip_stats(c, st) == SLIMM_OK)
-                    fprintf(stderr, "%sgzip SAM on the device: %llu members, %llu chunks (%llu candidates dropped), %llu bytes of text\n",
-                            head.c_str(), (unsigned long long)st[0], (unsigned long long)st[1], (unsigned long long)st[3], (unsigned long long)st[9]);
+                form.end_line(head.c_str(), &c, 1);
             }
             {
                 // (a window's buffer is the library's until the NEXT push returns: its copy runs beside the work on the
@@ -961,18 +1064,6 @@ struct RecordPump {
     }
 };
 
-// --split-input: every member of a group reads, inflates and decodes its own contiguous byte range of a file -- GROUPED by
-// read name or in any order (the stitch then deals the records by key) -- at
-// once -- its own pread threads, page-locked buffers and pushing thread -- and the library stitches the cuts on the
-// devices (include/slimm_hip.h, "ONE FILE SPLIT BY BYTE RANGE").  The file's form: BAM or SAM text in BGZF blocks -- ranges
-// of whole blocks, member 0 skips the header's inflated bytes -- or plain SAM text: ranges cut anywhere behind the header,
-// read as they lie in the file (`names`: the header's reference names, which every member's SAM decoder needs) -- or bzip2
-// SAM: ranges cut at any byte behind the header's block, each read with slimm_bzip2_split_slack() bytes behind it (at most
-// to the file's end) so that its last block can finish; member 0 skips the header's decoded bytes -- or zstd SAM: ranges
-// cut where frames start (slimm_host_zstd_ranges), each announced and read exactly, without slack.  The
-// reader threads are split over the members, not multiplied (a command gets 16 CPUs).  Returns SLIMM_OK or the code of
-// what failed; *why says what.
-enum class SplitForm { Bam, BgzfSam, Sam, Bzip2Sam, ZstdSam };
 struct SplitBuffers {   // (page-locked for the life of the group's contexts: they outlive the group)
     struct Map {
         uint8_t* p = nullptr;
@@ -990,22 +1081,134 @@ struct SplitBuffers {   // (page-locked for the life of the group's contexts: th
         return static_cast<uint8_t*>(p);
     }
 };
-int read_split(slimm_group* grp, uint32_t G, const std::string& path, SplitForm form, const std::vector<std::string>& names,
+// One member's reading of its range of a split file (read_split).  Three buffers: one being read, one being copied, the one
+// before it still the library's until the next push
+struct SplitMember {
+    // set by read_split: the member's context and place, its range [begin, range_end) of the file and where its reads end (the
+    // form's slack behind the range -- none behind the file's last --, at most to the file's end), its share of the threads
+    const InputForm* form = nullptr;
+    slimm_ctx* ctx = nullptr;
+    uint32_t index = 0, header_skip = 0;   // (header_skip: member 0's, the header's inflated or decoded bytes)
+    bool file_last = false;
+    uint64_t begin = 0, range_end = 0, read_end = 0;
+    int fd = -1;
+    unsigned threads = 1;
+    size_t cap = 0, read_hint = 0;
+    uint8_t* buf[3] = {};
+    // what it came to
+    int rc = SLIMM_OK;
+    std::string err;
+    uint64_t records = 0;
+    double pread_ms = 0, push_ms = 0, last_ms = 0;
+
+    static double ms(std::chrono::steady_clock::time_point a) {
+        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count();
+    }
+    // bytes [at, at + n) of the file into dst, by pread on at most `threads` threads (one per MiB); false on a read error
+    static bool pread_span(int fd, uint8_t* dst, uint64_t at, size_t n, unsigned threads) {
+        const unsigned nt = static_cast<unsigned>(std::max<size_t>(1, std::min<size_t>(threads, n >> 20)));
+        const size_t per = (n + nt - 1) / nt;
+        std::atomic<bool> ok{true};
+        std::vector<std::thread> th;
+        for (unsigned t = 0; t < nt; ++t)
+            th.emplace_back([&, t] {
+                const size_t lo = std::min(n, t * per), hi = std::min(n, lo + per);
+                if (!pread_all(fd, dst + lo, at + lo, hi - lo)) ok = false;
+            });
+        for (auto& t : th) t.join();
+        return ok;
+    }
+    // The bytes of the whole BGZF blocks at the front of buf[0, want) (0: none fits).  Blocks of SAM text end a push at
+    // `max_inflated` inflated bytes as well (max_inflated_per_push); *read_hint is then set to what is worth reading
+    static size_t whole_bgzf_blocks(const uint8_t* buf, size_t want, bool sam, uint64_t max_inflated, size_t* read_hint) {
+        size_t n = 0;
+        uint64_t inflated = 0;
+        while (want - n >= 18) {
+            const uint8_t* h = buf + n;
+            const size_t bsize = (static_cast<size_t>(h[16]) | (static_cast<size_t>(h[17]) << 8)) + 1u;
+            if (h[0] != 0x1f || h[1] != 0x8b || want - n < bsize) break;
+            const uint8_t* t = h + bsize - 4;   // (ISIZE)
+            const uint64_t isize = !sam || bsize < 28u ? 0u
+                                                       : static_cast<uint64_t>(t[0]) | (static_cast<uint64_t>(t[1]) << 8) |
+                                                             (static_cast<uint64_t>(t[2]) << 16) | (static_cast<uint64_t>(t[3]) << 24);
+            if (n && inflated + isize > max_inflated) {
+                *read_hint = n + (n >> 2) + (1u << 16);
+                break;
+            }
+            inflated += isize;
+            n += bsize;
+        }
+        return n;
+    }
+    // the next push's bytes from `at` on into buffer w: their count -- whole blocks of a BGZF form, else the bytes as they lie
+    // there, cut anywhere --, 0 at the end of the reads (or when no block fits), -1 on a read error
+    long fill(unsigned w, uint64_t at) {
+        const size_t want = static_cast<size_t>(std::min<uint64_t>(std::min(cap, read_hint), read_end - at));
+        if (!want) return 0;
+        if (!pread_span(fd, buf[w], at, want, threads)) return -1;
+        if (form->read != InputForm::Bgzf) return static_cast<long>(want);
+        return static_cast<long>(whole_bgzf_blocks(buf[w], want, form->sam, form->sam ? max_inflated_per_push(cap) : ~0ull, &read_hint));
+    }
+    void failed(int code, const std::string& e) {
+        rc = code;
+        err = "member " + std::to_string(index) + ": " + e;
+    }
+    void run(const char* const* names) {
+        int r = form->sam ? slimm_set_reference_names(ctx, names) : SLIMM_OK;
+        if (r == SLIMM_OK) r = slimm_set_input_mid_file(ctx, index > 0 ? 1 : 0, file_last ? 0 : 1);
+        if (r == SLIMM_OK && form->announce_range) r = slimm_set_input_range(ctx, begin, range_end);
+        if (r == SLIMM_OK) r = slimm_set_input_size_hint(ctx, range_end - begin);
+        if (r != SLIMM_OK) return failed(r, slimm_last_error(ctx));
+        for (auto* b : buf) (void)slimm_pin_host_buffer(ctx, b, cap);   // (pageable memory still works)
+        // the next buffer is read while this one is pushed (the one before it is the library's until this push returns)
+        read_hint = cap;
+        uint64_t pos = begin;
+        auto t0 = std::chrono::steady_clock::now();
+        long n = fill(0, pos);
+        pread_ms += ms(t0);
+        for (unsigned w = 0;; w = (w + 1) % 3) {
+            if (n < 0) return failed(SLIMM_E_INVALID, "read error");
+            if (n == 0 && pos < read_end) return failed(SLIMM_E_INVALID, "a BGZF block does not fit the window");
+            const bool last = pos + static_cast<uint64_t>(n) == read_end;
+            long next = 0;
+            double next_ms = 0;
+            std::thread ahead;
+            if (!last)
+                ahead = std::thread([&, w] {
+                    const auto a = std::chrono::steady_clock::now();
+                    next = fill((w + 1) % 3, pos + static_cast<uint64_t>(n));
+                    next_ms = ms(a);
+                });
+            uint64_t got = 0;
+            t0 = std::chrono::steady_clock::now();
+            r = push_window(*form, ctx, buf[w], static_cast<uint64_t>(n), true, pos == begin ? header_skip : 0u, last, &got);
+            const double t = ms(t0);
+            if (ahead.joinable()) ahead.join();
+            pread_ms += next_ms;
+            push_ms += t;
+            if (last) last_ms = t;
+            if (r != SLIMM_OK) return failed(r, slimm_last_error(ctx));
+            records += got;
+            pos += static_cast<uint64_t>(n);
+            n = next;
+            if (last) return;
+        }
+    }
+};
+// --split-input: every member of a group reads, inflates and decodes its own contiguous byte range of a file -- GROUPED by
+// read name or in any order (the stitch then deals the records by key) -- at once, and the library stitches the cuts on the
+// devices (include/slimm_hip.h, "ONE FILE SPLIT BY BYTE RANGE").  The form's row says how the file is cut and read; member 0
+// skips the header's inflated (decoded) bytes; `names`: the header's reference names, for every member's SAM decoder.  The
+// reader threads are split over the members, not multiplied (a command gets 16 CPUs).  Returns SLIMM_OK or the code of what
+// failed; *why says what.
+int read_split(slimm_group* grp, uint32_t G, const std::string& path, const InputForm& form, const std::vector<std::string>& names,
                uint64_t header_bytes, size_t window_cap, SplitBuffers& bufs, const char* head, std::string& why) {
     std::vector<uint64_t> off(G + 1, 0);
-    const bool bzip2 = form == SplitForm::Bzip2Sam, zstd = form == SplitForm::ZstdSam;
-    const bool text = form == SplitForm::Sam || bzip2 || zstd, sam = form != SplitForm::Bam;   // (text: the bytes as they lie in the file)
-    if (zstd    ? slimm_host_zstd_ranges(path.c_str(), header_bytes, G, off.data()) != SLIMM_OK
-        : bzip2 ? (header_bytes >= (1ull << 32) || slimm_host_bzip2_ranges(path.c_str(), header_bytes, G, off.data()) != SLIMM_OK)
-        : text ? slimm_host_text_ranges(path.c_str(), header_bytes, G, off.data()) != SLIMM_OK
-               : (header_bytes >= (1ull << 32) || slimm_host_bgzf_ranges(path.c_str(), header_bytes, G, off.data()) != SLIMM_OK)) {
-        why = zstd   ? "the file's zstd frames could not be planned into ranges"
-              : bzip2 ? "the file's bzip2 streams could not be planned into ranges"
-              : text ? "the file's text could not be planned into ranges"
-                     : "the file's BGZF blocks could not be planned into ranges";
+    if (!form.plan || (form.header_32bit && header_bytes >= (1ull << 32)) || form.plan(path.c_str(), header_bytes, G, off.data()) != SLIMM_OK) {
+        why = std::string("the file's ") + form.planned + " could not be planned into ranges";
         return SLIMM_E_INVALID;
     }
-    const uint64_t slack = bzip2 ? slimm_bzip2_split_slack() : 0u;
+    const uint64_t slack = form.slack ? form.slack() : 0u;
     std::vector<const char*> name_ptrs;
     for (const std::string& nm : names) name_ptrs.push_back(nm.c_str());
     const int fd = open(path.c_str(), O_RDONLY);
@@ -1014,149 +1217,34 @@ int read_split(slimm_group* grp, uint32_t G, const std::string& path, SplitForm 
         return SLIMM_E_INVALID;
     }
     const unsigned cores = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-    const unsigned per_member = std::max(1u, cores / G);
-    // (three buffers a member: one being read, one being copied, the one before it still the library's until the next push)
-    const size_t cap = std::max<size_t>(1u << 20, G <= 2 ? window_cap : window_cap * 2 / G);
-    struct Member {
-        int rc = SLIMM_OK;
-        std::string err;
-        uint64_t records = 0, bytes = 0;
-        double pread_ms = 0, push_ms = 0, last_ms = 0;
-        uint8_t* buf[3] = {};
-    };
-    std::vector<Member> m(G);
-    for (uint32_t i = 0; i < G; ++i)
-        for (auto& b : m[i].buf)
-            if (!(b = bufs.get(cap))) {
+    std::vector<SplitMember> m(G);
+    std::vector<slimm_ctx*> ctxs(G);
+    for (uint32_t i = 0; i < G; ++i) {
+        SplitMember& M = m[i];
+        M.form = &form, M.fd = fd, M.index = i, M.file_last = i + 1 == G;
+        M.ctx = ctxs[i] = slimm_group_context(grp, i);
+        M.header_skip = i == 0 ? static_cast<uint32_t>(header_bytes) : 0u;
+        M.begin = off[i], M.range_end = off[i + 1];
+        M.read_end = std::min<uint64_t>(off[G], off[i + 1] + (M.file_last ? 0u : slack));
+        M.threads = std::max(1u, cores / G);
+        M.cap = std::max<size_t>(1u << 20, G <= 2 ? window_cap : window_cap * 2 / G);
+        for (auto& b : M.buf)
+            if (!(b = bufs.get(M.cap))) {
                 close(fd);
                 why = "out of host memory for the members' buffers";
                 return SLIMM_E_INVALID;
             }
-    auto ms = [](std::chrono::steady_clock::time_point a) {
-        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count();
-    };
-    auto member = [&](uint32_t i) {
-        Member& M = m[i];
-        slimm_ctx* ctx = slimm_group_context(grp, i);
-        auto failed = [&](int rc, const std::string& e) {
-            M.rc = rc;
-            M.err = "member " + std::to_string(i) + ": " + e;
-        };
-        int rc = sam ? slimm_set_reference_names(ctx, name_ptrs.data()) : SLIMM_OK;
-        if (rc == SLIMM_OK) rc = slimm_set_input_mid_file(ctx, i > 0 ? 1 : 0, i + 1 < G ? 1 : 0);
-        if (rc == SLIMM_OK && (bzip2 || zstd)) rc = slimm_set_input_range(ctx, off[i], off[i + 1]);
-        if (rc == SLIMM_OK) rc = slimm_set_input_size_hint(ctx, off[i + 1] - off[i]);
-        if (rc != SLIMM_OK) return failed(rc, slimm_last_error(ctx));
-        for (auto* b : M.buf) (void)slimm_pin_host_buffer(ctx, b, cap);   // (pageable memory still works)
-        // (bzip2: the slack behind the range -- none behind the file's last --, at most to the file's end)
-        const uint64_t end = std::min<uint64_t>(off[G], off[i + 1] + (i + 1 < G ? slack : 0u));
-        // whole BGZF blocks of [at, end) into buffer w, at most `cap` bytes, by pread on the member's share of the threads:
-        // the bytes of those blocks (0: none fits), -1 on a read error.  Blocks of SAM text end a push at `max_inflated`
-        // inflated bytes as well (a push is one device window at most, and text may compress 24-fold: 80 MB of blocks
-        // fill it; as RecordPump::device_window bounds one context's pushes); read_hint: what is worth reading once that
-        // bound has ended a push.  Plain text: the bytes as they lie there, cut anywhere
-        const uint64_t max_inflated = sam ? std::min<uint64_t>(10ull * cap, 1900ull << 20) : ~0ull;
-        size_t read_hint = cap;
-        auto read_blocks = [&](unsigned w, uint64_t at) -> long {
-            const size_t want = static_cast<size_t>(std::min<uint64_t>(std::min(cap, read_hint), end - at));
-            if (!want) return 0;
-            const unsigned nt = static_cast<unsigned>(std::max<size_t>(1, std::min<size_t>(per_member, want >> 20)));
-            const size_t per = (want + nt - 1) / nt;
-            std::atomic<bool> ok{true};
-            std::vector<std::thread> th;
-            for (unsigned t = 0; t < nt; ++t)
-                th.emplace_back([&, t] {
-                    size_t lo = std::min(want, t * per);
-                    const size_t hi = std::min(want, lo + per);
-                    while (lo < hi) {
-                        const ssize_t k = pread(fd, M.buf[w] + lo, hi - lo, static_cast<off_t>(at + lo));
-                        if (k <= 0) {
-                            ok = false;
-                            return;
-                        }
-                        lo += static_cast<size_t>(k);
-                    }
-                });
-            for (auto& t : th) t.join();
-            if (!ok) return -1;
-            if (text) return static_cast<long>(want);
-            size_t n = 0;
-            uint64_t inflated = 0;
-            while (want - n >= 18) {
-                const uint8_t* h = M.buf[w] + n;
-                const size_t bsize = (static_cast<size_t>(h[16]) | (static_cast<size_t>(h[17]) << 8)) + 1u;
-                if (h[0] != 0x1f || h[1] != 0x8b || want - n < bsize) break;
-                const uint8_t* t = h + bsize - 4;   // (ISIZE)
-                const uint64_t isize = !sam || bsize < 28u ? 0u
-                                                           : static_cast<uint64_t>(t[0]) | (static_cast<uint64_t>(t[1]) << 8) |
-                                                                 (static_cast<uint64_t>(t[2]) << 16) | (static_cast<uint64_t>(t[3]) << 24);
-                if (n && inflated + isize > max_inflated) {
-                    read_hint = n + (n >> 2) + (1u << 16);
-                    break;
-                }
-                inflated += isize;
-                n += bsize;
-            }
-            return static_cast<long>(n);
-        };
-        // the next buffer is read while this one is pushed (the one before it is the library's until this push returns)
-        uint64_t pos = off[i];
-        auto t0 = std::chrono::steady_clock::now();
-        long n = read_blocks(0, pos);
-        M.pread_ms += ms(t0);
-        for (unsigned w = 0;; w = (w + 1) % 3) {
-            if (n < 0) return failed(SLIMM_E_INVALID, "read error");
-            if (n == 0 && pos < end) return failed(SLIMM_E_INVALID, "a BGZF block does not fit the window");
-            const bool last = pos + static_cast<uint64_t>(n) == end;
-            long next = 0;
-            double next_ms = 0;
-            std::thread ahead;
-            if (!last)
-                ahead = std::thread([&, w] {
-                    const auto a = std::chrono::steady_clock::now();
-                    next = read_blocks((w + 1) % 3, pos + static_cast<uint64_t>(n));
-                    next_ms = ms(a);
-                });
-            uint64_t got = 0;
-            t0 = std::chrono::steady_clock::now();
-            const uint32_t skip = pos == off[i] && i == 0 ? static_cast<uint32_t>(header_bytes) : 0u;
-            const uint64_t nb = static_cast<uint64_t>(n);
-            if (bzip2)
-                rc = slimm_push_bzip2_sam_bytes(ctx, n ? M.buf[w] : nullptr, nb, skip, last ? 1 : 0, &got);
-            else if (zstd)
-                rc = slimm_push_zstd_sam_bytes(ctx, n ? M.buf[w] : nullptr, nb, skip, last ? 1 : 0, &got);
-            else if (!n)   // (an empty range)
-                rc = sam ? slimm_push_sam_bytes(ctx, nullptr, 0, 1, &got) : slimm_push_bam_bytes(ctx, nullptr, 0, 1, &got);
-            else if (text)
-                rc = slimm_push_sam_bytes(ctx, M.buf[w], nb, last ? 1 : 0, &got);
-            else
-                rc = sam ? slimm_push_bgzf_sam_blocks(ctx, M.buf[w], nb, skip, last ? 1 : 0, &got)
-                         : slimm_push_bgzf_blocks(ctx, M.buf[w], nb, skip, last ? 1 : 0, &got);
-            const double t = ms(t0);
-            if (ahead.joinable()) ahead.join();
-            M.pread_ms += next_ms;
-            M.push_ms += t;
-            if (last) M.last_ms = t;
-            if (rc != SLIMM_OK) return failed(rc, slimm_last_error(ctx));
-            M.records += got;
-            M.bytes += static_cast<uint64_t>(n);
-            pos += static_cast<uint64_t>(n);
-            n = next;
-            if (last) return;
-        }
-    };
+    }
     {
         std::vector<std::thread> th;
-        for (uint32_t i = 0; i < G; ++i) th.emplace_back(member, i);
+        for (SplitMember& M : m) th.emplace_back([&M, &name_ptrs] { M.run(name_ptrs.data()); });
         for (auto& t : th) t.join();
     }
     close(fd);
-    for (uint32_t i = 0; i < G; ++i) {
-        if (g_trace)
-            fprintf(stderr, "%ssplit member %u: bytes [%llu, %llu) of %llu, %llu records, pread %.2f ms, push %.2f ms, last push (wait) %.2f ms\n", head, i,
-                    static_cast<unsigned long long>(off[i]), static_cast<unsigned long long>(off[i + 1]), static_cast<unsigned long long>(off[G]),
-                    static_cast<unsigned long long>(m[i].records), m[i].pread_ms, m[i].push_ms, m[i].last_ms);
-    }
+    for (uint32_t i = 0; i < G && g_trace; ++i)
+        fprintf(stderr, "%ssplit member %u: bytes [%llu, %llu) of %llu, %llu records, pread %.2f ms, push %.2f ms, last push (wait) %.2f ms\n", head, i,
+                static_cast<unsigned long long>(off[i]), static_cast<unsigned long long>(off[i + 1]), static_cast<unsigned long long>(off[G]),
+                static_cast<unsigned long long>(m[i].records), m[i].pread_ms, m[i].push_ms, m[i].last_ms);
     for (uint32_t i = 0; i < G; ++i)
         if (m[i].rc != SLIMM_OK) {
             why = m[i].err;
@@ -1164,59 +1252,8 @@ int read_split(slimm_group* grp, uint32_t G, const std::string& path, SplitForm 
         }
     const int rc = slimm_group_stitch_ranges(grp);
     if (rc != SLIMM_OK) why = slimm_group_last_error(grp);
-    if (zstd && g_trace && rc == SLIMM_OK) {   // (the members' counters summed: the whole file's)
-        uint64_t frames = 0, blocks = 0, text_bytes = 0;
-        for (uint32_t i = 0; i < G; ++i) {
-            uint64_t st[20] = {};
-            if (slimm_get_zstd_stats(slimm_group_context(grp, i), st) != SLIMM_OK) continue;
-            frames += st[0], blocks += st[2] + st[3] + st[4], text_bytes += st[16];
-        }
-        fprintf(stderr, "%szstd SAM on the device: %llu frames, %llu blocks, %llu bytes of text\n", head, (unsigned long long)frames,
-                (unsigned long long)blocks, (unsigned long long)text_bytes);
-    }
+    if (form.end_line && g_trace && rc == SLIMM_OK) form.end_line(head, ctxs.data(), G);   // (the members' counters summed: the whole file's)
     return rc;
-}
-
-// The files read_split takes whatever they hold: a regular file of BAM records, of SAM text, of SAM text in BGZF blocks, or
-// of bzip2 SAM.  (A plain gzip stream cannot be cut: it goes through one member.  zstd SAM: zstd_reads_by_byte_range.)
-bool reads_by_byte_range(const AlignmentFile& f) {
-    return f.regular_file() && (f.is_bam() || f.compression() == Compression::None || f.compression() == Compression::Bgzf ||
-                                f.compression() == Compression::Bzip2);
-}
-// zstd SAM is cut where frames start and nowhere else (slimm_host_zstd_ranges): read_split takes a regular file whose plan
-// for G members has at least two ranges that are not empty -- a file of one frame has none -- and, with_floor, whose
-// members get slimm_zstd_split_floor() bytes each or more: (the file's size - the first legal cut) / G (the cap's re-read
-// does not ask: it has no other way).  The floor is a stated default, the codec's round size, not a measurement
-bool zstd_reads_by_byte_range(const AlignmentFile& f, const std::string& path, uint32_t G, bool with_floor) {
-    if (f.is_bam() || f.compression() != Compression::Zstd || !f.regular_file() || f.header_bytes() >= (1ull << 32) || G < 2u) return false;
-    std::vector<uint64_t> off(G + 1u, 0);
-    if (slimm_host_zstd_ranges(path.c_str(), f.header_bytes(), G, off.data()) != SLIMM_OK) return false;
-    uint32_t filled = 0;
-    for (uint32_t i = 0; i < G; ++i) filled += off[i + 1] > off[i] ? 1u : 0u;
-    if (filled < 2u) return false;
-    if (!with_floor) return true;
-    const int fd = open(path.c_str(), O_RDONLY);
-    if (fd < 0) return false;
-    const uint64_t size = off[G];
-    uint64_t first = 0;
-    const bool ok = zstd_header_end(
-        [&](uint64_t at, uint8_t* dst, size_t n) {
-            for (; n;) {
-                const ssize_t k = pread(fd, dst, n, static_cast<off_t>(at));
-                if (k <= 0) return false;
-                dst += k, at += static_cast<uint64_t>(k), n -= static_cast<size_t>(k);
-            }
-            return true;
-        },
-        size, f.header_bytes(), &first);
-    close(fd);
-    return ok && first <= size && (size - first) / G >= slimm_zstd_split_floor();
-}
-SplitForm split_form(const AlignmentFile& f) {
-    if (f.is_bam()) return SplitForm::Bam;
-    if (f.compression() == Compression::Zstd) return SplitForm::ZstdSam;
-    if (f.compression() == Compression::Bzip2) return SplitForm::Bzip2Sam;
-    return f.compression() == Compression::Bgzf ? SplitForm::BgzfSam : SplitForm::Sam;
 }
 
 // One reading of a file up to its context: the file open at its first record, the choices its header and the options make,
@@ -1383,12 +1420,12 @@ std::unique_ptr<Reading> set_up(Session& S, const std::string& path, bool any_or
     // slimm_group_get_profiles: a GROUPED file in stretches cut at qName runs, any other order by key; what the pump does
     // not push raw -- --host-decode, pipes ... -- the host reader deals)
     const bool may_split = options.split_input && options.devices.size() > 1 && !options.host_decode && !options.verify_grouping && !options.packed_records;
-    F->split_input = may_split && (reads_by_byte_range(bam) || zstd_reads_by_byte_range(bam, path, static_cast<uint32_t>(options.devices.size()), true));
-    if (g_trace && !any_order && options.split_input && options.devices.size() > 1 && !bam.is_bam() && bam.compression() == Compression::Gzip)
-        fprintf(stderr, "%s--split-input: a gzip stream is not cut by byte range; member 0 reads %s\n", S.trace_head(), path.c_str());
-    // (a zstd file of one frame, or one whose members would get less than the floor; or the host decoders were asked for)
-    if (g_trace && !any_order && !F->split_input && options.split_input && options.devices.size() > 1 && !bam.is_bam() && bam.compression() == Compression::Zstd)
-        fprintf(stderr, "%s--split-input: a zstd stream is not cut by byte range; member 0 reads %s\n", S.trace_head(), path.c_str());
+    F->split_input = may_split && cut_by_byte_range(bam, path, static_cast<uint32_t>(options.devices.size()), true);
+    // (a form that is not cut whenever it is asked: gzip never; a zstd file of one frame, or one whose members would get less
+    // than the floor; or the host decoders were asked for)
+    const InputForm& form = form_of(bam);
+    if (g_trace && !any_order && !F->split_input && options.split_input && options.devices.size() > 1 && (!form.plan || form.may_cut))
+        fprintf(stderr, "%s--split-input: a %s stream is not cut by byte range; member 0 reads %s\n", S.trace_head(), form.name, path.c_str());
     if (!F->split_input)
         F->pump.reset(new RecordPump(bam, F->check_words, true, options, S.log->head));
 
@@ -1446,8 +1483,8 @@ std::unique_ptr<Reading> set_up(Session& S, const std::string& path, bool any_or
 }
 
 // What a push that found more records than one context takes leads to (the --split-input reading decides in run_group):
-// a group reading through member 0 -- HostDecode, the host reader deals them; one context of a BAM, SAM, BGZF SAM or bzip2 SAM file, grouped
-// or in any order -- MoreMembers, a group on the device reads the file by byte range; any other one context -- Fail.
+// a group reading through member 0 -- HostDecode, the host reader deals them; one context of a file whose form is cut
+// (kForms), grouped or in any order -- MoreMembers, a group on the device reads the file by byte range; any other one context -- Fail.
 enum class OnCap { Fail, HostDecode, MoreMembers };
 
 // The file's records through F.pump into `t`: Done, or Failed with the reason printed.  A record longer than the device
@@ -1537,7 +1574,7 @@ Outcome run_group(Session& S, Reading& F, const std::vector<int>& devs, bool spl
     bool split_read = false;
     if (split) {   // every member its own byte range (read_split); what fails there goes through member 0 after all
         std::string why;
-        const int src = read_split(grp.get(), static_cast<uint32_t>(devs.size()), F.path, split_form(F.bam), F.bam.ref_names(),
+        const int src = read_split(grp.get(), static_cast<uint32_t>(devs.size()), F.path, form_of(F.bam), F.bam.ref_names(),
                                    F.bam.header_bytes(), RecordPump::raw_cap(), F.split_bufs, S.trace_head(), why);
         F.trace.mark("split: read + decode + stitch");
         if (src == SLIMM_E_REGROUP) return Outcome::ReadAgainAnyOrder;
@@ -1612,10 +1649,9 @@ Outcome run_context(Session& S, Reading& F) {
     S.err() << "Analysing alignments, reads and references ....... ";
     // (zstd SAM: whether the file can be cut is asked only once the cap is met -- the plan reads the file; the floor is not
     // consulted here.  A file of one frame cannot be cut and ends at the cap, as it did)
-    const bool zstd_file = !F.bam.is_bam() && F.bam.compression() == Compression::Zstd && F.bam.regular_file();
-    const bool byte_ranges = reads_by_byte_range(F.bam) || zstd_file;
-    const Outcome pushed = push_file(S, F, Target{ctx}, byte_ranges ? OnCap::MoreMembers : OnCap::Fail);
-    if (pushed == Outcome::MoreMembers && zstd_file && !zstd_reads_by_byte_range(F.bam, F.path, 2u, false)) {
+    const InputForm& form = form_of(F.bam);
+    const Outcome pushed = push_file(S, F, Target{ctx}, F.bam.regular_file() && form.plan ? OnCap::MoreMembers : OnCap::Fail);
+    if (pushed == Outcome::MoreMembers && form.may_cut && !form.may_cut(F.bam, F.path, 2u, false)) {
         S.err() << "slimm: pushing records: " << slimm_last_error(ctx) << "\n";
         return Outcome::Failed;
     }

@@ -8,12 +8,9 @@
 // left member's last line must end with the head.  A range of bzip2 SAM starts at the first block of its own
 // (bzip2_decode.hip) and is text from there on; its chain of blocks is held against its neighbours' first (split_bz2_chains).  A range of zstd SAM starts and ends where frames do
 // (zstd_decode.hip) and is text in between; that every member's frames ended at its range's end is checked first (split_zstd_ends).  The reference reads one file with one reader (src/misc.hpp:498-522).
-#include <fcntl.h>
-#include <sys/stat.h>
-#include <unistd.h>
-
 #include "context.h"
 #include "split.h"
+#include "split_plan.h"
 #include "host/zstd.cpp"   // (the host's serial zstd decoder, for the header's frames: the library holds no other copy of it)
 
 namespace {
@@ -30,22 +27,7 @@ uint32_t bgzf_header_size(const uint8_t* h) {
     return total >= 28u ? total : 0u;
 }
 
-struct File {
-    int fd = -1;
-    uint64_t size = 0;
-    ~File() {
-        if (fd >= 0) ::close(fd);
-    }
-    bool read(uint64_t off, uint8_t* dst, size_t n) const {
-        while (n) {
-            const ssize_t k = pread(fd, dst, n, static_cast<off_t>(off));
-            if (k <= 0) return false;
-            dst += k;
-            off += static_cast<uint64_t>(k);
-            n -= static_cast<size_t>(k);
-        }
-        return true;
-    }
+struct BgzfFile : slimm::PlanFile {   // (where blocks start)
     uint32_t header_at(uint64_t off) const {   // the block size of a header at off, 0 when there is none
         uint8_t h[18];
         if (off + 18 > size || !read(off, h, 18)) return 0;
@@ -90,11 +72,8 @@ uint64_t slimm_record_cap(void) { return slimm::record_cap(); }
 
 int slimm_host_bgzf_ranges(const char* path, uint64_t skip, uint32_t n, uint64_t* offsets_out) {
     if (!path || !n || !offsets_out) return SLIMM_E_INVALID;
-    File f;
-    f.fd = open(path, O_RDONLY);
-    struct stat sb;
-    if (f.fd < 0 || fstat(f.fd, &sb) != 0 || !S_ISREG(sb.st_mode)) return SLIMM_E_INVALID;
-    f.size = static_cast<uint64_t>(sb.st_size);
+    BgzfFile f;
+    if (!f.open_regular(path)) return SLIMM_E_INVALID;
     // no cut in front of the first block whose inflated bytes start at or behind `skip`: member 0 holds the whole header
     uint64_t floor = 0, before = 0;
     while (skip && before < skip && floor < f.size) {
@@ -104,24 +83,17 @@ int slimm_host_bgzf_ranges(const char* path, uint64_t skip, uint32_t n, uint64_t
         before += rd32(t);
         floor += total;
     }
-    offsets_out[0] = 0;
-    for (uint32_t i = 1; i < n; ++i) {
-        const uint64_t t = floor + static_cast<uint64_t>(static_cast<unsigned __int128>(f.size - floor) * i / n);
-        offsets_out[i] = std::max(f.cut_at(t), offsets_out[i - 1]);
-    }
-    offsets_out[n] = f.size;
+    slimm::even_ranges(floor, f.size, n, offsets_out, [&](uint64_t t) { return f.cut_at(t); });
     return SLIMM_OK;
 }
 
 // plain text is cut anywhere: the device finds the line starts (windows.hip: guess_first_record)
 int slimm_host_text_ranges(const char* path, uint64_t skip, uint32_t n, uint64_t* offsets_out) {
     if (!path || !n || !offsets_out) return SLIMM_E_INVALID;
-    struct stat sb;
-    if (stat(path, &sb) != 0 || !S_ISREG(sb.st_mode)) return SLIMM_E_INVALID;
-    const uint64_t size = static_cast<uint64_t>(sb.st_size);
-    if (skip > size) return SLIMM_E_INVALID;
-    for (uint32_t i = 0; i <= n; ++i)
-        offsets_out[i] = skip + static_cast<uint64_t>(static_cast<unsigned __int128>(size - skip) * i / n);
+    uint64_t size = 0;
+    if (!slimm::PlanFile::regular_size(path, &size) || skip > size) return SLIMM_E_INVALID;   // (the file is not opened)
+    slimm::even_ranges(skip, size, n, offsets_out, [](uint64_t t) { return t; });
+    offsets_out[0] = skip;   // (member 0 reads from the first alignment line on)
     return SLIMM_OK;
 }
 
@@ -132,11 +104,8 @@ uint64_t slimm_bzip2_split_slack(void) { return slimm::bz2::kSplitSlack; }
 int slimm_host_bzip2_ranges(const char* path, uint64_t skip, uint32_t n, uint64_t* offsets_out) {
     namespace bz2 = slimm::bz2;
     if (!path || !n || !offsets_out) return SLIMM_E_INVALID;
-    File f;
-    f.fd = open(path, O_RDONLY);
-    struct stat sb;
-    if (f.fd < 0 || fstat(f.fd, &sb) != 0 || !S_ISREG(sb.st_mode)) return SLIMM_E_INVALID;
-    f.size = static_cast<uint64_t>(sb.st_size);
+    slimm::PlanFile f;
+    if (!f.open_regular(path)) return SLIMM_E_INVALID;
     std::vector<uint8_t> in;
     auto more = [&]() {   // the file's next bytes behind `in` (false: none left, or a read error)
         const size_t have = in.size(), add = static_cast<size_t>(std::min<uint64_t>(f.size - have, std::max<uint64_t>(4u << 20, have)));
@@ -190,13 +159,9 @@ int slimm_host_bzip2_ranges(const char* path, uint64_t skip, uint32_t n, uint64_
         bit = info.end_bit;
     }
     const uint64_t floor = std::min<uint64_t>(f.size, (bit + 7u) >> 3);
-    offsets_out[0] = 0;
-    for (uint32_t i = 1; i < n; ++i)
-        offsets_out[i] = floor + static_cast<uint64_t>(static_cast<unsigned __int128>(f.size - floor) * i / n);
-    offsets_out[n] = f.size;
+    slimm::even_ranges(floor, f.size, n, offsets_out, [](uint64_t t) { return t; });
     return SLIMM_OK;
 }
-
 
 // zstd is cut where a frame -- or a skippable frame -- starts, and nowhere else: frames are independent of each other (the
 // window, the repeat offsets and the entropy tables start afresh at a frame header), and a frame cannot be entered in its
@@ -210,19 +175,15 @@ constexpr uint64_t kZstdCutSearch = 64ull << 20;
 int slimm_host_zstd_ranges(const char* path, uint64_t skip, uint32_t n, uint64_t* offsets_out) {
     namespace zs = slimm::zs;
     if (!path || !n || !offsets_out || skip >= (1ull << 32)) return SLIMM_E_INVALID;
-    File f;
-    struct stat sb;
-    if (stat(path, &sb) != 0 || !S_ISREG(sb.st_mode)) return SLIMM_E_INVALID;   // (asked before it is opened: opening a FIFO waits for its writer)
-    f.fd = open(path, O_RDONLY);
-    if (f.fd < 0 || fstat(f.fd, &sb) != 0 || !S_ISREG(sb.st_mode)) return SLIMM_E_INVALID;
-    f.size = static_cast<uint64_t>(sb.st_size);
+    slimm::PlanFile f;
+    if (!f.open_regular(path)) return SLIMM_E_INVALID;
     auto read = [&](uint64_t off, uint8_t* dst, size_t k) { return off <= f.size && k <= f.size - off && f.read(off, dst, k); };
     // no cut in front of the end of the frame that holds decoded byte skip - 1: member 0 holds the whole header
     uint64_t first = 0;
     if (!slimm::zstd_header_end(read, f.size, skip, &first)) return SLIMM_E_INVALID;
     long v = 0;
     const uint64_t search = slimm::forced("zstd_cut_search", &v) && v > 0 ? static_cast<uint64_t>(v) : kZstdCutSearch;
-    constexpr uint64_t kNone = ~0ull;
+    constexpr uint64_t kNone = slimm::kNoCut;
     std::vector<uint8_t> buf(1u << 20);
     // the first start at or behind t that is a cut, looked for in [t, t + search)
     auto cut_at = [&](uint64_t t) -> uint64_t {
@@ -243,12 +204,7 @@ int slimm_host_zstd_ranges(const char* path, uint64_t skip, uint32_t n, uint64_t
         }
         return kNone;
     };
-    offsets_out[0] = 0;
-    offsets_out[n] = f.size;
-    for (uint32_t i = 1; i < n; ++i) offsets_out[i] = cut_at(first + static_cast<uint64_t>(static_cast<unsigned __int128>(f.size - first) * i / n));
-    for (uint32_t i = n; i-- > 1;)
-        if (offsets_out[i] == kNone) offsets_out[i] = offsets_out[i + 1];
-    for (uint32_t i = 1; i < n; ++i) offsets_out[i] = std::max(offsets_out[i], offsets_out[i - 1]);
+    slimm::even_ranges(first, f.size, n, offsets_out, cut_at);
     // (SLIMM_FORCE zstd_split_wrong_cut: the second cut -- the first of two members -- lands one byte late, where no frame
     // starts: the members, or the stitch, must refuse it)
     if (n > 1 && slimm::forced("zstd_split_wrong_cut")) {
