@@ -259,7 +259,10 @@ int slimm_push_bgzf_blocks(slimm_ctx* ctx, const uint8_t* blocks, uint64_t n_byt
  * sequences: the compressed bytes of a round, 120 B per block, the Huffman-coded literals' bytes, 12 B per sequence, and per
  * byte of a round's text (at most 512 MB by the blocks' bounds) 1 B + 4 B for the position it copies from, plus twice the
  * frame's window (at most 128 MiB) of history; a frame that states a checksum also takes a page-locked host copy of the
- * round's text, which is host memory (slimm_window_memory does not count it) and is released by slimm_reset. */
+ * round's text, which is host memory (slimm_window_memory does not count it) and is released by slimm_reset.
+ * xz SAM (slimm_push_xz_sam_bytes) sizes everything from the chunk headers, which state every size: the compressed bytes of
+ * a round, 1 B per byte of its text (at most 512 MB, or one block alone of up to 1 GiB; the text is the blocks' dictionary
+ * as well: no 16-bit symbols, no history), 104 B per block and 16 B per 2 KiB of text.  slimm_window_memory counts all of it. */
 int slimm_set_input_size_hint(slimm_ctx* ctx, uint64_t compressed_bytes);
 int slimm_window_memory(slimm_ctx* ctx, uint64_t* device_bytes);
 /* hipMemGetInfo of the context's device: bytes in use (by every process and context on it) and the device's total. */
@@ -344,6 +347,36 @@ int slimm_push_zstd_sam_bytes(slimm_ctx* ctx, const uint8_t* bytes, uint64_t n_b
  * of an earlier round, [15] rounds, [16] bytes of text, [17] compressed bytes, [18] content checksums checked, [19] the most
  * pointer-doubling passes a round took (at most ceil(log2(its text + history)) + 1). */
 int slimm_get_zstd_stats(slimm_ctx* ctx, uint64_t out[20]);
+/* XZ-COMPRESSED SAM TEXT (`xz x.sam`; xz -T, --block-size, pixz, pxz: many blocks; streams back to back with stream padding)
+ * decoded on the device (slimm_amd/csrc/xz_decode.hip; the format: xz_stream.h).  The contract is that of
+ * slimm_push_zstd_sam_bytes: `bytes` = the file's next n_bytes, from its first byte on and in order across calls, cut
+ * anywhere (inside a stream header, a block header, a chunk header, a chunk, the check, the index, the footer); of the decoded
+ * text the first `skip` bytes are the header (0 in every later call); slimm_set_reference_names first; the caller's buffer
+ * is free when the call returns; what cannot be decoded yet -- a block whose bytes have not all come -- waits for the next
+ * push; the form does not mix with the others within a file.  Behind slimm_set_input_mid_file it is refused ("an xz stream
+ * is not cut by byte range").  Pushes are gathered on the host and decoded in rounds (32 MiB of compressed bytes; the whole
+ * blocks at hand, at most 512 MB of text or one block alone): the host reads stream headers, block headers, indexes and
+ * footers and walks every block's LZMA2 chunk headers, which state all sizes; the device decodes the blocks, ONE LANE PER
+ * BLOCK, each into its place in the round's text, computes every block's CRC32 or CRC64 from pieces, and the host compares
+ * them with the check fields and every index with the blocks in front of it.  A file of few blocks therefore keeps few
+ * lanes busy: the library decodes whatever it is pushed, the `slimm` command reads such a file on the host.  Limits: LZMA2 is
+ * the one filter (BCJ and delta chains are refused, the filter named); a block of more than 1 GiB of text is refused
+ * ("decode this file on the host"); SHA-256 checks are NOT verified (the blocks are counted: out[10] below); check kinds
+ * other than none, CRC32, CRC64 and SHA-256 are refused.  Errors: SLIMM_E_INVALID "xz-compressed input is not supported
+ * unless it decodes: <where>: <cause>" in the words of the host reader -- truncation, a header, index or footer CRC32
+ * mismatch, reserved flags, a bad block header or dictionary size, a bad control byte, a first chunk that does not reset the
+ * dictionary, an LZMA chunk without properties or (behind an uncompressed chunk) without a state reset, lc + lp > 4, a
+ * distance beyond the block's start or dictionary, a match that runs over its chunk's end, a chunk that does not end where
+ * its compressed size says, a range coder that does not end at zero, sizes that disagree with the block header, bad
+ * padding, "check mismatch", "index does not match the blocks", bytes behind the last stream that are neither padding nor
+ * a stream. */
+int slimm_push_xz_sam_bytes(slimm_ctx* ctx, const uint8_t* bytes, uint64_t n_bytes, uint32_t skip, int last, uint64_t* n_records);
+/* The counters of the xz file read last (they outlive slimm_reset, and are zeroed by the next xz file's first push):
+ * out[0] streams, [1] blocks, [2] LZMA chunks, [3] uncompressed chunks, [4] LZMA chunks that reset the state, [5] ... that set
+ * a properties byte, [6] ... other than the default 0x5D (lc 3, lp 0, pb 2), blocks by check kind: [7] none, [8] CRC32,
+ * [9] CRC64, [10] SHA-256 (not verified), [11] match bytes, [12] the longest distance, [13] rounds, [14] bytes of text,
+ * [15] compressed bytes, [16] index records checked against their blocks. */
+int slimm_get_xz_stats(slimm_ctx* ctx, uint64_t out[17]);
 /* Page-locks a buffer of the caller (hipHostRegister) until the context is destroyed: copies out of it then run at the
  * speed of the bus instead of the runtime's own staging. */
 int slimm_pin_host_buffer(slimm_ctx* ctx, const void* buffer, uint64_t n_bytes);

@@ -8,15 +8,16 @@ W="${1:-/tmp/slimm_sanitize}"
 mkdir -p "$W"
 FLAGS="-std=c++17 -g -O1 -fsanitize=address,undefined -fno-omit-frame-pointer"
 g++ $FLAGS "$ROOT/tests/native/san_readers.cpp" "$ROOT/slimm_amd/csrc/host/alignment_file.cpp" "$ROOT/slimm_amd/csrc/host/bzip2.cpp" \
-    "$ROOT/slimm_amd/csrc/host/zstd.cpp" "$ROOT/slimm_amd/csrc/host/sldb.cpp" -lz -lpthread -ldl -o "$W/san_readers"
+    "$ROOT/slimm_amd/csrc/host/zstd.cpp" "$ROOT/slimm_amd/csrc/host/xz.cpp" "$ROOT/slimm_amd/csrc/host/sldb.cpp" -lz -lpthread -ldl -o "$W/san_readers"
 g++ $FLAGS "$ROOT/tests/native/san_zstd.cpp" "$ROOT/slimm_amd/csrc/host/zstd.cpp" -o "$W/san_zstd"
+g++ $FLAGS "$ROOT/tests/native/san_xz.cpp" "$ROOT/slimm_amd/csrc/host/xz.cpp" -o "$W/san_xz"
 g++ $FLAGS "$ROOT/tests/native/host_profile_bench.cpp" "$ROOT/slimm_amd/csrc/host_profile.cpp" -o "$W/san_profile"
 g++ $FLAGS "$ROOT/slimm_amd/csrc/host/slimm_build_main.cpp" "$ROOT/slimm_amd/csrc/host/sldb.cpp" -lz -o "$W/san_build"
 # ThreadSanitizer over the parallel BGZF inflate / record decode
 g++ -std=c++17 -g -O1 -fsanitize=thread "$ROOT/tests/native/san_readers.cpp" "$ROOT/slimm_amd/csrc/host/alignment_file.cpp" \
-    "$ROOT/slimm_amd/csrc/host/bzip2.cpp" "$ROOT/slimm_amd/csrc/host/zstd.cpp" "$ROOT/slimm_amd/csrc/host/sldb.cpp" -lz -lpthread -ldl -o "$W/tsan_readers"
+    "$ROOT/slimm_amd/csrc/host/bzip2.cpp" "$ROOT/slimm_amd/csrc/host/zstd.cpp" "$ROOT/slimm_amd/csrc/host/xz.cpp" "$ROOT/slimm_amd/csrc/host/sldb.cpp" -lz -lpthread -ldl -o "$W/tsan_readers"
 g++ -std=c++17 -g -O1 -fsanitize=thread -I"$ROOT/include" "$ROOT/slimm_amd/csrc/host/slimm_main.cpp" "$ROOT/slimm_amd/csrc/host/alignment_file.cpp" \
-    "$ROOT/slimm_amd/csrc/host/bzip2.cpp" "$ROOT/slimm_amd/csrc/host/zstd.cpp" "$ROOT/slimm_amd/csrc/host/sldb.cpp" -lz -lpthread -ldl -o "$W/tsan_slimm"
+    "$ROOT/slimm_amd/csrc/host/bzip2.cpp" "$ROOT/slimm_amd/csrc/host/zstd.cpp" "$ROOT/slimm_amd/csrc/host/xz.cpp" "$ROOT/slimm_amd/csrc/host/sldb.cpp" -lz -lpthread -ldl -o "$W/tsan_slimm"
 # the host emulator for a command whose threads drive several contexts at once (tests/native/emu_one_launch.cpp)
 if [ -e "$ROOT/tests/native/libslimm_emu.so" ]; then
     g++ -std=c++17 -g -O1 -shared -fPIC -I"$ROOT/tests/native/hip_emu" "$ROOT/tests/native/emu_one_launch.cpp" -L"$ROOT/tests/native" \
@@ -83,6 +84,24 @@ r = subprocess.run([f"{d}/san_zstd"] + zfiles, capture_output=True, text=True)
 print(f"san_zstd: {len(zfiles)} files,", sum(1 for l in r.stdout.splitlines() if "\tok\t" in l), "decoded")
 if r.returncode or r.stderr.strip():
     bad += 1; print("SANITIZER OUTPUT (san_zstd):\n" + r.stderr[-4000:])
+# the host xz decoder (and the LZMA decoder the device runs): the committed inputs and written containers decoded, then
+# damaged copies of three of them -- bits flipped, cut short, stretches copied elsewhere
+from tests import sam_xz as X
+short = X.case_text(d, True, 1_000)
+xblobs = [X.golden(n) for n in sorted(os.listdir(X.GOLDEN)) if n.endswith(".xz")] + list(X.written_copies(short, "grouped").values())
+xfiles = []
+for k, blob in enumerate(xblobs):
+    open(f"{d}/x{k}.xz", "wb").write(blob)
+    xfiles.append(f"{d}/x{k}.xz")
+r = subprocess.run([f"{d}/san_xz"] + xfiles, capture_output=True, text=True)
+print(f"san_xz: {len(xfiles)} files,", sum(1 for l in r.stdout.splitlines() if "\tok\t" in l), "decoded")
+if r.returncode or r.stderr.strip():
+    bad += 1; print("SANITIZER OUTPUT (san_xz):\n" + r.stderr[-4000:])
+for k in (0, len(xblobs) - 3, len(xblobs) - 2):
+    r = subprocess.run([f"{d}/san_xz", "--mutate", "3", "3000", xfiles[k]], capture_output=True, text=True)
+    print(f"san_xz --mutate {os.path.basename(xfiles[k])}:", r.stdout.strip())
+    if r.returncode or r.stderr.strip():
+        bad += 1; print("SANITIZER OUTPUT (san_xz --mutate):\n" + r.stderr[-4000:])
 r = subprocess.run([f"{d}/san_profile"], capture_output=True, text=True)
 print(r.stdout)
 if r.returncode or r.stderr.strip():

@@ -25,6 +25,7 @@
 #include "bzip2_block.h"
 #include "deflate_stream.h"
 #include "zstd_frame.h"
+#include "xz_stream.h"
 #include "kernels.h"
 #include "read_identity.h"
 

@@ -16,6 +16,10 @@
 //   zstd_round=N (zstd SAM decoded every N compressed bytes: frame headers, block headers, blocks and checksums cut across
 //   rounds), zstd_round_text=N (a round's text at most, by the blocks' bounds: copies reach into the history of an earlier
 //   round)                                    tests/test_gpu_zstd_sam.py, tests/test_cli_zstd_sam_device.py
+//   xz_round=N (xz SAM decoded every N compressed bytes: stream, block and chunk headers, chunks, checks, indexes and
+//   footers cut across rounds), xz_round_text=N (a round's text at most: a round takes one block, the next round the
+//   rest), xz_device_blocks=N (the `slimm` command reads an xz file of fewer than N blocks, by its index, on the host: 16
+//   unless told)                              tests/test_gpu_xz_sam.py, tests/test_cli_xz_sam_device.py
 //   bzip2_split_wrong_first (a mid-file member of a split bzip2 file passes over its first block or marker:
 //   slimm_group_stitch_ranges must refuse the cut)                                   tests/test_gpu_split_bzip2_sam.py
 //   zstd_split_floor=N (the least bytes per member at which the command cuts a zstd file for --split-input: 32 MiB unless

@@ -2,6 +2,7 @@
 
 #include "bzip2.hpp"
 #include "zstd.hpp"
+#include "xz.hpp"
 
 #include <dlfcn.h>
 #include <zlib.h>
@@ -195,6 +196,7 @@ void AlignmentFile::close() {
     gz_.reset();
     bz_.reset();
     zs_.reset();
+    xz_.reset();
     workers_.reset();
     inflaters_.reset();
 }
@@ -265,8 +267,20 @@ bool AlignmentFile::open(const std::string& path) {
                        (memcmp(&head[4], "\x31\x41\x59\x26\x53\x59", 6) == 0 || memcmp(&head[4], "\x17\x72\x45\x38\x50\x90", 6) == 0);
     // zstd: a frame's magic, or a skippable frame's in front of it
     const bool zstd = starts("\x28\xb5\x2f\xfd", 4) || (head.size() >= 4 && (head[0] & 0xf0) == 0x50 && memcmp(&head[1], "\x2a\x4d\x18", 3) == 0);
+    const bool xz = starts("\xfd" "7zXZ\0", 6);
     bool ok;
-    if (zstd) {
+    if (xz) {
+        comp_ = Compression::Xz;
+        FILE* fp = fp_;
+        xz_.reset(new XzReader([fp](uint8_t* d, size_t n) { return fread(d, 1, n, fp); }));
+        ok = refill_text() || !text_bad_;
+        if (ok && buf_.size() >= 4 && memcmp(buf_.data(), "BAM\1", 4) == 0) {
+            err_ = "an xz stream that holds BAM: BAM is read from BGZF blocks only: " + path;
+            ok = false;
+        }
+        if (ok) ok = read_sam_header();
+        if (!ok && text_bad_) err_ += ": " + path;
+    } else if (zstd) {
         comp_ = Compression::Zstd;
         FILE* fp = fp_;
         zs_.reset(new ZstdReader([fp](uint8_t* d, size_t n) { return fread(d, 1, n, fp); }));
@@ -288,8 +302,8 @@ bool AlignmentFile::open(const std::string& path) {
         }
         if (ok) ok = read_sam_header();
         if (!ok && text_bad_) err_ += ": " + path;
-    } else if (starts("BZh", 3) || starts("\xfd" "7zXZ\0", 6)) {
-        err_ = std::string(starts("BZh", 3) ? "bzip2" : "xz") + "-compressed input is not supported (SAM / BAM, BGZF or gzip): " + path;
+    } else if (starts("BZh", 3)) {
+        err_ = "bzip2-compressed input is not supported (SAM / BAM, BGZF or gzip): " + path;
         ok = false;
     } else if (bgzf) {
         comp_ = Compression::Bgzf;
@@ -592,7 +606,7 @@ bool AlignmentFile::refill_text() {
     }
     buf_.resize(1 << 20);
     const long got = comp_ == Compression::Gzip    ? gz_read(buf_.data(), buf_.size())
-                     : comp_ == Compression::Bzip2 || comp_ == Compression::Zstd ? bz_read(buf_.data(), buf_.size())
+                     : comp_ == Compression::Bzip2 || comp_ == Compression::Zstd || comp_ == Compression::Xz ? bz_read(buf_.data(), buf_.size())
                                                    : static_cast<long>(fread(buf_.data(), 1, buf_.size(), fp_));
     buf_.resize(got > 0 ? static_cast<size_t>(got) : 0u);
     pos_ = 0;
@@ -647,9 +661,10 @@ long AlignmentFile::gz_read(uint8_t* dst, size_t cap) {
 // the end, -1 + err_ -- which keeps the words of the reader that did not decode bzip2 at all, and says why this did not.
 long AlignmentFile::bz_read(uint8_t* dst, size_t cap) {
     if (text_bad_) return -1;
-    const long n = zs_ ? zs_->read(dst, cap) : bz_->read(dst, cap);
+    const long n = xz_ ? xz_->read(dst, cap) : zs_ ? zs_->read(dst, cap) : bz_->read(dst, cap);
     if (n < 0) {
-        err_ = std::string(zs_ ? "zstd" : "bzip2") + "-compressed input is not supported unless it decodes: " + (zs_ ? zs_->error() : bz_->error());
+        err_ = std::string(xz_ ? "xz" : zs_ ? "zstd" : "bzip2") + "-compressed input is not supported unless it decodes: " +
+               (xz_ ? xz_->error() : zs_ ? zs_->error() : bz_->error());
         text_bad_ = true;
     } else if (n == 0) {
         bz_end_ = true;
@@ -1094,8 +1109,8 @@ long AlignmentFile::read_blocks(uint8_t* dst, size_t cap, size_t max_inflated, s
 }
 
 long AlignmentFile::read_compressed(uint8_t* dst, size_t cap) {
-    if ((comp_ != Compression::Bzip2 && comp_ != Compression::Gzip && comp_ != Compression::Zstd) || bam_ || !fp_ || !dst) {
-        err_ = "read_compressed: a bzip2, gzip or zstd SAM file";
+    if ((comp_ != Compression::Bzip2 && comp_ != Compression::Gzip && comp_ != Compression::Zstd && comp_ != Compression::Xz) || bam_ || !fp_ || !dst) {
+        err_ = "read_compressed: a bzip2, gzip, zstd or xz SAM file";
         return -1;
     }
     const int fd = fileno(fp_);
@@ -1114,7 +1129,8 @@ long AlignmentFile::read_compressed(uint8_t* dst, size_t cap) {
     while (out < want) {
         const ssize_t got = pread(fd, dst + out, want - out, static_cast<off_t>(bz_raw_pos_ + out));
         if (got <= 0) {
-            err_ = comp_ == Compression::Zstd   ? "truncated zstd stream (the file shrank while it was read)"
+            err_ = comp_ == Compression::Xz     ? "truncated xz stream (the file shrank while it was read)"
+                   : comp_ == Compression::Zstd ? "truncated zstd stream (the file shrank while it was read)"
                    : comp_ == Compression::Gzip ? "truncated gzip stream (the file shrank while it was read)"
                                               : "truncated bzip2 stream (the file shrank while it was read)";
             return -1;
@@ -1131,7 +1147,7 @@ long AlignmentFile::read_text(uint8_t* dst, size_t cap) {
         err_ = "read_text: a SAM file (plain or gzip) and a buffer of at least 64 KiB";
         return -1;
     }
-    if (comp_ == Compression::Gzip || comp_ == Compression::Bzip2 || comp_ == Compression::Zstd) {   // (on the caller's thread: the command's reader thread, beside the device's work)
+    if (comp_ == Compression::Gzip || comp_ == Compression::Bzip2 || comp_ == Compression::Zstd || comp_ == Compression::Xz) {   // (on the caller's thread: the command's reader thread, beside the device's work)
         StageClock clk(ms_inflate_);
         sam_text_started_ = true;
         size_t out = take_lead(dst, cap);

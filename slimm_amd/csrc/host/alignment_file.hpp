@@ -46,11 +46,12 @@ struct RecordBatch {
 enum class SortOrder { Unknown, Unsorted, QueryName, Coordinate, QueryGrouped };
 // How the file's bytes are stored: as they are, in BGZF blocks (BAM, or SAM text from bgzip), as one plain gzip stream of
 // one or more members (SAM text from gzip), as bzip2 streams back to back (SAM text from bzip2 / pbzip2 / lbzip2), or as zstd
-// frames back to back (SAM text from zstd / pzstd)
-enum class Compression { None, Bgzf, Gzip, Bzip2, Zstd };
+// frames back to back (SAM text from zstd / pzstd), or as xz streams of LZMA2 blocks (SAM text from xz / pixz / pxz)
+enum class Compression { None, Bgzf, Gzip, Bzip2, Zstd, Xz };
 
 class Bzip2Reader;   // (bzip2.hpp)
 class ZstdReader;    // (zstd.hpp)
+class XzReader;      // (xz.hpp)
 
 // 62-bit identity of a read name.  The reader makes it exact where grouped input needs it to be: a record whose name
 // differs from its predecessor's never gets the predecessor's key (separate_adjacent_names).  Names colliding far
@@ -126,8 +127,8 @@ public:
     // SAM goes through read_raw / read_blocks.)
     long read_text(uint8_t* dst, size_t cap);
     bool can_read_text() const { return !bam_ && comp_ != Compression::Bgzf && fp_ != nullptr; }
-    // bzip2, gzip and zstd SAM: the file's bytes as they lie in it, from its first byte on, window by window (for
-    // slimm_push_bzip2_sam_bytes / _gzip_sam_bytes / _zstd_sam_bytes: the device decodes them; the header's text_header_bytes()
+    // bzip2, gzip, zstd and xz SAM: the file's bytes as they lie in it, from its first byte on, window by window (for
+    // slimm_push_bzip2_sam_bytes / _gzip_sam_bytes / _zstd_sam_bytes / _xz_sam_bytes: the device decodes them; the header's text_header_bytes()
     // decoded bytes are skipped there).  Read by pread, beside whatever read_text read.  Returns the bytes written, 0 at the end, -1 + error().
     long read_compressed(uint8_t* dst, size_t cap);
     bool compressed_exhausted() const { return bz_raw_pos_ >= bz_raw_size_ && bz_raw_started_; }
@@ -135,7 +136,7 @@ public:
     // after a read_raw that returned bytes: nothing will follow them (false may also mean "not known yet")
     bool raw_exhausted() const {
         if (comp_ == Compression::Gzip) return gz_end_ && lead_off_ >= lead_.size() && pos_ >= buf_.size();
-        if (comp_ == Compression::Bzip2 || comp_ == Compression::Zstd) return bz_end_ && lead_off_ >= lead_.size() && pos_ >= buf_.size();
+        if (comp_ == Compression::Bzip2 || comp_ == Compression::Zstd || comp_ == Compression::Xz) return bz_end_ && lead_off_ >= lead_.size() && pos_ >= buf_.size();
         return raw_stage_ == 2 ? eof_ : (raw_stage_ == 1 && eof_ && raw_off_ >= spare_.size());
     }
 
@@ -165,7 +166,7 @@ private:
     bool next_sam_line(std::string& line);
     bool refill_text();       // the next stretch of SAM text into buf_ (false: its end, or an error in err_)
     long gz_read(uint8_t* dst, size_t cap);   // plain gzip: the next inflated bytes of the stream (0 at its end, -1 + err_)
-    long bz_read(uint8_t* dst, size_t cap);   // bzip2, zstd: the next decoded bytes of the streams (0 at their end, -1 + err_)
+    long bz_read(uint8_t* dst, size_t cap);   // bzip2, zstd, xz: the next decoded bytes of the streams (0 at their end, -1 + err_)
     size_t take_lead(uint8_t* dst, size_t cap);   // compressed SAM: the first alignment line and the rest of buf_, once
     void parse_hd_line(const std::string& line);
 
@@ -179,6 +180,7 @@ private:
     // bzip2: the host decoder, the end of its streams; read_compressed's file position and the file's size
     std::unique_ptr<Bzip2Reader> bz_;
     std::unique_ptr<ZstdReader> zs_;   // zstd: the host decoder (the rest of its state: bzip2's)
+    std::unique_ptr<XzReader> xz_;     // xz: the host decoder (likewise)
     bool bz_end_ = false, bz_raw_started_ = false;
     size_t bz_raw_pos_ = 0, bz_raw_size_ = 0;
     bool text_bad_ = false;   // compressed SAM: the text ran into a format error (err_); the reader's answer from then on

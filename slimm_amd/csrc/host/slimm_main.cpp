@@ -127,6 +127,8 @@ SLIMM_FORWARD(int, slimm_push_gzip_sam_bytes, (slimm_ctx* a, const uint8_t* b, u
 SLIMM_FORWARD(int, slimm_get_gzip_stats, (slimm_ctx* a, uint64_t* b), (a, b))
 SLIMM_FORWARD(int, slimm_push_zstd_sam_bytes, (slimm_ctx* a, const uint8_t* b, uint64_t c, uint32_t s, int d, uint64_t* e), (a, b, c, s, d, e))
 SLIMM_FORWARD(int, slimm_get_zstd_stats, (slimm_ctx* a, uint64_t* b), (a, b))
+SLIMM_FORWARD(int, slimm_push_xz_sam_bytes, (slimm_ctx* a, const uint8_t* b, uint64_t c, uint32_t s, int d, uint64_t* e), (a, b, c, s, d, e))
+SLIMM_FORWARD(int, slimm_get_xz_stats, (slimm_ctx* a, uint64_t* b), (a, b))
 SLIMM_FORWARD(int, slimm_pin_host_buffer, (slimm_ctx* a, const void* b, uint64_t c), (a, b, c))
 SLIMM_FORWARD(int, slimm_host_bgzf_ranges, (const char* a, uint64_t b, uint32_t c, uint64_t* d), (a, b, c, d))
 SLIMM_FORWARD(int, slimm_host_text_ranges, (const char* a, uint64_t b, uint32_t c, uint64_t* d), (a, b, c, d))
@@ -170,6 +172,8 @@ SLIMM_FORWARD(int, slimm_group_reset, (slimm_group* a), (a))
 #include "accession.hpp"
 #include "alignment_file.hpp"
 #include "zstd.hpp"
+#include "xz.hpp"
+#include "../force.h"
 #include "sldb.hpp"
 
 namespace {
@@ -428,7 +432,8 @@ int dump_raw(const Options& o) {
     const size_t cap = static_cast<size_t>(std::max(1u, o.window_mb)) << 20;
     std::vector<uint8_t> buf(cap);
     long n;
-    const bool text = f.compression() == Compression::Gzip || f.compression() == Compression::Bzip2 || f.compression() == Compression::Zstd;
+    const bool text = f.compression() == Compression::Gzip || f.compression() == Compression::Bzip2 || f.compression() == Compression::Zstd ||
+                      f.compression() == Compression::Xz;
     while ((n = text ? f.read_text(buf.data(), cap) : f.read_raw(buf.data(), cap)) > 0) {
         std::cerr << "window\t" << n << "\t" << (f.raw_exhausted() ? "last" : "more") << "\n";
         if (fwrite(buf.data(), 1, static_cast<size_t>(n), stdout) != static_cast<size_t>(n)) return 1;
@@ -606,6 +611,7 @@ struct Target {
 // and read_split -- need to know of it.  A new form is a row.
 struct InputForm {
     const char* name;   // in the [trace] lines (a streamed codec's: "a <name> stream", "<name> SAM on the device")
+    const char* article = "a";   // ... and its article there
     bool sam;           // SAM text: the decoder wants the header's reference names first (slimm_set_reference_names)
     // Which AlignmentFile path supplies the pump's bytes.  Bgzf: read_blocks -- whole blocks, the device inflates them -- every
     // device_period-th window, else read_raw; `last` from raw_exhausted().  Text: read_text.  Streamed: read_compressed, the
@@ -627,6 +633,8 @@ struct InputForm {
     bool (*may_cut)(const AlignmentFile& f, const std::string& path, uint32_t G, bool with_floor) = nullptr;
     // SLIMM_TRACE=cli, at the file's end: what the device decoded, the counters of the n contexts summed (none: no line)
     void (*end_line)(const char* head, slimm_ctx* const* ctx, uint32_t n) = nullptr;
+    // a regular file of this form that the host reader takes all the same, and says so under SLIMM_TRACE=cli (none: never)
+    bool (*by_host)(const std::string& path, const char* head) = nullptr;
 };
 int push_sam_text(slimm_ctx* c, const uint8_t* p, uint64_t n, uint32_t, int last, uint64_t* got) { return slimm_push_sam_bytes(c, p, n, last, got); }
 int push_bam_records(slimm_ctx* c, const uint8_t* p, uint64_t n, uint32_t, int last, uint64_t* got) { return slimm_push_bam_bytes(c, p, n, last, got); }
@@ -658,6 +666,35 @@ void zstd_end_line(const char* head, slimm_ctx* const* ctx, uint32_t n) {
     if (told) fprintf(stderr, "%szstd SAM on the device: %llu frames, %llu blocks, %llu bytes of text\n", head, (unsigned long long)frames,
             (unsigned long long)blocks, (unsigned long long)text);
 }
+void xz_end_line(const char* head, slimm_ctx* const* ctx, uint32_t n) {
+    uint64_t streams = 0, blocks = 0, text = 0, told = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        uint64_t st[20] = {};
+        if (slimm_get_xz_stats(ctx[i], st) == SLIMM_OK) ++told, streams += st[0], blocks += st[1], text += st[14];
+    }
+    if (told) fprintf(stderr, "%sxz SAM on the device: %llu streams, %llu blocks, %llu bytes of text\n", head, (unsigned long long)streams,
+            (unsigned long long)blocks, (unsigned long long)text);
+}
+// xz SAM is decoded a lane per block, so a file of few blocks would keep few lanes busy for a long time: the command reads
+// the file's index or indexes from its end (xz_read_index) and takes the device path only for kXzDeviceBlocks blocks or more
+// -- a stated default, not a measurement (SLIMM_FORCE xz_device_blocks=N).  A file whose index does not parse goes by the
+// host reader as well, which says what is wrong with it
+constexpr uint64_t kXzDeviceBlocks = 16;
+bool xz_by_host(const std::string& path, const char* head) {
+    long least = 0;
+    if (!forced("xz_device_blocks", &least) || least < 0) least = static_cast<long>(kXzDeviceBlocks);
+    const int fd = open(path.c_str(), O_RDONLY);
+    struct stat sb;
+    std::vector<XzIndexBlock> blocks;
+    uint32_t streams = 0;
+    const bool ok = fd >= 0 && fstat(fd, &sb) == 0 &&
+                    xz_read_index([&](uint64_t at, uint8_t* dst, size_t n) { return pread_all(fd, dst, at, n); }, static_cast<uint64_t>(sb.st_size), &blocks, &streams);
+    if (fd >= 0) close(fd);
+    if (ok && blocks.size() >= static_cast<uint64_t>(least)) return false;
+    if (g_trace && ok) fprintf(stderr, "%sxz SAM of %llu block(s): read on the host\n", head, (unsigned long long)blocks.size());
+    if (g_trace && !ok) fprintf(stderr, "%sxz SAM whose index does not parse: read on the host\n", head);
+    return true;
+}
 // zstd SAM is cut where frames start and nowhere else (slimm_host_zstd_ranges): read_split takes a file whose plan for G
 // members has at least two ranges that are not empty -- a file of one frame has none -- and, with_floor, whose members get
 // slimm_zstd_split_floor() bytes each or more: (the file's size - the first legal cut) / G (the cap's re-read does not ask:
@@ -679,7 +716,7 @@ bool zstd_may_cut(const AlignmentFile& f, const std::string& path, uint32_t G, b
     return ok && first <= size && (size - first) / G >= slimm_zstd_split_floor();
 }
 
-enum { kBam, kBgzfSam, kSam, kBzip2Sam, kGzipSam, kZstdSam };
+enum { kBam, kBgzfSam, kSam, kBzip2Sam, kGzipSam, kZstdSam, kXzSam };
 const InputForm kForms[] = {
     {.name = "BAM", .sam = false, .read = InputForm::Bgzf, .push = push_bam_records, .push_blocks = slimm_push_bgzf_blocks,
      .plan = slimm_host_bgzf_ranges, .planned = "BGZF blocks"},
@@ -692,6 +729,8 @@ const InputForm kForms[] = {
      .wide_header_by_host = true, .end_line = gzip_end_line},
     {.name = "zstd", .sam = true, .read = InputForm::Streamed, .push = slimm_push_zstd_sam_bytes, .plan = slimm_host_zstd_ranges,
      .planned = "zstd frames", .wide_header_by_host = true, .announce_range = true, .may_cut = zstd_may_cut, .end_line = zstd_end_line},
+    {.name = "xz", .article = "an", .sam = true, .read = InputForm::Streamed, .push = slimm_push_xz_sam_bytes, .planned = "xz stream",
+     .wide_header_by_host = true, .end_line = xz_end_line, .by_host = xz_by_host},
 };
 const InputForm& form_of(const AlignmentFile& f) {
     if (f.is_bam()) return kForms[kBam];
@@ -700,10 +739,11 @@ const InputForm& form_of(const AlignmentFile& f) {
         case Compression::Bzip2: return kForms[kBzip2Sam];
         case Compression::Gzip: return kForms[kGzipSam];
         case Compression::Zstd: return kForms[kZstdSam];
+        case Compression::Xz: return kForms[kXzSam];
         default: return kForms[kSam];
     }
 }
-// What RecordPump's raw windows push a file as: its own form -- but where the row says so (gzip, zstd) a header of 2^32 text
+// What RecordPump's raw windows push a file as: its own form -- but where the row says so (gzip, zstd, xz) a header of 2^32 text
 // bytes or more goes through the host reader (the push's `skip` has 32 bits): read_text decodes it, and the text is plain SAM's
 const InputForm& pushed_as(const AlignmentFile& f) {
     const InputForm& form = form_of(f);
@@ -1425,9 +1465,14 @@ std::unique_ptr<Reading> set_up(Session& S, const std::string& path, bool any_or
     // than the floor; or the host decoders were asked for)
     const InputForm& form = form_of(bam);
     if (g_trace && !any_order && !F->split_input && options.split_input && options.devices.size() > 1 && (!form.plan || form.may_cut))
-        fprintf(stderr, "%s--split-input: a %s stream is not cut by byte range; member 0 reads %s\n", S.trace_head(), form.name, path.c_str());
-    if (!F->split_input)
-        F->pump.reset(new RecordPump(bam, F->check_words, true, options, S.log->head));
+        fprintf(stderr, "%s--split-input: %s %s stream is not cut by byte range; member 0 reads %s\n", S.trace_head(), form.article, form.name, path.c_str());
+    if (!F->split_input) {
+        // (a regular file that its form gives to the host reader -- an xz file of few blocks --: the pump's host path)
+        Options pump_options = options;
+        const bool device_asked = !options.host_decode && !options.verify_grouping && !options.packed_records;
+        if (form.by_host && device_asked && has_raw_windows(bam) && form.by_host(path, S.trace_head())) pump_options.host_decode = true;
+        F->pump.reset(new RecordPump(bam, F->check_words, true, pump_options, S.log->head));
+    }
 
     S.err() << "Intializing coverages for all reference genome ... ";
     const uint32_t R = static_cast<uint32_t>(bam.ref_names().size());

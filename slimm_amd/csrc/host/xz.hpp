@@ -1,0 +1,71 @@
+// xz on the host: one serial decoder for the SAM header of an xz-compressed SAM file, for `--host-decode`,
+// `--verify-grouping`, `--packed-records`, pipes and `--dump-records` / `--dump-raw` (the reader thread), for files of few
+// blocks, and for the CPU tests.  The format is ../xz_stream.h, the device decoder's own source; streams back to back, with
+// stream padding, are read one after the other.  LZMA2 is the one filter; SHA-256 checks are not verified.  No liblzma:
+// the command does not depend on it.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <functional>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../xz_stream.h"
+
+namespace slimm {
+
+class XzReader {
+public:
+    // what the file held so far (the tests compare with their own walk; the device decoder counts the same)
+    struct Counts {
+        uint64_t streams = 0, blocks = 0, lzma_chunks = 0, raw_chunks = 0, state_resets = 0, prop_changes = 0, odd_props = 0;
+        uint64_t check_none = 0, check_crc32 = 0, check_crc64 = 0, sha256_unverified = 0;
+        uint64_t match_bytes = 0, max_dist = 0, text = 0, index_records = 0;
+    };
+    // `source(dst, cap)`: the next compressed bytes of the file, in order (0 at its end)
+    explicit XzReader(std::function<size_t(uint8_t*, size_t)> source);
+    // the next decoded bytes, at most `cap`; 0 at the end of the last stream, -1 + error()
+    long read(uint8_t* dst, size_t cap);
+    // "block at byte N: <cause>", "index at byte N: <cause>", ... (without the reader's "xz-compressed input ..." in front)
+    const std::string& error() const { return err_; }
+    const Counts& counts() const { return n_; }
+
+private:
+    enum class Stage { Between, Stream, Chunks };
+    bool next_chunk();   // decode up to the next chunk that holds text (false: the end, or err_)
+    bool need(size_t n); // at least n bytes at pos_ (false: the file has no more)
+    bool fail(const std::string& where, uint32_t status, const std::string& more = "");
+    bool end_block();
+    bool read_index();
+    std::function<size_t(uint8_t*, size_t)> source_;
+    std::vector<uint8_t> in_;   // compressed bytes from file offset in_base_ on; the next to read: pos_
+    uint64_t in_base_ = 0;
+    size_t pos_ = 0;
+    bool in_eof_ = false, done_ = false, bad_ = false;
+    Stage stage_ = Stage::Between;
+    uint32_t check_ = 0;
+    std::vector<std::pair<uint64_t, uint64_t>> records_;   // the stream's blocks so far: unpadded size, uncompressed size
+    // the block being read: its header, where it starts, its bytes and text so far, the chunk rules, the decoder
+    xz::BlockHeader bh_{};
+    uint64_t block_at_ = 0, block_comp_ = 0, block_text_ = 0, since_ = 0, crc_ = 0;
+    xz::Rules rules_;
+    xz::Lzma lz_{};
+    std::vector<uint16_t> probs_;
+    std::vector<uint8_t> text_;   // the block's text: at least its dictionary's worth
+    size_t served_ = 0;           // ... of which [served_, size) have not been handed out
+    Counts n_;
+    std::string err_;
+};
+
+// A block by its stream's index: where its header lies in the file, its unpadded size (header, data and check) and its text
+struct XzIndexBlock {
+    uint64_t at, unpadded, uncompressed;
+    uint32_t stream;
+};
+// A file of `size` bytes seen through read(offset, dst, n) (false: a read error): the blocks of all its streams in file
+// order, read from the file's end -- footer, backward size, index, the stream's header, stream padding, the stream in front.
+// false: it does not parse that way (nothing is decoded: the blocks themselves are not looked at)
+bool xz_read_index(const std::function<bool(uint64_t, uint8_t*, size_t)>& read, uint64_t size, std::vector<XzIndexBlock>* blocks, uint32_t* streams);
+
+}  // namespace slimm

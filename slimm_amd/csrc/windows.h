@@ -101,6 +101,20 @@ struct WindowPipeline {
            kZsRepeated, kZsSequences, kZsFromFront, kZsFromHistory, kZsRounds, kZsText, kZsCompressedBytes, kZsChecksums, kZsPasses, kZsStats };
     uint64_t zs_stats[kZsStats] = {};
 
+    // xz SAM (xz_decode.hip), the decode scratch: the compressed bytes of a round, a descriptor per block, the round's text
+    // (which is each block's dictionary as well), the check register of every piece of text (gz::kPiece bytes)
+    struct Xz {
+        DevBuf<uint8_t> comp, text;
+        DevBuf<xz::Block> blocks;
+        DevBuf<xz::Piece> piece;
+        template <typename F>
+        void each_held(F&& f) { f(comp), f(text), f(blocks), f(piece); }
+    } xzs;
+    // the counters of the xz file read last (slimm_get_xz_stats): they outlive the file's state
+    enum { kXzStreams, kXzBlocks, kXzLzmaChunks, kXzRawChunks, kXzStateResets, kXzPropChanges, kXzOddProps, kXzCheckNone, kXzCheckCrc32, kXzCheckCrc64,
+           kXzSha256Unverified, kXzMatchBytes, kXzMaxDist, kXzRounds, kXzText, kXzCompressedBytes, kXzIndexRecords, kXzStats };
+    uint64_t xz_stats[kXzStats] = {};
+
     // ---- announced before the file's first window (slimm_set_input_size_hint, slimm_set_input_mid_file), cleared when it ends
     struct Announced {
         uint64_t size_hint = 0;   // the file's compressed bytes (0 = not told): what its gathered windows are sized for
@@ -144,10 +158,10 @@ struct WindowPipeline {
         bool found_start = false;   // a range that starts inside the file: its first window holds a record start (false: all head)
         bool has_first = false;     // `first` holds the name of the range's first record (decoded in any window)
         uint64_t head_len = 0;
-        // a streamed codec's SAM (bzip2, gzip, zstd: the file's bytes as they lie in it, decoded here), what every codec
+        // a streamed codec's SAM (bzip2, gzip, zstd, xz: the file's bytes as they lie in it, decoded here), what every codec
         // keeps on the host: the compressed bytes not decoded yet (file offset `base` on; `bit`: the next bit to read --
         // zstd reads at bytes), the decoded bytes still to skip (the header)
-        enum class Codec : uint8_t { None, Bzip2, Gzip, Zstd };
+        enum class Codec : uint8_t { None, Bzip2, Gzip, Zstd, Xz };
         struct Stream {
             Codec codec = Codec::None;
             std::vector<uint8_t> pend;
@@ -247,6 +261,17 @@ struct WindowPipeline {
             uint64_t text = 0;                // the round's text bytes (behind zs_round)
             uint64_t round_hist = 0;
         } zst;
+        // xz SAM, the host's side: where stream.bit is -- between streams, or among a stream's blocks --, the stream's check
+        // kind and its blocks so far (unpadded size, text bytes: what its index must say); the blocks of the round at hand
+        struct Xz {
+            enum Stage { Between, Blocks } stage = Between;
+            uint32_t check = 0;
+            uint64_t any_streams = 0;
+            std::vector<std::pair<uint64_t, uint64_t>> records;
+            std::vector<xz::Block> ready;
+            std::vector<uint64_t> ready_at;   // the blocks' file offsets (errors)
+            uint64_t text = 0;                // the round's text bytes (behind xz_round)
+        } xz;
     } file;
 
     // the buffers that grow with a file's windows: what held_bytes() counts is what end_file gives back
@@ -258,6 +283,7 @@ struct WindowPipeline {
         bz2.each_held(f);
         gz.each_held(f);
         zst.each_held(f);
+        xzs.each_held(f);
     }
     uint64_t held_bytes() {   // device memory of the window pipeline (slimm_window_memory)
         uint64_t n = 0;
@@ -315,6 +341,14 @@ bool zs_next_window(const slimm_ctx* c, uint64_t cap, uint64_t* n);
 int zs_emit(slimm_ctx* c, uint8_t* dst, uint64_t cap, uint64_t* n_out, uint8_t* last_byte);
 int zs_check(slimm_ctx* c);
 void zs_trace_file(const slimm_ctx* c);
+// xz_decode.hip (slimm_push_xz_sam_bytes): xz_round walks what lies at stream.bit -- stream headers, block headers and
+// their chunk chains, indexes, footers, padding -- and leaves the whole blocks at hand, with their exact text offsets, in
+// file.xz.ready.  xz_emit: the blocks decoded, a lane each, their checks folded from pieces and compared, the text written
+// to dst.  An xz stream is not cut by byte range
+int xz_round(slimm_ctx* c, bool last);
+bool xz_next_window(const slimm_ctx* c, uint64_t cap, uint64_t* n);
+int xz_emit(slimm_ctx* c, uint8_t* dst, uint64_t cap, uint64_t* n_out, uint8_t* last_byte);
+void xz_trace_file(const slimm_ctx* c);
 // the decoders' shared steps (windows.hip).  stream.pend to the device, into `comp` with `tail` zeroed bytes behind it.
 // The candidates a find kernel left at d_cand, counted at count[0]: `launch(cap)` runs it with room for cap of them, again
 // with more room when there were more; *got of them are there (and the stream is idle)

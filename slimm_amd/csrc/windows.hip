@@ -1,7 +1,7 @@
 // The window pipeline (include/slimm_hip.h: slimm_push_bam_bytes, _bgzf_blocks, _sam_bytes, _bgzf_sam_blocks, _bzip2_sam_bytes,
-// _gzip_sam_bytes, _zstd_sam_bytes): a file's bytes -- inflated BAM records, whole BGZF blocks of them, SAM text, BGZF blocks of SAM
-// text, SAM text in a streamed codec (bzip2, gzip, zstd) -- cross the bus in windows; the device inflates (bgzf_tokens.hip,
-// bgzf_inflate.hip) or decodes (the codecs: bzip2_decode.hip, gzip_decode.hip, zstd_decode.hip) them, finds the
+// _gzip_sam_bytes, _zstd_sam_bytes, _xz_sam_bytes): a file's bytes -- inflated BAM records, whole BGZF blocks of them, SAM text, BGZF blocks of SAM
+// text, SAM text in a streamed codec (bzip2, gzip, zstd, xz) -- cross the bus in windows; the device inflates (bgzf_tokens.hip,
+// bgzf_inflate.hip) or decodes (the codecs: bzip2_decode.hip, gzip_decode.hip, zstd_decode.hip, xz_decode.hip) them, finds the
 // records (bam_decode.hip, sam_decode.hip) and appends them to the context's record stream.  Its state: windows.h.
 // Replaces seqan::BamFileIn + readRecord of the reference (src/misc.hpp:498-522, src/slimm.hpp:194-208).
 // A push's steps (push_window): check_push, open_file; one of three sources fills window buffers -- push_stream (a streamed
@@ -306,7 +306,7 @@ int add_last_newline(slimm_ctx* c, uint64_t at, hipStream_t st) {   // at: bytes
 }
 
 // ---- a push
-enum { kFormatBam = 0, kFormatBgzf = 1, kFormatSam = 2, kFormatBgzfSam = 3, kFormatBzip2Sam = 4, kFormatGzipSam = 5, kFormatZstdSam = 6 };
+enum { kFormatBam = 0, kFormatBgzf = 1, kFormatSam = 2, kFormatBgzfSam = 3, kFormatBzip2Sam = 4, kFormatGzipSam = 5, kFormatZstdSam = 6, kFormatXzSam = 7 };
 
 // What a streamed codec supplies (windows.h: the hooks' contracts), by File::Codec
 struct StreamCodec {
@@ -329,18 +329,22 @@ struct StreamCodec {
     // its counters (they outlive the file: slimm_get_*_stats), how many, and which of them counts the compressed bytes
     uint64_t* (*stats)(WindowPipeline&);
     size_t n_stats, stat_compressed;
+    const char* article;     // "an" where the name wants it (null: "a")
 };
 const StreamCodec kCodecs[] = {
     {},
     // (ended: the range's chain has stopped, what comes now are bytes of the slack)
     {"bzip2", "bzip2_round", 32ull << 20, true, false, bz2_decode_batch, bz2_next_window, bz2_emit, nullptr, bz2_trace_file, nullptr,
-     [](const File& F) { return F.bz2.chain.ended; }, nullptr, 0, 0},
+     [](const File& F) { return F.bz2.chain.ended; }, nullptr, 0, 0, nullptr},
     {"gzip", "gzip_round", 32ull << 20, false, false, gz_round, gz_next_window, gz_emit, nullptr, gz_trace_file,
      [](const File& F) { return static_cast<int>(F.gz.stage); }, nullptr, [](WindowPipeline& W) { return W.gz_stats; },
-     WindowPipeline::kGzStats, WindowPipeline::kGzCompressed},
+     WindowPipeline::kGzStats, WindowPipeline::kGzCompressed, nullptr},
     {"zstd", "zstd_round", kZstdRoundBytes, true, true, zs_round, zs_next_window, zs_emit, zs_check, zs_trace_file,
      [](const File& F) { return static_cast<int>(F.zst.stage); }, nullptr, [](WindowPipeline& W) { return W.zs_stats; },
-     WindowPipeline::kZsStats, WindowPipeline::kZsCompressedBytes},
+     WindowPipeline::kZsStats, WindowPipeline::kZsCompressedBytes, nullptr},
+    {"xz", "xz_round", 32ull << 20, false, false, xz_round, xz_next_window, xz_emit, nullptr, xz_trace_file,
+     [](const File& F) { return static_cast<int>(F.xz.stage); }, nullptr, [](WindowPipeline& W) { return W.xz_stats; },
+     WindowPipeline::kXzStats, WindowPipeline::kXzCompressedBytes, "an"},
 };
 const StreamCodec& codec_of(Codec k) { return kCodecs[static_cast<size_t>(k)]; }
 
@@ -398,7 +402,7 @@ int check_push(slimm_ctx* c, Push& p) {
     const bool mid = c->win.announced.starts_mid || c->win.announced.ends_mid;
     if (F.active && mine != p.codec)   // (two codecs: the text names the first of them in Codec's order)
         return fail(c, SLIMM_E_INVALID, "%s SAM bytes and the other forms do not mix within a file", codec_of(named).name);
-    if (K.name && !K.cut_by_range && mid) return fail(c, SLIMM_E_INVALID, "a %s stream is not cut by byte range", K.name);
+    if (K.name && !K.cut_by_range && mid) return fail(c, SLIMM_E_INVALID, "%s %s stream is not cut by byte range", K.article ? K.article : "a", K.name);
     if (K.name && K.cut_at_frames && mid && !c->win.announced.has_range)
         return fail(c, SLIMM_E_INVALID, "a %s stream is not cut by byte range unless its range is announced (slimm_set_input_range) and starts at a frame", K.name);
     if (K.name && p.skip && F.active) return fail(c, SLIMM_E_INVALID, "skip: only in front of a file's first records");
@@ -656,12 +660,12 @@ int release_callers_buffer(slimm_ctx* c, const Push& p) {
     return SLIMM_OK;
 }
 
-// A window of a file's bytes in one of the seven forms: record bytes (`bytes` are BAM records or SAM text), whole BGZF blocks
+// A window of a file's bytes in one of the eight forms: record bytes (`bytes` are BAM records or SAM text), whole BGZF blocks
 // of them (the first `skip` inflated bytes are not records), SAM text in a streamed codec.
 int push_window(slimm_ctx* c, const uint8_t* bytes, uint64_t src_bytes, int format, uint32_t skip, int last, uint64_t* n_records) {
     if (!c) return SLIMM_E_INVALID;
     if (n_records) *n_records = 0;
-    const Codec codec = format == kFormatBzip2Sam ? Codec::Bzip2 : format == kFormatGzipSam ? Codec::Gzip : format == kFormatZstdSam ? Codec::Zstd : Codec::None;
+    const Codec codec = format == kFormatBzip2Sam ? Codec::Bzip2 : format == kFormatGzipSam ? Codec::Gzip : format == kFormatZstdSam ? Codec::Zstd : format == kFormatXzSam ? Codec::Xz : Codec::None;
     const bool sam = format == kFormatSam || format == kFormatBgzfSam || codec != Codec::None;
     Push p{bytes, src_bytes, src_bytes, skip, last != 0, sam, codec, format == kFormatBgzf || format == kFormatBgzfSam};
     SLIMM_TRY(check_push(c, p));
@@ -774,6 +778,15 @@ int slimm_push_gzip_sam_bytes(slimm_ctx* c, const uint8_t* bytes, uint64_t n_byt
 }
 int slimm_push_zstd_sam_bytes(slimm_ctx* c, const uint8_t* bytes, uint64_t n_bytes, uint32_t skip, int last, uint64_t* n_records) {
     return push_window(c, bytes, n_bytes, kFormatZstdSam, skip, last, n_records);
+}
+int slimm_push_xz_sam_bytes(slimm_ctx* c, const uint8_t* bytes, uint64_t n_bytes, uint32_t skip, int last, uint64_t* n_records) {
+    return push_window(c, bytes, n_bytes, kFormatXzSam, skip, last, n_records);
+}
+int slimm_get_xz_stats(slimm_ctx* c, uint64_t out[17]) {
+    if (!c || !out) return SLIMM_E_INVALID;
+    static_assert(WindowPipeline::kXzStats == 17, "slimm_get_xz_stats: seventeen counters");
+    std::copy(c->win.xz_stats, c->win.xz_stats + WindowPipeline::kXzStats, out);
+    return SLIMM_OK;
 }
 int slimm_get_zstd_stats(slimm_ctx* c, uint64_t out[20]) {
     if (!c || !out) return SLIMM_E_INVALID;

@@ -295,7 +295,7 @@ class Slimm:
         return total
 
     def _push_streamed_sam_bytes(self, push, blob, skip, window, cuts, empty_last) -> int:
-        """The cut-and-push loop of push_bzip2_sam_bytes, _gzip_ and _zstd_: `push` is the codec's entry point."""
+        """The cut-and-push loop of push_bzip2_sam_bytes, _gzip_, _zstd_ and _xz_: `push` is the codec's entry point."""
         buf = np.frombuffer(blob, dtype=np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob, dtype=np.uint8)
         n = buf.shape[0]
         if cuts is None:
@@ -350,6 +350,22 @@ class Slimm:
         out = (C.c_uint64 * 20)()
         self._check(self.L.slimm_get_zstd_stats(self.ctx, out))
         return dict(zip(self.ZSTD_STATS, [int(v) for v in out]))
+
+    def push_xz_sam_bytes(self, blob, skip: int = 0, window: int = 0, cuts=None, empty_last: bool = False) -> int:
+        """slimm_push_xz_sam_bytes: an xz-compressed SAM file's bytes from its first byte on, of whose decoded text the first
+        `skip` bytes are the header (set_reference_names first); the arguments are those of push_bzip2_sam_bytes.  The host
+        walks the streams, blocks and chunk headers, the device decodes the blocks (a lane each), checks them, finds the
+        lines and decodes them.  Returns the number of records."""
+        return self._push_streamed_sam_bytes(self.L.slimm_push_xz_sam_bytes, blob, skip, window, cuts, empty_last)
+
+    XZ_STATS = ("streams", "blocks", "lzma_chunks", "raw_chunks", "state_resets", "prop_changes", "odd_props", "check_none", "check_crc32",
+                "check_crc64", "sha256_unverified", "match_bytes", "max_dist", "rounds", "text_bytes", "compressed_bytes", "index_records")
+
+    def xz_stats(self) -> dict:
+        """slimm_get_xz_stats: the counters of the xz file read last."""
+        out = (C.c_uint64 * 17)()
+        self._check(self.L.slimm_get_xz_stats(self.ctx, out))
+        return dict(zip(self.XZ_STATS, [int(v) for v in out]))
 
     def push_bgzf_blocks(self, blob, skip: int = 0, window: int = 0, host_every: int = 0, sam: bool = False) -> int:
         """slimm_push_bgzf_blocks: whole BGZF blocks of a BAM file (compressed), the first of which holds the first alignment
