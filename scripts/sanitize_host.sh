@@ -11,6 +11,7 @@ g++ $FLAGS "$ROOT/tests/native/san_readers.cpp" "$ROOT/slimm_amd/csrc/host/align
     "$ROOT/slimm_amd/csrc/host/zstd.cpp" "$ROOT/slimm_amd/csrc/host/xz.cpp" "$ROOT/slimm_amd/csrc/host/sldb.cpp" -lz -lpthread -ldl -o "$W/san_readers"
 g++ $FLAGS "$ROOT/tests/native/san_zstd.cpp" "$ROOT/slimm_amd/csrc/host/zstd.cpp" -o "$W/san_zstd"
 g++ $FLAGS "$ROOT/tests/native/san_xz.cpp" "$ROOT/slimm_amd/csrc/host/xz.cpp" -o "$W/san_xz"
+g++ $FLAGS -Wall -Wextra "$ROOT/tests/native/san_bgzf_block.cpp" -o "$W/san_bgzf_block"
 g++ $FLAGS "$ROOT/tests/native/host_profile_bench.cpp" "$ROOT/slimm_amd/csrc/host_profile.cpp" -o "$W/san_profile"
 g++ $FLAGS "$ROOT/slimm_amd/csrc/host/slimm_build_main.cpp" "$ROOT/slimm_amd/csrc/host/sldb.cpp" -lz -o "$W/san_build"
 # ThreadSanitizer over the parallel BGZF inflate / record decode
@@ -102,6 +103,10 @@ for k in (0, len(xblobs) - 3, len(xblobs) - 2):
     print(f"san_xz --mutate {os.path.basename(xfiles[k])}:", r.stdout.strip())
     if r.returncode or r.stderr.strip():
         bad += 1; print("SANITIZER OUTPUT (san_xz --mutate):\n" + r.stderr[-4000:])
+r = subprocess.run([f"{d}/san_bgzf_block"], capture_output=True, text=True)
+print("san_bgzf_block:", r.stdout.strip().splitlines()[-1])
+if r.returncode or r.stderr.strip():
+    bad += 1; print("SANITIZER OUTPUT (san_bgzf_block):\n" + r.stdout + r.stderr[-4000:])
 r = subprocess.run([f"{d}/san_profile"], capture_output=True, text=True)
 print(r.stdout)
 if r.returncode or r.stderr.strip():

@@ -29,6 +29,7 @@
 #include <string>
 #include <vector>
 
+#include "bgzf_block.h"
 #include "kernels.h"
 
 namespace slimm {
@@ -440,55 +441,31 @@ bool bgzf_parse_blocks(const uint8_t* bytes, uint64_t n_bytes, uint64_t dst0, st
     uint32_t tok = 0;
     inflated = 0;
     while (p < n_bytes) {
-        if (n_bytes - p < 28) {
-            err = "truncated BGZF block";
+        const uint64_t avail = n_bytes - p;
+        bgzf::Header h{};
+        // (the bytes are whole blocks, so one that ends beyond them is cut short -- and so is one whose BSIZE does not hold it)
+        const bgzf::Status st = avail < 28 ? bgzf::kMore : bgzf::block_at(bytes + p, avail, &h);
+        if (st != bgzf::kOk) {
+            err = st == bgzf::kNotBgzf ? "not a BGZF block (gzip magic / FEXTRA)"
+                  : st == bgzf::kNoBc && avail >= 12ull + h.xlen + 8ull ? "BGZF block without a BC field"
+                  : st == bgzf::kTooLarge ? "BGZF block of more than 64 KB"
+                                          : "truncated BGZF block";
             return false;
         }
-        const uint8_t* h = bytes + p;
-        if (h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || !(h[3] & 4)) {
-            err = "not a BGZF block (gzip magic / FEXTRA)";
-            return false;
-        }
-        const uint32_t xlen = h[10] | (static_cast<uint32_t>(h[11]) << 8);
-        if (n_bytes - p < 12ull + xlen + 8ull) {
-            err = "truncated BGZF block";
-            return false;
-        }
-        uint32_t bsize = 0;
-        for (uint32_t q = 0; q + 4 <= xlen;) {  // the BC subfield
-            const uint8_t* f = h + 12 + q;
-            const uint32_t slen = f[2] | (static_cast<uint32_t>(f[3]) << 8);
-            if (f[0] == 'B' && f[1] == 'C' && slen == 2 && q + 6 <= xlen) bsize = (f[4] | (static_cast<uint32_t>(f[5]) << 8)) + 1u;
-            q += 4 + slen;
-        }
-        if (bsize < 12u + xlen + 8u || bsize > n_bytes - p) {
-            err = bsize ? "truncated BGZF block" : "BGZF block without a BC field";
-            return false;
-        }
-        const uint8_t* t = h + bsize - 4;
-        const uint32_t isize = t[0] | (static_cast<uint32_t>(t[1]) << 8) | (static_cast<uint32_t>(t[2]) << 16) | (static_cast<uint32_t>(t[3]) << 24);
-        if (isize > 65536u) {
-            err = "BGZF block of more than 64 KB";
-            return false;
-        }
-        const uint8_t* tc = h + bsize - 8;
         BgzfBlock d;
-        d.crc = tc[0] | (static_cast<uint32_t>(tc[1]) << 8) | (static_cast<uint32_t>(tc[2]) << 16) | (static_cast<uint32_t>(tc[3]) << 24);
+        d.crc = h.crc;
         d.tok = tok;
-        d.src = p + 12u + xlen;
-        d.csize = bsize - 12u - xlen - 8u;
-        d.isize = isize;
+        d.src = p + 12u + h.xlen;
+        d.csize = h.csize;
+        d.isize = h.isize;
         d.dst = dst;
-        // (the empty block at the end of a file -- a fixed-code block that holds its end-of-block code only -- has nothing to
-        // inflate; any other payload that claims ISIZE 0 is inflated all the same: it must give no byte and the CRC of none)
-        const bool eof_block = isize == 0 && d.csize == 2 && h[12u + xlen] == 0x03 && h[13u + xlen] == 0x00 && d.crc == 0;
-        if (!eof_block) {
+        if (!bgzf::is_eof_block(bytes + d.src, h.csize, h.isize, h.crc)) {
             out.push_back(d);
-            tok += bgzf_token_room(isize);
+            tok += bgzf_token_room(h.isize);
         }
-        dst += isize;
-        inflated += isize;
-        p += bsize;
+        dst += h.isize;
+        inflated += h.isize;
+        p += h.total;
     }
     return true;
 }

@@ -1,5 +1,6 @@
 #include "alignment_file.hpp"
 
+#include "../bgzf_block.h"
 #include "bzip2.hpp"
 #include "zstd.hpp"
 #include "xz.hpp"
@@ -150,7 +151,94 @@ struct StageClock {  // SLIMM_TRACE=cli: where the reader's time goes, printed w
     explicit StageClock(double& acc) : into(acc) {}
     ~StageClock() { into += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 };
+
+// Plain gzip (one deflate stream per member, members back to back): inflated in order by zlib -- a deflate stream has no
+// place to cut it for other threads -- a piece at a time.
+class GzipReader : public TextReader {
+public:
+    explicit GzipReader(Source source) : TextReader(std::move(source)) {
+        memset(&zs_, 0, sizeof(zs_));
+        if (inflateInit2(&zs_, 15 + 16) != Z_OK) {   // (gzip wrapping only)
+            err_ = "zlib: inflateInit2 failed";
+            bad_ = true;
+        }
+    }
+    ~GzipReader() override { inflateEnd(&zs_); }
+
+private:
+    bool next_text() override {
+        constexpr size_t kPiece = 256u << 10;
+        text_.resize(kPiece);
+        served_ = 0;
+        size_t out = 0;
+        while (out == 0) {
+            if (zs_.avail_in == 0 && !in_eof_) {
+                in_.resize(4u << 20);
+                const size_t got = source_(in_.data(), in_.size());
+                if (got < in_.size()) in_eof_ = true;
+                zs_.next_in = in_.data();
+                zs_.avail_in = static_cast<uInt>(got);
+            }
+            if (zs_.avail_in == 0) {   // the file is used up: between two members, or inside one
+                if (member_open_) return fail("truncated gzip stream");
+                done_ = true;
+                break;
+            }
+            member_open_ = true;
+            zs_.next_out = text_.data();
+            zs_.avail_out = static_cast<uInt>(kPiece);
+            const int rc = inflate(&zs_, Z_NO_FLUSH);
+            out = kPiece - zs_.avail_out;
+            if (rc == Z_STREAM_END) {   // (the member's CRC and ISIZE are checked; another member may follow)
+                member_open_ = false;
+                if (inflateReset(&zs_) == Z_OK) continue;
+            } else if (rc == Z_OK || (rc == Z_BUF_ERROR && zs_.avail_in == 0)) {
+                continue;
+            }
+            return fail(std::string("corrupt gzip stream (") + (zs_.msg ? zs_.msg : "inflate failed") + ")");
+        }
+        text_.resize(out);
+        return out > 0;
+    }
+    bool fail(const std::string& why) {
+        err_ = why;
+        bad_ = true;
+        text_.clear();
+        return false;
+    }
+    z_stream zs_;
+    bool member_open_ = false;   // a member begun and not finished
+};
+
+template <typename Reader>
+std::unique_ptr<TextReader> make_reader(FILE* fp, double*) {
+    return std::unique_ptr<TextReader>(new Reader([fp](uint8_t* d, size_t n) { return fread(d, 1, n, fp); }));
+}
+// (gzip's reads of the file count as the reader's read time; the other decoders' never did)
+std::unique_ptr<TextReader> make_gzip_reader(FILE* fp, double* ms_read) {
+    return std::unique_ptr<TextReader>(new GzipReader([fp, ms_read](uint8_t* d, size_t n) {
+        StageClock clk(*ms_read);
+        return fread(d, 1, n, fp);
+    }));
+}
 }  // namespace
+
+// The codecs whose file is one stream decoded in order, a row each: all that open(), codec_read and read_compressed tell apart.
+struct StreamedCodec {
+    Compression comp;
+    const char* noun;
+    const char* holds_bam;   // open()'s words for BAM inside (the path follows)
+    bool wraps_errors;       // a decode error reads "<noun>-compressed input is not supported unless it decodes: <error>: <path>"
+    bool ends_short;         // the text's end shows with its last bytes (a read that comes short), not only as a read of 0 bytes
+    std::unique_ptr<TextReader> (*make)(FILE* fp, double* ms_read);
+};
+static constexpr StreamedCodec kStreamedCodecs[] = {
+    {Compression::Gzip, "gzip", "a plain gzip stream that holds BAM (not BGZF): BAM is read from BGZF blocks only: ", false, true, make_gzip_reader},
+    {Compression::Bzip2, "bzip2", "a bzip2 stream that holds BAM: BAM is read from BGZF blocks only: ", true, false, make_reader<Bzip2Reader>},
+    {Compression::Zstd, "zstd", "a zstd stream that holds BAM: BAM is read from BGZF blocks only: ", true, false, make_reader<ZstdReader>},
+    {Compression::Xz, "xz", "an xz stream that holds BAM: BAM is read from BGZF blocks only: ", true, false, make_reader<XzReader>},
+};
+
 AlignmentFile::~AlignmentFile() { close(); }
 bool AlignmentFile::regular_file() const {
     struct stat sb;
@@ -192,11 +280,7 @@ void AlignmentFile::close() {
     map_size_ = map_pos_ = 0;
     if (fp_) fclose(fp_);
     fp_ = nullptr;
-    if (gz_) inflateEnd(gz_.get());
-    gz_.reset();
-    bz_.reset();
-    zs_.reset();
-    xz_.reset();
+    codec_.reset();
     workers_.reset();
     inflaters_.reset();
 }
@@ -231,10 +315,9 @@ bool AlignmentFile::open(const std::string& path) {
     err_.clear();
     bam_ = false;
     comp_ = Compression::None;
-    gz_in_.clear();
-    gz_in_eof_ = gz_member_open_ = gz_end_ = text_bad_ = false;
-    bz_end_ = bz_raw_started_ = false;
-    bz_raw_pos_ = bz_raw_size_ = 0;
+    streamed_ = nullptr;
+    text_bad_ = codec_end_ = raw_started_ = false;
+    raw_pos_ = raw_size_ = 0;
     lead_.clear();
     lead_off_ = 0;
     fp_ = fopen(path.c_str(), "rb");
@@ -248,17 +331,11 @@ bool AlignmentFile::open(const std::string& path) {
     std::vector<uint8_t> head(12);
     head.resize(fread(head.data(), 1, head.size(), fp_));
     const bool gzip = head.size() >= 2 && head[0] == 0x1f && head[1] == 0x8b;
-    bool bgzf = false;
-    if (gzip && head.size() == 12 && head[2] == 8 && (head[3] & 4)) {
-        const size_t xlen = rd_u16(&head[10]);
-        head.resize(12 + xlen);
-        if (fread(head.data() + 12, 1, xlen, fp_) == xlen)
-            for (size_t o = 0; o + 4 <= xlen;) {
-                const uint8_t* x = &head[12 + o];
-                const uint16_t slen = rd_u16(x + 2);
-                if (x[0] == 'B' && x[1] == 'C' && slen == 2 && o + 6 <= xlen) bgzf = true;
-                o += 4 + slen;
-            }
+    bool is_bgzf = false;
+    bgzf::Header bh;
+    if (head.size() == 12 && bgzf::block_at(head.data(), 12, &bh) == bgzf::kMore) {   // (a gzip member with an extra field)
+        head.resize(12 + bh.xlen);
+        if (fread(head.data() + 12, 1, bh.xlen, fp_) == bh.xlen) is_bgzf = bgzf::block_at(head.data(), head.size(), &bh) != bgzf::kNoBc;
     }
     rewind(fp_);
     auto starts = [&](const char* m, size_t n) { return head.size() >= n && memcmp(head.data(), m, n) == 0; };
@@ -269,65 +346,30 @@ bool AlignmentFile::open(const std::string& path) {
     const bool zstd = starts("\x28\xb5\x2f\xfd", 4) || (head.size() >= 4 && (head[0] & 0xf0) == 0x50 && memcmp(&head[1], "\x2a\x4d\x18", 3) == 0);
     const bool xz = starts("\xfd" "7zXZ\0", 6);
     bool ok;
-    if (xz) {
-        comp_ = Compression::Xz;
-        FILE* fp = fp_;
-        xz_.reset(new XzReader([fp](uint8_t* d, size_t n) { return fread(d, 1, n, fp); }));
-        ok = refill_text() || !text_bad_;
-        if (ok && buf_.size() >= 4 && memcmp(buf_.data(), "BAM\1", 4) == 0) {
-            err_ = "an xz stream that holds BAM: BAM is read from BGZF blocks only: " + path;
-            ok = false;
-        }
-        if (ok) ok = read_sam_header();
-        if (!ok && text_bad_) err_ += ": " + path;
-    } else if (zstd) {
-        comp_ = Compression::Zstd;
-        FILE* fp = fp_;
-        zs_.reset(new ZstdReader([fp](uint8_t* d, size_t n) { return fread(d, 1, n, fp); }));
-        ok = refill_text() || !text_bad_;
-        if (ok && buf_.size() >= 4 && memcmp(buf_.data(), "BAM\1", 4) == 0) {
-            err_ = "a zstd stream that holds BAM: BAM is read from BGZF blocks only: " + path;
-            ok = false;
-        }
-        if (ok) ok = read_sam_header();
-        if (!ok && text_bad_) err_ += ": " + path;
-    } else if (bzip2) {
-        comp_ = Compression::Bzip2;
-        FILE* fp = fp_;
-        bz_.reset(new Bzip2Reader([fp](uint8_t* d, size_t n) { return fread(d, 1, n, fp); }));
-        ok = refill_text() || !text_bad_;
-        if (ok && buf_.size() >= 4 && memcmp(buf_.data(), "BAM\1", 4) == 0) {
-            err_ = "a bzip2 stream that holds BAM: BAM is read from BGZF blocks only: " + path;
-            ok = false;
-        }
-        if (ok) ok = read_sam_header();
-        if (!ok && text_bad_) err_ += ": " + path;
-    } else if (starts("BZh", 3)) {
+    if (!bzip2 && starts("BZh", 3)) {
         err_ = "bzip2-compressed input is not supported (SAM / BAM, BGZF or gzip): " + path;
         ok = false;
-    } else if (bgzf) {
-        comp_ = Compression::Bgzf;
-        ok = fill(4) || err_.empty();   // (false without an error: fewer than 4 bytes in all)
-        bam_ = ok && buf_.size() - pos_ >= 4 && memcmp(&buf_[pos_], "BAM\1", 4) == 0;
-        if (ok && !bam_) sam_buf_off_ = 0 - pos_;   // (mod 2^64: the window's slack lies in front of the text's first byte)
-        if (ok) ok = bam_ ? read_bam_header() : read_sam_header();
-    } else if (gzip) {
-        comp_ = Compression::Gzip;
-        gz_.reset(new z_stream);
-        memset(gz_.get(), 0, sizeof(z_stream));
-        if (inflateInit2(gz_.get(), 15 + 16) != Z_OK) {   // (gzip wrapping only)
-            gz_.reset();
-            err_ = "zlib: inflateInit2 failed";
-            return false;
-        }
-        ok = refill_text() || !text_bad_;
-        if (ok && buf_.size() >= 4 && memcmp(buf_.data(), "BAM\1", 4) == 0) {
-            err_ = "a plain gzip stream that holds BAM (not BGZF): BAM is read from BGZF blocks only: " + path;
-            ok = false;
-        }
-        if (ok) ok = read_sam_header();
     } else {
-        ok = read_sam_header();
+        comp_ = xz ? Compression::Xz : zstd ? Compression::Zstd : bzip2 ? Compression::Bzip2 : is_bgzf ? Compression::Bgzf : gzip ? Compression::Gzip : Compression::None;
+        for (const StreamedCodec& c : kStreamedCodecs)
+            if (c.comp == comp_) streamed_ = &c;
+        if (streamed_) {
+            codec_ = streamed_->make(fp_, &ms_read_);
+            ok = refill_text() || !text_bad_;
+            if (ok && buf_.size() >= 4 && memcmp(buf_.data(), "BAM\1", 4) == 0) {
+                err_ = streamed_->holds_bam + path;
+                ok = false;
+            }
+            if (ok) ok = read_sam_header();
+            if (!ok && text_bad_ && streamed_->wraps_errors) err_ += ": " + path;
+        } else if (comp_ == Compression::Bgzf) {
+            ok = fill(4) || err_.empty();   // (false without an error: fewer than 4 bytes in all)
+            bam_ = ok && buf_.size() - pos_ >= 4 && memcmp(&buf_[pos_], "BAM\1", 4) == 0;
+            if (ok && !bam_) sam_buf_off_ = 0 - pos_;   // (mod 2^64: the window's slack lies in front of the text's first byte)
+            if (ok) ok = bam_ ? read_bam_header() : read_sam_header();
+        } else {
+            ok = read_sam_header();
+        }
     }
     if (!ok && err_.empty()) err_ = "bad header in " + path;
     return ok;
@@ -372,9 +414,8 @@ struct ThreadDecompressor {  // one per worker thread, freed with the thread
 };
 
 bool inflate_one(const uint8_t* src, size_t clen, uint8_t* dst, uint32_t isize, uint32_t crc) {
-    // (the end-of-file block -- a fixed-code block with its end-of-block code only -- has nothing to inflate; any other payload
-    // under an ISIZE of 0 must give no byte and the CRC of none, like on the device: bgzf_parse_blocks)
-    if (isize == 0 && clen == 2 && src[0] == 0x03 && src[1] == 0x00 && crc == 0) return true;
+    // (any other payload under an ISIZE of 0 must give no byte and the CRC of none, like on the device: bgzf_parse_blocks)
+    if (bgzf::is_eof_block(src, clen, isize, crc)) return true;
     uint8_t none[8];
     if (isize == 0) dst = none;
     const Deflate& L = deflate_lib();
@@ -403,6 +444,74 @@ bool inflate_one(const uint8_t* src, size_t clen, uint8_t* dst, uint32_t isize, 
 
 const char* AlignmentFile::inflate_backend() { return deflate_lib().ok ? "libdeflate" : "zlib"; }
 
+bool AlignmentFile::walk_blocks(const uint8_t* base, size_t& p, size_t end, bool last, size_t& out, size_t cap, std::string& err, bool* full) {
+    blocks_.clear();
+    if (full) *full = false;
+    while (end - p >= bgzf::kMinHeader) {
+        bgzf::Header h;
+        const bgzf::Status st = bgzf::block_at(base + p, end - p, &h);
+        if (st == bgzf::kMore) break;
+        if (st != bgzf::kOk) {
+            // (a size beyond the format's 64 KiB too: nothing is allocated on a file's word)
+            err = st == bgzf::kNotBgzf ? "not a BGZF block" : st == bgzf::kNoBc ? "BGZF block without BC field" : "bad BGZF block size";
+            return false;
+        }
+        if (out + h.isize > cap) {   // (the rest waits, compressed, for the next call)
+            if (full) *full = true;
+            return true;
+        }
+        blocks_.push_back(Block{p + bgzf::kFixedHeader + h.xlen, h.csize, out, h.isize, h.crc});
+        out += h.isize;
+        p += h.total;
+    }
+    if (last && blocks_.empty() && p != end) {
+        err = end - p < bgzf::kMinHeader ? "truncated BGZF header" : "truncated BGZF block";
+        return false;
+    }
+    return true;
+}
+
+bool AlignmentFile::inflate_blocks(const uint8_t* base, uint8_t* dst, std::string& err, const std::function<void()>& also) {
+    if (blocks_.empty()) return true;
+    StageClock clk(ms_inflate_);
+    std::atomic<size_t> next{0};
+    std::atomic<bool> ok{true}, extra{static_cast<bool>(also)};
+    inflaters_->run(std::min<unsigned>(inflaters_->size(), static_cast<unsigned>(blocks_.size()) + (also ? 1u : 0u)), [&](unsigned) {
+        if (extra.exchange(false)) also();
+        for (size_t k; (k = next.fetch_add(1)) < blocks_.size();) {
+            const Block& b = blocks_[k];
+            if (!inflate_one(base + b.coff, b.clen, dst + b.ooff, b.isize, b.crc)) ok = false;
+        }
+    });
+    if (!ok) err = "corrupt BGZF block (inflate or CRC failed)";
+    return ok;
+}
+
+// (as many threads as the process has cores to run them on -- the pool holds twice that --, 12 at least: on the 16-core
+// quota of the GPU box 12 / 16 / 24 / 32 threads read a 7.8 GB file in 200-460 / 180-200 / 150-200 / 160-180 ms,
+// profiles/round6/06_pread_threads.txt)
+bool AlignmentFile::pread_range(uint8_t* dst, size_t n, size_t off) {
+    const int fd = fileno(fp_);
+    const unsigned pread_threads = std::max(12u, inflaters_->size() / 2u);
+    const unsigned nt = static_cast<unsigned>(std::max<size_t>(1, std::min<size_t>(std::min<unsigned>(inflaters_->size(), pread_threads), n >> 22)));
+    const size_t per = (n + nt - 1) / nt;
+    std::atomic<bool> ok{true};
+    inflaters_->run(nt, [&](unsigned t) {
+        size_t lo = std::min(n, t * per);
+        const size_t hi = std::min(n, lo + per);
+        while (lo < hi) {
+            const ssize_t k = pread(fd, dst + lo, hi - lo, static_cast<off_t>(off + lo));
+            if (k <= 0) {
+                ok = false;
+                return;
+            }
+            lo += static_cast<size_t>(k);
+        }
+    });
+    if (!ok) err_ = "read error";
+    return ok;
+}
+
 // The next stretch of the file, inflated into dst[dst_off ...): one fread of `batch_bytes` compressed bytes (what is left of
 // an incomplete block at its end waits in cbuf_ for the next call), the BGZF block headers walked in memory, the blocks
 // inflated on the inflate workers.  Runs on the prefetch thread while the caller works on the window before.
@@ -416,69 +525,12 @@ bool AlignmentFile::read_inflate(Bytes& dst, size_t dst_off, size_t batch_bytes,
             cfill_ += got;
             if (got < batch_bytes) file_eof_ = true;
         }
-        blocks_.clear();
         size_t p = 0;
-        while (cfill_ - p >= 18) {
-            const uint8_t* hdr = cbuf_.data() + p;
-            if (hdr[0] != 0x1f || hdr[1] != 0x8b || hdr[2] != 8 || !(hdr[3] & 4)) {
-                err = "not a BGZF block";
-                return false;
-            }
-            const size_t xlen = rd_u16(hdr + 10);
-            if (cfill_ - p < 12 + xlen) break;
-            int bsize = -1;
-            for (size_t o = 0; o + 4 <= xlen;) {
-                const uint8_t* x = hdr + 12 + o;
-                const uint16_t slen = rd_u16(x + 2);
-                if (x[0] == 'B' && x[1] == 'C' && slen == 2 && o + 6 <= xlen) bsize = rd_u16(x + 4);
-                o += 4 + slen;
-            }
-            if (bsize < 0) {
-                err = "BGZF block without BC field";
-                return false;
-            }
-            const size_t total = static_cast<size_t>(bsize) + 1;
-            if (total < 12u + xlen + 8u) {
-                err = "bad BGZF block size";
-                return false;
-            }
-            if (cfill_ - p < total) break;
-            Block b;
-            b.coff = p + 12 + xlen;
-            b.clen = total - 12 - xlen - 8;  // deflate data (crc32 and isize follow)
-            b.crc = rd_u32(&cbuf_[p + total - 8]);
-            b.isize = rd_u32(&cbuf_[p + total - 4]);
-            if (b.isize > 65536u) {  // (the format caps a block's payload at 64 KiB; nothing is allocated on a file's word)
-                err = "bad BGZF block size";
-                return false;
-            }
-            b.ooff = out;
-            out += b.isize;
-            blocks_.push_back(b);
-            p += total;
-        }
-        if (file_eof_ && blocks_.empty() && cfill_ - p != 0) {
-            err = cfill_ - p < 18 ? "truncated BGZF header" : "truncated BGZF block";
-            return false;
-        }
+        if (!walk_blocks(cbuf_.data(), p, cfill_, file_eof_, out, ~size_t(0), err)) return false;
         cdone_ = p;
     }
     dst.resize(out);
-    if (!blocks_.empty()) {
-        StageClock clk(ms_inflate_);
-        std::atomic<size_t> next{0};
-        std::atomic<bool> ok{true};
-        inflaters_->run(std::min<unsigned>(inflaters_->size(), static_cast<unsigned>(blocks_.size())), [&](unsigned) {
-            for (size_t k; (k = next.fetch_add(1)) < blocks_.size();) {
-                const Block& b = blocks_[k];
-                if (!inflate_one(cbuf_.data() + b.coff, b.clen, dst.data() + b.ooff, b.isize, b.crc)) ok = false;
-            }
-        });
-        if (!ok) {
-            err = "corrupt BGZF block (inflate or CRC failed)";
-            return false;
-        }
-    }
+    if (!inflate_blocks(cbuf_.data(), dst.data(), err)) return false;
     // what is left of the last, incomplete block moves to the front
     memmove(cbuf_.data(), cbuf_.data() + cdone_, cfill_ - cdone_);
     cfill_ -= cdone_;
@@ -590,7 +642,7 @@ bool AlignmentFile::read_bam_header() {
 
 // ---- SAM text --------------------------------------------------------------------------------------------------
 // The next stretch of the text into buf_[pos_ ...): read as it lies in the file, inflated by the BGZF machinery of BAM
-// (fill: the prefetch thread and the inflate workers), or inflated from the one gzip stream.  sam_buf_off_ stays the
+// (fill: the prefetch thread and the inflate workers), or decoded from the one stream.  sam_buf_off_ stays the
 // text offset of buf_[0].  false at the end of the text, or on a format error (text_bad_, err_).
 bool AlignmentFile::refill_text() {
     if (text_bad_) return false;
@@ -605,9 +657,7 @@ bool AlignmentFile::refill_text() {
         return true;
     }
     buf_.resize(1 << 20);
-    const long got = comp_ == Compression::Gzip    ? gz_read(buf_.data(), buf_.size())
-                     : comp_ == Compression::Bzip2 || comp_ == Compression::Zstd || comp_ == Compression::Xz ? bz_read(buf_.data(), buf_.size())
-                                                   : static_cast<long>(fread(buf_.data(), 1, buf_.size(), fp_));
+    const long got = streamed() ? codec_read(buf_.data(), buf_.size()) : static_cast<long>(fread(buf_.data(), 1, buf_.size(), fp_));
     buf_.resize(got > 0 ? static_cast<size_t>(got) : 0u);
     pos_ = 0;
     sam_buf_off_ = consumed;
@@ -615,59 +665,17 @@ bool AlignmentFile::refill_text() {
     return got > 0;
 }
 
-// Plain gzip (one deflate stream per member, members back to back): inflated in order by zlib on the calling thread --
-// a deflate stream has no place to cut it for other threads -- up to `cap` bytes.  0 at the end, -1 + err_.
-long AlignmentFile::gz_read(uint8_t* dst, size_t cap) {
+// streamed(): the stream's next text, up to `cap` bytes, decoded in order on the calling thread.  0 at the end, -1 + err_ --
+// which, where the codec's row says so, keeps the words of the reader that did not decode the codec at all, and says why
+// this did not.
+long AlignmentFile::codec_read(uint8_t* dst, size_t cap) {
     if (text_bad_) return -1;
-    z_stream& zs = *gz_;
-    size_t out = 0;
-    while (out < cap && !gz_end_) {
-        if (zs.avail_in == 0 && !gz_in_eof_) {
-            StageClock clk(ms_read_);
-            gz_in_.resize(4u << 20);
-            const size_t got = fread(gz_in_.data(), 1, gz_in_.size(), fp_);
-            if (got < gz_in_.size()) gz_in_eof_ = true;
-            zs.next_in = gz_in_.data();
-            zs.avail_in = static_cast<uInt>(got);
-        }
-        if (zs.avail_in == 0) {   // the file is used up: between two members, or inside one
-            if (gz_member_open_) {
-                err_ = "truncated gzip stream";
-                text_bad_ = true;
-                return -1;
-            }
-            gz_end_ = true;
-            break;
-        }
-        gz_member_open_ = true;
-        zs.next_out = dst + out;
-        zs.avail_out = static_cast<uInt>(std::min<size_t>(cap - out, 1u << 30));
-        const int rc = inflate(&zs, Z_NO_FLUSH);
-        out = static_cast<size_t>(zs.next_out - dst);
-        if (rc == Z_STREAM_END) {   // (the member's CRC and ISIZE are checked; another member may follow)
-            gz_member_open_ = false;
-            if (inflateReset(&zs) == Z_OK) continue;
-        } else if (rc == Z_OK || (rc == Z_BUF_ERROR && zs.avail_in == 0)) {
-            continue;
-        }
-        err_ = std::string("corrupt gzip stream (") + (zs.msg ? zs.msg : "inflate failed") + ")";
-        text_bad_ = true;
-        return -1;
-    }
-    return static_cast<long>(out);
-}
-
-// bzip2 (streams back to back, blocks decoded in order on the calling thread: host/bzip2.cpp), up to `cap` bytes.  0 at
-// the end, -1 + err_ -- which keeps the words of the reader that did not decode bzip2 at all, and says why this did not.
-long AlignmentFile::bz_read(uint8_t* dst, size_t cap) {
-    if (text_bad_) return -1;
-    const long n = xz_ ? xz_->read(dst, cap) : zs_ ? zs_->read(dst, cap) : bz_->read(dst, cap);
+    const long n = codec_->read(dst, cap);
     if (n < 0) {
-        err_ = std::string(xz_ ? "xz" : zs_ ? "zstd" : "bzip2") + "-compressed input is not supported unless it decodes: " +
-               (xz_ ? xz_->error() : zs_ ? zs_->error() : bz_->error());
+        err_ = (streamed_->wraps_errors ? std::string(streamed_->noun) + "-compressed input is not supported unless it decodes: " : "") + codec_->error();
         text_bad_ = true;
-    } else if (n == 0) {
-        bz_end_ = true;
+    } else if (n == 0 || (streamed_->ends_short && static_cast<size_t>(n) < cap)) {
+        codec_end_ = true;
     }
     return n;
 }
@@ -1026,75 +1034,10 @@ long AlignmentFile::read_blocks(uint8_t* dst, size_t cap, size_t max_inflated, s
     // thread, and the device inflates a GB in 15).  The blocks are then walked in the buffer.
     size_t want = std::min(cap, map_size_ - map_pos_);
     if (blk_hint_) want = std::min(want, std::max<size_t>(blk_hint_, 1u << 20));
-    {
-        const int fd = fileno(fp_);
-        // (as many threads as the process has cores to run them on -- the pool holds twice that --, 12 at least: on the 16-core
-        // quota of the GPU box 12 / 16 / 24 / 32 threads read a 7.8 GB file in 200-460 / 180-200 / 150-200 / 160-180 ms,
-        // profiles/round6/06_pread_threads.txt)
-        const unsigned pread_threads = std::max(12u, inflaters_->size() / 2u);
-        const unsigned nt = static_cast<unsigned>(std::max<size_t>(1, std::min<size_t>(std::min<unsigned>(inflaters_->size(), pread_threads), want >> 22)));
-        const size_t per = (want + nt - 1) / nt;
-        std::atomic<bool> ok{true};
-        inflaters_->run(nt, [&](unsigned t) {
-            size_t lo = std::min(want, t * per);
-            const size_t hi = std::min(want, lo + per);
-            while (lo < hi) {
-                const ssize_t k = pread(fd, dst + lo, hi - lo, static_cast<off_t>(map_pos_ + lo));
-                if (k <= 0) {
-                    ok = false;
-                    return;
-                }
-                lo += static_cast<size_t>(k);
-            }
-        });
-        if (!ok) {
-            err_ = "read error";
-            return -1;
-        }
-    }
+    if (!pread_range(dst, want, map_pos_)) return -1;
     size_t out = 0, inf = 0;
     bool by_inflated = false;
-    while (want - out >= 18) {
-        const uint8_t* hdr = dst + out;
-        if (hdr[0] != 0x1f || hdr[1] != 0x8b || hdr[2] != 8 || !(hdr[3] & 4)) {
-            err_ = "not a BGZF block";
-            return -1;
-        }
-        const size_t xlen = rd_u16(hdr + 10);
-        if (want - out < 12 + xlen) break;
-        int bsize = -1;
-        for (size_t o = 0; o + 4 <= xlen;) {
-            const uint8_t* x = hdr + 12 + o;
-            const uint16_t slen = rd_u16(x + 2);
-            if (x[0] == 'B' && x[1] == 'C' && slen == 2 && o + 6 <= xlen) bsize = rd_u16(x + 4);
-            o += 4 + slen;
-        }
-        if (bsize < 0) {
-            err_ = "BGZF block without BC field";
-            return -1;
-        }
-        const size_t total = static_cast<size_t>(bsize) + 1;
-        if (total < 12u + xlen + 8u) {
-            err_ = "bad BGZF block size";
-            return -1;
-        }
-        if (want - out < total) break;
-        const uint32_t isize = rd_u32(hdr + total - 4);
-        if (isize > 65536u) {
-            err_ = "bad BGZF block size";
-            return -1;
-        }
-        if (inf + isize > max_inflated) {
-            by_inflated = true;
-            break;
-        }
-        out += total;
-        inf += isize;
-    }
-    if (out == 0 && !by_inflated && map_pos_ + want == map_size_) {
-        err_ = want < 18 ? "truncated BGZF header" : "truncated BGZF block";
-        return -1;
-    }
+    if (!walk_blocks(dst, out, want, map_pos_ + want == map_size_, inf, max_inflated, err_, &by_inflated)) return -1;
     if (out == 0) {
         err_ = "a BGZF block does not fit the window";
         return -1;
@@ -1109,35 +1052,32 @@ long AlignmentFile::read_blocks(uint8_t* dst, size_t cap, size_t max_inflated, s
 }
 
 long AlignmentFile::read_compressed(uint8_t* dst, size_t cap) {
-    if ((comp_ != Compression::Bzip2 && comp_ != Compression::Gzip && comp_ != Compression::Zstd && comp_ != Compression::Xz) || bam_ || !fp_ || !dst) {
+    if (!streamed() || bam_ || !fp_ || !dst) {
         err_ = "read_compressed: a bzip2, gzip, zstd or xz SAM file";
         return -1;
     }
     const int fd = fileno(fp_);
-    if (!bz_raw_started_) {
+    if (!raw_started_) {
         struct stat sb;
         if (fstat(fd, &sb) != 0) {
             err_ = "read_compressed: fstat failed";
             return -1;
         }
-        bz_raw_size_ = static_cast<size_t>(sb.st_size);
-        bz_raw_started_ = true;
+        raw_size_ = static_cast<size_t>(sb.st_size);
+        raw_started_ = true;
     }
     StageClock clk(ms_read_);
     size_t out = 0;
-    const size_t want = std::min(cap, bz_raw_size_ - bz_raw_pos_);
+    const size_t want = std::min(cap, raw_size_ - raw_pos_);
     while (out < want) {
-        const ssize_t got = pread(fd, dst + out, want - out, static_cast<off_t>(bz_raw_pos_ + out));
+        const ssize_t got = pread(fd, dst + out, want - out, static_cast<off_t>(raw_pos_ + out));
         if (got <= 0) {
-            err_ = comp_ == Compression::Xz     ? "truncated xz stream (the file shrank while it was read)"
-                   : comp_ == Compression::Zstd ? "truncated zstd stream (the file shrank while it was read)"
-                   : comp_ == Compression::Gzip ? "truncated gzip stream (the file shrank while it was read)"
-                                              : "truncated bzip2 stream (the file shrank while it was read)";
+            err_ = std::string("truncated ") + streamed_->noun + " stream (the file shrank while it was read)";
             return -1;
         }
         out += static_cast<size_t>(got);
     }
-    bz_raw_pos_ += out;
+    raw_pos_ += out;
     if (out) ++n_windows_;
     return static_cast<long>(out);
 }
@@ -1147,12 +1087,12 @@ long AlignmentFile::read_text(uint8_t* dst, size_t cap) {
         err_ = "read_text: a SAM file (plain or gzip) and a buffer of at least 64 KiB";
         return -1;
     }
-    if (comp_ == Compression::Gzip || comp_ == Compression::Bzip2 || comp_ == Compression::Zstd || comp_ == Compression::Xz) {   // (on the caller's thread: the command's reader thread, beside the device's work)
+    if (streamed()) {   // (on the caller's thread: the command's reader thread, beside the device's work)
         StageClock clk(ms_inflate_);
         sam_text_started_ = true;
         size_t out = take_lead(dst, cap);
         if (out < cap) {
-            const long n = comp_ == Compression::Gzip ? gz_read(dst + out, cap - out) : bz_read(dst + out, cap - out);
+            const long n = codec_read(dst + out, cap - out);
             if (n < 0) return -1;
             out += static_cast<size_t>(n);
         }
@@ -1172,26 +1112,7 @@ long AlignmentFile::read_text(uint8_t* dst, size_t cap) {
     if (sam_text_pos_ >= sam_size_) return 0;
     StageClock clk(ms_read_);
     const size_t want = std::min(cap, sam_size_ - sam_text_pos_);
-    const int fd = fileno(fp_);
-    const unsigned nt = static_cast<unsigned>(std::max<size_t>(1, std::min<size_t>(std::min<unsigned>(inflaters_->size(), std::max(12u, inflaters_->size() / 2u)), want >> 22)));   // (as read_blocks)
-    const size_t per = (want + nt - 1) / nt;
-    std::atomic<bool> ok{true};
-    inflaters_->run(nt, [&](unsigned t) {
-        size_t lo = std::min(want, t * per);
-        const size_t hi = std::min(want, lo + per);
-        while (lo < hi) {
-            const ssize_t k = pread(fd, dst + lo, hi - lo, static_cast<off_t>(sam_text_pos_ + lo));
-            if (k <= 0) {
-                ok = false;
-                return;
-            }
-            lo += static_cast<size_t>(k);
-        }
-    });
-    if (!ok) {
-        err_ = "read error";
-        return -1;
-    }
+    if (!pread_range(dst, want, sam_text_pos_)) return -1;
     sam_text_pos_ += want;
     ++n_windows_;
     return static_cast<long>(want);
@@ -1252,73 +1173,15 @@ long AlignmentFile::read_raw(uint8_t* dst, size_t cap) {
         size_t p = map_pos_;
         {
             StageClock clk(ms_read_);
-            blocks_.clear();
-            while (map_size_ - p >= 18) {
-                const uint8_t* hdr = map_ + p;
-                if (hdr[0] != 0x1f || hdr[1] != 0x8b || hdr[2] != 8 || !(hdr[3] & 4)) {
-                    err_ = "not a BGZF block";
-                    return -1;
-                }
-                const size_t xlen = rd_u16(hdr + 10);
-                if (map_size_ - p < 12 + xlen) break;
-                int bsize = -1;
-                for (size_t o = 0; o + 4 <= xlen;) {
-                    const uint8_t* x = hdr + 12 + o;
-                    const uint16_t slen = rd_u16(x + 2);
-                    if (x[0] == 'B' && x[1] == 'C' && slen == 2 && o + 6 <= xlen) bsize = rd_u16(x + 4);
-                    o += 4 + slen;
-                }
-                if (bsize < 0) {
-                    err_ = "BGZF block without BC field";
-                    return -1;
-                }
-                const size_t total = static_cast<size_t>(bsize) + 1;
-                if (total < 12u + xlen + 8u) {
-                    err_ = "bad BGZF block size";
-                    return -1;
-                }
-                if (map_size_ - p < total) break;
-                Block b;
-                b.coff = p + 12 + xlen;
-                b.clen = total - 12 - xlen - 8;
-                b.crc = rd_u32(map_ + p + total - 8);
-                b.isize = rd_u32(map_ + p + total - 4);
-                if (b.isize > 65536u) {
-                    err_ = "bad BGZF block size";
-                    return -1;
-                }
-                if (out + b.isize > cap) break;
-                b.ooff = out;
-                out += b.isize;
-                blocks_.push_back(b);
-                p += total;
-            }
-            if (blocks_.empty() && p != map_size_) {
-                err_ = map_size_ - p < 18 ? "truncated BGZF header" : "truncated BGZF block";
-                return -1;
-            }
+            if (!walk_blocks(map_, p, map_size_, true, out, cap, err_)) return -1;
         }
-        if (!blocks_.empty()) {
-            StageClock clk(ms_inflate_);
-            std::atomic<size_t> next{0};
-            std::atomic<bool> ok{true};
-            // (one more job beside the blocks: the page tables of the stretch the NEXT call will parse -- the parser is
-            // one thread and would take a page fault per block header otherwise)
-            const size_t ahead_lo = p & ~size_t(4095), ahead_hi = std::min(map_size_, p + (24u << 20));
-            std::atomic<bool> populate{true};
-            inflaters_->run(std::min<unsigned>(inflaters_->size(), static_cast<unsigned>(blocks_.size()) + 1u), [&](unsigned) {
-                if (populate.exchange(false) && ahead_hi > ahead_lo)
-                    (void)madvise(const_cast<uint8_t*>(map_) + ahead_lo, ahead_hi - ahead_lo, 22 /* MADV_POPULATE_READ */);
-                for (size_t k; (k = next.fetch_add(1)) < blocks_.size();) {
-                    const Block& b = blocks_[k];
-                    if (!inflate_one(map_ + b.coff, b.clen, dst + b.ooff, b.isize, b.crc)) ok = false;
-                }
-            });
-            if (!ok) {
-                err_ = "corrupt BGZF block (inflate or CRC failed)";
-                return -1;
-            }
-        }
+        // (one more job beside the blocks: the page tables of the stretch the NEXT call will parse -- the parser is
+        // one thread and would take a page fault per block header otherwise)
+        const size_t ahead_lo = p & ~size_t(4095), ahead_hi = std::min(map_size_, p + (24u << 20));
+        if (!inflate_blocks(map_, dst, err_, [&] {
+                if (ahead_hi > ahead_lo) (void)madvise(const_cast<uint8_t*>(map_) + ahead_lo, ahead_hi - ahead_lo, 22 /* MADV_POPULATE_READ */);
+            }))
+            return -1;
         map_pos_ = p;
         ++n_windows_;
         if (map_pos_ == map_size_) eof_ = true;
@@ -1343,69 +1206,11 @@ long AlignmentFile::read_raw(uint8_t* dst, size_t cap) {
                 cfill_ += got;
                 if (got < kRawBatch) file_eof_ = true;
             }
-            blocks_.clear();
             size_t p = cstart_;
-            while (cfill_ - p >= 18) {
-                const uint8_t* hdr = cbuf_.data() + p;
-                if (hdr[0] != 0x1f || hdr[1] != 0x8b || hdr[2] != 8 || !(hdr[3] & 4)) {
-                    err_ = "not a BGZF block";
-                    return -1;
-                }
-                const size_t xlen = rd_u16(hdr + 10);
-                if (cfill_ - p < 12 + xlen) break;
-                int bsize = -1;
-                for (size_t o = 0; o + 4 <= xlen;) {
-                    const uint8_t* x = hdr + 12 + o;
-                    const uint16_t slen = rd_u16(x + 2);
-                    if (x[0] == 'B' && x[1] == 'C' && slen == 2 && o + 6 <= xlen) bsize = rd_u16(x + 4);
-                    o += 4 + slen;
-                }
-                if (bsize < 0) {
-                    err_ = "BGZF block without BC field";
-                    return -1;
-                }
-                const size_t total = static_cast<size_t>(bsize) + 1;
-                if (total < 12u + xlen + 8u) {
-                    err_ = "bad BGZF block size";
-                    return -1;
-                }
-                if (cfill_ - p < total) break;
-                Block b;
-                b.coff = p + 12 + xlen;
-                b.clen = total - 12 - xlen - 8;
-                b.crc = rd_u32(&cbuf_[p + total - 8]);
-                b.isize = rd_u32(&cbuf_[p + total - 4]);
-                if (b.isize > 65536u) {
-                    err_ = "bad BGZF block size";
-                    return -1;
-                }
-                if (out + b.isize > cap) break;  // (the buffer is full: the rest waits, compressed, for the next call)
-                b.ooff = out;
-                out += b.isize;
-                blocks_.push_back(b);
-                p += total;
-            }
-            if (file_eof_ && blocks_.empty() && cfill_ - p != 0 && out == 0) {
-                err_ = cfill_ - p < 18 ? "truncated BGZF header" : "truncated BGZF block";
-                return -1;
-            }
+            if (!walk_blocks(cbuf_.data(), p, cfill_, file_eof_, out, cap, err_)) return -1;
             cdone_ = p;
         }
-        if (!blocks_.empty()) {
-            StageClock clk(ms_inflate_);
-            std::atomic<size_t> next{0};
-            std::atomic<bool> ok{true};
-            inflaters_->run(std::min<unsigned>(inflaters_->size(), static_cast<unsigned>(blocks_.size())), [&](unsigned) {
-                for (size_t k; (k = next.fetch_add(1)) < blocks_.size();) {
-                    const Block& b = blocks_[k];
-                    if (!inflate_one(cbuf_.data() + b.coff, b.clen, dst + b.ooff, b.isize, b.crc)) ok = false;
-                }
-            });
-            if (!ok) {
-                err_ = "corrupt BGZF block (inflate or CRC failed)";
-                return -1;
-            }
-        }
+        if (!inflate_blocks(cbuf_.data(), dst, err_)) return -1;
         const bool progressed = cdone_ != cstart_;
         cstart_ = cdone_;
         ++n_windows_;

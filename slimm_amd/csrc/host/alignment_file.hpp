@@ -4,13 +4,15 @@
 // src/slimm.hpp:194-208, 420-424): header reference names + lengths in header order (= refID), and per record
 // qName, flag, refID, 0-based position and sequence length.  CIGAR, MAPQ, qualities and tags are never looked at by
 // SLIMM and are skipped.  BAM = BGZF (concatenated gzip members, inflated with libdeflate when the box has it, else zlib) carrying the binary records of the
-// SAM specification; SAM = the tab-separated text form, as it is, in BGZF blocks (bgzip) or in a plain gzip stream of one
-// or more members (gzip, inflated here by one zlib stream; the command hands a regular file's bytes to the device instead).  Written against the SAM/BAM specification -- SeqAn's source
+// SAM specification; SAM = the tab-separated text form, as it is, in BGZF blocks (bgzip) or in a gzip, bzip2, zstd or xz
+// stream (decoded here in order by one TextReader, text_reader.hpp, on the calling thread; the command hands a regular file's
+// bytes to the device instead).  A BGZF block's header is read in ../bgzf_block.h.  Written against the SAM/BAM specification -- SeqAn's source
 // is not part of the reference checkout -- and cross-checked in tests against files produced by an independent
 // Python writer (tests/bam_io.py).
 #pragma once
 #include <cstdint>
 #include <cstdio>
+#include <functional>
 #include <memory>
 #include <string>
 #include <thread>
@@ -18,8 +20,6 @@
 #include <vector>
 
 #include "../read_identity.h"
-
-struct z_stream_s;   // (zlib.h)
 
 namespace slimm {
 
@@ -49,9 +49,8 @@ enum class SortOrder { Unknown, Unsorted, QueryName, Coordinate, QueryGrouped };
 // frames back to back (SAM text from zstd / pzstd), or as xz streams of LZMA2 blocks (SAM text from xz / pixz / pxz)
 enum class Compression { None, Bgzf, Gzip, Bzip2, Zstd, Xz };
 
-class Bzip2Reader;   // (bzip2.hpp)
-class ZstdReader;    // (zstd.hpp)
-class XzReader;      // (xz.hpp)
+class TextReader;    // (text_reader.hpp)
+struct StreamedCodec;   // (alignment_file.cpp: what differs between gzip, bzip2, zstd and xz)
 
 // 62-bit identity of a read name.  The reader makes it exact where grouped input needs it to be: a record whose name
 // differs from its predecessor's never gets the predecessor's key (separate_adjacent_names).  Names colliding far
@@ -86,6 +85,8 @@ public:
     const std::string& error() const { return err_; }
     bool is_bam() const { return bam_; }   // the payload: BAM records (else SAM text)
     Compression compression() const { return comp_; }
+    // one stream decoded in order (gzip, bzip2, zstd, xz): its text comes from read_text, its bytes from read_compressed
+    bool streamed() const { return streamed_ != nullptr; }
     // "libdeflate" when libdeflate.so.0 could be dlopen()ed, else "zlib"
     static const char* inflate_backend();
 
@@ -122,21 +123,20 @@ public:
     bool can_read_blocks() const { return raw_stage_ == 2 && map_ != nullptr && !eof_; }
     // SAM only: the file's text behind the header -- the alignment lines -- window by window straight into the caller's
     // buffer, cut anywhere (for slimm_push_sam_bytes: the lines are found and decoded on the device); read by pread on
-    // several threads, or -- a plain gzip file -- inflated by one zlib stream on the calling thread.  Returns the bytes
+    // several threads, or -- streamed() -- decoded by the stream's reader on the calling thread.  Returns the bytes
     // written, 0 at the end of the file, -1 + error().  Not to be mixed with read_batch / read_into afterwards.  (BGZF
     // SAM goes through read_raw / read_blocks.)
     long read_text(uint8_t* dst, size_t cap);
     bool can_read_text() const { return !bam_ && comp_ != Compression::Bgzf && fp_ != nullptr; }
-    // bzip2, gzip, zstd and xz SAM: the file's bytes as they lie in it, from its first byte on, window by window (for
+    // streamed() SAM: the file's bytes as they lie in it, from its first byte on, window by window (for
     // slimm_push_bzip2_sam_bytes / _gzip_sam_bytes / _zstd_sam_bytes / _xz_sam_bytes: the device decodes them; the header's text_header_bytes()
     // decoded bytes are skipped there).  Read by pread, beside whatever read_text read.  Returns the bytes written, 0 at the end, -1 + error().
     long read_compressed(uint8_t* dst, size_t cap);
-    bool compressed_exhausted() const { return bz_raw_pos_ >= bz_raw_size_ && bz_raw_started_; }
+    bool compressed_exhausted() const { return raw_pos_ >= raw_size_ && raw_started_; }
     bool regular_file() const;   // (read_text and the mapped reads want one; a pipe or a device goes through the buffered reads)
-    // after a read_raw that returned bytes: nothing will follow them (false may also mean "not known yet")
+    // after a read_raw (streamed(): a read_text) that returned bytes: nothing will follow them (false may also mean "not known yet")
     bool raw_exhausted() const {
-        if (comp_ == Compression::Gzip) return gz_end_ && lead_off_ >= lead_.size() && pos_ >= buf_.size();
-        if (comp_ == Compression::Bzip2 || comp_ == Compression::Zstd || comp_ == Compression::Xz) return bz_end_ && lead_off_ >= lead_.size() && pos_ >= buf_.size();
+        if (streamed()) return codec_end_ && lead_off_ >= lead_.size() && pos_ >= buf_.size();
         return raw_stage_ == 2 ? eof_ : (raw_stage_ == 1 && eof_ && raw_off_ >= spare_.size());
     }
 
@@ -165,24 +165,18 @@ private:
     bool read_sam_header();
     bool next_sam_line(std::string& line);
     bool refill_text();       // the next stretch of SAM text into buf_ (false: its end, or an error in err_)
-    long gz_read(uint8_t* dst, size_t cap);   // plain gzip: the next inflated bytes of the stream (0 at its end, -1 + err_)
-    long bz_read(uint8_t* dst, size_t cap);   // bzip2, zstd, xz: the next decoded bytes of the streams (0 at their end, -1 + err_)
+    long codec_read(uint8_t* dst, size_t cap);   // streamed(): the next decoded bytes of the stream (0 at its end, -1 + err_)
     size_t take_lead(uint8_t* dst, size_t cap);   // compressed SAM: the first alignment line and the rest of buf_, once
     void parse_hd_line(const std::string& line);
 
     FILE* fp_ = nullptr;
     bool bam_ = false, eof_ = false;
     Compression comp_ = Compression::None;
-    // plain gzip: the zlib stream, its compressed input, the input's end, a member begun and not finished, the stream's end
-    std::unique_ptr<::z_stream_s> gz_;
-    std::vector<uint8_t> gz_in_;
-    bool gz_in_eof_ = false, gz_member_open_ = false, gz_end_ = false;
-    // bzip2: the host decoder, the end of its streams; read_compressed's file position and the file's size
-    std::unique_ptr<Bzip2Reader> bz_;
-    std::unique_ptr<ZstdReader> zs_;   // zstd: the host decoder (the rest of its state: bzip2's)
-    std::unique_ptr<XzReader> xz_;     // xz: the host decoder (likewise)
-    bool bz_end_ = false, bz_raw_started_ = false;
-    size_t bz_raw_pos_ = 0, bz_raw_size_ = 0;
+    // streamed(): the codec's row, its host decoder, the end of its text; read_compressed's file position and the file's size
+    const StreamedCodec* streamed_ = nullptr;
+    std::unique_ptr<TextReader> codec_;
+    bool codec_end_ = false, raw_started_ = false;
+    size_t raw_pos_ = 0, raw_size_ = 0;
     bool text_bad_ = false;   // compressed SAM: the text ran into a format error (err_); the reader's answer from then on
     // compressed SAM: the first alignment line as it stands in the text (the header parse took it out of buf_), handed out
     // in front of the rest by read_text / read_raw; line_cr_ / line_nl_: the last line next_sam_line read ended with CR LF / LF
@@ -217,6 +211,16 @@ private:
     // BAM windows are double-buffered: while the caller decodes buf_, the prefetch thread reads and inflates the next
     // stretch of the file into spare_
     bool read_inflate(Bytes& dst, size_t dst_off, size_t batch_bytes, bool& at_eof, std::string& err);
+    // The whole BGZF blocks of base[p, end) into blocks_ -- their payloads as offsets from `base`, their outputs one behind the
+    // other from `out` on --, up to the first that would take the output beyond `cap` (*full) or that the bytes do not hold
+    // whole; p and out move behind what was taken.  last: no byte will follow `end`, so a first block cut short is an error.
+    // false + err: not BGZF
+    bool walk_blocks(const uint8_t* base, size_t& p, size_t end, bool last, size_t& out, size_t cap, std::string& err, bool* full = nullptr);
+    // blocks_ inflated from `base` into `dst` on the inflate workers, `also` (if any) as one more job beside them; false + err:
+    // a block that does not inflate to its size and CRC
+    bool inflate_blocks(const uint8_t* base, uint8_t* dst, std::string& err, const std::function<void()>& also = {});
+    // [off, off + n) of the file into dst by pread on several threads; false + err_
+    bool pread_range(uint8_t* dst, size_t n, size_t off);
     void start_prefetch();
     void stop_prefetch();
     static constexpr size_t kSlack = 4u << 20;  // room in front of a new window for the unread tail of the one before

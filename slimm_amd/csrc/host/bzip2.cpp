@@ -5,7 +5,7 @@
 
 namespace slimm {
 
-Bzip2Reader::Bzip2Reader(std::function<size_t(uint8_t*, size_t)> source) : source_(std::move(source)), tables_(new bz2::Tables) {
+Bzip2Reader::Bzip2Reader(Source source) : TextReader(std::move(source)), tables_(new bz2::Tables) {
     bz2::crc_table(crc_tab_);
 }
 Bzip2Reader::~Bzip2Reader() { delete tables_; }
@@ -17,22 +17,14 @@ long Bzip2Reader::fail(const std::string& why) {
 }
 
 bool Bzip2Reader::more_input() {
-    if (in_eof_) return false;
-    const size_t drop = static_cast<size_t>(bit_ >> 3);   // (the bytes in front of the one being read are done with)
-    if (drop) {
-        in_.erase(in_.begin(), in_.begin() + static_cast<long>(drop));
-        in_base_ += drop;
-        bit_ -= drop * 8u;
-    }
-    const size_t have = in_.size(), chunk = 4u << 20;
-    in_.resize(have + chunk);
-    const size_t got = source_(in_.data() + have, chunk);
-    in_.resize(have + got);
-    if (got == 0) in_eof_ = true;
-    return got > 0;
+    pos_ = static_cast<size_t>(bit_ >> 3);   // (the byte being read: what lies in front of it may go)
+    const uint64_t base = in_base_;
+    const bool more = need(in_.size() - pos_ + 1);
+    bit_ -= (in_base_ - base) * 8u;
+    return more;
 }
 
-bool Bzip2Reader::next_block() {
+bool Bzip2Reader::next_text() {
     auto at = [&](uint64_t bit) { return std::to_string(in_base_ + (bit >> 3)); };
     for (;;) {
         if (!in_stream_) {   // a stream header, at a byte
@@ -97,11 +89,11 @@ bool Bzip2Reader::next_block() {
             fail("block at byte " + at(bit_) + ": " + bz2::status_text(st));
             return false;
         }
-        // inverse BWT from origPtr, then RLE1 undone into out_, the text's CRC checked
+        // inverse BWT from origPtr, then RLE1 undone into text_, the text's CRC checked
         uint32_t cf[256];
         bz2::link_block(ll_.data(), info.n, counts, tt_.data(), cf);
-        out_.clear();
-        out_pos_ = 0;
+        text_.clear();
+        served_ = 0;
         uint32_t crc = 0xffffffffu, p = info.orig_ptr;
         bz2::Rle1 r;
         for (uint32_t k = 0; k < info.n; ++k) {
@@ -110,7 +102,7 @@ bool Bzip2Reader::next_block() {
             const uint32_t copies = r.step(u >> 24, byte);
             p = u & bz2::kLinkMask;
             for (uint32_t c = 0; c < copies; ++c) {
-                out_.push_back(static_cast<uint8_t>(byte));
+                text_.push_back(static_cast<uint8_t>(byte));
                 crc = bz2::crc_byte(crc_tab_, crc, byte);
             }
         }
@@ -122,23 +114,6 @@ bool Bzip2Reader::next_block() {
         bit_ = info.end_bit;
         return true;
     }
-}
-
-long Bzip2Reader::read(uint8_t* dst, size_t cap) {
-    if (bad_) return -1;
-    size_t out = 0;
-    while (out < cap) {
-        if (out_pos_ >= out_.size()) {
-            if (done_ || !next_block()) break;
-            continue;
-        }
-        const size_t n = std::min(cap - out, out_.size() - out_pos_);
-        memcpy(dst + out, out_.data() + out_pos_, n);
-        out_pos_ += n;
-        out += n;
-    }
-    if (bad_) return -1;
-    return static_cast<long>(out);
 }
 
 }  // namespace slimm

@@ -432,9 +432,7 @@ int dump_raw(const Options& o) {
     const size_t cap = static_cast<size_t>(std::max(1u, o.window_mb)) << 20;
     std::vector<uint8_t> buf(cap);
     long n;
-    const bool text = f.compression() == Compression::Gzip || f.compression() == Compression::Bzip2 || f.compression() == Compression::Zstd ||
-                      f.compression() == Compression::Xz;
-    while ((n = text ? f.read_text(buf.data(), cap) : f.read_raw(buf.data(), cap)) > 0) {
+    while ((n = f.streamed() ? f.read_text(buf.data(), cap) : f.read_raw(buf.data(), cap)) > 0) {
         std::cerr << "window\t" << n << "\t" << (f.raw_exhausted() ? "last" : "more") << "\n";
         if (fwrite(buf.data(), 1, static_cast<size_t>(n), stdout) != static_cast<size_t>(n)) return 1;
     }

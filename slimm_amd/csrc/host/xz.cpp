@@ -38,28 +38,10 @@ bool all_zero(const uint8_t* p, size_t n) {
 
 }  // namespace
 
-XzReader::XzReader(std::function<size_t(uint8_t*, size_t)> source) : source_(std::move(source)) {}
-
 bool XzReader::fail(const std::string& where, uint32_t status, const std::string& more) {
     err_ = where + ": " + xz::status_text(status) + more;
     bad_ = true;
     return false;
-}
-
-bool XzReader::need(size_t n) {
-    while (in_.size() - pos_ < n && !in_eof_) {
-        if (pos_ > (1u << 20)) {   // (the bytes in front of the one being read are done with)
-            in_.erase(in_.begin(), in_.begin() + static_cast<long>(pos_));
-            in_base_ += pos_;
-            pos_ = 0;
-        }
-        const size_t have = in_.size(), chunk = 4u << 20;
-        in_.resize(have + chunk);
-        const size_t got = source_(in_.data() + have, chunk);
-        in_.resize(have + got);
-        if (got == 0) in_eof_ = true;
-    }
-    return in_.size() - pos_ >= n;
 }
 
 // behind a block's end marker: the padding, the sizes against the header's, the check
@@ -115,7 +97,7 @@ bool XzReader::read_index() {
     return true;
 }
 
-bool XzReader::next_chunk() {
+bool XzReader::next_text() {
     auto at = [&](size_t pos) { return std::to_string(in_base_ + pos); };
     for (;;) {
         if (stage_ == Stage::Between) {
@@ -222,23 +204,6 @@ bool XzReader::next_chunk() {
         pos_ += ch.header + static_cast<size_t>(ch.csize);
         return true;
     }
-}
-
-long XzReader::read(uint8_t* dst, size_t cap) {
-    if (bad_) return -1;
-    size_t out = 0;
-    while (out < cap) {
-        if (served_ >= text_.size()) {
-            if (done_ || !next_chunk()) break;
-            continue;
-        }
-        const size_t n = std::min(cap - out, text_.size() - served_);
-        memcpy(dst + out, text_.data() + served_, n);
-        served_ += n;
-        out += n;
-    }
-    if (bad_) return -1;
-    return static_cast<long>(out);
 }
 
 bool xz_read_index(const std::function<bool(uint64_t, uint8_t*, size_t)>& read, uint64_t size, std::vector<XzIndexBlock>* blocks, uint32_t* streams) {

@@ -12,10 +12,12 @@
 #include <vector>
 
 #include "../xz_stream.h"
+#include "text_reader.hpp"
 
 namespace slimm {
 
-class XzReader {
+// error(): "block at byte N: <cause>", "index at byte N: <cause>", ...
+class XzReader : public TextReader {
 public:
     // what the file held so far (the tests compare with their own walk; the device decoder counts the same)
     struct Counts {
@@ -23,26 +25,15 @@ public:
         uint64_t check_none = 0, check_crc32 = 0, check_crc64 = 0, sha256_unverified = 0;
         uint64_t match_bytes = 0, max_dist = 0, text = 0, index_records = 0;
     };
-    // `source(dst, cap)`: the next compressed bytes of the file, in order (0 at its end)
-    explicit XzReader(std::function<size_t(uint8_t*, size_t)> source);
-    // the next decoded bytes, at most `cap`; 0 at the end of the last stream, -1 + error()
-    long read(uint8_t* dst, size_t cap);
-    // "block at byte N: <cause>", "index at byte N: <cause>", ... (without the reader's "xz-compressed input ..." in front)
-    const std::string& error() const { return err_; }
+    explicit XzReader(Source source) : TextReader(std::move(source)) {}
     const Counts& counts() const { return n_; }
 
 private:
     enum class Stage { Between, Stream, Chunks };
-    bool next_chunk();   // decode up to the next chunk that holds text (false: the end, or err_)
-    bool need(size_t n); // at least n bytes at pos_ (false: the file has no more)
+    bool next_text() override;   // the next chunk that holds text, behind the block's text so far (at least its dictionary's worth is kept)
     bool fail(const std::string& where, uint32_t status, const std::string& more = "");
     bool end_block();
     bool read_index();
-    std::function<size_t(uint8_t*, size_t)> source_;
-    std::vector<uint8_t> in_;   // compressed bytes from file offset in_base_ on; the next to read: pos_
-    uint64_t in_base_ = 0;
-    size_t pos_ = 0;
-    bool in_eof_ = false, done_ = false, bad_ = false;
     Stage stage_ = Stage::Between;
     uint32_t check_ = 0;
     std::vector<std::pair<uint64_t, uint64_t>> records_;   // the stream's blocks so far: unpadded size, uncompressed size
@@ -52,10 +43,7 @@ private:
     xz::Rules rules_;
     xz::Lzma lz_{};
     std::vector<uint16_t> probs_;
-    std::vector<uint8_t> text_;   // the block's text: at least its dictionary's worth
-    size_t served_ = 0;           // ... of which [served_, size) have not been handed out
     Counts n_;
-    std::string err_;
 };
 
 // A block by its stream's index: where its header lies in the file, its unpadded size (header, data and check) and its text

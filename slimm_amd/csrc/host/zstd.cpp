@@ -6,28 +6,10 @@
 
 namespace slimm {
 
-ZstdReader::ZstdReader(std::function<size_t(uint8_t*, size_t)> source) : source_(std::move(source)) {}
-
 bool ZstdReader::fail(const std::string& where, uint32_t status) {
     err_ = where + ": " + zs::status_text(status);
     bad_ = true;
     return false;
-}
-
-bool ZstdReader::need(size_t n) {
-    while (in_.size() - pos_ < n && !in_eof_) {
-        if (pos_ > (1u << 20)) {   // (the bytes in front of the one being read are done with)
-            in_.erase(in_.begin(), in_.begin() + static_cast<long>(pos_));
-            in_base_ += pos_;
-            pos_ = 0;
-        }
-        const size_t have = in_.size(), chunk = 4u << 20;
-        in_.resize(have + chunk);
-        const size_t got = source_(in_.data() + have, chunk);
-        in_.resize(have + got);
-        if (got == 0) in_eof_ = true;
-    }
-    return in_.size() - pos_ >= n;
 }
 
 uint32_t ZstdReader::decode_compressed(const uint8_t* content, uint32_t size, uint32_t block_max, uint64_t window, zs::Entropy& e, uint32_t rep[3],
@@ -97,7 +79,7 @@ uint32_t ZstdReader::decode_compressed(const uint8_t* content, uint32_t size, ui
     return zs::kOk;
 }
 
-bool ZstdReader::next_block() {
+bool ZstdReader::next_text() {
     auto at = [&](size_t pos) { return std::to_string(in_base_ + pos); };
     for (;;) {
         if (!in_frame_) {
@@ -171,23 +153,6 @@ bool ZstdReader::next_block() {
         }
         if (text_.size() > before) return true;
     }
-}
-
-long ZstdReader::read(uint8_t* dst, size_t cap) {
-    if (bad_) return -1;
-    size_t out = 0;
-    while (out < cap) {
-        if (served_ >= text_.size()) {
-            if (done_ || !next_block()) break;
-            continue;
-        }
-        const size_t n = std::min(cap - out, text_.size() - served_);
-        memcpy(dst + out, text_.data() + served_, n);
-        served_ += n;
-        out += n;
-    }
-    if (bad_) return -1;
-    return static_cast<long>(out);
 }
 
 bool zstd_header_end(const std::function<bool(uint64_t, uint8_t*, size_t)>& read, uint64_t size, uint64_t skip, uint64_t* end) {

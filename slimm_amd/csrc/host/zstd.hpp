@@ -10,17 +10,14 @@
 #include <vector>
 
 #include "../zstd_frame.h"
+#include "text_reader.hpp"
 
 namespace slimm {
 
-class ZstdReader {
+// error(): "block at byte N: <cause>", "frame at byte N: <cause>", ...
+class ZstdReader : public TextReader {
 public:
-    // `source(dst, cap)`: the next compressed bytes of the file, in order (0 at its end)
-    explicit ZstdReader(std::function<size_t(uint8_t*, size_t)> source);
-    // the next decoded bytes, at most `cap`; 0 at the end of the last frame, -1 + error()
-    long read(uint8_t* dst, size_t cap);
-    // "block at byte N: <cause>", "frame at byte N: <cause>", ... (without the reader's "zstd-compressed input ..." in front)
-    const std::string& error() const { return err_; }
+    explicit ZstdReader(Source source) : TextReader(std::move(source)) {}
     // where the reader stands: the file offset behind the last block it decoded (its checksum included), whether a frame
     // goes on there, and that frame's header (the split planner walks on from here: split.hip)
     uint64_t file_pos() const { return in_base_ + pos_; }
@@ -32,22 +29,14 @@ public:
                                       std::vector<uint8_t>& text, size_t frame_lo);
 
 private:
-    bool next_block();   // decode the next block into out_ (false: the end, or err_)
-    bool need(size_t n); // at least n bytes at pos_ (false: the file has no more)
+    bool next_text() override;   // the next block that holds text, behind the frame's text so far (at least its last `window` bytes are kept)
     bool fail(const std::string& where, uint32_t status);
-    std::function<size_t(uint8_t*, size_t)> source_;
-    std::vector<uint8_t> in_;   // compressed bytes from file offset in_base_ on; the next to read: pos_
-    uint64_t in_base_ = 0;
-    size_t pos_ = 0;
-    bool in_eof_ = false, in_frame_ = false, done_ = false, bad_ = false;
+    bool in_frame_ = false;
     uint64_t frames_ = 0, frame_at_ = 0, frame_len_ = 0;
     zs::FrameHeader fh_{};
     zs::Entropy entropy_;
     uint32_t rep_[3] = {1, 4, 8};
     zs::Xxh64 xxh_;
-    std::vector<uint8_t> text_;   // the frame's text: at least its last `window` bytes
-    size_t served_ = 0;           // ... of which [served_, size) have not been handed out
-    std::string err_;
 };
 
 // A file of `size` bytes seen through read(offset, dst, n) (false: a read error): *end = the first byte behind the frame

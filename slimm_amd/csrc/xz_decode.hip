@@ -152,7 +152,7 @@ void push_trace_xz(const char* fmt, ...) {   // "[push xz] ..."
     va_end(ap);
 }
 
-// the host reader's words (host/alignment_file.cpp: bz_read)
+// the host reader's words (host/alignment_file.cpp: codec_read)
 int xz_fail(slimm_ctx* c, const std::string& where, uint32_t status, const std::string& more = "") {
     return fail(c, SLIMM_E_INVALID, "xz-compressed input is not supported unless it decodes: %s: %s%s", where.c_str(), xz::status_text(status), more.c_str());
 }

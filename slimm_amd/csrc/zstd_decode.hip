@@ -174,7 +174,7 @@ void push_trace_zs(const char* fmt, ...) {   // "[push zstd] ..."
     va_end(ap);
 }
 
-// the host reader's words (host/alignment_file.cpp: zs_read)
+// the host reader's words (host/alignment_file.cpp: codec_read)
 int zs_fail(slimm_ctx* c, const std::string& where, uint32_t status) {
     return fail(c, SLIMM_E_INVALID, "zstd-compressed input is not supported unless it decodes: %s: %s", where.c_str(), zs::status_text(status));
 }

@@ -111,6 +111,33 @@ def test_corrupt_blocks_are_errors_not_output():
     assert rc != 0 and "too small" in err
 
 
+def test_the_block_header_is_read_by_its_subfields():
+    """The library's descriptor walk (bgzf_parse_blocks over slimm_amd/csrc/bgzf_block.h): BC is found among other
+    subfields, and each thing that is no BGZF block is refused in the words include/slimm_hip.h promises."""
+    text = [b"".join(b"read%04d\t%d\tref%d\t%d\n" % (k, 16 * (k % 2), k % 7, 100 * k + j) for k in range(45)) for j in range(3)]
+    blocks = [bgzf_block(t) for t in text]
+
+    def rewrap(block, extra):
+        """The same deflate data and trailer behind the extra field `extra` ("BC"'s BSIZE filled in where it holds one)."""
+        body = block[18:]
+        at = next((o for o in range(0, len(extra) - 3) if extra[o:o + 4] == b"BC\x02\0"), None)
+        if at is not None:
+            extra = extra[:at + 4] + struct.pack("<H", 12 + len(extra) + len(body) - 1) + extra[at + 6:]
+        return block[:10] + struct.pack("<H", len(extra)) + extra + body
+
+    rc, want, err, _ = device_inflate(b"".join(blocks))
+    assert rc == 0 and want == b"".join(text), err
+    front, behind = b"XY\x03\0abc", b"ZZ\x05\0hello"
+    rc, got, err, _ = device_inflate(blocks[0] + rewrap(blocks[1], front + b"BC\x02\0\0\0" + behind) + blocks[2])
+    assert rc == 0 and got == want, err
+    rc, _, err, _ = device_inflate(blocks[0] + rewrap(blocks[1], front + b"BD\x02\0\0\0" + behind) + blocks[2])
+    assert rc != 0 and err == "BGZF block without a BC field", err
+    rc, _, err, _ = device_inflate(blocks[0] + b"\x1f\x8c" + blocks[1][2:] + blocks[2])
+    assert rc != 0 and err == "not a BGZF block (gzip magic / FEXTRA)", err
+    rc, _, err, _ = device_inflate(blocks[0] + blocks[1][:-4] + struct.pack("<I", 65537) + blocks[2])
+    assert rc != 0 and err == "BGZF block of more than 64 KB", err
+
+
 def _bam_file(tmp_path, w, names, seed, level=6):
     """A BAM file of this repository's writer + where its alignment records start: (compressed bytes of the blocks from the
     first record-bearing one on, inflated bytes to skip there, the records' bytes)."""
