@@ -526,8 +526,10 @@ __global__ __launch_bounds__(128) void k_inflate_decode(const uint8_t* __restric
                 // behind a literal: a second literal?
                 const bool lit2 = is_lit & (l2 <= 15u) & (s2hi == 0u);
                 // behind a length: the distance
+                // (behind a literal s2lo is a literal's low byte, not a distance symbol: the count of extra bits is kept below 16
+                // so that the two shifts below are defined for it as well; a distance symbol is at most 31, which asks for 14)
                 const uint32_t ds = s2lo;
-                const uint32_t de = ds >= 4u ? (ds >> 1) - 1u : 0u;
+                const uint32_t de = ds >= 4u ? ((ds >> 1) - 1u) & 15u : 0u;
                 const uint32_t dbv = ds < 4u ? ds + 1u : 1u + ((2u + (ds & 1u)) << de);
                 const uint32_t dist = dbv + ((w2 >> (l2 > 15u ? 15u : l2)) & ((1u << de) - 1u));
                 if (is_len) {

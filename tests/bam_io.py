@@ -47,12 +47,16 @@ def _bgzf_block(data: bytes) -> bytes:
             + comp + struct.pack("<II", zlib.crc32(data) & 0xffffffff, len(data)))
 
 
-def bam_record_bytes(records, read_len=100, irregular_seed=None, l_seq_of=None) -> bytes:
+def bam_record_bytes(records, read_len=100, irregular_seed=None, l_seq_of=None, lifelike_seed=None) -> bytes:
     """The alignment records of a BAM file as they follow its header (SAM/BAM specification 4.2), concatenated:
     block_size | refID | pos | l_read_name | mapq | bin | n_cigar_op | flag | l_seq | next_refID | next_pos | tlen |
     read_name | cigar | seq | qual (| tags).  irregular_seed: record sizes vary (sequence lengths 0 .. 3 x read_len, one to
     four CIGAR operations, a few optional tag bytes), so that record boundaries fall anywhere.  l_seq_of: {record index:
-    sequence length} for single records of another size."""
+    sequence length} for single records of another size.  lifelike_seed: what a mapper writes -- sequence lengths 1 .. 300
+    (records 3 and 7: 1 and 2; a few of length 0), packed bases drawn from A, C, G, T with about 1 % N, quality bytes 0 .. 93,
+    a CIGAR of the sequence's length and an NM tag --, everything drawn from random.Random(lifelike_seed).  Off by default."""
+    if lifelike_seed is not None:
+        return _lifelike_record_bytes(records, lifelike_seed)
     q = qnames_of(records)
     fflag = _file_flags(records)
     rng = np.random.default_rng(irregular_seed) if irregular_seed is not None else None
@@ -80,14 +84,44 @@ def bam_record_bytes(records, read_len=100, irregular_seed=None, l_seq_of=None) 
     return bytes(out)
 
 
-def write_bam(path, ref_names, ref_len, records, read_len=100, hd="@HD\tVN:1.6\tSO:unsorted\tGO:query", irregular_seed=None,
-              l_seq_of=None):
+def _lifelike_record_bytes(records, seed) -> bytes:
+    import random
+    rng = random.Random(seed)
+    q = qnames_of(records)
+    fflag = _file_flags(records)
+    out = bytearray()
+    for i in range(len(records)):
+        name = q[i].encode() + b"\x00"
+        l_seq = 1 if i == 3 else 2 if i == 7 else 0 if rng.random() < 0.01 else rng.randrange(1, 301)
+        codes = rng.choices((1, 2, 4, 8, 15), weights=(99, 99, 99, 99, 4), k=l_seq + (l_seq & 1))   # (=ACMGRSVTWYHKDBN: A 1, C 2, G 4, T 8, N 15)
+        if l_seq & 1:
+            codes[-1] = 0
+        sq = bytes((codes[k] << 4) | codes[k + 1] for k in range(0, len(codes), 2))
+        ql = bytes(rng.randrange(94) for _ in range(l_seq))
+        clip = rng.randrange(l_seq // 3 + 1) if rng.random() < 0.3 else 0
+        ops = ([(clip, 4)] if clip else []) + [(l_seq - clip, 0)] if l_seq else []
+        cg = b"".join(struct.pack("<I", (n << 4) | op) for n, op in ops)
+        tags = b"NMC" + bytes([rng.randrange(l_seq // 10 + 1)])
+        body = struct.pack("<iiBBHHHIiii", int(records.ref_id[i]), int(records.begin_pos[i]), len(name), rng.randrange(61), 4680, len(ops),
+                           int(fflag[i]), l_seq, -1, -1, 0) + name + cg + sq + ql + tags
+        out += struct.pack("<i", len(body)) + body
+    return bytes(out)
+
+
+def bam_header_bytes(ref_names, ref_len, hd="@HD\tVN:1.6\tSO:unsorted\tGO:query") -> bytes:
+    """A BAM file's bytes in front of its first alignment record: magic, header text, reference names and lengths."""
     text = sam_header(ref_names, ref_len, hd).encode()
     out = bytearray()
     out += b"BAM\x01" + struct.pack("<i", len(text)) + text + struct.pack("<i", len(ref_names))
     for n, l in zip(ref_names, ref_len):
         nb = n.encode() + b"\x00"
         out += struct.pack("<i", len(nb)) + nb + struct.pack("<i", int(l))
+    return bytes(out)
+
+
+def write_bam(path, ref_names, ref_len, records, read_len=100, hd="@HD\tVN:1.6\tSO:unsorted\tGO:query", irregular_seed=None,
+              l_seq_of=None):
+    out = bytearray(bam_header_bytes(ref_names, ref_len, hd))
     out += bam_record_bytes(records, read_len, irregular_seed, l_seq_of)
     with open(path, "wb") as f:
         for s in range(0, len(out), 0xff00):

@@ -65,7 +65,12 @@ struct Fiber {
 
 std::vector<Fiber> g_fibers;
 std::vector<Wave> g_waves;
-std::vector<char*> g_stack_pool;
+struct StackPool : std::vector<char*> {   // (released at exit: a leak checker then reports the kernels' leaks only)
+    ~StackPool() {
+        for (char* p : *this) std::free(p);
+    }
+};
+StackPool g_stack_pool;
 Fiber* g_cur = nullptr;
 void* g_sched_sp = nullptr;
 const std::function<void()>* g_body = nullptr;
