@@ -428,30 +428,16 @@ struct Staged {
 #define SLIMM_HASH_WALK 32
 #endif
 constexpr uint32_t kHashWalk = SLIMM_HASH_WALK;
-// D = N0 & (N0 << 1) marks the second and later lanes of every stretch of set bits of N0 (non-start lanes: a segment of
-// L records is a stretch of L - 1).  Is there a stretch of D of at least n bits (a segment of more than n + 1 records)?
-__device__ __forceinline__ bool has_run_of(uint64_t D, uint32_t n) {
-    // stretches of >= 2^k bits by doubling, then the remainder
-    uint64_t x = D;
-    uint32_t have = 1;
-    while (have * 2u <= n) {
-        x &= x << have;
-        have *= 2u;
-    }
-    if (have < n) x &= x << (n - have);
-    return x != 0ull;
-}
+static_assert(kHashWalk == 16 || kHashWalk == 24 || kHashWalk == 32 || kHashWalk == 48,
+              "the threshold is one of the distances window_fast's doubling chain knows");
 
 // ---------------------------------------------------------------------------------------------------------
-// fast path: lanes [0, X) of the window hold whole runs whose mates never decrease.  field = the staged reference field,
-// SS = segment starts (run starts and mate changes), V = mapped lanes, both inside [0, X).
+// fast path: the lanes PR = [0, X) of the window hold whole runs whose mates never decrease.  field = the staged reference
+// field, SS = segment starts (run starts and mate changes; lane 0 is one), V = mapped lanes, both inside PR.
 // ---------------------------------------------------------------------------------------------------------
-struct WinMasks {  // what the caller needs to cut the filter's windows: the window's targets and read heads
-    uint64_t F, H;
-};
-__device__ __forceinline__ WinMasks window_fast(uint32_t field, uint32_t gbin, uint32_t lane, uint64_t SS, uint64_t V, uint32_t X,
-                                                WinOut& so, uint32_t* __restrict__ tgt_ref, uint32_t* __restrict__ tgt_gbin,
-                                                uint32_t* tab) {
+__device__ __forceinline__ void window_fast(uint32_t field, uint32_t gbin, uint32_t lane, uint64_t SS, uint64_t V, uint64_t PR,
+                                            WinOut& so, uint32_t* __restrict__ tgt_ref, uint32_t* __restrict__ tgt_gbin,
+                                            uint32_t* tab) {
     // Q1: an earlier lane of my segment with my reference?  T = {segment number, field} is never zero and equal only
     // inside a segment; x_d[i] = T[i - d] ^ T[i] (T of the lanes in front of lane 0 taken as zero) follows from
     // x_{d+1}[i] = x_d[i - 1] ^ x_1[i]: ONE xor with a lane shift per step.  A lane is a duplicate iff some x_d is zero.
@@ -461,39 +447,52 @@ __device__ __forceinline__ WinMasks window_fast(uint32_t field, uint32_t gbin, u
     // longest segment, the table's cost is the same whatever the segments look like (config 5, 40 hits per read: every
     // window; config 3, 8 hits per read: one window in three).
     const uint32_t T = (f_rank(SS >> 1) << kTagShift) | field;
-    const uint64_t N0 = ~SS & f_below_nz(X);  // (a window holds a record)
-    uint64_t D = N0 & (N0 << 1);
+    // ONE doubling chain over the non-start lanes serves both the choice of the path and the walk's length (the scalar
+    // unit is what a CU has one of): Ek = the lanes at least k records behind their segment's start.  The walk goes on in
+    // stretches that end where the chain knows a distance -- 1, 3, 7, 11, 15, 23, 31, 47 steps -- so a window pays one
+    // scalar test per stretch and walks at most a few steps further than its longest segment asks for.
+    const uint64_t N0 = SS ^ PR;  // (the segment starts are lanes of the window)
+    const uint64_t E2 = N0 & (N0 << 1), E4 = E2 & (E2 << 2), E8 = E4 & (E4 << 4), E12 = E8 & (E8 << 4), E16 = E8 & (E8 << 8);
+    const uint64_t E24 = E16 & (E16 << 8), E32 = E16 & (E16 << 16), E48 = E32 & (E32 << 16);
     uint64_t F;
-    if (has_run_of(D, kHashWalk - 1u)) {
+    if ((kHashWalk == 16 ? E16 : kHashWalk == 24 ? E24 : kHashWalk == 32 ? E32 : E48) != 0ull) {
         hash_clear(tab, lane);
         bool overflow = false;  // (never: 64 keys at most)
         F = f_ballot(hash_first(tab, T, lane, f_bit(V), overflow));
     } else {
         const uint32_t x1 = f_shr1z(T) ^ T;
         uint32_t x = x1, differ = x1;
-        // (the scalar unit is what a CU has one of: segments of up to six records -- four steps -- update D step by step,
-        // longer ones go on eight steps at a time with D advanced by doubling: one scalar instruction per step, not two)
-        if (D) {
+        const auto walk = [&](int steps) {
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                x = f_shr1z(x) ^ x1;
-                differ = min(differ, x);
-                D &= D << 1;
-            }
-        }
-        while (D) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
+            for (int u = 0; u < steps; ++u) {
                 x = f_shr1z(x) ^ x1;
                 differ = min(differ, x);
             }
-            const uint64_t t2 = D & (D << 1), t4 = t2 & (t2 << 2), t8 = t4 & (t4 << 4);
-            D = t8 & (D << 8);
+        };
+        if (E2) {
+            walk(2);
+            if (E4) {
+                walk(4);
+                if (E8) {
+                    walk(4);
+                    if (E12) {
+                        walk(4);
+                        if (kHashWalk > 16 && E16) {
+                            walk(8);
+                            if (kHashWalk > 24 && E24) {
+                                walk(8);
+                                if (kHashWalk > 32 && E32) walk(16);
+                            }
+                        }
+                    }
+                }
+            }
         }
         F = f_ballot(differ != 0u) & V;
     }
-    // heads: the first mapped lane of every segment; the last lane of a segment stops the carry of its start
-    const uint64_t H = f_first_after(SS, V, (SS >> 1) | (1ull << (X - 1u)));
+    // heads: the first mapped lane of every segment; the last lane of a segment stops the carry of its start (the last
+    // segment's needs no stop: behind the window's last lane nothing is mapped, and `& V` drops what the carry leaves there)
+    const uint64_t H = f_first_after(SS, V, SS >> 1);
     // unique reads: a head whose NEXT target is a head again (or there is none in the window: the next run's first
     // target is a head).  In bit-reversed order "the target in front of g" is "the first target above g".
     const uint64_t Fr = __builtin_bitreverse64(F), Gr = __builtin_bitreverse64(F & ~H);
@@ -503,13 +502,12 @@ __device__ __forceinline__ WinMasks window_fast(uint32_t field, uint32_t gbin, u
         // (the index in a vector register: the scalar unit is the kernel's bottleneck, and a scalar base per array costs
         // it two 64-bit adds and a shift per window)
         const uint32_t p = so.base + so.nf + f_rank(F);
-        tgt_ref[p] = (field - 1u) | (f_bit(H) ? 0x80000000u : 0u);
+        tgt_ref[p] = (field - 1u) + (f_bit(H) ? 0x80000000u : 0u);  // (a reference has 26 bits: one three-operand add)
         tgt_gbin[p] = gbin | (uniq ? 0x80000000u : 0u);
     }
     so.nf += static_cast<uint32_t>(__popcll(F));
     so.nh += static_cast<uint32_t>(__popcll(H));
     so.nv += static_cast<uint32_t>(__popcll(V));
-    return WinMasks{F, H};
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -950,12 +948,13 @@ __global__ __launch_bounds__(kFrontBlock, 4) void k_front(const Acc acc, uint32_
     const uint32_t N = acc.count(counters);
     const uint32_t lane = f_lane();
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t n_waves = gridDim.x * (kFrontBlock / 64);
     uint32_t* const st1 = s_stage[wave][0];
     uint32_t* const st2 = s_stage[wave][1];
     uint32_t* const tab = s_tab[wave];
     bool bad = false, collide = false;
-    for (uint32_t slot = blockIdx.x * (kFrontBlock / 64) + wave; slot < nslots; slot += n_waves) {
+    // (one slot per wave: front_grid)
+    const uint32_t slot = blockIdx.x * (kFrontBlock / 64) + wave;
+    if (slot < nslots) {
         const uint32_t B = slot * kSlotRecs;
         WinOut so{B, 0u, 0u, 0u};
         FPROF_T(f0);
@@ -973,7 +972,27 @@ __global__ __launch_bounds__(kFrontBlock, 4) void k_front(const Acc acc, uint32_
             FPROF_ADD(0, f0, f1);
             uint32_t off = next_run_start(st1, lane, 0u);
             so.base = B + min(off, kSlotRecs);
-            while (off < kSlotRecs && B + off < N) {  // (the stream may end inside the slot)
+            const uint32_t lim = min(kSlotRecs, N - B);  // the slot's records (the stream may end inside the slot)
+            const uint32_t* const st1_lane = st1 + lane;  // (the lane's part of a window's address, once per slot)
+            const uint32_t* const st2_lane = st2 + lane;
+            while (off < lim) {
+                // The common windows in a loop of their own, so that the scalar unit is spared what the others need: 64
+                // records that exist and lie inside the slot (no clamp at the stream's or the slot's end), whole runs
+                // with non-decreasing mates.  Anything else leaves the loop for ONE window of the full form below.
+                while (static_cast<int32_t>(off) <= static_cast<int32_t>(lim) - 64) {
+                    const uint32_t w1 = st1_lane[off], w2 = st2_lane[off];
+                    const uint64_t RSw = f_ballot(static_cast<int32_t>(w1) < 0);  // (bit 0 is set: a window starts a run)
+                    const uint32_t lead = static_cast<uint32_t>(__builtin_clzll(RSw));
+                    if (lead == 63u) break;  // a run of 64 records or more
+                    const uint32_t X = 63u - lead;  // complete runs end at the last run start of the window
+                    const uint64_t PR = (~0ull >> 1) >> lead;
+                    const uint32_t field = w1 & kRefField, mate = (w1 >> kStMateShift) & 3u, mprev = f_shr1z(mate);
+                    if ((f_ballot(mate < mprev) & ~RSw & PR) != 0ull) break;  // mates interleave
+                    window_fast(field, w2, lane, (RSw | f_ballot(mate != mprev)) & PR, f_ballot(field != kRefField) & PR, PR, so, tgt_ref,
+                                tgt_gbin, tab);
+                    off += X;
+                }
+                if (off >= lim) break;
                 const uint32_t w1 = st1[off + lane], w2 = st2[off + lane];
                 const uint64_t RSw = f_ballot(static_cast<int32_t>(w1) < 0);  // (bit 0 is set: a window starts a run)
                 const uint32_t pos = B + off;
@@ -990,7 +1009,7 @@ __global__ __launch_bounds__(kFrontBlock, 4) void k_front(const Acc acc, uint32_
                     const uint32_t mprev = f_shr1z(mate);
                     const uint64_t V = f_ballot(field != kRefField) & PR;
                     if ((f_ballot(mate < mprev) & ~RS & PR) == 0ull) {
-                        (void)window_fast(field, w2, lane, (RS | f_ballot(mate != mprev)) & PR, V, X, so, tgt_ref, tgt_gbin, tab);
+                        window_fast(field, w2, lane, (RS | f_ballot(mate != mprev)) & PR, V, PR, so, tgt_ref, tgt_gbin, tab);
                     } else {  // (mates interleave: the window's targets are not in lane order)
                         window_general(Staged{mate, field - 1u, w2, f_bit(V)}, lane, RS, V, X, so, tgt_ref, tgt_gbin);
                     }
