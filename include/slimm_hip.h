@@ -586,6 +586,9 @@ int slimm_get_bins(slimm_ctx* ctx, int which, uint32_t* out);
  *            every reference padded to a multiple of 4 bins) | bit 31: the read has this one target only
  * Call with ref = gbin = NULL to get the number of entries in *n; otherwise cap entries are available and *n are written. */
 int slimm_get_read_targets(slimm_ctx* ctx, uint32_t* ref, uint32_t* gbin, uint64_t cap, uint64_t* n);
+/* Diagnostic: the width in bits of a target's reference word in device memory -- 16 for a database of at most 32768
+ * references (15 bits of reference and the flag), 32 otherwise.  slimm_get_read_targets gives the 32-bit form either way. */
+int slimm_target_ref_bits(slimm_ctx* ctx);
 
 /* taxon_id__read_count (src/slimm.hpp:126). stage 0: direct LCA hits only (:536-557); 1: final (:560-610). */
 int slimm_taxon_count_size(slimm_ctx* ctx, int stage, uint32_t* n);

@@ -163,6 +163,7 @@ struct slimm_ctx {
     bool rows16_base_ready = false;    // h_rows16 holds the static part of every row
     std::vector<uint32_t> rows16_prev; // references whose valid bit is set in h_rows16
     bool use_rows16 = false;
+    bool ref16 = false;                // the targets' reference words are 16 bits wide (kernels.h: TargetRefs)
     // records
     DevBuf<uint64_t> in_key;
     DevBuf<int32_t> in_ref, in_pos;
@@ -180,7 +181,9 @@ struct slimm_ctx {
     DevBuf<uint64_t> c_ident, s_ident;
     DevBuf<uint2> c_pay, s_pay;
     DevBuf<uint32_t> group_hist, c_chk, s_chk;
-    DevBuf<uint32_t> tgt_ref, tgt_gbin;  // targets (bit 31: first of its read / the read has one target), in slots
+    DevBuf<uint32_t> tgt_ref, tgt_gbin;  // targets (top bit: first of its read / the read has one target), in slots;
+                                         // tgt_ref holds uint16_t words when ref16 (target_refs())
+    TargetRefs target_refs() const { return TargetRefs{tgt_ref.p, ref16}; }
     DevBuf<uint4> slots;                 // per kSlotRecs records: {first target, targets, reads, mapped records}
     DevBuf<uint4> tot_part;              // per workgroup of k_tile_count: totals of its slots (kernels.h: Totals)
     DevBuf<uint16_t> bucket;                            // targets bucketed by bin tile (13-bit bin | unique bit)

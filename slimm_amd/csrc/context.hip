@@ -176,6 +176,12 @@ int slimm_create(const slimm_config* cfg, slimm_ctx** out) {
     // into per-taxon ones (kernels.h: PackArgs::sum_k).  No taxon look-up, one dependent round trip less, on k_filter's
     // path.  With the 32-byte rows the selector is the dense taxon itself.
     {
+        // the targets' reference words: 16 bits (15 of reference, the head flag) where every reference fits them
+        long r16 = 1;
+        (void)forced("ref16", &r16);
+        c->ref16 = c->R <= kRef16Max && r16 != 0;
+    }
+    {
         c->use_rows16 = c->host->rows16_ok() && !forced("wide_rows");
         c->Tsel = c->T;
         if (c->use_rows16) {
@@ -557,13 +563,13 @@ int slimm_analyze_alignments(slimm_ctx* c) {
         }
         {
             KernelTimer t(c, K_FRONT);
-            launch_front_sorted(st, n, c->c_ident.p, c->c_pay.p, c->counters.p, c->tgt_ref.p, c->tgt_gbin.p, c->slots.p,
+            launch_front_sorted(st, n, c->c_ident.p, c->c_pay.p, c->counters.p, c->target_refs(), c->tgt_gbin.p, c->slots.p,
                                 c->rec.check ? c->c_chk.p : nullptr);
         }
     } else {
         // grouped input: one pass straight over the caller's record arrays
         KernelTimer t(c, K_FRONT, true);
-        launch_front_raw(st, c->rec, c->R, c->d_geo.p, half_read, hc.bin_width, c->counters.p, c->tgt_ref.p, c->tgt_gbin.p,
+        launch_front_raw(st, c->rec, c->R, c->d_geo.p, half_read, hc.bin_width, c->counters.p, c->target_refs(), c->tgt_gbin.p,
                          c->slots.p, t.t0(), t.t1());
     }
     // Where every slot's reads start among all reads (for k_filter's dense selectors): two small launches on a side
@@ -949,7 +955,7 @@ int filter_launch(slimm_ctx* c, bool copy_rows) {
     {
         KernelTimer t(c, K_FILTER, true);  // (the dispatch's own time stamps, like k_front)
         FilterArgs fa;
-        fa.tgt_ref = c->tgt_ref.p;
+        fa.tgt_ref = c->target_refs();
         fa.tgt_gbin = c->tgt_gbin.p;
         fa.slots = c->slots.p;
         fa.nslots = nslots;
@@ -1413,16 +1419,25 @@ int slimm_get_read_targets(slimm_ctx* c, uint32_t* ref, uint32_t* gbin, uint64_t
     if (!ref && !gbin) return SLIMM_OK;
     if (cap < total) return fail(c, SLIMM_E_INVALID, "slimm_get_read_targets: %llu entries, room for %llu",
                                  static_cast<unsigned long long>(total), static_cast<unsigned long long>(cap));
+    std::vector<uint16_t> ref16(ref && c->ref16 ? total : 0);
     uint64_t o = 0;
     for (const uint4& d : sl) {  // (a slot's targets are contiguous; runs of slots are too when nothing was dropped)
         if (!d.y) continue;
-        if (ref) HIP_TRY(c, hipMemcpyAsync(ref + o, c->tgt_ref.p + d.x, d.y * 4ull, hipMemcpyDeviceToHost, c->stream));
+        if (ref && c->ref16)  // (widened below)
+            HIP_TRY(c, hipMemcpyAsync(ref16.data() + o, reinterpret_cast<const uint16_t*>(c->tgt_ref.p) + d.x, d.y * 2ull,
+                                      hipMemcpyDeviceToHost, c->stream));
+        else if (ref)
+            HIP_TRY(c, hipMemcpyAsync(ref + o, c->tgt_ref.p + d.x, d.y * 4ull, hipMemcpyDeviceToHost, c->stream));
         if (gbin) HIP_TRY(c, hipMemcpyAsync(gbin + o, c->tgt_gbin.p + d.x, d.y * 4ull, hipMemcpyDeviceToHost, c->stream));
         o += d.y;
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (ref && c->ref16)  // the caller sees the 32-bit form: reference | first of its read << 31
+        for (uint64_t k = 0; k < total; ++k) ref[k] = (ref16[k] & 0x7fffu) | ((ref16[k] & 0x8000u) << 16);
     return SLIMM_OK;
 }
+
+int slimm_target_ref_bits(slimm_ctx* c) { return c ? (c->ref16 ? 16 : 32) : SLIMM_E_INVALID; }
 
 int slimm_taxon_count_size(slimm_ctx* c, int stage, uint32_t* n) {
     if (!c || !n) return SLIMM_E_INVALID;

@@ -26,6 +26,8 @@
 //   told), zstd_cut_search=N (slimm_host_zstd_ranges gives a cut up N bytes behind its target: 64 MiB unless told),
 //   zstd_split_wrong_cut (the planner's second cut -- of two members: its only one -- lands one byte late, where no frame
 //   starts: the members or the stitch must refuse it)   tests/test_gpu_split_zstd_sam.py, tests/test_cli_split_input_zstd.py
+//   ref16=0 (the targets' reference words stay 32 bits wide on a database of at most 32 768 references, which takes the
+//   16-bit form otherwise: kernels.h, TargetRefs)                                    tests/test_gpu_ref16.py
 #pragma once
 #include <cstdlib>
 #include <cstring>

@@ -35,9 +35,11 @@
 //            rotation (quadratic in the run length, without any limit on it), one pass per mate number when the run's
 //            mates interleave
 //
-// Output (all 32-bit):
-//   tgt_ref [p]  reference id | bit 31: first target of its read
-//   tgt_gbin[p]  global bin (bin_off[ref] + bin) | bit 31: the read has exactly one target (src/slimm.hpp:224)
+// Output:
+//   tgt_ref [p]  reference id | top bit: first target of its read -- 32 bits wide, or 16 (reference in bits 0-14, the
+//                flag in bit 15; 0xffff is reference 32767 heading its read, no sentinel) when the database has at most
+//                kRef16Max references (context.hip chooses; the kernels' RefT): 6 bytes written per target for 8
+//   tgt_gbin[p]  32 bits: global bin (bin_off[ref] + bin) | bit 31: the read has exactly one target (src/slimm.hpp:224)
 //   slots   [s]  {start, targets, reads, mapped records} of slot s
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -104,6 +106,11 @@ __device__ __forceinline__ uint64_t f_below(uint32_t n) {  // lanes 0 .. n-1 (n 
 __device__ __forceinline__ uint64_t f_first_after(uint64_t starts, uint64_t bits, uint64_t stops) {
     const uint64_t ones = ~bits & ~stops;
     return (ones + starts) & ~ones & bits;
+}
+// "first target of its read" in a target's reference word of type RefT: its top bit
+template <typename RefT>
+__device__ __forceinline__ uint32_t f_head_bit(bool head) {
+    return head ? 1u << (8u * sizeof(RefT) - 1u) : 0u;
 }
 
 
@@ -435,8 +442,9 @@ static_assert(kHashWalk == 16 || kHashWalk == 24 || kHashWalk == 32 || kHashWalk
 // fast path: the lanes PR = [0, X) of the window hold whole runs whose mates never decrease.  field = the staged reference
 // field, SS = segment starts (run starts and mate changes; lane 0 is one), V = mapped lanes, both inside PR.
 // ---------------------------------------------------------------------------------------------------------
+template <typename RefT>
 __device__ __forceinline__ void window_fast(uint32_t field, uint32_t gbin, uint32_t lane, uint64_t SS, uint64_t V, uint64_t PR,
-                                            WinOut& so, uint32_t* __restrict__ tgt_ref, uint32_t* __restrict__ tgt_gbin,
+                                            WinOut& so, RefT* __restrict__ tgt_ref, uint32_t* __restrict__ tgt_gbin,
                                             uint32_t* tab) {
     // Q1: an earlier lane of my segment with my reference?  T = {segment number, field} is never zero and equal only
     // inside a segment; x_d[i] = T[i - d] ^ T[i] (T of the lanes in front of lane 0 taken as zero) follows from
@@ -502,7 +510,8 @@ __device__ __forceinline__ void window_fast(uint32_t field, uint32_t gbin, uint3
         // (the index in a vector register: the scalar unit is the kernel's bottleneck, and a scalar base per array costs
         // it two 64-bit adds and a shift per window)
         const uint32_t p = so.base + so.nf + f_rank(F);
-        tgt_ref[p] = (field - 1u) + (f_bit(H) ? 0x80000000u : 0u);  // (a reference has 26 bits: one three-operand add)
+        // (a reference has 26 bits -- 15 in the 16-bit form: one three-operand add)
+        tgt_ref[p] = static_cast<RefT>((field - 1u) + f_head_bit<RefT>(f_bit(H)));
         tgt_gbin[p] = gbin | (uniq ? 0x80000000u : 0u);
     }
     so.nf += static_cast<uint32_t>(__popcll(F));
@@ -514,8 +523,9 @@ __device__ __forceinline__ void window_fast(uint32_t field, uint32_t gbin, uint3
 // general path: mates interleave inside some run of the window.  Per-lane walks over the run by lane shuffles; the
 // targets of a run are written ordered by (mate, file order), so a read's targets stay contiguous.
 // ---------------------------------------------------------------------------------------------------------
+template <typename RefT>
 __device__ __forceinline__ void window_general(const Staged& rec, uint32_t lane, uint64_t RS, uint64_t V, uint32_t X,
-                                               WinOut& so, uint32_t* __restrict__ tgt_ref,
+                                               WinOut& so, RefT* __restrict__ tgt_ref,
                                                uint32_t* __restrict__ tgt_gbin) {
     const bool in_pr = lane < X;
     const bool use = f_bit(V);
@@ -554,7 +564,7 @@ __device__ __forceinline__ void window_general(const Staged& rec, uint32_t lane,
         // targets of the runs before mine in this window, then my place inside my run
         const uint32_t before_run = static_cast<uint32_t>(__popcll(F & ((1ull << run_from) - 1ull)));
         const uint32_t p = so.base + so.nf + before_run + smaller + same_before;
-        tgt_ref[p] = rec.ref | (head ? 0x80000000u : 0u);
+        tgt_ref[p] = static_cast<RefT>(rec.ref | f_head_bit<RefT>(head));
         tgt_gbin[p] = rec.gbin | ((head && same_total == 1u) ? 0x80000000u : 0u);
     }
     so.nf += static_cast<uint32_t>(__popcll(F));
@@ -567,9 +577,9 @@ __device__ __forceinline__ void window_general(const Staged& rec, uint32_t lane,
 // with the chunk's earlier lanes (shift) and with every earlier chunk of the run (64 rotations each).  Returns the index
 // of the record behind the run.
 // ---------------------------------------------------------------------------------------------------------
-template <bool kChk, typename Acc>
+template <bool kChk, typename Acc, typename RefT>
 __device__ __forceinline__ uint32_t long_run(const Acc& acc, uint32_t pos, uint32_t N, uint32_t lane, WinOut& so,
-                                          uint32_t* __restrict__ tgt_ref, uint32_t* __restrict__ tgt_gbin, bool& bad,
+                                          RefT* __restrict__ tgt_ref, uint32_t* __restrict__ tgt_gbin, bool& bad,
                                           bool& collide, uint32_t* tab) {
     // 1. where the run ends, whether its mates ever decrease
     uint32_t klo0, khi0;
@@ -665,7 +675,7 @@ __device__ __forceinline__ uint32_t long_run(const Acc& acc, uint32_t pos, uint3
                 const FrontRaw3 rw{0u, first ? r.ref : 0u, 0u};
                 const uint32_t g = first ? acc.gbin(r, acc.geo_of(rw)) : 0u;
                 if (first) {
-                    tgt_ref[p] = r.ref | (head ? 0x80000000u : 0u);
+                    tgt_ref[p] = static_cast<RefT>(r.ref | f_head_bit<RefT>(head));
                     if (!head) tgt_gbin[p] = g;  // a head's bin word waits for the end of the run (unique or not)
                 }
                 uint64_t Hm = H;
@@ -712,8 +722,9 @@ __device__ __forceinline__ uint32_t next_run_start(const uint32_t* st1, uint32_t
 // more distinct (mate, reference) pairs than the table does: the caller then takes long_run, which can fall back to
 // the comparison walk.  `so` is unchanged in that case.
 // ---------------------------------------------------------------------------------------------------------
+template <typename RefT>
 __device__ __forceinline__ bool long_run_staged(const uint32_t* st1, const uint32_t* st2, uint32_t off, uint32_t end_off,
-                                                uint32_t lane, WinOut& so, uint32_t* __restrict__ tgt_ref,
+                                                uint32_t lane, WinOut& so, RefT* __restrict__ tgt_ref,
                                                 uint32_t* __restrict__ tgt_gbin, uint32_t* tab) {
     // 1. mapper output: the run's mates never decrease (all of mate 1, then all of mate 2), a read is a stretch of the run.
     // ONE pass that says so on the way; heads and the targets per mate by mask arithmetic on two ballots.
@@ -758,7 +769,7 @@ __device__ __forceinline__ bool long_run_staged(const uint32_t* st1, const uint3
             const bool head = f_bit(H);
             const uint32_t p = so.base + so.nf + f_rank(F);
             if (first) {
-                tgt_ref[p] = (field - 1u) | (head ? 0x80000000u : 0u);
+                tgt_ref[p] = static_cast<RefT>((field - 1u) | f_head_bit<RefT>(head));
                 if (!head) tgt_gbin[p] = g;  // a head's bin word waits for the end of the run (unique or not)
             }
             uint64_t Hm = H;
@@ -818,7 +829,7 @@ __device__ __forceinline__ bool long_run_staged(const uint32_t* st1, const uint3
             const bool head = f_bit(H);
             const uint32_t p = so.base + so.nf + f_rank(F);
             if (first) {
-                tgt_ref[p] = (field - 1u) | (head ? 0x80000000u : 0u);
+                tgt_ref[p] = static_cast<RefT>((field - 1u) | f_head_bit<RefT>(head));
                 if (!head) tgt_gbin[p] = g;  // a head's bin word waits for the end of the run (unique or not)
             }
             uint64_t Hm = H;
@@ -939,9 +950,9 @@ __device__ __forceinline__ void stage_slot(const Acc& acc, uint32_t B, uint32_t 
 // ---------------------------------------------------------------------------------------------------------
 // k_front
 // ---------------------------------------------------------------------------------------------------------
-template <typename Acc, bool kChk>
+template <typename Acc, bool kChk, typename RefT>
 __global__ __launch_bounds__(kFrontBlock, 4) void k_front(const Acc acc, uint32_t nslots, uint32_t* __restrict__ counters,
-                                                       uint32_t* __restrict__ tgt_ref, uint32_t* __restrict__ tgt_gbin,
+                                                       RefT* __restrict__ tgt_ref, uint32_t* __restrict__ tgt_gbin,
                                                        uint4* __restrict__ slots) {
     __shared__ uint32_t s_stage[kFrontBlock / 64][2][kStageRecs];
     __shared__ __attribute__((aligned(16))) uint32_t s_tab[kFrontBlock / 64][2 * kHashSlots];  // hash_first's table, one per wave
@@ -1011,7 +1022,7 @@ __global__ __launch_bounds__(kFrontBlock, 4) void k_front(const Acc acc, uint32_
                     if ((f_ballot(mate < mprev) & ~RS & PR) == 0ull) {
                         window_fast(field, w2, lane, (RS | f_ballot(mate != mprev)) & PR, V, PR, so, tgt_ref, tgt_gbin, tab);
                     } else {  // (mates interleave: the window's targets are not in lane order)
-                        window_general(Staged{mate, field - 1u, w2, f_bit(V)}, lane, RS, V, X, so, tgt_ref, tgt_gbin);
+                        window_general<RefT>(Staged{mate, field - 1u, w2, f_bit(V)}, lane, RS, V, X, so, tgt_ref, tgt_gbin);
                     }
                     off += X;
                 } else {
@@ -1023,7 +1034,7 @@ __global__ __launch_bounds__(kFrontBlock, 4) void k_front(const Acc acc, uint32_
                     if (end_off < kStageRecs && long_run_staged(st1, st2, off, end_off, lane, so, tgt_ref, tgt_gbin, tab)) {
                         off = end_off;
                     } else {
-                        const uint32_t end = long_run<kChk>(acc, pos, N, lane, so, tgt_ref, tgt_gbin, bad, collide, tab);
+                        const uint32_t end = long_run<kChk, Acc, RefT>(acc, pos, N, lane, so, tgt_ref, tgt_gbin, bad, collide, tab);
                         __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0): this path's loads stay out of the other windows' waits
                         off = end - B < kStageRecs ? next_run_start(st1, lane, end - B) : kStageRecs;
                     }
@@ -1056,8 +1067,22 @@ static uint32_t front_grid(uint32_t nslots) {
     return std::max(1u, blocks);
 }
 
+// the kernel of one record source, in the width of the targets' reference words (TargetRefs::ref16)
+template <typename Acc, bool kChk>
+static void front_launch(hipStream_t st, const Acc& a, uint32_t ns, uint32_t* counters, TargetRefs tgt_ref, uint32_t* tgt_gbin,
+                         uint4* slots, hipEvent_t t0, hipEvent_t t1) {
+    // (t0 / t1, when given: the dispatch's own start and end time stamps -- what rocprofv3 reports as the kernel's
+    // duration; events recorded around the launch add the 4 - 6 us it takes a dependent dispatch to start)
+    if (tgt_ref.ref16)
+        hipExtLaunchKernelGGL((k_front<Acc, kChk, uint16_t>), dim3(front_grid(ns)), dim3(kFrontBlock), 0, st, t0, t1, 0, a, ns,
+                              counters, static_cast<uint16_t*>(tgt_ref.p), tgt_gbin, slots);
+    else
+        hipExtLaunchKernelGGL((k_front<Acc, kChk, uint32_t>), dim3(front_grid(ns)), dim3(kFrontBlock), 0, st, t0, t1, 0, a, ns,
+                              counters, static_cast<uint32_t*>(tgt_ref.p), tgt_gbin, slots);
+}
+
 void launch_front_raw(hipStream_t st, const DeviceRecords& in, uint32_t n_refs, const uint2* geo, uint32_t half_read,
-                      uint32_t bin_width, uint32_t* counters, uint32_t* tgt_ref, uint32_t* tgt_gbin, uint4* slots,
+                      uint32_t bin_width, uint32_t* counters, TargetRefs tgt_ref, uint32_t* tgt_gbin, uint4* slots,
                       hipEvent_t t0, hipEvent_t t1) {
     const uint32_t ns = front_slots(in.n);
     if (!ns) return;
@@ -1073,8 +1098,6 @@ void launch_front_raw(hipStream_t st, const DeviceRecords& in, uint32_t n_refs, 
     a.half_read = half_read;
     a.bin_width = bin_width;
     a.bw_magic = bin_width ? 0xffffffffu / bin_width : 0u;
-    // (t0 / t1, when given: the dispatch's own start and end time stamps -- what rocprofv3 reports as the kernel's
-    // duration; events recorded around the launch add the 4 - 6 us it takes a dependent dispatch to start)
     if (in.marked) {
         FrontMarked m;
         m.word = reinterpret_cast<const uint32_t*>(in.ref);
@@ -1085,38 +1108,31 @@ void launch_front_raw(hipStream_t st, const DeviceRecords& in, uint32_t n_refs, 
         m.half_read = half_read;
         m.bin_width = bin_width;
         m.bw_magic = a.bw_magic;
-        hipExtLaunchKernelGGL((k_front<FrontMarked, false>), dim3(front_grid(ns)), dim3(kFrontBlock), 0, st, t0, t1, 0, m, ns,
-                              counters, tgt_ref, tgt_gbin, slots);
+        front_launch<FrontMarked, false>(st, m, ns, counters, tgt_ref, tgt_gbin, slots, t0, t1);
     } else if (in.packed) {  // (same members, other accessors)
         FrontPacked b;
         b.key = a.key, b.ref = a.ref, b.pos = a.pos, b.flag = nullptr, b.check = a.check, b.geo = a.geo, b.n = a.n;
         b.n_refs = a.n_refs, b.half_read = a.half_read, b.bin_width = a.bin_width, b.bw_magic = a.bw_magic;
         if (in.check)
-            hipExtLaunchKernelGGL((k_front<FrontPacked, true>), dim3(front_grid(ns)), dim3(kFrontBlock), 0, st, t0, t1, 0, b, ns,
-                                  counters, tgt_ref, tgt_gbin, slots);
+            front_launch<FrontPacked, true>(st, b, ns, counters, tgt_ref, tgt_gbin, slots, t0, t1);
         else
-            hipExtLaunchKernelGGL((k_front<FrontPacked, false>), dim3(front_grid(ns)), dim3(kFrontBlock), 0, st, t0, t1, 0, b, ns,
-                                  counters, tgt_ref, tgt_gbin, slots);
+            front_launch<FrontPacked, false>(st, b, ns, counters, tgt_ref, tgt_gbin, slots, t0, t1);
     } else if (in.check)
-        hipExtLaunchKernelGGL((k_front<FrontRaw, true>), dim3(front_grid(ns)), dim3(kFrontBlock), 0, st, t0, t1, 0, a, ns,
-                              counters, tgt_ref, tgt_gbin, slots);
+        front_launch<FrontRaw, true>(st, a, ns, counters, tgt_ref, tgt_gbin, slots, t0, t1);
     else
-        hipExtLaunchKernelGGL((k_front<FrontRaw, false>), dim3(front_grid(ns)), dim3(kFrontBlock), 0, st, t0, t1, 0, a, ns,
-                              counters, tgt_ref, tgt_gbin, slots);
+        front_launch<FrontRaw, false>(st, a, ns, counters, tgt_ref, tgt_gbin, slots, t0, t1);
 }
 
 void launch_front_sorted(hipStream_t st, uint32_t n_upper, const uint64_t* ident, const uint2* pay,
-                         uint32_t* counters, uint32_t* tgt_ref, uint32_t* tgt_gbin, uint4* slots,
+                         uint32_t* counters, TargetRefs tgt_ref, uint32_t* tgt_gbin, uint4* slots,
                          const uint32_t* cchk) {
     const uint32_t ns = front_slots(n_upper);
     if (!ns) return;
     FrontSorted a{ident, pay, cchk};
     if (cchk)
-        hipLaunchKernelGGL((k_front<FrontSorted, true>), dim3(front_grid(ns)), dim3(kFrontBlock), 0, st, a, ns, counters, tgt_ref,
-                           tgt_gbin, slots);
+        front_launch<FrontSorted, true>(st, a, ns, counters, tgt_ref, tgt_gbin, slots, nullptr, nullptr);
     else
-        hipLaunchKernelGGL((k_front<FrontSorted, false>), dim3(front_grid(ns)), dim3(kFrontBlock), 0, st, a, ns, counters,
-                           tgt_ref, tgt_gbin, slots);
+        front_launch<FrontSorted, false>(st, a, ns, counters, tgt_ref, tgt_gbin, slots, nullptr, nullptr);
 }
 
 }  // namespace slimm

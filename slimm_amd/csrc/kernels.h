@@ -111,7 +111,7 @@ struct DeviceRecords {
 
 // ---- front.hip: the single-pass front end of phase A ----
 // A slot = kSlotRecs consecutive records; its targets (the runs that START in it) lie compacted at
-// [slot.x, slot.x + slot.y) of tgt_ref / tgt_gbin; slot.z = reads (targets with bit 31 of tgt_ref), slot.w = mapped records
+// [slot.x, slot.x + slot.y) of tgt_ref / tgt_gbin; slot.z = reads (targets with the top bit of tgt_ref), slot.w = mapped records
 // 768 records: measured, not derived.  k_front by slot size at 1 B records / config 2 / config 5 (one box, four waves per
 // SIMD throughout): 1088: 5 075 / 73 / 753 us, 1024: 5 141 / 76 / 757, 896: 5 283 / 74 / 769, 832: 5 061-5 144 / 77 / 726,
 // 768: 4 934-4 989 / 69 / 683, 704: 4 973 / 67 / 684, 640: 5 034 / 67 / 686, 512: 5 141 / 67 / 704 -- while every consumer
@@ -121,12 +121,20 @@ constexpr uint32_t kSlotRecs = 768;
 constexpr int kFrontBlock = 64;   // one slot, one wave, one workgroup: the dispatcher backfills wave by wave (config 3: 594 -> 549 us)
 constexpr uint32_t kMaxRefs = (1u << 26) - 2u;      // reference id + 1 fits 26 bits and is not all ones (front.hip)
 constexpr uint32_t kMaxBins = 0x7ffffff0u;          // global bin indices fit 31 bits (bit 31 of tgt_gbin: unique read)
+// A target's reference word: the reference, and in its top bit "first target of its read".  16 bits wide when the
+// database's references fit 15 (slimm_create decides, SLIMM_FORCE ref16=0 says no): k_front writes 2 bytes less per target
+// and k_filter_compact reads 2 less.  Every value of the 16 bits is a word (0xffff: reference 32767 heading its read).
+constexpr uint32_t kRef16Max = 1u << 15;            // references at most for the 16-bit form
+struct TargetRefs {
+    void* p = nullptr;     // uint16_t[] when ref16, uint32_t[] otherwise (one allocation, sized for the wider)
+    bool ref16 = false;
+};
 uint32_t front_slots(uint32_t n_records);
 void launch_front_raw(hipStream_t st, const DeviceRecords& in, uint32_t n_refs, const uint2* geo, uint32_t half_read,
-                      uint32_t bin_width, uint32_t* counters, uint32_t* tgt_ref, uint32_t* tgt_gbin, uint4* slots,
+                      uint32_t bin_width, uint32_t* counters, TargetRefs tgt_ref, uint32_t* tgt_gbin, uint4* slots,
                       hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);  // t0 / t1: the dispatch's time stamps
 void launch_front_sorted(hipStream_t st, uint32_t n_upper, const uint64_t* ident, const uint2* pay,
-                         uint32_t* counters, uint32_t* tgt_ref, uint32_t* tgt_gbin, uint4* slots,
+                         uint32_t* counters, TargetRefs tgt_ref, uint32_t* tgt_gbin, uint4* slots,
                          const uint32_t* cchk = nullptr);  // pay: {reference, global bin}; cchk: check words (equal keys must carry equal ones)
 
 // diagnostic: run starts whose identity (key & id_mask) started an earlier run too; tab: (tab_mask + 1) words of ~0
@@ -144,7 +152,7 @@ void launch_ref_stats(hipStream_t st, const uint32_t* a, const uint32_t* b, cons
 // of the reads whose references agree at no level.  rows16 != nullptr: 16-byte lineage rows (level_off: host array of 8
 // offsets into level_taxon); otherwise 32-byte rows lin_dense + the byte array valid.
 struct FilterArgs {
-    const uint32_t* tgt_ref = nullptr;
+    TargetRefs tgt_ref;
     const uint32_t* tgt_gbin = nullptr;
     const uint4* slots = nullptr;
     uint32_t nslots = 0;

@@ -5,7 +5,7 @@
 // Layout (all SoA, 32-bit indices; one context handles < 2^31 records):
 //   records   key u64 | ref i32 | pos i32 | flag u16               (what the reference reads per BamAlignmentRecord)
 //   grouped   ident u64 | {ref u32, gbin u32}                      (record_order = ANY: mapped records, a read's adjacent)
-//   targets   tgt_ref u32 (bit31 = first target of its read) | tgt_gbin u32   (CSR over reads: read_off u32[M+1])
+//   targets   tgt_ref u32 or u16 (top bit = first target of its read, TgtWord) | tgt_gbin u32   (CSR over reads: read_off u32[M+1])
 //   bins      cov[Bp] | uniq_cov[Bp] | tail[64] | uniq_cov2[Bp]    (u32; each reference padded to a multiple of 4 bins)
 //
 // Reference semantics implemented here:
@@ -24,6 +24,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "kernels.h"
 
@@ -376,17 +377,27 @@ __device__ __forceinline__ void read_children(const FilterOut& out, bool mine, u
 // permute), per level one ballot says which lanes differ from it, and the first valid lane of each read -- its owner --
 // finds the first level at which no lane between itself and the next read's head does.  The owners' taxa are ONE gather
 // per window, left to the caller (Lookup) so that the gathers of a batch of windows are in flight together.
+// A target's reference word as the front end wrote it, RefT = uint32_t or uint16_t (kernels.h: TargetRefs), zero-extended
+// into a register: the reference below the top bit of RefT, "first target of its read" in it.  kHead alone is what a lane
+// without a target takes where it must read as a head.
+template <typename RefT>
+struct TgtWord {
+    static constexpr uint32_t kShift = 8u * sizeof(RefT) - 1u;
+    static constexpr uint32_t kHead = 1u << kShift;
+    static constexpr uint32_t kRefMask = kHead - 1u;
+};
+
 struct Lookup {
     uint64_t q4;     // first valid lanes of the reads on whose targets no level agrees (quirk Q4): left to filter_q4
 };
 
-template <typename Rows>
+template <typename RefT, typename Rows>
 __device__ __forceinline__ Lookup filter_window(const Rows& rows, const FilterOut& out, uint32_t lane, uint32_t X, uint32_t w,
                                                 uint32_t g, const typename Rows::Row& row, uint64_t valid_lanes,
                                                 uint32_t sel_base) {
     const uint64_t PR = k_below(X);
-    const uint64_t H = k_ballot((w >> 31) != 0u) & PR;  // (bit 0 is set: a window starts at a read's first target)
-    const uint32_t ref = w & 0x7fffffffu;
+    const uint64_t H = k_ballot((w >> TgtWord<RefT>::kShift) != 0u) & PR;  // (bit 0 is set: a window starts at a read's first target)
+    const uint32_t ref = w & TgtWord<RefT>::kRefMask;
     const uint64_t VB = valid_lanes & PR;               // valid_lanes = k_ballot(Rows::valid(row)), taken by the caller
     const uint64_t stops = (H >> 1) | (1ull << (X - 1u));
     const uint64_t FV = k_first_after(H, VB, stops);              // first valid target of every read
@@ -448,12 +459,12 @@ __device__ __forceinline__ Lookup filter_window(const Rows& rows, const FilterOu
 // with this path's loads and loops inside it, the compiler no longer knows how many memory operations are under way
 // where the paths join and makes every window wait for all of them (s_waitcnt vmcnt(0): the stores of the window
 // before, the loads asked for ahead).
-template <typename Rows>
+template <typename RefT, typename Rows>
 __device__ __forceinline__ void filter_q4(const Rows& rows, const FilterOut& out, uint32_t lane, uint32_t X, uint32_t w,
                                           const typename Rows::Row& row, uint64_t valid_lanes, uint32_t sel_base, uint64_t Q4) {
     const uint64_t PR = k_below(X);
-    const uint64_t H = k_ballot((w >> 31) != 0u) & PR;
-    const uint32_t ref = w & 0x7fffffffu;
+    const uint64_t H = k_ballot((w >> TgtWord<RefT>::kShift) != 0u) & PR;
+    const uint32_t ref = w & TgtWord<RefT>::kRefMask;
     const uint64_t VB = valid_lanes & PR;
     uint32_t f[8];
     Rows::fields(row, f);
@@ -475,30 +486,31 @@ __device__ __forceinline__ void filter_q4(const Rows& rows, const FilterOut& out
 }
 
 // ... and the same with the owners' taxa looked up at once (the windows of filter_span, one at a time)
-template <typename Rows>
+template <typename RefT, typename Rows>
 __device__ __forceinline__ void filter_window_now(const Rows& rows, const FilterOut& out, uint32_t lane, uint32_t X, uint32_t w,
                                                   uint32_t g, const typename Rows::Row& row, uint32_t sel_base) {
     const uint64_t vb = k_ballot(Rows::valid(row));
-    const Lookup lk = filter_window(rows, out, lane, X, w, g, row, vb, sel_base);
-    if (lk.q4) filter_q4(rows, out, lane, X, w, row, vb, sel_base, lk.q4);
+    const Lookup lk = filter_window<RefT>(rows, out, lane, X, w, g, row, vb, sel_base);
+    if (lk.q4) filter_q4<RefT>(rows, out, lane, X, w, row, vb, sel_base, lk.q4);
 }
 
 // The targets [pos, endp) -- whole reads, any number of them, reads of 64 targets and more among them -- one window
 // after the other (what a run of 64 records or more leaves behind, front.hip).
-template <typename Rows>
-__device__ __forceinline__ void filter_span(const Rows& rows, const FilterOut& out, const uint32_t* __restrict__ tgt_ref,
+template <typename Rows, typename RefT>
+__device__ __forceinline__ void filter_span(const Rows& rows, const FilterOut& out, const RefT* __restrict__ tgt_ref,
                                          const uint32_t* __restrict__ tgt_gbin, uint32_t lane, uint32_t pos, uint32_t endp,
                                          uint32_t sel_base) {
+    using TW = TgtWord<RefT>;
     while (pos < endp) {
         const uint32_t n_live = min(64u, endp - pos);
         const bool live = lane < n_live;
         const uint32_t w = live ? tgt_ref[pos + lane] : 0u;
         const uint32_t g = live ? tgt_gbin[pos + lane] : 0u;
-        const uint64_t HB = k_ballot((w >> 31) != 0u) & k_below(n_live);
+        const uint64_t HB = k_ballot((w >> TW::kShift) != 0u) & k_below(n_live);
         const uint32_t X = pos + 64u >= endp ? n_live : 63u - static_cast<uint32_t>(__builtin_clzll(HB | 1ull));
         if (X != 0u) {
-            const typename Rows::Row row = rows.load(lane < X ? (w & 0x7fffffffu) : 0u);
-            filter_window_now(rows, out, lane, X, w, g, row, sel_base);
+            const typename Rows::Row row = rows.load(lane < X ? (w & TW::kRefMask) : 0u);
+            filter_window_now<RefT>(rows, out, lane, X, w, g, row, sel_base);
             sel_base += static_cast<uint32_t>(__popcll(HB & k_below(X)));
             pos += X;
             continue;
@@ -509,12 +521,12 @@ __device__ __forceinline__ void filter_span(const Rows& rows, const FilterOut& o
         uint32_t e = pos;  // end of the read
         while (true) {
             const bool in = e + lane < endp;
-            const uint32_t ww = in ? tgt_ref[e + lane] : 0x80000000u;
+            const uint32_t ww = in ? tgt_ref[e + lane] : TW::kHead;
             const uint32_t gg = in ? tgt_gbin[e + lane] : 0u;
-            uint64_t heads = k_ballot((ww >> 31) != 0u);
+            uint64_t heads = k_ballot((ww >> TW::kShift) != 0u);
             if (e == pos) heads &= ~1ull;
             const uint32_t n_in = heads ? static_cast<uint32_t>(__builtin_ctzll(heads)) : 64u;
-            const uint32_t rr = ww & 0x7fffffffu;
+            const uint32_t rr = ww & TW::kRefMask;
             const typename Rows::Row row = rows.load(lane < n_in ? rr : 0u);
             uint32_t f[8];
             Rows::fields(row, f);
@@ -533,7 +545,7 @@ __device__ __forceinline__ void filter_span(const Rows& rows, const FilterOut& o
             sel = out.taxon_base + index;
             for (uint32_t c = pos; c < e; c += 64u) {
                 const bool in = c + lane < e;
-                const uint32_t rr = in ? (tgt_ref[c + lane] & 0x7fffffffu) : 0u;
+                const uint32_t rr = in ? (tgt_ref[c + lane] & TW::kRefMask) : 0u;
                 const typename Rows::Row row = rows.load(rr);
                 read_children(out, in && Rows::valid(row), rr, lv, taxon);
             }
@@ -571,9 +583,9 @@ constexpr uint32_t kFcBatch = 4;                   // chunks of 64 targets per t
 // 8 waves per SIMD the kernel has 78 of them, and with every argument held from the kernel's start it spilled 29 into the
 // lanes of a vector register, reloaded per batch, per chunk and per window.  (With the argument segment's address pinned
 // in the rare blocks the compiler also reads the window path's fields -- rows, marks, taxon_base -- where the windows are.)
-template <typename Rows>
+template <typename Rows, typename RefT>
 struct FilterKernArgs {
-    const uint32_t* tgt_ref;
+    const RefT* tgt_ref;   // (16-bit words: 2 of the 8 bytes per target are not read)
     const uint32_t* tgt_gbin;
     const uint4* slots;
     const uint32_t* valid_bits;
@@ -596,10 +608,11 @@ __device__ __forceinline__ T kernarg_now(const Args& args, size_t offset) {
     return v;
 }
 
-template <typename Rows>
-__device__ __forceinline__ void compact_window(const FilterKernArgs<Rows>& ka, uint32_t lane, uint32_t X, uint64_t Hc,
+template <typename Rows, typename RefT>
+__device__ __forceinline__ void compact_window(const FilterKernArgs<Rows, RefT>& ka, uint32_t lane, uint32_t X, uint64_t Hc,
                                                uint32_t cref, uint32_t cg, uint32_t cr, const typename Rows::Row& row,
                                                uint32_t* __restrict__ s_sel) {
+    using KA = FilterKernArgs<Rows, RefT>;
     const Rows& rows = ka.rows;
     const FilterOut& out = ka.out;
     const uint64_t PR = k_below(X);
@@ -635,8 +648,8 @@ __device__ __forceinline__ void compact_window(const FilterKernArgs<Rows>& ka, u
         const uint32_t lv_read = __builtin_amdgcn_ds_bpermute(fvl << 2, lv);
         if (k_bit(PR & ~single) && lv_read < 8u) out.marks[cref * kMarkBytes + lv_read] = 1;  // plain, idempotent byte store
         if (__builtin_expect(Q4 != 0ull, 0)) {
-            const Rows rows_q = kernarg_now<Rows>(ka, offsetof(FilterKernArgs<Rows>, rows));
-            const FilterOut out_q = kernarg_now<FilterOut>(ka, offsetof(FilterKernArgs<Rows>, out));
+            const Rows rows_q = kernarg_now<Rows>(ka, offsetof(KA, rows));
+            const FilterOut out_q = kernarg_now<FilterOut>(ka, offsetof(KA, out));
             uint32_t f[8];
             Rows::fields(row, f);
             uint64_t todo = Q4;
@@ -659,9 +672,11 @@ __device__ __forceinline__ void compact_window(const FilterKernArgs<Rows>& ka, u
     }
 }
 
-template <typename Rows>
-__global__ __launch_bounds__(64, 8) void k_filter_compact(const FilterKernArgs<Rows> ka) {
-    const uint32_t* __restrict__ const tgt_ref = ka.tgt_ref;
+template <typename Rows, typename RefT>
+__global__ __launch_bounds__(64, 8) void k_filter_compact(const FilterKernArgs<Rows, RefT> ka) {
+    using KA = FilterKernArgs<Rows, RefT>;
+    using TW = TgtWord<RefT>;
+    const RefT* __restrict__ const tgt_ref = ka.tgt_ref;
     const uint32_t* __restrict__ const tgt_gbin = ka.tgt_gbin;
     const uint32_t* __restrict__ const valid_bits = ka.valid_bits;
     __shared__ uint32_t s_ref[kFcRing], s_g[kFcRing], s_r[kFcRing];
@@ -685,7 +700,8 @@ __global__ __launch_bounds__(64, 8) void k_filter_compact(const FilterKernArgs<R
     uint32_t wn[kFcBatch], gn[kFcBatch];
     auto ask = [&](uint32_t t) {
         if (t + 64u * kFcBatch <= tend) {   // a full batch: one base per array, the chunks at constant offsets
-            const uint32_t *pr = tgt_ref + t, *pg = tgt_gbin + t;
+            const RefT* pr = tgt_ref + t;
+            const uint32_t* pg = tgt_gbin + t;
 #pragma unroll
             for (uint32_t u = 0; u < kFcBatch; ++u) {
                 wn[u] = pr[lane + 64u * u];
@@ -711,7 +727,7 @@ __global__ __launch_bounds__(64, 8) void k_filter_compact(const FilterKernArgs<R
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (uint32_t u = 0; u < kFcBatch; ++u) bits[u] = valid_bits[(w[u] & 0x7fffffffu) >> 5];
+        for (uint32_t u = 0; u < kFcBatch; ++u) bits[u] = valid_bits[(w[u] & TW::kRefMask) >> 5];
         __builtin_amdgcn_sched_barrier(0);
         if (t + 64u * kFcBatch < tend) ask(t + 64u * kFcBatch);
         __builtin_amdgcn_sched_barrier(0);
@@ -732,7 +748,7 @@ __global__ __launch_bounds__(64, 8) void k_filter_compact(const FilterKernArgs<R
                 SLIMM_PIN_VGPR(wk);
                 wu = wk;
                 gu = gk;
-                H = k_ballot((wk >> 31) != 0u);
+                H = k_ballot((wk >> TW::kShift) != 0u);
                 VB = k_ballot(((bk >> (wk & 31u)) & 1u) != 0u);
             };
             if (full) {
@@ -753,14 +769,14 @@ __global__ __launch_bounds__(64, 8) void k_filter_compact(const FilterKernArgs<R
                     bu = u == k ? bits[k] : bu;
                 }
                 const bool live = tu + lane < tend;
-                H = k_ballot(live && (wu >> 31) != 0u);
+                H = k_ballot(live && (wu >> TW::kShift) != 0u);
                 VB = k_ballot(live && ((bu >> (wu & 31u)) & 1u) != 0u);
             }
             // every valid target gets its place in the ring and the number of its read among the slot's
             if (k_bit(VB)) {
                 const uint32_t p = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(VB >> 32),
                                                              __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(VB), ccount)) & (kFcRing - 1u);
-                s_ref[p] = wu & 0x7fffffffu;
+                s_ref[p] = wu & TW::kRefMask;
                 s_g[p] = gu;
                 // (the read's number: the heads up to and including this lane, less one)
                 s_r[p] = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(H >> 32),
@@ -794,8 +810,8 @@ __global__ __launch_bounds__(64, 8) void k_filter_compact(const FilterKernArgs<R
     }
     __builtin_amdgcn_wave_barrier();
     if (__builtin_expect(whole_reads_walk, 0)) {   // (rare: left to k_filter_walk, a kernel of its own -- inlined, its registers would be this kernel's)
-        uint32_t* const redo = kernarg_now<uint32_t*>(ka, offsetof(FilterKernArgs<Rows>, redo));
-        uint32_t* const counters = kernarg_now<uint32_t*>(ka, offsetof(FilterKernArgs<Rows>, out.counters));
+        uint32_t* const redo = kernarg_now<uint32_t*>(ka, offsetof(KA, redo));
+        uint32_t* const counters = kernarg_now<uint32_t*>(ka, offsetof(KA, out.counters));
         if (lane == 0u) redo[atomicAdd(&counters[CNT_REDO], 1u)] = slot;
     } else {
         for (uint32_t r = lane; r < d.z; r += 64u) ka.out.sel[rb + r] = s_sel[r];   // the slot's selectors, reads without a valid target included
@@ -803,8 +819,8 @@ __global__ __launch_bounds__(64, 8) void k_filter_compact(const FilterKernArgs<R
 }
 
 // the slots k_filter_compact could not take: one window at a time, reads of any length (filter_span)
-template <typename Rows>
-__global__ __launch_bounds__(64) void k_filter_walk(const uint32_t* __restrict__ tgt_ref, const uint32_t* __restrict__ tgt_gbin,
+template <typename Rows, typename RefT>
+__global__ __launch_bounds__(64) void k_filter_walk(const RefT* __restrict__ tgt_ref, const uint32_t* __restrict__ tgt_gbin,
                                                     const uint4* __restrict__ slots, const uint32_t* __restrict__ redo, const Rows rows,
                                                     const FilterOut out) {
     const uint32_t lane = lane_id();
@@ -1028,21 +1044,29 @@ void launch_filter(hipStream_t st, const FilterArgs& a, hipEvent_t t0, hipEvent_
     // stream of batches with the next slot's first batch asked for ahead -- 3 to 4 % slower, and with the descriptors two slots
     // ahead the registers spill; 2 / 8 chunks per trip: the same; row gathers or the target words past the L1: slower.)
     const uint32_t grid = a.nslots;
+    // the two kernels of one row form, in the width of the targets' reference words
+    auto launch = [&](const auto& r, auto ref_word) {
+        using Rows = std::decay_t<decltype(r)>;
+        using RefT = decltype(ref_word);
+        const RefT* const tgt_ref = static_cast<const RefT*>(a.tgt_ref.p);
+        const FilterKernArgs<Rows, RefT> ka{tgt_ref, a.tgt_gbin, a.slots, a.valid_bits, a.redo, a.nslots, r, out};
+        hipExtLaunchKernelGGL((k_filter_compact<Rows, RefT>), dim3(grid), dim3(64), 0, st, t0, t1, 0, ka);
+        hipLaunchKernelGGL((k_filter_walk<Rows, RefT>), dim3(std::min(a.nslots, 256u)), dim3(64), 0, st, tgt_ref, a.tgt_gbin, a.slots,
+                           a.redo, r, out);
+    };
     if (a.rows16) {
         Rows16 r;
         r.rows = reinterpret_cast<const uint4*>(a.rows16);
         r.taxon_flat = a.taxon_flat;
         r.shift = a.taxon_shift;
-        const FilterKernArgs<Rows16> ka{a.tgt_ref, a.tgt_gbin, a.slots, a.valid_bits, a.redo, a.nslots, r, out};
-        hipExtLaunchKernelGGL(k_filter_compact<Rows16>, dim3(grid), dim3(64), 0, st, t0, t1, 0, ka);
-        hipLaunchKernelGGL(k_filter_walk<Rows16>, dim3(std::min(a.nslots, 256u)), dim3(64), 0, st, a.tgt_ref, a.tgt_gbin, a.slots, a.redo, r, out);
+        if (a.tgt_ref.ref16) launch(r, uint16_t{});
+        else launch(r, uint32_t{});
     } else {
         Rows32 r;
         r.lin4 = reinterpret_cast<const uint4*>(a.lin_dense);
         r.valid_of = a.valid;
-        const FilterKernArgs<Rows32> ka{a.tgt_ref, a.tgt_gbin, a.slots, a.valid_bits, a.redo, a.nslots, r, out};
-        hipExtLaunchKernelGGL(k_filter_compact<Rows32>, dim3(grid), dim3(64), 0, st, t0, t1, 0, ka);
-        hipLaunchKernelGGL(k_filter_walk<Rows32>, dim3(std::min(a.nslots, 256u)), dim3(64), 0, st, a.tgt_ref, a.tgt_gbin, a.slots, a.redo, r, out);
+        if (a.tgt_ref.ref16) launch(r, uint16_t{});
+        else launch(r, uint32_t{});
     }
 }
 

@@ -688,6 +688,10 @@ class Slimm:
         self._check(self.L.slimm_get_read_targets(self.ctx, _p(ref), _p(gbin), n.value, C.byref(n)))
         return ref, gbin
 
+    def target_ref_bits(self) -> int:
+        """Width of a target's reference word on the device: 16 (at most 32768 references) or 32."""
+        return self.L.slimm_target_ref_bits(self.ctx)
+
     def taxon_counts(self, stage: int = 1) -> Dict[int, int]:
         n = C.c_uint32()
         self._check(self.L.slimm_taxon_count_size(self.ctx, stage, C.byref(n)))
