@@ -353,8 +353,9 @@ int slimm_get_zstd_stats(slimm_ctx* ctx, uint64_t out[20]);
  * anywhere (inside a stream header, a block header, a chunk header, a chunk, the check, the index, the footer); of the decoded
  * text the first `skip` bytes are the header (0 in every later call); slimm_set_reference_names first; the caller's buffer
  * is free when the call returns; what cannot be decoded yet -- a block whose bytes have not all come -- waits for the next
- * push; the form does not mix with the others within a file.  Behind slimm_set_input_mid_file it is refused ("an xz stream
- * is not cut by byte range").  Pushes are gathered on the host and decoded in rounds (32 MiB of compressed bytes; the whole
+ * push; the form does not mix with the others within a file.  Behind slimm_set_input_mid_file it is a byte range of a split
+ * file, taken only when slimm_set_input_range has told where the range lies ("xz SAM by byte range" below; otherwise "an xz
+ * stream is not cut by byte range unless its range is announced (slimm_set_input_range) and starts at a block").  Pushes are gathered on the host and decoded in rounds (32 MiB of compressed bytes; the whole
  * blocks at hand, at most 512 MB of text or one block alone): the host reads stream headers, block headers, indexes and
  * footers and walks every block's LZMA2 chunk headers, which state all sizes; the device decodes the blocks, ONE LANE PER
  * BLOCK, each into its place in the round's text, computes every block's CRC32 or CRC64 from pieces, and the host compares
@@ -782,8 +783,46 @@ int slimm_group_get_profiles(slimm_group* g, const char* path); /* path may be N
  * gain from that has been measured: a stated default, not a measurement; SLIMM_FORCE zstd_split_floor=N). */
 int slimm_host_zstd_ranges(const char* path, uint64_t skip, uint32_t n, uint64_t* offsets_out);
 uint64_t slimm_zstd_split_floor(void);
+/*   xz SAM by byte range.  An xz file is cut where its indexes say so, and nothing is guessed: the index at each stream's
+ * end states every block's unpadded size and text size, blocks are byte-aligned, and a block needs nothing of the one in
+ * front (dictionary and state are reset at its first chunk).  slimm_host_xz_ranges reads only the file's tail or tails --
+ * footer, index and stream header, stream by stream from the file's end -- and decodes nothing: offsets_out[0] = 0,
+ * offsets_out[n] = the file's size, every other offset the first byte of a block that is not the first of its stream, the
+ * first byte of a stream header (the cut in front of a stream's first block; stream padding belongs to the member on the
+ * left), or the file's size.  No cut lies in front of the end of the block that holds decoded byte skip - 1, found from
+ * the indexes' cumulative text sizes (member 0 holds the whole header and pushes with that skip).  Cut i is the earliest
+ * legal cut at or behind first + i * (size - first) / n; the indexes are complete, so no search gives up, and more members
+ * than blocks get empty ranges.  SLIMM_E_INVALID for a path that is no regular file, an index that does not parse, a skip
+ * of 2^32 or more, and a skip beyond the text the indexes state.
+ *   A range that starts at a block inside a stream has not seen that stream's header, so it does not know the check kind,
+ * which also sizes the field behind every block.  slimm_host_xz_check_at(path, offset, &check): -1 when offset is 0, a
+ * stream header's first byte or no byte of a stream, else the check id of the stream around it, from its footer.  Every
+ * member announces its flags with slimm_set_input_mid_file, its range with slimm_set_input_range(ctx, begin, end) AND that
+ * check with slimm_set_xz_range_check(ctx, check) (-1, the default: none told), all before its first window, and pushes --
+ * slimm_push_xz_sam_bytes, skip for member 0 only -- exactly its range: there is no slack.  With a told check the walk
+ * starts among the stream's blocks, without one at a stream header; a first byte that starts neither is SLIMM_E_SPLIT.  So
+ * is a range that ends inside the file and at last = 1 does not stand exactly at its end, at a block's first byte or
+ * between streams ("the range does not end at a block boundary").  The file's last member keeps the truncation errors of
+ * one context.  Nothing in front of the range exists for the member, and error messages name the file's bytes.  The member
+ * in whose range a stream's index lies reads it and the footer: it checks the index's last k records against its own k
+ * blocks of that stream and keeps the first N - k for the stitch; a footer of another check kind than the told one is
+ * SLIMM_E_SPLIT.  An empty range is an empty member.  slimm_get_xz_stats stays per context and the members' counters sum to
+ * the file's: a stream is counted by the member that read its header, index records by the member that read the index.
+ *   slimm_group_stitch_ranges first checks on host scalars, left to right: every member's walker stopped exactly at its
+ * range's end (SLIMM_E_SPLIT names the member); a member that was told a check has a stream open across the cut in front
+ * of it, of that kind (SLIMM_E_SPLIT); the (unpadded size, text size) pairs of the left members' blocks of that stream
+ * equal, in order and in number, the records the member that met the index kept (SLIMM_E_INVALID "index does not match the
+ * blocks") -- so every index record of the file is checked against its block exactly once.  The text is then stitched as
+ * SAM text is.  slimm_xz_split_floor(): the least blocks per member -- the blocks behind the first legal cut / members --
+ * at which the command cuts an xz file for --split-input: 16, the command's default for reading an xz file on the device at
+ * all, since a range is decoded a lane per block as a file is (a stated default, NOT a measurement; SLIMM_FORCE
+ * xz_split_blocks=N). */
+int slimm_host_xz_ranges(const char* path, uint64_t skip, uint32_t n, uint64_t* offsets_out);
+int slimm_host_xz_check_at(const char* path, uint64_t offset, int* check_out);
+int slimm_set_xz_range_check(slimm_ctx* ctx, int check);
+uint64_t slimm_xz_split_floor(void);
 int slimm_host_bzip2_ranges(const char* path, uint64_t skip, uint32_t n, uint64_t* offsets_out);
-/* A range's absolute file offsets [begin, end) (bzip2 SAM, zstd SAM; before the range's first window, beside slimm_set_input_mid_file) */
+/* A range's absolute file offsets [begin, end) (bzip2 SAM, zstd SAM, xz SAM; before the range's first window, beside slimm_set_input_mid_file) */
 int slimm_set_input_range(slimm_ctx* ctx, uint64_t begin, uint64_t end);
 /* the bytes a member reads behind its range of a bzip2 file (slimm_amd/csrc/bzip2_block.h: kSplitSlack, from the format's bounds) */
 uint64_t slimm_bzip2_split_slack(void);

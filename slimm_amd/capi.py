@@ -201,6 +201,10 @@ SYMBOLS = [
     ("slimm_bzip2_split_slack", C.c_uint64, []),
     ("slimm_host_zstd_ranges", C.c_int, [C.c_char_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]),
     ("slimm_zstd_split_floor", C.c_uint64, []),
+    ("slimm_host_xz_ranges", C.c_int, [C.c_char_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]),
+    ("slimm_host_xz_check_at", C.c_int, [C.c_char_p, C.c_uint64, C.POINTER(C.c_int)]),
+    ("slimm_set_xz_range_check", C.c_int, [_P, C.c_int]),
+    ("slimm_xz_split_floor", C.c_uint64, []),
     ("slimm_group_stitch_ranges", C.c_int, [_P]),
     ("slimm_record_cap", C.c_uint64, []),
     ("slimm_shutdown", C.c_int, []),

@@ -20,6 +20,9 @@
 //   footers cut across rounds), xz_round_text=N (a round's text at most: a round takes one block, the next round the
 //   rest), xz_device_blocks=N (the `slimm` command reads an xz file of fewer than N blocks, by its index, on the host: 16
 //   unless told)                              tests/test_gpu_xz_sam.py, tests/test_cli_xz_sam_device.py
+//   xz_split_blocks=N (the least blocks per member at which the command cuts an xz file for --split-input: 16 unless told;
+//   a key of its own, which does not follow xz_device_blocks)
+//                                             tests/test_split_xz_ranges.py, tests/test_cli_split_input_xz.py
 //   bzip2_split_wrong_first (a mid-file member of a split bzip2 file passes over its first block or marker:
 //   slimm_group_stitch_ranges must refuse the cut)                                   tests/test_gpu_split_bzip2_sam.py
 //   zstd_split_floor=N (the least bytes per member at which the command cuts a zstd file for --split-input: 32 MiB unless

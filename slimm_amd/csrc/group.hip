@@ -712,6 +712,12 @@ int slimm_group_stitch_ranges(slimm_group* g) {
         if (rc == SLIMM_E_SPLIT) return gfail(g, SLIMM_E_SPLIT, "the range of member %u: %s", bad, slimm_last_error(g->ctx[bad]));
         if (rc < 0) return member_failed(g, bad, rc, "the frames of a range");
     }
+    if (slimm::split_is_xz(g->ctx[0])) {   // (every member's walker stopped where its range does, and a stream over cuts matches its index)
+        uint32_t bad = 0;
+        const int rc = slimm::split_xz_streams(g->ctx.data(), n, &bad);
+        if (rc == SLIMM_E_SPLIT) return gfail(g, SLIMM_E_SPLIT, "the range of member %u: %s", bad, slimm_last_error(g->ctx[bad]));
+        if (rc < 0) return member_failed(g, bad, rc, "the blocks of a stream across a cut");
+    }
     std::vector<uint32_t> left_of(n, 0);
     uint32_t left = 0;
     for (uint32_t k = 1; k < n; ++k) {

@@ -138,6 +138,10 @@ SLIMM_FORWARD(int, slimm_set_input_range, (slimm_ctx* a, uint64_t b, uint64_t c)
 SLIMM_FORWARD(uint64_t, slimm_bzip2_split_slack, (), ())
 SLIMM_FORWARD(int, slimm_host_zstd_ranges, (const char* a, uint64_t b, uint32_t c, uint64_t* d), (a, b, c, d))
 SLIMM_FORWARD(uint64_t, slimm_zstd_split_floor, (), ())
+SLIMM_FORWARD(int, slimm_host_xz_ranges, (const char* a, uint64_t b, uint32_t c, uint64_t* d), (a, b, c, d))
+SLIMM_FORWARD(int, slimm_host_xz_check_at, (const char* a, uint64_t b, int* c), (a, b, c))
+SLIMM_FORWARD(int, slimm_set_xz_range_check, (slimm_ctx* a, int b), (a, b))
+SLIMM_FORWARD(uint64_t, slimm_xz_split_floor, (), ())
 SLIMM_FORWARD(int, slimm_group_stitch_ranges, (slimm_group* a), (a))
 SLIMM_FORWARD(uint64_t, slimm_record_cap, (), ())
 SLIMM_FORWARD(int, slimm_shutdown, (), ())
@@ -627,6 +631,9 @@ struct InputForm {
     bool wide_header_by_host = false;  // the pump: a header of 2^32 text bytes or more goes through the host reader (pushed_as)
     uint64_t (*slack)() = nullptr;     // bytes a member reads behind its range, at most to the file's end (none: 0)
     bool announce_range = false;       // the members are told their ranges (slimm_set_input_range)
+    // ... and what a range that starts at `offset` cannot see of the file in front of it, beside its range (none: nothing)
+    int (*range_note)(const char* path, uint64_t offset, int* note) = nullptr;
+    int (*announce_note)(slimm_ctx*, int note) = nullptr;
     // what else must hold for a regular file of this form to be cut over G members (none: nothing)
     bool (*may_cut)(const AlignmentFile& f, const std::string& path, uint32_t G, bool with_floor) = nullptr;
     // SLIMM_TRACE=cli, at the file's end: what the device decoded, the counters of the n contexts summed (none: no line)
@@ -666,7 +673,7 @@ void zstd_end_line(const char* head, slimm_ctx* const* ctx, uint32_t n) {
 }
 void xz_end_line(const char* head, slimm_ctx* const* ctx, uint32_t n) {
     uint64_t streams = 0, blocks = 0, text = 0, told = 0;
-    for (uint32_t i = 0; i < n; ++i) {
+    for (uint32_t i = 0; i < n; ++i) {   // (a stream is counted by the member that read its header)
         uint64_t st[20] = {};
         if (slimm_get_xz_stats(ctx[i], st) == SLIMM_OK) ++told, streams += st[0], blocks += st[1], text += st[14];
     }
@@ -678,17 +685,26 @@ void xz_end_line(const char* head, slimm_ctx* const* ctx, uint32_t n) {
 // -- a stated default, not a measurement (SLIMM_FORCE xz_device_blocks=N).  A file whose index does not parse goes by the
 // host reader as well, which says what is wrong with it
 constexpr uint64_t kXzDeviceBlocks = 16;
-bool xz_by_host(const std::string& path, const char* head) {
+uint64_t xz_device_blocks() {
     long least = 0;
-    if (!forced("xz_device_blocks", &least) || least < 0) least = static_cast<long>(kXzDeviceBlocks);
+    return forced("xz_device_blocks", &least) && least >= 0 ? static_cast<uint64_t>(least) : kXzDeviceBlocks;
+}
+// (one reading of a file's indexes for the two questions below; false: not a file whose index parses)
+bool xz_index_of(const std::string& path, uint64_t* size, std::vector<XzIndexBlock>* blocks, std::vector<XzIndexStream>* layout) {
     const int fd = open(path.c_str(), O_RDONLY);
     struct stat sb;
-    std::vector<XzIndexBlock> blocks;
     uint32_t streams = 0;
-    const bool ok = fd >= 0 && fstat(fd, &sb) == 0 &&
-                    xz_read_index([&](uint64_t at, uint8_t* dst, size_t n) { return pread_all(fd, dst, at, n); }, static_cast<uint64_t>(sb.st_size), &blocks, &streams);
+    const bool ok = fd >= 0 && fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) &&
+                    xz_read_index([&](uint64_t at, uint8_t* dst, size_t n) { return pread_all(fd, dst, at, n); }, static_cast<uint64_t>(sb.st_size), blocks, &streams, layout);
     if (fd >= 0) close(fd);
-    if (ok && blocks.size() >= static_cast<uint64_t>(least)) return false;
+    if (ok) *size = static_cast<uint64_t>(sb.st_size);
+    return ok;
+}
+bool xz_by_host(const std::string& path, const char* head) {
+    uint64_t size = 0;
+    std::vector<XzIndexBlock> blocks;
+    const bool ok = xz_index_of(path, &size, &blocks, nullptr);
+    if (ok && blocks.size() >= xz_device_blocks()) return false;
     if (g_trace && ok) fprintf(stderr, "%sxz SAM of %llu block(s): read on the host\n", head, (unsigned long long)blocks.size());
     if (g_trace && !ok) fprintf(stderr, "%sxz SAM whose index does not parse: read on the host\n", head);
     return true;
@@ -713,6 +729,34 @@ bool zstd_may_cut(const AlignmentFile& f, const std::string& path, uint32_t G, b
     close(fd);
     return ok && first <= size && (size - first) / G >= slimm_zstd_split_floor();
 }
+// xz SAM is cut where its indexes say a block or a stream starts (xz_plan_ranges, the rule of slimm_host_xz_ranges, over one
+// reading of the indexes): read_split takes a file whose plan for G members has at least two ranges that are not empty and,
+// with_floor, whose members get slimm_xz_split_floor() blocks each or more: the blocks behind the first legal cut / G (the
+// cap's re-read does not ask: it has no other way).  The floor is the stated default of kXzDeviceBlocks -- a range is decoded
+// a lane per block, as a file is --, not a measurement.  Whether the device reads the file at all is xz_by_host's to say, and
+// set_up asks it only behind this: so a file of fewer than xz_device_blocks() blocks -- the one threshold, asked here as
+// xz_by_host asks it -- is not cut, --split-input leaves it to member 0's host reader, and at the cap, where the host reader
+// has read it, it fails as it did
+bool xz_may_cut(const AlignmentFile& f, const std::string& path, uint32_t G, bool with_floor) {
+    if (G < 2u || f.header_bytes() >= (1ull << 32)) return false;
+    uint64_t size = 0;
+    std::vector<XzIndexBlock> blocks;
+    std::vector<XzIndexStream> layout;
+    if (!xz_index_of(path, &size, &blocks, &layout) || blocks.size() < xz_device_blocks()) return false;
+    std::vector<uint64_t> off(G + 1u, 0);
+    if (!xz_plan_ranges(blocks, layout, size, f.header_bytes(), G, off.data())) return false;
+    uint32_t filled = 0;
+    for (uint32_t i = 0; i < G; ++i) filled += off[i + 1] > off[i] ? 1u : 0u;
+    if (filled < 2u) return false;
+    if (!with_floor) return true;
+    uint64_t text = 0, behind = blocks.size();
+    for (const XzIndexBlock& b : blocks) {   // (the blocks that hold the header are member 0's in any case)
+        if (text >= f.header_bytes()) break;
+        text += b.uncompressed;
+        --behind;
+    }
+    return behind / G >= slimm_xz_split_floor();
+}
 
 enum { kBam, kBgzfSam, kSam, kBzip2Sam, kGzipSam, kZstdSam, kXzSam };
 const InputForm kForms[] = {
@@ -727,8 +771,9 @@ const InputForm kForms[] = {
      .wide_header_by_host = true, .end_line = gzip_end_line},
     {.name = "zstd", .sam = true, .read = InputForm::Streamed, .push = slimm_push_zstd_sam_bytes, .plan = slimm_host_zstd_ranges,
      .planned = "zstd frames", .wide_header_by_host = true, .announce_range = true, .may_cut = zstd_may_cut, .end_line = zstd_end_line},
-    {.name = "xz", .article = "an", .sam = true, .read = InputForm::Streamed, .push = slimm_push_xz_sam_bytes, .planned = "xz stream",
-     .wide_header_by_host = true, .end_line = xz_end_line, .by_host = xz_by_host},
+    {.name = "xz", .article = "an", .sam = true, .read = InputForm::Streamed, .push = slimm_push_xz_sam_bytes, .plan = slimm_host_xz_ranges,
+     .planned = "xz blocks", .wide_header_by_host = true, .announce_range = true, .range_note = slimm_host_xz_check_at,
+     .announce_note = slimm_set_xz_range_check, .may_cut = xz_may_cut, .end_line = xz_end_line, .by_host = xz_by_host},
 };
 const InputForm& form_of(const AlignmentFile& f) {
     if (f.is_bam()) return kForms[kBam];
@@ -1129,6 +1174,7 @@ struct SplitMember {
     uint32_t index = 0, header_skip = 0;   // (header_skip: member 0's, the header's inflated or decoded bytes)
     bool file_last = false;
     uint64_t begin = 0, range_end = 0, read_end = 0;
+    int note = -1;   // what the form's range_note said of `begin` (xz: the check kind of the stream around it)
     int fd = -1;
     unsigned threads = 1;
     size_t cap = 0, read_hint = 0;
@@ -1195,6 +1241,7 @@ struct SplitMember {
         int r = form->sam ? slimm_set_reference_names(ctx, names) : SLIMM_OK;
         if (r == SLIMM_OK) r = slimm_set_input_mid_file(ctx, index > 0 ? 1 : 0, file_last ? 0 : 1);
         if (r == SLIMM_OK && form->announce_range) r = slimm_set_input_range(ctx, begin, range_end);
+        if (r == SLIMM_OK && form->announce_note) r = form->announce_note(ctx, note);
         if (r == SLIMM_OK) r = slimm_set_input_size_hint(ctx, range_end - begin);
         if (r != SLIMM_OK) return failed(r, slimm_last_error(ctx));
         for (auto* b : buf) (void)slimm_pin_host_buffer(ctx, b, cap);   // (pageable memory still works)
@@ -1263,6 +1310,11 @@ int read_split(slimm_group* grp, uint32_t G, const std::string& path, const Inpu
         M.ctx = ctxs[i] = slimm_group_context(grp, i);
         M.header_skip = i == 0 ? static_cast<uint32_t>(header_bytes) : 0u;
         M.begin = off[i], M.range_end = off[i + 1];
+        if (form.range_note && form.range_note(path.c_str(), M.begin, &M.note) != SLIMM_OK) {
+            close(fd);
+            why = std::string("the file's ") + form.planned + " could not be planned into ranges";
+            return SLIMM_E_INVALID;
+        }
         M.read_end = std::min<uint64_t>(off[G], off[i + 1] + (M.file_last ? 0u : slack));
         M.threads = std::max(1u, cores / G);
         M.cap = std::max<size_t>(1u << 20, G <= 2 ? window_cap : window_cap * 2 / G);
@@ -1460,7 +1512,8 @@ std::unique_ptr<Reading> set_up(Session& S, const std::string& path, bool any_or
     const bool may_split = options.split_input && options.devices.size() > 1 && !options.host_decode && !options.verify_grouping && !options.packed_records;
     F->split_input = may_split && cut_by_byte_range(bam, path, static_cast<uint32_t>(options.devices.size()), true);
     // (a form that is not cut whenever it is asked: gzip never; a zstd file of one frame, or one whose members would get less
-    // than the floor; or the host decoders were asked for)
+    // bytes than its floor; an xz file the host reader takes, or one whose members would get fewer blocks than its floor; or
+    // the host decoders were asked for)
     const InputForm& form = form_of(bam);
     if (g_trace && !any_order && !F->split_input && options.split_input && options.devices.size() > 1 && (!form.plan || form.may_cut))
         fprintf(stderr, "%s--split-input: %s %s stream is not cut by byte range; member 0 reads %s\n", S.trace_head(), form.article, form.name, path.c_str());
@@ -1690,8 +1743,9 @@ Outcome run_context(Session& S, Reading& F) {
     S.err() << "[" << F.watch.lap() << " secs]" << std::endl;
 
     S.err() << "Analysing alignments, reads and references ....... ";
-    // (zstd SAM: whether the file can be cut is asked only once the cap is met -- the plan reads the file; the floor is not
-    // consulted here.  A file of one frame cannot be cut and ends at the cap, as it did)
+    // (zstd and xz SAM: whether the file can be cut is asked only once the cap is met -- the plan reads the file; the floor is
+    // not consulted here.  A zstd file of one frame, an xz file of one block behind the header's or one that the host reader
+    // took -- fewer than xz_device_blocks() blocks -- cannot be cut and ends at the cap, as it did)
     const InputForm& form = form_of(F.bam);
     const Outcome pushed = push_file(S, F, Target{ctx}, F.bam.regular_file() && form.plan ? OnCap::MoreMembers : OnCap::Fail);
     if (pushed == Outcome::MoreMembers && form.may_cut && !form.may_cut(F.bam, F.path, 2u, false)) {

@@ -4,6 +4,8 @@
 #include <algorithm>
 #include <cstring>
 
+#include "../split_plan.h"
+
 namespace slimm {
 namespace {
 
@@ -206,10 +208,13 @@ bool XzReader::next_text() {
     }
 }
 
-bool xz_read_index(const std::function<bool(uint64_t, uint8_t*, size_t)>& read, uint64_t size, std::vector<XzIndexBlock>* blocks, uint32_t* streams) {
+bool xz_read_index(const std::function<bool(uint64_t, uint8_t*, size_t)>& read, uint64_t size, std::vector<XzIndexBlock>* blocks, uint32_t* streams,
+                   std::vector<XzIndexStream>* layout) {
     blocks->clear();
     *streams = 0;
+    if (layout) layout->clear();
     std::vector<std::vector<XzIndexBlock>> per_stream;   // (the last stream first)
+    std::vector<XzIndexStream> where;                    // (the same)
     uint64_t end = size;
     std::vector<uint8_t> index;
     while (end > 0) {
@@ -241,6 +246,7 @@ bool xz_read_index(const std::function<bool(uint64_t, uint8_t*, size_t)>& read, 
         uint32_t check = 0;
         if (!read(start, head, xz::kHeaderBytes) || !xz::is_magic(head) || xz::stream_header(head, &check) != xz::kOk || check != foot[9]) return false;
         for (XzIndexBlock& b : mine) b.at += start + xz::kHeaderBytes;
+        where.push_back(XzIndexStream{start, index_at + index_bytes + xz::kHeaderBytes, count, check});
         per_stream.push_back(std::move(mine));
         end = start;
     }
@@ -251,6 +257,47 @@ bool xz_read_index(const std::function<bool(uint64_t, uint8_t*, size_t)>& read, 
             b.stream = static_cast<uint32_t>(per_stream.size() - 1u - s);
             blocks->push_back(b);
         }
+    if (layout) layout->assign(where.rbegin(), where.rend());
+    return true;
+}
+
+bool xz_plan_ranges(const std::function<bool(uint64_t, uint8_t*, size_t)>& read, uint64_t size, uint64_t skip, uint32_t n, uint64_t* offsets) {
+    std::vector<XzIndexBlock> blocks;
+    std::vector<XzIndexStream> layout;
+    uint32_t streams = 0;
+    return n && xz_read_index(read, size, &blocks, &streams, &layout) && xz_plan_ranges(blocks, layout, size, skip, n, offsets);
+}
+
+bool xz_plan_ranges(const std::vector<XzIndexBlock>& blocks, const std::vector<XzIndexStream>& layout, uint64_t size, uint64_t skip, uint32_t n,
+                    uint64_t* offsets) {
+    if (!n) return false;
+    // no cut in front of the end of the block that holds decoded byte skip - 1: member 0 holds the whole header
+    uint64_t first = 0, text = 0;
+    for (size_t b = 0; skip && b < blocks.size() && text < skip; ++b) {
+        text += blocks[b].uncompressed;
+        first = blocks[b].at + ((blocks[b].unpadded + 3u) & ~3ull);
+    }
+    if (text < skip) return false;   // (the index states less text than that)
+    std::vector<uint64_t> cuts;      // (in file order)
+    size_t b = 0;
+    for (const XzIndexStream& s : layout) {
+        cuts.push_back(s.at);
+        for (uint64_t k = 0; k < s.blocks; ++k, ++b)
+            if (k) cuts.push_back(blocks[b].at);
+    }
+    cuts.push_back(size);
+    even_ranges(first, size, n, offsets, [&](uint64_t t) { return *std::lower_bound(cuts.begin(), cuts.end(), std::min(t, size)); });
+    return true;
+}
+
+bool xz_check_at(const std::function<bool(uint64_t, uint8_t*, size_t)>& read, uint64_t size, uint64_t offset, int* check) {
+    std::vector<XzIndexBlock> blocks;
+    std::vector<XzIndexStream> layout;
+    uint32_t streams = 0;
+    if (!xz_read_index(read, size, &blocks, &streams, &layout)) return false;
+    *check = -1;
+    for (const XzIndexStream& s : layout)
+        if (offset > s.at && offset < s.end) *check = static_cast<int>(s.check);
     return true;
 }
 

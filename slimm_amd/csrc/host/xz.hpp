@@ -54,6 +54,26 @@ struct XzIndexBlock {
 // A file of `size` bytes seen through read(offset, dst, n) (false: a read error): the blocks of all its streams in file
 // order, read from the file's end -- footer, backward size, index, the stream's header, stream padding, the stream in front.
 // false: it does not parse that way (nothing is decoded: the blocks themselves are not looked at)
-bool xz_read_index(const std::function<bool(uint64_t, uint8_t*, size_t)>& read, uint64_t size, std::vector<XzIndexBlock>* blocks, uint32_t* streams);
+// (layout, where asked for: every stream in file order -- one without blocks too --, its header's first byte, the byte behind
+// its footer, its check kind and how many blocks it has)
+struct XzIndexStream {
+    uint64_t at, end, blocks;
+    uint32_t check;
+};
+bool xz_read_index(const std::function<bool(uint64_t, uint8_t*, size_t)>& read, uint64_t size, std::vector<XzIndexBlock>* blocks, uint32_t* streams,
+                   std::vector<XzIndexStream>* layout = nullptr);
+
+// Where a file may be cut into byte ranges (split.hip: slimm_host_xz_ranges), by its index or indexes alone.  A legal cut is
+// the first byte of a block that is not the first of its stream, the first byte of a stream header -- the cut in front of a
+// stream's first block: stream padding stays on the left --, or the file's size; none lies in front of the end of the block
+// that holds decoded byte skip - 1.  offsets[0] = 0, offsets[n] = size, offsets[i] the earliest legal cut at or behind member
+// i's even share of the bytes behind the first legal one.  false: the index does not parse, or states less text than `skip`
+bool xz_plan_ranges(const std::function<bool(uint64_t, uint8_t*, size_t)>& read, uint64_t size, uint64_t skip, uint32_t n, uint64_t* offsets);
+// ... the same over an index that xz_read_index has read already (its blocks and its layout)
+bool xz_plan_ranges(const std::vector<XzIndexBlock>& blocks, const std::vector<XzIndexStream>& layout, uint64_t size, uint64_t skip, uint32_t n,
+                    uint64_t* offsets);
+// What a range that starts at `offset` cannot see: the check kind of the stream whose blocks it starts among (from that
+// stream's footer) -- or -1, when offset is 0, a stream header's first byte, or no byte of a stream.  false as above
+bool xz_check_at(const std::function<bool(uint64_t, uint8_t*, size_t)>& read, uint64_t size, uint64_t offset, int* check);
 
 }  // namespace slimm

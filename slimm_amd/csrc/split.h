@@ -1,5 +1,5 @@
 // Internal to the library: the per-member steps of slimm_group_stitch_ranges (group.hip drives them, split.hip holds them)
-// -- one file (BAM, SAM, BGZF SAM, bzip2 SAM, zstd SAM) split by byte range over a group's members (include/slimm_hip.h, "ONE FILE SPLIT BY BYTE RANGE").
+// -- one file (BAM, SAM, BGZF SAM, bzip2 SAM, zstd SAM, xz SAM) split by byte range over a group's members (include/slimm_hip.h, "ONE FILE SPLIT BY BYTE RANGE").
 // Every step finishes its own device work before it returns: the next step may run on another member's device.
 #pragma once
 #include <stdint.h>
@@ -23,6 +23,12 @@ int split_bz2_chains(slimm_ctx* const* members, uint32_t n, uint32_t* bad);
 // the range read.  SLIMM_OK, or SLIMM_E_SPLIT with the message on member *bad
 bool split_is_zstd(const slimm_ctx* c);
 int split_zstd_ends(slimm_ctx* const* members, uint32_t n, uint32_t* bad);
+// xz SAM: left to right on host scalars, every member's walker stands at its range's end with every byte of the range read; a
+// member that was told a check kind has a stream over the cut in front of it, of that kind; the blocks of such a stream in
+// the ranges on the left are, in order and in number, the index records that the member which met the index kept (those in
+// front of its own blocks' records).  SLIMM_OK, or the code with the message on member *bad
+bool split_is_xz(const slimm_ctx* c);
+int split_xz_streams(slimm_ctx* const* members, uint32_t n, uint32_t* bad);
 // the head of `right` as one more window of `left` (final: it must end with a complete record, else SLIMM_E_SPLIT)
 int split_append_head(slimm_ctx* left, slimm_ctx* right, bool final, uint64_t* n_records);
 // `right`'s first record against the last record of `left` (its carry): the same name clears the run-start bit and

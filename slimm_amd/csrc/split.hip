@@ -1,17 +1,19 @@
-// One file -- BAM, SAM text, BGZF blocks of SAM text, bzip2 SAM or zstd SAM -- split by byte range over a group's members
+// One file -- BAM, SAM text, BGZF blocks of SAM text, bzip2 SAM, zstd SAM or xz SAM -- split by byte range over a group's members
 // (include/slimm_hip.h, "ONE FILE SPLIT BY BYTE RANGE"): the host's plan of the ranges (slimm_host_bgzf_ranges,
-// slimm_host_text_ranges, slimm_host_bzip2_ranges, slimm_host_zstd_ranges) and the per-member steps of slimm_group_stitch_ranges (split.h; group.hip runs them cut by cut).  A range that starts inside
+// slimm_host_text_ranges, slimm_host_bzip2_ranges, slimm_host_zstd_ranges, slimm_host_xz_ranges) and the per-member steps of slimm_group_stitch_ranges (split.h; group.hip runs them cut by cut).  A range that starts inside
 // the file guesses its first record as k_bam_pieces guesses a piece's (windows.hip, bam_decode.hip: k_bam_first_guess);
 // the member on its left confirms the guess one level up, as k_bam_verify confirms a piece's: its incomplete last record
 // followed by the right member's head must be whole records that end exactly where the guess begins.  A range of SAM
 // text guesses nothing: its first line starts behind its first newline (sam_decode.hip: k_sam_first_newline), and the
 // left member's last line must end with the head.  A range of bzip2 SAM starts at the first block of its own
 // (bzip2_decode.hip) and is text from there on; its chain of blocks is held against its neighbours' first (split_bz2_chains).  A range of zstd SAM starts and ends where frames do
-// (zstd_decode.hip) and is text in between; that every member's frames ended at its range's end is checked first (split_zstd_ends).  The reference reads one file with one reader (src/misc.hpp:498-522).
+// (zstd_decode.hip) and is text in between; that every member's frames ended at its range's end is checked first (split_zstd_ends).  A range of xz SAM starts at a stream header or at a block and ends where
+// a block or a stream does (xz_decode.hip); the blocks of a stream that lies over cuts are held against its index (split_xz_streams).  The reference reads one file with one reader (src/misc.hpp:498-522).
 #include "context.h"
 #include "split.h"
 #include "split_plan.h"
 #include "host/zstd.cpp"   // (the host's serial zstd decoder, for the header's frames: the library holds no other copy of it)
+#include "host/xz.cpp"     // (xz_read_index and the planner on it: the same)
 
 namespace {
 
@@ -223,6 +225,34 @@ uint64_t slimm_zstd_split_floor(void) {
     return slimm::forced("zstd_split_floor", &v) && v >= 0 ? static_cast<uint64_t>(v) : slimm::kZstdRoundBytes;
 }
 
+// xz is cut where its indexes say a block or a stream starts (host/xz.cpp: xz_plan_ranges): only the file's tail or tails
+// are read -- footer, index, stream header, stream by stream from the file's end --, nothing is decoded and nothing guessed
+int slimm_host_xz_ranges(const char* path, uint64_t skip, uint32_t n, uint64_t* offsets_out) {
+    if (!path || !n || !offsets_out || skip >= (1ull << 32)) return SLIMM_E_INVALID;
+    slimm::PlanFile f;
+    if (!f.open_regular(path)) return SLIMM_E_INVALID;
+    auto read = [&](uint64_t off, uint8_t* dst, size_t k) { return off <= f.size && k <= f.size - off && f.read(off, dst, k); };
+    return slimm::xz_plan_ranges(read, f.size, skip, n, offsets_out) ? SLIMM_OK : SLIMM_E_INVALID;
+}
+
+int slimm_host_xz_check_at(const char* path, uint64_t offset, int* check_out) {
+    if (!path || !check_out) return SLIMM_E_INVALID;
+    slimm::PlanFile f;
+    if (!f.open_regular(path)) return SLIMM_E_INVALID;
+    auto read = [&](uint64_t off, uint8_t* dst, size_t k) { return off <= f.size && k <= f.size - off && f.read(off, dst, k); };
+    return slimm::xz_check_at(read, f.size, offset, check_out) ? SLIMM_OK : SLIMM_E_INVALID;
+}
+
+// The least blocks per member at which the command cuts an xz file for --split-input: a range is decoded a lane per block,
+// as a file is, so the floor is the same stated default as the command's kXzDeviceBlocks -- NOT a measurement: nothing is
+// known yet of an LZMA lane's rate on the device (SLIMM_FORCE xz_split_blocks=N; a key of its own: xz_device_blocks decides
+// whether the device reads the file at all)
+constexpr uint64_t kXzSplitBlocks = 16;
+uint64_t slimm_xz_split_floor(void) {
+    long v = 0;
+    return slimm::forced("xz_split_blocks", &v) && v >= 0 ? static_cast<uint64_t>(v) : kXzSplitBlocks;
+}
+
 }  // extern "C"
 
 namespace slimm {
@@ -294,12 +324,59 @@ int split_zstd_ends(slimm_ctx* const* members, uint32_t n, uint32_t* bad) {
     return SLIMM_OK;
 }
 
+bool split_is_xz(const slimm_ctx* c) { return c->win.file.stream.codec == WindowPipeline::File::Codec::Xz; }
+
+int split_xz_streams(slimm_ctx* const* members, uint32_t n, uint32_t* bad) {
+    using XF = WindowPipeline::File::Xz;
+    // the stream that lies over the cut in front of member k: its check kind and its blocks in the ranges on the left
+    bool open = false;
+    uint32_t check = 0;
+    std::vector<std::pair<uint64_t, uint64_t>> blocks;
+    for (uint32_t k = 0; k < n; ++k) {
+        slimm_ctx* c = members[k];
+        const WindowPipeline::Announced& A = c->win.announced;
+        const WindowPipeline::File::Stream& T = c->win.file.stream;
+        const XF& Z = c->win.file.xz;
+        const uint64_t at = T.base + (T.bit >> 3);   // (the file's byte its walker stands at)
+        *bad = k;
+        if (!split_is_xz(c) || !A.has_range) return fail(c, SLIMM_E_INVALID, "a range of an xz file: slimm_set_input_range tells where it lies");
+        if (at != A.range_end || T.pend.size() != (T.bit >> 3) || !Z.ready.empty())
+            return fail(c, SLIMM_E_SPLIT, "xz: the blocks of member %u end at byte %llu, its range at byte %llu: the range does not end at a block boundary", k,
+                        static_cast<unsigned long long>(at), static_cast<unsigned long long>(A.range_end));
+        if (Z.from_left != open)
+            return fail(c, SLIMM_E_SPLIT, open ? "xz: member %u starts at a stream header, and the stream on its left has not ended"
+                                               : "xz: member %u was told a check kind, and no stream lies over the cut in front of it", k);
+        if (Z.from_left && Z.check != check && !Z.left_closed)
+            return fail(c, SLIMM_E_SPLIT, "xz: member %u was told check kind %u, the stream's header states %u", k, static_cast<unsigned>(Z.check),
+                        static_cast<unsigned>(check));
+        if (Z.from_left && Z.left_closed) {   // (its footer's kind was the told one: xz_round)
+            if (static_cast<uint32_t>(A.xz_check) != check)
+                return fail(c, SLIMM_E_SPLIT, "xz: member %u was told check kind %d, the stream's header states %u", k, A.xz_check, static_cast<unsigned>(check));
+            if (blocks != Z.left_kept)
+                return fail(c, SLIMM_E_INVALID, "xz-compressed input is not supported unless it decodes: index at byte %llu: %s",
+                            static_cast<unsigned long long>(Z.left_index_at), xz::status_text(xz::kIndexMismatch));
+            open = false;
+            blocks.clear();
+        }
+        if (Z.stage == XF::Blocks) {   // (the range ends among a stream's blocks)
+            if (!open) check = Z.check;
+            open = true;
+            blocks.insert(blocks.end(), Z.records.begin(), Z.records.end());
+        }
+    }
+    *bad = n - 1u;
+    if (open) return fail(members[n - 1u], SLIMM_E_SPLIT, "xz: the last range ends among a stream's blocks");
+    return SLIMM_OK;
+}
+
 int split_range(slimm_ctx* c, SplitRange* out) {
     if (!c || !out) return SLIMM_E_INVALID;
     if (c->device < 0 || !c->win.file.active || !c->win.file.closed)
-        return fail(c, SLIMM_E_INVALID, "a range of a split file: a range of BAM, SAM, BGZF SAM, bzip2 SAM or zstd SAM pushed to its end");
+        return fail(c, SLIMM_E_INVALID, "a range of a split file: a range of BAM, SAM, BGZF SAM, bzip2 SAM, zstd SAM or xz SAM pushed to its end");
     if (split_is_bzip2(c) && !c->win.announced.has_range)
         return fail(c, SLIMM_E_INVALID, "a range of a bzip2 file: slimm_set_input_range tells where it lies");
+    if (split_is_xz(c) && !c->win.announced.has_range)
+        return fail(c, SLIMM_E_INVALID, "a range of an xz file: slimm_set_input_range tells where it lies");
     out->found_start = c->win.file.found_start || !c->win.announced.starts_mid;
     out->head_len = c->win.announced.starts_mid ? c->win.file.head_len : 0u;
     out->n_records = c->n_pushed;

@@ -125,6 +125,9 @@ struct WindowPipeline {
         // magic's first bit lies in, and the stitch compares absolute bit positions)
         bool has_range = false;
         uint64_t range_begin = 0, range_end = 0;
+        // xz SAM: the check kind of the stream among whose blocks the range starts (slimm_set_xz_range_check; -1: the range
+        // starts at a stream header, which tells it)
+        int xz_check = -1;
     } announced;
 
     // ---- this file: reset as a whole, by end_file alone -- a new member needs its initialiser and nothing else
@@ -271,6 +274,16 @@ struct WindowPipeline {
             std::vector<xz::Block> ready;
             std::vector<uint64_t> ready_at;   // the blocks' file offsets (errors)
             uint64_t text = 0;                // the round's text bytes (behind xz_round)
+            // a byte range of a split file (Announced::has_range).  A range that was told a check kind starts among the
+            // blocks of a stream whose header lies on its left: until it meets that stream's index `records` holds its own
+            // blocks of it; the index's last records are then checked against them, and the records in front of those --
+            // the blocks of the ranges on the left -- are kept for the stitch (split.hip: split_xz_streams).  A range that
+            // ends among a stream's blocks leaves its blocks of that stream in `records`
+            bool started = false;        // the walk has taken its start from what was announced
+            bool from_left = false;      // the range starts among the blocks of a stream
+            bool left_closed = false;    // ... and has met that stream's index, at file offset left_index_at
+            uint64_t left_index_at = 0;
+            std::vector<std::pair<uint64_t, uint64_t>> left_kept;
         } xz;
     } file;
 
@@ -344,7 +357,10 @@ void zs_trace_file(const slimm_ctx* c);
 // xz_decode.hip (slimm_push_xz_sam_bytes): xz_round walks what lies at stream.bit -- stream headers, block headers and
 // their chunk chains, indexes, footers, padding -- and leaves the whole blocks at hand, with their exact text offsets, in
 // file.xz.ready.  xz_emit: the blocks decoded, a lane each, their checks folded from pieces and compared, the text written
-// to dst.  An xz stream is not cut by byte range
+// to dst.
+// (A byte range of a split file -- Announced::has_range --: the range starts at a stream header or, told the stream's check
+// kind, at a block's first byte, and ends at a block's first byte or between streams, both SLIMM_E_SPLIT otherwise; nothing
+// in front of the range exists for it, and an empty range decodes no text)
 int xz_round(slimm_ctx* c, bool last);
 bool xz_next_window(const slimm_ctx* c, uint64_t cap, uint64_t* n);
 int xz_emit(slimm_ctx* c, uint8_t* dst, uint64_t cap, uint64_t* n_out, uint8_t* last_byte);

@@ -316,7 +316,7 @@ struct StreamCodec {
     const char* round_key;
     uint64_t round_bytes;
     bool cut_by_range;       // a byte range of a split file may cut it (slimm_set_input_mid_file)
-    bool cut_at_frames;      // ... only where the caller's plan found a frame start: not without slimm_set_input_range
+    bool cut_at_frames;      // ... only where the caller's plan found a frame start (xz: a block start): not without slimm_set_input_range
     int (*round)(slimm_ctx*, bool last);
     bool (*next_window)(const slimm_ctx*, uint64_t cap, uint64_t* n);
     int (*emit)(slimm_ctx*, uint8_t* dst, uint64_t cap, uint64_t* n_out, uint8_t* last_byte);
@@ -330,21 +330,22 @@ struct StreamCodec {
     uint64_t* (*stats)(WindowPipeline&);
     size_t n_stats, stat_compressed;
     const char* article;     // "an" where the name wants it (null: "a")
+    const char* cut_unit;    // cut_at_frames: what a range starts at (null: "frame")
 };
 const StreamCodec kCodecs[] = {
     {},
     // (ended: the range's chain has stopped, what comes now are bytes of the slack)
     {"bzip2", "bzip2_round", 32ull << 20, true, false, bz2_decode_batch, bz2_next_window, bz2_emit, nullptr, bz2_trace_file, nullptr,
-     [](const File& F) { return F.bz2.chain.ended; }, nullptr, 0, 0, nullptr},
+     [](const File& F) { return F.bz2.chain.ended; }, nullptr, 0, 0, nullptr, nullptr},
     {"gzip", "gzip_round", 32ull << 20, false, false, gz_round, gz_next_window, gz_emit, nullptr, gz_trace_file,
      [](const File& F) { return static_cast<int>(F.gz.stage); }, nullptr, [](WindowPipeline& W) { return W.gz_stats; },
-     WindowPipeline::kGzStats, WindowPipeline::kGzCompressed, nullptr},
+     WindowPipeline::kGzStats, WindowPipeline::kGzCompressed, nullptr, nullptr},
     {"zstd", "zstd_round", kZstdRoundBytes, true, true, zs_round, zs_next_window, zs_emit, zs_check, zs_trace_file,
      [](const File& F) { return static_cast<int>(F.zst.stage); }, nullptr, [](WindowPipeline& W) { return W.zs_stats; },
-     WindowPipeline::kZsStats, WindowPipeline::kZsCompressedBytes, nullptr},
-    {"xz", "xz_round", 32ull << 20, false, false, xz_round, xz_next_window, xz_emit, nullptr, xz_trace_file,
+     WindowPipeline::kZsStats, WindowPipeline::kZsCompressedBytes, nullptr, nullptr},
+    {"xz", "xz_round", 32ull << 20, true, true, xz_round, xz_next_window, xz_emit, nullptr, xz_trace_file,
      [](const File& F) { return static_cast<int>(F.xz.stage); }, nullptr, [](WindowPipeline& W) { return W.xz_stats; },
-     WindowPipeline::kXzStats, WindowPipeline::kXzCompressedBytes, "an"},
+     WindowPipeline::kXzStats, WindowPipeline::kXzCompressedBytes, "an", "block"},
 };
 const StreamCodec& codec_of(Codec k) { return kCodecs[static_cast<size_t>(k)]; }
 
@@ -404,7 +405,8 @@ int check_push(slimm_ctx* c, Push& p) {
         return fail(c, SLIMM_E_INVALID, "%s SAM bytes and the other forms do not mix within a file", codec_of(named).name);
     if (K.name && !K.cut_by_range && mid) return fail(c, SLIMM_E_INVALID, "%s %s stream is not cut by byte range", K.article ? K.article : "a", K.name);
     if (K.name && K.cut_at_frames && mid && !c->win.announced.has_range)
-        return fail(c, SLIMM_E_INVALID, "a %s stream is not cut by byte range unless its range is announced (slimm_set_input_range) and starts at a frame", K.name);
+        return fail(c, SLIMM_E_INVALID, "%s %s stream is not cut by byte range unless its range is announced (slimm_set_input_range) and starts at a %s",
+                    K.article ? K.article : "a", K.name, K.cut_unit ? K.cut_unit : "frame");
     if (K.name && p.skip && F.active) return fail(c, SLIMM_E_INVALID, "skip: only in front of a file's first records");
     if (K.name && K.cut_by_range && !F.active && mid && !c->win.announced.has_range)
         return fail(c, SLIMM_E_INVALID, "slimm_set_input_range first: a range of a %s file is cut at bits, told by where it lies in the file", K.name);
@@ -735,6 +737,13 @@ int slimm_set_input_range(slimm_ctx* c, uint64_t begin, uint64_t end) {
     c->win.announced.has_range = true;
     c->win.announced.range_begin = begin;
     c->win.announced.range_end = end;
+    return SLIMM_OK;
+}
+int slimm_set_xz_range_check(slimm_ctx* c, int check) {
+    if (!c) return SLIMM_E_INVALID;
+    if (c->win.file.active) return fail(c, SLIMM_E_INVALID, "slimm_set_xz_range_check: before the range's first window");
+    if (check < -1 || check > 15) return fail(c, SLIMM_E_INVALID, "slimm_set_xz_range_check: a check kind is 0 to 15, or -1 for none told");
+    c->win.announced.xz_check = check;
     return SLIMM_OK;
 }
 int slimm_set_input_size_hint(slimm_ctx* c, uint64_t compressed_bytes) {

@@ -13,6 +13,9 @@
 //   k_xz_check    a thread per gz::kPiece bytes of text: the block's CRC32 or CRC64 register over the piece, from 0;
 //   k_xz_fold     a thread per block sums its pieces (xz_stream.h: crc64_mul; deflate_stream.h: crc_mul)
 //   (host)        the registers against the blocks' check fields.  SHA-256 is NOT verified: such blocks are counted
+// A byte range of a split file (include/slimm_hip.h, "xz SAM by byte range") changes the host's walk alone: where it starts --
+// at a stream header, or among a stream's blocks with the check kind it was told --, where it must stop, and what it keeps of
+// an index whose first records are blocks of the ranges on its left (split.hip: split_xz_streams holds them against those).
 // No workgroup waits for another.  One round is one window; the window then goes to the SAM finder and decoder as any text
 // window does (windows.hip).  NOT MEASURED on an MI355X: nothing is known of an LZMA lane's rate there.
 #include "context.h"
@@ -196,11 +199,32 @@ int xz_round(slimm_ctx* c, bool last) {
     long cap_text = 0;
     if (!forced("xz_round_text", &cap_text) || cap_text <= 0) cap_text = static_cast<long>(kXzRoundText);
     auto at = [&](uint64_t byte) { return std::to_string(T.base + byte); };
+    // a byte range of a split file (check_push: its range is announced).  It starts at a stream header or -- told the check
+    // kind of the stream around it, which sizes the field behind every block -- at a block's first byte, and ends at a
+    // block's first byte or between streams, or the cut is refused: SLIMM_E_SPLIT, no verdict on the file
+    const WindowPipeline::Announced& A = W.announced;
+    const bool starts_mid = A.has_range && A.starts_mid, ends_mid = A.has_range && A.ends_mid;
+    auto no_start = [&](uint64_t byte, const char* what) {
+        return fail(c, SLIMM_E_SPLIT, "xz: the range starts at byte %s, where no %s starts", at(byte).c_str(), what);
+    };
+    auto no_end = [&](const std::string& where) {
+        return fail(c, SLIMM_E_SPLIT, "xz: %s runs past byte %llu: the range does not end at a block boundary", where.c_str(),
+                    static_cast<unsigned long long>(A.range_end));
+    };
+    if (!Z.started) {
+        Z.started = true;
+        if (starts_mid && A.xz_check >= 0) {   // (among the blocks of a stream whose header lies in a range on the left)
+            Z.stage = Stage::Blocks;
+            Z.check = static_cast<uint32_t>(A.xz_check);
+            Z.from_left = true;
+            Z.any_streams = 1;
+        }
+    }
     // what a step lacks: more bytes may come, or the file ends inside it
     // (errors come in file order: what is wrong behind blocks that are ready is looked at again by the next round, once
     // those blocks are decoded -- nothing is read past it: XZ_FAIL)
     auto wait_or = [&](const std::string& where) {
-        if (last && Z.ready.empty()) return xz_fail(c, where, xz::kRanOut);
+        if (last && Z.ready.empty()) return ends_mid ? no_end(where) : xz_fail(c, where, xz::kRanOut);
         if (!last) T.waiting = true;
         return static_cast<int>(SLIMM_OK);
     };
@@ -213,15 +237,19 @@ int xz_round(slimm_ctx* c, bool last) {
         if (Z.stage == Stage::Between) {
             while (Z.any_streams > 0 && avail >= 4u && all_zero(p + pos, 4)) pos += 4u, avail -= 4u;   // (stream padding)
             if (avail < xz::kHeaderBytes) {
-                if (!last || (avail == 0 && Z.any_streams > 0)) {   // (the file may end here)
+                if (!last || (avail == 0 && (Z.any_streams > 0 || starts_mid || ends_mid))) {   // (the file may end here; a range may be empty)
                     T.waiting = true;
                     break;
                 }
+                if (ends_mid) XZ_FAIL(no_end("what starts at byte " + at(pos)));
+                if (starts_mid && Z.any_streams == 0) XZ_FAIL(no_start(pos, "stream"));
                 if (Z.any_streams == 0 || xz::magic_prefix(p + pos, avail)) XZ_FAIL(xz_fail(c, "stream header at byte " + at(pos), xz::kRanOut));
                 XZ_FAIL(xz_fail(c, "at byte " + at(pos), all_zero(p + pos, avail) ? xz::kBadPadding : xz::kTrailing));
             }
+            if (!xz::is_magic(p + pos) && starts_mid && Z.any_streams == 0) XZ_FAIL(no_start(pos, "stream"));
             if (!xz::is_magic(p + pos)) XZ_FAIL(xz_fail(c, "at byte " + at(pos), Z.any_streams > 0 && p[pos] == 0 ? xz::kBadPadding : xz::kTrailing));
             const uint32_t hs = xz::stream_header(p + pos, &Z.check);
+            if (hs != xz::kOk && starts_mid && Z.any_streams == 0) XZ_FAIL(no_start(pos, "stream"));   // (the magic's bytes, inside some block)
             if (hs != xz::kOk) XZ_FAIL(xz_fail(c, "stream header at byte " + at(pos), hs));
             pos += xz::kHeaderBytes;
             Z.records.clear();
@@ -231,9 +259,16 @@ int xz_round(slimm_ctx* c, bool last) {
             continue;
         }
         if (avail < 1u) {
+            if (ends_mid) {   // (a range may end at a block's first byte: the stitch holds the walker's place against the range's end)
+                T.waiting = true;
+                break;
+            }
             SLIMM_TRY(wait_or("block header at byte " + at(pos)));
             break;
         }
+        // (the first thing of a range that starts among a stream's blocks is a block)
+        const bool at_start = Z.from_left && T.base + pos == A.range_begin;
+        if (p[pos] == 0 && at_start) XZ_FAIL(no_start(pos, "block"));
         if (p[pos] == 0) {   // the index, and the footer behind it
             uint64_t count = 0, first = 0, bytes = 0;
             const std::string where = "index at byte " + at(pos);
@@ -247,18 +282,37 @@ int xz_round(slimm_ctx* c, bool last) {
                 SLIMM_TRY(wait_or("stream footer at byte " + at(pos + bytes)));
                 break;
             }
-            bool same = count == Z.records.size();
+            // (of a stream whose header lies on the left the index's last records are this range's blocks; the records in
+            // front of them are kept for the stitch, which holds them against the blocks of the ranges on the left)
+            const bool open_left = Z.from_left && !Z.left_closed;
+            bool same = open_left ? count >= Z.records.size() : count == Z.records.size();
+            std::vector<std::pair<uint64_t, uint64_t>> kept;
+            for (uint64_t r = 0; same && open_left && r < count - Z.records.size(); ++r) {
+                uint64_t unpadded = 0, uncompressed = 0;
+                xz::index_record(p + pos, bytes, &first, &unpadded, &uncompressed);
+                kept.emplace_back(unpadded, uncompressed);
+            }
             for (size_t r = 0; same && r < Z.records.size(); ++r) {
                 uint64_t unpadded = 0, uncompressed = 0;
                 xz::index_record(p + pos, bytes, &first, &unpadded, &uncompressed);
                 same = unpadded == Z.records[r].first && uncompressed == Z.records[r].second;
             }
             if (!same) XZ_FAIL(xz_fail(c, where, xz::kIndexMismatch));
-            stats[WindowPipeline::kXzIndexRecords] += count;
+            const uint8_t* foot = p + pos + bytes;
             uint64_t stated = 0;
-            uint32_t fs = xz::stream_footer(p + pos + bytes, Z.check, &stated);
+            if (open_left && foot[9] != Z.check && xz::stream_footer(foot, foot[9], &stated) == xz::kOk)
+                XZ_FAIL(fail(c, SLIMM_E_SPLIT, "xz: the stream footer at byte %s states check kind %u, the range was told %u", at(pos + bytes).c_str(),
+                             static_cast<unsigned>(foot[9]), static_cast<unsigned>(Z.check)));
+            uint32_t fs = xz::stream_footer(foot, Z.check, &stated);
             if (fs == xz::kOk && stated != bytes) fs = xz::kBadFooter;
             if (fs != xz::kOk) XZ_FAIL(xz_fail(c, "stream footer at byte " + at(pos + bytes), fs));
+            stats[WindowPipeline::kXzIndexRecords] += count;
+            if (open_left) {
+                Z.left_kept = std::move(kept);
+                Z.left_closed = true;
+                Z.left_index_at = T.base + pos;
+            }
+            Z.records.clear();
             pos += bytes + xz::kHeaderBytes;
             Z.stage = Stage::Between;
             continue;
@@ -267,10 +321,11 @@ int xz_round(slimm_ctx* c, bool last) {
         const std::string where = "block at byte " + at(pos);
         xz::BlockHeader bh{};
         const uint32_t hs = xz::block_header(p + pos, avail, bh);
-        if (hs == xz::kRanOut) {
+        if (hs == xz::kRanOut && !(last && at_start)) {
             SLIMM_TRY(wait_or("block header at byte " + at(pos)));
             break;
         }
+        if (hs != xz::kOk && hs != xz::kBadFilter && at_start) XZ_FAIL(no_start(pos, "block"));
         if (hs == xz::kBadFilter) XZ_FAIL(xz_fail(c, "block header at byte " + at(pos), hs, " (filter id " + std::to_string(bh.filter_id) + ")"));
         if (hs != xz::kOk) XZ_FAIL(xz_fail(c, "block header at byte " + at(pos), hs));
         uint64_t q = pos + bh.bytes, btext = 0;

@@ -843,20 +843,22 @@ class SlimmGroup:
             e = min(n, s + step)
             self._check(self.L.slimm_group_push_records_marked(self.g, _p(w[s:e]), _p(rec.begin_pos[s:e]), e - s))
 
-    SPLIT_FORMS = ("bam", "sam", "bgzf_sam", "bzip2_sam", "zstd_sam")
+    SPLIT_FORMS = ("bam", "sam", "bgzf_sam", "bzip2_sam", "zstd_sam", "xz_sam")
 
-    def push_split(self, data, form: str, skip: int = 0, window: int = 0, offsets=None):
+    def push_split(self, data, form: str, skip: int = 0, window: int = 0, offsets=None, xz_checks=None):
         """One file split by byte range, every member its own (include/slimm_hip.h, "ONE FILE SPLIT BY BYTE RANGE"): GROUPED by
         read name, or -- a group made with grouped=False -- in any order, in which case the stitch deals the records by key.
         `data`: the whole file -- header included -- as bytes, or its path; `form`: "bam" (BGZF blocks of BAM records), "sam"
-        (plain text), "bgzf_sam" (BGZF blocks of SAM text), "bzip2_sam" (bzip2-compressed SAM text) or "zstd_sam" (zstd-compressed
-        SAM text of several frames); `skip`: the header's
+        (plain text), "bgzf_sam" (BGZF blocks of SAM text), "bzip2_sam" (bzip2-compressed SAM text), "zstd_sam" (zstd-compressed
+        SAM text of several frames) or "xz_sam" (xz-compressed SAM text of several blocks); `skip`: the header's
         bytes (for the compressed forms its INFLATED / DECODED bytes).  The ranges come from slimm_host_text_ranges /
-        slimm_host_bgzf_ranges / slimm_host_bzip2_ranges / slimm_host_zstd_ranges; member by member: the reference names (SAM),
+        slimm_host_bgzf_ranges / slimm_host_bzip2_ranges / slimm_host_zstd_ranges / slimm_host_xz_ranges; member by member: the reference names (SAM),
         slimm_set_input_mid_file, the size hint, the range pushed in windows of `window` bytes (0: one); then
         slimm_group_stitch_ranges.  A bzip2 member also announces its range's file offsets (slimm_set_input_range) and
         pushes its range plus slimm_bzip2_split_slack() bytes behind it (at most to the file's end).  A zstd member announces its range too and pushes exactly its range: the
-        planner cuts at frame starts only, and a cut anywhere else is SLIMM_E_SPLIT.  `offsets`: the n + 1
+        planner cuts at frame starts only, and a cut anywhere else is SLIMM_E_SPLIT.  An xz member announces its range and, beside
+        it, the check kind of the stream its range starts in (slimm_host_xz_check_at -> slimm_set_xz_range_check; `xz_checks`:
+        the n kinds to tell instead), and pushes exactly its range.  `offsets`: the n + 1
         offsets to use instead of the planner's (bzip2 is cut at any byte behind the header's block).  Returns (the n + 1 offsets, the records every member decoded before the stitch)."""
         # (the planners, the announcements and the pushes are the same for both orders)
         import os
@@ -865,23 +867,39 @@ class SlimmGroup:
         assert form in self.SPLIT_FORMS, form
         G = len(self.devices)
         offs = (C.c_uint64 * (G + 1))()
-        plan = {"sam": self.L.slimm_host_text_ranges, "bzip2_sam": self.L.slimm_host_bzip2_ranges,
-                "zstd_sam": self.L.slimm_host_zstd_ranges}.get(form, self.L.slimm_host_bgzf_ranges)
-        if offsets is not None:
-            assert len(offsets) == G + 1
-            offs[:] = list(offsets)
-            blob, rc = (open(os.fspath(data), "rb").read() if isinstance(data, (str, os.PathLike)) else bytes(data)), capi.OK
-        elif isinstance(data, (str, os.PathLike)):
+        plan = {"sam": self.L.slimm_host_text_ranges, "bzip2_sam": self.L.slimm_host_bzip2_ranges, "zstd_sam": self.L.slimm_host_zstd_ranges,
+                "xz_sam": self.L.slimm_host_xz_ranges}.get(form, self.L.slimm_host_bgzf_ranges)
+        checks = list(xz_checks) if xz_checks is not None else None
+
+        def planned(path):   # the offsets, unless given; an xz file: the check kind at every range's start, unless given
+            nonlocal checks
+            rc = capi.OK
+            if offsets is not None:
+                assert len(offsets) == G + 1
+                offs[:] = list(offsets)
+            else:
+                rc = plan(path.encode(), int(skip), G, offs)
+            if rc == capi.OK and form == "xz_sam" and checks is None:
+                checks = []
+                for i in range(G):
+                    kind = C.c_int(-1)
+                    rc = rc or self.L.slimm_host_xz_check_at(path.encode(), offs[i], C.byref(kind))
+                    checks.append(kind.value)
+            return rc
+
+        if isinstance(data, (str, os.PathLike)):
             path = os.fspath(data)
             with open(path, "rb") as f:
                 blob = f.read()
-            rc = plan(path.encode(), int(skip), G, offs)
+            rc = planned(path)
+        elif offsets is not None and (form != "xz_sam" or checks is not None):   # (nothing is asked of a file)
+            blob, rc = bytes(data), planned("")
         else:
             blob = bytes(data)
             with tempfile.NamedTemporaryFile(suffix="." + form) as f:   # (the planners read a file)
                 f.write(blob)
                 f.flush()
-                rc = plan(f.name.encode(), int(skip), G, offs)
+                rc = planned(f.name)
         if rc != capi.OK:
             raise capi.SlimmError(rc, "the file could not be planned into ranges")
         counts = []
@@ -899,6 +917,10 @@ class SlimmGroup:
             elif form == "zstd_sam":
                 m._check(self.L.slimm_set_input_range(m.ctx, offs[i], offs[i + 1]))
                 counts.append(m.push_zstd_sam_bytes(part, skip=skip if i == 0 else 0, window=window))
+            elif form == "xz_sam":
+                m._check(self.L.slimm_set_input_range(m.ctx, offs[i], offs[i + 1]))
+                m._check(self.L.slimm_set_xz_range_check(m.ctx, checks[i]))
+                counts.append(m.push_xz_sam_bytes(part, skip=skip if i == 0 else 0, window=window))
             elif form == "sam":
                 counts.append(m.push_sam_bytes(part, window=window))
             else:
