@@ -647,6 +647,42 @@ void slimm_host_q18_note(slimm_q18_runs* q, int starts_run, int shortened);
 int slimm_host_q18_regroup_needed(const slimm_q18_runs* q);
 /* The same two counts of the file a context's device decoders have read so far (0, 0 for any other record form). */
 int slimm_get_q18_runs(slimm_ctx* ctx, uint64_t* short_starts, uint64_t* short_to_plain);
+/* ---- THE RECORD FILTER (slimm_amd/csrc/record_filter.h holds the one definition): which alignment records the readers of
+ * a file's BYTES leave out -- what samtools view takes as -q, -f and -F, plus a least number of aligned bases and a least
+ * identity.  A filtered record is handed on as NOT MAPPED (flag | 0x4; run-marked form: reference word 0), so it is what a
+ * copy of the file without that record's alignment would give.  An all-zero filter is off.
+ *   A record is JUDGED only if its own 0x4 bit is clear; the flag judged is the file's (not the mate bit Q18 derives from a
+ *   name).  The criteria are tried in this order -- flags, MAPQ, aligned length, identity -- and a dropped record is counted
+ *   under the first it fails.
+ *   aligned = M + = + X bases, columns = M + = + X + I + D of the CIGAR FIELD (a long CIGAR kept in a CG tag is not
+ *   followed); "*" / no op: 0 and 0, which fails any min_aligned > 0 and any min_identity_permille > 0.
+ *   identity: the record passes iff NM is present (BAM: of any integer type), columns > 0, NM <= columns and
+ *   (columns - NM) * 1000 >= min_identity_permille * columns.  A record without NM (BAM: or with a tag area that does not
+ *   parse) fails a non-zero identity threshold and is counted as no_nm as well.
+ * The filter is part of a context's configuration: set before a file's first push (afterwards: an error), kept across
+ * slimm_reset.  It applies to the byte pushes (slimm_push_bam_bytes, _bgzf_blocks, _sam_bytes, ... every form).  Record
+ * ARRAYS carry no MAPQ or CIGAR: there the filter is the producer's job, which calls slimm_host_record_passes_* per record
+ * and hands a dropped record on with flag | 0x4.  Filtered records still count toward slimm_record_cap(). */
+typedef struct slimm_record_filter {
+    uint32_t min_mapq;              /* drop MAPQ < min_mapq (255 is a number like any other, as samtools -q) */
+    uint32_t require_flags;         /* drop unless (flag & require) == require   (samtools -f) */
+    uint32_t exclude_flags;         /* drop if (flag & exclude) != 0             (samtools -F) */
+    uint32_t min_aligned;           /* drop if M + = + X bases < min_aligned */
+    uint32_t min_identity_permille; /* 0..1000 */
+    uint32_t reserved[3];           /* must be 0 */
+} slimm_record_filter;
+/* f == NULL: off.  Refused: permille > 1000, flag masks above 0xffff, non-zero reserved words, a file already begun. */
+int slimm_set_record_filter(slimm_ctx* ctx, const slimm_record_filter* f);
+/* out[] = judged, dropped_flags, dropped_mapq, dropped_aligned, dropped_identity, no_nm, 0, 0 of the file's byte pushes so
+ * far (no_nm is a subset of dropped_identity); cleared by slimm_reset.  Member 0 of a group: the sum over the members. */
+int slimm_get_record_filter_stats(slimm_ctx* ctx, uint64_t out[8]);
+/* One record against a filter, on the host: 1 = keep it as it is, 0 = dropped.  *why (may be NULL): 0 passes, 1 flags,
+ * 2 MAPQ, 3 aligned length, 4 identity, 5 identity for want of NM, 6 not judged (its 0x4 bit is set: kept as it is).
+ * BAM: `record` is the record behind its block_size word and n_bytes that block_size; SAM: `line` is one alignment line,
+ * n_bytes its length without (or with) the newline.  No byte outside [0, n_bytes) is read, whatever the bytes say.
+ * -1: a NULL argument or a filter slimm_set_record_filter would refuse. */
+int slimm_host_record_passes_bam(const slimm_record_filter* f, const uint8_t* record, uint32_t n_bytes, int* why);
+int slimm_host_record_passes_sam(const slimm_record_filter* f, const char* line, uint32_t n_bytes, int* why);
 /* hipDeviceReset() of the process's devices: for a host about to leave the process.  Contexts must not be used afterwards. */
 int slimm_shutdown(void);
 /* Library build info. */
@@ -668,6 +704,9 @@ uint32_t slimm_group_size(const slimm_group* g);
 slimm_ctx* slimm_group_context(slimm_group* g, uint32_t i);
 int slimm_group_uses_rccl(const slimm_group* g);
 int slimm_group_reset(slimm_group* g);
+/* slimm_set_record_filter on every member (a file split over the members is filtered by each in its own range; the stats
+ * are read from member 0, which sums them). */
+int slimm_group_set_record_filter(slimm_group* g, const slimm_record_filter* f);
 int slimm_group_push_records(slimm_group* g, const uint64_t* read_key, const int32_t* ref_id, const int32_t* begin_pos,
                              const uint16_t* flag, uint64_t n);
 /* Packed 16-byte records (slimm_push_records_packed; the identity of a read name is the key's low 61 bits). */

@@ -66,6 +66,14 @@ class Stats(C.Structure):
         ("n_records", C.c_uint64), ("n_targets", C.c_uint64), ("total_bins", C.c_uint64)]
 
 
+class RecordFilter(C.Structure):
+    _fields_ = [("min_mapq", C.c_uint32), ("require_flags", C.c_uint32), ("exclude_flags", C.c_uint32),
+                ("min_aligned", C.c_uint32), ("min_identity_permille", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+RECORD_FILTER_STATS = ("judged", "dropped_flags", "dropped_mapq", "dropped_aligned", "dropped_identity", "no_nm")
+
+
 class RefColumns(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in (
         "reads_count", "uniq_reads_count", "uniq_reads_count2", "nbins", "nz_cov", "nz_uniq_cov", "nz_uniq_cov2",
@@ -193,6 +201,11 @@ SYMBOLS = [
     ("slimm_host_q18_note", None, [_P, C.c_int, C.c_int]),
     ("slimm_host_q18_regroup_needed", C.c_int, [_P]),
     ("slimm_get_q18_runs", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("slimm_set_record_filter", C.c_int, [_P, C.POINTER(RecordFilter)]),
+    ("slimm_group_set_record_filter", C.c_int, [_P, C.POINTER(RecordFilter)]),
+    ("slimm_get_record_filter_stats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    ("slimm_host_record_passes_bam", C.c_int, [C.POINTER(RecordFilter), _P, C.c_uint32, C.POINTER(C.c_int)]),
+    ("slimm_host_record_passes_sam", C.c_int, [C.POINTER(RecordFilter), _P, C.c_uint32, C.POINTER(C.c_int)]),
     ("slimm_host_bgzf_ranges", C.c_int, [C.c_char_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]),
     ("slimm_host_text_ranges", C.c_int, [C.c_char_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]),
     ("slimm_set_input_mid_file", C.c_int, [_P, C.c_int, C.c_int]),

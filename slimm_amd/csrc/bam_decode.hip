@@ -295,13 +295,16 @@ __device__ __forceinline__ uint32_t bam_canonical(const uint8_t* name, uint32_t&
     return fl;
 }
 
-// a wave per piece, a lane per record
-template <bool kMarked>
+// a wave per piece, a lane per record.  kFilter: fa is the one DecodeFilter (kernels.h) -- the lane judges the record it
+// holds (record_filter.h) and writes a dropped one as not mapped; without it there is no such argument and no such code
+__device__ __forceinline__ const DecodeFilter& filter_of(const DecodeFilter& fa) { return fa; }
+template <bool kMarked, bool kFilter, typename... FilterArg>
 __global__ __launch_bounds__(64) void k_bam_decode(const uint8_t* __restrict__ b, const BamPiece* __restrict__ pieces,
                                                    const uint32_t* __restrict__ offs, uint32_t n_pieces, BamCarry* __restrict__ carry,
                                                    const BamWindowResult* __restrict__ res, uint64_t out_at, uint64_t* __restrict__ key,
                                                    int32_t* __restrict__ ref, int32_t* __restrict__ pos, uint16_t* __restrict__ flag,
-                                                   uint32_t* __restrict__ check) {
+                                                   uint32_t* __restrict__ check, FilterArg... fa) {
+    static_assert(sizeof...(FilterArg) == (kFilter ? 1 : 0), "the filter is an argument of the kFilter instantiation alone");
     const uint32_t c = blockIdx.x;
     const BamPiece pc = pieces[c];
     const uint32_t* po = offs + static_cast<size_t>(c) * kBamSlots;
@@ -318,6 +321,7 @@ __global__ __launch_bounds__(64) void k_bam_decode(const uint8_t* __restrict__ b
         }
     }
     uint32_t n_short_starts = 0, n_short_to_plain = 0;
+    uint32_t n_verdicts[SLIMM_RF_N_NO_NM + 1] = {};
     for (uint32_t k = threadIdx.x; k < pc.count; k += 64u) {
         const uint8_t* r = b + po[k] + 4;
         const int32_t rid = static_cast<int32_t>(ld_u32(r));
@@ -328,6 +332,12 @@ __global__ __launch_bounds__(64) void k_bam_decode(const uint8_t* __restrict__ b
         const uint32_t fl0 = ld_u16(r + 14);
         const uint32_t fl = bam_canonical(name, nlen, fl0);
         const uint64_t at = out_at + pc.base + k;
+        bool dropped = false;
+        if constexpr (kFilter) {   // (the record lies whole in front of the window's end: bam_walk)
+            const int why = slimm_rf_bam(&filter_of(fa...).f, r, ld_u32(r - 4));
+            slimm_rf_lane_count(n_verdicts, why);
+            dropped = slimm_rf_dropped(why) != 0;
+        }
         if (kMarked) {
             bool starts, prev_short;
             const uint32_t po_prev = k ? po[k - 1] : prev0;
@@ -348,7 +358,8 @@ __global__ __launch_bounds__(64) void k_bam_decode(const uint8_t* __restrict__ b
             n_short_to_plain += (!is_short & !starts & prev_short) ? 1u : 0u;
             // slimm_mark_word (context.hip): reference + 1 (0: not mapped) | mate << 29 | starts a qName run << 31
             const uint32_t mate = (fl & 0x40u) ? 1u : ((fl & 0x80u) ? 2u : 0u);
-            const bool mapped = !(fl & 0x4u) && rid != -1;
+            bool mapped = !(fl & 0x4u) && rid != -1;
+            if constexpr (kFilter) mapped = mapped & !dropped;
             const uint32_t r1 = mapped ? min(static_cast<uint32_t>(rid) + 1u, 0x1fffffffu) : 0u;
             reinterpret_cast<uint32_t*>(ref)[at] = r1 | (mate << 29) | (starts ? 0x80000000u : 0u);
             pos[at] = rpos;
@@ -356,7 +367,7 @@ __global__ __launch_bounds__(64) void k_bam_decode(const uint8_t* __restrict__ b
             key[at] = bam_hash_name(name, nlen);
             ref[at] = rid;
             pos[at] = rpos;
-            flag[at] = static_cast<uint16_t>(fl);
+            flag[at] = static_cast<uint16_t>(fl | (dropped ? 0x4u : 0u));
             check[at] = bam_check_name(name, nlen);
         }
     }
@@ -370,6 +381,7 @@ __global__ __launch_bounds__(64) void k_bam_decode(const uint8_t* __restrict__ b
             if (n_short_to_plain) atomicAdd(&carry->short_to_plain, n_short_to_plain);
         }
     }
+    if constexpr (kFilter) slimm_rf_wave_add(filter_of(fa...).counts, n_verdicts);
 }
 
 // the window's last record's name -> the carry (after k_bam_decode of the same window has read the old one)
@@ -486,14 +498,21 @@ void launch_bam_scan(hipStream_t st, BamPiece* pieces, uint32_t n_pieces, uint64
 
 void launch_bam_decode(hipStream_t st, const uint8_t* bytes, uint64_t lo, uint64_t end, const BamPiece* pieces, const uint32_t* offs,
                        BamCarry* carry, const BamWindowResult* result, bool marked, uint64_t out_at, uint64_t* key, int32_t* ref,
-                       int32_t* pos, uint16_t* flag, uint32_t* check) {
+                       int32_t* pos, uint16_t* flag, uint32_t* check, slimm_record_filter filter, uint32_t* filter_counts) {
     const uint32_t np = bam_pieces(end - lo);
     if (!np) return;
-    if (marked)
-        hipLaunchKernelGGL(k_bam_decode<true>, dim3(np), dim3(64), 0, st, bytes, pieces, offs, np, carry, result, out_at, key, ref, pos,
+    const DecodeFilter fa{filter, filter_counts};
+    if (slimm_rf_on(&filter) && marked)
+        hipLaunchKernelGGL((k_bam_decode<true, true, DecodeFilter>), dim3(np), dim3(64), 0, st, bytes, pieces, offs, np, carry, result, out_at, key,
+                           ref, pos, flag, check, fa);
+    else if (slimm_rf_on(&filter))
+        hipLaunchKernelGGL((k_bam_decode<false, true, DecodeFilter>), dim3(np), dim3(64), 0, st, bytes, pieces, offs, np, carry, result, out_at, key,
+                           ref, pos, flag, check, fa);
+    else if (marked)
+        hipLaunchKernelGGL((k_bam_decode<true, false>), dim3(np), dim3(64), 0, st, bytes, pieces, offs, np, carry, result, out_at, key, ref, pos,
                            flag, check);
     else
-        hipLaunchKernelGGL(k_bam_decode<false>, dim3(np), dim3(64), 0, st, bytes, pieces, offs, np, carry, result, out_at, key, ref, pos,
+        hipLaunchKernelGGL((k_bam_decode<false, false>), dim3(np), dim3(64), 0, st, bytes, pieces, offs, np, carry, result, out_at, key, ref, pos,
                            flag, check);
     hipLaunchKernelGGL(k_bam_carry, dim3(1), dim3(64), 0, st, bytes, pieces, offs, result, carry);
 }

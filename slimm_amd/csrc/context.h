@@ -173,6 +173,7 @@ struct slimm_ctx {
     bool packed = false;           // slimm_push_records_packed: 16 bytes per record, no flag array (forms do not mix)
     bool marked = false;           // slimm_push_records_marked: 8 bytes per record, no key array (grouped input only)
     WindowPipeline win;     // a file's bytes in windows, inflated and decoded on the device (windows.h, windows.hip)
+    std::vector<slimm_ctx*> filter_peers;   // member 0 of a group: the other members (its record filter stats are the group's)
     DeviceRecords rec;      // what analyze reads (owned buffers or borrowed pointers)
     bool borrowed = false;
     uint64_t n_pushed = 0;

@@ -6,6 +6,7 @@
 //   filter          : lineage rows with the valid bit up (16 bytes per reference); uniq2 / LCA counts / child marks down
 // both through pinned host memory that a copy kernel reads / writes (no DMA-engine start-up latency).
 // Multi-GPU entry points (coverage summary in all-gather or all-to-all form, device-side partials merge) are further down.
+#define SLIMM_RF_HOST_API   // (record_filter.h: slimm_host_record_passes_bam / _sam are defined in this translation unit)
 #include "context.h"
 
 namespace slimm {
@@ -1589,6 +1590,32 @@ int slimm_get_q18_runs(slimm_ctx* c, uint64_t* short_starts, uint64_t* short_to_
     *short_to_plain = c->win.file.q18_plain;
     return SLIMM_OK;
 }
+// ---- the record filter (record_filter.h)
+int slimm_set_record_filter(slimm_ctx* c, const slimm_record_filter* f) {
+    if (!c) return SLIMM_E_INVALID;
+    const slimm_record_filter off{};
+    if (!f) f = &off;
+    if (f->min_identity_permille > 1000u) return fail(c, SLIMM_E_INVALID, "record filter: min_identity_permille is 0 .. 1000");
+    if (f->require_flags > 0xffffu || f->exclude_flags > 0xffffu) return fail(c, SLIMM_E_INVALID, "record filter: a flag mask has 16 bits");
+    if (!slimm_rf_valid(f)) return fail(c, SLIMM_E_INVALID, "record filter: the reserved words must be 0");
+    if (c->win.file.active || c->n_pushed || c->borrowed)
+        return fail(c, SLIMM_E_INVALID, "the record filter is set before a file's first push; reset first");
+    c->win.filter = *f;
+    return SLIMM_OK;
+}
+int slimm_get_record_filter_stats(slimm_ctx* c, uint64_t out[8]) {
+    if (!c || !out) return SLIMM_E_INVALID;
+    static_assert(SLIMM_RF_N_STATS == 8, "slimm_get_record_filter_stats: eight counters");
+    SLIMM_TRY(fetch_filter_stats(c, out));
+    for (slimm_ctx* peer : c->filter_peers) {
+        uint64_t theirs[SLIMM_RF_N_STATS];
+        const int rc = fetch_filter_stats(peer, theirs);
+        if (rc != SLIMM_OK) return fail(c, rc, "%s", peer->err.c_str());
+        for (int k = 0; k < SLIMM_RF_N_STATS; ++k) out[k] += theirs[k];
+    }
+    return SLIMM_OK;
+}
+// (slimm_host_record_passes_bam / _sam: record_filter.h, SLIMM_RF_HOST_API -- defined at the top of this file)
 uint32_t slimm_host_bin_of(int32_t begin_pos, uint32_t avg_read_len, uint32_t ref_len, uint32_t bin_width) {
     uint32_t center = std::min(static_cast<uint32_t>(begin_pos) + (avg_read_len / 2), ref_len);  // slimm.hpp:200
     return bin_width ? center / bin_width : 0;                                                   // slimm.hpp:201

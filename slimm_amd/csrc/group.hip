@@ -510,6 +510,8 @@ int slimm_group_create(const slimm_config* cfg, const int* devices, uint32_t n_d
         slimm_group_destroy(g);
         return SLIMM_E_HIP;
     }
+    // (slimm_get_record_filter_stats of member 0: the sum over the members)
+    slimm::group_filter_peers(g->ctx[0], g->ctx.data() + 1, n_devices - 1u);
     if (n_devices > 1 || g->use_rccl)  // the collectives run on the members' streams: no host fences around them
         for (slimm_ctx* c : g->ctx) (void)slimm_set_stream_ordered(c, 1);
     *out = g;
@@ -555,6 +557,12 @@ int slimm_group_reset(slimm_group* g) {
     g->checked = -1;
     g->have_last = false;
     g->stitched = false;
+    return SLIMM_OK;
+}
+
+int slimm_group_set_record_filter(slimm_group* g, const slimm_record_filter* f) {
+    if (!g) return SLIMM_E_INVALID;
+    for (uint32_t i = 0; i < g->ctx.size(); ++i) GTRY(g, i, slimm_set_record_filter(g->ctx[i], f));
     return SLIMM_OK;
 }
 

@@ -302,6 +302,7 @@ bool AlignmentFile::open(const std::string& path) {
     have_last_ = false;
     last_short_ = false;
     q18_short_starts_ = q18_short_to_plain_ = 0;
+    std::fill(filter_stats_, filter_stats_ + SLIMM_RF_N_STATS, 0ull);
     threads_ = settings().threads ? settings().threads : default_threads();
     workers_.reset(new Workers(threads_));
     inflaters_.reset(new Workers(threads_));  // (the prefetch thread's own: its jobs run beside the decode jobs)
@@ -1222,6 +1223,17 @@ long AlignmentFile::read_raw(uint8_t* dst, size_t cap) {
     return 0;
 }
 
+// The record filter on the BAM record at r (behind its block_size word): its verdict counted, 0x4 for a dropped record
+static uint16_t judge_bam(const slimm_record_filter& f, const uint8_t* r, uint64_t* verdicts) {
+    const int why = slimm_rf_bam(&f, r, rd_u32(r - 4));
+    slimm_rf_count(verdicts, why);
+    return slimm_rf_dropped(why) ? 0x4u : 0u;
+}
+static void add_verdicts(std::mutex& mu, uint64_t* total, const uint64_t* verdicts) {
+    std::lock_guard<std::mutex> g(mu);
+    for (int k = 0; k < SLIMM_RF_N_STATS; ++k) total[k] += verdicts[k];
+}
+
 // The four record fields of the hot path straight into the caller's arrays (the page-locked staging sets of
 // slimm_staging_buffers: the DMA engine reads what the decode threads wrote, no copy in between).
 long AlignmentFile::read_into(uint64_t* read_key, int32_t* ref_id, int32_t* begin_pos, uint16_t* flag, size_t max_records,
@@ -1242,18 +1254,22 @@ long AlignmentFile::read_into(uint64_t* read_key, int32_t* ref_id, int32_t* begi
     const long cnt = bam_record_starts(max_records, offs);
     if (cnt <= 0) return cnt;
     std::unique_ptr<StageClock> clk(new StageClock(ms_decode_));
+    const bool filtered = slimm_rf_on(&filter_) != 0;
     decode_parallel(static_cast<size_t>(cnt), [&](size_t lo, size_t hi) {
+        uint64_t verdicts[SLIMM_RF_N_STATS] = {};
         for (size_t k = lo; k < hi; ++k) {
             const uint8_t* r = &buf_[offs[k] + 4];
             const uint8_t l_read_name = r[8];
             const char* name = reinterpret_cast<const char*>(r + 32);
             size_t nlen = l_read_name ? l_read_name - 1u : 0u;
             flag[k] = canonical_read(name, nlen, rd_u16(r + 14));
+            if (filtered) flag[k] |= judge_bam(filter_, r, verdicts);
             read_key[k] = hash_read_name(name, nlen);
             if (check) check[k] = check_read_name(name, nlen);
             ref_id[k] = static_cast<int32_t>(rd_u32(r));
             begin_pos[k] = static_cast<int32_t>(rd_u32(r + 4));
         }
+        if (filtered) add_verdicts(filter_mu_, filter_stats_, verdicts);
     });
     clk.reset(new StageClock(ms_names_));
     separate_adjacent_names(read_key, offs);
@@ -1277,7 +1293,9 @@ long AlignmentFile::read_batch(RecordBatch& out, size_t max_records, bool keep_n
             out.qname.resize(base + cnt);
             out.base_len.resize(base + cnt);
         }
+        const bool filtered = slimm_rf_on(&filter_) != 0;
         decode_parallel(cnt, [&](size_t lo, size_t hi) {
+            uint64_t verdicts[SLIMM_RF_N_STATS] = {};
             for (size_t k = lo; k < hi; ++k) {
                 const uint8_t* r = &buf_[offs[k] + 4];
                 const uint8_t l_read_name = r[8];
@@ -1285,6 +1303,7 @@ long AlignmentFile::read_batch(RecordBatch& out, size_t max_records, bool keep_n
                 const size_t nlen = l_read_name ? l_read_name - 1u : 0u;
                 size_t blen = nlen;
                 out.flag[base + k] = canonical_read(name, blen, rd_u16(r + 14));
+                if (filtered) out.flag[base + k] |= judge_bam(filter_, r, verdicts);
                 out.read_key[base + k] = hash_read_name(name, blen);
                 out.ref_id[base + k] = static_cast<int32_t>(rd_u32(r));
                 out.begin_pos[base + k] = static_cast<int32_t>(rd_u32(r + 4));
@@ -1294,6 +1313,7 @@ long AlignmentFile::read_batch(RecordBatch& out, size_t max_records, bool keep_n
                     out.base_len[base + k] = static_cast<uint32_t>(blen);
                 }
             }
+            if (filtered) add_verdicts(filter_mu_, filter_stats_, verdicts);
         });
         separate_adjacent_names(out.read_key.data() + base, offs);
         return static_cast<long>(cnt);
@@ -1348,6 +1368,11 @@ long AlignmentFile::read_batch(RecordBatch& out, size_t max_records, bool keep_n
             q18_short_starts_ += (sh && starts) ? 1u : 0u;
             q18_short_to_plain_ += (!sh && !starts && last_short_) ? 1u : 0u;
             last_short_ = sh;
+        }
+        if (slimm_rf_on(&filter_)) {   // (the file's flag, the line without its newline: record_filter.h)
+            const int why = slimm_rf_sam(&filter_, flag0, reinterpret_cast<const uint8_t*>(line.data()), nf > 4 ? f[4] : line.size(), line.size());
+            slimm_rf_count(filter_stats_, why);
+            if (slimm_rf_dropped(why)) flag |= 0x4u;
         }
         last_name_ = bn;
         last_key_ = key;

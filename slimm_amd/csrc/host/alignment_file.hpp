@@ -14,12 +14,14 @@
 #include <cstdio>
 #include <functional>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <thread>
 #include <unordered_map>
 #include <vector>
 
 #include "../read_identity.h"
+#include "../record_filter.h"
 
 namespace slimm {
 
@@ -102,6 +104,12 @@ public:
     // read_into have handed out, some run of adjacent records with one canonical base holds SHORTENED names only -- their
     // flagged namesakes may lie anywhere in the file: the file must go through the any-order path
     bool q18_regroup_needed() const { return q18_short_starts_ != q18_short_to_plain_; }
+    // The record filter (../record_filter.h), for the files opened afterwards and the one open now: read_batch / read_into
+    // hand a dropped record on with 0x4 in its flag -- as the device decoders do -- and count the verdicts per file
+    // (filter_stats: the SLIMM_RF_N_STATS counters of slimm_get_record_filter_stats).  The other reads (read_raw, read_text,
+    // ...) hand on bytes, which their consumer filters.
+    void set_filter(const slimm_record_filter& f) { filter_ = f; }
+    const uint64_t* filter_stats() const { return filter_stats_; }
 
     // Appends up to max_records records to `out`; returns the number appended (0 at end of file), -1 on a format error.
     long read_batch(RecordBatch& out, size_t max_records, bool keep_names = false);
@@ -158,6 +166,9 @@ private:
     bool have_last_ = false;
     uint64_t q18_short_starts_ = 0, q18_short_to_plain_ = 0;   // runs that start shortened; shortened -> plain steps inside a run
     bool last_short_ = false;                                   // the last record handed out had a shortened name
+    slimm_record_filter filter_{};
+    uint64_t filter_stats_[SLIMM_RF_N_STATS] = {};
+    std::mutex filter_mu_;   // (decode_parallel's threads add their counts under it, once each)
     // record starts in buf_[pos_, end): appended to offs, at most max_records; returns false on a malformed record
     bool find_records(size_t end, size_t max_records, std::vector<size_t>& offs, size_t& new_pos);
     bool plausible_record(size_t o, size_t end, int depth) const;

@@ -173,6 +173,9 @@ SLIMM_FORWARD(int, slimm_group_push_records,
               (slimm_group* a, const uint64_t* b, const int32_t* c, const int32_t* d, const uint16_t* e, uint64_t f_), (a, b, c, d, e, f_))
 SLIMM_FORWARD(int, slimm_group_get_profiles, (slimm_group* a, const char* b), (a, b))
 SLIMM_FORWARD(int, slimm_group_reset, (slimm_group* a), (a))
+SLIMM_FORWARD(int, slimm_set_record_filter, (slimm_ctx* a, const slimm_record_filter* b), (a, b))
+SLIMM_FORWARD(int, slimm_group_set_record_filter, (slimm_group* a, const slimm_record_filter* b), (a, b))
+SLIMM_FORWARD(int, slimm_get_record_filter_stats, (slimm_ctx* a, uint64_t* b), (a, b))
 #include "accession.hpp"
 #include "alignment_file.hpp"
 #include "zstd.hpp"
@@ -207,6 +210,10 @@ struct Options {  // arg_options, reference src/slimm.hpp:49-87
     // context on its device (run_file_per_device); parse() moves the list here and leaves `devices` empty: no group
     bool file_per_device = false;
     std::vector<int> slots;
+    // -q, --require-flags, --exclude-flags, --min-aligned, --min-identity: one record filter for the whole run and every reader
+    // (include/slimm_hip.h, "THE RECORD FILTER"); all zero: none
+    slimm_record_filter filter{};
+    bool filtered() const { return slimm_rf_on(&filter) != 0; }
 };
 bool g_trace = false;              // SLIMM_TRACE=cli (or all): millisecond marks of the stages on stderr
 
@@ -271,6 +278,12 @@ void usage() {
                  "  -ro, --raw-output             write raw reference statistics\n"
                  "  -co, --coverage-output        write raw coverage statistics\n"
                  "  -v,  --verbose\n"
+                 "  -q,  --min-mapq INT           leave out alignments with MAPQ below INT, in [0, 255] (as samtools view -q)\n"
+                 "       --require-flags INT      leave out alignments that lack one of these flag bits (samtools view -f; decimal or 0x...)\n"
+                 "       --exclude-flags INT      leave out alignments with one of these flag bits (samtools view -F; decimal or 0x...)\n"
+                 "       --min-aligned INT        leave out alignments with fewer aligned bases (CIGAR M + = + X)\n"
+                 "       --min-identity FLOAT     leave out alignments whose identity 1 - NM / (M + = + X + I + D) is below FLOAT, in\n"
+                 "                                [0, 1] (rounded to per-mille), or that carry no NM tag\n"
                  "       --device N | --devices N,M,... [--split-input] | --query-grouped | --any-order | --dump-records | --dump-raw\n"
                  "       --devices N,M,... --file-per-device   every listed device (one may be listed twice) is a slot that takes whole\n"
                  "                                     files of a directory, one at a time; the outputs are those of --device N\n"
@@ -279,6 +292,19 @@ void usage() {
                  "       --propagation-walk default|reversed   order in which the directly counted taxa hand their read counts up\n"
                  "                                     (default: lower ranks first, then ascending taxid; a [WARNING] names\n"
                  "                                     the taxa when a file's counts depend on it)\n";
+}
+
+// an unsigned number in [0, max], decimal or -- hex_too -- 0x...; nothing else in the text
+bool parse_unsigned(const std::string& v, bool hex_too, uint64_t max, uint32_t& out) {
+    const bool hex = hex_too && v.size() > 2 && v[0] == '0' && (v[1] == 'x' || v[1] == 'X');
+    const size_t from = hex ? 2 : 0;
+    if (v.size() == from || v.size() > from + 12) return false;
+    for (size_t i = from; i < v.size(); ++i)
+        if (!(hex ? isxdigit(static_cast<unsigned char>(v[i])) : isdigit(static_cast<unsigned char>(v[i])))) return false;
+    const uint64_t n = strtoull(v.c_str() + from, nullptr, hex ? 16 : 10);
+    if (n > max) return false;
+    out = static_cast<uint32_t>(n);
+    return true;
 }
 
 // 0 ok, 1 error, 2 help
@@ -383,6 +409,33 @@ int parse(int argc, char** argv, Options& o) {
             AlignmentFile::settings().threads = static_cast<unsigned>(std::max(1l, atol(v.c_str())));
         } else if (a == "--no-mmap") {
             AlignmentFile::settings().no_mmap = true;
+        } else if (a == "-q" || a == "--min-mapq") {
+            if (!value(v)) return 1;
+            if (!parse_unsigned(v, false, 255, o.filter.min_mapq)) {
+                std::cerr << "slimm: min-mapq must be an integer in [0, 255]\n";
+                return 1;
+            }
+        } else if (a == "--require-flags" || a == "--exclude-flags") {
+            if (!value(v)) return 1;
+            if (!parse_unsigned(v, true, 0xffff, a == "--require-flags" ? o.filter.require_flags : o.filter.exclude_flags)) {
+                std::cerr << "slimm: " << a.substr(2) << " must be a flag mask in [0, 65535], decimal or 0x...\n";
+                return 1;
+            }
+        } else if (a == "--min-aligned") {
+            if (!value(v)) return 1;
+            if (!parse_unsigned(v, false, 0xffffffffull, o.filter.min_aligned)) {
+                std::cerr << "slimm: min-aligned must be a number of bases, 0 or more\n";
+                return 1;
+            }
+        } else if (a == "--min-identity") {
+            if (!value(v)) return 1;
+            char* rest = nullptr;
+            const double d = strtod(v.c_str(), &rest);
+            if (v.empty() || *rest || !(d >= 0.0 && d <= 1.0)) {
+                std::cerr << "slimm: min-identity must be in [0, 1]\n";
+                return 1;
+            }
+            o.filter.min_identity_permille = static_cast<uint32_t>(d * 1000.0 + 0.5);
         } else if (a == "--dump-records") {
             o.dump_records = true;
         } else if (a == "--dump-raw") {
@@ -447,9 +500,19 @@ int dump_raw(const Options& o) {
     return 0;
 }
 
+// the record filter's counts of a file, as its log line has them: judged, the four dropped counts, no_nm when there is one
+std::string filter_stats_line(const uint64_t* st) {
+    std::ostringstream line;
+    line << "record filter: " << st[SLIMM_RF_N_JUDGED] << " judged; dropped: " << st[SLIMM_RF_N_FLAGS] << " by flags, " << st[SLIMM_RF_N_MAPQ]
+         << " by MAPQ, " << st[SLIMM_RF_N_ALIGNED] << " by aligned length, " << st[SLIMM_RF_N_IDENTITY] << " by identity";
+    if (st[SLIMM_RF_N_NO_NM]) line << " (" << st[SLIMM_RF_N_NO_NM] << " of them without NM)";
+    return line.str();
+}
+
 int dump_records(const Options& o) {
     if (o.dump_raw) return dump_raw(o);
     AlignmentFile f;
+    f.set_filter(o.filter);
     if (!f.open(o.input_path)) {
         std::cerr << f.error() << "\n";
         return 1;
@@ -469,6 +532,7 @@ int dump_records(const Options& o) {
         return 1;
     }
     std::cerr << "#q18_regroup_needed\t" << (f.q18_regroup_needed() ? 1 : 0) << "\n";   // (reader tests)
+    if (o.filtered()) std::cerr << "#" << filter_stats_line(f.filter_stats()) << "\n";
     return 0;
 }
 
@@ -1482,6 +1546,7 @@ std::unique_ptr<Reading> set_up(Session& S, const std::string& path, bool any_or
     F->trace.head = S.log->head;
     AlignmentFile& bam = F->bam;
     bam.set_trace_head(S.log->head);
+    if (options.filtered()) bam.set_filter(options.filter);
     end = Outcome::Done;
     if (!bam.open(path)) {  // src/misc.hpp:500-504: message, skip the file
         S.err() << bam.error() << "\n";
@@ -1637,6 +1702,15 @@ void warn_propagation_order(slimm_ctx* ctx, const std::string& path, int walk, s
     err << line.str() << std::endl;
 }
 
+// The record filter's line of a file: what the device decoders judged (member 0 of a group: all members) and what the host
+// reader judged of the records it decoded itself -- a record goes through one of the two
+void log_filter_stats(Session& S, Reading& F, slimm_ctx* ctx) {
+    uint64_t st[SLIMM_RF_N_STATS] = {};
+    (void)slimm_get_record_filter_stats(ctx, st);
+    for (int k = 0; k < SLIMM_RF_N_STATS; ++k) st[k] += F.bam.filter_stats()[k];
+    S.err() << "  " << filter_stats_line(st) << std::endl;
+}
+
 // ---- several GPUs, one process (--devices), or members of a group on ONE device for a file of more records than one
 // context takes (for_cap): the group deals the records to its members by read and runs the phases with the two RCCL
 // exchanges in between (slimm_amd/csrc/group.hip); the profile comes from member 0
@@ -1663,6 +1737,10 @@ Outcome run_group(Session& S, Reading& F, const std::vector<int>& devs, bool spl
     }
     slimm_ctx* c0 = slimm_group_context(grp.get(), 0);
     (void)slimm_set_propagation_walk(c0, options.propagation_walk);   // (member 0 propagates)
+    if (options.filtered() && slimm_group_set_record_filter(grp.get(), &options.filter) != SLIMM_OK) {
+        S.err() << "slimm: " << slimm_group_last_error(grp.get()) << "\n";
+        return Outcome::Failed;
+    }
     F.trace.mark("lineage table + slimm_group_create");
     S.err() << "[" << F.watch.lap() << " secs]" << std::endl;
     S.err() << "Analysing alignments on " << devs.size() << " devices ("
@@ -1701,6 +1779,7 @@ Outcome run_group(Session& S, Reading& F, const std::vector<int>& devs, bool spl
     F.trace.mark("phases + exchanges + profile");
     if (F.trace.on) trace_memory(c0, S.trace_head());
     S.err() << "[" << F.watch.lap() << " secs]" << std::endl;
+    if (options.filtered()) log_filter_stats(S, F, c0);
     slimm_stats st;
     slimm_get_stats(c0, &st);
     S.total_hits += st.hits_count;
@@ -1737,6 +1816,7 @@ Outcome run_context(Session& S, Reading& F) {
     slimm_ctx* ctx = owned.get();
     CHECK(ctx, slimm_set_cutoff_cache(ctx, S.cc_cache, S.ucc_cache));
     CHECK(ctx, slimm_set_propagation_walk(ctx, options.propagation_walk));
+    if (options.filtered()) CHECK(ctx, slimm_set_record_filter(ctx, &options.filter));
     set_size_hint(ctx, F.path);
     slimm_keep_bins(ctx, (options.raw_output || options.coverage_output) ? 1 : 0);  // (only -ro / -co read the arrays back)
     F.trace.mark("lineage table + slimm_create");
@@ -1795,6 +1875,7 @@ Outcome run_context(Session& S, Reading& F) {
     }
     F.trace.mark("analyze_alignments + finish_coverage");
     S.err() << "[" << F.watch.lap() << " secs]" << std::endl;
+    if (options.filtered()) log_filter_stats(S, F, ctx);
     slimm_stats st;
     slimm_get_stats(ctx, &st);
     S.total_hits += st.hits_count;

@@ -6,6 +6,8 @@
 #include <string>
 #include <vector>
 
+#include "record_filter.h"
+
 // "This value is in a vector register HERE": an empty asm statement that takes and returns it.  It costs nothing and
 // gives a loaded value a use the compiler can neither move nor remove -- without one, a read-only load whose only uses
 // sit in a conditional block is sunk into that block, and the loads a kernel issued together come back one at a time.
@@ -290,10 +292,17 @@ uint32_t bam_pieces(uint64_t n_bytes);
 // record boundaries of bytes[lo, end) (lo: a record starts there) -> pieces, offs (bam_pieces x kBamSlots), *result
 void launch_bam_find(hipStream_t st, const uint8_t* bytes, uint64_t lo, uint64_t end, uint32_t n_refs, BamPiece* pieces, uint32_t* offs,
                      BamWindowResult* result);
-// the window's records appended at out_at: marked -> ref (the words) + pos; otherwise key, ref, pos, flag, check
+// the window's records appended at out_at: marked -> ref (the words) + pos; otherwise key, ref, pos, flag, check.
+// A record filter that is on (record_filter.h): the kFilter instantiation -- a dropped record is written as not mapped
+// (flag | 0x4; marked: reference word 0), everything else of it as for a kept one; the verdicts are added to
+// filter_counts[SLIMM_RF_N_STATS] (a wave's sum per atomic).  Off: the kernels and launches as they are without one
+struct DecodeFilter {
+    slimm_record_filter f;
+    uint32_t* counts;
+};
 void launch_bam_decode(hipStream_t st, const uint8_t* bytes, uint64_t lo, uint64_t end, const BamPiece* pieces, const uint32_t* offs,
                        BamCarry* carry, const BamWindowResult* result, bool marked, uint64_t out_at, uint64_t* key, int32_t* ref,
-                       int32_t* pos, uint16_t* flag, uint32_t* check);
+                       int32_t* pos, uint16_t* flag, uint32_t* check, slimm_record_filter filter, uint32_t* filter_counts);
 // a byte range that starts inside a file (split.hip): the first offset in [lo, hi) where a plausible record starts (as
 // k_bam_pieces guesses a piece's first record) -> atomicMin into *out (set it to ~0 first); the name of the record at o
 // -> *name (as the carry keeps it)
@@ -327,7 +336,8 @@ void launch_sam_find(hipStream_t st, const uint8_t* bytes, uint64_t lo, uint64_t
 void launch_sam_end_line(hipStream_t st, uint8_t* bytes, uint64_t lo, uint64_t end, uint32_t* ended);
 void launch_sam_decode(hipStream_t st, const uint8_t* bytes, uint64_t lo, uint64_t end, const BamPiece* pieces, const uint32_t* offs,
                        BamCarry* carry, const BamWindowResult* result, bool marked, uint64_t out_at, uint64_t* key, int32_t* ref, int32_t* pos,
-                       uint16_t* flag, uint32_t* check, const SamRefEntry* table, uint32_t table_mask, const uint8_t* names);
+                       uint16_t* flag, uint32_t* check, const SamRefEntry* table, uint32_t table_mask, const uint8_t* names,
+                       slimm_record_filter filter, uint32_t* filter_counts);
 // a byte range that starts inside a file (split.hip): the offset of the first newline in bytes[lo, hi) -> atomicMin into
 // *out (set it to ~0 first; the bytes are read in aligned 16s: the buffer has room on both sides); the name of the line
 // at o -> *name (as the carry keeps it)

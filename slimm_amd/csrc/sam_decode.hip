@@ -193,13 +193,16 @@ __device__ __forceinline__ void line_identity(const uint8_t* b, uint64_t o, uint
     after_flag = f0 + fn + 1;
 }
 
-// a wave per piece, a lane per line
-template <bool kMarked>
+// a wave per piece, a lane per line.  kFilter: fa is the one DecodeFilter (kernels.h), as in k_bam_decode
+__device__ __forceinline__ const DecodeFilter& filter_of(const DecodeFilter& fa) { return fa; }
+template <bool kMarked, bool kFilter, typename... FilterArg>
 __global__ __launch_bounds__(64) void k_sam_decode(const uint8_t* __restrict__ b, uint64_t end, const BamPiece* __restrict__ pieces,
                                                    const uint32_t* __restrict__ offs, uint32_t n_pieces, BamCarry* __restrict__ carry,
                                                    uint64_t out_at, uint64_t* __restrict__ key, int32_t* __restrict__ ref,
                                                    int32_t* __restrict__ pos, uint16_t* __restrict__ flag, uint32_t* __restrict__ check,
-                                                   const SamRefEntry* __restrict__ table, uint32_t table_mask, const uint8_t* __restrict__ names) {
+                                                   const SamRefEntry* __restrict__ table, uint32_t table_mask, const uint8_t* __restrict__ names,
+                                                   FilterArg... fa) {
+    static_assert(sizeof...(FilterArg) == (kFilter ? 1 : 0), "the filter is an argument of the kFilter instantiation alone");
     const uint32_t c = blockIdx.x;
     const BamPiece pc = pieces[c];
     const uint32_t* po = offs + static_cast<size_t>(c) * kBamSlots;
@@ -214,6 +217,7 @@ __global__ __launch_bounds__(64) void k_sam_decode(const uint8_t* __restrict__ b
         }
     }
     uint32_t n_short_starts = 0, n_short_to_plain = 0;
+    uint32_t n_verdicts[SLIMM_RF_N_NO_NM + 1] = {};
     for (uint32_t k = threadIdx.x; k < pc.count; k += 64u) {
         const uint64_t o = po[k] & 0x7fffffffu;
         const uint8_t* name;
@@ -239,6 +243,13 @@ __global__ __launch_bounds__(64) void k_sam_decode(const uint8_t* __restrict__ b
         const uint32_t pn = field_len(b, p, end);
         const int32_t rpos = static_cast<int32_t>(field_number(b + p, pn) - 1);   // SAM POS is 1-based; 0 ("unavailable") becomes -1
         const uint64_t at = out_at + pc.base + k;
+        bool dropped = false;
+        if constexpr (kFilter) {   // (the file's flag: without the mate bit of a shortened name; MAPQ is the field behind POS)
+            const uint64_t pe = p + pn;
+            const int why = slimm_rf_sam(&filter_of(fa...).f, is_short ? (fl & ~0xC0u) : fl, b, slimm_rf_next_field(b, pe, end), end);
+            slimm_rf_lane_count(n_verdicts, why);
+            dropped = slimm_rf_dropped(why) != 0;
+        }
         if (kMarked) {
             bool starts, prev_short;
             const uint32_t po_prev = k ? (po[k - 1] & 0x7fffffffu) : prev0;
@@ -256,7 +267,8 @@ __global__ __launch_bounds__(64) void k_sam_decode(const uint8_t* __restrict__ b
             n_short_starts += (is_short & starts) ? 1u : 0u;
             n_short_to_plain += (!is_short & !starts & prev_short) ? 1u : 0u;
             const uint32_t mate = (fl & 0x40u) ? 1u : ((fl & 0x80u) ? 2u : 0u);
-            const bool mapped = !(fl & 0x4u) && rid != -1;
+            bool mapped = !(fl & 0x4u) && rid != -1;
+            if constexpr (kFilter) mapped = mapped & !dropped;
             const uint32_t r1 = mapped ? min(static_cast<uint32_t>(rid) + 1u, 0x1fffffffu) : 0u;
             reinterpret_cast<uint32_t*>(ref)[at] = r1 | (mate << 29) | (starts ? 0x80000000u : 0u);
             pos[at] = rpos;
@@ -264,7 +276,7 @@ __global__ __launch_bounds__(64) void k_sam_decode(const uint8_t* __restrict__ b
             key[at] = sam_hash_name(name, nlen);
             ref[at] = rid;
             pos[at] = rpos;
-            flag[at] = static_cast<uint16_t>(fl);
+            flag[at] = static_cast<uint16_t>(fl | (dropped ? 0x4u : 0u));
             check[at] = sam_check_name(name, nlen);
         }
     }
@@ -278,6 +290,7 @@ __global__ __launch_bounds__(64) void k_sam_decode(const uint8_t* __restrict__ b
             if (n_short_to_plain) atomicAdd(&carry->short_to_plain, n_short_to_plain);
         }
     }
+    if constexpr (kFilter) slimm_rf_wave_add(filter_of(fa...).counts, n_verdicts);
 }
 
 // one wave: the name of the line at o (its canonical base, at most 255 bytes: QNAME is at most 254 characters) and whether
@@ -380,15 +393,23 @@ void launch_sam_end_line(hipStream_t st, uint8_t* bytes, uint64_t lo, uint64_t e
 
 void launch_sam_decode(hipStream_t st, const uint8_t* bytes, uint64_t lo, uint64_t end, const BamPiece* pieces, const uint32_t* offs,
                        BamCarry* carry, const BamWindowResult* result, bool marked, uint64_t out_at, uint64_t* key, int32_t* ref, int32_t* pos,
-                       uint16_t* flag, uint32_t* check, const SamRefEntry* table, uint32_t table_mask, const uint8_t* names) {
+                       uint16_t* flag, uint32_t* check, const SamRefEntry* table, uint32_t table_mask, const uint8_t* names,
+                       slimm_record_filter filter, uint32_t* filter_counts) {
     const uint32_t np = sam_pieces(end - lo);
     if (!np) return;
-    if (marked)
-        hipLaunchKernelGGL(k_sam_decode<true>, dim3(np), dim3(64), 0, st, bytes, end, pieces, offs, np, carry, out_at, key, ref, pos, flag, check,
-                           table, table_mask, names);
+    const DecodeFilter fa{filter, filter_counts};
+    if (slimm_rf_on(&filter) && marked)
+        hipLaunchKernelGGL((k_sam_decode<true, true, DecodeFilter>), dim3(np), dim3(64), 0, st, bytes, end, pieces, offs, np, carry, out_at, key, ref,
+                           pos, flag, check, table, table_mask, names, fa);
+    else if (slimm_rf_on(&filter))
+        hipLaunchKernelGGL((k_sam_decode<false, true, DecodeFilter>), dim3(np), dim3(64), 0, st, bytes, end, pieces, offs, np, carry, out_at, key, ref,
+                           pos, flag, check, table, table_mask, names, fa);
+    else if (marked)
+        hipLaunchKernelGGL((k_sam_decode<true, false>), dim3(np), dim3(64), 0, st, bytes, end, pieces, offs, np, carry, out_at, key, ref, pos, flag,
+                           check, table, table_mask, names);
     else
-        hipLaunchKernelGGL(k_sam_decode<false>, dim3(np), dim3(64), 0, st, bytes, end, pieces, offs, np, carry, out_at, key, ref, pos, flag, check,
-                           table, table_mask, names);
+        hipLaunchKernelGGL((k_sam_decode<false, false>), dim3(np), dim3(64), 0, st, bytes, end, pieces, offs, np, carry, out_at, key, ref, pos, flag,
+                           check, table, table_mask, names);
     hipLaunchKernelGGL(k_sam_carry, dim3(1), dim3(64), 0, st, bytes, end, pieces, offs, result, carry);
 }
 

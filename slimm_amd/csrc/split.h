@@ -40,5 +40,8 @@ int split_first_start(slimm_ctx* c, uint64_t* index);
 int split_take(slimm_ctx* dst, slimm_ctx* src, uint64_t n);
 // the member's records are [from, its count) from now on; its Q18 counts are the group's business
 int split_keep(slimm_ctx* c, uint64_t from);
+// (not a step of the stitch: when the group is made) member 0 answers slimm_get_record_filter_stats with the sum over the
+// members, whichever of them decoded a record
+void group_filter_peers(slimm_ctx* member0, slimm_ctx* const* others, uint32_t n);
 
 }  // namespace slimm

@@ -459,4 +459,6 @@ int split_keep(slimm_ctx* c, uint64_t from) {
     return SLIMM_OK;
 }
 
+void group_filter_peers(slimm_ctx* member0, slimm_ctx* const* others, uint32_t n) { member0->filter_peers.assign(others, others + n); }
+
 }  // namespace slimm

@@ -48,6 +48,10 @@ struct WindowPipeline {
     DevBuf<uint8_t> head_bytes;
     DevBuf<BamCarry> first, join;
     DevBuf<unsigned long long> guess;
+    // the record filter (record_filter.h; slimm_set_record_filter): part of the configuration -- it outlives a file -- and
+    // the decoders' counters of the file at hand (SLIMM_RF_N_STATS words, zeroed by open_file when the filter is on)
+    slimm_record_filter filter{};
+    DevBuf<uint32_t> filter_counts;
     // bzip2 SAM (bzip2_decode.hip), the decode scratch: the compressed bytes not decoded yet, the candidates (block magics),
     // and per slot of a batch the BWT string -- then its RLE1 text --, the inverse BWT's links, the byte histogram, what
     // decoding found and the text's length
@@ -158,6 +162,7 @@ struct WindowPipeline {
         // of a split file: summed by the group (slimm_group_stitch_ranges), not checked per member
         uint64_t q18_starts = 0, q18_plain = 0;
         bool q18_by_group = false;
+        bool filter_counted = false;   // filter_counts holds this file's verdicts (the filter was on when the file began)
         bool found_start = false;   // a range that starts inside the file: its first window holds a record start (false: all head)
         bool has_first = false;     // `first` holds the name of the range's first record (decoded in any window)
         uint64_t head_len = 0;
@@ -316,6 +321,7 @@ struct WindowPipeline {
 // SLIMM_TRACE=push: what the pipeline does and when, on stderr: "[push <ms since the first line>] ...", or "[push <tag>] ..."
 void push_trace_line(const char* tag, const char* fmt, va_list ap);
 void push_trace(const char* fmt, ...);
+int fetch_filter_stats(slimm_ctx* c, uint64_t* out);   // the filter's counters of the file so far (every window launched); zeros without one
 int fetch_q18(slimm_ctx* c);   // the Q18 run counts of the device decoders so far (every window launched) -> file.q18_*
 // `n` bytes at `src` (on device src_device) as one more window behind the closed file's carry (split.hip); end_line: one
 // newline instead

@@ -99,10 +99,11 @@ void launch_decode(slimm_ctx* c, const uint8_t* bytes, uint64_t lo, uint64_t end
     WindowPipeline& W = c->win;
     if (W.file.sam)
         launch_sam_decode(c->stream, bytes, lo, end, W.pieces.p, W.offs.p, W.carry.p, W.result.p, marked, c->n_pushed, c->in_key.p,
-                          c->in_ref.p, c->in_pos.p, c->in_flag.p, c->in_check.p, W.sam_table.p, W.sam_mask, W.sam_names.p);
+                          c->in_ref.p, c->in_pos.p, c->in_flag.p, c->in_check.p, W.sam_table.p, W.sam_mask, W.sam_names.p, W.filter,
+                          W.filter_counts.p);
     else
         launch_bam_decode(c->stream, bytes, lo, end, W.pieces.p, W.offs.p, W.carry.p, W.result.p, marked, c->n_pushed, c->in_key.p,
-                          c->in_ref.p, c->in_pos.p, c->in_flag.p, c->in_check.p);
+                          c->in_ref.p, c->in_pos.p, c->in_flag.p, c->in_check.p, W.filter, W.filter_counts.p);
 }
 struct FormTexts { const char *bad, *skipped, *too_long; };
 const FormTexts kBamTexts{"bad BAM record", "bad BAM record", "a BAM record longer than 16 MiB: decode this file on the host"};
@@ -445,6 +446,11 @@ int open_file(slimm_ctx* c, const Push& p) {
     for (auto& e : W.h2d_done)
         if (!e) HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     HIP_TRY(c, hipMemsetAsync(W.carry.p, 0, sizeof(BamCarry), c->stream));
+    if (slimm_rf_on(&W.filter)) {
+        HIP_TRY(c, W.filter_counts.ensure(SLIMM_RF_N_STATS));
+        HIP_TRY(c, hipMemsetAsync(W.filter_counts.p, 0, SLIMM_RF_N_STATS * sizeof(uint32_t), c->stream));
+        W.file.filter_counted = true;
+    }
     return SLIMM_OK;
 }
 
@@ -877,6 +883,18 @@ int stream_candidates(slimm_ctx* c, DevBuf<unsigned long long>& d_cand, DevBuf<u
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         if (*got <= cap) return SLIMM_OK;
     }
+}
+
+int fetch_filter_stats(slimm_ctx* c, uint64_t* out) {
+    WindowPipeline& W = c->win;
+    std::fill(out, out + SLIMM_RF_N_STATS, 0ull);
+    if (c->device < 0 || !W.file.filter_counted || !W.filter_counts.p) return SLIMM_OK;
+    (void)hipSetDevice(c->device);
+    uint32_t w[SLIMM_RF_N_STATS] = {};
+    HIP_TRY(c, hipMemcpyAsync(w, W.filter_counts.p, sizeof(w), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    std::copy(w, w + SLIMM_RF_N_STATS, out);
+    return SLIMM_OK;
 }
 
 int fetch_q18(slimm_ctx* c) {

@@ -255,6 +255,20 @@ class Slimm:
         self._check(self.L.slimm_records_device(self.ctx, *[C.byref(q) for q in ptr], C.byref(n), C.byref(form)))
         return n.value, form.value
 
+    def set_record_filter(self, min_mapq: int = 0, require_flags: int = 0, exclude_flags: int = 0, min_aligned: int = 0,
+                          min_identity: float = 0.0):
+        """slimm_set_record_filter: which records the byte pushes leave out (handed on as not mapped).  min_identity in
+        [0, 1] is rounded to per-mille.  Set before a file's first push; it survives reset().  All zero: off."""
+        f = capi.RecordFilter(min_mapq=min_mapq, require_flags=require_flags, exclude_flags=exclude_flags,
+                              min_aligned=min_aligned, min_identity_permille=int(round(min_identity * 1000.0)) & 0xffffffff)
+        self._check(self.L.slimm_set_record_filter(self.ctx, C.byref(f)))
+
+    def record_filter_stats(self) -> dict:
+        """slimm_get_record_filter_stats: judged and dropped records of the file's byte pushes so far."""
+        out = (C.c_uint64 * 8)()
+        self._check(self.L.slimm_get_record_filter_stats(self.ctx, out))
+        return dict(zip(capi.RECORD_FILTER_STATS, [int(v) for v in out]))
+
     def push_bam_bytes(self, data, window: int = 0) -> int:
         """slimm_push_bam_bytes: the alignment-record bytes of a BAM file (behind its header, BGZF-inflated), in windows of
         `window` bytes (0: one); the device finds the records and decodes them.  Returns the number of records."""
@@ -808,6 +822,14 @@ class SlimmGroup:
 
     def reset(self):
         self._check(self.L.slimm_group_reset(self.g))
+
+    def set_record_filter(self, min_mapq: int = 0, require_flags: int = 0, exclude_flags: int = 0, min_aligned: int = 0,
+                          min_identity: float = 0.0):
+        """slimm_group_set_record_filter: Slimm.set_record_filter on every member; member(0).record_filter_stats() is the
+        sum over the members."""
+        f = capi.RecordFilter(min_mapq=min_mapq, require_flags=require_flags, exclude_flags=exclude_flags,
+                              min_aligned=min_aligned, min_identity_permille=int(round(min_identity * 1000.0)) & 0xffffffff)
+        self._check(self.L.slimm_group_set_record_filter(self.g, C.byref(f)))
 
     def push_records(self, rec: Records, batch: int = 0):
         n = len(rec)

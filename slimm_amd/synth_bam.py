@@ -121,21 +121,23 @@ def _decimal_names(key: np.ndarray) -> np.ndarray:
     return out
 
 
-def _record_dtype(read_len: int, l_name: int = 17):
+def _record_dtype(read_len: int, l_name: int = 17, n_tags: int = 0):
     dt = np.dtype([("bs", "<i4"), ("ref", "<i4"), ("pos", "<i4"), ("lname", "u1"), ("mapq", "u1"), ("bin", "<u2"),
                    ("ncig", "<u2"), ("flag", "<u2"), ("lseq", "<i4"), ("nref", "<i4"), ("npos", "<i4"), ("tlen", "<i4"),
-                   ("name", f"S{l_name}"), ("cigar", "<u4"), ("seq", f"S{(read_len + 1) // 2}"), ("qual", f"S{read_len}")])
-    assert dt.itemsize == 36 + l_name + 4 + (read_len + 1) // 2 + read_len
+                   ("name", f"S{l_name}"), ("cigar", "<u4"), ("seq", f"S{(read_len + 1) // 2}"), ("qual", f"S{read_len}")]
+                  + ([("tags", f"S{n_tags}")] if n_tags else []))
+    assert dt.itemsize == 36 + l_name + 4 + (read_len + 1) // 2 + read_len + n_tags
     return dt
 
 
 def write_synthetic_bam(path: str, ref_names, ref_len, records, read_len: int = 100,
                         hd: str = "@HD\tVN:1.6\tSO:unsorted\tGO:query", threads: int = 32, piece: int = 10_000_000,
-                        realistic: bool = False, level: int = None) -> dict:
-    """Returns {"records", "raw_bytes", "compressed_bytes", "seconds", "deflate"}."""
+                        realistic: bool = False, level: int = None, tags: bytes = b"") -> dict:
+    """tags: the optional fields every record ends with, as BAM bytes (none by default; the record filter's measurements give
+    every record an MD and an NM tag).  Returns {"records", "raw_bytes", "compressed_bytes", "seconds", "deflate"}."""
     t0 = time.time()
     n = len(records)
-    dt = _record_dtype(read_len, 44 if realistic else 17)
+    dt = _record_dtype(read_len, 44 if realistic else 17, len(tags))
     pool_seq = pool_qual = None
     if realistic:
         pool_seq, pool_qual = _pools(read_len)
@@ -171,6 +173,8 @@ def write_synthetic_bam(path: str, ref_names, ref_len, records, read_len: int = 
             b["nref"] = -1
             b["npos"] = -1
             b["cigar"] = read_len << 4
+            if tags:
+                b["tags"] = np.frombuffer(tags, dtype=f"V{len(tags)}")
             if not realistic:
                 b["seq"] = np.frombuffer(b"\x11" * n_seq, dtype=f"V{n_seq}")
                 b["qual"] = np.frombuffer(b"\x28" * read_len, dtype=f"V{read_len}")
