@@ -109,6 +109,7 @@ constexpr uint32_t kTailWords = 64;
 }  // namespace slimm
 
 #include "windows.h"
+#include "tile_bucketing.h"
 
 using namespace slimm;   // (library-internal header)
 
@@ -143,12 +144,13 @@ struct slimm_ctx {
     } staging[2];
 
     uint32_t R = 0, T = 0;
-    uint64_t Bp = 0;                   // padded bins per coverage array (multiple of 64)
+    TileBucketing tiles;               // the bin tiles' layout, the plan of their bucketing and its tables (tile_bucketing.h)
+    uint64_t Bp() const { return tiles.layout.Bp; }   // padded bins per coverage array (whole tiles)
+    bool use_tiles() const { return tiles.plan.use_tiles; }   // LDS tile histograms (default) vs direct global atomics
     std::vector<uint32_t> bin_off_h;   // [R+1] padded offsets
 
     // static tables
     DevBuf<uint32_t> d_ref_len, d_bin_off, d_lin_dense;
-    DevBuf<uint32_t> d_tile_ref0;     // per bin tile: first reference overlapping it (fused statistics)
     DevBuf<uint2> d_geo;              // {contig length, first bin} per reference: one gather in k_emit
     DevBuf<uint8_t> d_valid;
     DevBuf<uint4> d_rows16;           // per run: 16-byte lineage rows with the valid bit
@@ -186,43 +188,22 @@ struct slimm_ctx {
                                          // tgt_ref holds uint16_t words when ref16 (target_refs())
     TargetRefs target_refs() const { return TargetRefs{tgt_ref.p, ref16}; }
     DevBuf<uint4> slots;                 // per kSlotRecs records: {first target, targets, reads, mapped records}
-    DevBuf<uint4> tot_part;              // per workgroup of k_tile_count: totals of its slots (kernels.h: Totals)
-    DevBuf<uint16_t> bucket;                            // targets bucketed by bin tile (13-bit bin | unique bit)
-    DevBuf<uint32_t> tile_count, tile_base, tile_cursor, split_tiles;
     bool keep_bins = true;       // materialise cov / uniq_cov / uniq_cov2 in HBM (slimm_keep_bins)
     bool binsA_stored = false, binsB_stored = false;
-    DevBuf<uint4> tile_items, part_items;
-    DevBuf<uint32_t> mid, sup_cursor;                   // level-1 buckets (by super tile) and their cursors
     DevBuf<uint32_t> sel;                               // per read, dense: its uniq_cov2 bin, Bp + LCA taxon, or 0xffffffff
     DevBuf<uint32_t> filter_redo;                       // slots k_filter_compact leaves to k_filter_walk
     DevBuf<uint32_t> slot_rbase, slot_bbase;            // reads in front of a slot = rbase[s] + bbase[s >> 10] (side stream)
     hipStream_t side_stream = nullptr;
     hipEvent_t front_done = nullptr, prefix_done = nullptr;
     bool prefix_pending = false;  // prefix_done has been recorded and not been waited for by the main stream yet
-    uint32_t tile_shift = kTileShiftSmall;              // log2 of the bins per tile: which build of tile_hist.hip runs (kernels.h)
-    uint32_t tile_bins() const { return 1u << tile_shift; }
-    uint32_t ntiles = 0;
-    uint32_t Tpad = 0, ntiles2 = 0;                     // taxa padded to whole tiles; tiles of [uniq_cov2 | taxa]
-    bool fused_scan = false;                            // k_tile_scan runs inside the one-level bucketing kernel
-    uint32_t treps = 1, tstride = 0;                    // copies of the tile counters / cursors and their stride
-    bool two_level = false;   // bucket through super tiles first (many tiles: one-level scatter stores are too scattered)
-    bool matrix = false;      // phase B may bucket through a count matrix (one row per counting workgroup, no atomics)
-    bool matrix_always = false;
-    int wide_tiles = -1;      // SLIMM_FORCE wide_tiles: -1 = by the file's size, 0 / 1 = never / always (tests)
-    // far more entries per tile than a packed work item holds (1 B records on 20 k references): work items of up to
-    // kTileSubWide entries with 32-bit counts, so that a tile is one item again (kernels.h)
-    bool wide_for(uint32_t n_records) const {
-        return wide_tiles >= 0 ? wide_tiles != 0 : (ntiles && n_records / ntiles > 32768u);
-    }
-    DevBuf<uint32_t> tile_matrix;
     // multi-GPU coverage summary [4R sums | 16 scalars | bitmaps]: n_slices = 0: not announced (bitmaps by extra kernels),
     // 1: bitmaps written by k_tile_hist as [cov | uniq_cov], n > 1: in n slices of tiles for the all-to-all exchange
     uint32_t summary_slices = 0;
     bool summary_has_bits = false;   // the bitmaps of this analysis are in `summary` already
     uint32_t summary_layout = 0xffffffffu;  // n_slices the buffer was last zeroed for
     DevBuf<uint32_t> d_sum_vec;      // all-to-all form: [4R | 16] additive vector, all-reduced in place
-    uint32_t slice_tiles() const { return summary_slices > 1 ? (ntiles + summary_slices - 1) / summary_slices : ntiles; }
-    uint64_t slice_words() const { return static_cast<uint64_t>(slice_tiles()) * (tile_bins() / 32); }  // per array
+    uint32_t slice_tiles() const { return summary_slices > 1 ? (tiles.layout.ntiles + summary_slices - 1) / summary_slices : tiles.layout.ntiles; }
+    uint64_t slice_words() const { return static_cast<uint64_t>(slice_tiles()) * (tiles.layout.tile_bins() / 32); }  // per array
     uint64_t summary_words() const { return 4ull * R + 16 + 2ull * std::max<uint32_t>(summary_slices, 1u) * slice_words(); }
     BitsLayout bits_layout() {
         BitsLayout b;
@@ -235,7 +216,6 @@ struct slimm_ctx {
     }
     bool statsA_final = false;  // k_pack has added the non-zero counts of the split tiles to the fused statistics
     bool bins_exposed = false;  // the caller holds the coverage buffer (may have merged other ranks' bins into it)
-    bool use_tiles = false;   // LDS-privatised histograms (default) vs direct global atomics (too many tiles for LDS)
     DevBuf<uint32_t> bins;       // cov | uniq_cov | tail | uniq_cov2
     DevBuf<uint32_t> counters;   // CNT_WORDS
     DevBuf<uint32_t> ref_stats;  // [R*4] then [R*4]
@@ -274,10 +254,10 @@ struct slimm_ctx {
     size_t statsB_words() const { return 5ull * R + 32 + T; }
     bool pair_clean = false;  // the (taxon, ref) hash set holds only empty slots
     uint32_t* cov() { return bins.p; }
-    uint32_t* ucov() { return bins.p + Bp; }
-    uint32_t* tail() { return bins.p + 2 * Bp; }
-    uint32_t* ucov2() { return bins.p + 2 * Bp + kTailWords; }
-    uint32_t* lca_tiles() { return bins.p + 3 * Bp + kTailWords; }  // [Tpad] right behind uniq_cov2: one index space
+    uint32_t* ucov() { return bins.p + Bp(); }
+    uint32_t* tail() { return bins.p + 2 * Bp(); }
+    uint32_t* ucov2() { return bins.p + 2 * Bp() + kTailWords; }
+    uint32_t* lca_tiles() { return bins.p + 3 * Bp() + kTailWords; }  // [Tpad] right behind uniq_cov2: one index space
 };
 
 namespace slimm {

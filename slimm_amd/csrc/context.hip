@@ -56,18 +56,11 @@ int ensure_work_buffers(slimm_ctx* c, uint32_t n) {
     HIP_TRY(c, c->tgt_ref.ensure(n + 1));
     HIP_TRY(c, c->tgt_gbin.ensure(n + 8));  // (+ the reach of the bucketing kernels' 16-byte loads, tile_hist.hip: piece_load)
     HIP_TRY(c, c->slots.ensure(front_slots(n) + 1));
-    HIP_TRY(c, c->tot_part.ensure(512));
     HIP_TRY(c, c->sel.ensure(n + 8));
     HIP_TRY(c, c->slot_rbase.ensure(front_slots(n) + 8));
     HIP_TRY(c, c->slot_bbase.ensure(front_slots(n) / 1024 + 8));
     HIP_TRY(c, c->filter_redo.ensure(front_slots(n) + 1));
-    if (c->use_tiles) {
-        HIP_TRY(c, c->bucket.ensure(n + 1));
-        HIP_TRY(c, c->tile_items.ensure(TILES(c->tile_shift, tile_items_upper(c->ntiles2, n)) + 1));
-        HIP_TRY(c, c->mid.ensure(n + 1));
-        HIP_TRY(c, c->part_items.ensure(TILES(c->tile_shift, part_items_upper(c->ntiles2, n)) + 1));
-        HIP_TRY(c, c->sup_cursor.ensure(kMaxSuper));
-    }
+    HIP_TRY(c, c->tiles.reserve(n));
     if (c->order == SLIMM_ORDER_ANY) {
         HIP_TRY(c, c->c_ident.ensure(n + 1));
         HIP_TRY(c, c->c_pay.ensure(n + 1));
@@ -194,26 +187,10 @@ int slimm_create(const slimm_config* cfg, slimm_ctx** out) {
             c->Tsel = 8u << c->taxon_shift;
         }
     }
-    // Tile size by layout: the small tiles while the whole bucketing fits the fused kernel's tile tables (their histograms
-    // run at twice the occupancy), the large ones beyond -- where the scatter's direct rounds pay a returning atomic per
-    // run of one tile among neighbouring targets and half as many tiles make those runs longer (1 B records over 20 k
-    // references: scatter 3.03 -> 2.3 ms, histograms 0.41 -> 0.67 ms; kernels.h)
-    {
-        const uint64_t small = (off + (1ull << kTileShiftSmall) - 1) >> kTileShiftSmall;
-        const uint64_t small2 = small + ((static_cast<uint64_t>(c->Tsel) + (1ull << kTileShiftSmall) - 1) >> kTileShiftSmall);
-        c->tile_shift = small2 > kFusedScanTiles ? kTileShiftLarge : kTileShiftSmall;
-        long ts = 0;
-        if (forced("tile_shift", &ts)) {
-            if (ts == static_cast<long>(kTileShiftSmall)) c->tile_shift = kTileShiftSmall;
-            if (ts == static_cast<long>(kTileShiftLarge)) c->tile_shift = kTileShiftLarge;
-        }
-    }
-    const uint32_t tile_bins = c->tile_bins();
-    c->Bp = (off + tile_bins - 1) & ~static_cast<uint64_t>(tile_bins - 1);
-    c->ntiles = static_cast<uint32_t>(c->Bp >> c->tile_shift);
-    c->Tpad = (c->Tsel + tile_bins - 1) & ~(tile_bins - 1);
-    c->ntiles2 = c->ntiles + (c->Tpad >> c->tile_shift);
-    if (c->Bp + c->Tpad >= kMaxBins) return fail(nullptr, SLIMM_E_INVALID, "more than 2^31 coverage bins; use a larger bin width");
+    // the bin tiles and how they are bucketed (tile_plan.h); SLIMM_FORCE is read here, once
+    const TileForces forces = TileForces::from_env();
+    const TileLayout& tl = c->tiles.layout = tile_layout(off, c->Tsel, forces.tile_shift);
+    if (tl.Bp + tl.Tpad >= kMaxBins) return fail(nullptr, SLIMM_E_INVALID, "more than 2^31 coverage bins; use a larger bin width");
 
     if (c->device >= 0) {
         slimm_ctx* cc = c.get();
@@ -242,7 +219,7 @@ int slimm_create(const slimm_config* cfg, slimm_ctx** out) {
         HIP_TRY0(cc->d_valid_bits.ensure(c->R / 32 + 2));
         HIP_TRY0(cc->h_valid_bits.ensure(c->R / 32 + 2));
         memset(cc->h_valid_bits.p, 0, (c->R / 32 + 2) * 4);
-        HIP_TRY0(cc->bins.ensure(3 * c->Bp + kTailWords + c->Tpad));
+        HIP_TRY0(cc->bins.ensure(3 * tl.Bp + kTailWords + tl.Tpad));
         HIP_TRY0(cc->counters.ensure(CNT_WORDS));
         HIP_TRY0(cc->ref_stats.ensure(c->statsA_words() + c->statsB_words() + 64));
         HIP_TRY0(cc->lca_count.ensure(c->Tsel));
@@ -295,61 +272,16 @@ int slimm_create(const slimm_config* cfg, slimm_ctx** out) {
                 return fail(nullptr, SLIMM_E_HIP, "out of device memory for lineage rows");
         }
         trc.mark("tables to the device");
-        cc->use_tiles = !forced("direct_atomics") && TILES(c->tile_shift, tile_hist_setup(c->ntiles2)) == 0;
+        const bool setup_ok = !forces.direct_atomics && TILES(tl.tile_shift, tile_hist_setup(tl.ntiles2)) == 0;
         if (cc->order == SLIMM_ORDER_ANY && group_init() != 0) {
             *out = nullptr;
             return fail(nullptr, SLIMM_E_HIP, "group_init: hipFuncSetAttribute failed");
         }
         trc.mark("kernel attributes (tile_hist_setup, group_init: the code objects are loaded here)");
-        {
-            // default by size: with the register-resident scatter chunks one level wins up to ~10 K tiles (config 3:
-            // 494 vs 601 us) and is level with two at 24 K (config 5: 430 vs 396 us)
-            long tl = 0;
-            cc->two_level = forced("two_level", &tl) ? tl == 1 : (c->ntiles2 > 16384);
-        }
-        if (cc->use_tiles) {
-            cc->treps = (cc->two_level || c->ntiles2 > 16384) ? 1u : kTileReps;  // (k_tile_scan stages the copies of <= 16 K tiles)
-            cc->tstride = c->ntiles2 + 1;
-            {
-                long fs = 1;
-                (void)forced("fused_scan", &fs);
-                cc->fused_scan = !cc->two_level && cc->treps == kTileReps && c->ntiles2 <= kFusedScanTiles && fs != 0;
-            }
-            {
-                // Layouts beyond the fused kernel's 4064 tiles, PHASE B only, when a tile gets few selectors (decided per
-                // file from the number of reads): a count matrix instead of counter copies and cursors -- one row of tile
-                // counts per counting workgroup, no global atomics and no rounds in the scatter.  (Phase A stays on the
-                // rounds: with hundreds of thousands of values per tile, appending at ONE frontier per tile and counter
-                // copy keeps the bucket's open cache lines in L2, while 256 private frontiers per tile -- 2.5 M partially
-                // written lines at config 3 -- turn every 2-byte store into a partial-line write: measured 834 vs 362 us.)
-                // Since round 5 only beyond kBigRoundTiles tiles: up to there the rounds ordered by tile in LDS
-                // (k_tile_scatter_big) are faster for both phases (config 3, phase B: count 28 -> 17 us, scatter 52 -> 42).
-                long mx = 1;
-                (void)forced("matrix", &mx);
-                cc->matrix = !cc->fused_scan && mx != 0 && (c->ntiles2 > kBigRoundTiles || mx == 2);
-                if (cc->matrix &&
-                    cc->tile_matrix.ensure(static_cast<size_t>(TILES(c->tile_shift, tile_count_grid(512))) * cc->tstride) != hipSuccess)
-                    return fail(nullptr, SLIMM_E_HIP, "out of device memory for the tile count matrix");
-                if (mx == 2) cc->matrix_always = true;  // (tests: small layouts, whatever the number of reads)
-                long wt = 0;
-                if (forced("wide_tiles", &wt)) cc->wide_tiles = wt == 1 ? 1 : 0;
-            }
-            const size_t rep_words = static_cast<size_t>(cc->treps) * cc->tstride;
-            if (cc->tile_count.ensure(rep_words) != hipSuccess || cc->tile_base.ensure(c->ntiles2 + 1) != hipSuccess ||
-                cc->tile_cursor.ensure(rep_words) != hipSuccess || cc->split_tiles.ensure(c->ntiles2 + 1) != hipSuccess)
-                return fail(nullptr, SLIMM_E_HIP, "out of device memory for tile tables");
-            std::vector<uint32_t> ref0(c->ntiles2 + 1, c->R);
-            uint32_t r = 0;
-            for (uint32_t t = 0; t < c->ntiles2; ++t) {
-                const uint64_t t0 = static_cast<uint64_t>(t) * tile_bins;
-                if (t0 >= c->bin_off_h[c->R]) break;
-                while (r + 1 < c->R && c->bin_off_h[r + 1] <= t0) ++r;
-                ref0[t] = r;
-            }
-            if (cc->d_tile_ref0.ensure(ref0.size()) != hipSuccess ||
-                hipMemcpy(cc->d_tile_ref0.p, ref0.data(), ref0.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-                return fail(nullptr, SLIMM_E_HIP, "out of device memory for tile tables");
-        }
+        cc->tiles.plan = tile_plan(tl.ntiles2, forces, setup_ok);
+        if (cc->use_tiles())
+            if (const char* what = cc->tiles.init(c->bin_off_h.data(), c->R))
+                return fail(nullptr, SLIMM_E_HIP, "out of device memory for %s", what);
         uint32_t cap = 1u << 16;
         while (cap < 8ull * c->R && cap < (1u << 30)) cap <<= 1;
         long pc = 0;
@@ -503,24 +435,21 @@ int slimm_analyze_alignments(slimm_ctx* c) {
         HIP_TRY(c, hipStreamWaitEvent(st, c->prefix_done, 0));
         c->prefix_pending = false;
     }
+    TileJob job;  // the targets by bin tile, then cov and uniq_cov from the buckets
+    job.run = c->tiles.run(TilePhase::A, n, n);
     {
         KernelTimer t(c, K_MEMSET);
-        if (!c->use_tiles)  // (the tile kernels write every cov / uniq_cov word themselves)
-            HIP_TRY(c, hipMemsetAsync(c->bins.p, 0, 2 * c->Bp * sizeof(uint32_t), st));
+        if (!c->use_tiles())  // (the tile kernels write every cov / uniq_cov word themselves)
+            HIP_TRY(c, hipMemsetAsync(c->bins.p, 0, 2 * c->Bp() * sizeof(uint32_t), st));
         ZeroArgs z;
         z.p[0] = c->counters.p;
         z.n[0] = CNT_WORDS;
         z.p[1] = c->tail();
         z.n[1] = kTailWords;
-        if (c->use_tiles) {
-            z.p[2] = c->tile_count.p;
-            z.n[2] = c->treps * c->tstride;
-            z.p[3] = c->ref_stats.p;  // per-reference statistics accumulated by k_tile_hist
-            z.n[3] = 4 * c->R;
-            if (c->fused_scan) {      // (otherwise k_tile_scan clears the cursors)
-                z.p[4] = c->tile_cursor.p;
-                z.n[4] = c->treps * c->tstride;
-            }
+        if (c->use_tiles()) {
+            z.p[2] = c->ref_stats.p;  // per-reference statistics accumulated by k_tile_hist
+            z.n[2] = 4 * c->R;
+            c->tiles.zero_tables(z, job.run);
         }
         launch_zero(st, z);
     }
@@ -585,59 +514,30 @@ int slimm_analyze_alignments(slimm_ctx* c) {
         HIP_TRY(c, hipEventRecord(c->prefix_done, c->side_stream));
         return SLIMM_OK;
     };
-    SlotValues targets;
-    targets.vals = c->tgt_gbin.p;
-    targets.slots = c->slots.p;
-    targets.nslots = nslots;
-    targets.per_read = false;
-    const bool wide = c->wide_for(n);
-    const uint32_t tile_sub = wide ? kTileSubWide : kTileSub;
-    if (c->use_tiles) {
-        const uint32_t grid = 512;  // two persistent workgroups per CU
-        {
-            KernelTimer t(c, K_TILE_COUNT);
-            TILES(c->tile_shift, launch_tile_count(st, grid, c->ntiles, targets, c->tot_part.p, c->tile_count.p, c->treps, c->tstride));
-        }
-        Totals tot;
-        tot.part = c->tot_part.p;
-        tot.nparts = TILES(c->tile_shift, tile_count_grid(grid));
-        tot.tail = c->tail();
-        if (c->fused_scan) {
-            KernelTimer t(c, K_TILE_SCATTER);
-            TILES(c->tile_shift, launch_tile_scatter_fused(st, grid, c->ntiles, targets, c->counters.p, c->tile_count.p, c->tile_cursor.p,
-                                      c->bucket.p, c->cov(), c->ucov(), c->tstride, c->tile_items.p, c->split_tiles.p, tot,
-                                      tile_sub));
-        } else {
-            {
-                KernelTimer t(c, K_TILE_SCAN);
-                TILES(c->tile_shift, launch_tile_scan(st, c->ntiles, c->tile_count.p, c->tile_base.p, c->tile_cursor.p, c->tile_items.p,
-                                 c->counters.p, c->part_items.p, c->sup_cursor.p, c->split_tiles.p, c->treps, c->tstride,
-                                 c->two_level, tot, tile_sub));
-            }
-            {
-                KernelTimer t(c, K_TILE_SCATTER);
-                TILES(c->tile_shift, launch_tile_scatter(st, grid, c->ntiles, n, targets, c->counters.p, c->tile_base.p, c->tile_cursor.p,
-                                    c->sup_cursor.p, c->part_items.p, c->mid.p, c->bucket.p, c->cov(), c->ucov(),
-                                    c->two_level, c->tile_count.p, c->treps, c->tstride, tile_sub));
-            }
-        }
+    if (c->use_tiles()) {
+        job.values.vals = c->tgt_gbin.p;
+        job.values.slots = c->slots.p;
+        job.values.nslots = nslots;
+        job.n_upper = n;
+        job.a = c->cov();
+        job.b = c->ucov();
+        job.tail = c->tail();  // (with the stream's totals)
+        job.stats = c->ref_stats.p;
+        job.store_from = c->keep_bins ? 0u : c->tiles.layout.ntiles;
+        bucket(c, job);
         if (int rc = slot_prefix_beside_what_follows()) return rc;
-        {
-            KernelTimer t(c, K_TILE_HIST);
-            c->summary_has_bits = false;
-            if (c->summary_slices) {
-                const bool fresh = c->summary.cap < c->summary_words() || c->summary_layout != c->summary_slices;
-                HIP_TRY(c, c->summary.ensure(c->summary_words()));
-                if (fresh)  // the padding behind the last tile of the last slice is never written: zero it once per layout
-                    HIP_TRY(c, hipMemsetAsync(c->summary.p, 0, c->summary_words() * 4, st));
-                c->summary_layout = c->summary_slices;
-                c->summary_has_bits = true;
-            }
-            TILES(c->tile_shift, launch_tile_hist(st, c->ntiles, n, c->bucket.p, c->tile_base.p, c->tile_items.p, c->counters.p, c->cov(),
-                             c->ucov(), c->d_bin_off.p, c->R, c->d_tile_ref0.p, c->ref_stats.p, c->bits_layout(),
-                             c->keep_bins ? 0u : c->ntiles, wide));
-            c->binsA_stored = c->keep_bins;
+        c->summary_has_bits = false;
+        if (c->summary_slices) {
+            const bool fresh = c->summary.cap < c->summary_words() || c->summary_layout != c->summary_slices;
+            HIP_TRY(c, c->summary.ensure(c->summary_words()));
+            if (fresh)  // the padding behind the last tile of the last slice is never written: zero it once per layout
+                HIP_TRY(c, hipMemsetAsync(c->summary.p, 0, c->summary_words() * 4, st));
+            c->summary_layout = c->summary_slices;
+            c->summary_has_bits = true;
         }
+        job.bits = c->bits_layout();
+        histogram(c, job);
+        c->binsA_stored = c->keep_bins;
     } else {
         if (int rc = slot_prefix_beside_what_follows()) return rc;
         KernelTimer t(c, K_HIST);
@@ -676,7 +576,7 @@ int slimm_coverage_buffer(slimm_ctx* c, void** d_ptr, uint64_t* n_words) {
     if (!c->stream_ordered) HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->bins_exposed = true;  // the statistics k_tile_hist accumulated describe the local bins only
     *d_ptr = c->bins.p;
-    *n_words = 2 * c->Bp + 16;
+    *n_words = 2 * c->Bp() + 16;
     return SLIMM_OK;
 }
 
@@ -688,7 +588,7 @@ int slimm_uniq_cov2_buffer(slimm_ctx* c, void** d_ptr, uint64_t* n_words) {
     (void)hipSetDevice(c->device);
     if (!c->stream_ordered) HIP_TRY(c, hipStreamSynchronize(c->stream));
     *d_ptr = c->ucov2();
-    *n_words = c->Bp;
+    *n_words = c->Bp();
     return SLIMM_OK;
 }
 
@@ -728,10 +628,11 @@ int slimm_finish_coverage(slimm_ctx* c) {
     pk.n[0] = 32;
     pk.src[1] = c->tail();
     pk.n[1] = 16;
-    if (c->use_tiles && !c->bins_exposed) {  // k_tile_hist left the per-reference statistics in place
+    if (c->use_tiles() && !c->bins_exposed) {  // k_tile_hist left the per-reference statistics in place
         KernelTimer t(c, K_PACK);
-        TILES(c->tile_shift, launch_pack(c->stream, c->ref_stats.p + 4ull * c->R, pk, c->split_tiles.p, c->counters.p, c->cov(), c->ucov(),
-                    c->d_bin_off.p, c->R, c->d_tile_ref0.p, c->statsA_final ? nullptr : c->ref_stats.p, c->bits_layout()));
+        const TileTables tt = c->tiles.tables(c->counters.p);
+        TILES(tt.tile_shift, launch_pack(c->stream, c->ref_stats.p + 4ull * c->R, pk, &tt, c->cov(), c->ucov(), c->d_bin_off.p, c->R,
+                                        c->statsA_final ? nullptr : c->ref_stats.p, c->bits_layout()));
         c->statsA_final = true;
     } else {
         KernelTimer t(c, K_REF_STATS);
@@ -749,8 +650,8 @@ int slimm_keep_bins(slimm_ctx* c, int on) {
 
 int slimm_prepare_summary(slimm_ctx* c, uint32_t n_slices) {
     if (!c) return SLIMM_E_INVALID;
-    if (n_slices > 1 && !c->use_tiles) return fail(c, SLIMM_E_INVALID, "sliced summaries need the tile histogram path");
-    c->summary_slices = (c->device >= 0 && c->use_tiles) ? n_slices : 0;
+    if (n_slices > 1 && !c->use_tiles()) return fail(c, SLIMM_E_INVALID, "sliced summaries need the tile histogram path");
+    c->summary_slices = (c->device >= 0 && c->use_tiles()) ? n_slices : 0;
     return SLIMM_OK;
 }
 
@@ -760,12 +661,12 @@ int slimm_coverage_summary(slimm_ctx* c, void** d_ptr, uint64_t* n_words) {
     (void)hipSetDevice(c->device);
     if (c->summary_slices > 1 && (!c->summary_has_bits || c->bins_exposed))
         return fail(c, SLIMM_E_INVALID, "sliced summary: call slimm_prepare_summary before slimm_analyze_alignments");
-    const uint64_t bits_words = c->Bp / 32;
+    const uint64_t bits_words = c->Bp() / 32;
     const uint64_t W = c->summary_words();
     HIP_TRY(c, c->summary.ensure(W));
     hipStream_t st = c->stream;
     bool have_bits = false;  // k_tile_hist / k_pack already wrote the bitmaps into the summary buffer
-    if (c->use_tiles && !c->bins_exposed) {
+    if (c->use_tiles() && !c->bins_exposed) {
         KernelTimer t(c, K_PACK);
         PackArgs pk;
         pk.src[0] = c->ref_stats.p;
@@ -773,11 +674,12 @@ int slimm_coverage_summary(slimm_ctx* c, void** d_ptr, uint64_t* n_words) {
         pk.src[1] = c->tail();
         pk.n[1] = 16;
         if (!c->statsA_final) {  // first finish the statistics (and bitmaps) of the split tiles in place, then copy
-            TILES(c->tile_shift, launch_pack(st, c->summary.p, PackArgs(), c->split_tiles.p, c->counters.p, c->cov(), c->ucov(), c->d_bin_off.p,
-                        c->R, c->d_tile_ref0.p, c->ref_stats.p, c->bits_layout()));
+            const TileTables tt = c->tiles.tables(c->counters.p);
+            TILES(tt.tile_shift, launch_pack(st, c->summary.p, PackArgs(), &tt, c->cov(), c->ucov(), c->d_bin_off.p, c->R, c->ref_stats.p,
+                                            c->bits_layout()));
             c->statsA_final = true;
         }
-        TILES(c->tile_shift, launch_pack(st, c->summary.p, pk));
+        TILES(c->tiles.layout.tile_shift, launch_pack(st, c->summary.p, pk));
         have_bits = c->summary_has_bits;
     } else {
         KernelTimer t(c, K_REF_STATS);
@@ -789,8 +691,8 @@ int slimm_coverage_summary(slimm_ctx* c, void** d_ptr, uint64_t* n_words) {
     if (!have_bits && !c->binsA_stored)
         return fail(c, SLIMM_E_INVALID, "no bit maps and no coverage arrays: call slimm_prepare_summary or slimm_keep_bins");
     if (!have_bits) {
-        launch_nonzero_bits(st, c->cov(), c->Bp, c->summary.p + 4ull * c->R + 16);
-        launch_nonzero_bits(st, c->ucov(), c->Bp, c->summary.p + 4ull * c->R + 16 + bits_words);
+        launch_nonzero_bits(st, c->cov(), c->Bp(), c->summary.p + 4ull * c->R + 16);
+        launch_nonzero_bits(st, c->ucov(), c->Bp(), c->summary.p + 4ull * c->R + 16 + bits_words);
     }
     if (!c->stream_ordered) HIP_TRY(c, hipStreamSynchronize(st));
     *d_ptr = c->summary.p;
@@ -810,9 +712,9 @@ int slimm_merge_summary_slices(slimm_ctx* c, const void* d_recv, uint32_t n_rank
     const uint64_t W = 4ull * c->R + 16;
     HIP_TRY(c, c->d_sum_vec.ensure(W));
     const uint64_t lo_tile = static_cast<uint64_t>(my_rank) * c->slice_tiles();
-    const uint64_t hi_tile = std::min<uint64_t>(lo_tile + c->slice_tiles(), c->ntiles);
-    const uint32_t lo_bin = static_cast<uint32_t>(std::min<uint64_t>(lo_tile, c->ntiles) * c->tile_bins());
-    const uint32_t hi_bin = static_cast<uint32_t>(std::max<uint64_t>(hi_tile, std::min<uint64_t>(lo_tile, c->ntiles)) * c->tile_bins());
+    const uint64_t hi_tile = std::min<uint64_t>(lo_tile + c->slice_tiles(), c->tiles.layout.ntiles);
+    const uint32_t lo_bin = static_cast<uint32_t>(std::min<uint64_t>(lo_tile, c->tiles.layout.ntiles) * c->tiles.layout.tile_bins());
+    const uint32_t hi_bin = static_cast<uint32_t>(std::max<uint64_t>(hi_tile, std::min<uint64_t>(lo_tile, c->tiles.layout.ntiles)) * c->tiles.layout.tile_bins());
     // own sums and scalars come from the summary buffer (slimm_coverage_summary filled it)
     launch_merge_slices(c->stream, static_cast<const uint32_t*>(d_recv), n_ranks, c->slice_words(), lo_bin, hi_bin,
                         c->d_bin_off.p, c->R, c->summary.p, c->summary.p + 4ull * c->R, c->d_sum_vec.p);
@@ -834,7 +736,7 @@ int slimm_finish_coverage_reduced(slimm_ctx* c) {
     pk.n[1] = 32;
     pk.src[2] = c->d_sum_vec.p + 4ull * c->R;
     pk.n[2] = 16;
-    TILES(c->tile_shift, launch_pack(c->stream, c->ref_stats.p, pk));
+    TILES(c->tiles.layout.tile_shift, launch_pack(c->stream, c->ref_stats.p, pk));
     return finish_from_device_stats(c);
 }
 
@@ -843,7 +745,7 @@ int slimm_finish_coverage_merged(slimm_ctx* c, const void* d_gathered, uint32_t 
     if (!c->analyzed) return fail(c, SLIMM_E_INVALID, "call slimm_analyze_alignments first");
     (void)hipSetDevice(c->device);
     if (c->summary_slices > 1) return fail(c, SLIMM_E_INVALID, "sliced summaries are merged with slimm_merge_summary_slices");
-    const uint64_t bits_words = c->Bp / 32;
+    const uint64_t bits_words = c->Bp() / 32;
     const uint64_t W = 4ull * c->R + 16 + 2 * bits_words;
     // merged statistics, this rank's counters and the merged scalars land in the packed block A
     launch_merge_summary(c->stream, static_cast<const uint32_t*>(d_gathered), W, n_ranks, c->d_bin_off.p, c->R, 4ull * c->R + 16,
@@ -908,30 +810,23 @@ int filter_prepare(slimm_ctx* c, bool& rows_ride_along) {
 
 // the launches of phase B / C(1): clears, k_filter, the selector histogram, the packed result block B
 int filter_launch(slimm_ctx* c, bool copy_rows) {
-    HostProfile& h = *c->host;
-    (void)h;
     hipStream_t st = c->stream;
     const uint32_t R = c->R, T = c->T;
     uint32_t* const blockB = c->ref_stats.p + c->statsA_words();
-    const bool rows_ride_along = copy_rows;
-    const int attempt = 0;
+    TileJob job;  // uniq_cov2 and the per-taxon LCA counts from the per-read selectors, through the LDS tile histogram
+    job.run = c->tiles.run(TilePhase::B, c->local_M, c->rec.n);
     {
         KernelTimer t(c, K_MEMSET);
-        if (!c->use_tiles) HIP_TRY(c, hipMemsetAsync(c->ucov2(), 0, c->Bp * sizeof(uint32_t), st));
+        if (!c->use_tiles()) HIP_TRY(c, hipMemsetAsync(c->ucov2(), 0, c->Bp() * sizeof(uint32_t), st));
         ZeroArgs z;
         z.p[0] = c->marks.p;
         z.n[0] = R * (kMarkBytes / 4);  // one byte per (reference, level)
         z.p[1] = c->counters.p + CNT_ERR;  // ERR, PAIRS, REDO
         z.n[1] = 3;
-        if (c->use_tiles) {
-            z.p[2] = c->tile_count.p;
-            z.n[2] = c->treps * c->tstride;
-            z.p[3] = blockB;  // per-reference statistics of uniq_cov2, accumulated by k_tile_hist
-            z.n[3] = 4 * R;
-            if (c->fused_scan) {
-                z.p[4] = c->tile_cursor.p;
-                z.n[4] = c->treps * c->tstride;
-            }
+        if (c->use_tiles()) {
+            z.p[2] = blockB;  // per-reference statistics of uniq_cov2, accumulated by k_tile_hist
+            z.n[2] = 4 * R;
+            c->tiles.zero_tables(z, job.run);
         } else {
             z.p[2] = c->lca_count.p;
             z.n[2] = c->Tsel;
@@ -940,7 +835,7 @@ int filter_launch(slimm_ctx* c, bool copy_rows) {
             z.p64 = c->pair_tab.p;
             z.n64 = c->pair_cap;
         }
-        if (rows_ride_along && attempt == 0) {
+        if (copy_rows) {
             z.cp_dst = reinterpret_cast<uint32_t*>(c->d_rows16.p);
             z.cp_src = reinterpret_cast<const uint32_t*>(c->h_rows16.p);
             z.cp_n = R * 4u;
@@ -977,60 +872,23 @@ int filter_launch(slimm_ctx* c, bool copy_rows) {
         fa.pair_tab = c->pair_tab.p;
         fa.pair_list = c->pair_list.p;
         fa.pair_mask = c->pair_cap - 1;
-        fa.taxon_base = static_cast<uint32_t>(c->Bp);
+        fa.taxon_base = static_cast<uint32_t>(c->Bp());
         fa.counters = c->counters.p;
         launch_filter(st, fa, t.t0(), t.t1());
     }
-    SlotValues selectors;  // dense: k_filter wrote every slot's selectors behind those of the slots before
-    selectors.vals = c->sel.p;
-    selectors.slots = nullptr;
-    selectors.nslots = c->local_M;
-    if (!c->use_tiles) {
+    if (c->use_tiles()) {
+        job.values.vals = c->sel.p;  // dense: k_filter wrote every slot's selectors behind those of the slots before
+        job.values.nslots = c->local_M;
+        job.n_upper = c->rec.n;
+        job.a = c->ucov2();
+        job.stats = blockB;
+        // (the tiles behind the bins hold the per-taxon LCA counts k_pack reads back)
+        job.store_from = c->keep_bins ? 0u : c->tiles.layout.ntiles;
+        bucket(c, job);
+        histogram(c, job);
+    } else {
         KernelTimer t(c, K_HIST);
-        launch_sel_atomics(st, c->sel.p, c->local_M, static_cast<uint32_t>(c->Bp), c->ucov2(), c->lca_count.p);
-    }
-    if (c->use_tiles) {  // uniq_cov2 and the per-taxon LCA counts from the per-read selectors, through the LDS tile histogram
-        const uint32_t grid = 512;
-        // few selectors per tile (config 5: 100; config 3: 1 200): the count matrix (88 -> 61 us at config 3, 112 -> 33 us at
-        // config 5); many (config 4: 12 000): the direct rounds, whose shared frontier per tile keeps the open lines in L2
-        const bool matrix = c->matrix && (c->matrix_always || c->local_M / std::max(1u, c->ntiles2) < 4096u);
-        const uint32_t tile_sub = c->wide_for(c->rec.n) ? kTileSubWide : kTileSubB;  // (one array: its counts are 32-bit already)
-        {
-            KernelTimer t(c, K_TILE_COUNT2);
-            TILES(c->tile_shift, launch_tile_count(st, grid, c->ntiles2, selectors, nullptr, c->tile_count.p, c->treps, c->tstride,
-                              matrix ? c->tile_matrix.p : nullptr));
-            if (matrix) TILES(c->tile_shift, launch_matrix_prefix(st, grid, c->ntiles2, c->tile_matrix.p, c->tstride, c->tile_count.p));
-        }
-        if (c->fused_scan) {
-            KernelTimer t(c, K_TILE_SCATTER2);
-            TILES(c->tile_shift, launch_tile_scatter_fused(st, grid, c->ntiles2, selectors, c->counters.p, c->tile_count.p, c->tile_cursor.p,
-                                      c->bucket.p, c->ucov2(), nullptr, c->tstride, c->tile_items.p, c->split_tiles.p, Totals(),
-                                      tile_sub));
-        } else {
-            {
-                KernelTimer t(c, K_TILE_SCAN2);
-                TILES(c->tile_shift, launch_tile_scan(st, c->ntiles2, c->tile_count.p, c->tile_base.p, c->tile_cursor.p, c->tile_items.p,
-                                 c->counters.p, c->part_items.p, c->sup_cursor.p, c->split_tiles.p, matrix ? 1u : c->treps,
-                                 c->tstride, matrix ? false : c->two_level, Totals(), tile_sub));
-            }
-            {
-                KernelTimer t(c, K_TILE_SCATTER2);
-                if (matrix)
-                    TILES(c->tile_shift, launch_tile_scatter_matrix(st, grid, c->ntiles2, selectors, c->tile_base.p, c->tile_matrix.p, c->tstride,
-                                               c->bucket.p, c->ucov2(), nullptr, tile_sub));
-                else
-                    TILES(c->tile_shift, launch_tile_scatter(st, grid, c->ntiles2, c->rec.n, selectors, c->counters.p, c->tile_base.p,
-                                        c->tile_cursor.p, c->sup_cursor.p, c->part_items.p, c->mid.p, c->bucket.p,
-                                        c->ucov2(), nullptr, c->two_level, c->tile_count.p, c->treps, c->tstride, tile_sub));
-            }
-        }
-        {
-            KernelTimer t(c, K_TILE_HIST2);
-            TILES(c->tile_shift, launch_tile_hist(st, c->ntiles2, c->rec.n, c->bucket.p, c->tile_base.p, c->tile_items.p, c->counters.p,
-                             c->ucov2(), nullptr, c->d_bin_off.p, R, c->d_tile_ref0.p, blockB, BitsLayout(),
-                             // (the tiles behind the bins hold the per-taxon LCA counts k_pack reads back)
-                             c->keep_bins ? 0u : static_cast<uint32_t>(c->Bp / c->tile_bins())));
-        }
+        launch_sel_atomics(st, c->sel.p, c->local_M, static_cast<uint32_t>(c->Bp()), c->ucov2(), c->lca_count.p);
     }
     {
         PackArgs pk;
@@ -1039,17 +897,17 @@ int filter_launch(slimm_ctx* c, bool copy_rows) {
         pk.src[1] = c->marks.p;
         pk.n[1] = R;
         pk.reps[1] = kPackBytes8;  // k_filter sets one byte per (reference, level)
-        pk.src[2] = c->use_tiles ? c->lca_tiles() : c->lca_count.p;
+        pk.src[2] = c->use_tiles() ? c->lca_tiles() : c->lca_count.p;
         pk.n[2] = T;
         if (c->use_rows16) {  // counted per (level, index): summed into per-taxon counts on the way out
             pk.sum_k = 2;
             pk.sum_off = c->d_taxon_off.p;
             pk.sum_idx = c->d_taxon_idx.p;
         }
-        if (c->use_tiles) {  // k_tile_hist left the uniq_cov2 statistics in place
+        if (c->use_tiles()) {  // k_tile_hist left the uniq_cov2 statistics in place
             KernelTimer t(c, K_PACK2);
-            TILES(c->tile_shift, launch_pack(st, blockB + 4ull * R, pk, c->split_tiles.p, c->counters.p, c->ucov2(), nullptr,
-                        c->d_bin_off.p, R, c->d_tile_ref0.p, blockB));
+            const TileTables tt = c->tiles.tables(c->counters.p);
+            TILES(tt.tile_shift, launch_pack(st, blockB + 4ull * R, pk, &tt, c->ucov2(), nullptr, c->d_bin_off.p, R, blockB));
         } else {
             KernelTimer t(c, K_REF_STATS2);
             launch_ref_stats(st, c->ucov2(), nullptr, c->d_bin_off.p, R, blockB, &pk);
@@ -1114,7 +972,7 @@ int slimm_filter_alignments(slimm_ctx* c) {
     const uint32_t* s2 = c->h_stats.p + c->statsA_words();
     h.set_partials_rows(s2, 4, s2 + 5ull * R + 32, s2 + 4ull * R + 32, c->part_pairs.data(), c->n_pairs);
     tr.mark("partials to host profile");
-    c->binsB_stored = !c->use_tiles || c->keep_bins;
+    c->binsB_stored = !c->use_tiles() || c->keep_bins;
     c->filtered = true;
     return SLIMM_OK;
 }
@@ -1137,7 +995,7 @@ int slimm_filter_alignments_launch(slimm_ctx* c) {
     launch_partials_pack(c->stream, c->ref_stats.p + c->statsA_words(), c->R, c->T, c->d_partials.p);
     c->filter_pending = true;
     c->filtered = true;
-    c->binsB_stored = !c->use_tiles || c->keep_bins;
+    c->binsB_stored = !c->use_tiles() || c->keep_bins;
     return SLIMM_OK;
 }
 
@@ -1394,8 +1252,8 @@ int slimm_get_bins(slimm_ctx* c, int which, uint32_t* out) {
         return fail(c, SLIMM_E_INVALID, "the coverage arrays were not kept (slimm_keep_bins)");
     (void)hipSetDevice(c->device);
     const uint32_t* src = which == 0 ? c->cov() : which == 1 ? c->ucov() : c->ucov2();
-    std::vector<uint32_t> padded(c->Bp);
-    HIP_TRY(c, hipMemcpyAsync(padded.data(), src, c->Bp * 4, hipMemcpyDeviceToHost, c->stream));
+    std::vector<uint32_t> padded(c->Bp());
+    HIP_TRY(c, hipMemcpyAsync(padded.data(), src, c->Bp() * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     uint64_t k = 0;
     for (uint32_t r = 0; r < c->R; ++r) {

@@ -1,9 +1,11 @@
 // SLIMM_FORCE: the ONE environment variable by which tests and tuning runs make the library take a path it would not pick
 // by itself -- the layout fallbacks of the tile kernels, the 32-byte lineage rows, a pair set that overflows, a grouping plan.
 //   SLIMM_FORCE="key=value,key,key=value"      (a key without a value reads as 1)
-// Read at every use (a test varies it between two contexts of one process).  Every key has a `-m gpu` test that names it:
-//   direct_atomics, two_level=0|1, fused_scan=0, matrix=0|2, wide_tiles=0|1, tile_shift=13|14, wide_rows, pair_cap=N,
-//   scatter_big=0|1                                   tests/test_gpu_parity.py, test_gpu_layouts.py, test_gpu_group.py
+// Read where a key is used -- the keys of the tile bucketing once, when a context is created (tile_plan.h: TileForces) -- so
+// a test varies it between two contexts of one process.  Every key has a `-m gpu` test that names it:
+//   direct_atomics, two_level=0|1, fused_scan=0, matrix=0|2, wide_tiles=0|1, tile_shift=13|14, scatter_big=0|1 (the tile
+//   bucketing's: which path each takes a layout to is walked by tests/test_tile_plan.py), wide_rows, pair_cap=N
+//                                                     tests/test_gpu_parity.py, test_gpu_layouts.py, test_gpu_group.py
 //   group_bits=N, group_width=N, group_passes=N, group_grid=N, group_staged=0|1      tests/test_gpu_group_by_ident.py
 //   group_collectives=rccl|copy                                                       tests/test_gpu_group.py
 //   record_cap=N (fewer records per context), split_shift_guess (a mid-file member reports its first record one byte

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "record_filter.h"
+#include "tile_plan.h"
 
 // "This value is in a vector register HERE": an empty asm statement that takes and returns it.  It costs nothing and
 // gives a loaded value a use the compiler can neither move nor remove -- without one, a read-only load whose only uses
@@ -195,32 +196,7 @@ void launch_merge_summary(hipStream_t st, const uint32_t* gathered, uint64_t ran
                           const uint32_t* bin_off, uint32_t n_refs, uint64_t bits_off_cov, uint64_t bits_off_ucov,
                           uint32_t* out_stats, const uint32_t* counters);
 
-// ---- LDS-privatised coverage histograms (tile_hist.hip) ----
-// The bins are cut into TILES of 2^shift consecutive bins; tile_hist.hip is compiled once per tile size into its own
-// namespace (tiles13: 8192 bins, tiles14: 16384 bins -- what the 16-bit bucket entries hold beside the unique bit), and a
-// context picks one per layout (context.hip: tile_shift_for).  Smaller tiles: more workgroups of k_tile_hist per CU,
-// faster histograms; larger tiles: half as many bucket frontiers, longer runs of one tile among neighbouring targets
-// and so fewer returning atomics in the direct rounds of the scatter.
-constexpr uint32_t kTileShiftSmall = 13, kTileShiftLarge = 14;
-constexpr uint32_t kTileSub = 49152;                    // bucket entries per k_tile_hist work item (packed 16-bit counts: below
-                                                        // 65536).  Hot tiles (a few present genomes take most of a sample's
-                                                        // reads) are cut into items of this size, each adding its counts to
-                                                        // global memory with atomics, and k_pack goes over them once more:
-                                                        // 16384 / 32768 / 49152 at config 3: k_tile_hist 224 / 162 / 153 us,
-                                                        // k_pack 46 / 27 / 17; config 5: 319 / 312 / 310 and 27 / 15 / 13
-constexpr uint32_t kTileSubB = 16384;                   // ... of phase B's single-array histogram (32-bit counts): the reads
-                                                        // that keep several targets meet in the few tiles of the taxon
-                                                        // entries, and smaller items are more workgroups on those
-constexpr uint32_t kTileSubWide = 262144;               // ... of the wide form (32-bit counts): layouts with far more than
-                                                        // kTileSub entries per tile (tile_sub / wide arguments below)
-constexpr size_t kTileLdsMax = 144 * 1024;              // LDS histogram of tile ids in k_tile_count / k_tile_scatter
-// tile_count: `reps` copies of rep_stride words, zero on entry (k_zero); workgroup b adds to copy b % reps.
-// k_tile_scan sums the copies into tile_base and turns every copy into the start of its stretch inside the buckets,
-// which k_tile_scatter (same grid) then fills through the copy's own cursors: 1/reps of the same-address atomics.
-#ifndef SLIMM_TILE_REPS
-#define SLIMM_TILE_REPS 8
-#endif
-constexpr uint32_t kTileReps = SLIMM_TILE_REPS;
+// ---- LDS-privatised coverage histograms (tile_hist.hip); tile sizes, limits and which kernels a layout runs: tile_plan.h ----
 // the values the bucketing kernels read: one per target (tgt_gbin: bit 31 = unique read), lying in the slots front.hip
 // wrote -- or, slots == nullptr, a dense array of nslots values (the selectors of phase B, one per read: 0xffffffff = none)
 struct SlotValues {
@@ -230,9 +206,9 @@ struct SlotValues {
     bool per_read = false;     // (slot form) a slot's values are its reads', not its targets'
 };
 // The front end leaves the totals of the stream {mapped records, reads, targets} to its consumers (thousands of waves
-// adding to three counters would be as many memory-side atomics in a row): launch_tile_count with part != nullptr
-// writes one partial sum per workgroup (part[grid]), and the scan that follows (launch_tile_scan or
-// launch_tile_scatter_fused, given the same part) adds them up into counters[CNT_V / CNT_M / CNT_P] and tail[0..2].
+// adding to three counters would be as many memory-side atomics in a row): the count (tile_api.inc), told `totals`,
+// writes one partial sum per workgroup (tot_part[grid]), and the scan that follows (k_tile_scan, alone or inside the fused
+// scatter, given them as `part`) adds them up into counters[CNT_V / CNT_M / CNT_P] and tail[0..2].
 struct Totals {
     const uint4* part = nullptr;
     uint32_t nparts = 0;
@@ -252,16 +228,26 @@ struct BitsLayout {
     uint32_t tps = 1;           // tiles per slice
     uint64_t slice_w64 = 0;     // 64-bit words of one array in one slice = tps * (bins per tile / 64)
 };
-constexpr uint32_t kBigRoundTiles = 6144;   // tiles up to which the one-level scatter orders its rounds by tile in LDS
-                                            // (k_tile_scatter_big; the direct rounds beyond)
-constexpr uint32_t kFusedScanTiles = 4064;  // (4096 table entries less the room three small arrays take: tile_hist.hip)
+// The bucketing's tables as the launchers see them (filled by TileBucketing::tables, tile_bucketing.h, which owns them and
+// says what they are; TileTable in tile_plan.h: which of them a path touches)
+struct TileTables {
+    uint32_t tile_shift;  // which build of tile_hist.hip they are for: TILES(t.tile_shift, ...)
+    uint16_t* bucket;
+    uint32_t *tile_count, *tile_base, *tile_cursor, *split_tiles;
+    uint32_t reps, stride;  // copies of the tile counters / cursors and their stride (also a row of the matrix)
+    uint4 *tile_items, *part_items;
+    uint32_t *mid, *sup_cursor, *matrix;
+    uint4* tot_part;
+    const uint32_t* tile_ref0;
+    uint32_t* counters;  // the context's counter block
+};
 namespace tiles13 {
 #include "tile_api.inc"
 }
 namespace tiles14 {
 #include "tile_api.inc"
 }
-// TILES(shift, launch_tile_count(st, ...)): the call in the namespace of the tile size
+// TILES(shift, tile_count_grid(grid)): the call in the namespace of the tile size
 #define TILES(shift, call) ((shift) == ::slimm::kTileShiftLarge ? ::slimm::tiles14::call : ::slimm::tiles13::call)
 
 // ---- bam_decode.hip: BAM alignment records decoded on the device (slimm_push_bam_bytes) ----

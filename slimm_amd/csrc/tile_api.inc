@@ -1,48 +1,40 @@
 // Declarations of tile_hist.hip's entry points -- included by kernels.h inside namespace tiles13 and namespace tiles14
-// (no include guard: once per tile size).
+// (no include guard: once per tile size).  The launch_tile_* are called by the driver alone (tile_bucketing.hip), which
+// takes the kernels of a TilePath (tile_plan.h); `t` are the tables (kernels.h: TileTables).
 int tile_hist_setup(uint32_t ntiles);                   // 0 = usable for this many tiles
 uint32_t tile_count_grid(uint32_t grid);
-void launch_tile_count(hipStream_t st, uint32_t grid, uint32_t ntiles, const SlotValues& in, uint4* part,
-                       uint32_t* tile_count, uint32_t reps, uint32_t rep_stride, uint32_t* matrix = nullptr);
-// Matrix bucketing (more than kFusedScanTiles tiles, as many as an LDS cursor array holds): launch_tile_count with
-// matrix != nullptr stores one ROW of counts per counting workgroup (tile_count_grid(grid) rows of row_stride words),
-// launch_matrix_prefix makes every column its exclusive prefix over the rows and leaves the column sums in total[]
-// (which launch_tile_scan then scans with reps = 1), and launch_tile_scatter_matrix -- same grid as the count -- places
-// every value at tile_base[tile] + its row's prefix + a running LDS count: no global atomics, no rounds.
-void launch_matrix_prefix(hipStream_t st, uint32_t grid, uint32_t ntiles, uint32_t* matrix, uint32_t row_stride, uint32_t* total);
-void launch_tile_scatter_matrix(hipStream_t st, uint32_t grid, uint32_t ntiles, const SlotValues& in, const uint32_t* tile_base,
-                                const uint32_t* matrix, uint32_t row_stride, uint16_t* bucket, uint32_t* cov, uint32_t* ucov,
-                                uint32_t tile_sub = kTileSub);
 uint32_t part_items_upper(uint32_t ntiles, uint32_t n_upper);
 uint32_t tile_items_upper(uint32_t ntiles, uint32_t n_upper);
-void launch_tile_scan(hipStream_t st, uint32_t ntiles, uint32_t* tile_count, uint32_t* tile_base,
-                      uint32_t* tile_cursor, uint4* items, uint32_t* counters, uint4* items2, uint32_t* sup_cursor,
-                      uint32_t* split_tiles, uint32_t reps, uint32_t rep_stride, bool two_level,
-                      const Totals& tot = Totals(), uint32_t tile_sub = kTileSub);
-// bucketing by tile: one level (k_tile_scatter) or two (k_part_super + k_part_tile); also zeroes the tiles (of cov, and of
-// ucov when given) that k_tile_hist will accumulate with atomics
-void launch_tile_scatter(hipStream_t st, uint32_t grid, uint32_t ntiles, uint32_t n_upper, const SlotValues& in,
-                         const uint32_t* counters, const uint32_t* tile_base, uint32_t* tile_cursor, uint32_t* sup_cursor,
-                         const uint4* items2, uint32_t* mid, uint16_t* bucket, uint32_t* cov, uint32_t* ucov, bool two_level,
-                         const uint32_t* rep_base, uint32_t reps, uint32_t rep_stride, uint32_t tile_sub = kTileSub);
-// one-level bucketing with k_tile_scan folded in (<= kFusedScanTiles tiles, kTileReps copies of the counters): after
-// launch_tile_count, with tile_cursor zero; also writes k_tile_hist's work items, the split-tile list and their counts
-void launch_tile_scatter_fused(hipStream_t st, uint32_t grid, uint32_t ntiles, const SlotValues& in, uint32_t* counters,
-                               const uint32_t* tile_count, uint32_t* tile_cursor, uint16_t* bucket, uint32_t* cov,
-                               uint32_t* ucov, uint32_t rep_stride, uint4* items, uint32_t* split_tiles,
-                               const Totals& tot = Totals(), uint32_t tile_sub = kTileSub);
+// totals: also one partial sum {mapped records, reads, targets} per workgroup into t.tot_part (kernels.h: Totals).
+// matrix: instead of adding to a copy of t.tile_count, every counting workgroup stores one ROW of counts
+// (tile_count_grid(grid) rows of t.stride words in t.matrix) ...
+void launch_tile_count(hipStream_t st, uint32_t grid, uint32_t ntiles, const SlotValues& in, const TileTables& t, bool totals,
+                       bool matrix);
+// ... launch_matrix_prefix makes every column its exclusive prefix over the rows and leaves the column sums in
+// t.tile_count (which launch_tile_scan then scans with reps = 1)
+void launch_matrix_prefix(hipStream_t st, uint32_t grid, uint32_t ntiles, const TileTables& t);
+void launch_tile_scan(hipStream_t st, uint32_t ntiles, const TileTables& t, uint32_t reps, bool two_level, const Totals& tot,
+                      uint32_t tile_sub);
+// bucketing by tile, by the path's kernel; also zeroes the tiles (of cov, and of ucov when given) that k_tile_hist will
+// accumulate with atomics.
+//   Fused: one-level with k_tile_scan folded in (<= kFusedScanTiles tiles, kTileReps copies of the counters): after
+//     launch_tile_count, with t.tile_cursor zero; also writes k_tile_hist's work items, the split-tile list and their counts
+//   OrderedRounds / DirectRounds: one level, k_tile_scatter_big / k_tile_scatter
+//   Matrix: same grid as the count, places every value at tile_base[tile] + its row's prefix + a running LDS count: no
+//     global atomics, no rounds
+//   TwoLevel: k_part_super + k_part_tile
+void launch_tile_scatter(hipStream_t st, TilePath path, uint32_t grid, uint32_t ntiles, uint32_t n_upper, const SlotValues& in,
+                         const TileTables& t, uint32_t* cov, uint32_t* ucov, const Totals& tot, uint32_t tile_sub);
 // stats != nullptr: k_tile_hist also accumulates the per-reference statistics {sum a, non-zero a, sum b, non-zero b}
-// (stats[ref * 4 ..], zeroed by the caller) of the finished arrays; tile_ref0[tile] = first reference overlapping the
+// (stats[ref * 4 ..], zeroed by the caller) of the finished arrays; t.tile_ref0[tile] = first reference overlapping the
 // tile (n_refs when none does).  For tiles cut into pieces only the sums are final; launch_pack adds their non-zero
 // counts.  bits: also the 'bin != 0' bitmaps of the two arrays; finished tiles below store_from are not written out
 // (their statistics are still taken)
-void launch_tile_hist(hipStream_t st, uint32_t ntiles, uint32_t n_upper, const uint16_t* bucket, const uint32_t* tile_base,
-                      const uint4* items, const uint32_t* counters, uint32_t* cov, uint32_t* ucov, const uint32_t* bin_off,
-                      uint32_t n_refs, const uint32_t* tile_ref0, uint32_t* stats,
-                      const BitsLayout& bits = BitsLayout(), uint32_t store_from = 0, bool wide = false);
-// small arrays copied back to back to dst; with stats != nullptr also the non-zero bin counts of the tiles k_tile_hist
-// accumulated in pieces (split_tiles[0 .. counters[CNT_SPLIT])), read back from the finished arrays a / b
-void launch_pack(hipStream_t st, uint32_t* dst, const PackArgs& pack, const uint32_t* split_tiles = nullptr,
-                 const uint32_t* counters = nullptr, const uint32_t* a = nullptr, const uint32_t* b = nullptr,
-                 const uint32_t* bin_off = nullptr, uint32_t n_refs = 0, const uint32_t* tile_ref0 = nullptr,
-                 uint32_t* stats = nullptr, const BitsLayout& bits = BitsLayout());
+void launch_tile_hist(hipStream_t st, uint32_t ntiles, uint32_t n_upper, const TileTables& t, uint32_t* cov, uint32_t* ucov,
+                      const uint32_t* bin_off, uint32_t n_refs, uint32_t* stats, const BitsLayout& bits, uint32_t store_from,
+                      bool wide);
+// small arrays copied back to back to dst; with t and stats != nullptr also the non-zero bin counts of the tiles k_tile_hist
+// accumulated in pieces (t->split_tiles[0 .. t->counters[CNT_SPLIT])), read back from the finished arrays a / b
+void launch_pack(hipStream_t st, uint32_t* dst, const PackArgs& pack, const TileTables* t = nullptr, const uint32_t* a = nullptr,
+                 const uint32_t* b = nullptr, const uint32_t* bin_off = nullptr, uint32_t n_refs = 0, uint32_t* stats = nullptr,
+                 const BitsLayout& bits = BitsLayout());

@@ -29,7 +29,6 @@
 
 #include <algorithm>
 
-#include "force.h"
 #include "kernels.h"
 
 // compiled once per tile size (Makefile: -DSLIMM_TILE_SHIFT=13 -> namespace tiles13, =14 -> tiles14; kernels.h)
@@ -71,7 +70,7 @@ __device__ unsigned long long g_prof_t[8 * 4096];
 
 constexpr int kTBlock = 512;
 constexpr uint32_t kTileMask = kTileBins - 1;
-constexpr uint32_t kScanStaged = 16384;  // tiles whose counts k_tile_scan stages in LDS (the one-level bucketing range)
+constexpr uint32_t kScanStaged = kScanStagedTiles;  // tiles whose counts k_tile_scan stages in LDS (the one-level bucketing range)
 
 // The bucketing kernels read values that lie in slots (front.hip): slot s holds its entries compacted at
 // [slots[s].x, slots[s].x + n) with n = slots[s].y (one value per target) or slots[s].z (one value per read).
@@ -1495,10 +1494,12 @@ __global__ __launch_bounds__(512) void k_pack(uint32_t* __restrict__ dst, const 
     }
 }
 
-void launch_pack(hipStream_t st, uint32_t* dst, const PackArgs& pack, const uint32_t* split_tiles, const uint32_t* counters,
-                 const uint32_t* a, const uint32_t* b, const uint32_t* bin_off, uint32_t n_refs, const uint32_t* tile_ref0,
-                 uint32_t* stats, const BitsLayout& bits) {
+void launch_pack(hipStream_t st, uint32_t* dst, const PackArgs& pack, const TileTables* t, const uint32_t* a, const uint32_t* b,
+                 const uint32_t* bin_off, uint32_t n_refs, uint32_t* stats, const BitsLayout& bits) {
     const uint32_t blocks = 256;
+    const uint32_t* const split_tiles = t ? t->split_tiles : nullptr;
+    const uint32_t* const counters = t ? t->counters : nullptr;
+    const uint32_t* const tile_ref0 = t ? t->tile_ref0 : nullptr;
     if (b)
         hipLaunchKernelGGL(k_pack<true>, dim3(blocks), dim3(512), 0, st, dst, pack, split_tiles, counters, a, b, bin_off,
                            n_refs, tile_ref0, stats, bits);
@@ -1511,8 +1512,8 @@ uint32_t tile_count_grid(uint32_t grid) { return (grid + kCountFold - 1) / kCoun
 
 int tile_hist_setup(uint32_t ntiles) {
     // dynamic LDS above 64 KiB has to be opted into
-    size_t bytes = static_cast<size_t>(ntiles) * 4;
-    if (bytes > kTileLdsMax) return -1;
+    const size_t bytes = static_cast<size_t>(ntiles) * 4;
+    if (!tile_tables_fit_lds(ntiles)) return -1;
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_tile_count), hipFuncAttributeMaxDynamicSharedMemorySize,
                             static_cast<int>(bytes)) != hipSuccess)
         return -1;
@@ -1529,94 +1530,80 @@ int tile_hist_setup(uint32_t ntiles) {
     return 0;
 }
 
-void launch_tile_count(hipStream_t st, uint32_t grid, uint32_t ntiles, const SlotValues& in, uint4* part,
-                       uint32_t* tile_count, uint32_t reps, uint32_t rep_stride, uint32_t* matrix) {
+void launch_tile_count(hipStream_t st, uint32_t grid, uint32_t ntiles, const SlotValues& in, const TileTables& t, bool totals,
+                       bool matrix) {
     hipLaunchKernelGGL(k_tile_count, dim3(tile_count_grid(grid)), dim3(kTBlock * kCountFold), static_cast<size_t>(ntiles) * 4, st, in.vals, in.slots,
-                       in.nslots, in.per_read ? 1 : 0, ntiles, tile_count, reps, rep_stride, part, matrix);
+                       in.nslots, in.per_read ? 1 : 0, ntiles, t.tile_count, t.reps, t.stride, totals ? t.tot_part : nullptr,
+                       matrix ? t.matrix : nullptr);
 }
 
-void launch_matrix_prefix(hipStream_t st, uint32_t grid, uint32_t ntiles, uint32_t* matrix, uint32_t row_stride, uint32_t* total) {
-    hipLaunchKernelGGL(k_matrix_prefix, dim3((ntiles + 255u) / 256u), dim3(256), 0, st, matrix, tile_count_grid(grid), ntiles,
-                       row_stride, total);
+void launch_matrix_prefix(hipStream_t st, uint32_t grid, uint32_t ntiles, const TileTables& t) {
+    hipLaunchKernelGGL(k_matrix_prefix, dim3((ntiles + 255u) / 256u), dim3(256), 0, st, t.matrix, tile_count_grid(grid), ntiles,
+                       t.stride, t.tile_count);
 }
 
-void launch_tile_scatter_matrix(hipStream_t st, uint32_t grid, uint32_t ntiles, const SlotValues& in, const uint32_t* tile_base,
-                                const uint32_t* matrix, uint32_t row_stride, uint16_t* bucket, uint32_t* cov, uint32_t* ucov,
-                                uint32_t tile_sub) {
-    hipLaunchKernelGGL(k_tile_scatter_matrix, dim3(tile_count_grid(grid)), dim3(kTBlock * kCountFold),
-                       static_cast<size_t>(ntiles) * 4, st, in.vals, in.slots, in.nslots, in.per_read ? 1 : 0, ntiles, tile_base,
-                       matrix, row_stride, bucket, cov, ucov, tile_sub);
-}
-
-void launch_tile_scan(hipStream_t st, uint32_t ntiles, uint32_t* tile_count, uint32_t* tile_base,
-                      uint32_t* tile_cursor, uint4* items, uint32_t* counters, uint4* items2, uint32_t* sup_cursor,
-                      uint32_t* split_tiles, uint32_t reps, uint32_t rep_stride, bool two_level, const Totals& tot,
+void launch_tile_scan(hipStream_t st, uint32_t ntiles, const TileTables& t, uint32_t reps, bool two_level, const Totals& tot,
                       uint32_t tile_sub) {
-    hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(1024), 0, st, tile_count, ntiles, tile_base, tile_cursor, items, counters,
-                       items2, sup_cursor, split_tiles, reps, rep_stride, two_level ? 1 : 0, tot.part, tot.nparts, tot.tail,
-                       tile_sub);
+    hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(1024), 0, st, t.tile_count, ntiles, t.tile_base, t.tile_cursor, t.tile_items,
+                       t.counters, t.part_items, t.sup_cursor, t.split_tiles, reps, t.stride, two_level ? 1 : 0, tot.part,
+                       tot.nparts, tot.tail, tile_sub);
 }
 
 uint32_t part_items_upper(uint32_t ntiles, uint32_t n_upper) {
     return (ntiles + kSuperTiles - 1) / kSuperTiles + n_upper / kPartSub + 1;
 }
 
-void launch_tile_scatter(hipStream_t st, uint32_t grid, uint32_t ntiles, uint32_t n_upper, const SlotValues& in,
-                         const uint32_t* counters, const uint32_t* tile_base, uint32_t* tile_cursor, uint32_t* sup_cursor,
-                         const uint4* items2, uint32_t* mid, uint16_t* bucket, uint32_t* cov, uint32_t* ucov, bool two_level,
-                         const uint32_t* rep_base, uint32_t reps, uint32_t rep_stride, uint32_t tile_sub) {
-    long big = 1;
-    (void)forced("scatter_big", &big);  // (SLIMM_FORCE, force.h: tests) 0: the direct rounds
-    const bool big_rounds = big != 0;
-    // (the copies' workgroups are the count's: tile_count_grid(grid) of them)
-    if (!two_level && big_rounds && reps > 1 && ntiles <= static_cast<uint32_t>(kBigE) * kBigBlock) {
+void launch_tile_scatter(hipStream_t st, TilePath path, uint32_t grid, uint32_t ntiles, uint32_t n_upper, const SlotValues& in,
+                         const TileTables& t, uint32_t* cov, uint32_t* ucov, const Totals& tot, uint32_t tile_sub) {
+    const int per_read = in.per_read ? 1 : 0;
+    const size_t lds = static_cast<size_t>(ntiles) * 4;
+    switch (path) {
+    case TilePath::Fused:  // (t.tile_cursor zero; t.counters is written: work item and split-tile counts)
+        hipLaunchKernelGGL(k_tile_scatter_fused, dim3(grid), dim3(kTBlock), 0, st, in.vals, in.slots, in.nslots, per_read,
+                           t.counters, ntiles, t.tile_count, t.tile_cursor, t.bucket, cov, ucov, t.stride, t.tile_items,
+                           t.split_tiles, tot.part, tot.nparts, tot.tail, tile_sub);
+        break;
+    case TilePath::OrderedRounds:  // (the copies' workgroups are the count's: tile_count_grid(grid) of them)
         hipLaunchKernelGGL(k_tile_scatter_big<kBigE>, dim3(tile_count_grid(grid)), dim3(kBigBlock), big_lds_bytes(kBigE), st,
-                           in.vals, in.slots, in.nslots, in.per_read ? 1 : 0, ntiles, tile_base, tile_cursor, bucket, cov,
-                           ucov, rep_base, reps, rep_stride, tile_sub);
-        return;
+                           in.vals, in.slots, in.nslots, per_read, ntiles, t.tile_base, t.tile_cursor, t.bucket, cov, ucov,
+                           t.tile_count, t.reps, t.stride, tile_sub);
+        break;
+    case TilePath::DirectRounds:
+        hipLaunchKernelGGL(k_tile_scatter, dim3(grid), dim3(kTBlock), lds, st, in.vals, in.slots, in.nslots, per_read, ntiles,
+                           t.tile_base, t.tile_cursor, t.bucket, cov, ucov, t.tile_count, t.reps, t.stride, tile_sub);
+        break;
+    case TilePath::Matrix:
+        hipLaunchKernelGGL(k_tile_scatter_matrix, dim3(tile_count_grid(grid)), dim3(kTBlock * kCountFold), lds, st, in.vals,
+                           in.slots, in.nslots, per_read, ntiles, t.tile_base, t.matrix, t.stride, t.bucket, cov, ucov, tile_sub);
+        break;
+    case TilePath::TwoLevel:
+        hipLaunchKernelGGL(k_part_super, dim3(grid), dim3(kTBlock), 0, st, in.vals, in.slots, in.nslots, per_read, ntiles,
+                           t.tile_base, t.sup_cursor, t.mid, cov, ucov, tile_sub);
+        hipLaunchKernelGGL(k_part_tile, dim3(part_items_upper(ntiles, n_upper)), dim3(kTBlock), 0, st, t.mid, t.part_items,
+                           t.counters, t.tile_base, t.tile_cursor, ntiles, t.bucket);
+        break;
+    case TilePath::DirectAtomics:  // (no bucketing: not the driver's to launch)
+        break;
     }
-    if (!two_level) {
-        const size_t lds = static_cast<size_t>(ntiles) * 4;
-        hipLaunchKernelGGL(k_tile_scatter, dim3(grid), dim3(kTBlock), lds, st, in.vals, in.slots, in.nslots,
-                           in.per_read ? 1 : 0, ntiles, tile_base, tile_cursor, bucket, cov, ucov, rep_base, reps, rep_stride,
-                           tile_sub);
-        return;
-    }
-    hipLaunchKernelGGL(k_part_super, dim3(grid), dim3(kTBlock), 0, st, in.vals, in.slots, in.nslots, in.per_read ? 1 : 0,
-                       ntiles, tile_base, sup_cursor, mid, cov, ucov, tile_sub);
-    hipLaunchKernelGGL(k_part_tile, dim3(part_items_upper(ntiles, n_upper)), dim3(kTBlock), 0, st, mid, items2, counters,
-                       tile_base, tile_cursor, ntiles, bucket);
-}
-
-// count -> scan -> scatter of the one-level bucketing with the scan inside the scatter kernel (<= 4096 tiles, copies of
-// the counters / cursors in use); tile_cursor must be zero.  counters is written (work item and split-tile counts).
-void launch_tile_scatter_fused(hipStream_t st, uint32_t grid, uint32_t ntiles, const SlotValues& in, uint32_t* counters,
-                               const uint32_t* tile_count, uint32_t* tile_cursor, uint16_t* bucket, uint32_t* cov,
-                               uint32_t* ucov, uint32_t rep_stride, uint4* items, uint32_t* split_tiles,
-                               const Totals& tot, uint32_t tile_sub) {
-    hipLaunchKernelGGL(k_tile_scatter_fused, dim3(grid), dim3(kTBlock), 0, st, in.vals, in.slots, in.nslots,
-                       in.per_read ? 1 : 0, counters, ntiles, tile_count, tile_cursor, bucket, cov, ucov, rep_stride, items,
-                       split_tiles, tot.part, tot.nparts, tot.tail, tile_sub);
 }
 
 uint32_t tile_items_upper(uint32_t ntiles, uint32_t n_upper) { return ntiles + n_upper / std::min(kTileSub, kTileSubB) + 1; }
 
 // cov + ucov (ucov != nullptr: bit kTileShift -- 13 or 14 -- of a bucket entry selects uniq_cov as well) or a single array
 // stats != nullptr: also accumulate the per-reference statistics (zeroed by the caller) of the finished arrays
-void launch_tile_hist(hipStream_t st, uint32_t ntiles, uint32_t n_upper, const uint16_t* bucket, const uint32_t* tile_base,
-                      const uint4* items, const uint32_t* counters, uint32_t* cov, uint32_t* ucov, const uint32_t* bin_off,
-                      uint32_t n_refs, const uint32_t* tile_ref0, uint32_t* stats, const BitsLayout& bits, uint32_t store_from,
+void launch_tile_hist(hipStream_t st, uint32_t ntiles, uint32_t n_upper, const TileTables& t, uint32_t* cov, uint32_t* ucov,
+                      const uint32_t* bin_off, uint32_t n_refs, uint32_t* stats, const BitsLayout& bits, uint32_t store_from,
                       bool wide) {
     const uint32_t grid = tile_items_upper(ntiles, n_upper);
     if (ucov && wide)
-        hipLaunchKernelGGL((k_tile_hist<true, false>), dim3(grid), dim3(hist_block<true, false>()), 0, st, bucket, items, counters, cov, ucov, bin_off,
-                           n_refs, tile_ref0, stats, bits, store_from);
+        hipLaunchKernelGGL((k_tile_hist<true, false>), dim3(grid), dim3(hist_block<true, false>()), 0, st, t.bucket, t.tile_items, t.counters, cov, ucov, bin_off,
+                           n_refs, t.tile_ref0, stats, bits, store_from);
     else if (ucov)
-        hipLaunchKernelGGL((k_tile_hist<true, true>), dim3(grid), dim3(hist_block<true, true>()), 0, st, bucket, items, counters, cov, ucov, bin_off,
-                           n_refs, tile_ref0, stats, bits, store_from);
+        hipLaunchKernelGGL((k_tile_hist<true, true>), dim3(grid), dim3(hist_block<true, true>()), 0, st, t.bucket, t.tile_items, t.counters, cov, ucov, bin_off,
+                           n_refs, t.tile_ref0, stats, bits, store_from);
     else
-        hipLaunchKernelGGL((k_tile_hist<false, false>), dim3(grid), dim3(hist_block<false, false>()), 0, st, bucket, items, counters, cov, cov, bin_off,
-                           n_refs, tile_ref0, stats, bits, store_from);
+        hipLaunchKernelGGL((k_tile_hist<false, false>), dim3(grid), dim3(hist_block<false, false>()), 0, st, t.bucket, t.tile_items, t.counters, cov, cov, bin_off,
+                           n_refs, t.tile_ref0, stats, bits, store_from);
 }
 
 }  // namespace SLIMM_TILE_NS

@@ -47,6 +47,30 @@ def test_layout_fallback_paths(monkeypatch, cfg, knob):
     _check(cfg, seed=6)
 
 
+TILE_BRACKETS = ("k_hist", "k_tile_count", "k_tile_scan", "k_tile_scatter", "k_tile_hist",
+                 "k_tile_count2", "k_tile_scan2", "k_tile_scatter2", "k_tile_hist2")
+
+
+@pytest.mark.parametrize("knobs, counts", [
+    ({}, (0, 1, 0, 1, 1, 1, 0, 1, 1)),                                  # fused: the scan runs inside the scatter
+    ({"fused_scan": 0}, (0, 1, 1, 1, 1, 1, 1, 1, 1)),
+    ({"fused_scan": 0, "matrix": 2}, (0, 1, 1, 1, 1, 1, 1, 1, 1)),      # (the matrix prefix is inside k_tile_count2's bracket)
+    ({"two_level": 1}, (0, 1, 1, 1, 1, 1, 1, 1, 1)),
+    ({"direct_atomics": 1}, (2, 0, 0, 0, 0, 0, 0, 0, 0)),               # k_hist in both phases, no tile kernel
+], ids=["default", "fused_scan=0", "fused_scan=0,matrix=2", "two_level=1", "direct_atomics"])
+def test_layout_timing_brackets_of_each_bucketing_path(monkeypatch, knobs, counts):
+    """Which kernel-timing brackets one profile of a small layout opens under each bucketing path: how often k_hist and
+    the eight k_tile_* ids were bracketed, phase A and phase B."""
+    force(monkeypatch, **knobs)
+    w = make_workload(TINY_REFS, seed=5)
+    s = Slimm.for_workload(w, device=0)
+    s.enable_kernel_timing(True)
+    s.push_records(w.records)
+    assert s.get_profiles() is not None
+    t = s.kernel_times()
+    assert tuple(t[k][1] for k in TILE_BRACKETS) == counts, {k: t[k][1] for k in TILE_BRACKETS}
+
+
 def test_layout_any_order():
     _check(MIXED, seed=7, grouped=False)
 
