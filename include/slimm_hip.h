@@ -608,6 +608,15 @@ int slimm_time_only_kernel(slimm_ctx* ctx, const char* name);
 int slimm_kernel_times(slimm_ctx* ctx, const char** names, double* ms, uint32_t* launches, uint32_t cap,
                        uint32_t* n, int reset);
 
+/* Which count the tile bucketing of the last file took in phase A (out[0..2]) and phase B (out[3..5]):
+ *   stride     1: every value counted, the buckets laid out back to back; S > 1: every S-th slot counted, the buckets laid
+ *              out with capacities ("the sampled count"); 0: the layout has no buckets (direct atomics).  Before the
+ *              context's first file: 1
+ *   fallback   1: a capacity did not hold and the exact chain behind the attempt placed the buckets (S > 1 only)
+ *   peak       the fullest stretch of the attempt, fill / capacity in 1/1024 (above 1024: the one that did not fit)
+ * Waits for the context's stream.  SLIMM_FORCE sample_stride=S, sample_k=K choose S and the head-room for a test. */
+int slimm_get_bucket_sampling(slimm_ctx* ctx, uint32_t out[6]);
+
 /* Diagnostic for record_order = SLIMM_ORDER_ANY: the stream as the device grouped it by read identity for the front end
  * (after slimm_analyze_alignments): per mapped record its identity (qName key << 2 | mate number, src/slimm.hpp:204-208),
  * reference and global bin, records of one identity adjacent and in file order.  Copies min(cap, *n) records to host

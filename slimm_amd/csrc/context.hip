@@ -304,6 +304,12 @@ void slimm_destroy(slimm_ctx* c) {
     if (c->device >= 0) {
         (void)hipSetDevice(c->device);
         if (c->stream) (void)hipStreamSynchronize(c->stream);
+        if (traced("tiles") && c->stream) {  // SLIMM_TRACE=tiles: which count placed the last file's buckets
+            uint32_t v[6];
+            if (slimm_get_bucket_sampling(c, v) == SLIMM_OK)
+                fprintf(stderr, "[trace] tiles: phase A S=%u fallback=%u peak=%.3f, phase B S=%u fallback=%u peak=%.3f (peak: fullest stretch, fill / capacity)\n",
+                        v[0], v[1], v[2] / 1024.0, v[3], v[4], v[5] / 1024.0);
+        }
         for (auto& e : c->ev_used) {
             (void)hipEventDestroy(e.a);
             (void)hipEventDestroy(e.b);
@@ -1297,6 +1303,23 @@ int slimm_get_read_targets(slimm_ctx* c, uint32_t* ref, uint32_t* gbin, uint64_t
 }
 
 int slimm_target_ref_bits(slimm_ctx* c) { return c ? (c->ref16 ? 16 : 32) : SLIMM_E_INVALID; }
+
+int slimm_get_bucket_sampling(slimm_ctx* c, uint32_t out[6]) {
+    if (!c || !out) return SLIMM_E_INVALID;
+    uint32_t cnt[CNT_WORDS] = {0};
+    for (int i = 0; i < 6; ++i) out[i] = 0;
+    if (c->device < 0) return SLIMM_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (c->counters.p) HIP_TRY(c, hipMemcpy(cnt, c->counters.p, sizeof(cnt), hipMemcpyDeviceToHost));
+    for (int ph = 0; ph < 2; ++ph) {
+        const uint32_t S = c->use_tiles() ? c->tiles.sampled[ph] : 0u;
+        out[3 * ph] = S;
+        out[3 * ph + 1] = S > 1 ? cnt[CNT_FALLBACK + ph] : 0u;
+        out[3 * ph + 2] = S > 1 ? cnt[CNT_PEAK + ph] : 0u;
+    }
+    return SLIMM_OK;
+}
 
 int slimm_taxon_count_size(slimm_ctx* c, int stage, uint32_t* n) {
     if (!c || !n) return SLIMM_E_INVALID;

@@ -31,6 +31,9 @@
 //   told), zstd_cut_search=N (slimm_host_zstd_ranges gives a cut up N bytes behind its target: 64 MiB unless told),
 //   zstd_split_wrong_cut (the planner's second cut -- of two members: its only one -- lands one byte late, where no frame
 //   starts: the members or the stitch must refuse it)   tests/test_gpu_split_zstd_sam.py, tests/test_cli_split_input_zstd.py
+//   sample_stride=S (the tile bucketing counts every S-th slot wherever a sampled count can run, 1: nowhere), sample_k=K
+//   (standard deviations of head-room in a capacity: 8 unless told), bucket_room=N (the bucket allocation holds N entries
+//   whatever the file: tile_plan.h)              tests/test_gpu_sampled_count.py, tests/test_tile_sample_plan.py
 //   ref16=0 (the targets' reference words stay 32 bits wide on a database of at most 32 768 references, which takes the
 //   16-bit form otherwise: kernels.h, TargetRefs)                                    tests/test_gpu_ref16.py
 #pragma once
@@ -73,7 +76,8 @@ inline unsigned long long record_cap() {
 
 // SLIMM_TRACE="cli,host,push" (or "all" / "1"): diagnostics on stderr -- cli: the command's stage marks (host/slimm_main.cpp),
 // host: the library's host steps between the device phases (context.h: HostTrace), push: the window pipeline's events
-// (windows.hip).  Nothing is computed differently with it.
+// (windows.hip), tiles: which count placed the last file's buckets, when a context is destroyed (context.hip).  Nothing is
+// computed differently with it.
 inline bool traced(const char* what) {
     const char* e = getenv("SLIMM_TRACE");
     if (!e || !*e) return false;

@@ -33,6 +33,9 @@ enum {
     CNT_ANYGB = 8,  // some record follows a record of the same qName run with a larger mate number (mates interleave)
     CNT_MODE = 7,   // classification picked on the device: 0 = look-back walk, 2 = tagged-word walk (both k_runs), 1 = hash table (k_runs_hash)
     CNT_SPLIT = 9,  // bin tiles cut into several k_tile_hist work items (their non-zero counts are finished by k_pack)
+    CNT_FALLBACK = 11,  // [phase A, phase B]: the sampled count's capacities did not hold (k_tile_scan: their sum against the
+                        // allocation; k_tile_fit: a fill against its capacity) and the exact chain behind them ran
+    CNT_PEAK = 13,      // [phase A, phase B]: the largest fill / capacity of a stretch in 1/1024 (k_tile_fit, first attempt)
     CNT_WORDS = 32
 };
 enum { ERR_REF_RANGE = 1, ERR_RUN_LENGTH = 2, ERR_PAIR_OVERFLOW = 4, ERR_KEY_COLLISION = 8 };
@@ -240,6 +243,16 @@ struct TileTables {
     uint4* tot_part;
     const uint32_t* tile_ref0;
     uint32_t* counters;  // the context's counter block
+    uint32_t entries;    // bucket entries allocated (tile_plan.h: tile_bucket_entries)
+};
+// The sampled count's chain (tile_plan.h, tile_bucketing.hip).  stride S > 1: the count takes every S-th slot, the scan
+// lays out capacities (k standard deviations of head-room) and raises counters[flag] when they do not fit t.entries, the
+// scatter clamps its stores to the allocation and leaves the split tiles to k_tile_fit.  gated: the exact chain behind a
+// sampled attempt -- every kernel returns at once unless counters[flag] is set.
+struct TileSample {
+    uint32_t stride = 1, k = 0;
+    uint32_t flag = 0;   // index of the phase's CNT_FALLBACK word
+    bool gated = false;
 };
 namespace tiles13 {
 #include "tile_api.inc"

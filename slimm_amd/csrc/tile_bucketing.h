@@ -12,6 +12,8 @@ struct TileBucketing {
     TileRun run(TilePhase phase, uint64_t values, uint64_t records) const { return tile_run(layout, plan, phase, values, records); }
 
     DevBuf<uint16_t> bucket;           // targets bucketed by bin tile (the bin inside its tile | unique bit)
+    uint32_t entries = 0;              // ... its entries as reserve() asked for them: what the sampled capacities have to fit
+    uint32_t sampled[2] = {1, 1};      // the S of the last bucket() of phase A / B (slimm_get_bucket_sampling)
     DevBuf<uint32_t> tile_count, tile_base, tile_cursor, split_tiles, tile_matrix;
     DevBuf<uint4> tile_items, part_items;
     DevBuf<uint32_t> mid, sup_cursor;  // level-1 buckets (by super tile) and their cursors
@@ -24,7 +26,7 @@ struct TileBucketing {
     hipError_t reserve(uint32_t n_records);  // the tables sized by the file
     TileTables tables(uint32_t* counters) const {
         return TileTables{layout.tile_shift, bucket.p, tile_count.p, tile_base.p, tile_cursor.p, split_tiles.p, plan.reps, plan.stride,
-                          tile_items.p, part_items.p, mid.p, sup_cursor.p, tile_matrix.p, tot_part.p, d_tile_ref0.p, counters};
+                          tile_items.p, part_items.p, mid.p, sup_cursor.p, tile_matrix.p, tot_part.p, d_tile_ref0.p, counters, entries};
     }
     // what has to be zero when the run's first kernel starts, into the free entries of a phase's clearing launch
     void zero_tables(ZeroArgs& z, const TileRun& r) const {

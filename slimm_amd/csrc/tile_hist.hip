@@ -15,6 +15,8 @@
 //                   tile and round on the copy's cursor, 16-bit entries (bin-in-tile | unique bit) out -- up to
 //                   4096 tiles (k_tile_scatter_fused) ordered by tile in LDS first, so that a tile's run leaves as
 //                   consecutive stores.  Also zeroes the tiles that k_tile_hist will accumulate with atomics.
+//   k_tile_fit      (the sampled count, tile_plan.h: k_tile_count over every S-th slot, k_tile_scan lays out capacities)
+//                   behind the scatter: fills against capacities -- the fallback flag, or the work items from the real fills
 //   k_part_super    two levels, level 1: targets go to their SUPER tile (64 tiles) as 32-bit words
 //                   (bin-in-super | unique bit): few destinations per workgroup, long runs
 //   k_part_tile     level 2: work items of <= 32 K entries of one super tile are split into its 64 tiles
@@ -218,13 +220,21 @@ __device__ __forceinline__ bool piece_load_packed(SlotWalk& w, const uint32_t* _
 // a selector)
 __device__ __forceinline__ uint32_t tile_of(uint32_t v) { return (v & 0x7fffffffu) >> kTileShift; }
 
+// kMode (tile_plan.h: the sampled count) 0: every value; 1: every S-th slot of the workgroup's range (dense form: every S-th
+// piece) -- wave w of the workgroup's W takes the slots lo + w + W j as ever, and of those the ones with (j + w) % S == 0, so
+// that every wave has its share of the sample; the totals come from a pass of their own over ALL the range's descriptors
+// (coalesced: 16 bytes per 768 records); 2: every value, but only when *gate is set (the exact chain behind a sample that
+// did not fit).  The three are three kernels: mode 0 is compiled as if the others were not there.
+template <int kMode>
 __global__ __launch_bounds__(kTBlock * kCountFold) void k_tile_count(const uint32_t* __restrict__ vals, const uint4* __restrict__ slots,
                                                         uint32_t nslots, int per_read, uint32_t ntiles,
                                                         uint32_t* __restrict__ tile_count_all, uint32_t reps,
                                                         uint32_t rep_stride, uint4* __restrict__ part,
-                                                        uint32_t* __restrict__ matrix) {
+                                                        uint32_t* __restrict__ matrix, uint32_t S,
+                                                        const uint32_t* __restrict__ gate) {
     HIP_DYNAMIC_SHARED(uint32_t, s_hist)
     __shared__ uint32_t s_sum[3];
+    if (kMode == 2 && *gate == 0u) return;
     if (threadIdx.x < 3) s_sum[threadIdx.x] = 0;
     // 512 workgroups adding to the same 2.4 K counters serialise in the memory-side atomic units: every workgroup adds to
     // one of `reps` copies instead, and k_tile_scan sums the copies
@@ -233,6 +243,35 @@ __global__ __launch_bounds__(kTBlock * kCountFold) void k_tile_count(const uint3
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63u;
     SlotWalk w = slot_walk(slots, nslots, per_read != 0, kCountFold);
+    if (kMode == 1) {
+        const uint32_t waves = blockDim.x >> 6, wave = w.d_wave;
+        const uint32_t first = tile_sample_first(wave, waves, S);  // this wave's first sampled slot (piece) of the range
+        if (slots) {
+            const uint32_t lo = w.s - wave;
+            if (part) {
+                uint32_t v = 0, h = 0, f = 0;
+                for (uint32_t s = lo + threadIdx.x; s < w.s_end; s += blockDim.x) {
+                    const uint4 d = slots[s];
+                    f += d.y;
+                    h += d.z;
+                    v += d.w;
+                }
+                v = wave_sum_dpp(v);
+                h = wave_sum_dpp(h);
+                f = wave_sum_dpp(f);
+                if (lane == 0u) {
+                    atomicAdd(&s_sum[0], v);
+                    atomicAdd(&s_sum[1], h);
+                    atomicAdd(&s_sum[2], f);
+                }
+            }
+            w.s = lo + first;
+            w.nd = w.s < w.s_end ? slots[w.s] : make_uint4(0u, 0u, 0u, 0u);
+        } else {
+            w.d_wave = first;
+        }
+        w.step = tile_sample_step(waves, S);
+    }
     while (true) {  // four pieces of 256 values per trip, their loads in flight together
         uint32_t v[16];
         bool any = false;
@@ -248,7 +287,7 @@ __global__ __launch_bounds__(kTBlock * kCountFold) void k_tile_count(const uint3
         for (int u = 0; u < 16; ++u)
             if (v[u] != 0xffffffffu) atomicAdd(&s_hist[tile_of(v[u])], 1u);
     }
-    if (part && lane == 0u) {  // the totals of this workgroup's slots (the front end leaves them to its first consumer)
+    if (kMode != 1 && part && lane == 0u) {  // the totals of this workgroup's slots (the front end leaves them to its first consumer)
         atomicAdd(&s_sum[0], w.sum_v);
         atomicAdd(&s_sum[1], w.sum_h);
         atomicAdd(&s_sum[2], w.sum_f);
@@ -333,16 +372,29 @@ __device__ __forceinline__ void publish_totals(const uint4* __restrict__ part, u
 // One workgroup: exclusive scan tile_count -> tile_base (tile_base[ntiles] = total), zero tile_cursor, and cut every
 // tile's bucket into work items of at most kTileSub entries for k_tile_hist: items[k] = {tile, lo, hi, pieces of tile}.
 // A tile with no entry still gets one item (its finished tile is all zeros and has to be written).
+template <bool kSampled>  // (two kernels: the exact one is compiled as if the capacities were not there)
 __global__ __launch_bounds__(1024) void k_tile_scan(uint32_t* __restrict__ tile_count, uint32_t ntiles,
                                                     uint32_t* __restrict__ tile_base, uint32_t* __restrict__ tile_cursor,
                                                     uint4* __restrict__ items, uint32_t* __restrict__ counters,
                                                     uint4* __restrict__ items2, uint32_t* __restrict__ sup_cursor,
                                                     uint32_t* __restrict__ split_tiles, uint32_t reps,
                                                     uint32_t rep_stride, int two_level, const uint4* __restrict__ part,
-                                                    uint32_t nparts, uint32_t* __restrict__ tail, uint32_t tile_sub) {
+                                                    uint32_t nparts, uint32_t* __restrict__ tail, uint32_t tile_sub,
+                                                    uint32_t S, uint32_t cap_k, uint32_t entries, uint32_t flag, int gated) {
+    // S > 1 (kTileReps copies, one stretch of tiles): the counts are a sample's -- every copy's count becomes its CAPACITY
+    // (tile_plan.h: tile_cap) before anything else looks at it, the stretches are laid out with those, no work item is cut
+    // (k_tile_fit cuts them from the fills) and counters[flag] says whether the capacities' sum exceeds the allocation (the
+    // bases are then of no use: the scatter's clamped stores, the fit's early return and the exact chain deal with it).
+    // gated: today's scan, but only when counters[flag] is set; the work items' lo / hi are then counted over the tile's
+    // entries, k_tile_fit's form, which the k_tile_hist of a sampled phase reads (the exact stretches abut).
     __shared__ uint2 s_part[1024];
     __shared__ uint32_t s_nsplit;
     __shared__ uint32_t s_tot[3];
+    __shared__ unsigned long long s_caps;
+    if (gated && counters[flag] == 0u) return;
+    constexpr bool sampled = kSampled;
+    if (sampled && threadIdx.x == 0) s_caps = 0ull;
+    if (sampled) __syncthreads();
     if (part) publish_totals(part, nparts, counters, tail, s_tot);
     __shared__ uint32_t s_cnt[kScanStaged];  // a stretch of tiles: a tile's total over the copies, then its base
     __shared__ uint2 s_wave[16];
@@ -351,6 +403,7 @@ __global__ __launch_bounds__(1024) void k_tile_scan(uint32_t* __restrict__ tile_
     const bool kept = ntiles <= 4096 && reps == kTileReps;  // the copies of <= 4 tiles per thread stay in registers
     uint32_t keep[4][kTileReps];
     uint2 carry = make_uint2(0u, 0u);  // entries and work items of the stretches before this one
+    unsigned long long caps64 = 0ull;  // (sampled) this thread's capacities, added up in 64 bits: ONE LDS atomic per thread
     // stretches of kScanStaged tiles (one for the one-level layouts; the two-level ones, reps == 1, have up to 64 K tiles:
     // reading them in place, every thread its own consecutive tiles, was 85 us for the 45 K tiles of 200 k references)
     for (uint32_t c0 = 0; c0 < ntiles; c0 += kScanStaged) {
@@ -365,6 +418,13 @@ __global__ __launch_bounds__(1024) void k_tile_scan(uint32_t* __restrict__ tile_
                 uint32_t c = 0;
 #pragma unroll
                 for (uint32_t rep = 0; rep < kTileReps; ++rep) keep[q][rep] = tc[static_cast<size_t>(rep) * rep_stride + i];
+                if (sampled) {
+#pragma unroll
+                    for (uint32_t rep = 0; rep < kTileReps; ++rep) {
+                        keep[q][rep] = tile_cap(keep[q][rep], S, cap_k);
+                        caps64 += keep[q][rep];
+                    }
+                }
 #pragma unroll
                 for (uint32_t rep = 0; rep < kTileReps; ++rep) c += keep[q][rep];
                 s_cnt[i] = c;
@@ -376,6 +436,14 @@ __global__ __launch_bounds__(1024) void k_tile_scan(uint32_t* __restrict__ tile_
                     uint32_t v[kTileReps];
 #pragma unroll
                     for (uint32_t rep = 0; rep < kTileReps; ++rep) v[rep] = tc[static_cast<size_t>(rep) * rep_stride + i];
+                    if (sampled) {  // (the capacities back into the table: the second pass below reads them again)
+#pragma unroll
+                        for (uint32_t rep = 0; rep < kTileReps; ++rep) {
+                            v[rep] = tile_cap(v[rep], S, cap_k);
+                            tc[static_cast<size_t>(rep) * rep_stride + i] = v[rep];
+                            caps64 += v[rep];
+                        }
+                    }
 #pragma unroll
                     for (uint32_t rep = 0; rep < kTileReps; ++rep) c += v[rep];
                 } else {
@@ -384,6 +452,7 @@ __global__ __launch_bounds__(1024) void k_tile_scan(uint32_t* __restrict__ tile_
                 s_cnt[i] = c;
             }
         }
+        if (sampled && caps64) atomicAdd(&s_caps, caps64), caps64 = 0ull;
         __syncthreads();
         const uint32_t per = (n + 1023) / 1024;
         const uint32_t lo = min(tid * per, n), hi = min(lo + per, n);
@@ -423,11 +492,12 @@ __global__ __launch_bounds__(1024) void k_tile_scan(uint32_t* __restrict__ tile_
             const uint32_t c = s_cnt[i];
             const uint32_t pieces = c ? (c + tile_sub - 1) / tile_sub : 1u;
             s_cnt[i] = run.x;
-            if (pieces > 1) split_tiles[atomicAdd(&s_nsplit, 1u)] = c0 + i;
-            for (uint32_t k = 0; k < pieces; ++k) {
+            if (pieces > 1 && !sampled) split_tiles[atomicAdd(&s_nsplit, 1u)] = c0 + i;
+            for (uint32_t k = 0; k < pieces && !sampled; ++k) {
                 uint32_t a = run.x + k * tile_sub;
                 uint32_t b = min(a + tile_sub, run.x + c);
-                items[run.y + k] = make_uint4(c0 + i, a, b, pieces);
+                // (gated: a sampled phase's k_tile_hist reads lo / hi counted over the tile's entries, k_tile_fit's form)
+                items[run.y + k] = gated ? make_uint4(c0 + i, a - run.x, b - run.x, pieces) : make_uint4(c0 + i, a, b, pieces);
             }
             run.x += c;
             run.y += pieces;
@@ -480,7 +550,8 @@ __global__ __launch_bounds__(1024) void k_tile_scan(uint32_t* __restrict__ tile_
     }
     if (tid == 1023) {
         tile_base[ntiles] = carry.x;
-        counters[CNT_ITEMS] = carry.y;
+        counters[CNT_ITEMS] = sampled ? 0u : carry.y;
+        if (sampled) counters[flag] = s_caps > entries ? 1u : 0u;
     }
     __shared__ uint32_t s_n2;
     if (tid == 0) s_n2 = 0;
@@ -620,7 +691,7 @@ template <int kPieces>
 __device__ __forceinline__ void scatter_round_direct(const uint32_t (&v)[kPieces], uint32_t ntiles,
                                                      const uint32_t* __restrict__ tile_base,
                                                      uint32_t* __restrict__ tile_cursor, uint16_t* __restrict__ bucket,
-                                                     uint32_t* s_hist) {
+                                                     uint32_t* s_hist, uint32_t last) {
     constexpr int kMaxTilesPerThread = 8;  // tiles per thread whose reservations are in flight together
     for (uint32_t i = threadIdx.x; i < ntiles; i += kTBlock) s_hist[i] = 0;
     __syncthreads();
@@ -649,7 +720,7 @@ __device__ __forceinline__ void scatter_round_direct(const uint32_t (&v)[kPieces
     for (int k = 0; k < kPieces; ++k) {
         if (v[k] == 0xffffffffu) continue;
         const uint32_t pos = atomicAdd(&s_hist[tile_of(v[k])], 1u);
-        bucket[pos] = static_cast<uint16_t>(entry_of(v[k]));
+        bucket[min(pos, last)] = static_cast<uint16_t>(entry_of(v[k]));  // (last: see k_tile_scatter)
     }
     __syncthreads();  // s_hist is cleared by the next round
 }
@@ -694,9 +765,15 @@ __global__ __launch_bounds__(kTBlock) void k_tile_scatter(const uint32_t* __rest
                                                           uint16_t* __restrict__ bucket, uint32_t* __restrict__ cov,
                                                           uint32_t* __restrict__ ucov,
                                                           const uint32_t* __restrict__ rep_base_all, uint32_t reps,
-                                                          uint32_t rep_stride, uint32_t tile_sub) {
+                                                          uint32_t rep_stride, uint32_t tile_sub, uint32_t last,
+                                                          const uint32_t* __restrict__ gate) {
+    // last: the last entry of the bucket allocation.  With counts the stretches hold their values exactly; with the
+    // CAPACITIES of a sampled count (tile_plan.h) a stretch may be too small, its values then run into the next one -- a
+    // result k_tile_fit throws away -- and those of the last stretch would leave the buffer: no store goes behind `last`.
+    // (tile_sub is 0xffffffff then: which tiles are split is k_tile_fit's to say.)  gate != nullptr: only when *gate is set.
     HIP_DYNAMIC_SHARED(uint32_t, s_hist)
     __shared__ uint32_t s_more[kTBlock / 64];
+    if (gate && *gate == 0u) return;
     const uint32_t lid = xcd_logical_id();
     const size_t rep_off = static_cast<size_t>((lid / kCountFold) % reps) * rep_stride;
     uint32_t* __restrict__ tile_cursor = tile_cursor_all + rep_off;
@@ -704,7 +781,7 @@ __global__ __launch_bounds__(kTBlock) void k_tile_scatter(const uint32_t* __rest
     zero_split_tiles(tile_base, ntiles, cov, ucov, tile_sub);
     SlotWalk walk = slot_walk(slots, nslots, per_read != 0, 1, lid);
     bucketing_rounds<kDirectPieces, false>(walk, vals, s_more, [&](const uint32_t (&v)[kDirectPieces]) {
-        scatter_round_direct(v, ntiles, rep_base, tile_cursor, bucket, s_hist);
+        scatter_round_direct(v, ntiles, rep_base, tile_cursor, bucket, s_hist, last);
     });
 }
 
@@ -737,7 +814,9 @@ __global__ __launch_bounds__(kBigBlock) void k_tile_scatter_big(const uint32_t* 
                                                                 uint16_t* __restrict__ bucket, uint32_t* __restrict__ cov,
                                                                 uint32_t* __restrict__ ucov,
                                                                 const uint32_t* __restrict__ rep_base_all, uint32_t reps,
-                                                                uint32_t rep_stride, uint32_t tile_sub) {
+                                                                uint32_t rep_stride, uint32_t tile_sub, uint32_t last,
+                                                                const uint32_t* __restrict__ gate) {
+    // (last, gate: as for k_tile_scatter -- a wave-uniform bound on the store's index and an early return, no register per tile)
     // s_tab[kE * kBigBlock] | 64 more entries, nobody's tiles: where a lane's "no value" counts | s_dst, as large |
     // s_stage[kBigRound] | 64 more words, where a lane's "no value" is put -- the rounds' LDS operations are issued
     // unconditionally, batch after batch (a value behind `if (there is one)` is a branch, and a returning LDS atomic inside
@@ -753,6 +832,7 @@ __global__ __launch_bounds__(kBigBlock) void k_tile_scatter_big(const uint32_t* 
     HIP_DYNAMIC_SHARED(uint32_t, s_dyn)
     __shared__ uint32_t s_more[kBigBlock / 64], s_wtot[kBigBlock / 64];
     constexpr uint32_t kNoTile = kE * kBigBlock;
+    if (gate && *gate == 0u) return;
     static_assert(kBigPieces * (kBigBlock / 64) < 65536 && kBigRound < 65536, "ranks are packed as 16-bit halves");
     uint32_t* const s_tab = s_dyn;
     uint32_t* const s_dst = s_dyn + kNoTile + 64;
@@ -887,7 +967,7 @@ __global__ __launch_bounds__(kBigBlock) void k_tile_scatter_big(const uint32_t* 
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const uint32_t j = (k0 + k) * kBigBlock + tid;
-                if (j < total) bucket[d[k] + j] = static_cast<uint16_t>(e[k] & ((1u << kEntryBits) - 1u));
+                if (j < total) bucket[min(d[k] + j, last)] = static_cast<uint16_t>(e[k] & ((1u << kEntryBits) - 1u));
             }
         }
         __syncthreads();  // (the next round counts in the first table and refills the stage)
@@ -1157,6 +1237,124 @@ __global__ __launch_bounds__(kTBlock) void k_part_tile(const uint32_t* __restric
     }
 }
 
+// Behind the scatter of a sampled attempt (tile_plan.h: the sampled count).  rep_base[copy][tile] = start of the
+// stretch, as k_tile_scan left it; its capacity is the distance to the next stretch's start (copy + 1 of the same tile;
+// behind the last copy tile_base[tile + 1]); cursor[copy][tile] = its fill.
+//   Workgroup 0: any fill above its capacity (or a flag k_tile_scan raised already) -> counters[flag] = 1, the counter
+//   copies cleared for the exact count that follows, nothing else.  Otherwise k_tile_hist's work items from the REAL fills:
+//   {tile, lo, hi, pieces}, lo / hi counted over the tile's entries as its stretches' fills follow each other (k_tile_hist
+//   finds the stretches again); the split tiles listed.  Also counters[peak] = the largest fill / capacity in 1/1024.
+//   Every workgroup: zeroes the tiles cut into pieces (by their fills; of an attempt that did not fit: whatever, the
+//   exact chain's fit zeroes the right ones).
+// (The exact chain behind a failed attempt needs no fit: its scan cuts the items from exact counts, its scatter zeroes.)
+__global__ __launch_bounds__(1024) void k_tile_fit(uint32_t* rep_base, const uint32_t* __restrict__ tile_base,
+                                                   const uint32_t* __restrict__ cursor,
+                                                   uint32_t ntiles, uint32_t rep_stride, uint4* __restrict__ items,
+                                                   uint32_t* __restrict__ split_tiles, uint32_t* __restrict__ counters,
+                                                   uint32_t* __restrict__ cov, uint32_t* __restrict__ ucov, uint32_t tile_sub,
+                                                   uint32_t flag, uint32_t peak) {
+    __shared__ uint32_t s_cnt[kScanStaged];  // a tile's fill over the copies
+    __shared__ uint2 s_wave[16];
+    __shared__ uint32_t s_over, s_peak, s_nsplit;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t raised = counters[flag];
+    if (blockIdx.x == 0) {
+        if (tid == 0) s_over = 0u, s_peak = 0u, s_nsplit = 0u;
+        __syncthreads();
+        uint32_t over = 0u, pk = 0u;
+        for (uint32_t i = tid; i < ntiles; i += 1024u) {
+            uint32_t b[kTileReps + 1], f[kTileReps], c = 0;
+#pragma unroll
+            for (uint32_t rep = 0; rep < kTileReps; ++rep) {
+                b[rep] = rep_base[static_cast<size_t>(rep) * rep_stride + i];
+                f[rep] = cursor[static_cast<size_t>(rep) * rep_stride + i];
+            }
+            b[kTileReps] = tile_base[i + 1];
+#pragma unroll
+            for (uint32_t rep = 0; rep < kTileReps; ++rep) {
+                const uint32_t cap = b[rep + 1] - b[rep];
+                if (f[rep] > cap) over = 1u;
+                // (a float quotient: the figure is a diagnostic, and 39 K 64-bit divisions in one workgroup were 30 us)
+                if (f[rep]) pk = max(pk, static_cast<uint32_t>(min(4.0e9f, 1024.0f * static_cast<float>(f[rep]) / static_cast<float>(max(cap, 1u)))));
+                c += f[rep];
+            }
+            s_cnt[i] = c;
+        }
+        if (over) atomicOr(&s_over, 1u);
+        if (pk) atomicMax(&s_peak, pk);
+        __syncthreads();
+        if (tid == 0) counters[peak] = s_peak;
+        if (raised | s_over) {  // did not fit: the exact chain starts from cleared counter copies
+            if (tid == 0) counters[flag] = 1u;
+            for (uint32_t i = tid; i < kTileReps * rep_stride; i += 1024u) rep_base[i] = 0u;
+            return;
+        }
+        // the work items, as k_tile_scan cuts them from counts: every thread its consecutive tiles
+        const uint32_t per = (ntiles + 1023u) / 1024u;
+        const uint32_t lo = min(tid * per, ntiles), hi = min(lo + per, ntiles);
+        uint32_t mine = 0;
+        for (uint32_t i = lo; i < hi; ++i) {
+            const uint32_t c = s_cnt[i];
+            mine += c ? (c + tile_sub - 1u) / tile_sub : 1u;
+        }
+        const uint32_t lane = tid & 63u, wave = tid >> 6;
+        uint32_t inc = mine;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t a = __shfl_up(inc, o, 64);
+            if (lane >= static_cast<uint32_t>(o)) inc += a;
+        }
+        if (lane == 63u) s_wave[wave] = make_uint2(inc, 0u);
+        __syncthreads();
+        uint32_t at = inc - mine, total = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < 16u; ++w) {
+            const uint32_t t = s_wave[w].x;
+            if (w < wave) at += t;
+            total += t;
+        }
+        for (uint32_t i = lo; i < hi; ++i) {
+            const uint32_t c = s_cnt[i];
+            const uint32_t pieces = c ? (c + tile_sub - 1u) / tile_sub : 1u;
+            if (pieces > 1u) split_tiles[atomicAdd(&s_nsplit, 1u)] = i;
+            for (uint32_t k = 0; k < pieces; ++k) items[at + k] = make_uint4(i, k * tile_sub, min((k + 1u) * tile_sub, c), pieces);
+            at += pieces;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            counters[CNT_ITEMS] = total;
+            counters[CNT_SPLIT] = s_nsplit;
+        }
+    }
+    // every workgroup its consecutive tiles: a thread per tile adds up the fills (one round of loads, not one per tile),
+    // the tiles cut into pieces are listed in LDS and zeroed by the whole workgroup
+    __shared__ uint32_t s_zero[64], s_nzero;
+    const uint32_t share = (ntiles + gridDim.x - 1u) / gridDim.x;
+    for (uint32_t t0 = blockIdx.x * share; t0 < min(ntiles, (blockIdx.x + 1u) * share); t0 += 64u) {
+        __syncthreads();
+        if (tid == 0) s_nzero = 0u;
+        __syncthreads();
+        const uint32_t mine = t0 + tid;
+        if (tid < 64u && mine < min(ntiles, (blockIdx.x + 1u) * share)) {
+            uint32_t c = 0;
+#pragma unroll
+            for (uint32_t rep = 0; rep < kTileReps; ++rep) c += cursor[static_cast<size_t>(rep) * rep_stride + mine];
+            if (c > tile_sub) s_zero[atomicAdd(&s_nzero, 1u)] = mine;
+        }
+        __syncthreads();
+        for (uint32_t z = 0; z < s_nzero; ++z) {
+            const uint32_t tile = s_zero[z];
+            uint4* oc = reinterpret_cast<uint4*>(cov + static_cast<size_t>(tile) * kTileBins);
+            uint4* ou = reinterpret_cast<uint4*>((ucov ? ucov : cov) + static_cast<size_t>(tile) * kTileBins);
+            const uint4 z4 = make_uint4(0, 0, 0, 0);
+            for (uint32_t i = tid; i < kTileBins / 4; i += 1024u) {
+                oc[i] = z4;
+                if (ucov) ou[i] = z4;
+            }
+        }
+    }
+}
+
 // Per-reference statistics of the tile held in LDS (src/reference_contig.hpp:84-91 and the sums reads_count /
 // uniq_reads_count are): every wave owns one eighth of the tile, walks the references overlapping it (their offsets
 // are staged in LDS) and adds its partial results to stats[ref * 4 + {0: sum a, 1: non-zero a, 2: sum b, 3: non-zero b}].
@@ -1304,7 +1502,12 @@ __global__ __launch_bounds__((hist_block<kTwo, kPacked>()), (hist_waves_per_simd
                                                    const uint32_t* __restrict__ counters, uint32_t* __restrict__ cov,
                                                    uint32_t* __restrict__ ucov, const uint32_t* __restrict__ bin_off,
                                                    uint32_t n_refs, const uint32_t* __restrict__ tile_ref0,
-                                                   uint32_t* __restrict__ stats, const BitsLayout bits, uint32_t store_from) {
+                                                   uint32_t* __restrict__ stats, const BitsLayout bits, uint32_t store_from,
+                                                   const uint32_t* __restrict__ rep_base, const uint32_t* __restrict__ rep_fill,
+                                                   uint32_t rep_stride) {
+    // rep_base != nullptr: the items are k_tile_fit's -- [lo, hi) counts over the tile's entries as the fills of its
+    // kTileReps stretches (rep_base / rep_fill [copy][tile]) follow each other; between the stretches lie the unused ends
+    // of their capacities.  Everything behind the accumulation is the same for both kinds of item.
     constexpr uint32_t kWords = kPacked ? kPackWords : kTileBins;   // (packed: two 16-bit counts per word, tile_load4)
     constexpr uint32_t kHB = hist_block<kTwo, kPacked>();
     constexpr uint32_t kWaves = kHB / 64;
@@ -1335,6 +1538,14 @@ __global__ __launch_bounds__((hist_block<kTwo, kPacked>()), (hist_waves_per_simd
     }
     // first reference overlapping the tile (host table; n_refs for tiles behind the last reference), then its and its
     // successors' offsets: issued now, needed after the accumulation
+    // (fit's items: the stretches' starts and fills, asked for now -- scalar loads behind the item's own, a second round
+    // trip per item that the clearing of the tile hides)
+    uint32_t sb[kTileReps], sf[kTileReps];
+#pragma unroll
+    for (uint32_t rep = 0; rep < kTileReps; ++rep) {
+        sb[rep] = rep_base ? rep_base[static_cast<size_t>(rep) * rep_stride + tile] : 0u;
+        sf[rep] = rep_base ? rep_fill[static_cast<size_t>(rep) * rep_stride + tile] : 0u;
+    }
     const uint32_t r0 = stats ? tile_ref0[tile] : n_refs;
     const bool stage_off = threadIdx.x <= kStatRefs && r0 < n_refs && r0 + threadIdx.x <= n_refs;
     const uint32_t off_reg = stage_off ? bin_off[r0 + threadIdx.x] : 0u;  // lands in LDS after the accumulation
@@ -1357,29 +1568,82 @@ __global__ __launch_bounds__((hist_block<kTwo, kPacked>()), (hist_waves_per_simd
             tile_count<kPacked>(s_cov, v & kTileMask);
             if (kTwo && (v & kTileBins)) tile_count<kPacked>(s_ucov, v & kTileMask);
         };
-        const uint32_t a0 = min(hi, (lo + 7u) & ~7u);          // first entry on a 16-byte boundary
-        const uint32_t n8 = (hi - a0) >> 3;                     // whole groups of eight behind it
-        const uint32_t a1 = a0 + (n8 << 3);
-        if (lo + threadIdx.x < a0) one(bucket[lo + threadIdx.x]);
-        if (a1 + threadIdx.x < hi) one(bucket[a1 + threadIdx.x]);
-        const uint4* __restrict__ b8 = reinterpret_cast<const uint4*>(bucket + a0);
-        for (uint32_t i0 = 0; i0 < n8; i0 += 2 * kHB) {
-            uint4 q[2];
+        if (!rep_base) {
+            const uint32_t a0 = min(hi, (lo + 7u) & ~7u);          // first entry on a 16-byte boundary
+            const uint32_t n8 = (hi - a0) >> 3;                     // whole groups of eight behind it
+            const uint32_t a1 = a0 + (n8 << 3);
+            if (lo + threadIdx.x < a0) one(bucket[lo + threadIdx.x]);
+            if (a1 + threadIdx.x < hi) one(bucket[a1 + threadIdx.x]);
+            const uint4* __restrict__ b8 = reinterpret_cast<const uint4*>(bucket + a0);
+            for (uint32_t i0 = 0; i0 < n8; i0 += 2 * kHB) {
+                uint4 q[2];
 #pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const uint32_t i = i0 + u * kHB + threadIdx.x;
-                q[u] = i < n8 ? b8[i] : make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
-            }
+                for (int u = 0; u < 2; ++u) {
+                    const uint32_t i = i0 + u * kHB + threadIdx.x;
+                    q[u] = i < n8 ? b8[i] : make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
+                }
 #pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                if (i0 + u * kHB + threadIdx.x >= n8) continue;
-                const uint32_t w[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
+                for (int u = 0; u < 2; ++u) {
+                    if (i0 + u * kHB + threadIdx.x >= n8) continue;
+                    const uint32_t w[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    one(w[k] & 0xffffu);
-                    one(w[k] >> 16);
+                    for (int k = 0; k < 4; ++k) {
+                        one(w[k] & 0xffffu);
+                        one(w[k] >> 16);
+                    }
                 }
             }
+        } else {  // (wave-uniform: the item's tile picks the words, scalar loads)
+            // ONE loop over the aligned groups of eight of all the stretches, numbered through (a group's stretch: the last
+            // one whose first group is not behind it -- seven selects on wave-uniform numbers), so that the trips are as full
+            // and their loads as far ahead as over one contiguous range; the ragged ends, at most seven entries at either end of
+            // every stretch, go to sixteen threads per stretch and are counted behind the first trip's loads.
+            const uint32_t(&b)[kTileReps] = sb;
+            const uint32_t(&f)[kTileReps] = sf;
+            static_assert(kHB >= 16u * kTileReps, "sixteen threads per stretch take its ragged ends");
+            uint32_t first[kTileReps], pre[kTileReps + 1];  // a stretch's first aligned entry; groups in front of it
+            uint32_t p = 0, ev = 0xffffffffu;
+            pre[0] = 0u;
+#pragma unroll
+            for (uint32_t rep = 0; rep < kTileReps; ++rep) {
+                const uint32_t s = max(lo, p), e = min(hi, p + f[rep]);
+                const uint32_t slo = s < e ? b[rep] + (s - p) : 0u, shi = s < e ? b[rep] + (e - p) : 0u;
+                const uint32_t a0 = min(shi, (slo + 7u) & ~7u), n8 = (shi - a0) >> 3, a1 = a0 + (n8 << 3);
+                first[rep] = a0;
+                pre[rep + 1] = pre[rep] + n8;
+                if ((threadIdx.x >> 4) == rep) {
+                    const uint32_t sub = threadIdx.x & 15u;
+                    const uint32_t at = sub < 8u ? slo + sub : a1 + (sub - 8u), end = sub < 8u ? a0 : shi;
+                    if (at < end) ev = bucket[at];
+                }
+                p += f[rep];
+            }
+            const uint32_t groups = pre[kTileReps];
+            for (uint32_t i0 = 0; i0 < groups; i0 += 2 * kHB) {
+                uint4 q[2];
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const uint32_t g = i0 + u * kHB + threadIdx.x;
+                    uint32_t at = first[0], g0 = 0u;
+#pragma unroll
+                    for (uint32_t rep = 1; rep < kTileReps; ++rep)
+                        if (g >= pre[rep]) at = first[rep], g0 = pre[rep];
+                    q[u] = g < groups ? *reinterpret_cast<const uint4*>(bucket + at + ((g - g0) << 3))
+                                      : make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
+                }
+                if (i0 == 0u && ev != 0xffffffffu) one(ev);
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    if (i0 + u * kHB + threadIdx.x >= groups) continue;
+                    const uint32_t w[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        one(w[k] & 0xffffu);
+                        one(w[k] >> 16);
+                    }
+                }
+            }
+            if (groups == 0u && ev != 0xffffffffu) one(ev);
         }
     }
     HPROF_T(h3);
@@ -1514,9 +1778,10 @@ int tile_hist_setup(uint32_t ntiles) {
     // dynamic LDS above 64 KiB has to be opted into
     const size_t bytes = static_cast<size_t>(ntiles) * 4;
     if (!tile_tables_fit_lds(ntiles)) return -1;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_tile_count), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            static_cast<int>(bytes)) != hipSuccess)
-        return -1;
+    for (auto* k : {k_tile_count<0>, k_tile_count<1>, k_tile_count<2>})
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes)) !=
+            hipSuccess)
+            return -1;
     if ((ntiles + kSuperTiles - 1) / kSuperTiles > kMaxSuper) return -1;
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_tile_scatter), hipFuncAttributeMaxDynamicSharedMemorySize,
                             static_cast<int>(bytes)) != hipSuccess)
@@ -1531,10 +1796,11 @@ int tile_hist_setup(uint32_t ntiles) {
 }
 
 void launch_tile_count(hipStream_t st, uint32_t grid, uint32_t ntiles, const SlotValues& in, const TileTables& t, bool totals,
-                       bool matrix) {
-    hipLaunchKernelGGL(k_tile_count, dim3(tile_count_grid(grid)), dim3(kTBlock * kCountFold), static_cast<size_t>(ntiles) * 4, st, in.vals, in.slots,
+                       bool matrix, const TileSample& sm) {
+    auto* const k = sm.gated ? k_tile_count<2> : sm.stride > 1u ? k_tile_count<1> : k_tile_count<0>;
+    hipLaunchKernelGGL(k, dim3(tile_count_grid(grid)), dim3(kTBlock * kCountFold), static_cast<size_t>(ntiles) * 4, st, in.vals, in.slots,
                        in.nslots, in.per_read ? 1 : 0, ntiles, t.tile_count, t.reps, t.stride, totals ? t.tot_part : nullptr,
-                       matrix ? t.matrix : nullptr);
+                       matrix ? t.matrix : nullptr, sm.stride, t.counters + sm.flag);
 }
 
 void launch_matrix_prefix(hipStream_t st, uint32_t grid, uint32_t ntiles, const TileTables& t) {
@@ -1543,10 +1809,10 @@ void launch_matrix_prefix(hipStream_t st, uint32_t grid, uint32_t ntiles, const 
 }
 
 void launch_tile_scan(hipStream_t st, uint32_t ntiles, const TileTables& t, uint32_t reps, bool two_level, const Totals& tot,
-                      uint32_t tile_sub) {
-    hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(1024), 0, st, t.tile_count, ntiles, t.tile_base, t.tile_cursor, t.tile_items,
+                      uint32_t tile_sub, const TileSample& sm) {
+    hipLaunchKernelGGL(sm.stride > 1u ? k_tile_scan<true> : k_tile_scan<false>, dim3(1), dim3(1024), 0, st, t.tile_count, ntiles, t.tile_base, t.tile_cursor, t.tile_items,
                        t.counters, t.part_items, t.sup_cursor, t.split_tiles, reps, t.stride, two_level ? 1 : 0, tot.part,
-                       tot.nparts, tot.tail, tile_sub);
+                       tot.nparts, tot.tail, tile_sub, sm.stride, sm.k, t.entries, sm.flag, sm.gated ? 1 : 0);
 }
 
 uint32_t part_items_upper(uint32_t ntiles, uint32_t n_upper) {
@@ -1554,7 +1820,12 @@ uint32_t part_items_upper(uint32_t ntiles, uint32_t n_upper) {
 }
 
 void launch_tile_scatter(hipStream_t st, TilePath path, uint32_t grid, uint32_t ntiles, uint32_t n_upper, const SlotValues& in,
-                         const TileTables& t, uint32_t* cov, uint32_t* ucov, const Totals& tot, uint32_t tile_sub) {
+                         const TileTables& t, uint32_t* cov, uint32_t* ucov, const Totals& tot, uint32_t tile_sub,
+                         const TileSample& sm) {
+    const bool fit = sm.stride > 1u;  // k_tile_fit follows: it zeroes the split tiles
+    const uint32_t last = t.entries - 1u;  // (no store behind the allocation, whatever the bases are)
+    const uint32_t* const gate = sm.gated ? t.counters + sm.flag : nullptr;
+    if (fit) tile_sub = 0xffffffffu;
     const int per_read = in.per_read ? 1 : 0;
     const size_t lds = static_cast<size_t>(ntiles) * 4;
     switch (path) {
@@ -1566,11 +1837,11 @@ void launch_tile_scatter(hipStream_t st, TilePath path, uint32_t grid, uint32_t 
     case TilePath::OrderedRounds:  // (the copies' workgroups are the count's: tile_count_grid(grid) of them)
         hipLaunchKernelGGL(k_tile_scatter_big<kBigE>, dim3(tile_count_grid(grid)), dim3(kBigBlock), big_lds_bytes(kBigE), st,
                            in.vals, in.slots, in.nslots, per_read, ntiles, t.tile_base, t.tile_cursor, t.bucket, cov, ucov,
-                           t.tile_count, t.reps, t.stride, tile_sub);
+                           t.tile_count, t.reps, t.stride, tile_sub, last, gate);
         break;
     case TilePath::DirectRounds:
         hipLaunchKernelGGL(k_tile_scatter, dim3(grid), dim3(kTBlock), lds, st, in.vals, in.slots, in.nslots, per_read, ntiles,
-                           t.tile_base, t.tile_cursor, t.bucket, cov, ucov, t.tile_count, t.reps, t.stride, tile_sub);
+                           t.tile_base, t.tile_cursor, t.bucket, cov, ucov, t.tile_count, t.reps, t.stride, tile_sub, last, gate);
         break;
     case TilePath::Matrix:
         hipLaunchKernelGGL(k_tile_scatter_matrix, dim3(tile_count_grid(grid)), dim3(kTBlock * kCountFold), lds, st, in.vals,
@@ -1587,23 +1858,32 @@ void launch_tile_scatter(hipStream_t st, TilePath path, uint32_t grid, uint32_t 
     }
 }
 
+void launch_tile_fit(hipStream_t st, uint32_t ntiles, const TileTables& t, uint32_t* cov, uint32_t* ucov, uint32_t tile_sub,
+                     const TileSample& sm) {
+    const uint32_t peak = CNT_PEAK + (sm.flag - CNT_FALLBACK);
+    hipLaunchKernelGGL(k_tile_fit, dim3(std::min(ntiles, 256u)), dim3(1024), 0, st, t.tile_count, t.tile_base, t.tile_cursor,
+                       ntiles, t.stride, t.tile_items, t.split_tiles, t.counters, cov, ucov, tile_sub, sm.flag, peak);
+}
+
 uint32_t tile_items_upper(uint32_t ntiles, uint32_t n_upper) { return ntiles + n_upper / std::min(kTileSub, kTileSubB) + 1; }
 
 // cov + ucov (ucov != nullptr: bit kTileShift -- 13 or 14 -- of a bucket entry selects uniq_cov as well) or a single array
 // stats != nullptr: also accumulate the per-reference statistics (zeroed by the caller) of the finished arrays
 void launch_tile_hist(hipStream_t st, uint32_t ntiles, uint32_t n_upper, const TileTables& t, uint32_t* cov, uint32_t* ucov,
                       const uint32_t* bin_off, uint32_t n_refs, uint32_t* stats, const BitsLayout& bits, uint32_t store_from,
-                      bool wide) {
+                      bool wide, bool stretched) {
     const uint32_t grid = tile_items_upper(ntiles, n_upper);
+    const uint32_t* const rb = stretched ? t.tile_count : nullptr;
+    const uint32_t* const rf = stretched ? t.tile_cursor : nullptr;
     if (ucov && wide)
         hipLaunchKernelGGL((k_tile_hist<true, false>), dim3(grid), dim3(hist_block<true, false>()), 0, st, t.bucket, t.tile_items, t.counters, cov, ucov, bin_off,
-                           n_refs, t.tile_ref0, stats, bits, store_from);
+                           n_refs, t.tile_ref0, stats, bits, store_from, rb, rf, t.stride);
     else if (ucov)
         hipLaunchKernelGGL((k_tile_hist<true, true>), dim3(grid), dim3(hist_block<true, true>()), 0, st, t.bucket, t.tile_items, t.counters, cov, ucov, bin_off,
-                           n_refs, t.tile_ref0, stats, bits, store_from);
+                           n_refs, t.tile_ref0, stats, bits, store_from, rb, rf, t.stride);
     else
         hipLaunchKernelGGL((k_tile_hist<false, false>), dim3(grid), dim3(hist_block<false, false>()), 0, st, t.bucket, t.tile_items, t.counters, cov, cov, bin_off,
-                           n_refs, t.tile_ref0, stats, bits, store_from);
+                           n_refs, t.tile_ref0, stats, bits, store_from, rb, rf, t.stride);
 }
 
 }  // namespace SLIMM_TILE_NS

@@ -44,6 +44,82 @@ constexpr uint32_t kScanStagedTiles = 16384;  // tiles whose counter copies k_ti
 constexpr uint32_t kBigRoundTiles = 6144;     // tiles whose rounds k_tile_scatter_big orders in LDS (the direct rounds beyond)
 constexpr uint32_t kFusedScanTiles = 4064;    // (4096 table entries less the room three small arrays take: tile_hist.hip)
 
+// ---- the sampled count (OrderedRounds and DirectRounds with kTileReps counter copies) ----
+// k_tile_count may count every S-th slot (dense form: piece) only; k_tile_scan then gives every (copy, tile) stretch a
+// CAPACITY instead of its count, the scatter fills the stretches as ever, and k_tile_fit compares every fill with its
+// capacity: one stretch too small and the whole bucketing runs again with S = 1 (tile_bucketing.hip).  A 1-in-S thinning
+// of n entries estimates n with a standard deviation of sqrt(S n) -- at the TRUE n, which is what has to be bounded: the
+// largest n that lies within k deviations of the estimate S c solves (n - S c)^2 = k^2 S n, so
+//   cap(c) = S (c + k^2 / 2 + k sqrt(c + k^2 / 4)) + S      (c: the sampled count; k: kSampleK standard deviations)
+// With the variance taken at the estimate instead (S c + k sqrt(S (S c + S)) + S, the first form of this rule) the large
+// stretches had their k deviations and the small ones did not: a stretch of 145 entries of which a 1-in-16 sample saw none
+// overran cap(0) = 144 with probability 9e-5, and the headline has 39 K stretches (profiles/round17: the fullest stretch at
+// 0.98 of its capacity).  Now cap(0) = S k^2 + S = 1040 at S = 16, which 1040 entries miss with probability (15/16)^1040 =
+// 7e-30.  At S entries of the estimate per 1024 of the stretch (kSamplePerStride) the head-room is 29 % at most.
+#if defined(__HIPCC__)
+#define SLIMM_HD __host__ __device__
+#else
+#define SLIMM_HD
+#endif
+constexpr uint32_t kSampleMaxStride = 16;
+constexpr uint32_t kSampleK = 8;
+constexpr uint32_t kSamplePerStride = 1024;  // values per (copy, tile) and unit of S below which S is halved
+// Values a sample has to leave unread to be worth its risk: the sampled chain costs k_tile_fit, three launches that return
+// at once and a longer scan -- about 45 us a phase -- and the count reads 4 bytes per value at 5.2 TB/s.  Asked for: TWICE
+// that cost in skipped bytes, 112 M values = 86 us.  Measured (profiles/round17): config 3, phase A, 100 M values at S = 2
+// lost 16 us a step; the headline's phase B, 119 M selectors at S = 2, was level (-42 us of count, +53 of chain) and keeps
+// the full count with both; its phase A, 1 B at S = 16, skips 937 M.
+constexpr uint64_t kSampleMinSkipped = 112000000ull;
+SLIMM_HD inline uint64_t tile_isqrt_up(uint64_t x) {  // the least r with r * r >= x (x < 2^62); host: the allocation's bound
+    uint64_t r = static_cast<uint64_t>(__builtin_sqrt(static_cast<double>(x)));
+    while (r * r > x) --r;
+    while ((r + 1) * (r + 1) <= x) ++r;
+    return r * r < x ? r + 1 : r;
+}
+SLIMM_HD inline uint32_t tile_isqrt_up32(uint32_t x) {  // the same in 32 bits (x < 2^31): what k_tile_scan takes per stretch
+    uint32_t r = static_cast<uint32_t>(__builtin_sqrtf(static_cast<float>(x)));  // (a first guess: the loops make it exact)
+    while (r * r > x) --r;
+    while ((r + 1u) * (r + 1u) <= x) ++r;
+    return r * r < x ? r + 1u : r;
+}
+// the capacity of a stretch whose sample counted c: S c + S k^2 / 2 + k S ceil(sqrt(4 c + k^2)) / 2 (rounded up) + S; k <= 64.
+// Never above 0xffffffff (c from 2^28 on: the sum then cannot fit any allocation, and k_tile_scan, which adds the
+// capacities up in 64 bits, says so)
+SLIMM_HD inline uint32_t tile_cap(uint32_t c, uint32_t S, uint32_t k) {
+    if (c >= (1u << 28)) return 0xffffffffu;
+    const uint32_t r = tile_isqrt_up32(4u * c + k * k);  // < 2^15
+    const uint64_t cap = static_cast<uint64_t>(S) * c + (S * k * k + 1u) / 2u + (k * S * r + 1u) / 2u + S;
+    return cap > 0xffffffffull ? 0xffffffffu : static_cast<uint32_t>(cap);
+}
+// Which slots (dense form: pieces) of a counting workgroup's range a sampled count takes.  Wave w of the workgroup's W
+// walks the range's slots w, w + W, w + 2 W, ...: its j-th is sampled when (j + w) % S == 0, so every wave has a share of
+// the sample.  first: the wave's first sampled slot of the range, step: from one sampled slot to its next.
+SLIMM_HD inline uint32_t tile_sample_first(uint32_t wave, uint32_t waves, uint32_t S) { return wave + waves * ((S - wave % S) % S); }
+SLIMM_HD inline uint32_t tile_sample_step(uint32_t waves, uint32_t S) { return waves * S; }
+// S for `values` values at most over ntiles tiles and kTileReps copies: the largest power of two <= kSampleMaxStride that
+// leaves kSamplePerStride values per (copy, tile) and unit of S; 1 = count everything (fewer than 2048 per stretch).
+// `values` is what the host knows before the launch -- phase A: the file's RECORDS, of which 0.62 are targets at the
+// headline (15.8 K per stretch where S = 16 asks for 16 K) -- and an average: a skewed file has stretches of a few hundred
+// entries beside the full ones.  Neither matters to whether a stretch fits, which tile_cap holds at any size; they move
+// the head-room spent (k sqrt(S / n) of a stretch of n) up a little.
+inline uint32_t tile_sample_stride(uint64_t values, uint32_t ntiles) {
+    const uint64_t per = values / (static_cast<uint64_t>(kTileReps) * std::max(1u, ntiles));
+    uint32_t S = kSampleMaxStride;
+    while (S > 1 && per < static_cast<uint64_t>(kSamplePerStride) * S) S >>= 1;
+    return S;
+}
+// Bucket entries beyond the values themselves that the capacities of `stretches` stretches may take.  The estimates S c
+// add up to the values give or take sqrt(S values): est = values + k of those.  The roots ceil(sqrt(4 c + k^2)) add up to
+// at most sqrt(stretches * (4 est / S + k^2 stretches)) + stretches (Cauchy-Schwarz, and the rounding), so
+//   sum(cap) <= est + (k S / 2) (that) + (S k^2 / 2 + S + 2) stretches.
+// A sum that does not fit after all is one more reason for the exact fallback, never an overrun.
+inline uint64_t tile_cap_slack(uint64_t values, uint64_t stretches, uint32_t S, uint32_t k) {
+    if (S <= 1) return 0;
+    const uint64_t est = values + k * tile_isqrt_up(S * values);
+    const uint64_t roots = tile_isqrt_up(stretches * (4 * est / S + 4 + static_cast<uint64_t>(k) * k * stretches)) + stretches;
+    return (est - values) + (static_cast<uint64_t>(k) * S * roots + 1) / 2 + (static_cast<uint64_t>(S) * k * k / 2 + S + 2) * stretches;
+}
+
 struct TileLayout {
     uint32_t tile_shift = kTileShiftSmall;  // log2 of the bins per tile: which build of tile_hist.hip runs
     uint64_t Bp = 0;                        // bins per coverage array, padded to whole tiles
@@ -78,6 +154,10 @@ struct TileForces {
     long scatter_big = 1;  // 0: the direct rounds instead of the ordered ones
     int wide_tiles = -1;   // -1: by the file's size, 0 / 1: never / always
     long tile_shift = 0;   // 13 / 14
+    long sample_stride = 0;  // 0: by size; 1: always the full count; 2 .. 16: this S wherever a sampled count can run
+    long sample_k = -1;      // -1: kSampleK
+    long bucket_room = 0;    // > 0: the bucket allocation holds this many entries whatever the file (a test of the capacities'
+                             // sum against it; it has to hold the file's values)
     static TileForces from_env() {
         TileForces f;
         long v = 0;
@@ -88,6 +168,9 @@ struct TileForces {
         (void)forced("scatter_big", &f.scatter_big);
         if (forced("wide_tiles", &v)) f.wide_tiles = v == 1;
         (void)forced("tile_shift", &f.tile_shift);
+        (void)forced("sample_stride", &f.sample_stride);
+        (void)forced("sample_k", &f.sample_k);
+        (void)forced("bucket_room", &f.bucket_room);
         return f;
     }
 };
@@ -100,6 +183,8 @@ struct TilePlan {  // of a layout: what holds for both phases
     bool matrix_allowed = false;    // phase B may bucket through a count matrix (one row per counting workgroup, no atomics)
     bool matrix_always = false, scatter_big = true;
     int wide_tiles = -1;
+    uint32_t sample_stride = 0, sample_k = kSampleK;  // TileForces: 0 = by size
+    uint64_t bucket_room = 0;
 };
 // setup_ok: tile_hist_setup took the layout (it refuses what tile_tables_fit_lds refuses, and a failing HIP call)
 inline TilePlan tile_plan(uint32_t ntiles2, const TileForces& f, bool setup_ok) {
@@ -123,6 +208,9 @@ inline TilePlan tile_plan(uint32_t ntiles2, const TileForces& f, bool setup_ok) 
     p.matrix_always = f.matrix == 2;
     p.scatter_big = f.scatter_big != 0;
     p.wide_tiles = f.wide_tiles;
+    p.sample_stride = static_cast<uint32_t>(std::min<long>(std::max<long>(f.sample_stride, 0), kSampleMaxStride));
+    if (f.sample_k >= 0) p.sample_k = static_cast<uint32_t>(std::min<long>(f.sample_k, 64));
+    p.bucket_room = f.bucket_room > 0 ? static_cast<uint64_t>(f.bucket_room) : 0;
     return p;
 }
 
@@ -147,7 +235,14 @@ struct TileRun {  // the path of a phase and what depends on it
     uint32_t tile_sub = kTileSub;  // entries per work item of k_tile_hist
     bool wide_hist = false;        // k_tile_hist with 32-bit counts for two arrays (phase B's one array has them anyway)
     uint32_t tables = 0, zeroed = 0;  // TileTable bits: what the path uses, and what of it is zero when its first kernel starts
+    uint32_t sample = 1;           // S of the count: 1 = every value (today's chain), > 1 = sampled, capacities, k_tile_fit
+    uint32_t sample_k = kSampleK;
 };
+// whether a run may count a sample at all: the rounds whose bases and cursors come from k_tile_scan, with all the copies
+// (Fused scans inside its scatter, Matrix needs exact rows, TwoLevel exact super tiles, DirectAtomics has no buckets)
+inline bool tile_path_samples(const TilePlan& p, TilePath path, uint32_t ntiles) {
+    return (path == TilePath::OrderedRounds || path == TilePath::DirectRounds) && p.reps == kTileReps && ntiles <= kScanStagedTiles;
+}
 // values: the phase's values (phase A: a target per record at most; phase B: a selector per read); records: the file's
 inline TileRun tile_run(const TileLayout& l, const TilePlan& p, TilePhase phase, uint64_t values, uint64_t records) {
     TileRun r;
@@ -172,7 +267,24 @@ inline TileRun tile_run(const TileLayout& l, const TilePlan& p, TilePhase phase,
     r.tables = kTabCount | kTabItems | kTabBucket | (p.fused ? 0u : kTabBase) | (matrix ? kTabMatrix : kTabCursor) |
                (r.path == TilePath::TwoLevel ? kTabSuper : 0u);
     r.zeroed = kTabCount | (p.fused ? kTabCursor : 0u);  // (otherwise k_tile_scan clears the cursors)
+    r.sample_k = p.sample_k;
+    if (tile_path_samples(p, r.path, r.ntiles))
+        r.sample = p.sample_stride ? p.sample_stride : tile_sample_stride(values, r.ntiles);
+    if (!p.sample_stride && r.sample > 1 && values - values / r.sample < kSampleMinSkipped) r.sample = 1;
     return r;
+}
+
+// Entries of the bucket allocation for a file of n records (no more values than that in either phase): the values, one
+// more, and the head-room of the sampled capacities -- at 1 B records over 4 888 tiles of 8 copies, S = 16, k = 8: 22.5 % more
+// (0.45 GB).  k_tile_scan gets this number as the allocation the capacities have to fit.
+inline uint64_t tile_bucket_entries(const TileLayout& l, const TilePlan& p, uint64_t n) {
+    if (p.bucket_room) return p.bucket_room;
+    uint64_t slack = 0;
+    for (TilePhase ph : {TilePhase::A, TilePhase::B}) {
+        const TileRun r = tile_run(l, p, ph, n, n);
+        slack = std::max(slack, tile_cap_slack(n, static_cast<uint64_t>(kTileReps) * r.ntiles, r.sample, r.sample_k));
+    }
+    return n + 1 + slack;
 }
 
 }  // namespace slimm

@@ -706,6 +706,14 @@ class Slimm:
         """Width of a target's reference word on the device: 16 (at most 32768 references) or 32."""
         return self.L.slimm_target_ref_bits(self.ctx)
 
+    def bucket_sampling(self) -> Dict[str, Dict[str, int]]:
+        """Per phase ("A", "B") of the last file: the tile bucketing's count stride (1: every value, S > 1: sampled), whether
+        the exact fallback ran, and the fullest stretch's fill / capacity in 1/1024 (slimm_get_bucket_sampling)."""
+        v = np.zeros(6, dtype=np.uint32)
+        self._check(self.L.slimm_get_bucket_sampling(self.ctx, _p(v)))
+        return {ph: {"stride": int(v[3 * i]), "fallback": int(v[3 * i + 1]), "peak_1024": int(v[3 * i + 2])}
+                for i, ph in enumerate("AB")}
+
     def taxon_counts(self, stage: int = 1) -> Dict[int, int]:
         n = C.c_uint32()
         self._check(self.L.slimm_taxon_count_size(self.ctx, stage, C.byref(n)))
