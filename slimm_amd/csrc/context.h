@@ -24,8 +24,8 @@
 #include "force.h"
 #include "bzip2_block.h"
 #include "deflate_stream.h"
-#include "zstd_frame.h"
-#include "xz_stream.h"
+#include "zstd_walk.h"
+#include "xz_walk.h"
 #include "kernels.h"
 #include "read_identity.h"
 

@@ -11,7 +11,7 @@
 #include <utility>
 #include <vector>
 
-#include "../xz_stream.h"
+#include "../xz_walk.h"
 #include "text_reader.hpp"
 
 namespace slimm {
@@ -29,18 +29,10 @@ public:
     const Counts& counts() const { return n_; }
 
 private:
-    enum class Stage { Between, Stream, Chunks };
     bool next_text() override;   // the next chunk that holds text, behind the block's text so far (at least its dictionary's worth is kept)
-    bool fail(const std::string& where, uint32_t status, const std::string& more = "");
-    bool end_block();
-    bool read_index();
-    Stage stage_ = Stage::Between;
-    uint32_t check_ = 0;
-    std::vector<std::pair<uint64_t, uint64_t>> records_;   // the stream's blocks so far: unpadded size, uncompressed size
-    // the block being read: its header, where it starts, its bytes and text so far, the chunk rules, the decoder
-    xz::BlockHeader bh_{};
-    uint64_t block_at_ = 0, block_comp_ = 0, block_text_ = 0, since_ = 0, crc_ = 0;
-    xz::Rules rules_;
+    bool fail(const std::string& words);
+    xz::Walker walk_;   // the container: where the reader stands in it, the stream's check kind and records, the block at hand
+    uint64_t since_ = 0, crc_ = 0;   // the block's text since its last dictionary reset, its check register
     xz::Lzma lz_{};
     std::vector<uint16_t> probs_;
     Counts n_;

@@ -79,79 +79,52 @@ uint32_t ZstdReader::decode_compressed(const uint8_t* content, uint32_t size, ui
     return zs::kOk;
 }
 
+// the container is the walker's (../zstd_walk.h); here: the bytes it asks for, and what its blocks decode to
 bool ZstdReader::next_text() {
-    auto at = [&](size_t pos) { return std::to_string(in_base_ + pos); };
-    for (;;) {
-        if (!in_frame_) {
-            if (!need(4)) {
-                if (in_.size() == pos_ && frames_ > 0) {
-                    done_ = true;
-                    return false;
-                }
-                const size_t left = in_.size() - pos_;
-                return fail("at byte " + at(pos_), frames_ == 0 || zs::magic_prefix(in_.data() + pos_, left) ? zs::kRanOut : zs::kNoFrame);
-            }
-            const uint32_t magic = zs::le32(in_.data() + pos_);
-            if ((magic & 0xfffffff0u) == zs::kSkippable) {
-                if (!need(8)) return fail("skippable frame at byte " + at(pos_), zs::kRanOut);
-                const size_t n = zs::le32(in_.data() + pos_ + 4);
-                if (!need(8 + n)) return fail("skippable frame at byte " + at(pos_), zs::kRanOut);
-                pos_ += 8 + n;
-                ++frames_;
-                continue;
-            }
-            if (magic != zs::kMagic) return fail("at byte " + at(pos_), frames_ ? zs::kNoFrame : zs::kRanOut);
-            uint32_t st;
-            while ((st = zs::frame_header(in_.data() + pos_, in_.size() - pos_, fh_)) == zs::kRanOut && need(in_.size() - pos_ + 1)) {
-            }
-            if (st != zs::kOk) return fail("frame header at byte " + at(pos_), st);
-            frame_at_ = in_base_ + pos_;
-            pos_ += fh_.bytes;
-            in_frame_ = true;
-            ++frames_;
+    for (bool any = false;;) {
+        if (any && walk_.stage != zs::Walker::Checksum) return true;   // (a checksum behind the text is read with it)
+        const zs::Walker::Item it = walk_.peek(in_.data() + pos_, in_.size() - pos_, in_base_ + pos_);
+        if (it.kind == zs::Walker::More && need(it.want)) continue;
+        if (it.kind == zs::Walker::More || it.kind == zs::Walker::Error) return fail(it.where(), it.status);
+        if (it.kind == zs::Walker::MayEnd) {
+            if (need(1)) continue;
+            done_ = true;
+            return false;
+        }
+        const std::string frame = zs::place_text(zs::Place::Frame, walk_.frame_at);
+        if (it.kind == zs::Walker::Header) {
             frame_len_ = 0;
             entropy_.reset();
             rep_[0] = 1, rep_[1] = 4, rep_[2] = 8;
             xxh_.reset();
             text_.clear();
             served_ = 0;
-        }
-        if (!need(3)) return fail("block header at byte " + at(pos_), zs::kRanOut);
-        const uint32_t h = zs::le24(in_.data() + pos_), type = (h >> 1) & 3u, size = h >> 3;
-        const bool last = h & 1u;
-        const std::string where = "block at byte " + at(pos_);
-        if (type == 3u) return fail(where, zs::kReservedBlock);
-        if (size > fh_.block_max) return fail(where, zs::kBlockTooLarge);
-        const size_t content = type == zs::kRleBlock ? 1u : size;
-        if (!need(3 + content)) return fail(where, zs::kRanOut);
-        // (the text kept: the window in front of this block)
-        if (served_ == text_.size() && text_.size() > 2u * fh_.window + (1u << 20)) {
-            text_.erase(text_.begin(), text_.end() - static_cast<long>(fh_.window));
-            served_ = text_.size();
-        }
-        const size_t before = text_.size();
-        const size_t frame_lo = frame_len_ >= before ? 0u : before - static_cast<size_t>(frame_len_);
-        const uint8_t* p = in_.data() + pos_ + 3;
-        if (type == zs::kRaw) text_.insert(text_.end(), p, p + size);
-        else if (type == zs::kRleBlock)
-            text_.insert(text_.end(), size, p[0]);
-        else {
-            const uint32_t st = decode_compressed(p, size, fh_.block_max, fh_.window, entropy_, rep_, text_, frame_lo);
-            if (st != zs::kOk) return fail(where, st);
-        }
-        pos_ += 3 + content;
-        xxh_.update(text_.data() + before, text_.size() - before);
-        frame_len_ += text_.size() - before;
-        if (last) {
-            if (fh_.has_size && fh_.content_size != frame_len_) return fail("frame at byte " + std::to_string(frame_at_), zs::kBadContentSize);
-            if (fh_.has_checksum) {
-                if (!need(4)) return fail("checksum at byte " + at(pos_), zs::kRanOut);
-                if (zs::le32(in_.data() + pos_) != static_cast<uint32_t>(xxh_.digest())) return fail("frame at byte " + std::to_string(frame_at_), zs::kBadChecksum);
-                pos_ += 4;
+        } else if (it.kind == zs::Walker::Sum) {
+            if (it.sum != static_cast<uint32_t>(xxh_.digest())) return fail(frame, zs::kBadChecksum);
+        } else if (it.kind == zs::Walker::Block) {
+            const zs::FrameHeader& fh = walk_.fh;
+            // (the text kept: the window in front of this block)
+            if (served_ == text_.size() && text_.size() > 2u * fh.window + (1u << 20)) {
+                text_.erase(text_.begin(), text_.end() - static_cast<long>(fh.window));
+                served_ = text_.size();
             }
-            in_frame_ = false;
+            const size_t before = text_.size();
+            const size_t frame_lo = frame_len_ >= before ? 0u : before - static_cast<size_t>(frame_len_);
+            const uint8_t* p = in_.data() + pos_ + 3;
+            if (it.type == zs::kRaw) text_.insert(text_.end(), p, p + it.size);
+            else if (it.type == zs::kRleBlock)
+                text_.insert(text_.end(), it.size, p[0]);
+            else {
+                const uint32_t st = decode_compressed(p, it.size, fh.block_max, fh.window, entropy_, rep_, text_, frame_lo);
+                if (st != zs::kOk) return fail(it.where(), st);
+            }
+            xxh_.update(text_.data() + before, text_.size() - before);
+            frame_len_ += text_.size() - before;
+            if (it.last && fh.has_size && fh.content_size != frame_len_) return fail(frame, zs::kBadContentSize);
+            any = text_.size() > before;
         }
-        if (text_.size() > before) return true;
+        walk_.take(it);
+        pos_ += it.bytes;
     }
 }
 

@@ -9,7 +9,7 @@
 #include <string>
 #include <vector>
 
-#include "../zstd_frame.h"
+#include "../zstd_walk.h"
 #include "text_reader.hpp"
 
 namespace slimm {
@@ -21,8 +21,8 @@ public:
     // where the reader stands: the file offset behind the last block it decoded (its checksum included), whether a frame
     // goes on there, and that frame's header (the split planner walks on from here: split.hip)
     uint64_t file_pos() const { return in_base_ + pos_; }
-    bool in_frame() const { return in_frame_; }
-    const zs::FrameHeader& frame() const { return fh_; }
+    bool in_frame() const { return walk_.stage != zs::Walker::Between; }
+    const zs::FrameHeader& frame() const { return walk_.fh; }
     // one compressed block's content -> its text behind `text` (whose bytes from frame_lo on are the frame's so far):
     // the serial use of zstd_frame.h, also what the tests compare the device decoder's stages with
     static uint32_t decode_compressed(const uint8_t* content, uint32_t size, uint32_t block_max, uint64_t window, zs::Entropy& e, uint32_t rep[3],
@@ -31,9 +31,8 @@ public:
 private:
     bool next_text() override;   // the next block that holds text, behind the frame's text so far (at least its last `window` bytes are kept)
     bool fail(const std::string& where, uint32_t status);
-    bool in_frame_ = false;
-    uint64_t frames_ = 0, frame_at_ = 0, frame_len_ = 0;
-    zs::FrameHeader fh_{};
+    zs::Walker walk_;   // the frames and block headers: where the reader stands in them
+    uint64_t frame_len_ = 0;
     zs::Entropy entropy_;
     uint32_t rep_[3] = {1, 4, 8};
     zs::Xxh64 xxh_;

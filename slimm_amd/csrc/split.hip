@@ -317,7 +317,7 @@ int split_zstd_ends(slimm_ctx* const* members, uint32_t n, uint32_t* bad) {
         *bad = k;
         if (!split_is_zstd(c) || !A.has_range)
             return fail(c, SLIMM_E_INVALID, "a range of a zstd file: slimm_set_input_range tells where it lies");
-        if (c->win.file.zst.stage != WindowPipeline::File::Zstd::Between || at != A.range_end || T.pend.size() != (T.bit >> 3))
+        if (c->win.file.zst.walk.stage != zs::Walker::Between || at != A.range_end || T.pend.size() != (T.bit >> 3))
             return fail(c, SLIMM_E_SPLIT, "zstd: the frames of member %u end at byte %llu, its range at byte %llu: the range does not end at a frame boundary", k,
                         static_cast<unsigned long long>(at), static_cast<unsigned long long>(A.range_end));
     }
@@ -346,10 +346,10 @@ int split_xz_streams(slimm_ctx* const* members, uint32_t n, uint32_t* bad) {
         if (Z.from_left != open)
             return fail(c, SLIMM_E_SPLIT, open ? "xz: member %u starts at a stream header, and the stream on its left has not ended"
                                                : "xz: member %u was told a check kind, and no stream lies over the cut in front of it", k);
-        if (Z.from_left && Z.check != check && !Z.left_closed)
-            return fail(c, SLIMM_E_SPLIT, "xz: member %u was told check kind %u, the stream's header states %u", k, static_cast<unsigned>(Z.check),
+        if (Z.from_left && Z.walk.check != check && Z.walk.open_left)
+            return fail(c, SLIMM_E_SPLIT, "xz: member %u was told check kind %u, the stream's header states %u", k, static_cast<unsigned>(Z.walk.check),
                         static_cast<unsigned>(check));
-        if (Z.from_left && Z.left_closed) {   // (its footer's kind was the told one: xz_round)
+        if (Z.from_left && !Z.walk.open_left) {   // (its footer's kind was the told one: xz_round)
             if (static_cast<uint32_t>(A.xz_check) != check)
                 return fail(c, SLIMM_E_SPLIT, "xz: member %u was told check kind %d, the stream's header states %u", k, A.xz_check, static_cast<unsigned>(check));
             if (blocks != Z.left_kept)
@@ -358,10 +358,10 @@ int split_xz_streams(slimm_ctx* const* members, uint32_t n, uint32_t* bad) {
             open = false;
             blocks.clear();
         }
-        if (Z.stage == XF::Blocks) {   // (the range ends among a stream's blocks)
-            if (!open) check = Z.check;
+        if (Z.walk.stage == xz::Walker::Blocks) {   // (the range ends among a stream's blocks)
+            if (!open) check = Z.walk.check;
             open = true;
-            blocks.insert(blocks.end(), Z.records.begin(), Z.records.end());
+            blocks.insert(blocks.end(), Z.walk.records.begin(), Z.walk.records.end());
         }
     }
     *bad = n - 1u;

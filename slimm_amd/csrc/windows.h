@@ -241,17 +241,16 @@ struct WindowPipeline {
             bool carried = false;    // slot 0 of the window scratch holds the last 32 768 bytes of the text so far
             std::vector<gz::Chunk> ready;
         } gz;
-        // zstd SAM, the host's side: where in a frame stream.bit is and what the frame's blocks hand on (the descriptions a
-        // block may repeat, the repeat offsets, the text's length and XXH64 so far), the bytes of history the device holds;
-        // the blocks and frames of the round at hand
+        // zstd SAM, the host's side: where in the container stream.bit is (zstd_walk.h: the stage, the frame's header and
+        // file offset, the frames so far) and what the frame's blocks hand on (the descriptions a block may repeat, the
+        // repeat offsets, the text's length and XXH64 so far), the bytes of history the device holds; the blocks and
+        // frames of the round at hand
         struct Zstd {
-            enum Stage { Between, Blocks, Checksum } stage = Between;
-            zs::FrameHeader fh{};
-            uint64_t frame_at = 0, frame_len = 0;
+            zs::Walker walk;
+            uint64_t frame_len = 0;
             zs::Entropy entropy;
             uint32_t rep[3] = {1, 4, 8};
             zs::Xxh64 xxh{};
-            uint64_t any_frames = 0;
             uint64_t hist_len = 0;
             struct Frame {   // a frame with blocks in the round
                 uint32_t first = 0, n = 0;   // its blocks of the round
@@ -269,26 +268,21 @@ struct WindowPipeline {
             uint64_t text = 0;                // the round's text bytes (behind zs_round)
             uint64_t round_hist = 0;
         } zst;
-        // xz SAM, the host's side: where stream.bit is -- between streams, or among a stream's blocks --, the stream's check
-        // kind and its blocks so far (unpadded size, text bytes: what its index must say); the blocks of the round at hand
+        // xz SAM, the host's side: where in the container stream.bit is (xz_walk.h: between streams or among a stream's
+        // blocks, the stream's check kind and its blocks so far -- what its index must say); the blocks of the round at hand
         struct Xz {
-            enum Stage { Between, Blocks } stage = Between;
-            uint32_t check = 0;
-            uint64_t any_streams = 0;
-            std::vector<std::pair<uint64_t, uint64_t>> records;
+            xz::Walker walk;
             std::vector<xz::Block> ready;
             std::vector<uint64_t> ready_at;   // the blocks' file offsets (errors)
             uint64_t text = 0;                // the round's text bytes (behind xz_round)
             // a byte range of a split file (Announced::has_range).  A range that was told a check kind starts among the
-            // blocks of a stream whose header lies on its left: until it meets that stream's index `records` holds its own
-            // blocks of it; the index's last records are then checked against them, and the records in front of those --
-            // the blocks of the ranges on the left -- are kept for the stitch (split.hip: split_xz_streams).  A range that
-            // ends among a stream's blocks leaves its blocks of that stream in `records`
+            // blocks of a stream whose header lies on its left (xz::Walker::among_blocks): that stream's index hands back the
+            // records in front of the range's own -- the blocks of the ranges on the left --, kept for the stitch (split.hip:
+            // split_xz_streams).  A range that ends among a stream's blocks leaves its blocks of that stream in walk.records
             bool started = false;        // the walk has taken its start from what was announced
             bool from_left = false;      // the range starts among the blocks of a stream
-            bool left_closed = false;    // ... and has met that stream's index, at file offset left_index_at
-            uint64_t left_index_at = 0;
-            std::vector<std::pair<uint64_t, uint64_t>> left_kept;
+            uint64_t left_index_at = 0;  // ... and has met that stream's index (walk.open_left is off again) at this file offset
+            std::vector<xz::Walker::Record> left_kept;
         } xz;
     } file;
 
@@ -316,6 +310,58 @@ struct WindowPipeline {
     // slimm_destroy, once the context's main and copy streams are idle: the inflate streams waited for and destroyed, the
     // caller's buffers unlocked, `outgrown` freed, the events destroyed (the buffers free themselves)
     void destroy();
+};
+
+// What the rounds of the codecs that walk a container share (zs_round, xz_round; the walkers: zstd_walk.h, xz_walk.h): the
+// byte position in stream.pend, and what a walker's "needs more bytes" or error becomes.  A byte range of a split file
+// (check_push: its range is announced) starts and ends at the codec's boundaries or the cut is refused -- SLIMM_E_SPLIT, no
+// verdict on the file: the caller reads it through one context.  The range rules, once:
+//   an error, or a shortfall at the last push, on the range's FIRST item    the range starts mid-file    no_start
+//   a shortfall at the last push                                            the range ends mid-file      no_end
+//   anything else                                                                                        the codec's words
+int fail(slimm_ctx* c, int code, const char* fmt, ...);
+struct RoundCursor {
+    slimm_ctx* c;
+    WindowPipeline::File::Stream& T;
+    const WindowPipeline::Announced& A;
+    const char *codec, *start_noun, *end_noun;   // "zstd", "frame", "frame"; "xz", "stream", "block"
+    const bool last, starts_mid, ends_mid;
+    uint64_t pos;        // the next byte of stream.pend (these codecs read at bytes): put back into stream.bit however the round ends
+    bool hold = false;   // blocks in front are ready: an error behind them waits until they are decoded (errors come in file order)
+    RoundCursor(slimm_ctx* ctx, WindowPipeline& W, bool last_push, const char* name, const char* starts_at, const char* ends_at)
+        : c(ctx), T(W.file.stream), A(W.announced), codec(name), start_noun(starts_at), end_noun(ends_at), last(last_push),
+          starts_mid(A.has_range && A.starts_mid), ends_mid(A.has_range && A.ends_mid), pos(T.bit >> 3) {}
+    ~RoundCursor() { T.bit = pos * 8u; }
+    const uint8_t* p() const { return T.pend.data() + pos; }
+    uint64_t avail() const { return T.pend.size() - pos; }
+    uint64_t at() const { return T.base + pos; }   // the position as a file offset
+    int wait() { return T.waiting = true, SLIMM_OK; }   // more bytes may come
+    // the host reader's words (host/alignment_file.cpp: codec_read)
+    int fail_words(const std::string& words) {
+        return hold ? SLIMM_OK : fail(c, SLIMM_E_INVALID, "%s-compressed input is not supported unless it decodes: %s", codec, words.c_str());
+    }
+    int no_start(const char* what) {
+        return hold ? SLIMM_OK : fail(c, SLIMM_E_SPLIT, "%s: the range starts at byte %llu, where no %s starts", codec, static_cast<unsigned long long>(at()), what);
+    }
+    int no_end(const std::string& where) {
+        return hold ? SLIMM_OK : fail(c, SLIMM_E_SPLIT, "%s: %s runs past byte %llu: the range does not end at a %s boundary", codec, where.c_str(),
+                                      static_cast<unsigned long long>(A.range_end), end_noun);
+    }
+    // what a step lacks: more bytes may come, or the file ends inside it
+    int wait_or(const std::string& where, const std::string& words) {
+        if (!last) return wait();
+        return ends_mid ? no_end(where) : fail_words(words);
+    }
+    // A walker's outcome that is no item -- an error, or a shortfall (`where`, and `words` with its cause) --, `between`:
+    // where a frame / stream may start, `any` of which have been met.  SLIMM_OK: the round ends and waits, or holds
+    int settle(bool error, bool between, bool any, const std::string& where, const std::string& words) {
+        const bool first = between && starts_mid && !any;
+        if (error) return first ? no_start(start_noun) : fail_words(words);
+        if (!between) return wait_or(where, words);
+        if (!last || (avail() == 0 && (any || starts_mid || ends_mid))) return wait();   // (the file may end here; a range may be empty)
+        if (ends_mid) return no_end("what starts at byte " + std::to_string(at()));
+        return first ? no_start(start_noun) : fail_words(words);
+    }
 };
 
 // SLIMM_TRACE=push: what the pipeline does and when, on stderr: "[push <ms since the first line>] ...", or "[push <tag>] ..."
@@ -347,26 +393,26 @@ int gz_round(slimm_ctx* c, bool last);
 bool gz_next_window(const slimm_ctx* c, uint64_t cap, uint64_t* n);
 int gz_emit(slimm_ctx* c, uint8_t* dst, uint64_t cap, uint64_t* n_out, uint8_t* last_byte);
 void gz_trace_file(const slimm_ctx* c);
-// zstd_decode.hip (slimm_push_zstd_sam_bytes): zs_round plans the whole blocks of stream.pend (frame and block headers
-// walked on the host), decodes their literals and sequences on the device and leaves the round's blocks, with their text
-// lengths, in file.zst.ready.  zs_emit: the text built behind the history, resolved, and written to dst; zs_check, behind
-// the window's launch: the content checksums of the frames that ended
-// (A byte range of a split file -- Announced::has_range --: the range starts at a frame and ends between frames, both
-// SLIMM_E_SPLIT otherwise; nothing in front of the range exists for it, and an empty range, or one of skippable frames only,
-// decodes no text)
+// zstd_decode.hip (slimm_push_zstd_sam_bytes): zs_round takes the container's items from zs::Walker (zstd_walk.h) -- the
+// format's rules are there, the range rules in RoundCursor above --, plans the whole blocks of stream.pend up to the round's
+// text cap, decodes their literals and sequences on the device and leaves the round's blocks, with their text lengths, in
+// file.zst.ready.  zs_emit: the text built behind the history, resolved, and written to dst; zs_check, behind the window's
+// launch: the content checksums of the frames that ended
+// (A byte range of a split file -- Announced::has_range --: the range starts at a frame and ends between frames; nothing in
+// front of the range exists for it, and an empty range, or one of skippable frames only, decodes no text)
 constexpr uint64_t kZstdRoundBytes = 32ull << 20;   // compressed bytes gathered for a round; also the least a member's range of a split file is worth (slimm_zstd_split_floor)
 int zs_round(slimm_ctx* c, bool last);
 bool zs_next_window(const slimm_ctx* c, uint64_t cap, uint64_t* n);
 int zs_emit(slimm_ctx* c, uint8_t* dst, uint64_t cap, uint64_t* n_out, uint8_t* last_byte);
 int zs_check(slimm_ctx* c);
 void zs_trace_file(const slimm_ctx* c);
-// xz_decode.hip (slimm_push_xz_sam_bytes): xz_round walks what lies at stream.bit -- stream headers, block headers and
-// their chunk chains, indexes, footers, padding -- and leaves the whole blocks at hand, with their exact text offsets, in
-// file.xz.ready.  xz_emit: the blocks decoded, a lane each, their checks folded from pieces and compared, the text written
-// to dst.
+// xz_decode.hip (slimm_push_xz_sam_bytes): xz_round takes the container's items from xz::Walker (xz_walk.h), a block's
+// chunks up to its end -- a block whose bytes are not all at hand is left at its header --, and leaves the whole blocks at
+// hand, with their exact text offsets, in file.xz.ready.  xz_emit: the blocks decoded, a lane each, their checks folded
+// from pieces and compared, the text written to dst.
 // (A byte range of a split file -- Announced::has_range --: the range starts at a stream header or, told the stream's check
-// kind, at a block's first byte, and ends at a block's first byte or between streams, both SLIMM_E_SPLIT otherwise; nothing
-// in front of the range exists for it, and an empty range decodes no text)
+// kind, at a block's first byte, and ends at a block's first byte or between streams; nothing in front of the range exists
+// for it, and an empty range decodes no text)
 int xz_round(slimm_ctx* c, bool last);
 bool xz_next_window(const slimm_ctx* c, uint64_t cap, uint64_t* n);
 int xz_emit(slimm_ctx* c, uint8_t* dst, uint64_t cap, uint64_t* n_out, uint8_t* last_byte);

@@ -342,10 +342,10 @@ const StreamCodec kCodecs[] = {
      [](const File& F) { return static_cast<int>(F.gz.stage); }, nullptr, [](WindowPipeline& W) { return W.gz_stats; },
      WindowPipeline::kGzStats, WindowPipeline::kGzCompressed, nullptr, nullptr},
     {"zstd", "zstd_round", kZstdRoundBytes, true, true, zs_round, zs_next_window, zs_emit, zs_check, zs_trace_file,
-     [](const File& F) { return static_cast<int>(F.zst.stage); }, nullptr, [](WindowPipeline& W) { return W.zs_stats; },
+     [](const File& F) { return static_cast<int>(F.zst.walk.stage); }, nullptr, [](WindowPipeline& W) { return W.zs_stats; },
      WindowPipeline::kZsStats, WindowPipeline::kZsCompressedBytes, nullptr, nullptr},
     {"xz", "xz_round", 32ull << 20, true, true, xz_round, xz_next_window, xz_emit, nullptr, xz_trace_file,
-     [](const File& F) { return static_cast<int>(F.xz.stage); }, nullptr, [](WindowPipeline& W) { return W.xz_stats; },
+     [](const File& F) { return static_cast<int>(F.xz.walk.stage); }, nullptr, [](WindowPipeline& W) { return W.xz_stats; },
      WindowPipeline::kXzStats, WindowPipeline::kXzCompressedBytes, "an", "block"},
 };
 const StreamCodec& codec_of(Codec k) { return kCodecs[static_cast<size_t>(k)]; }

@@ -27,7 +27,6 @@ constexpr uint64_t kXzTail = 16;                    // zeroed bytes behind the c
 constexpr uint64_t kXzRoundText = 512ull << 20;     // a round's text at most (SLIMM_FORCE xz_round_text=N), or one block alone
 constexpr uint64_t kXzBlockTextMax = 1ull << 30;    // one block of more text than that is refused
 using XF = WindowPipeline::File::Xz;
-using Stage = XF::Stage;
 
 // (a decoder is ONE lane of a wave of its own, as k_gz_decode's and k_bz2_decode's: lanes of one wave that decode different
 // blocks would take each other's branches in turn, and a file has far fewer blocks than the device has waves.  The 28 268
@@ -156,21 +155,8 @@ void push_trace_xz(const char* fmt, ...) {   // "[push xz] ..."
 }
 
 // the host reader's words (host/alignment_file.cpp: codec_read)
-int xz_fail(slimm_ctx* c, const std::string& where, uint32_t status, const std::string& more = "") {
-    return fail(c, SLIMM_E_INVALID, "xz-compressed input is not supported unless it decodes: %s: %s%s", where.c_str(), xz::status_text(status), more.c_str());
-}
-
-// inside xz_round's loop: the error now, or -- behind blocks that are ready -- once they are decoded
-#define XZ_FAIL(call)                \
-    {                                \
-        if (!Z.ready.empty()) break; \
-        return call;                 \
-    }
-
-bool all_zero(const uint8_t* p, uint64_t n) {
-    for (uint64_t i = 0; i < n; ++i)
-        if (p[i]) return false;
-    return true;
+int xz_fail(slimm_ctx* c, const std::string& where, uint32_t status) {
+    return fail(c, SLIMM_E_INVALID, "xz-compressed input is not supported unless it decodes: %s: %s", where.c_str(), xz::status_text(status));
 }
 
 }  // namespace
@@ -190,188 +176,90 @@ int xz_round(slimm_ctx* c, bool last) {
     Z.text = 0;
     if (T.waiting && !last) return SLIMM_OK;
     T.waiting = false;   // (at the file's end what waited for bytes is looked at again: it ends the streams, or is truncated)
-    // (xz reads at bytes: `pos` is the stream's bit, put back however the round ends)
-    uint64_t pos = T.bit >> 3;
-    struct PutBack {
-        uint64_t &bit, &pos;
-        ~PutBack() { bit = pos * 8u; }
-    } put_back{T.bit, pos};
+    // (errors come in file order: what is wrong behind blocks that are ready is looked at again by the next round, once those
+    // blocks are decoded -- nothing is read past it: RoundCursor::hold)
+    RoundCursor cur(c, W, last, "xz", "stream", "block");
     long cap_text = 0;
     if (!forced("xz_round_text", &cap_text) || cap_text <= 0) cap_text = static_cast<long>(kXzRoundText);
-    auto at = [&](uint64_t byte) { return std::to_string(T.base + byte); };
-    // a byte range of a split file (check_push: its range is announced).  It starts at a stream header or -- told the check
-    // kind of the stream around it, which sizes the field behind every block -- at a block's first byte, and ends at a
-    // block's first byte or between streams, or the cut is refused: SLIMM_E_SPLIT, no verdict on the file
+    using Walk = xz::Walker;
+    Walk& K = Z.walk;
     const WindowPipeline::Announced& A = W.announced;
-    const bool starts_mid = A.has_range && A.starts_mid, ends_mid = A.has_range && A.ends_mid;
-    auto no_start = [&](uint64_t byte, const char* what) {
-        return fail(c, SLIMM_E_SPLIT, "xz: the range starts at byte %s, where no %s starts", at(byte).c_str(), what);
-    };
-    auto no_end = [&](const std::string& where) {
-        return fail(c, SLIMM_E_SPLIT, "xz: %s runs past byte %llu: the range does not end at a block boundary", where.c_str(),
-                    static_cast<unsigned long long>(A.range_end));
-    };
     if (!Z.started) {
         Z.started = true;
-        if (starts_mid && A.xz_check >= 0) {   // (among the blocks of a stream whose header lies in a range on the left)
-            Z.stage = Stage::Blocks;
-            Z.check = static_cast<uint32_t>(A.xz_check);
+        if (cur.starts_mid && A.xz_check >= 0) {   // (among the blocks of a stream whose header lies in a range on the left)
+            K.among_blocks(static_cast<uint32_t>(A.xz_check));
             Z.from_left = true;
-            Z.any_streams = 1;
         }
     }
-    // what a step lacks: more bytes may come, or the file ends inside it
-    // (errors come in file order: what is wrong behind blocks that are ready is looked at again by the next round, once
-    // those blocks are decoded -- nothing is read past it: XZ_FAIL)
-    auto wait_or = [&](const std::string& where) {
-        if (last && Z.ready.empty()) return ends_mid ? no_end(where) : xz_fail(c, where, xz::kRanOut);
-        if (!last) T.waiting = true;
-        return static_cast<int>(SLIMM_OK);
-    };
     const uint64_t n_bytes = T.pend.size();
     const uint8_t* p = T.pend.data();
     uint64_t text = 0;
     uint32_t pieces = 0;
-    while (!T.waiting) {
-        uint64_t avail = n_bytes - pos;
-        if (Z.stage == Stage::Between) {
-            while (Z.any_streams > 0 && avail >= 4u && all_zero(p + pos, 4)) pos += 4u, avail -= 4u;   // (stream padding)
-            if (avail < xz::kHeaderBytes) {
-                if (!last || (avail == 0 && (Z.any_streams > 0 || starts_mid || ends_mid))) {   // (the file may end here; a range may be empty)
-                    T.waiting = true;
-                    break;
-                }
-                if (ends_mid) XZ_FAIL(no_end("what starts at byte " + at(pos)));
-                if (starts_mid && Z.any_streams == 0) XZ_FAIL(no_start(pos, "stream"));
-                if (Z.any_streams == 0 || xz::magic_prefix(p + pos, avail)) XZ_FAIL(xz_fail(c, "stream header at byte " + at(pos), xz::kRanOut));
-                XZ_FAIL(xz_fail(c, "at byte " + at(pos), all_zero(p + pos, avail) ? xz::kBadPadding : xz::kTrailing));
-            }
-            if (!xz::is_magic(p + pos) && starts_mid && Z.any_streams == 0) XZ_FAIL(no_start(pos, "stream"));
-            if (!xz::is_magic(p + pos)) XZ_FAIL(xz_fail(c, "at byte " + at(pos), Z.any_streams > 0 && p[pos] == 0 ? xz::kBadPadding : xz::kTrailing));
-            const uint32_t hs = xz::stream_header(p + pos, &Z.check);
-            if (hs != xz::kOk && starts_mid && Z.any_streams == 0) XZ_FAIL(no_start(pos, "stream"));   // (the magic's bytes, inside some block)
-            if (hs != xz::kOk) XZ_FAIL(xz_fail(c, "stream header at byte " + at(pos), hs));
-            pos += xz::kHeaderBytes;
-            Z.records.clear();
-            Z.stage = Stage::Blocks;
-            ++Z.any_streams;
-            ++stats[WindowPipeline::kXzStreams];
-            continue;
-        }
-        if (avail < 1u) {
-            if (ends_mid) {   // (a range may end at a block's first byte: the stitch holds the walker's place against the range's end)
-                T.waiting = true;
-                break;
-            }
-            SLIMM_TRY(wait_or("block header at byte " + at(pos)));
-            break;
-        }
+    for (;;) {
+        const Walk::Item it = K.peek(cur.p(), cur.avail(), cur.at());
         // (the first thing of a range that starts among a stream's blocks is a block)
-        const bool at_start = Z.from_left && T.base + pos == A.range_begin;
-        if (p[pos] == 0 && at_start) XZ_FAIL(no_start(pos, "block"));
-        if (p[pos] == 0) {   // the index, and the footer behind it
-            uint64_t count = 0, first = 0, bytes = 0;
-            const std::string where = "index at byte " + at(pos);
-            const uint32_t is = xz::index_extent(p + pos, avail, &count, &first, &bytes);
-            if (is == xz::kRanOut) {
-                SLIMM_TRY(wait_or(where));
-                break;
-            }
-            if (is != xz::kOk) XZ_FAIL(xz_fail(c, where, is));
-            if (avail < bytes + xz::kHeaderBytes) {
-                SLIMM_TRY(wait_or("stream footer at byte " + at(pos + bytes)));
-                break;
-            }
-            // (of a stream whose header lies on the left the index's last records are this range's blocks; the records in
-            // front of them are kept for the stitch, which holds them against the blocks of the ranges on the left)
-            const bool open_left = Z.from_left && !Z.left_closed;
-            bool same = open_left ? count >= Z.records.size() : count == Z.records.size();
-            std::vector<std::pair<uint64_t, uint64_t>> kept;
-            for (uint64_t r = 0; same && open_left && r < count - Z.records.size(); ++r) {
-                uint64_t unpadded = 0, uncompressed = 0;
-                xz::index_record(p + pos, bytes, &first, &unpadded, &uncompressed);
-                kept.emplace_back(unpadded, uncompressed);
-            }
-            for (size_t r = 0; same && r < Z.records.size(); ++r) {
-                uint64_t unpadded = 0, uncompressed = 0;
-                xz::index_record(p + pos, bytes, &first, &unpadded, &uncompressed);
-                same = unpadded == Z.records[r].first && uncompressed == Z.records[r].second;
-            }
-            if (!same) XZ_FAIL(xz_fail(c, where, xz::kIndexMismatch));
-            const uint8_t* foot = p + pos + bytes;
+        const bool at_start = Z.from_left && cur.at() == A.range_begin;
+        // (a range may end at a block's first byte: the stitch holds the walker's place against the range's end)
+        if (K.stage == Walk::Blocks && cur.avail() == 0 && cur.ends_mid && cur.wait() == SLIMM_OK) break;
+        if (at_start && cur.avail() > 0 && (it.place >= xz::Place::Index || (it.kind == Walk::Error && it.status != xz::kBadFilter) || (it.kind == Walk::More && last))) {
+            SLIMM_TRY(cur.no_start("block"));
+            break;
+        }
+        if (it.kind == Walk::Error && it.place == xz::Place::Footer && K.open_left) {   // (the walker held the footer against the kind that was told)
+            const uint8_t* foot = cur.p() + (it.at - cur.at());
             uint64_t stated = 0;
-            if (open_left && foot[9] != Z.check && xz::stream_footer(foot, foot[9], &stated) == xz::kOk)
-                XZ_FAIL(fail(c, SLIMM_E_SPLIT, "xz: the stream footer at byte %s states check kind %u, the range was told %u", at(pos + bytes).c_str(),
-                             static_cast<unsigned>(foot[9]), static_cast<unsigned>(Z.check)));
-            uint32_t fs = xz::stream_footer(foot, Z.check, &stated);
-            if (fs == xz::kOk && stated != bytes) fs = xz::kBadFooter;
-            if (fs != xz::kOk) XZ_FAIL(xz_fail(c, "stream footer at byte " + at(pos + bytes), fs));
-            stats[WindowPipeline::kXzIndexRecords] += count;
-            if (open_left) {
-                Z.left_kept = std::move(kept);
-                Z.left_closed = true;
-                Z.left_index_at = T.base + pos;
+            if (foot[9] != K.check && xz::stream_footer(foot, foot[9], &stated) == xz::kOk) {
+                if (!cur.hold) return fail(c, SLIMM_E_SPLIT, "xz: the stream footer at byte %llu states check kind %u, the range was told %u",
+                                           static_cast<unsigned long long>(it.at), static_cast<unsigned>(foot[9]), static_cast<unsigned>(K.check));
+                break;
             }
-            Z.records.clear();
-            pos += bytes + xz::kHeaderBytes;
-            Z.stage = Stage::Between;
+        }
+        if (it.kind <= Walk::MayEnd) {   // (no item: an error, or what stands here needs more bytes -- RoundCursor)
+            SLIMM_TRY(cur.settle(it.kind == Walk::Error, K.stage == Walk::Between, K.streams > 0, it.where(), it.words()));
+            break;
+        }
+        if (it.kind == Walk::BlockStart) {   // a block: its header, its chunk chain, its padding and check
+            const Walk::InBlock before = K.block;
+            K.take(it);
+            uint64_t q = cur.pos + it.bytes;
+            Walk::Item in = K.peek(p + q, n_bytes - q, T.base + q);
+            for (; in.kind == Walk::ChunkItem && K.block.text <= kXzBlockTextMax; in = K.peek(p + q, n_bytes - q, T.base + q)) K.take(in), q += in.bytes;
+            const uint64_t btext = K.block.text;
+            const bool fits = Z.ready.empty() || text + btext <= static_cast<uint64_t>(cap_text);
+            if (in.kind != Walk::BlockEnd || btext > kXzBlockTextMax || !fits) {   // (it is left at its header)
+                K.leave_block(before);
+                if (btext > kXzBlockTextMax) {
+                    if (!cur.hold) return fail(c, SLIMM_E_INVALID, "an xz block of more than 1 GiB of text: decode this file on the host");
+                } else if (in.kind == Walk::Error) {
+                    SLIMM_TRY(cur.fail_words(in.words()));
+                } else if (in.kind == Walk::More) {   // (a block whose bytes are not all at hand waits for the next push)
+                    const std::string where = xz::place_text(xz::Place::Block, it.at);
+                    SLIMM_TRY(cur.wait_or(where, where + ": " + xz::status_text(xz::kRanOut)));
+                }
+                break;   // (or the round is full: this block starts the next one)
+            }
+            K.take(in);
+            xz::Block b{};
+            b.at = cur.pos + it.bytes, b.end = q + 1u, b.text_at = text, b.text_len = btext, b.check_at = q + 1u + in.pad;
+            b.dict_size = it.bh.dict_size, b.check = K.check, b.piece0 = pieces, b.status = xz::kOk;
+            const uint64_t tail = btext % gz::kPiece ? btext % gz::kPiece : (btext ? gz::kPiece : 0u);
+            b.last_mul = K.check == xz::kCheckCrc32 ? gz::crc_x_pow8(tail) : K.check == xz::kCheckCrc64 ? xz::crc64_x_pow8(tail) : 0u;
+            pieces += static_cast<uint32_t>((btext + gz::kPiece - 1u) / gz::kPiece);
+            Z.ready.push_back(b);
+            Z.ready_at.push_back(it.at);
+            cur.hold = true;
+            ++stats[WindowPipeline::kXzBlocks];
+            text += btext;
+            cur.pos = q + in.bytes;
             continue;
         }
-        // a block: its header, its chunk chain, its padding and check
-        const std::string where = "block at byte " + at(pos);
-        xz::BlockHeader bh{};
-        const uint32_t hs = xz::block_header(p + pos, avail, bh);
-        if (hs == xz::kRanOut && !(last && at_start)) {
-            SLIMM_TRY(wait_or("block header at byte " + at(pos)));
-            break;
+        if (it.kind == Walk::StreamStart) ++stats[WindowPipeline::kXzStreams];
+        if (it.kind == Walk::Index) {
+            stats[WindowPipeline::kXzIndexRecords] += it.count;
+            if (K.open_left) Z.left_kept = it.kept, Z.left_index_at = cur.at();
         }
-        if (hs != xz::kOk && hs != xz::kBadFilter && at_start) XZ_FAIL(no_start(pos, "block"));
-        if (hs == xz::kBadFilter) XZ_FAIL(xz_fail(c, "block header at byte " + at(pos), hs, " (filter id " + std::to_string(bh.filter_id) + ")"));
-        if (hs != xz::kOk) XZ_FAIL(xz_fail(c, "block header at byte " + at(pos), hs));
-        uint64_t q = pos + bh.bytes, btext = 0;
-        xz::Rules rules;
-        bool whole = false;
-        uint32_t bad = xz::kOk;
-        for (;;) {
-            xz::Chunk ch;
-            const uint32_t cs = xz::chunk_header(p + q, n_bytes - q, rules, ch);
-            if (cs == xz::kRanOut) break;
-            if (cs != xz::kOk) {
-                bad = cs;
-                break;
-            }
-            if (ch.control == 0) {
-                ++q;
-                whole = true;
-                break;
-            }
-            if (n_bytes - q < static_cast<uint64_t>(ch.header) + ch.csize) break;
-            btext += ch.usize;
-            q += static_cast<uint64_t>(ch.header) + ch.csize;
-            if (btext > kXzBlockTextMax) break;
-        }
-        if (bad != xz::kOk) XZ_FAIL(xz_fail(c, "chunk at byte " + at(q), bad));
-        if (btext > kXzBlockTextMax) XZ_FAIL(fail(c, SLIMM_E_INVALID, "an xz block of more than 1 GiB of text: decode this file on the host"));
-        const uint64_t comp = q - (pos + bh.bytes), pad = (4u - ((bh.bytes + comp) & 3u)) & 3u, cb = xz::check_bytes(Z.check);
-        if (!whole || n_bytes - q < pad + cb) {   // (a block whose bytes are not all at hand waits for the next push)
-            SLIMM_TRY(wait_or(where));
-            break;
-        }
-        if (!all_zero(p + q, pad)) XZ_FAIL(xz_fail(c, where, xz::kBadBlockPadding));
-        if ((bh.has_compressed && bh.compressed != comp) || (bh.has_uncompressed && bh.uncompressed != btext)) XZ_FAIL(xz_fail(c, where, xz::kBadBlockSizes));
-        if (!Z.ready.empty() && text + btext > static_cast<uint64_t>(cap_text)) break;   // (the round is full: this block starts the next one)
-        xz::Block b{};
-        b.at = pos + bh.bytes, b.end = q, b.text_at = text, b.text_len = btext, b.check_at = q + pad;
-        b.dict_size = bh.dict_size, b.check = Z.check, b.piece0 = pieces, b.status = xz::kOk;
-        const uint64_t tail = btext % gz::kPiece ? btext % gz::kPiece : (btext ? gz::kPiece : 0u);
-        b.last_mul = Z.check == xz::kCheckCrc32 ? gz::crc_x_pow8(tail) : Z.check == xz::kCheckCrc64 ? xz::crc64_x_pow8(tail) : 0u;
-        pieces += static_cast<uint32_t>((btext + gz::kPiece - 1u) / gz::kPiece);
-        Z.ready.push_back(b);
-        Z.ready_at.push_back(T.base + pos);
-        Z.records.emplace_back(bh.bytes + comp + cb, btext);
-        ++stats[WindowPipeline::kXzBlocks];
-        text += btext;
-        pos = q + pad + cb;
+        K.take(it);
+        cur.pos += it.bytes;
     }
     Z.text = text;
     return SLIMM_OK;

@@ -26,7 +26,6 @@ namespace {
 
 constexpr uint64_t kZsRoundText = 512ull << 20;   // a round's text at most, by the blocks' bounds (SLIMM_FORCE zstd_round_text=N)
 using ZF = WindowPipeline::File::Zstd;
-using Stage = ZF::Stage;
 
 __global__ __launch_bounds__(64) void k_zs_entropy(const uint8_t* __restrict__ base, zs::Block* __restrict__ blocks, uint32_t n, uint8_t* __restrict__ lit,
                                                     zs::Seq* __restrict__ seq) {
@@ -200,153 +199,76 @@ int zs_round(slimm_ctx* c, bool last) {
     Z.text = 0;
     if (T.waiting && !last) return SLIMM_OK;
     T.waiting = false;   // (at the file's end what waited for bytes is looked at again: it ends the frames, or is truncated)
-    // (what the rounds so far have read is gone: a round copies to the device only what is still to decode.  zstd reads at
-    // bytes: `pos` is the stream's bit, put back however the round ends)
-    uint64_t pos = T.bit >> 3;
-    struct PutBack {
-        uint64_t &bit, &pos;
-        ~PutBack() { bit = pos * 8u; }
-    } put_back{T.bit, pos};
+    // (what the rounds so far have read is gone: a round copies to the device only what is still to decode)
+    RoundCursor cur(c, W, last, "zstd", "frame", "frame");
     long cap_text = 0;
     if (!forced("zstd_round_text", &cap_text) || cap_text <= 0) cap_text = static_cast<long>(kZsRoundText);
-    auto at = [&](uint64_t byte) { return std::to_string(T.base + byte); };
-    // a byte range of a split file (check_push: its range is announced).  It starts at a frame and ends between frames, or
-    // the cut is refused -- SLIMM_E_SPLIT, no verdict on the file: the caller reads it through one context
-    const WindowPipeline::Announced& A = W.announced;
-    const bool starts_mid = A.has_range && A.starts_mid, ends_mid = A.has_range && A.ends_mid;
-    auto no_start = [&](uint64_t byte) {
-        return fail(c, SLIMM_E_SPLIT, "zstd: the range starts at byte %s, where no frame starts", at(byte).c_str());
-    };
-    auto no_end = [&](const std::string& where) {
-        return fail(c, SLIMM_E_SPLIT, "zstd: %s runs past byte %llu: the range does not end at a frame boundary", where.c_str(),
-                    static_cast<unsigned long long>(A.range_end));
-    };
-    // what a stage lacks: more bytes may come, or the file ends inside it
-    auto wait_or = [&](const std::string& where) {
-        if (last && ends_mid) return no_end(where);
-        if (last) return zs_fail(c, where, zs::kRanOut);
-        T.waiting = true;
-        return static_cast<int>(SLIMM_OK);
-    };
-    // ---- the plan
-    const uint64_t n_bytes = T.pend.size(), aux_base = n_bytes + zs::kPad;
+    // ---- the plan: the container's items (zstd_walk.h), whole blocks only
+    using Walk = zs::Walker;
+    Walk& K = Z.walk;
+    const uint64_t aux_base = T.pend.size() + zs::kPad;
     const uint8_t* p = T.pend.data();
     uint64_t bound = 0, lit_bytes = 0, n_seq_slots = 0;
-    bool full = false;
-    while (!full && !T.waiting) {
-        const uint64_t avail = n_bytes - pos;
-        if (Z.stage == Stage::Between) {
-            if (avail == 0 && (Z.any_frames > 0 || !last || starts_mid || ends_mid)) {
-                T.waiting = true;   // (the file may end here; a range may be empty)
-                break;
-            }
-            if (avail < 4u) {
-                if (last && ends_mid) return no_end("what starts at byte " + at(pos));
-                if (last && starts_mid && Z.any_frames == 0) return no_start(pos);
-                if (last) return zs_fail(c, "at byte " + at(pos), Z.any_frames == 0 || zs::magic_prefix(p + pos, avail) ? zs::kRanOut : zs::kNoFrame);
-                T.waiting = true;
-                break;
-            }
-            const uint32_t magic = zs::le32(p + pos);
-            if ((magic & 0xfffffff0u) == zs::kSkippable) {
-                if (avail < 8u || avail < 8ull + zs::le32(p + pos + 4)) {
-                    SLIMM_TRY(wait_or("skippable frame at byte " + at(pos)));
-                    break;
-                }
-                pos += 8ull + zs::le32(p + pos + 4);
-                ++Z.any_frames;
-                ++stats[WindowPipeline::kZsSkippable];
-                continue;
-            }
-            if (magic != zs::kMagic && starts_mid && Z.any_frames == 0) return no_start(pos);
-            if (magic != zs::kMagic) return zs_fail(c, "at byte " + at(pos), Z.any_frames ? zs::kNoFrame : zs::kRanOut);
-            const uint32_t hs = zs::frame_header(p + pos, avail, Z.fh);
-            if (hs == zs::kRanOut) {
-                SLIMM_TRY(wait_or("frame header at byte " + at(pos)));
-                break;
-            }
-            if (hs != zs::kOk && starts_mid && Z.any_frames == 0) return no_start(pos);   // (the magic's bytes, inside some frame)
-            if (hs != zs::kOk) return zs_fail(c, "frame header at byte " + at(pos), hs);
-            Z.frame_at = T.base + pos;
-            pos += Z.fh.bytes;
-            Z.stage = Stage::Blocks;
+    for (;;) {
+        const Walk::Item it = K.peek(cur.p(), cur.avail(), cur.at());
+        if (it.kind <= Walk::MayEnd) {   // (no item: an error, or what stands here needs more bytes -- RoundCursor)
+            // (a magic that is cut short is "what starts here"; a skippable frame or a frame header cut short is itself)
+            const bool between = K.stage == Walk::Between && (it.kind != Walk::More || it.place == zs::Place::At);
+            SLIMM_TRY(cur.settle(it.kind == Walk::Error, between, K.frames > 0, it.where(), it.words()));
+            break;
+        }
+        if (it.kind == Walk::SkippableFrame) ++stats[WindowPipeline::kZsSkippable];
+        if (it.kind == Walk::Header) {
             Z.frame_len = 0;
             Z.entropy.reset();
             Z.rep[0] = 1, Z.rep[1] = 4, Z.rep[2] = 8;
             Z.xxh.reset();
             if (Z.ready.empty()) Z.hist_len = 0;
-            ++Z.any_frames;
             ++stats[WindowPipeline::kZsFrames];
-            continue;
         }
-        if (Z.stage == Stage::Checksum) {
-            if (avail < 4u) {
-                SLIMM_TRY(wait_or("checksum at byte " + at(pos)));
-                break;
-            }
-            const uint32_t sum = zs::le32(p + pos);
+        if (it.kind == Walk::Sum) {
             if (!Z.frames.empty() && Z.frames.back().ends) {   // (its last blocks are of this round: zs_check compares)
                 Z.frames.back().has_sum = true;
-                Z.frames.back().sum = sum;
+                Z.frames.back().sum = it.sum;
             } else {
-                if (sum != static_cast<uint32_t>(Z.xxh.digest())) return zs_fail(c, "frame at byte " + std::to_string(Z.frame_at), zs::kBadChecksum);
+                if (it.sum != static_cast<uint32_t>(Z.xxh.digest())) return zs_fail(c, zs::place_text(zs::Place::Frame, K.frame_at), zs::kBadChecksum);
                 ++stats[WindowPipeline::kZsChecksums];
             }
-            pos += 4u;
-            Z.stage = Stage::Between;
-            continue;
         }
-        // a block
-        if (avail < 3u) {
-            SLIMM_TRY(wait_or("block header at byte " + at(pos)));
-            break;
+        if (it.kind == Walk::Block) {
+            const uint64_t most = it.type == zs::kCompressed ? K.fh.block_max : it.size;
+            if (!Z.ready.empty() && bound + most > static_cast<uint64_t>(cap_text)) break;   // (the round is full: this block starts the next one)
+            zs::Block b{};
+            b.at = cur.pos + 3u, b.size = static_cast<uint32_t>(it.bytes - 3u), b.type = it.type, b.max = K.fh.block_max, b.regen = it.size;
+            b.window = static_cast<uint32_t>(K.fh.window);
+            b.status = zs::kOk;
+            b.rep[0] = zs::sym(0), b.rep[1] = zs::sym(1), b.rep[2] = zs::sym(2);
+            if (it.type == zs::kCompressed) {
+                const uint32_t ps = zs::plan_compressed(p, b.at, it.size, Z.entropy, Z.aux, aux_base, b, &stats[WindowPipeline::kZsHufTree]);
+                if (ps != zs::kOk) return zs_fail(c, it.where(), ps);
+                b.lit_out = lit_bytes, b.seq_out = n_seq_slots;
+                if (b.lit_type >= 2u) lit_bytes += b.lit_regen;
+                n_seq_slots += b.n_seq + 1ull;
+                stats[WindowPipeline::kZsSequences] += b.n_seq;
+            }
+            ++stats[it.type == zs::kRaw ? WindowPipeline::kZsRaw : it.type == zs::kRleBlock ? WindowPipeline::kZsRle : WindowPipeline::kZsCompressed];
+            if (Z.frames.empty() || Z.frames.back().ends) {
+                ZF::Frame f;
+                f.first = static_cast<uint32_t>(Z.ready.size());
+                f.fh = K.fh, f.at = K.frame_at, f.len_before = Z.frame_len;
+                f.xxh = Z.xxh;   // (what the frame's header set, or what the rounds so far have left)
+                for (uint32_t r = 0; r < 3u; ++r) f.rep[r] = Z.rep[r];
+                Z.frames.push_back(f);
+            }
+            b.frame = static_cast<uint32_t>(Z.frames.size() - 1u);
+            ++Z.frames.back().n;
+            Z.frames.back().ends = it.last;
+            Z.ready.push_back(b);
+            Z.ready_at.push_back(it.at);
+            bound += most;
         }
-        const uint32_t h = zs::le24(p + pos), type = (h >> 1) & 3u, size = h >> 3;
-        const std::string where = "block at byte " + at(pos);
-        if (type == 3u) return zs_fail(c, where, zs::kReservedBlock);
-        if (size > Z.fh.block_max) return zs_fail(c, where, zs::kBlockTooLarge);
-        const uint64_t content = type == zs::kRleBlock ? 1u : size;
-        if (avail < 3u + content) {
-            SLIMM_TRY(wait_or(where));
-            break;
-        }
-        const uint64_t most = type == zs::kCompressed ? Z.fh.block_max : size;
-        if (!Z.ready.empty() && bound + most > static_cast<uint64_t>(cap_text)) {
-            full = true;   // (this block starts the next round)
-            break;
-        }
-        zs::Block b{};
-        b.at = pos + 3u, b.size = static_cast<uint32_t>(content), b.type = type, b.max = Z.fh.block_max, b.regen = size;
-        b.window = static_cast<uint32_t>(Z.fh.window);
-        b.status = zs::kOk;
-        b.rep[0] = zs::sym(0), b.rep[1] = zs::sym(1), b.rep[2] = zs::sym(2);
-        if (type == zs::kCompressed) {
-            const uint32_t ps = zs::plan_compressed(p, b.at, size, Z.entropy, Z.aux, aux_base, b, &stats[WindowPipeline::kZsHufTree]);
-            if (ps != zs::kOk) return zs_fail(c, where, ps);
-            b.lit_out = lit_bytes, b.seq_out = n_seq_slots;
-            if (b.lit_type >= 2u) lit_bytes += b.lit_regen;
-            n_seq_slots += b.n_seq + 1ull;
-            stats[WindowPipeline::kZsSequences] += b.n_seq;
-        }
-        ++stats[type == zs::kRaw ? WindowPipeline::kZsRaw : type == zs::kRleBlock ? WindowPipeline::kZsRle : WindowPipeline::kZsCompressed];
-        if (Z.frames.empty() || Z.frames.back().ends) {
-            ZF::Frame f;
-            f.first = static_cast<uint32_t>(Z.ready.size());
-            f.fh = Z.fh, f.at = Z.frame_at, f.len_before = Z.frame_len;
-            f.xxh = Z.xxh;   // (what the frame's header set, or what the rounds so far have left)
-            for (uint32_t r = 0; r < 3u; ++r) f.rep[r] = Z.rep[r];
-            Z.frames.push_back(f);
-        }
-        b.frame = static_cast<uint32_t>(Z.frames.size() - 1u);
-        ++Z.frames.back().n;
-        Z.ready.push_back(b);
-        Z.ready_at.push_back(T.base + pos);
-        bound += most;
-        pos += 3u + content;
-        if (h & 1u) {
-            Z.frames.back().ends = true;
-            Z.stage = Z.fh.has_checksum ? Stage::Checksum : Stage::Between;
-        }
+        K.take(it);
+        cur.pos += it.bytes;
     }
     const uint32_t nb = static_cast<uint32_t>(Z.ready.size());
     if (!nb) return SLIMM_OK;

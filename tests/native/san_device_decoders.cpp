@@ -18,25 +18,11 @@
 #include <string>
 #include <vector>
 
+#include "damaged_copies.h"
 #include "slimm_hip.h"
 
-using Bytes = std::vector<uint8_t>;
-
-static uint64_t rng_state;
-static uint64_t rng() {   // (xorshift64*)
-    rng_state ^= rng_state >> 12, rng_state ^= rng_state << 25, rng_state ^= rng_state >> 27;
-    return rng_state * 0x2545F4914F6CDD1Dull;
-}
-
-static bool slurp(const char* path, Bytes& out) {
-    FILE* f = fopen(path, "rb");
-    if (!f) return false;
-    uint8_t buf[65536];
-    size_t got;
-    while ((got = fread(buf, 1, sizeof buf, f)) > 0) out.insert(out.end(), buf, buf + got);
-    fclose(f);
-    return true;
-}
+using damage::Bytes;
+using damage::slurp;
 
 enum Codec { XZ, ZSTD, GZIP, BZIP2, BGZF_SAM, BGZF_BAM, SAM, N_CODECS };
 static const char* const kCodecNames[N_CODECS] = {"xz", "zstd", "gzip", "bzip2", "bgzf_sam", "bgzf_bam", "sam"};
@@ -89,53 +75,10 @@ struct Pusher {
     }
 };
 
-// Offsets 1 .. 5 000 bytes apart; BGZF: each moved up to the next block boundary of the (good) file.
 static std::vector<size_t> random_cuts(const Bytes& blob, Codec codec, size_t from) {
-    std::vector<size_t> ends;
-    if (codec == BGZF_SAM || codec == BGZF_BAM)
-        for (size_t p = 0; p + 18u <= blob.size();) {
-            p += (blob[p + 16] | (static_cast<size_t>(blob[p + 17]) << 8)) + 1u;
-            ends.push_back(p);
-        }
-    std::vector<size_t> cuts;
-    size_t at = from, e = 0;
-    while (true) {
-        at += 1u + rng() % 5000u;
-        if (!ends.empty()) {
-            while (e < ends.size() && ends[e] < at) ++e;
-            if (e == ends.size()) break;
-            at = ends[e];
-        }
-        if (at >= blob.size()) break;
-        cuts.push_back(at);
-    }
-    return cuts;
+    return damage::random_cuts(blob, codec == BGZF_SAM || codec == BGZF_BAM, from);
 }
-
-static Bytes damaged(const Bytes& blob, Codec codec, size_t skip) {
-    Bytes b = blob;
-    const uint32_t kind = static_cast<uint32_t>(rng() % (codec == SAM ? 7u : 4u));
-    if (kind < 2u) {
-        b[rng() % b.size()] ^= static_cast<uint8_t>(1u << (rng() % 8u));
-    } else if (kind == 2u) {
-        b.resize(rng() % b.size());
-    } else if (kind == 3u) {
-        const size_t len = 1u + rng() % std::min<size_t>(b.size(), 4096u), from = rng() % (b.size() - len + 1u), to = rng() % (b.size() - len + 1u);
-        memmove(b.data() + to, b.data() + from, len);
-    } else {   // (text only) somewhere behind the header: a line cut, the next tab removed, '@' at the next line's start
-        size_t at = skip + rng() % (b.size() - skip);
-        const uint8_t want = kind == 5u ? '\t' : '\n';
-        while (at < b.size() && b[at] != want) ++at;
-        if (at + 1u >= b.size()) return b;
-        if (kind == 4u) {
-            const size_t k = std::min<size_t>(at - skip, 1u + rng() % 40u);
-            b.erase(b.begin() + (at - k), b.begin() + at);
-        }
-        else if (kind == 5u) b.erase(b.begin() + static_cast<long>(at));
-        else b[at + 1u] = '@';
-    }
-    return b;
-}
+static Bytes damaged(const Bytes& blob, Codec codec, size_t skip) { return damage::damaged(blob, codec == SAM, skip); }
 
 int main(int argc, char** argv) {
     if (argc != 7) {
@@ -152,7 +95,7 @@ int main(int argc, char** argv) {
     const uint32_t skip = static_cast<uint32_t>(strtoul(argv[3], nullptr, 10));
     const uint64_t records = strtoull(argv[4], nullptr, 10);
     const int trials = atoi(argv[5]);
-    rng_state = strtoull(argv[6], nullptr, 10) * 2u + 1u;
+    damage::seed(strtoull(argv[6], nullptr, 10));
 
     // four references of 5 000 bases, each a strain of its own species under shared higher ranks
     const uint32_t ref_len[4] = {5000, 5000, 5000, 5000};

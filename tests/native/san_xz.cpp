@@ -7,6 +7,8 @@
 //   san_xz --crc64 SEED N FILE      FILE's CRC64 from N random cuts, each piece from 0, folded: "ok" or "mismatch" per trial
 //   san_xz --mutate SEED N FILE     N damaged copies of FILE decoded -- a byte flipped, the file cut short, a stretch of it
 //                                   copied elsewhere --: "flips_same=a flips_differ=b others_ok=c errors=d"
+//   san_xz --words SEED N FILE      the N damaged copies that `san_device_decoders xz FILE .. N SEED` makes (damaged_copies.h),
+//                                   decoded: "trial T: ok" or "trial T: message" (tests/golden/codec_words)
 // Damaged input must end in an error message, never in a sanitizer report.
 #include <cstdio>
 #include <cstdlib>
@@ -15,6 +17,7 @@
 #include <vector>
 
 #include "../../slimm_amd/csrc/host/xz.hpp"
+#include "damaged_copies.h"
 
 using slimm::XzReader;
 namespace xz = slimm::xz;
@@ -30,15 +33,8 @@ static uint64_t crc64_step(uint64_t reg, const uint8_t* p, size_t n) {
     return reg;
 }
 
-static bool slurp(const char* path, std::vector<uint8_t>& out) {
-    FILE* f = fopen(path, "rb");
-    if (!f) return false;
-    uint8_t buf[65536];
-    size_t got;
-    while ((got = fread(buf, 1, sizeof buf, f)) > 0) out.insert(out.end(), buf, buf + got);
-    fclose(f);
-    return true;
-}
+using damage::rng;
+using damage::slurp;
 
 static bool decode(const std::vector<uint8_t>& blob, std::vector<uint8_t>* keep, uint64_t& n, uint64_t& crc, std::string& err, XzReader::Counts* counts) {
     size_t fed = 0;
@@ -61,12 +57,6 @@ static bool decode(const std::vector<uint8_t>& blob, std::vector<uint8_t>* keep,
     if (got < 0) err = r.error();
     if (counts) *counts = r.counts();
     return got == 0;
-}
-
-static uint64_t rng_state;
-static uint64_t rng() {   // (xorshift64*)
-    rng_state ^= rng_state >> 12, rng_state ^= rng_state << 25, rng_state ^= rng_state >> 27;
-    return rng_state * 0x2545F4914F6CDD1Dull;
 }
 
 int main(int argc, char** argv) {
@@ -106,7 +96,7 @@ int main(int argc, char** argv) {
         return 0;
     }
     if (argc >= 5 && strcmp(argv[1], "--crc64") == 0) {
-        rng_state = strtoull(argv[2], nullptr, 10) * 2u + 1u;
+        damage::seed(strtoull(argv[2], nullptr, 10));
         const int trials = atoi(argv[3]);
         if (!slurp(argv[4], blob)) return 2;
         const uint64_t serial = crc64_step(~0ull, blob.data(), blob.size());
@@ -123,7 +113,7 @@ int main(int argc, char** argv) {
         return 0;
     }
     if (argc >= 5 && strcmp(argv[1], "--mutate") == 0) {
-        rng_state = strtoull(argv[2], nullptr, 10) * 2u + 1u;
+        damage::seed(strtoull(argv[2], nullptr, 10));
         const int trials = atoi(argv[3]);
         if (!slurp(argv[4], blob) || blob.empty()) return 2;
         std::vector<uint8_t> good;
@@ -135,16 +125,8 @@ int main(int argc, char** argv) {
         }
         unsigned long long same = 0, differ = 0, others = 0, errors = 0;
         for (int t = 0; t < trials; ++t) {
-            std::vector<uint8_t> b = blob;
-            const uint32_t kind = static_cast<uint32_t>(rng() % 4u);
-            if (kind < 2u) {
-                b[rng() % b.size()] ^= static_cast<uint8_t>(1u << (rng() % 8u));
-            } else if (kind == 2u) {
-                b.resize(rng() % b.size());
-            } else {
-                const size_t len = 1u + rng() % std::min<size_t>(b.size(), 4096u), from = rng() % (b.size() - len + 1u), to = rng() % (b.size() - len + 1u);
-                memmove(b.data() + to, b.data() + from, len);
-            }
+            uint32_t kind = 0;
+            const std::vector<uint8_t> b = damage::damaged(blob, false, 0, &kind);
             err.clear();
             const bool ok = decode(b, nullptr, n, h, err, nullptr);
             if (!ok && err.empty()) return 3;   // (an error without words)
@@ -155,6 +137,15 @@ int main(int argc, char** argv) {
                 ++differ;
         }
         printf("flips_same=%llu flips_differ=%llu others_ok=%llu errors=%llu\n", same, differ, others, errors);
+        return 0;
+    }
+    if (argc >= 5 && strcmp(argv[1], "--words") == 0) {
+        if (!slurp(argv[4], blob) || blob.empty()) return 2;
+        damage::device_trials(blob, strtoull(argv[2], nullptr, 10), atoi(argv[3]), [](int t, const std::vector<uint8_t>& b) {
+            uint64_t n = 0, h = 0;
+            std::string err;
+            printf("trial %d: %s\n", t, decode(b, nullptr, n, h, err, nullptr) ? "ok" : err.c_str());
+        });
         return 0;
     }
     if (argc >= 4 && strcmp(argv[1], "--out") == 0) {

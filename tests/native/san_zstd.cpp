@@ -3,6 +3,8 @@
 //   san_zstd FILE...              every file decoded: "FILE<tab>ok<tab>bytes<tab>xxh64" or "FILE<tab>error<tab>message"
 //   san_zstd --out OUT FILE       the decoded bytes of FILE into OUT (exit 1 + the message on an error)
 //   san_zstd --xxh64 PIECE FILE   XXH64 of FILE's bytes, taken PIECE bytes at a time
+//   san_zstd --words SEED N FILE  the N damaged copies that `san_device_decoders zstd FILE .. N SEED` makes (damaged_copies.h),
+//                                 decoded: "trial T: ok" or "trial T: message" (tests/golden/codec_words)
 // Damaged input must end in an error message, never in a sanitizer report.
 #include <cstdio>
 #include <cstdlib>
@@ -11,6 +13,7 @@
 #include <vector>
 
 #include "../../slimm_amd/csrc/host/zstd.hpp"
+#include "damaged_copies.h"
 
 static bool decode(const char* path, std::vector<uint8_t>* keep, uint64_t& n, uint64_t& hash, std::string& err) {
     FILE* f = fopen(path, "rb");
@@ -36,6 +39,25 @@ static bool decode(const char* path, std::vector<uint8_t>* keep, uint64_t& n, ui
 }
 
 int main(int argc, char** argv) {
+    if (argc >= 5 && strcmp(argv[1], "--words") == 0) {
+        std::vector<uint8_t> blob;
+        if (!damage::slurp(argv[4], blob) || blob.empty()) return 2;
+        damage::device_trials(blob, strtoull(argv[2], nullptr, 10), atoi(argv[3]), [](int t, const std::vector<uint8_t>& b) {
+            size_t fed = 0;
+            slimm::ZstdReader r([&](uint8_t* d, size_t cap) {
+                const size_t k = std::min(cap, b.size() - fed);
+                if (k) memcpy(d, b.data() + fed, k);
+                fed += k;
+                return k;
+            });
+            std::vector<uint8_t> buf(777777);
+            long got;
+            while ((got = r.read(buf.data(), buf.size())) > 0) {
+            }
+            printf("trial %d: %s\n", t, got == 0 ? "ok" : r.error().c_str());
+        });
+        return 0;
+    }
     if (argc >= 4 && strcmp(argv[1], "--xxh64") == 0) {
         FILE* f = fopen(argv[3], "rb");
         if (!f) return 2;
