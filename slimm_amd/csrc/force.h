@@ -17,11 +17,13 @@
 //   one, and every N bits)                    tests/test_gpu_gzip_sam.py, tests/test_cli_gzip_sam_device.py
 //   zstd_round=N (zstd SAM decoded every N compressed bytes: frame headers, block headers, blocks and checksums cut across
 //   rounds), zstd_round_text=N (a round's text at most, by the blocks' bounds: copies reach into the history of an earlier
-//   round)                                    tests/test_gpu_zstd_sam.py, tests/test_cli_zstd_sam_device.py
+//   round)                                    tests/test_gpu_zstd_sam.py, tests/test_cli_zstd_sam_device.py,
+//                                             tests/test_gpu_codec_paths.py (the directed inputs of tests/zstd_directed.py)
 //   xz_round=N (xz SAM decoded every N compressed bytes: stream, block and chunk headers, chunks, checks, indexes and
 //   footers cut across rounds), xz_round_text=N (a round's text at most: a round takes one block, the next round the
 //   rest), xz_device_blocks=N (the `slimm` command reads an xz file of fewer than N blocks, by its index, on the host: 16
-//   unless told)                              tests/test_gpu_xz_sam.py, tests/test_cli_xz_sam_device.py
+//   unless told)                              tests/test_gpu_xz_sam.py, tests/test_cli_xz_sam_device.py,
+//                                             tests/test_gpu_codec_paths.py (xz_round, xz_round_text: the directed inputs of tests/lzma_directed.py)
 //   xz_split_blocks=N (the least blocks per member at which the command cuts an xz file for --split-input: 16 unless told;
 //   a key of its own, which does not follow xz_device_blocks)
 //                                             tests/test_split_xz_ranges.py, tests/test_cli_split_input_xz.py

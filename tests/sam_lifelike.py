@@ -5,7 +5,11 @@ almost all long matches for every compressor (SEQ = A..., QUAL = *); this one is
 decoders' literal paths need.  Everything is drawn from random.Random(seed), so that the text is the same on every machine
 (tests/test_lifelike_inputs.py pins one sha256).  Test infrastructure only."""
 import random
+import types
 
+import numpy as np
+
+from slimm_amd.workload import Records
 from tests.bam_io import _bgzf_block, _file_flags, bam_header_bytes, bam_record_bytes, qnames_of, sam_header, write_sam
 
 BASES, BASE_WEIGHTS = "ACGTN", (99, 99, 99, 99, 4)   # (about 1 % N)
@@ -81,6 +85,19 @@ def lifelike_bam(w, seed: int, lo: int = 500, hi: int = 65_000):
         blocks.append(_bgzf_block(data[p:e]))
         p = e
     return b"".join(blocks) + _bgzf_block(b""), len(head), body
+
+
+def small_workload(records: int = 350):
+    """`records` records of 120 reads on the four references the program configures (R0 .. R3, 5 000 bases), grouped by name; a few
+    unmapped."""
+    rng = np.random.default_rng(5)
+    read = np.sort(rng.integers(0, 120, size=records))
+    flag = np.where(rng.random(records) < 0.5, 0x40, 0x80).astype(np.uint16)
+    ref = rng.integers(0, 4, size=records).astype(np.int32)
+    ref[::37] = -1
+    flag[::37] |= 4
+    rec = Records(read.astype(np.uint64), flag, ref, rng.integers(0, 4_700, size=records).astype(np.int32), [f"read/{i}/" for i in read.tolist()])
+    return types.SimpleNamespace(ref_names=["R0", "R1", "R2", "R3"], ref_len=[5_000] * 4, records=rec)
 
 
 # ---- compressed copies, made with the standard library -------------------------------------------------------------------

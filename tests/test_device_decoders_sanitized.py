@@ -18,33 +18,18 @@ a literal's low byte (up to 126 bits: undefined, though the value was never used
 case is test_good_bgzf_files_shift_by_less_than_a_word below."""
 import os
 import subprocess
-import types
 from concurrent.futures import ThreadPoolExecutor
 
-import numpy as np
 import pytest
 
-from slimm_amd.workload import Records
 from tests import sam_lifelike as L
+from tests.sam_lifelike import small_workload
 from tests.sam_gz import bgzf, header_len
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NATIVE = os.path.join(ROOT, "tests", "native")
 TRIALS, RECORDS = 100, 350
 CODECS = ["xz", "zstd", "gzip", "bzip2", "bgzf_sam", "bgzf_bam", "sam"]
-
-
-def small_workload():
-    """350 records of 120 reads on the four references the program configures (R0 .. R3, 5 000 bases), grouped by name; a few
-    unmapped."""
-    rng = np.random.default_rng(5)
-    read = np.sort(rng.integers(0, 120, size=RECORDS))
-    flag = np.where(rng.random(RECORDS) < 0.5, 0x40, 0x80).astype(np.uint16)
-    ref = rng.integers(0, 4, size=RECORDS).astype(np.int32)
-    ref[::37] = -1
-    flag[::37] |= 4
-    rec = Records(read.astype(np.uint64), flag, ref, rng.integers(0, 4_700, size=RECORDS).astype(np.int32), [f"read/{i}/" for i in read.tolist()])
-    return types.SimpleNamespace(ref_names=["R0", "R1", "R2", "R3"], ref_len=[5_000] * 4, records=rec)
 
 
 @pytest.fixture(scope="module")
