@@ -324,10 +324,15 @@ struct Rle1 {
         out = b;
         return 1u;
     }
+    // behind a block's last byte: four equal bytes stand there and their count byte is missing.  bzip2 itself refuses such
+    // a block (its reader runs past the block's end); so does every user of this struct, in the words of kBadRun
+    SLIMM_BZ2_HD bool count_missing() const { return run == 4u; }
 };
+constexpr uint32_t kLenBadLinks = ~0u, kLenBadRun = ~0u - 1u;   // k_bz2_unbwt's text_len of a block it refuses
+constexpr uint64_t kNoTextLength = ~0ull;
 
 // the length of a block's text (RLE1 undone) from its links: the n-step walk without the bytes (the host's planner of
-// slimm_host_bzip2_ranges counts decoded bytes up to the SAM header's end)
+// slimm_host_bzip2_ranges counts decoded bytes up to the SAM header's end); kNoTextLength: the last run's count byte is missing
 inline uint64_t text_length(const uint32_t* link, uint32_t n, uint32_t orig_ptr) {
     Rle1 st;
     uint64_t len = 0;
@@ -337,7 +342,7 @@ inline uint64_t text_length(const uint32_t* link, uint32_t n, uint32_t orig_ptr)
         len += st.step(u >> 24, byte);
         p = u & kLinkMask;
     }
-    return len;
+    return st.count_missing() ? kNoTextLength : len;
 }
 
 SLIMM_BZ2_HD inline void crc_table(uint32_t* tab) {

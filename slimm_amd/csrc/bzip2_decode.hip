@@ -70,8 +70,8 @@ __global__ __launch_bounds__(64) void k_bz2_decode(const uint8_t* __restrict__ b
     info[s] = r;
 }
 
-// text_len[k] = the RLE1 text's bytes of the block in slot slots[k]; ~0u: its links are no permutation (never for links
-// made by link_block: a guard against an out-of-range walk)
+// text_len[k] = the RLE1 text's bytes of the block in slot slots[k]; kLenBadLinks: its links are no permutation (never for
+// links made by link_block: a guard against an out-of-range walk); kLenBadRun: it ends in four equal bytes without a count byte
 __global__ __launch_bounds__(256) void k_bz2_unbwt(const uint32_t* __restrict__ slots, const bz2::BlockInfo* __restrict__ info,
                                                     uint8_t* __restrict__ ll_all, uint32_t* __restrict__ link_all, const uint32_t* __restrict__ hist,
                                                     uint32_t* __restrict__ text_len) {
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(256) void k_bz2_unbwt(const uint32_t* __restrict__ 
     }
     __syncthreads();
     if (bad) {
-        if (threadIdx.x == 0) text_len[blockIdx.x] = ~0u;
+        if (threadIdx.x == 0) text_len[blockIdx.x] = bz2::kLenBadLinks;
         return;
     }
     for (uint32_t r = threadIdx.x; r < total; r += blockDim.x) {
@@ -143,7 +143,7 @@ __global__ __launch_bounds__(256) void k_bz2_unbwt(const uint32_t* __restrict__ 
         bz2::Rle1 st;
         uint32_t len = 0, byte;
         for (uint32_t k = 0; k < n; ++k) len += st.step(ll[k], byte);
-        text_len[blockIdx.x] = len;
+        text_len[blockIdx.x] = st.count_missing() ? bz2::kLenBadRun : len;
     }
 }
 
@@ -173,7 +173,7 @@ __global__ __launch_bounds__(64) void k_bz2_emit(const uint32_t* __restrict__ sl
             if (j >= drop) dst[base + j] = static_cast<uint8_t>(byte);
         }
     }
-    crc_ok[blockIdx.x] = ~crc == info[s].crc ? 1u : 0u;
+    crc_ok[blockIdx.x] = ~crc == info[s].crc && !st.count_missing() ? 1u : 0u;   // (k_bz2_unbwt refused a missing count byte)
 }
 
 void push_trace_bz2(const char* fmt, ...) {   // "[push bzip2] ..."
@@ -475,7 +475,9 @@ int bz2_decode_batch(slimm_ctx* c, bool last) {
     HIP_TRY(c, hipStreamSynchronize(st));
     Z.ms_bwt += ms_since(t0);
     for (uint32_t i = 0; i < k; ++i) {
-        if (len[i] == ~0u) return BZ2_FAIL("block at byte %llu: %s", static_cast<unsigned long long>(ats[i]), bz2::status_text(bz2::kBadLinks));
+        if (len[i] == bz2::kLenBadLinks || len[i] == bz2::kLenBadRun)
+            return BZ2_FAIL("block at byte %llu: %s", static_cast<unsigned long long>(ats[i]),
+                            bz2::status_text(len[i] == bz2::kLenBadRun ? bz2::kBadRun : bz2::kBadLinks));
         WindowPipeline::File::Bzip2::Ready b;
         b.slot = slots[i];
         b.crc = crcs[i];

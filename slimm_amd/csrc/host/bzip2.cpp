@@ -106,6 +106,10 @@ bool Bzip2Reader::next_text() {
                 crc = bz2::crc_byte(crc_tab_, crc, byte);
             }
         }
+        if (r.count_missing()) {   // (four equal bytes end the block and no count byte follows: bzip2 refuses it too)
+            fail("block at byte " + at(bit_) + ": " + bz2::status_text(bz2::kBadRun));
+            return false;
+        }
         if (~crc != info.crc) {
             fail("block at byte " + at(bit_) + ": " + bz2::status_text(bz2::kBadCrc));
             return false;

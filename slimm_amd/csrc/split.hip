@@ -157,7 +157,9 @@ int slimm_host_bzip2_ranges(const char* path, uint64_t skip, uint32_t n, uint64_
         if (status == bz2::kRanOut && more()) continue;
         if (status != bz2::kOk) return SLIMM_E_INVALID;
         bz2::link_block(ll.data(), info.n, counts.data(), link.data(), cf.data());
-        decoded += bz2::text_length(link.data(), info.n, info.orig_ptr);
+        const uint64_t text = bz2::text_length(link.data(), info.n, info.orig_ptr);
+        if (text == bz2::kNoTextLength) return SLIMM_E_INVALID;
+        decoded += text;
         bit = info.end_bit;
     }
     const uint64_t floor = std::min<uint64_t>(f.size, (bit + 7u) >> 3);
