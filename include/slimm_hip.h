@@ -741,7 +741,8 @@ int slimm_group_get_profiles(slimm_group* g, const char* path); /* path may be N
 /* ONE FILE SPLIT BY BYTE RANGE over a group (files GROUPED by read name or in ANY order): every member reads, inflates and decodes its own contiguous
  * range of the file at once.  Five forms of file: BAM, SAM text, SAM text in BGZF blocks (bgzip), bzip2-compressed SAM
  * text (below: "bzip2 SAM by byte range") and zstd-compressed SAM text of several frames (below: "zstd SAM by byte range").
- * (A plain gzip stream and a zstd file of one frame cannot be cut: they go through one member.)
+ * gzip-compressed SAM text is cut at the bits where blocks start and read in two passes (below: "gzip SAM by byte range").
+ * (A zstd file of one frame cannot be cut: it goes through one member.)
  *   The plan (host only, no GPU): offsets_out[0, n]; range i = [offsets_out[i], offsets_out[i + 1]), ranges may be empty.
  * slimm_host_bgzf_ranges -- BAM and BGZF SAM --: offsets_out[0] = 0, offsets_out[n] = the file's size; a range starts on a
  * BGZF block boundary (a header whose next three headers chain through BSIZE + 1, or whose chain reaches the EOF block or
@@ -869,6 +870,53 @@ int slimm_host_xz_ranges(const char* path, uint64_t skip, uint32_t n, uint64_t* 
 int slimm_host_xz_check_at(const char* path, uint64_t offset, int* check_out);
 int slimm_set_xz_range_check(slimm_ctx* ctx, int check);
 uint64_t slimm_xz_split_floor(void);
+/*   gzip SAM by byte range.  A deflate stream has no marks, its blocks start at any bit, and a block copies from the 32 768
+ * bytes of text in front of it, whatever block they came from -- in SAM text those bytes never die out: a constant tag is
+ * copied from its previous copy for the whole file.  So a gzip file is cut at BITS and read in two passes.
+ *   The plan.  slimm_host_gzip_ranges: bit_offsets_out[0] = 0, bit_offsets_out[n] = 8 x the file's size; member i reads the
+ * file's bytes [bits[i] / 8, (bits[i + 1] + 7) / 8), so neighbours share at most one byte.  No cut lies in front of the end
+ * of the block that holds inflated byte skip - 1 (the file's first blocks are inflated on the host; member 0 holds the
+ * whole header and pushes with that skip).  Cut i is the first bit at or behind its even share of the bits behind that floor
+ * at which a non-final dynamic block that zlib would take starts (the two codes parse, the literal/length code complete)
+ * AND a walk from there -- Huffman codes only -- passes 4 further block boundaries, or a final block, without an error.  The
+ * walk also ends after 4 MiB of compressed bytes; the candidate then counts if at least one boundary was passed.  The
+ * search gives up 64 MiB behind its target: the cut is then the next one found, or the file's end, and the range in
+ * between is empty -- a stream of stored or fixed blocks only has every cut at the file's end.  (4 blocks, 64 MiB: stated
+ * defaults, not measurements; SLIMM_FORCE gzip_cut_blocks=N, gzip_cut_search=N.)  SLIMM_E_INVALID for a path that is no
+ * regular file, bytes that start no gzip member, a header that does not inflate, a skip of 2^32 or more.  The planner trusts
+ * nothing it cannot walk: a cut it took can still be false, and the members and the stitch decide.
+ *   Every member announces its flags with slimm_set_input_mid_file AND its range with slimm_set_gzip_range(ctx, begin_bit,
+ * end_bit) before its first push, and pushes -- slimm_push_gzip_sam_bytes, skip for member 0 only -- the bytes that hold
+ * its bits.  A range that starts inside the file starts among a gzip member's blocks at begin_bit: no member header is
+ * expected, 32 768 bytes of that member are taken to lie in front until slimm_group_gzip_windows knows better, and its CRC
+ * register and member length start at 0 (a partial).  A range that ends inside the file starts no chunk at or behind
+ * end_bit, its size pass stops there, and it is done when its chain stands exactly on end_bit; a chain that steps over
+ * end_bit, or has not reached it at last = 1, is SLIMM_E_SPLIT and names the bit.  An error among the blocks of the gzip
+ * member a range started in is SLIMM_E_SPLIT too, no verdict on the file: the range may have started where no block does.
+ *   THE WINDOW PASS: slimm_set_gzip_window_pass(ctx, 1) before the first push, then the same pushes of the same bytes.  The
+ * rounds find, walk, chain and decode as ever; instead of resolving the text they propagate the last 32 768 symbols chunk by
+ * chunk in 16 bits, each a byte or a marker for a byte of the 32 768 in front of the RANGE.  No text, no records, no CRC;
+ * memory is that of one round, whatever the range's size.  slimm_group_gzip_windows(g) then goes left to right: member k's
+ * chain ended on member k + 1's begin_bit (SLIMM_E_SPLIT); its final window, its markers filled from the bytes in front of
+ * its own range by a tiny kernel, is copied device to device and becomes the bytes in front of member k + 1, with how many
+ * of them belong to the open gzip member; every member's file state is made fresh, its announcements kept.  The last
+ * member need not run the window pass.  The serial work is 32 KiB per cut.
+ *   THE TEXT PASS is the pipeline of one context from the installed bytes: the same pushes once more.  It must reproduce
+ * the window pass's end bit and text length (SLIMM_E_SPLIT).  A member that starts inside a gzip member cannot check that
+ * member's trailer: at the first trailer in its range it keeps its partial register and length and the trailer's CRC32,
+ * ISIZE and byte offset; later gzip members it checks itself.  Text, heads and carries are SAM text's.
+ *   slimm_group_stitch_ranges first goes left to right on host scalars: every chain ended on its range's end; the register
+ * of a gzip member that lies over cuts is folded, s = s * x^(8 len_k) + partial_k, and held with the summed length against
+ * the trailer that member k read -- "corrupt gzip stream (incorrect data check)" or "(incorrect length check)" with the
+ * trailer's byte, SLIMM_E_INVALID; a range without a trailer hands both on.  slimm_get_gzip_stats stays per context and the
+ * members' counters sum to the file's: a gzip member is counted by whoever read its trailer, a block by exactly one member.
+ * slimm_gzip_split_floor(): the least bytes per member -- (size - first cut) / members -- at which the command cuts a gzip
+ * file for --split-input: 32 MiB as zstd's (a stated default, not a measurement; SLIMM_FORCE gzip_split_floor=N). */
+int slimm_host_gzip_ranges(const char* path, uint64_t skip, uint32_t n, uint64_t* bit_offsets_out);
+int slimm_set_gzip_range(slimm_ctx* ctx, uint64_t begin_bit, uint64_t end_bit);
+int slimm_set_gzip_window_pass(slimm_ctx* ctx, int on);
+int slimm_group_gzip_windows(slimm_group* g);
+uint64_t slimm_gzip_split_floor(void);
 int slimm_host_bzip2_ranges(const char* path, uint64_t skip, uint32_t n, uint64_t* offsets_out);
 /* A range's absolute file offsets [begin, end) (bzip2 SAM, zstd SAM, xz SAM; before the range's first window, beside slimm_set_input_mid_file) */
 int slimm_set_input_range(slimm_ctx* ctx, uint64_t begin, uint64_t end);

@@ -219,6 +219,11 @@ SYMBOLS = [
     ("slimm_host_xz_check_at", C.c_int, [C.c_char_p, C.c_uint64, C.POINTER(C.c_int)]),
     ("slimm_set_xz_range_check", C.c_int, [_P, C.c_int]),
     ("slimm_xz_split_floor", C.c_uint64, []),
+    ("slimm_host_gzip_ranges", C.c_int, [C.c_char_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]),
+    ("slimm_set_gzip_range", C.c_int, [_P, C.c_uint64, C.c_uint64]),
+    ("slimm_set_gzip_window_pass", C.c_int, [_P, C.c_int]),
+    ("slimm_group_gzip_windows", C.c_int, [_P]),
+    ("slimm_gzip_split_floor", C.c_uint64, []),
     ("slimm_group_stitch_ranges", C.c_int, [_P]),
     ("slimm_record_cap", C.c_uint64, []),
     ("slimm_shutdown", C.c_int, []),

@@ -33,6 +33,11 @@
 //   told), zstd_cut_search=N (slimm_host_zstd_ranges gives a cut up N bytes behind its target: 64 MiB unless told),
 //   zstd_split_wrong_cut (the planner's second cut -- of two members: its only one -- lands one byte late, where no frame
 //   starts: the members or the stitch must refuse it)   tests/test_gpu_split_zstd_sam.py, tests/test_cli_split_input_zstd.py
+//   gzip_split_floor=N (the least bytes per member at which the command cuts a gzip file for --split-input: 32 MiB unless
+//   told), gzip_cut_blocks=N (slimm_host_gzip_ranges takes a block candidate for a cut when a walk from it passes N block
+//   boundaries: 4 unless told), gzip_cut_search=N (... and gives a cut up N bytes behind its target: 64 MiB unless told),
+//   gzip_split_wrong_cut (the planner's second cut -- of two members: its only one -- lands one bit late, where no block
+//   starts: the members must refuse it)         tests/test_gpu_split_gzip_sam.py, tests/test_cli_split_input_gzip.py
 //   sample_stride=S (the tile bucketing counts every S-th slot wherever a sampled count can run, 1: nowhere), sample_k=K
 //   (standard deviations of head-room in a capacity: 8 unless told), bucket_room=N (the bucket allocation holds N entries
 //   whatever the file: tile_plan.h)              tests/test_gpu_sampled_count.py, tests/test_tile_sample_plan.py

@@ -720,6 +720,12 @@ int slimm_group_stitch_ranges(slimm_group* g) {
         if (rc == SLIMM_E_SPLIT) return gfail(g, SLIMM_E_SPLIT, "the range of member %u: %s", bad, slimm_last_error(g->ctx[bad]));
         if (rc < 0) return member_failed(g, bad, rc, "the frames of a range");
     }
+    if (slimm::split_is_gzip(g->ctx[0])) {   // (every chain ended on its range's end, a gzip member over cuts matches its trailer)
+        uint32_t bad = 0;
+        const int rc = slimm::split_gz_chains(g->ctx.data(), n, &bad);
+        if (rc == SLIMM_E_SPLIT) return gfail(g, SLIMM_E_SPLIT, "the range of member %u: %s", bad, slimm_last_error(g->ctx[bad]));
+        if (rc < 0) return member_failed(g, bad, rc, "a gzip member across a cut");
+    }
     if (slimm::split_is_xz(g->ctx[0])) {   // (every member's walker stopped where its range does, and a stream over cuts matches its index)
         uint32_t bad = 0;
         const int rc = slimm::split_xz_streams(g->ctx.data(), n, &bad);
@@ -775,6 +781,16 @@ int slimm_group_stitch_ranges(slimm_group* g) {
     }
     for (uint32_t k = 0; k < n; ++k) GTRY(g, k, slimm::split_keep(g->ctx[k], from[k]));
     g->stitched = true;
+    return SLIMM_OK;
+}
+
+// gzip SAM by byte range, between the members' window pass and their text pass (split.hip: split_gz_windows)
+int slimm_group_gzip_windows(slimm_group* g) {
+    if (!g) return SLIMM_E_INVALID;
+    uint32_t bad = 0;
+    const int rc = slimm::split_gz_windows(g->ctx.data(), static_cast<uint32_t>(g->ctx.size()), &bad);
+    if (rc == SLIMM_E_SPLIT) return gfail(g, SLIMM_E_SPLIT, "the range of member %u: %s", bad, slimm_last_error(g->ctx[bad]));
+    if (rc < 0) return member_failed(g, bad, rc, "the windows across a cut");
     return SLIMM_OK;
 }
 

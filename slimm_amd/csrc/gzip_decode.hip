@@ -79,7 +79,7 @@ __device__ bool is_start(const unsigned long long* starts, uint32_t from, uint32
 }
 
 __global__ __launch_bounds__(64) void k_gz_walk(const uint8_t* __restrict__ b, uint64_t n_bytes, const unsigned long long* __restrict__ starts,
-                                                     uint32_t n, uint64_t soft, gz::Walk* __restrict__ walk) {
+                                                     uint32_t n, uint64_t soft, uint64_t stop_bit, gz::Walk* __restrict__ walk) {
     __shared__ gz::Tables t;
     const uint32_t i = blockIdx.x;
     if (threadIdx.x != 0 || i >= n) return;
@@ -96,7 +96,8 @@ __global__ __launch_bounds__(64) void k_gz_walk(const uint8_t* __restrict__ b, u
         w.end_bit = br.pos();
         w.n = out.n;
         w.final = fin ? 1u : 0u;
-        if (fin || out.n >= soft || is_start(starts, i + 1u, n, w.end_bit)) break;
+        // (stop_bit: the end of a byte range of a split file -- a walk that reaches or steps over it goes no further)
+        if (fin || out.n >= soft || w.end_bit >= stop_bit || is_start(starts, i + 1u, n, w.end_bit)) break;
     }
     walk[i] = w;
 }
@@ -142,6 +143,44 @@ __global__ __launch_bounds__(1024) void k_gz_windows(const gz::Chunk* __restrict
         __threadfence_block();
         __syncthreads();
     }
+}
+
+// The window pass of a byte range of a split file (slimm_set_gzip_window_pass): k_gz_windows in 16 bits.  A symbol is a byte,
+// or a marker for a byte of the 32 768 in front of the RANGE, which its left neighbour knows; slot 0 before the range's
+// first chunk (identity): marker i for byte i.  One workgroup, chunk by chunk
+__global__ __launch_bounds__(1024) void k_gz_windows16(const gz::Chunk* __restrict__ chunks, uint32_t n, const uint16_t* __restrict__ sym,
+                                                        uint16_t* __restrict__ win, uint32_t identity) {
+    if (identity) {
+        for (uint32_t i = threadIdx.x; i < gz::kWindow; i += blockDim.x) win[i] = static_cast<uint16_t>(gz::kMarker | i);
+        __threadfence_block();
+        __syncthreads();
+    }
+    for (uint32_t k = 0; k < n; ++k) {
+        const uint16_t* prev = win + static_cast<uint64_t>(k) * gz::kWindow;
+        uint16_t* mine = win + static_cast<uint64_t>(k + 1u) * gz::kWindow;
+        const uint64_t len = chunks[k].len;
+        const uint16_t* s = sym + chunks[k].text_at;
+        for (uint32_t i = threadIdx.x; i < gz::kWindow; i += blockDim.x) {
+            uint16_t v;
+            if (len >= gz::kWindow || i >= gz::kWindow - len) {
+                const uint16_t u = s[len - (gz::kWindow - i)];
+                v = (u & gz::kMarker) ? prev[u & (gz::kWindow - 1u)] : u;
+            } else {
+                v = prev[i + len];
+            }
+            mine[i] = v;
+        }
+        __threadfence_block();
+        __syncthreads();
+    }
+}
+
+// a range's final 16-bit window against the 32 768 bytes in front of the range: the bytes in front of the NEXT range
+__global__ __launch_bounds__(256) void k_gz_window_apply(const uint16_t* __restrict__ win16, const uint8_t* __restrict__ front, uint8_t* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= gz::kWindow) return;
+    const uint16_t u = win16[i];
+    out[i] = (u & gz::kMarker) ? front[u & (gz::kWindow - 1u)] : static_cast<uint8_t>(u);
 }
 
 __global__ __launch_bounds__(256) void k_gz_resolve(const gz::Chunk* __restrict__ chunks, uint32_t n, uint32_t n_pieces, const uint16_t* __restrict__ sym,
@@ -200,6 +239,26 @@ void push_trace_gz(const char* fmt, ...) {   // "[push gzip] ..."
 #define GZ_CORRUPT(fmt, ...) fail(c, SLIMM_E_INVALID, "corrupt gzip stream (" fmt ")", __VA_ARGS__)
 #define GZ_TRUNCATED() fail(c, SLIMM_E_INVALID, "truncated gzip stream")
 
+// A byte range of a split file (slimm_set_gzip_range).  Its end as a bit of the bytes at hand; ~0: the file's end
+constexpr uint64_t kNoStop = ~0ull;
+uint64_t gz_stop_bit(const slimm_ctx* c) {
+    const WindowPipeline::Announced& A = c->win.announced;
+    return A.gz_range && A.ends_mid ? A.gz_end_bit - c->win.file.stream.base * 8u : kNoStop;
+}
+// the bytes ended, or the chain stopped, in front of the range's end: the cut is refused, no verdict on the file
+int gz_short_of_end(slimm_ctx* c) {
+    const WindowPipeline::File::Stream& T = c->win.file.stream;
+    return fail(c, SLIMM_E_SPLIT, "gzip: the chain of the range stands at bit %llu behind its last byte and has not reached the range's end, bit %llu",
+                static_cast<unsigned long long>(T.base * 8u + T.bit), static_cast<unsigned long long>(c->win.announced.gz_end_bit));
+}
+// an error among the blocks: a range that started among a member's blocks may have started where no block does
+int gz_bad_blocks(slimm_ctx* c, uint32_t status) {
+    if (c->win.file.gz.partial)
+        return fail(c, SLIMM_E_SPLIT, "gzip: the blocks from bit %llu on, where the range starts, do not decode (%s)",
+                    static_cast<unsigned long long>(c->win.announced.gz_begin_bit), gz::status_text(status));
+    return GZ_CORRUPT("%s", gz::status_text(status));
+}
+
 // the block candidates of pend from T.bit on, in order; the bytes go to the device first
 int gz_find(slimm_ctx* c) {
     WindowPipeline& W = c->win;
@@ -240,7 +299,7 @@ int gz_find(slimm_ctx* c) {
 bool gz_next_window(const slimm_ctx* c, uint64_t, uint64_t* n) {   // (a round's text is one window: kRoundText)
     uint64_t text = 0;
     for (const gz::Chunk& k : c->win.file.gz.ready) text += k.len;
-    *n = text - std::min(text, c->win.file.stream.skip_left);
+    *n = c->win.file.gz.window_pass ? 0u : text - std::min(text, c->win.file.stream.skip_left);   // (the window pass writes no text)
     return !c->win.file.gz.ready.empty();
 }
 
@@ -252,6 +311,13 @@ int gz_round(slimm_ctx* c, bool last) {
     hipStream_t st = c->stream;
     uint64_t* stats = W.gz_stats;
     Z.ready.clear();
+    const uint64_t stop = gz_stop_bit(c);
+    const bool ends_mid = stop != kNoStop;
+    if (Z.range_done) return SLIMM_OK;
+    if (W.announced.gz_range && (T.bit == stop || W.announced.gz_begin_bit == W.announced.gz_end_bit)) {   // (the chain stands on the range's end; an empty range)
+        Z.range_done = true;
+        return SLIMM_OK;
+    }
     if (T.waiting && !last) return SLIMM_OK;
     // the candidates in [from, to) of the bytes at hand lie in a trailer or a member header: passed over
     auto pass_over = [&](uint64_t from, uint64_t to) {
@@ -264,30 +330,40 @@ int gz_round(slimm_ctx* c, bool last) {
         const uint64_t byte = (T.bit + 7u) >> 3, avail = T.pend.size() - std::min<uint64_t>(byte, T.pend.size());
         const uint8_t* p = T.pend.data() + byte;
         if (Z.stage == Stage::Trailer) {
-            if (avail < 8) {
-                if (last) return GZ_TRUNCATED();
+            if (avail < 8 || (byte + 8u) * 8u > stop) {
+                if (last || avail >= 8) return ends_mid ? gz_short_of_end(c) : GZ_TRUNCATED();
                 T.waiting = true;
                 return SLIMM_OK;
             }
             const uint32_t crc = p[0] | (p[1] << 8) | (p[2] << 16) | (static_cast<uint32_t>(p[3]) << 24);
             const uint32_t isize = p[4] | (p[5] << 8) | (p[6] << 16) | (static_cast<uint32_t>(p[7]) << 24);
-            if (crc != ~Z.crc) return GZ_CORRUPT("%s", gz::status_text(gz::kBadCrc));
-            if (isize != static_cast<uint32_t>(Z.len)) return GZ_CORRUPT("%s", gz::status_text(gz::kBadLength));
+            if (Z.partial) {   // (the member started in front of the range: the stitch holds its parts against this trailer)
+                Z.left = {true, Z.crc, crc, isize, Z.len, T.base + byte};
+                Z.partial = false;
+            } else if (!Z.window_pass) {
+                if (crc != ~Z.crc) return GZ_CORRUPT("%s", gz::status_text(gz::kBadCrc));
+                if (isize != static_cast<uint32_t>(Z.len)) return GZ_CORRUPT("%s", gz::status_text(gz::kBadLength));
+            }
             pass_over(T.bit, (byte + 8u) * 8u);
             T.bit = (byte + 8u) * 8u;
             Z.stage = Stage::Header;
             ++stats[WindowPipeline::kGzMembers];
             continue;
         }
+        if (T.bit == stop) {   // (the range ends between two members)
+            Z.range_done = true;
+            return SLIMM_OK;
+        }
         if (avail == 0) {   // the file is used up between two members
+            if (last && ends_mid) return gz_short_of_end(c);
             if (last && stats[WindowPipeline::kGzMembers] == 0) return GZ_TRUNCATED();
             T.waiting = true;
             return SLIMM_OK;
         }
         const long h = gz::member_header(p, avail);
         if (h < 0) return GZ_CORRUPT("%s", "incorrect header check");
-        if (h == 0) {
-            if (last) return GZ_TRUNCATED();
+        if (h == 0 || (byte + static_cast<uint64_t>(h)) * 8u > stop) {
+            if (last || h > 0) return ends_mid ? gz_short_of_end(c) : GZ_TRUNCATED();
             T.waiting = true;
             return SLIMM_OK;
         }
@@ -296,6 +372,11 @@ int gz_round(slimm_ctx* c, bool last) {
         Z.stage = Stage::Deflate;
         Z.crc = 0xffffffffu;
         Z.len = 0;
+        Z.front = 0;
+    }
+    if (T.bit == stop) {   // (the range ends right behind a member header: the member's blocks are the next range's)
+        Z.range_done = true;
+        return SLIMM_OK;
     }
     // ---- a round on the device: candidates, chunk starts, the size pass
     if (!T.found) SLIMM_TRY(gz_find(c));
@@ -306,7 +387,7 @@ int gz_round(slimm_ctx* c, bool last) {
     const uint64_t cb = static_cast<uint64_t>(chunk) * 8u;
     for (uint64_t target = T.bit + cb;;) {   // (the first candidate at or behind every cb bits)
         const auto it = std::lower_bound(T.cand.begin(), T.cand.end(), target);
-        if (it == T.cand.end()) break;
+        if (it == T.cand.end() || *it >= stop) break;   // (no chunk starts at or behind the range's end)
         starts.push_back(*it);
         target = T.bit + ((*it - T.bit) / cb + 1u) * cb;
     }
@@ -322,11 +403,12 @@ int gz_round(slimm_ctx* c, bool last) {
     }
     std::sort(starts.begin(), starts.end());
     starts.erase(std::unique(starts.begin(), starts.end()), starts.end());
+    starts.erase(std::lower_bound(starts.begin() + 1, starts.end(), stop), starts.end());
     const uint32_t ns = static_cast<uint32_t>(starts.size());
     if (S.d_cand.cap < ns) HIP_TRY(c, S.d_cand.ensure_later(ns + (ns >> 2) + 256u, W.outgrown));
     if (S.walk.cap < ns) HIP_TRY(c, S.walk.ensure_later(ns + (ns >> 2) + 256u, W.outgrown));
     HIP_TRY(c, hipMemcpyAsync(S.d_cand.p, starts.data(), ns * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_gz_walk, dim3(ns), dim3(64), 0, st, S.comp.p, n_bytes, S.d_cand.p, ns, kChunkTextSoft, S.walk.p);
+    hipLaunchKernelGGL(k_gz_walk, dim3(ns), dim3(64), 0, st, S.comp.p, n_bytes, S.d_cand.p, ns, kChunkTextSoft, stop, S.walk.p);
     HIP_TRY(c, hipGetLastError());
     std::vector<gz::Walk> walk(ns);
     HIP_TRY(c, hipMemcpyAsync(walk.data(), S.walk.p, ns * sizeof(gz::Walk), hipMemcpyDeviceToHost, st));
@@ -339,14 +421,14 @@ int gz_round(slimm_ctx* c, bool last) {
     bool final = false;
     for (;;) {
         const gz::Walk& w = walk[i];
-        if (w.status != gz::kOk && w.status != gz::kRanOut) return GZ_CORRUPT("%s", gz::status_text(w.status));
+        if (w.status != gz::kOk && w.status != gz::kRanOut) return gz_bad_blocks(c, w.status);
         if (w.end_bit > cur) {
             if (w.n > kChunkTextMax)
                 return fail(c, SLIMM_E_INVALID, "a deflate block of more than 1 GiB of text: decode this file on the host");
             if (!Z.ready.empty() && text + w.n > kRoundText) break;   // (the round is full: this chunk starts the next one)
             gz::Chunk k{};
             k.start_bit = cur, k.stop_bit = w.end_bit, k.text_at = text, k.len = w.n;
-            k.avail = static_cast<uint32_t>(std::min<uint64_t>(gz::kWindow, member_len));
+            k.avail = static_cast<uint32_t>(std::min<uint64_t>(gz::kWindow, Z.front + member_len));
             k.piece0 = pieces;
             k.last_mul = gz::crc_x_pow8(w.n % gz::kPiece ? w.n % gz::kPiece : (w.n ? gz::kPiece : 0u));
             pieces += static_cast<uint32_t>((w.n + gz::kPiece - 1u) / gz::kPiece);
@@ -355,8 +437,14 @@ int gz_round(slimm_ctx* c, bool last) {
             member_len += w.n;
             cur = w.end_bit;
         }
+        if (cur > stop)
+            return fail(c, SLIMM_E_SPLIT, "gzip: the chain steps over the range's end, bit %llu: the block there ends at bit %llu",
+                        static_cast<unsigned long long>(W.announced.gz_end_bit), static_cast<unsigned long long>(T.base * 8u + cur));
         if (w.status == gz::kRanOut) {
-            if (last) return GZ_TRUNCATED();
+            if (last) {
+                T.bit = cur;
+                return ends_mid ? gz_short_of_end(c) : GZ_TRUNCATED();
+            }
             T.waiting = true;
             break;
         }
@@ -364,6 +452,7 @@ int gz_round(slimm_ctx* c, bool last) {
             final = true;
             break;
         }
+        if (cur == stop) break;
         const size_t nx = static_cast<size_t>(std::lower_bound(starts.begin() + static_cast<long>(i) + 1, starts.end(), cur) - starts.begin());
         if (nx >= ns || starts[nx] != cur) break;   // (stopped behind kChunkTextSoft bytes of text: an exact start for the next round)
         i = nx;
@@ -375,6 +464,47 @@ int gz_round(slimm_ctx* c, bool last) {
     stats[WindowPipeline::kGzChunks] += Z.ready.size();
     T.bit = cur;
     if (final) Z.stage = Stage::Trailer;
+    if (cur == stop && !final) Z.range_done = true;
+    return SLIMM_OK;
+}
+
+// A round of the window pass: the chain's chunks decoded as in gz_emit, and their last 32 768 symbols propagated in 16 bits
+// (k_gz_windows16) instead of resolved: no text, no CRC; slot 0 keeps the round's last window for the next round, and
+// behind the last round for slimm_group_gzip_windows.  Memory: one round's
+int gz_window_round(slimm_ctx* c) {
+    WindowPipeline& W = c->win;
+    WindowPipeline::File::Gzip& Z = W.file.gz;
+    WindowPipeline::Gzip& S = W.gz;
+    hipStream_t st = c->stream;
+    const uint32_t n = static_cast<uint32_t>(Z.ready.size());
+    uint64_t text = 0;
+    for (const gz::Chunk& k : Z.ready) text += k.len;
+    if (S.chunks.cap < n) HIP_TRY(c, S.chunks.ensure_later(n + (n >> 2) + 64u, W.outgrown));
+    if (S.sym.cap < text + 1u) HIP_TRY(c, S.sym.ensure_later(text + (text >> 3) + 1u, W.outgrown));
+    const uint64_t win_need = (static_cast<uint64_t>(n) + 1u) * gz::kWindow;
+    if (S.win16.cap < win_need) {
+        const uint64_t room = win_need + (win_need >> 2);
+        if (Z.carried) HIP_TRY(c, S.win16.grow_keeping(room, 0, gz::kWindow, st, false, &W.outgrown));
+        else
+            HIP_TRY(c, S.win16.ensure_later(room, W.outgrown));
+    }
+    const bool identity = !Z.carried && W.announced.starts_mid;
+    if (!Z.carried && !identity) HIP_TRY(c, hipMemsetAsync(S.win16.p, 0, gz::kWindow * sizeof(uint16_t), st));
+    HIP_TRY(c, hipMemcpyAsync(S.chunks.p, Z.ready.data(), n * sizeof(gz::Chunk), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_gz_decode, dim3(n), dim3(64), 0, st, S.comp.p, W.file.stream.pend.size(), S.chunks.p, n, S.sym.p);
+    hipLaunchKernelGGL(k_gz_windows16, dim3(1), dim3(1024), 0, st, S.chunks.p, n, S.sym.p, S.win16.p, identity ? 1u : 0u);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(S.win16.p, S.win16.p + static_cast<uint64_t>(n) * gz::kWindow, gz::kWindow * sizeof(uint16_t), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(Z.ready.data(), S.chunks.p, n * sizeof(gz::Chunk), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    Z.carried = true;
+    for (const gz::Chunk& k : Z.ready) {
+        if (k.status != gz::kOk) return gz_bad_blocks(c, k.status);
+        Z.len += k.len;
+    }
+    Z.text += text;
+    push_trace_gz("window pass, round %llu: %u chunks, %.1f MB of text passed over", (unsigned long long)W.gz_stats[WindowPipeline::kGzRounds], n, text / 1e6);
+    Z.ready.clear();
     return SLIMM_OK;
 }
 
@@ -387,6 +517,7 @@ int gz_emit(slimm_ctx* c, uint8_t* dst, uint64_t, uint64_t* n_out, uint8_t* last
     const uint32_t n = static_cast<uint32_t>(Z.ready.size());
     *n_out = 0;
     if (!n) return SLIMM_OK;
+    if (Z.window_pass) return gz_window_round(c);
     uint64_t text = 0;
     for (const gz::Chunk& k : Z.ready) text += k.len;
     const uint32_t pieces = Z.ready.back().piece0 + static_cast<uint32_t>((Z.ready.back().len + gz::kPiece - 1u) / gz::kPiece);
@@ -401,7 +532,13 @@ int gz_emit(slimm_ctx* c, uint8_t* dst, uint64_t, uint64_t* n_out, uint8_t* last
         else
             HIP_TRY(c, S.win.ensure_later(room, W.outgrown));
     }
-    if (!Z.carried) HIP_TRY(c, hipMemsetAsync(S.win.p, 0, gz::kWindow, st));
+    if (!Z.carried) {
+        // (a range that starts among a member's blocks: the bytes in front of it, as the window pass of its left neighbour left them)
+        if (W.announced.gz_range && W.announced.starts_mid && W.gz_pass.has_front)
+            HIP_TRY(c, hipMemcpyAsync(S.win.p, S.front.p, gz::kWindow, hipMemcpyDeviceToDevice, st));
+        else
+            HIP_TRY(c, hipMemsetAsync(S.win.p, 0, gz::kWindow, st));
+    }
     HIP_TRY(c, hipMemcpyAsync(S.chunks.p, Z.ready.data(), n * sizeof(gz::Chunk), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_gz_decode, dim3(n), dim3(64), 0, st, S.comp.p, W.file.stream.pend.size(), S.chunks.p, n, S.sym.p);
     hipLaunchKernelGGL(k_gz_windows, dim3(1), dim3(1024), 0, st, S.chunks.p, n, S.sym.p, S.win.p);
@@ -417,7 +554,7 @@ int gz_emit(slimm_ctx* c, uint8_t* dst, uint64_t, uint64_t* n_out, uint8_t* last
     for (const gz::Chunk& k : Z.ready) {
         // (a decode error here is one on the chain: the size pass took these blocks, so only a reach in front of the
         // member's start, which it cannot see, is expected)
-        if (k.status != gz::kOk) return GZ_CORRUPT("%s", gz::status_text(k.status));
+        if (k.status != gz::kOk) return gz_bad_blocks(c, k.status);
         Z.crc = gz::crc_mul(Z.crc, gz::crc_x_pow8(k.len)) ^ k.crc;
         Z.len += k.len;
         stats[WindowPipeline::kGzStored] += k.kinds[0];
@@ -426,10 +563,15 @@ int gz_emit(slimm_ctx* c, uint8_t* dst, uint64_t, uint64_t* n_out, uint8_t* last
         stats[WindowPipeline::kGzResolved] += k.markers;
     }
     stats[WindowPipeline::kGzText] += text;
+    Z.text += text;
     *n_out = text - drop;
     push_trace_gz("round %llu: %u chunks -> %.1f MB of text", (unsigned long long)stats[WindowPipeline::kGzRounds], n, text / 1e6);
     Z.ready.clear();
     return SLIMM_OK;
+}
+
+void launch_gz_window_apply(hipStream_t st, const uint16_t* win16, const uint8_t* front, uint8_t* out) {
+    hipLaunchKernelGGL(k_gz_window_apply, dim3(gz::kWindow / 256u), dim3(256), 0, st, win16, front, out);
 }
 
 void gz_trace_file(const slimm_ctx* c) {

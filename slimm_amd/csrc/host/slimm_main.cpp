@@ -142,6 +142,11 @@ SLIMM_FORWARD(int, slimm_host_xz_ranges, (const char* a, uint64_t b, uint32_t c,
 SLIMM_FORWARD(int, slimm_host_xz_check_at, (const char* a, uint64_t b, int* c), (a, b, c))
 SLIMM_FORWARD(int, slimm_set_xz_range_check, (slimm_ctx* a, int b), (a, b))
 SLIMM_FORWARD(uint64_t, slimm_xz_split_floor, (), ())
+SLIMM_FORWARD(int, slimm_host_gzip_ranges, (const char* a, uint64_t b, uint32_t c, uint64_t* d), (a, b, c, d))
+SLIMM_FORWARD(int, slimm_set_gzip_range, (slimm_ctx* a, uint64_t b, uint64_t c), (a, b, c))
+SLIMM_FORWARD(int, slimm_set_gzip_window_pass, (slimm_ctx* a, int b), (a, b))
+SLIMM_FORWARD(int, slimm_group_gzip_windows, (slimm_group* a), (a))
+SLIMM_FORWARD(uint64_t, slimm_gzip_split_floor, (), ())
 SLIMM_FORWARD(int, slimm_group_stitch_ranges, (slimm_group* a), (a))
 SLIMM_FORWARD(uint64_t, slimm_record_cap, (), ())
 SLIMM_FORWARD(int, slimm_shutdown, (), ())
@@ -181,6 +186,7 @@ SLIMM_FORWARD(int, slimm_get_record_filter_stats, (slimm_ctx* a, uint64_t* b), (
 #include "zstd.hpp"
 #include "xz.hpp"
 #include "../force.h"
+#include "../gzip_plan.h"
 #include "sldb.hpp"
 
 namespace {
@@ -695,6 +701,11 @@ struct InputForm {
     bool wide_header_by_host = false;  // the pump: a header of 2^32 text bytes or more goes through the host reader (pushed_as)
     uint64_t (*slack)() = nullptr;     // bytes a member reads behind its range, at most to the file's end (none: 0)
     bool announce_range = false;       // the members are told their ranges (slimm_set_input_range)
+    // gzip: the plan's offsets are BITS -- a member reads the bytes that hold its bits and is told the bits --, and every
+    // member but the last reads its range twice: the window pass (window_pass(ctx, 1)), then windows(group), then the text pass
+    int (*announce_bits)(slimm_ctx*, uint64_t begin_bit, uint64_t end_bit) = nullptr;
+    int (*window_pass)(slimm_ctx*, int on) = nullptr;
+    int (*windows)(slimm_group*) = nullptr;
     // ... and what a range that starts at `offset` cannot see of the file in front of it, beside its range (none: nothing)
     int (*range_note)(const char* path, uint64_t offset, int* note) = nullptr;
     int (*announce_note)(slimm_ctx*, int note) = nullptr;
@@ -793,6 +804,29 @@ bool zstd_may_cut(const AlignmentFile& f, const std::string& path, uint32_t G, b
     close(fd);
     return ok && first <= size && (size - first) / G >= slimm_zstd_split_floor();
 }
+// gzip SAM is cut at the bits where non-final dynamic blocks start (slimm_host_gzip_ranges): read_split takes a file with a
+// header of fewer than 2^32 bytes whose plan for G members has at least two ranges that are not empty and, with_floor, whose
+// members get slimm_gzip_split_floor() bytes each or more: (the file's size - the first legal cut) / G, asked before the plan,
+// which reads more of the file (the cap's re-read does not ask: it has no other way).  The floor is zstd's, a stated default,
+// not a measurement: a range is decoded twice, so two members may not gain
+bool gzip_may_cut(const AlignmentFile& f, const std::string& path, uint32_t G, bool with_floor) {
+    if (G < 2u || f.text_header_bytes() >= (1ull << 32)) return false;
+    if (with_floor) {
+        const int fd = open(path.c_str(), O_RDONLY);
+        struct stat sb;
+        uint64_t first_bit = 0;
+        const bool ok = fd >= 0 && fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) &&
+                        slimm::gzip_header_end([&](uint64_t at, uint8_t* dst, size_t n) { return pread_all(fd, dst, at, n); }, static_cast<uint64_t>(sb.st_size),
+                                        f.text_header_bytes(), &first_bit);
+        if (fd >= 0) close(fd);
+        if (!ok || (static_cast<uint64_t>(sb.st_size) - first_bit / 8u) / G < slimm_gzip_split_floor()) return false;
+    }
+    std::vector<uint64_t> off(G + 1u, 0);
+    if (slimm_host_gzip_ranges(path.c_str(), f.text_header_bytes(), G, off.data()) != SLIMM_OK) return false;
+    uint32_t filled = 0;
+    for (uint32_t i = 0; i < G; ++i) filled += off[i + 1] > off[i] ? 1u : 0u;
+    return filled >= 2u;
+}
 // xz SAM is cut where its indexes say a block or a stream starts (xz_plan_ranges, the rule of slimm_host_xz_ranges, over one
 // reading of the indexes): read_split takes a file whose plan for G members has at least two ranges that are not empty and,
 // with_floor, whose members get slimm_xz_split_floor() blocks each or more: the blocks behind the first legal cut / G (the
@@ -831,8 +865,9 @@ const InputForm kForms[] = {
     {.name = "SAM", .sam = true, .read = InputForm::Text, .push = push_sam_text, .plan = slimm_host_text_ranges, .planned = "text", .header_32bit = false},
     {.name = "bzip2", .sam = true, .read = InputForm::Streamed, .push = slimm_push_bzip2_sam_bytes, .plan = slimm_host_bzip2_ranges,
      .planned = "bzip2 streams", .slack = slimm_bzip2_split_slack, .announce_range = true},
-    {.name = "gzip", .sam = true, .read = InputForm::Streamed, .push = slimm_push_gzip_sam_bytes, .planned = "gzip stream",
-     .wide_header_by_host = true, .end_line = gzip_end_line},
+    {.name = "gzip", .sam = true, .read = InputForm::Streamed, .push = slimm_push_gzip_sam_bytes, .plan = slimm_host_gzip_ranges,
+     .planned = "gzip blocks", .wide_header_by_host = true, .announce_bits = slimm_set_gzip_range, .window_pass = slimm_set_gzip_window_pass,
+     .windows = slimm_group_gzip_windows, .may_cut = gzip_may_cut, .end_line = gzip_end_line},
     {.name = "zstd", .sam = true, .read = InputForm::Streamed, .push = slimm_push_zstd_sam_bytes, .plan = slimm_host_zstd_ranges,
      .planned = "zstd frames", .wide_header_by_host = true, .announce_range = true, .may_cut = zstd_may_cut, .end_line = zstd_end_line},
     {.name = "xz", .article = "an", .sam = true, .read = InputForm::Streamed, .push = slimm_push_xz_sam_bytes, .plan = slimm_host_xz_ranges,
@@ -1238,6 +1273,7 @@ struct SplitMember {
     uint32_t index = 0, header_skip = 0;   // (header_skip: member 0's, the header's inflated or decoded bytes)
     bool file_last = false;
     uint64_t begin = 0, range_end = 0, read_end = 0;
+    uint64_t begin_bit = 0, end_bit = 0;   // a form cut at bits (announce_bits): the range itself; [begin, range_end) are the bytes that hold it
     int note = -1;   // what the form's range_note said of `begin` (xz: the check kind of the stream around it)
     int fd = -1;
     unsigned threads = 1;
@@ -1301,10 +1337,12 @@ struct SplitMember {
         rc = code;
         err = "member " + std::to_string(index) + ": " + e;
     }
-    void run(const char* const* names) {
+    void run(const char* const* names, bool window_pass = false) {
         int r = form->sam ? slimm_set_reference_names(ctx, names) : SLIMM_OK;
         if (r == SLIMM_OK) r = slimm_set_input_mid_file(ctx, index > 0 ? 1 : 0, file_last ? 0 : 1);
         if (r == SLIMM_OK && form->announce_range) r = slimm_set_input_range(ctx, begin, range_end);
+        if (r == SLIMM_OK && form->announce_bits) r = form->announce_bits(ctx, begin_bit, end_bit);
+        if (r == SLIMM_OK && form->window_pass) r = form->window_pass(ctx, window_pass ? 1 : 0);
         if (r == SLIMM_OK && form->announce_note) r = form->announce_note(ctx, note);
         if (r == SLIMM_OK) r = slimm_set_input_size_hint(ctx, range_end - begin);
         if (r != SLIMM_OK) return failed(r, slimm_last_error(ctx));
@@ -1357,7 +1395,7 @@ int read_split(slimm_group* grp, uint32_t G, const std::string& path, const Inpu
         why = std::string("the file's ") + form.planned + " could not be planned into ranges";
         return SLIMM_E_INVALID;
     }
-    const uint64_t slack = form.slack ? form.slack() : 0u;
+    const uint64_t slack = form.slack ? form.slack() : 0u, file_size = form.announce_bits ? off[G] / 8u : off[G];
     std::vector<const char*> name_ptrs;
     for (const std::string& nm : names) name_ptrs.push_back(nm.c_str());
     const int fd = open(path.c_str(), O_RDONLY);
@@ -1374,12 +1412,16 @@ int read_split(slimm_group* grp, uint32_t G, const std::string& path, const Inpu
         M.ctx = ctxs[i] = slimm_group_context(grp, i);
         M.header_skip = i == 0 ? static_cast<uint32_t>(header_bytes) : 0u;
         M.begin = off[i], M.range_end = off[i + 1];
+        if (form.announce_bits) {   // (neighbours share at most one byte)
+            M.begin_bit = off[i], M.end_bit = off[i + 1];
+            M.begin = off[i] / 8u, M.range_end = (off[i + 1] + 7u) / 8u;
+        }
         if (form.range_note && form.range_note(path.c_str(), M.begin, &M.note) != SLIMM_OK) {
             close(fd);
             why = std::string("the file's ") + form.planned + " could not be planned into ranges";
             return SLIMM_E_INVALID;
         }
-        M.read_end = std::min<uint64_t>(off[G], off[i + 1] + (M.file_last ? 0u : slack));
+        M.read_end = std::min<uint64_t>(file_size, M.range_end + (M.file_last ? 0u : slack));
         M.threads = std::max(1u, cores / G);
         M.cap = std::max<size_t>(1u << 20, G <= 2 ? window_cap : window_cap * 2 / G);
         for (auto& b : M.buf)
@@ -1389,6 +1431,26 @@ int read_split(slimm_group* grp, uint32_t G, const std::string& path, const Inpu
                 return SLIMM_E_INVALID;
             }
     }
+    if (form.window_pass) {   // every member but the last reads its range once for its last 32 768 symbols alone; then they are handed on
+        const auto t0 = std::chrono::steady_clock::now();
+        std::vector<std::thread> th;
+        for (uint32_t i = 0; i + 1u < G; ++i) th.emplace_back([&m, i, &name_ptrs] { m[i].run(name_ptrs.data(), true); });
+        for (auto& t : th) t.join();
+        const double pass_ms = SplitMember::ms(t0);
+        int rc = SLIMM_OK;
+        for (uint32_t i = 0; i + 1u < G && rc == SLIMM_OK; ++i)
+            if ((rc = m[i].rc) != SLIMM_OK) why = m[i].err;
+        const auto t1 = std::chrono::steady_clock::now();
+        if (rc == SLIMM_OK && (rc = form.windows(grp)) != SLIMM_OK) why = slimm_group_last_error(grp);
+        if (g_trace)
+            fprintf(stderr, "%s%s window pass: %u members read their ranges in %.2f ms, the windows handed on in %.2f ms\n", head, form.name, G - 1u,
+                    pass_ms, SplitMember::ms(t1));
+        if (rc != SLIMM_OK) {
+            close(fd);
+            return rc;
+        }
+        for (SplitMember& M : m) M.records = 0, M.pread_ms = M.push_ms = M.last_ms = 0;
+    }
     {
         std::vector<std::thread> th;
         for (SplitMember& M : m) th.emplace_back([&M, &name_ptrs] { M.run(name_ptrs.data()); });
@@ -1397,7 +1459,7 @@ int read_split(slimm_group* grp, uint32_t G, const std::string& path, const Inpu
     close(fd);
     for (uint32_t i = 0; i < G && g_trace; ++i)
         fprintf(stderr, "%ssplit member %u: bytes [%llu, %llu) of %llu, %llu records, pread %.2f ms, push %.2f ms, last push (wait) %.2f ms\n", head, i,
-                static_cast<unsigned long long>(off[i]), static_cast<unsigned long long>(off[i + 1]), static_cast<unsigned long long>(off[G]),
+                static_cast<unsigned long long>(m[i].begin), static_cast<unsigned long long>(m[i].range_end), static_cast<unsigned long long>(m[G - 1u].range_end),
                 static_cast<unsigned long long>(m[i].records), m[i].pread_ms, m[i].push_ms, m[i].last_ms);
     for (uint32_t i = 0; i < G; ++i)
         if (m[i].rc != SLIMM_OK) {
@@ -1576,7 +1638,8 @@ std::unique_ptr<Reading> set_up(Session& S, const std::string& path, bool any_or
     // not push raw -- --host-decode, pipes ... -- the host reader deals)
     const bool may_split = options.split_input && options.devices.size() > 1 && !options.host_decode && !options.verify_grouping && !options.packed_records;
     F->split_input = may_split && cut_by_byte_range(bam, path, static_cast<uint32_t>(options.devices.size()), true);
-    // (a form that is not cut whenever it is asked: gzip never; a zstd file of one frame, or one whose members would get less
+    // (a form that is not cut whenever it is asked: a gzip file of one dynamic block, or one whose members would get less bytes
+    // than its floor; a zstd file of one frame, or one whose members would get less
     // bytes than its floor; an xz file the host reader takes, or one whose members would get fewer blocks than its floor; or
     // the host decoders were asked for)
     const InputForm& form = form_of(bam);
@@ -1748,8 +1811,10 @@ Outcome run_group(Session& S, Reading& F, const std::vector<int>& devs, bool spl
     bool split_read = false;
     if (split) {   // every member its own byte range (read_split); what fails there goes through member 0 after all
         std::string why;
-        const int src = read_split(grp.get(), static_cast<uint32_t>(devs.size()), F.path, form_of(F.bam), F.bam.ref_names(),
-                                   F.bam.header_bytes(), RecordPump::raw_cap(), F.split_bufs, S.trace_head(), why);
+        // (a streamed codec's header is counted in decoded text bytes: for gzip header_bytes() does not say them)
+        const InputForm& split_form = form_of(F.bam);
+        const int src = read_split(grp.get(), static_cast<uint32_t>(devs.size()), F.path, split_form, F.bam.ref_names(),
+                                   split_form.read == InputForm::Streamed ? F.bam.text_header_bytes() : F.bam.header_bytes(), RecordPump::raw_cap(), F.split_bufs, S.trace_head(), why);
         F.trace.mark("split: read + decode + stitch");
         if (src == SLIMM_E_REGROUP) return Outcome::ReadAgainAnyOrder;
         if (src != SLIMM_OK && for_cap && classify(why.c_str()) == PushError::RecordCap) return Outcome::MoreMembers;
@@ -1823,7 +1888,7 @@ Outcome run_context(Session& S, Reading& F) {
     S.err() << "[" << F.watch.lap() << " secs]" << std::endl;
 
     S.err() << "Analysing alignments, reads and references ....... ";
-    // (zstd and xz SAM: whether the file can be cut is asked only once the cap is met -- the plan reads the file; the floor is
+    // (gzip, zstd and xz SAM: whether the file can be cut is asked only once the cap is met -- the plan reads the file; the floor is
     // not consulted here.  A zstd file of one frame, an xz file of one block behind the header's or one that the host reader
     // took -- fewer than xz_device_blocks() blocks -- cannot be cut and ends at the cap, as it did)
     const InputForm& form = form_of(F.bam);

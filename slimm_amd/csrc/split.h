@@ -29,6 +29,16 @@ int split_zstd_ends(slimm_ctx* const* members, uint32_t n, uint32_t* bad);
 // front of its own blocks' records).  SLIMM_OK, or the code with the message on member *bad
 bool split_is_xz(const slimm_ctx* c);
 int split_xz_streams(slimm_ctx* const* members, uint32_t n, uint32_t* bad);
+// gzip SAM.  split_gz_windows, between the members' window pass and their text pass (slimm_group_gzip_windows), left to right:
+// member k's chain ended on member k + 1's first bit; its final 16-bit window, resolved against the bytes in front of its
+// own range (a tiny kernel on its device), becomes the 32 768 bytes in front of member k + 1's, copied device to device, with
+// how many of them belong to the open gzip member; then every member's file state is fresh for the text pass, its
+// announcements kept.  split_gz_chains, in the stitch on host scalars: every chain ended on its range's end and the text pass
+// reproduced the window pass's end bit and text length (SLIMM_E_SPLIT), and the CRC register and length of a gzip member
+// that lies over cuts, folded left to right, are its trailer's (SLIMM_E_INVALID, the single context's words)
+bool split_is_gzip(const slimm_ctx* c);
+int split_gz_windows(slimm_ctx* const* members, uint32_t n, uint32_t* bad);
+int split_gz_chains(slimm_ctx* const* members, uint32_t n, uint32_t* bad);
 // the head of `right` as one more window of `left` (final: it must end with a complete record, else SLIMM_E_SPLIT)
 int split_append_head(slimm_ctx* left, slimm_ctx* right, bool final, uint64_t* n_records);
 // `right`'s first record against the last record of `left` (its carry): the same name clears the run-start bit and

@@ -80,9 +80,22 @@ struct WindowPipeline {
         DevBuf<gz::Chunk> chunks;
         DevBuf<uint16_t> sym;
         DevBuf<uint2> piece;
+        // a byte range of a split file: the window pass's 16-bit windows (slot k as win's: a byte, or a marker into the
+        // 32 768 bytes in front of the RANGE), and the 32 768 bytes in front of the range that the member on the left
+        // installed for the text pass (slimm_group_gzip_windows; 64 KiB: not counted, not given back between the passes)
+        DevBuf<uint16_t> win16;
+        DevBuf<uint8_t> front, applied;
         template <typename F>
-        void each_held(F&& f) { f(comp), f(win), f(d_cand), f(flag), f(walk), f(chunks), f(sym), f(piece); }
+        void each_held(F&& f) { f(comp), f(win), f(d_cand), f(flag), f(walk), f(chunks), f(sym), f(piece), f(win16); }
     } gz;
+    // gzip SAM by byte range, what a member keeps between its window pass and its text pass (slimm_group_gzip_windows), and
+    // the text pass must reproduce: where its chain ended (the file's bit) and its text's length
+    struct GzipPass {
+        bool done = false;        // the window pass ran to its last push
+        bool has_front = false;   // gz.front holds the bytes in front of the range, front_len of them valid
+        uint32_t front_len = 0;
+        uint64_t end_bit = 0, text = 0;
+    } gz_pass;
     // the counters of the gzip file read last (slimm_get_gzip_stats): they outlive the file's state
     enum { kGzMembers, kGzChunks, kGzCandidates, kGzDropped, kGzStored, kGzFixed, kGzDynamic, kGzResolved, kGzRounds, kGzText, kGzCompressed, kGzForced, kGzStats };
     uint64_t gz_stats[kGzStats] = {};
@@ -132,6 +145,10 @@ struct WindowPipeline {
         // xz SAM: the check kind of the stream among whose blocks the range starts (slimm_set_xz_range_check; -1: the range
         // starts at a stream header, which tells it)
         int xz_check = -1;
+        // gzip SAM: the range in BITS of the file (slimm_set_gzip_range; the member reads the bytes that hold them), and
+        // whether the pushes to come are the window pass (slimm_set_gzip_window_pass)
+        bool gz_range = false, gz_window_pass = false;
+        uint64_t gz_begin_bit = 0, gz_end_bit = 0;
     } announced;
 
     // ---- this file: reset as a whole, by end_file alone -- a new member needs its initialiser and nothing else
@@ -240,6 +257,20 @@ struct WindowPipeline {
             uint64_t len = 0;
             bool carried = false;    // slot 0 of the window scratch holds the last 32 768 bytes of the text so far
             std::vector<gz::Chunk> ready;
+            // a byte range of a split file (Announced::gz_range).  A range that starts inside the file starts among a
+            // member's blocks: `front` bytes of that member lie in front of it (32 768 assumed until the stitch of the
+            // windows knows), crc is a register from 0 and len the range's share (`partial`) until the member's trailer,
+            // which it cannot check: what it read there is kept for the stitch (split.hip: split_gz_chains)
+            bool window_pass = false;   // this file's pushes are the window pass: no text, no CRC
+            bool partial = false;
+            bool range_done = false;    // the chain stands on the range's end bit
+            uint32_t front = 0;
+            uint64_t text = 0;          // text bytes of the range so far
+            struct LeftTrailer {
+                bool has = false;
+                uint32_t partial_crc = 0, crc32 = 0, isize = 0;
+                uint64_t partial_len = 0, at = 0;   // (at: the trailer's file offset)
+            } left;
         } gz;
         // zstd SAM, the host's side: where in the container stream.bit is (zstd_walk.h: the stage, the frame's header and
         // file offset, the frames so far) and what the frame's blocks hand on (the descriptions a block may repeat, the
@@ -393,6 +424,9 @@ int gz_round(slimm_ctx* c, bool last);
 bool gz_next_window(const slimm_ctx* c, uint64_t cap, uint64_t* n);
 int gz_emit(slimm_ctx* c, uint8_t* dst, uint64_t cap, uint64_t* n_out, uint8_t* last_byte);
 void gz_trace_file(const slimm_ctx* c);
+// (a byte range of a split file, between its two passes -- split.hip: split_gz_windows) out[i] = the byte that the range's
+// final 16-bit window win16 names: its own, or byte m of the 32 768 in `front` of the range
+void launch_gz_window_apply(hipStream_t st, const uint16_t* win16, const uint8_t* front, uint8_t* out);
 // zstd_decode.hip (slimm_push_zstd_sam_bytes): zs_round takes the container's items from zs::Walker (zstd_walk.h) -- the
 // format's rules are there, the range rules in RoundCursor above --, plans the whole blocks of stream.pend up to the round's
 // text cap, decodes their literals and sequences on the device and leaves the round's blocks, with their text lengths, in

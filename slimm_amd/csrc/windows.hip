@@ -53,6 +53,7 @@ int WindowPipeline::end_file(slimm_ctx* c) {
     // (a streamed codec: the next file sizes its own decode scratch; what the host held of this one's bytes goes)
     file = File{};
     announced = Announced{};
+    gz_pass = GzipPass{};
     if (held_bytes() > kWindowKeepAcrossFiles) {   // (a large file's windows: the next file sizes its own)
         (void)hipSetDevice(c->device);
         each_held([](auto& b) { b.release(); });
@@ -404,7 +405,8 @@ int check_push(slimm_ctx* c, Push& p) {
     const bool mid = c->win.announced.starts_mid || c->win.announced.ends_mid;
     if (F.active && mine != p.codec)   // (two codecs: the text names the first of them in Codec's order)
         return fail(c, SLIMM_E_INVALID, "%s SAM bytes and the other forms do not mix within a file", codec_of(named).name);
-    if (K.name && !K.cut_by_range && mid) return fail(c, SLIMM_E_INVALID, "%s %s stream is not cut by byte range", K.article ? K.article : "a", K.name);
+    const bool gz_range = p.codec == Codec::Gzip && c->win.announced.gz_range;   // (gzip is cut at announced bits only)
+    if (K.name && !K.cut_by_range && mid && !gz_range) return fail(c, SLIMM_E_INVALID, "%s %s stream is not cut by byte range", K.article ? K.article : "a", K.name);
     if (K.name && K.cut_at_frames && mid && !c->win.announced.has_range)
         return fail(c, SLIMM_E_INVALID, "%s %s stream is not cut by byte range unless its range is announced (slimm_set_input_range) and starts at a %s",
                     K.article ? K.article : "a", K.name, K.cut_unit ? K.cut_unit : "frame");
@@ -436,6 +438,19 @@ int open_file(slimm_ctx* c, const Push& p) {
     W.file.stream.skip_left = K.name ? p.skip : 0u;
     if (K.stats) std::fill(K.stats(W), K.stats(W) + K.n_stats, 0ull);
     if (K.cut_by_range && W.announced.has_range) W.file.stream.base = W.announced.range_begin;   // (errors name the file's bytes)
+    if (p.codec == Codec::Gzip && W.announced.gz_range) {
+        const WindowPipeline::Announced& A = W.announced;
+        File::Gzip& Z = W.file.gz;
+        W.file.stream.base = A.gz_begin_bit >> 3;
+        Z.window_pass = A.gz_window_pass;
+        if (A.starts_mid) {   // (among a member's blocks: no header is expected, and its trailer is not this range's to check)
+            W.file.stream.bit = A.gz_begin_bit & 7u;
+            Z.stage = File::Gzip::Deflate;
+            Z.partial = true;
+            Z.crc = 0;
+            Z.front = Z.window_pass || !W.gz_pass.has_front ? gz::kWindow : W.gz_pass.front_len;
+        }
+    }
     c->marked = marked;
     c->has_check = !marked;
     c->packed = false;
@@ -743,6 +758,22 @@ int slimm_set_input_range(slimm_ctx* c, uint64_t begin, uint64_t end) {
     c->win.announced.has_range = true;
     c->win.announced.range_begin = begin;
     c->win.announced.range_end = end;
+    return SLIMM_OK;
+}
+int slimm_set_gzip_range(slimm_ctx* c, uint64_t begin_bit, uint64_t end_bit) {
+    if (!c) return SLIMM_E_INVALID;
+    if (c->win.file.active) return fail(c, SLIMM_E_INVALID, "slimm_set_gzip_range: before the range's first window");
+    if (begin_bit > end_bit) return fail(c, SLIMM_E_INVALID, "slimm_set_gzip_range: a range ends at or behind its start");
+    c->win.announced.gz_range = true;
+    c->win.announced.gz_begin_bit = begin_bit;
+    c->win.announced.gz_end_bit = end_bit;
+    return SLIMM_OK;
+}
+int slimm_set_gzip_window_pass(slimm_ctx* c, int on) {
+    if (!c) return SLIMM_E_INVALID;
+    if (c->win.file.active) return fail(c, SLIMM_E_INVALID, "slimm_set_gzip_window_pass: before the range's first window");
+    if (on && !c->win.announced.gz_range) return fail(c, SLIMM_E_INVALID, "slimm_set_gzip_window_pass: slimm_set_gzip_range first");
+    c->win.announced.gz_window_pass = on != 0;
     return SLIMM_OK;
 }
 int slimm_set_xz_range_check(slimm_ctx* c, int check) {

@@ -873,7 +873,7 @@ class SlimmGroup:
             e = min(n, s + step)
             self._check(self.L.slimm_group_push_records_marked(self.g, _p(w[s:e]), _p(rec.begin_pos[s:e]), e - s))
 
-    SPLIT_FORMS = ("bam", "sam", "bgzf_sam", "bzip2_sam", "zstd_sam", "xz_sam")
+    SPLIT_FORMS = ("bam", "sam", "bgzf_sam", "bzip2_sam", "zstd_sam", "xz_sam", "gzip_sam")
 
     def push_split(self, data, form: str, skip: int = 0, window: int = 0, offsets=None, xz_checks=None):
         """One file split by byte range, every member its own (include/slimm_hip.h, "ONE FILE SPLIT BY BYTE RANGE"): GROUPED by
@@ -889,7 +889,11 @@ class SlimmGroup:
         planner cuts at frame starts only, and a cut anywhere else is SLIMM_E_SPLIT.  An xz member announces its range and, beside
         it, the check kind of the stream its range starts in (slimm_host_xz_check_at -> slimm_set_xz_range_check; `xz_checks`:
         the n kinds to tell instead), and pushes exactly its range.  `offsets`: the n + 1
-        offsets to use instead of the planner's (bzip2 is cut at any byte behind the header's block).  Returns (the n + 1 offsets, the records every member decoded before the stitch)."""
+        offsets to use instead of the planner's (bzip2 is cut at any byte behind the header's block).  "gzip_sam"
+        (gzip-compressed SAM text): the offsets are BITS (slimm_host_gzip_ranges); every member announces them with
+        slimm_set_gzip_range and pushes the bytes that hold its bits twice -- the window pass (slimm_set_gzip_window_pass; the
+        last member does without), slimm_group_gzip_windows, then the text pass; a plan with fewer than two ranges that are
+        not empty raises E_INVALID "a gzip stream is not cut by byte range".  Returns (the n + 1 offsets, the records every member decoded before the stitch)."""
         # (the planners, the announcements and the pushes are the same for both orders)
         import os
         import tempfile
@@ -898,7 +902,7 @@ class SlimmGroup:
         G = len(self.devices)
         offs = (C.c_uint64 * (G + 1))()
         plan = {"sam": self.L.slimm_host_text_ranges, "bzip2_sam": self.L.slimm_host_bzip2_ranges, "zstd_sam": self.L.slimm_host_zstd_ranges,
-                "xz_sam": self.L.slimm_host_xz_ranges}.get(form, self.L.slimm_host_bgzf_ranges)
+                "xz_sam": self.L.slimm_host_xz_ranges, "gzip_sam": self.L.slimm_host_gzip_ranges}.get(form, self.L.slimm_host_bgzf_ranges)
         checks = list(xz_checks) if xz_checks is not None else None
 
         def planned(path):   # the offsets, unless given; an xz file: the check kind at every range's start, unless given
@@ -933,6 +937,25 @@ class SlimmGroup:
         if rc != capi.OK:
             raise capi.SlimmError(rc, "the file could not be planned into ranges")
         counts = []
+        if form == "gzip_sam":
+            if sum(1 for a, b in zip(offs, offs[1:]) if b > a) < 2:
+                raise capi.SlimmError(capi.E_INVALID, "a gzip stream is not cut by byte range: the plan leaves one member all of the file")
+            members = [self.member(i) for i in range(G)]
+
+            def announce_and_push(i, window_pass):
+                m = members[i]
+                m.set_reference_names(self.w.ref_names)
+                m._check(self.L.slimm_set_input_mid_file(m.ctx, 1 if i > 0 else 0, 1 if i + 1 < G else 0))
+                m._check(self.L.slimm_set_gzip_range(m.ctx, offs[i], offs[i + 1]))
+                m._check(self.L.slimm_set_gzip_window_pass(m.ctx, 1 if window_pass else 0))
+                return m.push_gzip_sam_bytes(blob[offs[i] // 8:(offs[i + 1] + 7) // 8], skip=skip if i == 0 else 0, window=window)
+
+            for i in range(G - 1):
+                announce_and_push(i, True)
+            self._check(self.L.slimm_group_gzip_windows(self.g))
+            counts = [announce_and_push(i, False) for i in range(G)]
+            self._check(self.L.slimm_group_stitch_ranges(self.g))
+            return list(offs), counts
         for i in range(G):
             m = self.member(i)
             if form != "bam":
