@@ -44,7 +44,7 @@ __global__ __launch_bounds__(256) void k_bz2_find(const uint8_t* __restrict__ b,
 
 // A range that starts inside the file (a file split by byte range): the first end-of-stream magic whose first bit lies in
 // [bit_lo, bit_hi) -- the range's first element may be a marker, which no block decode vouches for; the stitch does
-// (split.hip: split_bz2_chains).  *first: ~0 before, the smallest such bit after
+// (split_bz2_chains, below).  *first: ~0 before, the smallest such bit after
 __global__ __launch_bounds__(256) void k_bz2_first_eos(const uint8_t* __restrict__ b, uint64_t n_bytes, uint64_t bit_lo, uint64_t bit_hi,
                                                         unsigned long long* __restrict__ first) {
     const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
@@ -558,6 +558,54 @@ int bz2_emit(slimm_ctx* c, uint8_t* dst, uint64_t cap, uint64_t* n_out, uint8_t*
         return BZ2_FAIL("block at byte %llu: %s", static_cast<unsigned long long>(b.at), bz2::status_text(bz2::kBadCrc));
     }
     Z.ready_pos += n_blocks;
+    return SLIMM_OK;
+}
+
+// ---- a file split by byte range over a group's members: this codec's check in slimm_group_stitch_ranges (windows.h)
+int split_bz2_chains(slimm_ctx* const* members, uint32_t n, uint32_t* bad) {
+    auto rotl = [](uint32_t v, uint32_t k) {
+        k &= 31u;
+        return k ? (v << k) | (v >> (32u - k)) : v;
+    };
+    // the chain so far: where it ended, inside a stream of which level and combined CRC -- member 0's to begin with
+    uint32_t left = 0;
+    const WindowPipeline::File::Bzip2* L = &members[0]->win.file.bz2;
+    bool in_stream = L->in_stream, at_file_end = L->chain.at_file_end;
+    uint32_t level = L->level, combined = L->combined;
+    uint64_t end_bit = L->chain.end_bit;
+    for (uint32_t k = 1; k < n; ++k) {
+        slimm_ctx* c = members[k];
+        const WindowPipeline::File::Bzip2& Z = c->win.file.bz2;
+        const WindowPipeline::File::Bzip2::Chain& K = Z.chain;
+        if (!K.any) continue;   // (no block or marker starts in this range)
+        *bad = k;
+        if (!in_stream || end_bit != K.first_bit)
+            return fail(c, SLIMM_E_SPLIT, "bzip2: the chain of member %u ends at bit %llu%s, this range's first block was found at bit %llu", left,
+                        static_cast<unsigned long long>(end_bit), in_stream ? "" : " (behind the last stream)",
+                        static_cast<unsigned long long>(K.first_bit));
+        if (K.first_max_n > level * 100000u)
+            return fail(c, SLIMM_E_INVALID, "bzip2-compressed input is not supported unless it decodes: block at byte %llu: %s",
+                        static_cast<unsigned long long>(K.first_max_at), bz2::status_text(bz2::kTooLong));
+        if (K.has_eos) {
+            if ((rotl(combined, K.first_blocks) ^ K.first_combined) != K.eos_crc)
+                return fail(c, SLIMM_E_INVALID, "bzip2-compressed input is not supported unless it decodes: end-of-stream marker at byte %llu: combined CRC mismatch",
+                            static_cast<unsigned long long>(K.eos_at));
+            level = Z.level;
+            combined = Z.combined;
+        } else {   // (no marker in this range: the stream goes on into the next)
+            combined = rotl(combined, K.first_blocks) ^ Z.combined;
+        }
+        in_stream = Z.in_stream;
+        at_file_end = K.at_file_end;
+        end_bit = K.end_bit;
+        left = k;
+    }
+    // the last chain ended the streams at the file's end (the file's last member checks that as one context does; a member
+    // in front of it has seen every byte behind its last marker)
+    *bad = left;
+    if (left + 1 < n && !(at_file_end && !in_stream))
+        return fail(members[left], SLIMM_E_SPLIT, "bzip2: the chain of member %u ends at bit %llu, and no range behind it holds a block", left,
+                    static_cast<unsigned long long>(end_bit));
     return SLIMM_OK;
 }
 

@@ -73,6 +73,12 @@ inline bool forced(const char* key, long* value = nullptr) {
     if (value) *value = t ? atol(t) : 1;
     return true;
 }
+// a key's forced value, or `fallback`: only a value of at least `least` counts (0: a floor, which 0 switches off; 1: a size
+// or a count that 0 would make meaningless)
+inline unsigned long long forced_or(const char* key, unsigned long long fallback, long least = 0) {
+    long v = 0;
+    return forced(key, &v) && v >= least ? static_cast<unsigned long long>(v) : fallback;
+}
 
 // the most records one context takes: below 2^31 (32-bit record indices), lower with SLIMM_FORCE record_cap=N
 inline unsigned long long record_cap() {

@@ -708,29 +708,12 @@ int slimm_group_stitch_ranges(slimm_group* g) {
     static const bool trace = slimm::traced("cli");
     std::vector<slimm::SplitRange> r(n);
     for (uint32_t i = 0; i < n; ++i) GTRY(g, i, slimm::split_range(g->ctx[i], &r[i]));
-    if (slimm::split_is_bzip2(g->ctx[0])) {   // (the chains of blocks first: host scalars only)
+    {   // (first, on host scalars only: what member 0's codec holds the members' ranges to)
         uint32_t bad = 0;
-        const int rc = slimm::split_bz2_chains(g->ctx.data(), n, &bad);
-        if (rc == SLIMM_E_SPLIT) return gfail(g, SLIMM_E_SPLIT, "cut in front of member %u: %s", bad, slimm_last_error(g->ctx[bad]));
-        if (rc < 0) return member_failed(g, bad, rc, "the chain of blocks across a cut");
-    }
-    if (slimm::split_is_zstd(g->ctx[0])) {   // (every member's frames ended where its range does: host scalars only)
-        uint32_t bad = 0;
-        const int rc = slimm::split_zstd_ends(g->ctx.data(), n, &bad);
-        if (rc == SLIMM_E_SPLIT) return gfail(g, SLIMM_E_SPLIT, "the range of member %u: %s", bad, slimm_last_error(g->ctx[bad]));
-        if (rc < 0) return member_failed(g, bad, rc, "the frames of a range");
-    }
-    if (slimm::split_is_gzip(g->ctx[0])) {   // (every chain ended on its range's end, a gzip member over cuts matches its trailer)
-        uint32_t bad = 0;
-        const int rc = slimm::split_gz_chains(g->ctx.data(), n, &bad);
-        if (rc == SLIMM_E_SPLIT) return gfail(g, SLIMM_E_SPLIT, "the range of member %u: %s", bad, slimm_last_error(g->ctx[bad]));
-        if (rc < 0) return member_failed(g, bad, rc, "a gzip member across a cut");
-    }
-    if (slimm::split_is_xz(g->ctx[0])) {   // (every member's walker stopped where its range does, and a stream over cuts matches its index)
-        uint32_t bad = 0;
-        const int rc = slimm::split_xz_streams(g->ctx.data(), n, &bad);
-        if (rc == SLIMM_E_SPLIT) return gfail(g, SLIMM_E_SPLIT, "the range of member %u: %s", bad, slimm_last_error(g->ctx[bad]));
-        if (rc < 0) return member_failed(g, bad, rc, "the blocks of a stream across a cut");
+        const char *split_words = nullptr, *noun = nullptr;
+        const int rc = slimm::split_codec_stitch(g->ctx.data(), n, &bad, &split_words, &noun);
+        if (rc == SLIMM_E_SPLIT) return gfail(g, SLIMM_E_SPLIT, split_words, bad, slimm_last_error(g->ctx[bad]));
+        if (rc < 0) return member_failed(g, bad, rc, noun);
     }
     std::vector<uint32_t> left_of(n, 0);
     uint32_t left = 0;
@@ -784,11 +767,11 @@ int slimm_group_stitch_ranges(slimm_group* g) {
     return SLIMM_OK;
 }
 
-// gzip SAM by byte range, between the members' window pass and their text pass (split.hip: split_gz_windows)
+// gzip SAM by byte range, between the members' window pass and their text pass (split.hip: split_codec_windows)
 int slimm_group_gzip_windows(slimm_group* g) {
     if (!g) return SLIMM_E_INVALID;
     uint32_t bad = 0;
-    const int rc = slimm::split_gz_windows(g->ctx.data(), static_cast<uint32_t>(g->ctx.size()), &bad);
+    const int rc = slimm::split_codec_windows(g->ctx.data(), static_cast<uint32_t>(g->ctx.size()), &bad);
     if (rc == SLIMM_E_SPLIT) return gfail(g, SLIMM_E_SPLIT, "the range of member %u: %s", bad, slimm_last_error(g->ctx[bad]));
     if (rc < 0) return member_failed(g, bad, rc, "the windows across a cut");
     return SLIMM_OK;

@@ -583,4 +583,150 @@ void gz_trace_file(const slimm_ctx* c) {
             (unsigned long long)s[4], (unsigned long long)s[5], (unsigned long long)s[6], (unsigned long long)s[7], (unsigned long long)s[9]);
 }
 
+// ---- a file split by byte range over a group's members: this codec's check in slimm_group_stitch_ranges (windows.h)
+namespace {
+// where a member's chain stands, as a bit of the file
+uint64_t gz_chain_end(const slimm_ctx* c) {
+    const WindowPipeline::Announced& A = c->win.announced;
+    const WindowPipeline::File::Stream& T = c->win.file.stream;
+    return A.gz_begin_bit == A.gz_end_bit ? A.gz_begin_bit : T.base * 8u + T.bit;
+}
+int gz_chain_ended(slimm_ctx* c, uint32_t k, uint64_t want) {
+    if (c->win.file.gz.range_done && gz_chain_end(c) == want) return SLIMM_OK;
+    return fail(c, SLIMM_E_SPLIT, "gzip: the chain of member %u ended at bit %llu, its range at bit %llu", k,
+                static_cast<unsigned long long>(gz_chain_end(c)), static_cast<unsigned long long>(want));
+}
+}  // namespace
+
+int split_gz_windows(slimm_ctx* const* members, uint32_t n, uint32_t* bad) {
+    using GF = WindowPipeline::File::Gzip;
+    std::vector<bool> ran(n, false);
+    for (uint32_t k = 0; k < n; ++k) {
+        slimm_ctx* c = members[k];
+        const WindowPipeline::File& F = c->win.file;
+        *bad = k;
+        // (the last member, which may do without the window pass, may announce its range behind this call)
+        if (!c->win.announced.gz_range && (k + 1u < n || F.active)) return fail(c, SLIMM_E_INVALID, "a range of a gzip file: slimm_set_gzip_range tells where it lies");
+        ran[k] = F.active && F.closed && c->win.file.stream.codec == WindowPipeline::File::Codec::Gzip && F.gz.window_pass;
+        if (F.active && !ran[k]) return fail(c, SLIMM_E_INVALID, "slimm_group_gzip_windows: behind the members' window pass (slimm_set_gzip_window_pass), pushed to its end");
+        if (!ran[k] && k + 1u < n) return fail(c, SLIMM_E_INVALID, "slimm_group_gzip_windows: only the last member may do without the window pass");
+    }
+    bool open = false;   // a gzip member lies over the cut behind member k
+    for (uint32_t k = 0; k + 1u < n; ++k) {
+        slimm_ctx *c = members[k], *r = members[k + 1u];
+        WindowPipeline& W = c->win;
+        WindowPipeline::Gzip& S = W.gz;
+        const WindowPipeline::Announced &A = W.announced, &AR = r->win.announced;
+        const GF& Z = W.file.gz;
+        const bool empty = A.gz_begin_bit == A.gz_end_bit;
+        *bad = k;
+        const bool told = AR.gz_range;
+        if (told && A.gz_end_bit != AR.gz_begin_bit)
+            return fail(c, SLIMM_E_INVALID, "slimm_group_gzip_windows: member %u's range ends at bit %llu, member %u's begins at bit %llu", k,
+                        static_cast<unsigned long long>(A.gz_end_bit), k + 1u, static_cast<unsigned long long>(AR.gz_begin_bit));
+        SLIMM_TRY(gz_chain_ended(c, k, A.gz_end_bit));
+        uint32_t front_len = 0;
+        if (!empty) {
+            open = Z.stage == GF::Deflate;
+            front_len = static_cast<uint32_t>(std::min<uint64_t>(gz::kWindow, (Z.partial ? W.gz_pass.front_len : 0u) + Z.len));
+            if (!open) front_len = 0;
+        } else {
+            front_len = W.gz_pass.front_len;
+        }
+        if (!open && told && AR.gz_begin_bit != AR.gz_end_bit)
+            return fail(c, SLIMM_E_SPLIT, "gzip: the chain of member %u ended between two gzip members at bit %llu, where member %u's range begins among blocks", k,
+                        static_cast<unsigned long long>(gz_chain_end(c)), k + 1u);
+        // the bytes in front of member k + 1: k's final window, its markers filled from the bytes in front of k
+        (void)hipSetDevice(c->device);
+        HIP_TRY(c, S.front.ensure(gz::kWindow));
+        HIP_TRY(c, S.applied.ensure(gz::kWindow));
+        if (!W.gz_pass.has_front) HIP_TRY(c, hipMemsetAsync(S.front.p, 0, gz::kWindow, c->stream));   // (member 0: nothing in front)
+        if (Z.carried) {
+            launch_gz_window_apply(c->stream, S.win16.p, S.front.p, S.applied.p);
+            HIP_TRY(c, hipGetLastError());
+        } else {   // (no chunk in this range: what lies in front of it lies in front of the next)
+            HIP_TRY(c, hipMemcpyAsync(S.applied.p, S.front.p, gz::kWindow, hipMemcpyDeviceToDevice, c->stream));
+        }
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        (void)hipSetDevice(r->device);
+        HIP_TRY(r, r->win.gz.front.ensure(gz::kWindow));
+        if (r->device == c->device)
+            HIP_TRY(r, hipMemcpyAsync(r->win.gz.front.p, S.applied.p, gz::kWindow, hipMemcpyDeviceToDevice, r->stream));
+        else
+            HIP_TRY(r, hipMemcpyPeerAsync(r->win.gz.front.p, r->device, S.applied.p, c->device, gz::kWindow, r->stream));
+        HIP_TRY(r, hipStreamSynchronize(r->stream));
+        r->win.gz_pass.has_front = true;
+        r->win.gz_pass.front_len = front_len;
+        W.gz_pass.done = true;
+        W.gz_pass.end_bit = gz_chain_end(c);
+        W.gz_pass.text = Z.text;
+    }
+    for (uint32_t k = 0; k < n; ++k) {   // the text pass starts from a fresh file, told what the window pass was told
+        if (!ran[k]) continue;
+        slimm_ctx* c = members[k];
+        *bad = k;
+        if (k + 1u == n) {
+            c->win.gz_pass.done = true;
+            c->win.gz_pass.end_bit = gz_chain_end(c);
+            c->win.gz_pass.text = c->win.file.gz.text;
+        }
+        WindowPipeline::Announced a = c->win.announced;
+        const WindowPipeline::GzipPass p = c->win.gz_pass;
+        a.gz_window_pass = false;
+        (void)hipSetDevice(c->device);
+        SLIMM_TRY(c->win.end_file(c));
+        c->win.announced = a;
+        c->win.gz_pass = p;
+    }
+    return SLIMM_OK;
+}
+
+int split_gz_chains(slimm_ctx* const* members, uint32_t n, uint32_t* bad) {
+    using GF = WindowPipeline::File::Gzip;
+    bool open = false;          // a gzip member lies over the cut in front of member k:
+    uint32_t s = 0;             // its CRC register and its length up to the cut
+    uint64_t len = 0;
+    for (uint32_t k = 0; k < n; ++k) {
+        slimm_ctx* c = members[k];
+        const WindowPipeline::Announced& A = c->win.announced;
+        const WindowPipeline::GzipPass& P = c->win.gz_pass;
+        const GF& Z = c->win.file.gz;
+        const bool empty = A.gz_begin_bit == A.gz_end_bit;
+        *bad = k;
+        if (c->win.file.stream.codec != WindowPipeline::File::Codec::Gzip || !A.gz_range) return fail(c, SLIMM_E_INVALID, "a range of a gzip file: slimm_set_gzip_range tells where it lies");
+        if (Z.window_pass) return fail(c, SLIMM_E_INVALID, "a range of a gzip file: slimm_group_gzip_windows and the text pass come before the stitch");
+        if (k && A.gz_begin_bit != members[k - 1u]->win.announced.gz_end_bit)
+            return fail(c, SLIMM_E_INVALID, "a range of a gzip file: member %u's range begins at bit %llu, member %u's ends at bit %llu", k,
+                        static_cast<unsigned long long>(A.gz_begin_bit), k - 1u, static_cast<unsigned long long>(members[k - 1u]->win.announced.gz_end_bit));
+        if (k + 1u < n) SLIMM_TRY(gz_chain_ended(c, k, A.gz_end_bit));
+        if (P.done && (P.end_bit != gz_chain_end(c) || P.text != Z.text))
+            return fail(c, SLIMM_E_SPLIT, "gzip: the window pass of member %u ended at bit %llu behind %llu bytes of text, its text pass at bit %llu behind %llu", k,
+                        static_cast<unsigned long long>(P.end_bit), static_cast<unsigned long long>(P.text),
+                        static_cast<unsigned long long>(gz_chain_end(c)), static_cast<unsigned long long>(Z.text));
+        if (empty && k) continue;   // (it hands on what it was handed)
+        if (A.starts_mid && k) {
+            if (!open)
+                return fail(c, SLIMM_E_SPLIT, "gzip: member %u's range begins among blocks, and no gzip member lies over the cut in front of it", k);
+            if (Z.left.has) {   // the member's trailer, read here: its parts on the left and this range's against it
+                s = gz::crc_mul(s, gz::crc_x_pow8(Z.left.partial_len)) ^ Z.left.partial_crc;
+                len += Z.left.partial_len;
+                if (Z.left.crc32 != ~s)
+                    return fail(c, SLIMM_E_INVALID, "corrupt gzip stream (%s): the trailer at byte %llu of a member that lies over a cut", gz::status_text(gz::kBadCrc),
+                                static_cast<unsigned long long>(Z.left.at));
+                if (Z.left.isize != static_cast<uint32_t>(len))
+                    return fail(c, SLIMM_E_INVALID, "corrupt gzip stream (%s): the trailer at byte %llu of a member that lies over a cut", gz::status_text(gz::kBadLength),
+                                static_cast<unsigned long long>(Z.left.at));
+            } else {   // (no trailer in this range: both go on)
+                s = gz::crc_mul(s, gz::crc_x_pow8(Z.len)) ^ Z.crc;
+                len += Z.len;
+                continue;
+            }
+        }
+        open = Z.stage == GF::Deflate;
+        s = Z.crc;
+        len = Z.len;
+    }
+    return SLIMM_OK;
+}
+
 }  // namespace slimm

@@ -5,7 +5,7 @@
 // holds, and a walk from there (Huffman codes only, the text counted and thrown away) passes kGzipCutBlocks block
 // boundaries, or a final block, without an error.  The walk reads at most kGzipCutWalk compressed bytes; when they run out
 // the candidate counts if at least one boundary was passed.  Nothing the walk cannot see is trusted: a cut it took can still
-// be false, and the members and the stitch decide (gzip_decode.hip, split.hip: split_gz_chains).
+// be false, and the members and the stitch decide (gzip_decode.hip: the rounds, split_gz_chains).
 #pragma once
 #include <memory>
 #include <vector>

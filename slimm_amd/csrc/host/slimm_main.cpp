@@ -187,6 +187,7 @@ SLIMM_FORWARD(int, slimm_get_record_filter_stats, (slimm_ctx* a, uint64_t* b), (
 #include "xz.hpp"
 #include "../force.h"
 #include "../gzip_plan.h"
+#include "../split_plan.h"
 #include "sldb.hpp"
 
 namespace {
@@ -709,8 +710,12 @@ struct InputForm {
     // ... and what a range that starts at `offset` cannot see of the file in front of it, beside its range (none: nothing)
     int (*range_note)(const char* path, uint64_t offset, int* note) = nullptr;
     int (*announce_note)(slimm_ctx*, int note) = nullptr;
-    // what else must hold for a regular file of this form to be cut over G members (none: nothing)
-    bool (*may_cut)(const AlignmentFile& f, const std::string& path, uint32_t G, bool with_floor) = nullptr;
+    // what else must hold for a regular file of this form to be cut over G members (cut_by_byte_range; none: nothing).  The
+    // least units -- bytes or blocks -- a member is worth; how many lie behind the header's last frame, block or bit (false:
+    // the file is not cut); units_gate: that answer is a condition of its own, asked without the floor too
+    uint64_t (*split_floor)() = nullptr;
+    bool (*units_behind)(const std::string& path, uint64_t header_bytes, uint64_t* units) = nullptr;
+    bool units_gate = false;
     // SLIMM_TRACE=cli, at the file's end: what the device decoded, the counters of the n contexts summed (none: no line)
     void (*end_line)(const char* head, slimm_ctx* const* ctx, uint32_t n) = nullptr;
     // a regular file of this form that the host reader takes all the same, and says so under SLIMM_TRACE=cli (none: never)
@@ -760,10 +765,7 @@ void xz_end_line(const char* head, slimm_ctx* const* ctx, uint32_t n) {
 // -- a stated default, not a measurement (SLIMM_FORCE xz_device_blocks=N).  A file whose index does not parse goes by the
 // host reader as well, which says what is wrong with it
 constexpr uint64_t kXzDeviceBlocks = 16;
-uint64_t xz_device_blocks() {
-    long least = 0;
-    return forced("xz_device_blocks", &least) && least >= 0 ? static_cast<uint64_t>(least) : kXzDeviceBlocks;
-}
+uint64_t xz_device_blocks() { return forced_or("xz_device_blocks", kXzDeviceBlocks); }
 // (one reading of a file's indexes for the two questions below; false: not a file whose index parses)
 bool xz_index_of(const std::string& path, uint64_t* size, std::vector<XzIndexBlock>* blocks, std::vector<XzIndexStream>* layout) {
     const int fd = open(path.c_str(), O_RDONLY);
@@ -784,76 +786,38 @@ bool xz_by_host(const std::string& path, const char* head) {
     if (g_trace && !ok) fprintf(stderr, "%sxz SAM whose index does not parse: read on the host\n", head);
     return true;
 }
-// zstd SAM is cut where frames start and nowhere else (slimm_host_zstd_ranges): read_split takes a file whose plan for G
-// members has at least two ranges that are not empty -- a file of one frame has none -- and, with_floor, whose members get
-// slimm_zstd_split_floor() bytes each or more: (the file's size - the first legal cut) / G (the cap's re-read does not ask:
-// it has no other way).  The floor is a stated default, the codec's round size, not a measurement
-bool zstd_may_cut(const AlignmentFile& f, const std::string& path, uint32_t G, bool with_floor) {
-    if (G < 2u) return false;
-    std::vector<uint64_t> off(G + 1u, 0);
-    if (slimm_host_zstd_ranges(path.c_str(), f.header_bytes(), G, off.data()) != SLIMM_OK) return false;
-    uint32_t filled = 0;
-    for (uint32_t i = 0; i < G; ++i) filled += off[i + 1] > off[i] ? 1u : 0u;
-    if (filled < 2u) return false;
-    if (!with_floor) return true;
-    const int fd = open(path.c_str(), O_RDONLY);
-    if (fd < 0) return false;
-    const uint64_t size = off[G];
+// What the forms with a floor count for cut_by_byte_range.  The floors are stated defaults, not measurements: zstd's is the
+// codec's round size, gzip's is zstd's (a range is decoded twice, so two members may not gain), xz's is kXzDeviceBlocks (a
+// range is decoded a lane per block, as a file is).  zstd, gzip: the bytes behind the first legal cut
+bool zstd_bytes_behind(const std::string& path, uint64_t header_bytes, uint64_t* bytes) {
+    PlanFile f;
     uint64_t first = 0;
-    const bool ok = zstd_header_end([&](uint64_t at, uint8_t* dst, size_t n) { return pread_all(fd, dst, at, n); }, size, f.header_bytes(), &first);
-    close(fd);
-    return ok && first <= size && (size - first) / G >= slimm_zstd_split_floor();
+    if (!f.open_regular(path.c_str()) || !zstd_header_end(f.reader(), f.size, header_bytes, &first) || first > f.size) return false;
+    *bytes = f.size - first;
+    return true;
 }
-// gzip SAM is cut at the bits where non-final dynamic blocks start (slimm_host_gzip_ranges): read_split takes a file with a
-// header of fewer than 2^32 bytes whose plan for G members has at least two ranges that are not empty and, with_floor, whose
-// members get slimm_gzip_split_floor() bytes each or more: (the file's size - the first legal cut) / G, asked before the plan,
-// which reads more of the file (the cap's re-read does not ask: it has no other way).  The floor is zstd's, a stated default,
-// not a measurement: a range is decoded twice, so two members may not gain
-bool gzip_may_cut(const AlignmentFile& f, const std::string& path, uint32_t G, bool with_floor) {
-    if (G < 2u || f.text_header_bytes() >= (1ull << 32)) return false;
-    if (with_floor) {
-        const int fd = open(path.c_str(), O_RDONLY);
-        struct stat sb;
-        uint64_t first_bit = 0;
-        const bool ok = fd >= 0 && fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) &&
-                        slimm::gzip_header_end([&](uint64_t at, uint8_t* dst, size_t n) { return pread_all(fd, dst, at, n); }, static_cast<uint64_t>(sb.st_size),
-                                        f.text_header_bytes(), &first_bit);
-        if (fd >= 0) close(fd);
-        if (!ok || (static_cast<uint64_t>(sb.st_size) - first_bit / 8u) / G < slimm_gzip_split_floor()) return false;
-    }
-    std::vector<uint64_t> off(G + 1u, 0);
-    if (slimm_host_gzip_ranges(path.c_str(), f.text_header_bytes(), G, off.data()) != SLIMM_OK) return false;
-    uint32_t filled = 0;
-    for (uint32_t i = 0; i < G; ++i) filled += off[i + 1] > off[i] ? 1u : 0u;
-    return filled >= 2u;
+bool gzip_bytes_behind(const std::string& path, uint64_t header_bytes, uint64_t* bytes) {
+    PlanFile f;
+    uint64_t first_bit = 0;
+    if (!f.open_regular(path.c_str()) || !slimm::gzip_header_end(f.reader(), f.size, header_bytes, &first_bit)) return false;
+    *bytes = f.size - first_bit / 8u;
+    return true;
 }
-// xz SAM is cut where its indexes say a block or a stream starts (xz_plan_ranges, the rule of slimm_host_xz_ranges, over one
-// reading of the indexes): read_split takes a file whose plan for G members has at least two ranges that are not empty and,
-// with_floor, whose members get slimm_xz_split_floor() blocks each or more: the blocks behind the first legal cut / G (the
-// cap's re-read does not ask: it has no other way).  The floor is the stated default of kXzDeviceBlocks -- a range is decoded
-// a lane per block, as a file is --, not a measurement.  Whether the device reads the file at all is xz_by_host's to say, and
-// set_up asks it only behind this: so a file of fewer than xz_device_blocks() blocks -- the one threshold, asked here as
-// xz_by_host asks it -- is not cut, --split-input leaves it to member 0's host reader, and at the cap, where the host reader
-// has read it, it fails as it did
-bool xz_may_cut(const AlignmentFile& f, const std::string& path, uint32_t G, bool with_floor) {
-    if (G < 2u || f.header_bytes() >= (1ull << 32)) return false;
-    uint64_t size = 0;
+// xz: the blocks behind those that hold the header, which are member 0's in any case.  Whether the device reads the file at
+// all is xz_by_host's to say, and set_up asks it only behind this: so a file of fewer than xz_device_blocks() blocks -- the one
+// threshold, asked here as xz_by_host asks it -- is not cut, --split-input leaves it to member 0's host reader, and at the
+// cap, where the host reader has read it, it fails as it did
+bool xz_blocks_behind(const std::string& path, uint64_t header_bytes, uint64_t* behind) {
+    uint64_t size = 0, text = 0;
     std::vector<XzIndexBlock> blocks;
-    std::vector<XzIndexStream> layout;
-    if (!xz_index_of(path, &size, &blocks, &layout) || blocks.size() < xz_device_blocks()) return false;
-    std::vector<uint64_t> off(G + 1u, 0);
-    if (!xz_plan_ranges(blocks, layout, size, f.header_bytes(), G, off.data())) return false;
-    uint32_t filled = 0;
-    for (uint32_t i = 0; i < G; ++i) filled += off[i + 1] > off[i] ? 1u : 0u;
-    if (filled < 2u) return false;
-    if (!with_floor) return true;
-    uint64_t text = 0, behind = blocks.size();
-    for (const XzIndexBlock& b : blocks) {   // (the blocks that hold the header are member 0's in any case)
-        if (text >= f.header_bytes()) break;
+    if (!xz_index_of(path, &size, &blocks, nullptr) || blocks.size() < xz_device_blocks()) return false;
+    *behind = blocks.size();
+    for (const XzIndexBlock& b : blocks) {
+        if (text >= header_bytes) break;
         text += b.uncompressed;
-        --behind;
+        --*behind;
     }
-    return behind / G >= slimm_xz_split_floor();
+    return true;
 }
 
 enum { kBam, kBgzfSam, kSam, kBzip2Sam, kGzipSam, kZstdSam, kXzSam };
@@ -867,12 +831,14 @@ const InputForm kForms[] = {
      .planned = "bzip2 streams", .slack = slimm_bzip2_split_slack, .announce_range = true},
     {.name = "gzip", .sam = true, .read = InputForm::Streamed, .push = slimm_push_gzip_sam_bytes, .plan = slimm_host_gzip_ranges,
      .planned = "gzip blocks", .wide_header_by_host = true, .announce_bits = slimm_set_gzip_range, .window_pass = slimm_set_gzip_window_pass,
-     .windows = slimm_group_gzip_windows, .may_cut = gzip_may_cut, .end_line = gzip_end_line},
+     .windows = slimm_group_gzip_windows, .split_floor = slimm_gzip_split_floor, .units_behind = gzip_bytes_behind, .end_line = gzip_end_line},
     {.name = "zstd", .sam = true, .read = InputForm::Streamed, .push = slimm_push_zstd_sam_bytes, .plan = slimm_host_zstd_ranges,
-     .planned = "zstd frames", .wide_header_by_host = true, .announce_range = true, .may_cut = zstd_may_cut, .end_line = zstd_end_line},
+     .planned = "zstd frames", .wide_header_by_host = true, .announce_range = true, .split_floor = slimm_zstd_split_floor,
+     .units_behind = zstd_bytes_behind, .end_line = zstd_end_line},
     {.name = "xz", .article = "an", .sam = true, .read = InputForm::Streamed, .push = slimm_push_xz_sam_bytes, .plan = slimm_host_xz_ranges,
      .planned = "xz blocks", .wide_header_by_host = true, .announce_range = true, .range_note = slimm_host_xz_check_at,
-     .announce_note = slimm_set_xz_range_check, .may_cut = xz_may_cut, .end_line = xz_end_line, .by_host = xz_by_host},
+     .announce_note = slimm_set_xz_range_check, .split_floor = slimm_xz_split_floor, .units_behind = xz_blocks_behind, .units_gate = true,
+     .end_line = xz_end_line, .by_host = xz_by_host},
 };
 const InputForm& form_of(const AlignmentFile& f) {
     if (f.is_bam()) return kForms[kBam];
@@ -894,10 +860,35 @@ const InputForm& pushed_as(const AlignmentFile& f) {
 // ... and whether it has raw windows at all: SAM text from anything but a regular file -- a pipe -- goes through the host
 // decoder's buffered reads
 bool has_raw_windows(const AlignmentFile& f) { return f.is_bam() || f.regular_file(); }
-// The files read_split takes: regular files of a form that has a planner, where the form's own condition holds
-bool cut_by_byte_range(const AlignmentFile& f, const std::string& path, uint32_t G, bool with_floor) {
+// The header's length as a form's planner and its member 0 count it: a streamed codec's in decoded text bytes (for gzip
+// header_bytes() does not say them; for the others the two are one number)
+uint64_t planned_header_bytes(const InputForm& form, const AlignmentFile& f) {
+    return form.read == InputForm::Streamed ? f.text_header_bytes() : f.header_bytes();
+}
+// A file's plan for G members: G + 1 offsets (false: the form has no planner, the header is too long for it, or it failed)
+bool plan_ranges(const InputForm& form, const std::string& path, uint64_t header_bytes, uint32_t G, std::vector<uint64_t>& off) {
+    off.assign(G + 1u, 0);
+    return form.plan && !(form.header_32bit && header_bytes >= (1ull << 32)) && form.plan(path.c_str(), header_bytes, G, off.data()) == SLIMM_OK;
+}
+// The files read_split takes: regular files of a form that has a planner.  A form with a floor (gzip, zstd, xz) is cut only for
+// two members or more, with a header of fewer than 2^32 bytes, where -- with_floor -- the units behind the first legal cut,
+// divided by G, reach the floor (the cap's re-read does not ask: it has no other way; asked first: the plan reads more of the
+// file), and where the plan leaves at least two ranges that are not empty (a zstd file of one frame has none).  *planned
+// keeps that plan's G + 1 offsets for read_split (empty: not cut, or a form without a floor, which read_split plans)
+bool cut_by_byte_range(const AlignmentFile& f, const std::string& path, uint32_t G, bool with_floor, std::vector<uint64_t>* planned) {
     const InputForm& form = form_of(f);
-    return f.regular_file() && form.plan && (!form.may_cut || form.may_cut(f, path, G, with_floor));
+    planned->clear();
+    if (!f.regular_file() || !form.plan) return false;
+    if (!form.split_floor) return true;
+    const uint64_t header_bytes = planned_header_bytes(form, f);
+    if (G < 2u || header_bytes >= (1ull << 32)) return false;
+    uint64_t units = 0, filled = 0;
+    if ((with_floor || form.units_gate) && !form.units_behind(path, header_bytes, &units)) return false;
+    if (with_floor && units / G < form.split_floor()) return false;
+    if (plan_ranges(form, path, header_bytes, G, *planned))
+        for (uint32_t i = 0; i < G; ++i) filled += (*planned)[i + 1] > (*planned)[i] ? 1u : 0u;
+    if (filled < 2u) planned->clear();
+    return filled >= 2u;
 }
 // One window of a file's bytes to the device decoder of its form; n = 0: the empty final push
 int push_window(const InputForm& form, slimm_ctx* ctx, const uint8_t* bytes, uint64_t n, bool compressed, uint32_t skip, bool last, uint64_t* got) {
@@ -1387,11 +1378,12 @@ struct SplitMember {
 // devices (include/slimm_hip.h, "ONE FILE SPLIT BY BYTE RANGE").  The form's row says how the file is cut and read; member 0
 // skips the header's inflated (decoded) bytes; `names`: the header's reference names, for every member's SAM decoder.  The
 // reader threads are split over the members, not multiplied (a command gets 16 CPUs).  Returns SLIMM_OK or the code of what
-// failed; *why says what.
+// failed; *why says what.  `planned`: the G + 1 offsets cut_by_byte_range kept, taken when they are for this G (a form without a
+// floor, and the cap's re-read with more members: planned here).
 int read_split(slimm_group* grp, uint32_t G, const std::string& path, const InputForm& form, const std::vector<std::string>& names,
-               uint64_t header_bytes, size_t window_cap, SplitBuffers& bufs, const char* head, std::string& why) {
-    std::vector<uint64_t> off(G + 1, 0);
-    if (!form.plan || (form.header_32bit && header_bytes >= (1ull << 32)) || form.plan(path.c_str(), header_bytes, G, off.data()) != SLIMM_OK) {
+               uint64_t header_bytes, const std::vector<uint64_t>& planned, size_t window_cap, SplitBuffers& bufs, const char* head, std::string& why) {
+    std::vector<uint64_t> off = planned;
+    if (off.size() != G + 1u && !plan_ranges(form, path, header_bytes, G, off)) {
         why = std::string("the file's ") + form.planned + " could not be planned into ranges";
         return SLIMM_E_INVALID;
     }
@@ -1482,6 +1474,7 @@ struct Reading {
     int record_order = SLIMM_ORDER_ANY;
     bool check_words = false;   // the stream is in no particular order: every record carries a second hash of its name
     bool split_input = false;   // --split-input: every member of the group reads its own byte range (read_split): no pump
+    std::vector<uint64_t> split_plan;   // ... the G + 1 offsets cut_by_byte_range planned last, for that G (none: read_split plans)
     std::unique_ptr<RecordPump> pump;
     SplitBuffers split_bufs;
     std::vector<std::string> accession;
@@ -1637,13 +1630,13 @@ std::unique_ptr<Reading> set_up(Session& S, const std::string& path, bool any_or
     // slimm_group_get_profiles: a GROUPED file in stretches cut at qName runs, any other order by key; what the pump does
     // not push raw -- --host-decode, pipes ... -- the host reader deals)
     const bool may_split = options.split_input && options.devices.size() > 1 && !options.host_decode && !options.verify_grouping && !options.packed_records;
-    F->split_input = may_split && cut_by_byte_range(bam, path, static_cast<uint32_t>(options.devices.size()), true);
+    F->split_input = may_split && cut_by_byte_range(bam, path, static_cast<uint32_t>(options.devices.size()), true, &F->split_plan);
     // (a form that is not cut whenever it is asked: a gzip file of one dynamic block, or one whose members would get less bytes
     // than its floor; a zstd file of one frame, or one whose members would get less
     // bytes than its floor; an xz file the host reader takes, or one whose members would get fewer blocks than its floor; or
     // the host decoders were asked for)
     const InputForm& form = form_of(bam);
-    if (g_trace && !any_order && !F->split_input && options.split_input && options.devices.size() > 1 && (!form.plan || form.may_cut))
+    if (g_trace && !any_order && !F->split_input && options.split_input && options.devices.size() > 1 && (!form.plan || form.split_floor))
         fprintf(stderr, "%s--split-input: %s %s stream is not cut by byte range; member 0 reads %s\n", S.trace_head(), form.article, form.name, path.c_str());
     if (!F->split_input) {
         // (a regular file that its form gives to the host reader -- an xz file of few blocks --: the pump's host path)
@@ -1811,10 +1804,9 @@ Outcome run_group(Session& S, Reading& F, const std::vector<int>& devs, bool spl
     bool split_read = false;
     if (split) {   // every member its own byte range (read_split); what fails there goes through member 0 after all
         std::string why;
-        // (a streamed codec's header is counted in decoded text bytes: for gzip header_bytes() does not say them)
         const InputForm& split_form = form_of(F.bam);
-        const int src = read_split(grp.get(), static_cast<uint32_t>(devs.size()), F.path, split_form, F.bam.ref_names(),
-                                   split_form.read == InputForm::Streamed ? F.bam.text_header_bytes() : F.bam.header_bytes(), RecordPump::raw_cap(), F.split_bufs, S.trace_head(), why);
+        const int src = read_split(grp.get(), static_cast<uint32_t>(devs.size()), F.path, split_form, F.bam.ref_names(), planned_header_bytes(split_form, F.bam),
+                                   F.split_plan, RecordPump::raw_cap(), F.split_bufs, S.trace_head(), why);
         F.trace.mark("split: read + decode + stitch");
         if (src == SLIMM_E_REGROUP) return Outcome::ReadAgainAnyOrder;
         if (src != SLIMM_OK && for_cap && classify(why.c_str()) == PushError::RecordCap) return Outcome::MoreMembers;
@@ -1893,7 +1885,7 @@ Outcome run_context(Session& S, Reading& F) {
     // took -- fewer than xz_device_blocks() blocks -- cannot be cut and ends at the cap, as it did)
     const InputForm& form = form_of(F.bam);
     const Outcome pushed = push_file(S, F, Target{ctx}, F.bam.regular_file() && form.plan ? OnCap::MoreMembers : OnCap::Fail);
-    if (pushed == Outcome::MoreMembers && form.may_cut && !form.may_cut(F.bam, F.path, 2u, false)) {
+    if (pushed == Outcome::MoreMembers && !cut_by_byte_range(F.bam, F.path, 2u, false, &F.split_plan)) {
         S.err() << "slimm: pushing records: " << slimm_last_error(ctx) << "\n";
         return Outcome::Failed;
     }

@@ -1,14 +1,16 @@
-// One file -- BAM, SAM text, BGZF blocks of SAM text, bzip2 SAM, zstd SAM or xz SAM -- split by byte range over a group's members
-// (include/slimm_hip.h, "ONE FILE SPLIT BY BYTE RANGE"): the host's plan of the ranges (slimm_host_bgzf_ranges,
-// slimm_host_text_ranges, slimm_host_bzip2_ranges, slimm_host_zstd_ranges, slimm_host_xz_ranges) and the per-member steps of slimm_group_stitch_ranges (split.h; group.hip runs them cut by cut).  A range that starts inside
-// the file guesses its first record as k_bam_pieces guesses a piece's (windows.hip, bam_decode.hip: k_bam_first_guess);
-// the member on its left confirms the guess one level up, as k_bam_verify confirms a piece's: its incomplete last record
-// followed by the right member's head must be whole records that end exactly where the guess begins.  A range of SAM
-// text guesses nothing: its first line starts behind its first newline (sam_decode.hip: k_sam_first_newline), and the
-// left member's last line must end with the head.  A range of bzip2 SAM starts at the first block of its own
-// (bzip2_decode.hip) and is text from there on; its chain of blocks is held against its neighbours' first (split_bz2_chains).  A range of zstd SAM starts and ends where frames do
-// (zstd_decode.hip) and is text in between; that every member's frames ended at its range's end is checked first (split_zstd_ends).  A range of xz SAM starts at a stream header or at a block and ends where
-// a block or a stream does (xz_decode.hip); the blocks of a stream that lies over cuts are held against its index (split_xz_streams).  The reference reads one file with one reader (src/misc.hpp:498-522).
+// One file split by byte range over a group's members (include/slimm_hip.h, "ONE FILE SPLIT BY BYTE RANGE"): the host's plans
+// of the ranges (slimm_host_*_ranges, on split_plan.h) and the codec-neutral steps of slimm_group_stitch_ranges (split.h;
+// group.hip runs them cut by cut).  A streamed codec's own check in the stitch is its row of kCodecs (windows.h) and lies with
+// its decoder.  Where each form is cut, and how a range that starts inside the file finds its start:
+//   BAM        at BGZF blocks; the first record is guessed (bam_decode.hip: k_bam_first_guess), the left member confirms it
+//   SAM        anywhere; the first line starts behind the first newline (sam_decode.hip: k_sam_first_newline)
+//   BGZF SAM   at BGZF blocks; text from there on, as SAM
+//   bzip2 SAM  anywhere; the range starts at its first block, the chains of blocks are held together (bzip2_decode.hip)
+//   zstd SAM   where frames start; every member's frames must end at its range's end (zstd_decode.hip)
+//   xz SAM     at a stream header or a block, by the indexes; a stream over cuts is held against its index (xz_decode.hip)
+//   gzip SAM   at the BITS where dynamic blocks start; two passes, the windows handed on in between (gzip_decode.hip)
+// The left member's incomplete last record (line) followed by the right member's head must be whole records (lines) that end
+// exactly where the right member's first begins.  The reference reads one file with one reader (src/misc.hpp:498-522).
 #include "context.h"
 #include "split.h"
 #include "split_plan.h"
@@ -67,6 +69,12 @@ struct BgzfFile : slimm::PlanFile {   // (where blocks start)
     }
 };
 
+// a planner's frame: its arguments are there, the header fits the first push's 32-bit `skip` (bgzf, bzip2: not asked), and
+// the file is a regular one, now open
+bool plan_opens(slimm::PlanFile& f, const char* path, uint32_t n, const uint64_t* offsets_out, uint64_t skip = 0) {
+    return path && n && offsets_out && skip < (1ull << 32) && f.open_regular(path);
+}
+
 }  // namespace
 
 extern "C" {
@@ -74,9 +82,8 @@ extern "C" {
 uint64_t slimm_record_cap(void) { return slimm::record_cap(); }
 
 int slimm_host_bgzf_ranges(const char* path, uint64_t skip, uint32_t n, uint64_t* offsets_out) {
-    if (!path || !n || !offsets_out) return SLIMM_E_INVALID;
     BgzfFile f;
-    if (!f.open_regular(path)) return SLIMM_E_INVALID;
+    if (!plan_opens(f, path, n, offsets_out)) return SLIMM_E_INVALID;
     // no cut in front of the first block whose inflated bytes start at or behind `skip`: member 0 holds the whole header
     uint64_t floor = 0, before = 0;
     while (skip && before < skip && floor < f.size) {
@@ -106,9 +113,8 @@ uint64_t slimm_bzip2_split_slack(void) { return slimm::bz2::kSplitSlack; }
 // blocks (bzip2_decode.hip).  Only the SAM header is decoded here, block by block from the file's start, for the floor
 int slimm_host_bzip2_ranges(const char* path, uint64_t skip, uint32_t n, uint64_t* offsets_out) {
     namespace bz2 = slimm::bz2;
-    if (!path || !n || !offsets_out) return SLIMM_E_INVALID;
     slimm::PlanFile f;
-    if (!f.open_regular(path)) return SLIMM_E_INVALID;
+    if (!plan_opens(f, path, n, offsets_out)) return SLIMM_E_INVALID;
     std::vector<uint8_t> in;
     auto more = [&]() {   // the file's next bytes behind `in` (false: none left, or a read error)
         const size_t have = in.size(), add = static_cast<size_t>(std::min<uint64_t>(f.size - have, std::max<uint64_t>(4u << 20, have)));
@@ -179,15 +185,13 @@ int slimm_host_bzip2_ranges(const char* path, uint64_t skip, uint32_t n, uint64_
 constexpr uint64_t kZstdCutSearch = 64ull << 20;
 int slimm_host_zstd_ranges(const char* path, uint64_t skip, uint32_t n, uint64_t* offsets_out) {
     namespace zs = slimm::zs;
-    if (!path || !n || !offsets_out || skip >= (1ull << 32)) return SLIMM_E_INVALID;
     slimm::PlanFile f;
-    if (!f.open_regular(path)) return SLIMM_E_INVALID;
-    auto read = [&](uint64_t off, uint8_t* dst, size_t k) { return off <= f.size && k <= f.size - off && f.read(off, dst, k); };
+    if (!plan_opens(f, path, n, offsets_out, skip)) return SLIMM_E_INVALID;
+    const auto read = f.reader();
     // no cut in front of the end of the frame that holds decoded byte skip - 1: member 0 holds the whole header
     uint64_t first = 0;
     if (!slimm::zstd_header_end(read, f.size, skip, &first)) return SLIMM_E_INVALID;
-    long v = 0;
-    const uint64_t search = slimm::forced("zstd_cut_search", &v) && v > 0 ? static_cast<uint64_t>(v) : kZstdCutSearch;
+    const uint64_t search = slimm::forced_or("zstd_cut_search", kZstdCutSearch, 1);
     constexpr uint64_t kNone = slimm::kNoCut;
     std::vector<uint8_t> buf(1u << 20);
     // the first start at or behind t that is a cut, looked for in [t, t + search)
@@ -210,72 +214,41 @@ int slimm_host_zstd_ranges(const char* path, uint64_t skip, uint32_t n, uint64_t
         return kNone;
     };
     slimm::even_ranges(first, f.size, n, offsets_out, cut_at);
-    // (SLIMM_FORCE zstd_split_wrong_cut: the second cut -- the first of two members -- lands one byte late, where no frame
-    // starts: the members, or the stitch, must refuse it)
-    if (n > 1 && slimm::forced("zstd_split_wrong_cut")) {
-        for (uint32_t i = std::min(2u, n - 1u); i >= 1u; --i) {
-            const uint64_t was = offsets_out[i];
-            if (was >= f.size || was == 0) continue;
-            for (uint32_t j = i; j < n && offsets_out[j] == was; ++j) ++offsets_out[j];
-            break;
-        }
-    }
+    if (slimm::forced("zstd_split_wrong_cut")) slimm::force_wrong_cut(offsets_out, n, f.size);   // (one byte late: no frame starts there)
     return SLIMM_OK;
 }
 
-uint64_t slimm_zstd_split_floor(void) {
-    long v = 0;
-    return slimm::forced("zstd_split_floor", &v) && v >= 0 ? static_cast<uint64_t>(v) : slimm::kZstdRoundBytes;
-}
+uint64_t slimm_zstd_split_floor(void) { return slimm::forced_or("zstd_split_floor", slimm::kZstdRoundBytes); }
 
 // xz is cut where its indexes say a block or a stream starts (host/xz.cpp: xz_plan_ranges): only the file's tail or tails
 // are read -- footer, index, stream header, stream by stream from the file's end --, nothing is decoded and nothing guessed
 int slimm_host_xz_ranges(const char* path, uint64_t skip, uint32_t n, uint64_t* offsets_out) {
-    if (!path || !n || !offsets_out || skip >= (1ull << 32)) return SLIMM_E_INVALID;
     slimm::PlanFile f;
-    if (!f.open_regular(path)) return SLIMM_E_INVALID;
-    auto read = [&](uint64_t off, uint8_t* dst, size_t k) { return off <= f.size && k <= f.size - off && f.read(off, dst, k); };
-    return slimm::xz_plan_ranges(read, f.size, skip, n, offsets_out) ? SLIMM_OK : SLIMM_E_INVALID;
+    if (!plan_opens(f, path, n, offsets_out, skip)) return SLIMM_E_INVALID;
+    return slimm::xz_plan_ranges(f.reader(), f.size, skip, n, offsets_out) ? SLIMM_OK : SLIMM_E_INVALID;
 }
 
 // gzip is cut at BITS: where a non-final dynamic block plausibly starts and a walk from there holds (gzip_plan.h).  The
 // header's blocks are inflated here for the floor.  What the walk cannot see the members and the stitch check
 int slimm_host_gzip_ranges(const char* path, uint64_t skip, uint32_t n, uint64_t* bit_offsets_out) {
-    if (!path || !n || !bit_offsets_out || skip >= (1ull << 32)) return SLIMM_E_INVALID;
     slimm::PlanFile f;
-    if (!f.open_regular(path)) return SLIMM_E_INVALID;
-    auto read = [&](uint64_t off, uint8_t* dst, size_t k) { return off <= f.size && k <= f.size - off && f.read(off, dst, k); };
+    if (!plan_opens(f, path, n, bit_offsets_out, skip)) return SLIMM_E_INVALID;
     slimm::GzipPlan plan;
-    long v = 0;
-    if (slimm::forced("gzip_cut_blocks", &v) && v > 0) plan.cut_blocks = static_cast<uint32_t>(v);
-    if (slimm::forced("gzip_cut_search", &v) && v > 0) plan.cut_search = static_cast<uint64_t>(v);
-    if (!slimm::gzip_plan_ranges(read, f.size, skip, n, bit_offsets_out, plan)) return SLIMM_E_INVALID;
-    // (SLIMM_FORCE gzip_split_wrong_cut: the second cut -- the first of two members -- lands one bit late, where no block
-    // starts: the members, or the stitch, must refuse it)
-    if (n > 1 && slimm::forced("gzip_split_wrong_cut")) {
-        for (uint32_t i = std::min(2u, n - 1u); i >= 1u; --i) {
-            const uint64_t was = bit_offsets_out[i];
-            if (was >= f.size * 8u || was == 0) continue;
-            for (uint32_t j = i; j < n && bit_offsets_out[j] == was; ++j) ++bit_offsets_out[j];
-            break;
-        }
-    }
+    plan.cut_blocks = static_cast<uint32_t>(slimm::forced_or("gzip_cut_blocks", plan.cut_blocks, 1));
+    plan.cut_search = slimm::forced_or("gzip_cut_search", plan.cut_search, 1);
+    if (!slimm::gzip_plan_ranges(f.reader(), f.size, skip, n, bit_offsets_out, plan)) return SLIMM_E_INVALID;
+    if (slimm::forced("gzip_split_wrong_cut")) slimm::force_wrong_cut(bit_offsets_out, n, f.size * 8u);   // (one bit late: no block starts there)
     return SLIMM_OK;
 }
 
 // The least bytes per member at which the command cuts a gzip file for --split-input: zstd's, a stated default, NOT a
 // measurement (SLIMM_FORCE gzip_split_floor=N)
-uint64_t slimm_gzip_split_floor(void) {
-    long v = 0;
-    return slimm::forced("gzip_split_floor", &v) && v >= 0 ? static_cast<uint64_t>(v) : (32ull << 20);
-}
+uint64_t slimm_gzip_split_floor(void) { return slimm::forced_or("gzip_split_floor", 32ull << 20); }
 
 int slimm_host_xz_check_at(const char* path, uint64_t offset, int* check_out) {
-    if (!path || !check_out) return SLIMM_E_INVALID;
     slimm::PlanFile f;
-    if (!f.open_regular(path)) return SLIMM_E_INVALID;
-    auto read = [&](uint64_t off, uint8_t* dst, size_t k) { return off <= f.size && k <= f.size - off && f.read(off, dst, k); };
-    return slimm::xz_check_at(read, f.size, offset, check_out) ? SLIMM_OK : SLIMM_E_INVALID;
+    if (!path || !check_out || !f.open_regular(path)) return SLIMM_E_INVALID;
+    return slimm::xz_check_at(f.reader(), f.size, offset, check_out) ? SLIMM_OK : SLIMM_E_INVALID;
 }
 
 // The least blocks per member at which the command cuts an xz file for --split-input: a range is decoded a lane per block,
@@ -283,286 +256,35 @@ int slimm_host_xz_check_at(const char* path, uint64_t offset, int* check_out) {
 // known yet of an LZMA lane's rate on the device (SLIMM_FORCE xz_split_blocks=N; a key of its own: xz_device_blocks decides
 // whether the device reads the file at all)
 constexpr uint64_t kXzSplitBlocks = 16;
-uint64_t slimm_xz_split_floor(void) {
-    long v = 0;
-    return slimm::forced("xz_split_blocks", &v) && v >= 0 ? static_cast<uint64_t>(v) : kXzSplitBlocks;
-}
+uint64_t slimm_xz_split_floor(void) { return slimm::forced_or("xz_split_blocks", kXzSplitBlocks); }
 
 }  // extern "C"
 
 namespace slimm {
 
-bool split_is_bzip2(const slimm_ctx* c) { return c->win.file.stream.codec == WindowPipeline::File::Codec::Bzip2; }
-
-int split_bz2_chains(slimm_ctx* const* members, uint32_t n, uint32_t* bad) {
-    auto rotl = [](uint32_t v, uint32_t k) {
-        k &= 31u;
-        return k ? (v << k) | (v >> (32u - k)) : v;
-    };
-    // the chain so far: where it ended, inside a stream of which level and combined CRC -- member 0's to begin with
-    uint32_t left = 0;
-    const WindowPipeline::File::Bzip2* L = &members[0]->win.file.bz2;
-    bool in_stream = L->in_stream, at_file_end = L->chain.at_file_end;
-    uint32_t level = L->level, combined = L->combined;
-    uint64_t end_bit = L->chain.end_bit;
-    for (uint32_t k = 1; k < n; ++k) {
-        slimm_ctx* c = members[k];
-        const WindowPipeline::File::Bzip2& Z = c->win.file.bz2;
-        const WindowPipeline::File::Bzip2::Chain& K = Z.chain;
-        if (!K.any) continue;   // (no block or marker starts in this range)
-        *bad = k;
-        if (!in_stream || end_bit != K.first_bit)
-            return fail(c, SLIMM_E_SPLIT, "bzip2: the chain of member %u ends at bit %llu%s, this range's first block was found at bit %llu", left,
-                        static_cast<unsigned long long>(end_bit), in_stream ? "" : " (behind the last stream)",
-                        static_cast<unsigned long long>(K.first_bit));
-        if (K.first_max_n > level * 100000u)
-            return fail(c, SLIMM_E_INVALID, "bzip2-compressed input is not supported unless it decodes: block at byte %llu: %s",
-                        static_cast<unsigned long long>(K.first_max_at), bz2::status_text(bz2::kTooLong));
-        if (K.has_eos) {
-            if ((rotl(combined, K.first_blocks) ^ K.first_combined) != K.eos_crc)
-                return fail(c, SLIMM_E_INVALID, "bzip2-compressed input is not supported unless it decodes: end-of-stream marker at byte %llu: combined CRC mismatch",
-                            static_cast<unsigned long long>(K.eos_at));
-            level = Z.level;
-            combined = Z.combined;
-        } else {   // (no marker in this range: the stream goes on into the next)
-            combined = rotl(combined, K.first_blocks) ^ Z.combined;
-        }
-        in_stream = Z.in_stream;
-        at_file_end = K.at_file_end;
-        end_bit = K.end_bit;
-        left = k;
-    }
-    // the last chain ended the streams at the file's end (the file's last member checks that as one context does; a member
-    // in front of it has seen every byte behind its last marker)
-    *bad = left;
-    if (left + 1 < n && !(at_file_end && !in_stream))
-        return fail(members[left], SLIMM_E_SPLIT, "bzip2: the chain of member %u ends at bit %llu, and no range behind it holds a block", left,
-                    static_cast<unsigned long long>(end_bit));
-    return SLIMM_OK;
-}
-
-bool split_is_zstd(const slimm_ctx* c) { return c->win.file.stream.codec == WindowPipeline::File::Codec::Zstd; }
-
-int split_zstd_ends(slimm_ctx* const* members, uint32_t n, uint32_t* bad) {
-    for (uint32_t k = 0; k < n; ++k) {
-        slimm_ctx* c = members[k];
-        const WindowPipeline::Announced& A = c->win.announced;
-        const WindowPipeline::File::Stream& T = c->win.file.stream;
-        const uint64_t at = T.base + (T.bit >> 3);   // (the file's byte its decoder stands at)
-        *bad = k;
-        if (!split_is_zstd(c) || !A.has_range)
-            return fail(c, SLIMM_E_INVALID, "a range of a zstd file: slimm_set_input_range tells where it lies");
-        if (c->win.file.zst.walk.stage != zs::Walker::Between || at != A.range_end || T.pend.size() != (T.bit >> 3))
-            return fail(c, SLIMM_E_SPLIT, "zstd: the frames of member %u end at byte %llu, its range at byte %llu: the range does not end at a frame boundary", k,
-                        static_cast<unsigned long long>(at), static_cast<unsigned long long>(A.range_end));
-    }
-    return SLIMM_OK;
-}
-
-bool split_is_xz(const slimm_ctx* c) { return c->win.file.stream.codec == WindowPipeline::File::Codec::Xz; }
-
-int split_xz_streams(slimm_ctx* const* members, uint32_t n, uint32_t* bad) {
-    using XF = WindowPipeline::File::Xz;
-    // the stream that lies over the cut in front of member k: its check kind and its blocks in the ranges on the left
-    bool open = false;
-    uint32_t check = 0;
-    std::vector<std::pair<uint64_t, uint64_t>> blocks;
-    for (uint32_t k = 0; k < n; ++k) {
-        slimm_ctx* c = members[k];
-        const WindowPipeline::Announced& A = c->win.announced;
-        const WindowPipeline::File::Stream& T = c->win.file.stream;
-        const XF& Z = c->win.file.xz;
-        const uint64_t at = T.base + (T.bit >> 3);   // (the file's byte its walker stands at)
-        *bad = k;
-        if (!split_is_xz(c) || !A.has_range) return fail(c, SLIMM_E_INVALID, "a range of an xz file: slimm_set_input_range tells where it lies");
-        if (at != A.range_end || T.pend.size() != (T.bit >> 3) || !Z.ready.empty())
-            return fail(c, SLIMM_E_SPLIT, "xz: the blocks of member %u end at byte %llu, its range at byte %llu: the range does not end at a block boundary", k,
-                        static_cast<unsigned long long>(at), static_cast<unsigned long long>(A.range_end));
-        if (Z.from_left != open)
-            return fail(c, SLIMM_E_SPLIT, open ? "xz: member %u starts at a stream header, and the stream on its left has not ended"
-                                               : "xz: member %u was told a check kind, and no stream lies over the cut in front of it", k);
-        if (Z.from_left && Z.walk.check != check && Z.walk.open_left)
-            return fail(c, SLIMM_E_SPLIT, "xz: member %u was told check kind %u, the stream's header states %u", k, static_cast<unsigned>(Z.walk.check),
-                        static_cast<unsigned>(check));
-        if (Z.from_left && !Z.walk.open_left) {   // (its footer's kind was the told one: xz_round)
-            if (static_cast<uint32_t>(A.xz_check) != check)
-                return fail(c, SLIMM_E_SPLIT, "xz: member %u was told check kind %d, the stream's header states %u", k, A.xz_check, static_cast<unsigned>(check));
-            if (blocks != Z.left_kept)
-                return fail(c, SLIMM_E_INVALID, "xz-compressed input is not supported unless it decodes: index at byte %llu: %s",
-                            static_cast<unsigned long long>(Z.left_index_at), xz::status_text(xz::kIndexMismatch));
-            open = false;
-            blocks.clear();
-        }
-        if (Z.walk.stage == xz::Walker::Blocks) {   // (the range ends among a stream's blocks)
-            if (!open) check = Z.walk.check;
-            open = true;
-            blocks.insert(blocks.end(), Z.walk.records.begin(), Z.walk.records.end());
-        }
-    }
-    *bad = n - 1u;
-    if (open) return fail(members[n - 1u], SLIMM_E_SPLIT, "xz: the last range ends among a stream's blocks");
-    return SLIMM_OK;
-}
-
-bool split_is_gzip(const slimm_ctx* c) { return c->win.file.stream.codec == WindowPipeline::File::Codec::Gzip; }
-
-namespace {
-// where a member's chain stands, as a bit of the file
-uint64_t gz_chain_end(const slimm_ctx* c) {
-    const WindowPipeline::Announced& A = c->win.announced;
-    const WindowPipeline::File::Stream& T = c->win.file.stream;
-    return A.gz_begin_bit == A.gz_end_bit ? A.gz_begin_bit : T.base * 8u + T.bit;
-}
-int gz_chain_ended(slimm_ctx* c, uint32_t k, uint64_t want) {
-    if (c->win.file.gz.range_done && gz_chain_end(c) == want) return SLIMM_OK;
-    return fail(c, SLIMM_E_SPLIT, "gzip: the chain of member %u ended at bit %llu, its range at bit %llu", k,
-                static_cast<unsigned long long>(gz_chain_end(c)), static_cast<unsigned long long>(want));
-}
-}  // namespace
-
-int split_gz_windows(slimm_ctx* const* members, uint32_t n, uint32_t* bad) {
-    using GF = WindowPipeline::File::Gzip;
-    std::vector<bool> ran(n, false);
-    for (uint32_t k = 0; k < n; ++k) {
-        slimm_ctx* c = members[k];
-        const WindowPipeline::File& F = c->win.file;
-        *bad = k;
-        // (the last member, which may do without the window pass, may announce its range behind this call)
-        if (!c->win.announced.gz_range && (k + 1u < n || F.active)) return fail(c, SLIMM_E_INVALID, "a range of a gzip file: slimm_set_gzip_range tells where it lies");
-        ran[k] = F.active && F.closed && split_is_gzip(c) && F.gz.window_pass;
-        if (F.active && !ran[k]) return fail(c, SLIMM_E_INVALID, "slimm_group_gzip_windows: behind the members' window pass (slimm_set_gzip_window_pass), pushed to its end");
-        if (!ran[k] && k + 1u < n) return fail(c, SLIMM_E_INVALID, "slimm_group_gzip_windows: only the last member may do without the window pass");
-    }
-    bool open = false;   // a gzip member lies over the cut behind member k
-    for (uint32_t k = 0; k + 1u < n; ++k) {
-        slimm_ctx *c = members[k], *r = members[k + 1u];
-        WindowPipeline& W = c->win;
-        WindowPipeline::Gzip& S = W.gz;
-        const WindowPipeline::Announced &A = W.announced, &AR = r->win.announced;
-        const GF& Z = W.file.gz;
-        const bool empty = A.gz_begin_bit == A.gz_end_bit;
-        *bad = k;
-        const bool told = AR.gz_range;
-        if (told && A.gz_end_bit != AR.gz_begin_bit)
-            return fail(c, SLIMM_E_INVALID, "slimm_group_gzip_windows: member %u's range ends at bit %llu, member %u's begins at bit %llu", k,
-                        static_cast<unsigned long long>(A.gz_end_bit), k + 1u, static_cast<unsigned long long>(AR.gz_begin_bit));
-        SLIMM_TRY(gz_chain_ended(c, k, A.gz_end_bit));
-        uint32_t front_len = 0;
-        if (!empty) {
-            open = Z.stage == GF::Deflate;
-            front_len = static_cast<uint32_t>(std::min<uint64_t>(gz::kWindow, (Z.partial ? W.gz_pass.front_len : 0u) + Z.len));
-            if (!open) front_len = 0;
-        } else {
-            front_len = W.gz_pass.front_len;
-        }
-        if (!open && told && AR.gz_begin_bit != AR.gz_end_bit)
-            return fail(c, SLIMM_E_SPLIT, "gzip: the chain of member %u ended between two gzip members at bit %llu, where member %u's range begins among blocks", k,
-                        static_cast<unsigned long long>(gz_chain_end(c)), k + 1u);
-        // the bytes in front of member k + 1: k's final window, its markers filled from the bytes in front of k
-        (void)hipSetDevice(c->device);
-        HIP_TRY(c, S.front.ensure(gz::kWindow));
-        HIP_TRY(c, S.applied.ensure(gz::kWindow));
-        if (!W.gz_pass.has_front) HIP_TRY(c, hipMemsetAsync(S.front.p, 0, gz::kWindow, c->stream));   // (member 0: nothing in front)
-        if (Z.carried) {
-            launch_gz_window_apply(c->stream, S.win16.p, S.front.p, S.applied.p);
-            HIP_TRY(c, hipGetLastError());
-        } else {   // (no chunk in this range: what lies in front of it lies in front of the next)
-            HIP_TRY(c, hipMemcpyAsync(S.applied.p, S.front.p, gz::kWindow, hipMemcpyDeviceToDevice, c->stream));
-        }
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        (void)hipSetDevice(r->device);
-        HIP_TRY(r, r->win.gz.front.ensure(gz::kWindow));
-        if (r->device == c->device)
-            HIP_TRY(r, hipMemcpyAsync(r->win.gz.front.p, S.applied.p, gz::kWindow, hipMemcpyDeviceToDevice, r->stream));
-        else
-            HIP_TRY(r, hipMemcpyPeerAsync(r->win.gz.front.p, r->device, S.applied.p, c->device, gz::kWindow, r->stream));
-        HIP_TRY(r, hipStreamSynchronize(r->stream));
-        r->win.gz_pass.has_front = true;
-        r->win.gz_pass.front_len = front_len;
-        W.gz_pass.done = true;
-        W.gz_pass.end_bit = gz_chain_end(c);
-        W.gz_pass.text = Z.text;
-    }
-    for (uint32_t k = 0; k < n; ++k) {   // the text pass starts from a fresh file, told what the window pass was told
-        if (!ran[k]) continue;
-        slimm_ctx* c = members[k];
-        *bad = k;
-        if (k + 1u == n) {
-            c->win.gz_pass.done = true;
-            c->win.gz_pass.end_bit = gz_chain_end(c);
-            c->win.gz_pass.text = c->win.file.gz.text;
-        }
-        WindowPipeline::Announced a = c->win.announced;
-        const WindowPipeline::GzipPass p = c->win.gz_pass;
-        a.gz_window_pass = false;
-        (void)hipSetDevice(c->device);
-        SLIMM_TRY(c->win.end_file(c));
-        c->win.announced = a;
-        c->win.gz_pass = p;
-    }
-    return SLIMM_OK;
-}
-
-int split_gz_chains(slimm_ctx* const* members, uint32_t n, uint32_t* bad) {
-    using GF = WindowPipeline::File::Gzip;
-    bool open = false;          // a gzip member lies over the cut in front of member k:
-    uint32_t s = 0;             // its CRC register and its length up to the cut
-    uint64_t len = 0;
-    for (uint32_t k = 0; k < n; ++k) {
-        slimm_ctx* c = members[k];
-        const WindowPipeline::Announced& A = c->win.announced;
-        const WindowPipeline::GzipPass& P = c->win.gz_pass;
-        const GF& Z = c->win.file.gz;
-        const bool empty = A.gz_begin_bit == A.gz_end_bit;
-        *bad = k;
-        if (!split_is_gzip(c) || !A.gz_range) return fail(c, SLIMM_E_INVALID, "a range of a gzip file: slimm_set_gzip_range tells where it lies");
-        if (Z.window_pass) return fail(c, SLIMM_E_INVALID, "a range of a gzip file: slimm_group_gzip_windows and the text pass come before the stitch");
-        if (k && A.gz_begin_bit != members[k - 1u]->win.announced.gz_end_bit)
-            return fail(c, SLIMM_E_INVALID, "a range of a gzip file: member %u's range begins at bit %llu, member %u's ends at bit %llu", k,
-                        static_cast<unsigned long long>(A.gz_begin_bit), k - 1u, static_cast<unsigned long long>(members[k - 1u]->win.announced.gz_end_bit));
-        if (k + 1u < n) SLIMM_TRY(gz_chain_ended(c, k, A.gz_end_bit));
-        if (P.done && (P.end_bit != gz_chain_end(c) || P.text != Z.text))
-            return fail(c, SLIMM_E_SPLIT, "gzip: the window pass of member %u ended at bit %llu behind %llu bytes of text, its text pass at bit %llu behind %llu", k,
-                        static_cast<unsigned long long>(P.end_bit), static_cast<unsigned long long>(P.text),
-                        static_cast<unsigned long long>(gz_chain_end(c)), static_cast<unsigned long long>(Z.text));
-        if (empty && k) continue;   // (it hands on what it was handed)
-        if (A.starts_mid && k) {
-            if (!open)
-                return fail(c, SLIMM_E_SPLIT, "gzip: member %u's range begins among blocks, and no gzip member lies over the cut in front of it", k);
-            if (Z.left.has) {   // the member's trailer, read here: its parts on the left and this range's against it
-                s = gz::crc_mul(s, gz::crc_x_pow8(Z.left.partial_len)) ^ Z.left.partial_crc;
-                len += Z.left.partial_len;
-                if (Z.left.crc32 != ~s)
-                    return fail(c, SLIMM_E_INVALID, "corrupt gzip stream (%s): the trailer at byte %llu of a member that lies over a cut", gz::status_text(gz::kBadCrc),
-                                static_cast<unsigned long long>(Z.left.at));
-                if (Z.left.isize != static_cast<uint32_t>(len))
-                    return fail(c, SLIMM_E_INVALID, "corrupt gzip stream (%s): the trailer at byte %llu of a member that lies over a cut", gz::status_text(gz::kBadLength),
-                                static_cast<unsigned long long>(Z.left.at));
-            } else {   // (no trailer in this range: both go on)
-                s = gz::crc_mul(s, gz::crc_x_pow8(Z.len)) ^ Z.crc;
-                len += Z.len;
-                continue;
-            }
-        }
-        open = Z.stage == GF::Deflate;
-        s = Z.crc;
-        len = Z.len;
-    }
-    return SLIMM_OK;
-}
-
 int split_range(slimm_ctx* c, SplitRange* out) {
     if (!c || !out) return SLIMM_E_INVALID;
     if (c->device < 0 || !c->win.file.active || !c->win.file.closed)
         return fail(c, SLIMM_E_INVALID, "a range of a split file: a range of BAM, SAM, BGZF SAM, bzip2 SAM, zstd SAM or xz SAM pushed to its end");
-    if (split_is_bzip2(c) && !c->win.announced.has_range)
-        return fail(c, SLIMM_E_INVALID, "a range of a bzip2 file: slimm_set_input_range tells where it lies");
-    if (split_is_xz(c) && !c->win.announced.has_range)
-        return fail(c, SLIMM_E_INVALID, "a range of an xz file: slimm_set_input_range tells where it lies");
+    const StreamCodec& K = codec_of(c->win.file.stream.codec);
+    if (K.range_announced && !c->win.announced.has_range)
+        return fail(c, SLIMM_E_INVALID, "a range of %s %s file: slimm_set_input_range tells where it lies", K.article ? K.article : "a", K.name);
     out->found_start = c->win.file.found_start || !c->win.announced.starts_mid;
     out->head_len = c->win.announced.starts_mid ? c->win.file.head_len : 0u;
     out->n_records = c->n_pushed;
     return SLIMM_OK;
+}
+
+int split_codec_stitch(slimm_ctx* const* members, uint32_t n, uint32_t* bad, const char** split_words, const char** noun) {
+    const StreamCodec& K = codec_of(members[0]->win.file.stream.codec);
+    *split_words = K.stitch_split;
+    *noun = K.stitch_noun;
+    return K.stitch ? K.stitch(members, n, bad) : SLIMM_OK;
+}
+
+int split_codec_windows(slimm_ctx* const* members, uint32_t n, uint32_t* bad) {
+    const StreamCodec& K = codec_of(members[0]->win.file.stream.codec);
+    return (K.window_stitch ? K.window_stitch : split_gz_windows)(members, n, bad);
 }
 
 int split_append_head(slimm_ctx* left, slimm_ctx* right, bool final, uint64_t* n_records) {

@@ -1,5 +1,5 @@
-// What the four planners of split.hip (slimm_host_bgzf_ranges, _text_ranges, _bzip2_ranges, _zstd_ranges) share: the regular
-// file they read, and the even shares their cuts start from.  Plain host C++ without the HIP runtime, so that
+// What the planners of split.hip (slimm_host_*_ranges) share: the regular file they read and its bounds-checked reader, the
+// even shares their cuts start from, and the wrong cut that tests force.  Plain host C++ without the HIP runtime, so that
 // tests/native/san_split_plan.cpp can run it under the sanitizers.
 #pragma once
 #include <fcntl.h>
@@ -44,6 +44,11 @@ struct PlanFile {
         }
         return true;
     }
+    // the reader the container walks take (zstd_frame.h, xz_stream.h, gzip_plan.h): n bytes at off, false when they are not
+    // all inside the file
+    auto reader() const {
+        return [this](uint64_t off, uint8_t* dst, size_t n) { return off <= size && n <= size - off && read(off, dst, n); };
+    }
 };
 
 // The ranges of n members over a file of `size` bytes: offsets[0] = 0, offsets[n] = size, and offsets[i] in between is what
@@ -58,6 +63,19 @@ void even_ranges(uint64_t floor, uint64_t size, uint32_t n, uint64_t* offsets, C
     for (uint32_t i = n; i-- > 1;)
         if (offsets[i] == kNoCut) offsets[i] = offsets[i + 1];
     for (uint32_t i = 1; i < n; ++i) offsets[i] = std::max(offsets[i], offsets[i - 1]);
+}
+
+// SLIMM_FORCE <codec>_split_wrong_cut: the second cut -- the first of two members -- lands one unit late, where nothing
+// starts, and the cuts equal to it move with it (they are one cut): the members, or the stitch, must refuse it.  A cut at 0
+// or at `limit` (the file's size in the offsets' unit, bytes or bits) or behind is no cut: the one in front of it is taken
+inline void force_wrong_cut(uint64_t* offsets, uint32_t n, uint64_t limit) {
+    if (n < 2) return;
+    for (uint32_t i = std::min(2u, n - 1u); i >= 1u; --i) {
+        const uint64_t was = offsets[i];
+        if (was >= limit || was == 0) continue;
+        for (uint32_t j = i; j < n && offsets[j] == was; ++j) ++offsets[j];
+        break;
+    }
 }
 
 }  // namespace slimm

@@ -233,7 +233,7 @@ struct WindowPipeline {
             // at its first element -- the first block candidate that decodes, or an end-of-stream marker in front of it --
             // inside a stream whose level it does not know: until its first end-of-stream marker it keeps the largest
             // block and the combined CRC from 0 over its blocks (`combined`), which the stitch checks against the chain on
-            // its left (split.hip: split_bz2_chains).  A range that ends inside the file stops at the first element that
+            // its left (bzip2_decode.hip: split_bz2_chains).  A range that ends inside the file stops at the first element that
             // starts at or behind its end.  Bit positions are the file's
             struct Chain {
                 bool started = false;        // the chain has its first element (a range from the file's start: its stream header)
@@ -260,7 +260,7 @@ struct WindowPipeline {
             // a byte range of a split file (Announced::gz_range).  A range that starts inside the file starts among a
             // member's blocks: `front` bytes of that member lie in front of it (32 768 assumed until the stitch of the
             // windows knows), crc is a register from 0 and len the range's share (`partial`) until the member's trailer,
-            // which it cannot check: what it read there is kept for the stitch (split.hip: split_gz_chains)
+            // which it cannot check: what it read there is kept for the stitch (gzip_decode.hip: split_gz_chains)
             bool window_pass = false;   // this file's pushes are the window pass: no text, no CRC
             bool partial = false;
             bool range_done = false;    // the chain stands on the range's end bit
@@ -308,7 +308,7 @@ struct WindowPipeline {
             uint64_t text = 0;                // the round's text bytes (behind xz_round)
             // a byte range of a split file (Announced::has_range).  A range that was told a check kind starts among the
             // blocks of a stream whose header lies on its left (xz::Walker::among_blocks): that stream's index hands back the
-            // records in front of the range's own -- the blocks of the ranges on the left --, kept for the stitch (split.hip:
+            // records in front of the range's own -- the blocks of the ranges on the left --, kept for the stitch (xz_decode.hip:
             // split_xz_streams).  A range that ends among a stream's blocks leaves its blocks of that stream in walk.records
             bool started = false;        // the walk has taken its start from what was announced
             bool from_left = false;      // the range starts among the blocks of a stream
@@ -416,6 +416,10 @@ int bz2_decode_batch(slimm_ctx* c, bool last);
 bool bz2_next_window(const slimm_ctx* c, uint64_t cap, uint64_t* n);
 int bz2_emit(slimm_ctx* c, uint8_t* dst, uint64_t cap, uint64_t* n_out, uint8_t* last_byte);
 void bz2_trace_file(const slimm_ctx* c);
+// (StreamCodec::stitch) the members' block chains against each other, left to right, on host scalars: every chain ends at the
+// bit where the next member that holds an element starts, that member's blocks fit the stream's level, and the combined CRC
+// of a stream over a cut is its marker's
+int split_bz2_chains(slimm_ctx* const* members, uint32_t n, uint32_t* bad);
 // gzip_decode.hip (slimm_push_gzip_sam_bytes): the member headers and trailers at stream.bit read on the host; then one
 // round on the device -- candidates found, chunk starts chosen, the size pass, the chain from the exact start -- which
 // leaves the chain's chunks in file.gz.ready.  gz_emit: the chunks decoded, resolved and written behind each other, their
@@ -424,7 +428,16 @@ int gz_round(slimm_ctx* c, bool last);
 bool gz_next_window(const slimm_ctx* c, uint64_t cap, uint64_t* n);
 int gz_emit(slimm_ctx* c, uint8_t* dst, uint64_t cap, uint64_t* n_out, uint8_t* last_byte);
 void gz_trace_file(const slimm_ctx* c);
-// (a byte range of a split file, between its two passes -- split.hip: split_gz_windows) out[i] = the byte that the range's
+// split_gz_windows (StreamCodec::window_stitch), between the members' window pass and their text pass, left to right: member
+// k's chain ended on member k + 1's first bit; its final 16-bit window, resolved against the bytes in front of its own range
+// (launch_gz_window_apply on its device), becomes the 32 768 bytes in front of member k + 1's, copied device to device, with
+// how many of them belong to the open gzip member; then every member's file state is fresh for the text pass, its
+// announcements kept.  split_gz_chains (StreamCodec::stitch), on host scalars: every chain ended on its range's end and the
+// text pass reproduced the window pass's end bit and text length (SLIMM_E_SPLIT), and the CRC register and length of a gzip
+// member that lies over cuts, folded left to right, are its trailer's (SLIMM_E_INVALID, the single context's words)
+int split_gz_windows(slimm_ctx* const* members, uint32_t n, uint32_t* bad);
+int split_gz_chains(slimm_ctx* const* members, uint32_t n, uint32_t* bad);
+// (a byte range of a split file, between its two passes -- split_gz_windows) out[i] = the byte that the range's
 // final 16-bit window win16 names: its own, or byte m of the 32 768 in `front` of the range
 void launch_gz_window_apply(hipStream_t st, const uint16_t* win16, const uint8_t* front, uint8_t* out);
 // zstd_decode.hip (slimm_push_zstd_sam_bytes): zs_round takes the container's items from zs::Walker (zstd_walk.h) -- the
@@ -440,6 +453,9 @@ bool zs_next_window(const slimm_ctx* c, uint64_t cap, uint64_t* n);
 int zs_emit(slimm_ctx* c, uint8_t* dst, uint64_t cap, uint64_t* n_out, uint8_t* last_byte);
 int zs_check(slimm_ctx* c);
 void zs_trace_file(const slimm_ctx* c);
+// (StreamCodec::stitch) left to right on host scalars, every member's decoder stands between frames at its range's end with
+// every byte of the range read (SLIMM_E_SPLIT otherwise)
+int split_zstd_ends(slimm_ctx* const* members, uint32_t n, uint32_t* bad);
 // xz_decode.hip (slimm_push_xz_sam_bytes): xz_round takes the container's items from xz::Walker (xz_walk.h), a block's
 // chunks up to its end -- a block whose bytes are not all at hand is left at its header --, and leaves the whole blocks at
 // hand, with their exact text offsets, in file.xz.ready.  xz_emit: the blocks decoded, a lane each, their checks folded
@@ -451,11 +467,53 @@ int xz_round(slimm_ctx* c, bool last);
 bool xz_next_window(const slimm_ctx* c, uint64_t cap, uint64_t* n);
 int xz_emit(slimm_ctx* c, uint8_t* dst, uint64_t cap, uint64_t* n_out, uint8_t* last_byte);
 void xz_trace_file(const slimm_ctx* c);
+// (StreamCodec::stitch) left to right on host scalars, every member's walker stands at its range's end with every byte of the
+// range read; a member that was told a check kind has a stream over the cut in front of it, of that kind; the blocks of such
+// a stream in the ranges on the left are, in order and in number, the index records that the member which met the index kept
+// (those in front of its own blocks' records)
+int split_xz_streams(slimm_ctx* const* members, uint32_t n, uint32_t* bad);
 // the decoders' shared steps (windows.hip).  stream.pend to the device, into `comp` with `tail` zeroed bytes behind it.
 // The candidates a find kernel left at d_cand, counted at count[0]: `launch(cap)` runs it with room for cap of them, again
 // with more room when there were more; *got of them are there (and the stream is idle)
 int stream_upload(slimm_ctx* c, DevBuf<uint8_t>& comp, uint64_t tail);
 int stream_candidates(slimm_ctx* c, DevBuf<unsigned long long>& d_cand, DevBuf<uint32_t>& count, uint32_t cap, const std::function<void(uint32_t)>& launch,
                       uint32_t* got);
+
+// ONE ROW PER STREAMED CODEC (windows.hip: kCodecs, by File::Codec; the row of Codec::None is empty): the hooks above, and the
+// codec's side of a file split by byte range over a group's members (split.h).  A new codec is a row and its decoder's file
+struct StreamCodec {
+    using File = WindowPipeline::File;
+    const char* name;        // traces and error texts
+    // compressed bytes gathered on the host before a round looks at them (the command's pushes are larger, the ABI's may be
+    // of any size); SLIMM_FORCE <round_key>=N: rounds of N bytes -- tests cut blocks, headers and trailers across rounds
+    const char* round_key;
+    uint64_t round_bytes;
+    bool cut_by_range;       // a byte range of a split file may cut it (slimm_set_input_mid_file)
+    bool cut_at_frames;      // ... only where the caller's plan found a frame start (xz: a block start): not without slimm_set_input_range
+    int (*round)(slimm_ctx*, bool last);
+    bool (*next_window)(const slimm_ctx*, uint64_t cap, uint64_t* n);
+    int (*emit)(slimm_ctx*, uint8_t* dst, uint64_t cap, uint64_t* n_out, uint8_t* last_byte);
+    int (*behind_submit)(slimm_ctx*);   // on the host, beside the window's decode -- also behind a round of no text (or null)
+    void (*trace_file)(const slimm_ctx*);
+    // where between its streams the codec is: a push's rounds go on while the file offset or this moves, and stop when the
+    // codec waits for bytes (null: they go on while a round leaves something ready)
+    int (*stage)(const File&);
+    bool (*ended)(const File&);   // the codec has stopped for good: bytes pushed now are dropped (or null)
+    // its counters (they outlive the file: slimm_get_*_stats), how many, and which of them counts the compressed bytes
+    uint64_t* (*stats)(WindowPipeline&);
+    size_t n_stats, stat_compressed;
+    const char* article;     // "an" where the name wants it (null: "a")
+    const char* cut_unit;    // cut_at_frames: what a range starts at (null: "frame")
+    // ---- a file split by byte range.  split_range takes a pushed range of this codec only when slimm_set_input_range announced it
+    bool range_announced;
+    // slimm_group_stitch_ranges, before any text is joined: the members' ranges held against each other, left to right, by the
+    // hook of MEMBER 0's codec (null: nothing to hold).  SLIMM_OK, or the code with the message on member *bad: SLIMM_E_SPLIT
+    // is wrapped in `stitch_split` (member, message), anything else is member_failed's "<stitch_noun>: <message>".
+    // window_stitch: the same between the members' two passes, slimm_group_gzip_windows (null: the codec has one pass)
+    int (*stitch)(slimm_ctx* const* members, uint32_t n, uint32_t* bad);
+    const char *stitch_split, *stitch_noun;
+    int (*window_stitch)(slimm_ctx* const* members, uint32_t n, uint32_t* bad);
+};
+const StreamCodec& codec_of(WindowPipeline::File::Codec k);
 
 }  // namespace slimm

@@ -310,46 +310,26 @@ int add_last_newline(slimm_ctx* c, uint64_t at, hipStream_t st) {   // at: bytes
 // ---- a push
 enum { kFormatBam = 0, kFormatBgzf = 1, kFormatSam = 2, kFormatBgzfSam = 3, kFormatBzip2Sam = 4, kFormatGzipSam = 5, kFormatZstdSam = 6, kFormatXzSam = 7 };
 
-// What a streamed codec supplies (windows.h: the hooks' contracts), by File::Codec
-struct StreamCodec {
-    const char* name;        // traces and error texts
-    // compressed bytes gathered on the host before a round looks at them (the command's pushes are larger, the ABI's may be
-    // of any size); SLIMM_FORCE <round_key>=N: rounds of N bytes -- tests cut blocks, headers and trailers across rounds
-    const char* round_key;
-    uint64_t round_bytes;
-    bool cut_by_range;       // a byte range of a split file may cut it (slimm_set_input_mid_file)
-    bool cut_at_frames;      // ... only where the caller's plan found a frame start (xz: a block start): not without slimm_set_input_range
-    int (*round)(slimm_ctx*, bool last);
-    bool (*next_window)(const slimm_ctx*, uint64_t cap, uint64_t* n);
-    int (*emit)(slimm_ctx*, uint8_t* dst, uint64_t cap, uint64_t* n_out, uint8_t* last_byte);
-    int (*behind_submit)(slimm_ctx*);   // on the host, beside the window's decode -- also behind a round of no text (or null)
-    void (*trace_file)(const slimm_ctx*);
-    // where between its streams the codec is: a push's rounds go on while the file offset or this moves, and stop when the
-    // codec waits for bytes (null: they go on while a round leaves something ready)
-    int (*stage)(const File&);
-    bool (*ended)(const File&);   // the codec has stopped for good: bytes pushed now are dropped (or null)
-    // its counters (they outlive the file: slimm_get_*_stats), how many, and which of them counts the compressed bytes
-    uint64_t* (*stats)(WindowPipeline&);
-    size_t n_stats, stat_compressed;
-    const char* article;     // "an" where the name wants it (null: "a")
-    const char* cut_unit;    // cut_at_frames: what a range starts at (null: "frame")
-};
+// What each streamed codec supplies (windows.h: StreamCodec), by File::Codec
 const StreamCodec kCodecs[] = {
     {},
-    // (ended: the range's chain has stopped, what comes now are bytes of the slack)
+    // (ended: the range's chain has stopped, what comes now are bytes of the slack.  Every row's last line: its split side)
     {"bzip2", "bzip2_round", 32ull << 20, true, false, bz2_decode_batch, bz2_next_window, bz2_emit, nullptr, bz2_trace_file, nullptr,
-     [](const File& F) { return F.bz2.chain.ended; }, nullptr, 0, 0, nullptr, nullptr},
+     [](const File& F) { return F.bz2.chain.ended; }, nullptr, 0, 0, nullptr, nullptr,
+     true, split_bz2_chains, "cut in front of member %u: %s", "the chain of blocks across a cut", nullptr},
     {"gzip", "gzip_round", 32ull << 20, false, false, gz_round, gz_next_window, gz_emit, nullptr, gz_trace_file,
      [](const File& F) { return static_cast<int>(F.gz.stage); }, nullptr, [](WindowPipeline& W) { return W.gz_stats; },
-     WindowPipeline::kGzStats, WindowPipeline::kGzCompressed, nullptr, nullptr},
+     WindowPipeline::kGzStats, WindowPipeline::kGzCompressed, nullptr, nullptr,
+     false, split_gz_chains, "the range of member %u: %s", "a gzip member across a cut", split_gz_windows},
     {"zstd", "zstd_round", kZstdRoundBytes, true, true, zs_round, zs_next_window, zs_emit, zs_check, zs_trace_file,
      [](const File& F) { return static_cast<int>(F.zst.walk.stage); }, nullptr, [](WindowPipeline& W) { return W.zs_stats; },
-     WindowPipeline::kZsStats, WindowPipeline::kZsCompressedBytes, nullptr, nullptr},
+     WindowPipeline::kZsStats, WindowPipeline::kZsCompressedBytes, nullptr, nullptr,
+     false, split_zstd_ends, "the range of member %u: %s", "the frames of a range", nullptr},
     {"xz", "xz_round", 32ull << 20, true, true, xz_round, xz_next_window, xz_emit, nullptr, xz_trace_file,
      [](const File& F) { return static_cast<int>(F.xz.walk.stage); }, nullptr, [](WindowPipeline& W) { return W.xz_stats; },
-     WindowPipeline::kXzStats, WindowPipeline::kXzCompressedBytes, "an", "block"},
+     WindowPipeline::kXzStats, WindowPipeline::kXzCompressedBytes, "an", "block",
+     true, split_xz_streams, "the range of member %u: %s", "the blocks of a stream across a cut", nullptr},
 };
-const StreamCodec& codec_of(Codec k) { return kCodecs[static_cast<size_t>(k)]; }
 
 struct Push {
     const uint8_t* bytes;
@@ -893,6 +873,8 @@ int slimm_set_reference_names(slimm_ctx* c, const char* const* names) {
 }  // extern "C"
 
 namespace slimm {
+
+const StreamCodec& codec_of(WindowPipeline::File::Codec k) { return kCodecs[static_cast<size_t>(k)]; }
 
 int stream_upload(slimm_ctx* c, DevBuf<uint8_t>& comp, uint64_t tail) {
     const std::vector<uint8_t>& pend = c->win.file.stream.pend;

@@ -15,7 +15,7 @@
 //   (host)        the registers against the blocks' check fields.  SHA-256 is NOT verified: such blocks are counted
 // A byte range of a split file (include/slimm_hip.h, "xz SAM by byte range") changes the host's walk alone: where it starts --
 // at a stream header, or among a stream's blocks with the check kind it was told --, where it must stop, and what it keeps of
-// an index whose first records are blocks of the ranges on its left (split.hip: split_xz_streams holds them against those).
+// an index whose first records are blocks of the ranges on its left (split_xz_streams, below, holds them against those).
 // No workgroup waits for another.  One round is one window; the window then goes to the SAM finder and decoder as any text
 // window does (windows.hip).  NOT MEASURED on an MI355X: nothing is known of an LZMA lane's rate there.
 #include "context.h"
@@ -335,6 +335,49 @@ void xz_trace_file(const slimm_ctx* c) {
             (unsigned long long)s[5], (unsigned long long)s[3], (unsigned long long)s[7], (unsigned long long)s[8], (unsigned long long)s[9],
             (unsigned long long)s[10], (unsigned long long)s[11], (unsigned long long)s[12], (unsigned long long)s[15], (unsigned long long)s[14],
             (unsigned long long)s[16]);
+}
+
+// ---- a file split by byte range over a group's members: this codec's check in slimm_group_stitch_ranges (windows.h)
+int split_xz_streams(slimm_ctx* const* members, uint32_t n, uint32_t* bad) {
+    // the stream that lies over the cut in front of member k: its check kind and its blocks in the ranges on the left
+    bool open = false;
+    uint32_t check = 0;
+    std::vector<std::pair<uint64_t, uint64_t>> blocks;
+    for (uint32_t k = 0; k < n; ++k) {
+        slimm_ctx* c = members[k];
+        const WindowPipeline::Announced& A = c->win.announced;
+        const WindowPipeline::File::Stream& T = c->win.file.stream;
+        const XF& Z = c->win.file.xz;
+        const uint64_t at = T.base + (T.bit >> 3);   // (the file's byte its walker stands at)
+        *bad = k;
+        if (c->win.file.stream.codec != WindowPipeline::File::Codec::Xz || !A.has_range) return fail(c, SLIMM_E_INVALID, "a range of an xz file: slimm_set_input_range tells where it lies");
+        if (at != A.range_end || T.pend.size() != (T.bit >> 3) || !Z.ready.empty())
+            return fail(c, SLIMM_E_SPLIT, "xz: the blocks of member %u end at byte %llu, its range at byte %llu: the range does not end at a block boundary", k,
+                        static_cast<unsigned long long>(at), static_cast<unsigned long long>(A.range_end));
+        if (Z.from_left != open)
+            return fail(c, SLIMM_E_SPLIT, open ? "xz: member %u starts at a stream header, and the stream on its left has not ended"
+                                               : "xz: member %u was told a check kind, and no stream lies over the cut in front of it", k);
+        if (Z.from_left && Z.walk.check != check && Z.walk.open_left)
+            return fail(c, SLIMM_E_SPLIT, "xz: member %u was told check kind %u, the stream's header states %u", k, static_cast<unsigned>(Z.walk.check),
+                        static_cast<unsigned>(check));
+        if (Z.from_left && !Z.walk.open_left) {   // (its footer's kind was the told one: xz_round)
+            if (static_cast<uint32_t>(A.xz_check) != check)
+                return fail(c, SLIMM_E_SPLIT, "xz: member %u was told check kind %d, the stream's header states %u", k, A.xz_check, static_cast<unsigned>(check));
+            if (blocks != Z.left_kept)
+                return fail(c, SLIMM_E_INVALID, "xz-compressed input is not supported unless it decodes: index at byte %llu: %s",
+                            static_cast<unsigned long long>(Z.left_index_at), xz::status_text(xz::kIndexMismatch));
+            open = false;
+            blocks.clear();
+        }
+        if (Z.walk.stage == xz::Walker::Blocks) {   // (the range ends among a stream's blocks)
+            if (!open) check = Z.walk.check;
+            open = true;
+            blocks.insert(blocks.end(), Z.walk.records.begin(), Z.walk.records.end());
+        }
+    }
+    *bad = n - 1u;
+    if (open) return fail(members[n - 1u], SLIMM_E_SPLIT, "xz: the last range ends among a stream's blocks");
+    return SLIMM_OK;
 }
 
 }  // namespace slimm

@@ -430,4 +430,21 @@ void zs_trace_file(const slimm_ctx* c) {
             (unsigned long long)s[17], (unsigned long long)s[16], (unsigned long long)s[18]);
 }
 
+// ---- a file split by byte range over a group's members: this codec's check in slimm_group_stitch_ranges (windows.h)
+int split_zstd_ends(slimm_ctx* const* members, uint32_t n, uint32_t* bad) {
+    for (uint32_t k = 0; k < n; ++k) {
+        slimm_ctx* c = members[k];
+        const WindowPipeline::Announced& A = c->win.announced;
+        const WindowPipeline::File::Stream& T = c->win.file.stream;
+        const uint64_t at = T.base + (T.bit >> 3);   // (the file's byte its decoder stands at)
+        *bad = k;
+        if (c->win.file.stream.codec != WindowPipeline::File::Codec::Zstd || !A.has_range)
+            return fail(c, SLIMM_E_INVALID, "a range of a zstd file: slimm_set_input_range tells where it lies");
+        if (c->win.file.zst.walk.stage != zs::Walker::Between || at != A.range_end || T.pend.size() != (T.bit >> 3))
+            return fail(c, SLIMM_E_SPLIT, "zstd: the frames of member %u end at byte %llu, its range at byte %llu: the range does not end at a frame boundary", k,
+                        static_cast<unsigned long long>(at), static_cast<unsigned long long>(A.range_end));
+    }
+    return SLIMM_OK;
+}
+
 }  // namespace slimm

@@ -6,6 +6,7 @@ All compute happens in libslimm_hip.so (HIP kernels + the C++ host glue); this f
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 from typing import Dict, List, Optional, Tuple
 
@@ -873,7 +874,26 @@ class SlimmGroup:
             e = min(n, s + step)
             self._check(self.L.slimm_group_push_records_marked(self.g, _p(w[s:e]), _p(rec.begin_pos[s:e]), e - s))
 
-    SPLIT_FORMS = ("bam", "sam", "bgzf_sam", "bzip2_sam", "zstd_sam", "xz_sam", "gzip_sam")
+    # push_split, one row per form: the planner; whether its offsets are BITS (a member pushes the bytes that hold them); what a
+    # member announces behind slimm_set_input_mid_file, in this order (push_split: `tell`); the bytes it pushes behind its range;
+    # its push (member, bytes, skip, window); and, for a form that reads its ranges twice, the switch of the window pass and the
+    # group's step between the two passes.  A new form is a row
+    _SplitForm = collections.namedtuple("_SplitForm", "plan bits announce slack push windows")
+    SPLIT_FORMS = {
+        "bam": _SplitForm("slimm_host_bgzf_ranges", False, ("hint",), None, lambda m, b, skip, window: m.push_bgzf_blocks(b, skip=skip, window=window), None),
+        "sam": _SplitForm("slimm_host_text_ranges", False, ("hint",), None, lambda m, b, skip, window: m.push_sam_bytes(b, window=window), None),
+        "bgzf_sam": _SplitForm("slimm_host_bgzf_ranges", False, ("hint",), None,
+                               lambda m, b, skip, window: m.push_bgzf_blocks(b, skip=skip, window=window, sam=True), None),
+        "bzip2_sam": _SplitForm("slimm_host_bzip2_ranges", False, ("hint", "range"), "slimm_bzip2_split_slack",
+                                lambda m, b, skip, window: m.push_bzip2_sam_bytes(b, skip=skip, window=window), None),
+        "zstd_sam": _SplitForm("slimm_host_zstd_ranges", False, ("hint", "range"), None,
+                               lambda m, b, skip, window: m.push_zstd_sam_bytes(b, skip=skip, window=window), None),
+        "xz_sam": _SplitForm("slimm_host_xz_ranges", False, ("hint", "range", "xz_check"), None,
+                             lambda m, b, skip, window: m.push_xz_sam_bytes(b, skip=skip, window=window), None),
+        "gzip_sam": _SplitForm("slimm_host_gzip_ranges", True, ("gzip_bits",), None,
+                               lambda m, b, skip, window: m.push_gzip_sam_bytes(b, skip=skip, window=window),
+                               ("slimm_set_gzip_window_pass", "slimm_group_gzip_windows")),
+    }
 
     def push_split(self, data, form: str, skip: int = 0, window: int = 0, offsets=None, xz_checks=None):
         """One file split by byte range, every member its own (include/slimm_hip.h, "ONE FILE SPLIT BY BYTE RANGE"): GROUPED by
@@ -899,10 +919,9 @@ class SlimmGroup:
         import tempfile
 
         assert form in self.SPLIT_FORMS, form
+        row = self.SPLIT_FORMS[form]
         G = len(self.devices)
         offs = (C.c_uint64 * (G + 1))()
-        plan = {"sam": self.L.slimm_host_text_ranges, "bzip2_sam": self.L.slimm_host_bzip2_ranges, "zstd_sam": self.L.slimm_host_zstd_ranges,
-                "xz_sam": self.L.slimm_host_xz_ranges, "gzip_sam": self.L.slimm_host_gzip_ranges}.get(form, self.L.slimm_host_bgzf_ranges)
         checks = list(xz_checks) if xz_checks is not None else None
 
         def planned(path):   # the offsets, unless given; an xz file: the check kind at every range's start, unless given
@@ -912,7 +931,7 @@ class SlimmGroup:
                 assert len(offsets) == G + 1
                 offs[:] = list(offsets)
             else:
-                rc = plan(path.encode(), int(skip), G, offs)
+                rc = getattr(self.L, row.plan)(path.encode(), int(skip), G, offs)
             if rc == capi.OK and form == "xz_sam" and checks is None:
                 checks = []
                 for i in range(G):
@@ -936,48 +955,30 @@ class SlimmGroup:
                 rc = planned(f.name)
         if rc != capi.OK:
             raise capi.SlimmError(rc, "the file could not be planned into ranges")
-        counts = []
-        if form == "gzip_sam":
-            if sum(1 for a, b in zip(offs, offs[1:]) if b > a) < 2:
-                raise capi.SlimmError(capi.E_INVALID, "a gzip stream is not cut by byte range: the plan leaves one member all of the file")
-            members = [self.member(i) for i in range(G)]
+        if row.windows and sum(1 for a, b in zip(offs, offs[1:]) if b > a) < 2:
+            raise capi.SlimmError(capi.E_INVALID, "a gzip stream is not cut by byte range: the plan leaves one member all of the file")
+        slack = getattr(self.L, row.slack)() if row.slack else 0
+        members = [self.member(i) for i in range(G)]
 
-            def announce_and_push(i, window_pass):
-                m = members[i]
-                m.set_reference_names(self.w.ref_names)
-                m._check(self.L.slimm_set_input_mid_file(m.ctx, 1 if i > 0 else 0, 1 if i + 1 < G else 0))
-                m._check(self.L.slimm_set_gzip_range(m.ctx, offs[i], offs[i + 1]))
-                m._check(self.L.slimm_set_gzip_window_pass(m.ctx, 1 if window_pass else 0))
-                return m.push_gzip_sam_bytes(blob[offs[i] // 8:(offs[i + 1] + 7) // 8], skip=skip if i == 0 else 0, window=window)
-
-            for i in range(G - 1):
-                announce_and_push(i, True)
-            self._check(self.L.slimm_group_gzip_windows(self.g))
-            counts = [announce_and_push(i, False) for i in range(G)]
-            self._check(self.L.slimm_group_stitch_ranges(self.g))
-            return list(offs), counts
-        for i in range(G):
-            m = self.member(i)
+        def announce_and_push(i, window_pass):
+            m, lo, hi = members[i], offs[i], offs[i + 1]
             if form != "bam":
                 m.set_reference_names(self.w.ref_names)
             m._check(self.L.slimm_set_input_mid_file(m.ctx, 1 if i > 0 else 0, 1 if i + 1 < G else 0))
-            m._check(self.L.slimm_set_input_size_hint(m.ctx, offs[i + 1] - offs[i]))
-            part = blob[offs[i]:offs[i + 1]]
-            if form == "bzip2_sam":
-                m._check(self.L.slimm_set_input_range(m.ctx, offs[i], offs[i + 1]))
-                part = blob[offs[i]:offs[i + 1] + self.L.slimm_bzip2_split_slack()]
-                counts.append(m.push_bzip2_sam_bytes(part, skip=skip if i == 0 else 0, window=window))
-            elif form == "zstd_sam":
-                m._check(self.L.slimm_set_input_range(m.ctx, offs[i], offs[i + 1]))
-                counts.append(m.push_zstd_sam_bytes(part, skip=skip if i == 0 else 0, window=window))
-            elif form == "xz_sam":
-                m._check(self.L.slimm_set_input_range(m.ctx, offs[i], offs[i + 1]))
-                m._check(self.L.slimm_set_xz_range_check(m.ctx, checks[i]))
-                counts.append(m.push_xz_sam_bytes(part, skip=skip if i == 0 else 0, window=window))
-            elif form == "sam":
-                counts.append(m.push_sam_bytes(part, window=window))
-            else:
-                counts.append(m.push_bgzf_blocks(part, skip=skip if i == 0 else 0, window=window, sam=form == "bgzf_sam"))
+            tell = {"hint": lambda: self.L.slimm_set_input_size_hint(m.ctx, hi - lo), "range": lambda: self.L.slimm_set_input_range(m.ctx, lo, hi),
+                    "xz_check": lambda: self.L.slimm_set_xz_range_check(m.ctx, checks[i]), "gzip_bits": lambda: self.L.slimm_set_gzip_range(m.ctx, lo, hi)}
+            for what in row.announce:
+                m._check(tell[what]())
+            if row.windows:
+                m._check(getattr(self.L, row.windows[0])(m.ctx, 1 if window_pass else 0))
+            part = blob[lo // 8:(hi + 7) // 8] if row.bits else blob[lo:hi + slack]
+            return row.push(m, part, skip if i == 0 else 0, window)
+
+        # (a window pass: every member but the last reads its range for its windows, the group hands them on; then the text)
+        for window_pass in ((True, False) if row.windows else (False,)):
+            counts = [announce_and_push(i, window_pass) for i in range(G - 1 if window_pass else G)]
+            if window_pass:
+                self._check(getattr(self.L, row.windows[1])(self.g))
         self._check(self.L.slimm_group_stitch_ranges(self.g))
         return list(offs), counts
 
