@@ -347,6 +347,31 @@ int slimm_push_zstd_sam_bytes(slimm_ctx* ctx, const uint8_t* bytes, uint64_t n_b
  * of an earlier round, [15] rounds, [16] bytes of text, [17] compressed bytes, [18] content checksums checked, [19] the most
  * pointer-doubling passes a round took (at most ceil(log2(its text + history)) + 1). */
 int slimm_get_zstd_stats(slimm_ctx* ctx, uint64_t out[20]);
+/* LZ4-COMPRESSED SAM TEXT (`lz4 x.sam`, `lz4 -BD`: linked blocks; frames back to back; skippable frames among them are passed
+ * over) decoded on the device (slimm_amd/csrc/lz4_decode.hip; the format: lz4_frame.h, the container: lz4_walk.h).  The
+ * contract is that of slimm_push_zstd_sam_bytes: `bytes` = the file's next n_bytes, from its first byte on and in order
+ * across calls, cut anywhere (inside a frame header, a block header, a block, a checksum); of the decoded text the first
+ * `skip` bytes are the header (0 in every later call); slimm_set_reference_names first; the caller's buffer is free when the
+ * call returns; what cannot be decoded yet waits for the next push; the form does not mix with the others within a file.
+ * Behind slimm_set_input_mid_file it is refused: "an lz4 stream is not cut by byte range".  Pushes are gathered on the host
+ * and decoded in rounds (32 MiB of compressed bytes, at most 512 MB of text by the blocks' bounds; SLIMM_FORCE lz4_round=N,
+ * lz4_round_text=N): the host walks the frame and block headers and checks the header and block checksums (XXH32), the
+ * device walks every compressed block's tokens at once (a wave per block, the bytes staged through LDS), builds the round's
+ * text in parallel over its bytes -- a literal byte is read from the block, a match byte gets the position it copies from,
+ * in the round or in a linked frame's last 64 KiB of text kept from the round before; pointer doubling resolves the chains
+ * -- and the host checks the content size and the content checksum (XXH32) of a frame that states them.  Limits: a
+ * dictionary id and the legacy format (`lz4 -l`) are refused.  Errors: SLIMM_E_INVALID "lz4-compressed input is not
+ * supported unless it decodes: <where>: <cause>" in the words of the host reader -- truncation, a version other than 1, a
+ * reserved bit, a block larger than its maximum, a header, block or content checksum mismatch, a content size mismatch, an
+ * offset of 0 or beyond the frame's start (in an independent frame: the block's), a block that ends inside a length, its
+ * literals or an offset, or behind a match, bytes behind the last frame that start no frame. */
+int slimm_push_lz4_sam_bytes(slimm_ctx* ctx, const uint8_t* bytes, uint64_t n_bytes, uint32_t skip, int last, uint64_t* n_records);
+/* The counters of the lz4 file read last (they outlive slimm_reset, and are zeroed by the next lz4 file's first push):
+ * out[0] frames, [1] skippable frames, [2] linked frames, [3] stored and [4] compressed blocks, [5] sequences (matches),
+ * [6] match bytes copied from in front of their own block, of which [7] from the history of an earlier round, [8] rounds,
+ * [9] bytes of text, [10] compressed bytes, [11] block checksums and [12] content checksums checked, [13] the most
+ * pointer-doubling passes a round took (at most ceil(log2(its text + history)) + 1); [14], [15]: 0. */
+int slimm_get_lz4_stats(slimm_ctx* ctx, uint64_t out[16]);
 /* XZ-COMPRESSED SAM TEXT (`xz x.sam`; xz -T, --block-size, pixz, pxz: many blocks; streams back to back with stream padding)
  * decoded on the device (slimm_amd/csrc/xz_decode.hip; the format: xz_stream.h).  The contract is that of
  * slimm_push_zstd_sam_bytes: `bytes` = the file's next n_bytes, from its first byte on and in order across calls, cut

@@ -179,6 +179,8 @@ SYMBOLS = [
     ("slimm_get_gzip_stats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("slimm_push_zstd_sam_bytes", C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]),
     ("slimm_get_zstd_stats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    ("slimm_push_lz4_sam_bytes", C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]),
+    ("slimm_get_lz4_stats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("slimm_push_xz_sam_bytes", C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]),
     ("slimm_get_xz_stats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("slimm_set_reference_names", C.c_int, [_P, C.POINTER(C.c_char_p)]),

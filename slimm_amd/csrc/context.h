@@ -26,6 +26,7 @@
 #include "deflate_stream.h"
 #include "zstd_walk.h"
 #include "xz_walk.h"
+#include "lz4_walk.h"
 #include "kernels.h"
 #include "read_identity.h"
 

@@ -24,6 +24,10 @@
 //   rest), xz_device_blocks=N (the `slimm` command reads an xz file of fewer than N blocks, by its index, on the host: 16
 //   unless told)                              tests/test_gpu_xz_sam.py, tests/test_cli_xz_sam_device.py,
 //                                             tests/test_gpu_codec_paths.py (xz_round, xz_round_text: the directed inputs of tests/lzma_directed.py)
+//   lz4_round=N (lz4 SAM decoded every N compressed bytes: frame headers, block headers, blocks, end marks and checksums cut
+//   across rounds), lz4_round_text=N (a round's text at most, by the blocks' bounds: with 65536 a round a block, so that a
+//   linked frame's copies reach into the history of an earlier round)
+//                                             tests/test_gpu_lz4_sam.py, tests/test_cli_lz4_sam_device.py
 //   xz_split_blocks=N (the least blocks per member at which the command cuts an xz file for --split-input: 16 unless told;
 //   a key of its own, which does not follow xz_device_blocks)
 //                                             tests/test_split_xz_ranges.py, tests/test_cli_split_input_xz.py

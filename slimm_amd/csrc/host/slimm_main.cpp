@@ -127,6 +127,8 @@ SLIMM_FORWARD(int, slimm_push_gzip_sam_bytes, (slimm_ctx* a, const uint8_t* b, u
 SLIMM_FORWARD(int, slimm_get_gzip_stats, (slimm_ctx* a, uint64_t* b), (a, b))
 SLIMM_FORWARD(int, slimm_push_zstd_sam_bytes, (slimm_ctx* a, const uint8_t* b, uint64_t c, uint32_t s, int d, uint64_t* e), (a, b, c, s, d, e))
 SLIMM_FORWARD(int, slimm_get_zstd_stats, (slimm_ctx* a, uint64_t* b), (a, b))
+SLIMM_FORWARD(int, slimm_push_lz4_sam_bytes, (slimm_ctx* a, const uint8_t* b, uint64_t c, uint32_t s, int d, uint64_t* e), (a, b, c, s, d, e))
+SLIMM_FORWARD(int, slimm_get_lz4_stats, (slimm_ctx* a, uint64_t* b), (a, b))
 SLIMM_FORWARD(int, slimm_push_xz_sam_bytes, (slimm_ctx* a, const uint8_t* b, uint64_t c, uint32_t s, int d, uint64_t* e), (a, b, c, s, d, e))
 SLIMM_FORWARD(int, slimm_get_xz_stats, (slimm_ctx* a, uint64_t* b), (a, b))
 SLIMM_FORWARD(int, slimm_pin_host_buffer, (slimm_ctx* a, const void* b, uint64_t c), (a, b, c))
@@ -751,6 +753,15 @@ void zstd_end_line(const char* head, slimm_ctx* const* ctx, uint32_t n) {
     if (told) fprintf(stderr, "%szstd SAM on the device: %llu frames, %llu blocks, %llu bytes of text\n", head, (unsigned long long)frames,
             (unsigned long long)blocks, (unsigned long long)text);
 }
+void lz4_end_line(const char* head, slimm_ctx* const* ctx, uint32_t n) {
+    uint64_t frames = 0, blocks = 0, text = 0, told = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        uint64_t st[20] = {};
+        if (slimm_get_lz4_stats(ctx[i], st) == SLIMM_OK) ++told, frames += st[0], blocks += st[3] + st[4], text += st[9];
+    }
+    if (told) fprintf(stderr, "%slz4 SAM on the device: %llu frames, %llu blocks, %llu bytes of text\n", head, (unsigned long long)frames,
+            (unsigned long long)blocks, (unsigned long long)text);
+}
 void xz_end_line(const char* head, slimm_ctx* const* ctx, uint32_t n) {
     uint64_t streams = 0, blocks = 0, text = 0, told = 0;
     for (uint32_t i = 0; i < n; ++i) {   // (a stream is counted by the member that read its header)
@@ -820,7 +831,7 @@ bool xz_blocks_behind(const std::string& path, uint64_t header_bytes, uint64_t* 
     return true;
 }
 
-enum { kBam, kBgzfSam, kSam, kBzip2Sam, kGzipSam, kZstdSam, kXzSam };
+enum { kBam, kBgzfSam, kSam, kBzip2Sam, kGzipSam, kZstdSam, kXzSam, kLz4Sam };
 const InputForm kForms[] = {
     {.name = "BAM", .sam = false, .read = InputForm::Bgzf, .push = push_bam_records, .push_blocks = slimm_push_bgzf_blocks,
      .plan = slimm_host_bgzf_ranges, .planned = "BGZF blocks"},
@@ -839,6 +850,9 @@ const InputForm kForms[] = {
      .planned = "xz blocks", .wide_header_by_host = true, .announce_range = true, .range_note = slimm_host_xz_check_at,
      .announce_note = slimm_set_xz_range_check, .split_floor = slimm_xz_split_floor, .units_behind = xz_blocks_behind, .units_gate = true,
      .end_line = xz_end_line, .by_host = xz_by_host},
+    // (no planner: an lz4 file goes through member 0's decoder whole, and --split-input leaves it there)
+    {.name = "lz4", .article = "an", .sam = true, .read = InputForm::Streamed, .push = slimm_push_lz4_sam_bytes, .wide_header_by_host = true,
+     .end_line = lz4_end_line},
 };
 const InputForm& form_of(const AlignmentFile& f) {
     if (f.is_bam()) return kForms[kBam];
@@ -848,6 +862,7 @@ const InputForm& form_of(const AlignmentFile& f) {
         case Compression::Gzip: return kForms[kGzipSam];
         case Compression::Zstd: return kForms[kZstdSam];
         case Compression::Xz: return kForms[kXzSam];
+        case Compression::Lz4: return kForms[kLz4Sam];
         default: return kForms[kSam];
     }
 }

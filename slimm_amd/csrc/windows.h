@@ -118,6 +118,24 @@ struct WindowPipeline {
            kZsRepeated, kZsSequences, kZsFromFront, kZsFromHistory, kZsRounds, kZsText, kZsCompressedBytes, kZsChecksums, kZsPasses, kZsStats };
     uint64_t zs_stats[kZsStats] = {};
 
+    // lz4 SAM (lz4_decode.hip), the decode scratch: the compressed bytes of a round, the blocks' descriptors and sequences, the
+    // round's text behind its history (a linked frame's last 64 KiB), the position each text byte copies from, the history
+    // kept for the next round
+    struct Lz4 {
+        DevBuf<uint8_t> comp, text, hist;
+        DevBuf<lz4::Block> blocks;
+        DevBuf<lz4::Seq> seq;
+        DevBuf<uint32_t> src;
+        PinBuf<uint8_t> h_text;             // the round's text on the host, for the content checksums (released by end_file)
+        DevBuf<unsigned long long> count;   // as Zstd's: [0] passes' "changed", [1] bad offsets, [2] first block with one, [3], [4]: stats 6, 7
+        template <typename F>
+        void each_held(F&& f) { f(comp), f(text), f(hist), f(blocks), f(seq), f(src); }
+    } lz;
+    // the counters of the lz4 file read last (slimm_get_lz4_stats: 16 words, the last two 0): they outlive the file's state
+    enum { kLzFrames, kLzSkippable, kLzLinked, kLzStored, kLzCompressed, kLzSequences, kLzFromFront, kLzFromHistory, kLzRounds, kLzText,
+           kLzCompressedBytes, kLzBlockSums, kLzContentSums, kLzPasses, kLzStats = 16 };
+    uint64_t lz_stats[kLzStats] = {};
+
     // xz SAM (xz_decode.hip), the decode scratch: the compressed bytes of a round, a descriptor per block, the round's text
     // (which is each block's dictionary as well), the check register of every piece of text (gz::kPiece bytes)
     struct Xz {
@@ -183,10 +201,10 @@ struct WindowPipeline {
         bool found_start = false;   // a range that starts inside the file: its first window holds a record start (false: all head)
         bool has_first = false;     // `first` holds the name of the range's first record (decoded in any window)
         uint64_t head_len = 0;
-        // a streamed codec's SAM (bzip2, gzip, zstd, xz: the file's bytes as they lie in it, decoded here), what every codec
+        // a streamed codec's SAM (bzip2, gzip, zstd, xz, lz4: the file's bytes as they lie in it, decoded here), what every codec
         // keeps on the host: the compressed bytes not decoded yet (file offset `base` on; `bit`: the next bit to read --
         // zstd reads at bytes), the decoded bytes still to skip (the header)
-        enum class Codec : uint8_t { None, Bzip2, Gzip, Zstd, Xz };
+        enum class Codec : uint8_t { None, Bzip2, Gzip, Zstd, Xz, Lz4 };
         struct Stream {
             Codec codec = Codec::None;
             std::vector<uint8_t> pend;
@@ -315,6 +333,27 @@ struct WindowPipeline {
             uint64_t left_index_at = 0;  // ... and has met that stream's index (walk.open_left is off again) at this file offset
             std::vector<xz::Walker::Record> left_kept;
         } xz;
+        // lz4 SAM, the host's side: where in the container stream.bit is (lz4_walk.h) and what the frame's blocks hand on (the
+        // text's length and XXH32 so far), the bytes of history the device holds; the blocks and frames of the round at hand
+        struct Lz4 {
+            lz4::Walker walk;
+            uint64_t frame_len = 0;
+            lz4::Xxh32 xxh{};
+            uint64_t hist_len = 0;
+            bool in_round = false;   // the frame at hand has blocks in the round: frames.back() is it
+            struct Frame {   // a frame with blocks in the round
+                uint32_t first = 0, n = 0;   // its blocks of the round
+                bool ends = false, has_sum = false;
+                uint32_t sum = 0;
+                lz4::FrameHeader fh{};
+                uint64_t at = 0, len_before = 0, text_at = 0, text_len = 0;
+                lz4::Xxh32 xxh{};   // the XXH32 state in front of its blocks of the round
+            };
+            std::vector<lz4::Block> ready;
+            std::vector<uint64_t> ready_at;   // the blocks' file offsets (errors)
+            std::vector<Frame> frames;
+            uint64_t text = 0;                // the round's text bytes (behind lz4_round)
+        } lz;
     } file;
 
     // the buffers that grow with a file's windows: what held_bytes() counts is what end_file gives back
@@ -327,6 +366,7 @@ struct WindowPipeline {
         gz.each_held(f);
         zst.each_held(f);
         xzs.each_held(f);
+        lz.each_held(f);
     }
     uint64_t held_bytes() {   // device memory of the window pipeline (slimm_window_memory)
         uint64_t n = 0;
@@ -456,6 +496,24 @@ void zs_trace_file(const slimm_ctx* c);
 // (StreamCodec::stitch) left to right on host scalars, every member's decoder stands between frames at its range's end with
 // every byte of the range read (SLIMM_E_SPLIT otherwise)
 int split_zstd_ends(slimm_ctx* const* members, uint32_t n, uint32_t* bad);
+// The copies of a round's text resolved (lz_resolve.hip; zs_emit, lz4_emit): src[i] is the position in [history H | text] that
+// text byte i copies from (itself: a literal, already written).  Pointer doubling until nothing changes -- at most
+// ceil(log2(text + H)) + 1 passes, counted into *passes --, then the match bytes fetched from where their chains end.
+// count (device, 5 words as Zstd::count) is fetched into `got` behind every pass: got[1] != 0 -- the expand kernel met an
+// offset out of reach -- ends it early, for the caller to say in its codec's words
+int resolve_copies(slimm_ctx* c, const char* codec, uint32_t* src, uint8_t* text, uint64_t H, uint64_t n_text, unsigned long long* count,
+                   unsigned long long got[5], uint32_t* passes);
+uint32_t copy_grid_for(uint64_t n);   // the grid of a kernel with a thread per text byte (256 threads a workgroup)
+// lz4_decode.hip (slimm_push_lz4_sam_bytes): lz4_round takes the container's items from lz4::Walker (lz4_walk.h), checks the
+// block checksums of the whole blocks at hand, has k_lz4_tokens walk their sequences and leaves the round's blocks, with their
+// text lengths, in file.lz.ready.  lz4_emit: the text built behind the history, resolved, and written to dst; lz4_check,
+// behind the window's launch: the content checksums of the frames that ended.  An lz4 stream is not cut by byte range
+constexpr uint64_t kLz4RoundBytes = 32ull << 20;   // compressed bytes gathered for a round: zstd's, a stated default
+int lz4_round(slimm_ctx* c, bool last);
+bool lz4_next_window(const slimm_ctx* c, uint64_t cap, uint64_t* n);
+int lz4_emit(slimm_ctx* c, uint8_t* dst, uint64_t cap, uint64_t* n_out, uint8_t* last_byte);
+int lz4_check(slimm_ctx* c);
+void lz4_trace_file(const slimm_ctx* c);
 // xz_decode.hip (slimm_push_xz_sam_bytes): xz_round takes the container's items from xz::Walker (xz_walk.h), a block's
 // chunks up to its end -- a block whose bytes are not all at hand is left at its header --, and leaves the whole blocks at
 // hand, with their exact text offsets, in file.xz.ready.  xz_emit: the blocks decoded, a lane each, their checks folded

@@ -15,7 +15,7 @@
 //                 written, a match byte gets the position it copies from -- in the round, or in the history in front of it
 //                 (the frame's last window of text, kept from round to round), else the stream is corrupt
 //   k_zs_double   pointer doubling until nothing changes: at most ceil(log2(text + history)) + 1 passes
-//   k_zs_gather   the match bytes fetched from where their chains end
+//   k_zs_gather   the match bytes fetched from where their chains end (both: lz_resolve.hip, shared with lz4_decode.hip)
 //   (host)        XXH64 of the frames that state one, on a copy of the round's text, while the device decodes the
 //                 window's SAM records (zs_check)
 // No workgroup waits for another: ordering comes from kernel boundaries only.
@@ -142,30 +142,6 @@ __global__ __launch_bounds__(256) void k_zs_expand(const uint8_t* __restrict__ b
     }
 }
 
-__global__ __launch_bounds__(256) void k_zs_double(uint32_t* src, uint64_t H, uint64_t n_text, unsigned long long* __restrict__ count) {
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
-    bool changed = false;
-    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n_text; i += stride) {
-        const uint32_t s = src[i];
-        if (s < H || s == H + i) continue;   // (a byte of the history, or a literal: the chain's end)
-        // (another thread may move src[s - H] on meanwhile: whatever is read there is a byte further up the same chain)
-        const uint32_t t = src[s - H];
-        if (t != s) {
-            src[i] = t;
-            changed = true;
-        }
-    }
-    if (changed) count[0] = 1ull;
-}
-
-__global__ __launch_bounds__(256) void k_zs_gather(const uint32_t* __restrict__ src, uint8_t* __restrict__ text, uint64_t H, uint64_t n_text) {
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
-    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n_text; i += stride) {
-        const uint32_t s = src[i];
-        if (s != H + i) text[H + i] = text[s];   // (s: a byte of the history or a literal; no match byte is read here)
-    }
-}
-
 void push_trace_zs(const char* fmt, ...) {   // "[push zstd] ..."
     va_list ap;
     va_start(ap, fmt);
@@ -177,8 +153,6 @@ void push_trace_zs(const char* fmt, ...) {   // "[push zstd] ..."
 int zs_fail(slimm_ctx* c, const std::string& where, uint32_t status) {
     return fail(c, SLIMM_E_INVALID, "zstd-compressed input is not supported unless it decodes: %s: %s", where.c_str(), zs::status_text(status));
 }
-
-uint32_t grid_for(uint64_t n) { return static_cast<uint32_t>(std::max<uint64_t>(1u, std::min<uint64_t>((n + 255u) / 256u, 16384u))); }
 
 }  // namespace
 
@@ -347,28 +321,14 @@ int zs_emit(slimm_ctx* c, uint8_t* dst, uint64_t, uint64_t* n_out, uint8_t* last
     HIP_TRY(c, hipMemcpyAsync(S.count.p, count, sizeof(count), hipMemcpyHostToDevice, st));
     uint32_t passes = 0;
     if (text) {
-        hipLaunchKernelGGL(k_zs_expand, dim3(grid_for(text)), dim3(256), 0, st, S.comp.p, S.blocks.p, nb, S.lit.p, S.seq.p, S.text.p, S.src.p, H, text,
+        hipLaunchKernelGGL(k_zs_expand, dim3(copy_grid_for(text)), dim3(256), 0, st, S.comp.p, S.blocks.p, nb, S.lit.p, S.seq.p, S.text.p, S.src.p, H, text,
                            S.count.p);
         HIP_TRY(c, hipGetLastError());
-        // every pass halves what is left of the longest chain, and one more finds nothing to do
-        uint32_t most = 1;
-        while ((1ull << (most - 1u)) < text + H) ++most;
-        for (;;) {
-            hipLaunchKernelGGL(k_zs_double, dim3(grid_for(text)), dim3(256), 0, st, S.src.p, H, text, S.count.p);
-            HIP_TRY(c, hipGetLastError());
-            ++passes;
-            HIP_TRY(c, hipMemcpyAsync(count, S.count.p, sizeof(count), hipMemcpyDeviceToHost, st));
-            HIP_TRY(c, hipMemsetAsync(S.count.p, 0, sizeof(unsigned long long), st));
-            HIP_TRY(c, hipStreamSynchronize(st));
-            if (count[1]) {
-                const uint64_t k = std::min<uint64_t>(count[2], nb - 1u);
-                return zs_fail(c, "block at byte " + std::to_string(Z.ready_at[k]), zs::kBadOffset);
-            }
-            if (!count[0]) break;
-            if (passes >= most) return fail(c, SLIMM_E_INVALID, "internal error: zstd: the copies of a round did not resolve in %u passes", most);
+        SLIMM_TRY(resolve_copies(c, "zstd", S.src.p, S.text.p, H, text, S.count.p, count, &passes));   // (lz_resolve.hip)
+        if (count[1]) {
+            const uint64_t k = std::min<uint64_t>(count[2], nb - 1u);
+            return zs_fail(c, "block at byte " + std::to_string(Z.ready_at[k]), zs::kBadOffset);
         }
-        hipLaunchKernelGGL(k_zs_gather, dim3(grid_for(text)), dim3(256), 0, st, S.src.p, S.text.p, H, text);
-        HIP_TRY(c, hipGetLastError());
     }
     // the history for the next round: the last window of the frame that goes on -- none when the round's last frame ended
     const ZF::Frame& f = Z.frames.back();
