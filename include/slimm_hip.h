@@ -262,7 +262,9 @@ int slimm_push_bgzf_blocks(slimm_ctx* ctx, const uint8_t* blocks, uint64_t n_byt
  * round's text, which is host memory (slimm_window_memory does not count it) and is released by slimm_reset.
  * xz SAM (slimm_push_xz_sam_bytes) sizes everything from the chunk headers, which state every size: the compressed bytes of
  * a round, 1 B per byte of its text (at most 512 MB, or one block alone of up to 1 GiB; the text is the blocks' dictionary
- * as well: no 16-bit symbols, no history), 104 B per block and 16 B per 2 KiB of text.  slimm_window_memory counts all of it. */
+ * as well: no 16-bit symbols, no history), 104 B per block and 16 B per 2 KiB of text.  slimm_window_memory counts all of it.
+ * lzip SAM (slimm_push_lzip_sam_bytes) sizes everything from the members' trailers in the same way: the compressed bytes of a
+ * round, 1 B per byte of its text, 104 B per member and 16 B per 2 KiB of text. */
 int slimm_set_input_size_hint(slimm_ctx* ctx, uint64_t compressed_bytes);
 int slimm_window_memory(slimm_ctx* ctx, uint64_t* device_bytes);
 /* hipMemGetInfo of the context's device: bytes in use (by every process and context on it) and the device's total. */
@@ -403,6 +405,38 @@ int slimm_push_xz_sam_bytes(slimm_ctx* ctx, const uint8_t* bytes, uint64_t n_byt
  * [9] CRC64, [10] SHA-256 (not verified), [11] match bytes, [12] the longest distance, [13] rounds, [14] bytes of text,
  * [15] compressed bytes, [16] index records checked against their blocks. */
 int slimm_get_xz_stats(slimm_ctx* ctx, uint64_t out[17]);
+/* LZIP-COMPRESSED SAM TEXT (`lzip x.sam`, `plzip x.sam`: many members back to back) decoded on the device
+ * (slimm_amd/csrc/lzip_decode.hip; the format: lzip_member.h, the member finder: lzip_walk.h).  The contract is that of
+ * slimm_push_xz_sam_bytes: `bytes` = the file's next n_bytes, from its first byte on and in order across calls, cut anywhere
+ * (inside a header, a stream, a trailer); of the decoded text the first `skip` bytes are the header (0 in every later call);
+ * slimm_set_reference_names first; the caller's buffer is free when the call returns; what cannot be decoded yet -- a member
+ * whose end has not come -- waits for the next push; the form does not mix with the others within a file.  Behind
+ * slimm_set_input_mid_file it is refused ("an lzip stream is not cut by byte range").  A member's sizes lie in its trailer,
+ * so the host FINDS a member's end: the offset q at which the next legal header (or, at the last push, the end of the bytes)
+ * stands and the eight bytes in front of q say q minus the member's start; a magic inside compressed data fails that test
+ * and is passed over; what has been searched is not searched again.  Pushes are gathered on the host and decoded in rounds
+ * (32 MiB of compressed bytes; the whole members at hand, at most 512 MB of text or one member alone; SLIMM_FORCE
+ * lzip_round=N, lzip_round_text=N): the device decodes the members, ONE LANE PER MEMBER, each into its place in the round's
+ * text, which is its dictionary; computes every member's CRC32 from pieces; the host compares them with the trailers.  A
+ * file of few members therefore keeps few lanes busy: the library decodes whatever it is pushed, the `slimm` command reads
+ * such a file on the host.  Memory: the compressed bytes of a round, 1 B per byte of its text, 104 B per member and 16 B per
+ * 2 KiB of text; slimm_window_memory counts all of it.  Limits: a member of more than 1 GiB of text is refused ("decode this
+ * file on the host"); version 0 members and the legacy `.lzma` format are not read.  Errors: SLIMM_E_INVALID
+ * "lzip-compressed input is not supported unless it decodes: <where>: <cause>" in the words of the host reader --
+ * truncation, "trailing data behind the last lzip member", a version other than 1, a dictionary size below 4 KiB or above
+ * 512 MiB, a range coder that does not start with a zero byte or end at zero, a distance beyond the member's start or
+ * dictionary, a match that runs over the member's data_size, an end marker in front of it, text that goes on behind it, a
+ * sync-flush marker, an end marker of a length other than 2, a stream that does not end at the trailer, "CRC32 mismatch". */
+int slimm_push_lzip_sam_bytes(slimm_ctx* ctx, const uint8_t* bytes, uint64_t n_bytes, uint32_t skip, int last, uint64_t* n_records);
+/* The counters of the lzip file read last (they outlive slimm_reset, and are zeroed by the next lzip file's first push):
+ * out[0] members, [1] of them empty (no text), [2] rounds, [3] CRC32 fields checked, [4] match bytes, [5] the longest
+ * distance, [6] the largest dictionary size a header stated, [7] bytes of text, [8] compressed bytes. */
+int slimm_get_lzip_stats(slimm_ctx* ctx, uint64_t out[9]);
+/* The members of a regular lzip file by its trailers alone: from the file's end, a trailer's member_size names its member's
+ * first byte, in front of which the trailer of the member before lies; every header is held against the format.  A few
+ * reads, nothing decoded.  *n_members and the sum of the stated data_sizes; SLIMM_E_INVALID when the chain does not close
+ * on byte 0 (trailing data, a truncated file, not an lzip file). */
+int slimm_host_lzip_members(const char* path, uint64_t* n_members, uint64_t* text_bytes);
 /* Page-locks a buffer of the caller (hipHostRegister) until the context is destroyed: copies out of it then run at the
  * speed of the bus instead of the runtime's own staging. */
 int slimm_pin_host_buffer(slimm_ctx* ctx, const void* buffer, uint64_t n_bytes);

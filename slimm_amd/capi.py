@@ -181,6 +181,9 @@ SYMBOLS = [
     ("slimm_get_zstd_stats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("slimm_push_lz4_sam_bytes", C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]),
     ("slimm_get_lz4_stats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    ("slimm_push_lzip_sam_bytes", C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]),
+    ("slimm_get_lzip_stats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    ("slimm_host_lzip_members", C.c_int, [C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("slimm_push_xz_sam_bytes", C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]),
     ("slimm_get_xz_stats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("slimm_set_reference_names", C.c_int, [_P, C.POINTER(C.c_char_p)]),

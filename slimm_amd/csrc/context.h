@@ -27,6 +27,7 @@
 #include "zstd_walk.h"
 #include "xz_walk.h"
 #include "lz4_walk.h"
+#include "lzip_walk.h"
 #include "kernels.h"
 #include "read_identity.h"
 

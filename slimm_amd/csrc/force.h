@@ -28,6 +28,10 @@
 //   across rounds), lz4_round_text=N (a round's text at most, by the blocks' bounds: with 65536 a round a block, so that a
 //   linked frame's copies reach into the history of an earlier round)
 //                                             tests/test_gpu_lz4_sam.py, tests/test_cli_lz4_sam_device.py
+//   lzip_round=N (lzip SAM decoded every N compressed bytes: headers, streams and trailers cut across rounds, the member
+//   finder fed a few bytes at a time), lzip_round_text=N (a round's text at most: a round takes one member, the next round
+//   the rest), lzip_device_members=N (the `slimm` command reads an lzip file of fewer than N members, by its trailers, on
+//   the host: 16 unless told)                 tests/test_gpu_lzip_sam.py, tests/test_cli_lzip_sam_device.py
 //   xz_split_blocks=N (the least blocks per member at which the command cuts an xz file for --split-input: 16 unless told;
 //   a key of its own, which does not follow xz_device_blocks)
 //                                             tests/test_split_xz_ranges.py, tests/test_cli_split_input_xz.py

@@ -4,6 +4,7 @@
 #include "bzip2.hpp"
 #include "zstd.hpp"
 #include "lz4.hpp"
+#include "lzip.hpp"
 #include "xz.hpp"
 
 #include <dlfcn.h>
@@ -239,6 +240,7 @@ static constexpr StreamedCodec kStreamedCodecs[] = {
     {Compression::Zstd, "zstd", "a zstd stream that holds BAM: BAM is read from BGZF blocks only: ", true, false, make_reader<ZstdReader>},
     {Compression::Xz, "xz", "an xz stream that holds BAM: BAM is read from BGZF blocks only: ", true, false, make_reader<XzReader>},
     {Compression::Lz4, "lz4", "an lz4 stream that holds BAM: BAM is read from BGZF blocks only: ", true, false, make_reader<Lz4Reader>},
+    {Compression::Lzip, "lzip", "an lzip stream that holds BAM: BAM is read from BGZF blocks only: ", true, false, make_reader<LzipReader>},
 };
 
 AlignmentFile::~AlignmentFile() { close(); }
@@ -350,12 +352,14 @@ bool AlignmentFile::open(const std::string& path) {
     const bool xz = starts("\xfd" "7zXZ\0", 6);
     // lz4: a frame's magic, or the legacy format's (which the reader refuses in words); a skippable frame in front is zstd's above
     const bool lz4 = starts("\x04\x22\x4d\x18", 4) || starts("\x02\x21\x4c\x18", 4);
+    // lzip: LZIP and version 1 -- or another version byte, which no SAM line holds there and the reader refuses in words
+    const bool lzip = starts("LZIP", 4) && head.size() >= 5 && static_cast<unsigned char>(head[4]) < 0x20;
     bool ok;
     if (!bzip2 && starts("BZh", 3)) {
         err_ = "bzip2-compressed input is not supported (SAM / BAM, BGZF or gzip): " + path;
         ok = false;
     } else {
-        comp_ = xz ? Compression::Xz : lz4 ? Compression::Lz4 : zstd ? Compression::Zstd : bzip2 ? Compression::Bzip2 : is_bgzf ? Compression::Bgzf : gzip ? Compression::Gzip : Compression::None;
+        comp_ = xz ? Compression::Xz : lzip ? Compression::Lzip : lz4 ? Compression::Lz4 : zstd ? Compression::Zstd : bzip2 ? Compression::Bzip2 : is_bgzf ? Compression::Bgzf : gzip ? Compression::Gzip : Compression::None;
         for (const StreamedCodec& c : kStreamedCodecs)
             if (c.comp == comp_) streamed_ = &c;
         if (streamed_) {
@@ -1058,7 +1062,7 @@ long AlignmentFile::read_blocks(uint8_t* dst, size_t cap, size_t max_inflated, s
 
 long AlignmentFile::read_compressed(uint8_t* dst, size_t cap) {
     if (!streamed() || bam_ || !fp_ || !dst) {
-        err_ = "read_compressed: a bzip2, gzip, zstd, xz or lz4 SAM file";
+        err_ = "read_compressed: a bzip2, gzip, zstd, xz, lz4 or lzip SAM file";
         return -1;
     }
     const int fd = fileno(fp_);

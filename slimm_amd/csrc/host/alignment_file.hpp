@@ -49,8 +49,8 @@ enum class SortOrder { Unknown, Unsorted, QueryName, Coordinate, QueryGrouped };
 // How the file's bytes are stored: as they are, in BGZF blocks (BAM, or SAM text from bgzip), as one plain gzip stream of
 // one or more members (SAM text from gzip), as bzip2 streams back to back (SAM text from bzip2 / pbzip2 / lbzip2), or as zstd
 // frames back to back (SAM text from zstd / pzstd), or as xz streams of LZMA2 blocks (SAM text from xz / pixz / pxz), or as
-// lz4 frames back to back (SAM text from lz4)
-enum class Compression { None, Bgzf, Gzip, Bzip2, Zstd, Xz, Lz4 };
+// lz4 frames back to back (SAM text from lz4), or as lzip members back to back (SAM text from lzip / plzip)
+enum class Compression { None, Bgzf, Gzip, Bzip2, Zstd, Xz, Lz4, Lzip };
 
 class TextReader;    // (text_reader.hpp)
 struct StreamedCodec;   // (alignment_file.cpp: what differs between gzip, bzip2, zstd and xz)

@@ -129,6 +129,9 @@ SLIMM_FORWARD(int, slimm_push_zstd_sam_bytes, (slimm_ctx* a, const uint8_t* b, u
 SLIMM_FORWARD(int, slimm_get_zstd_stats, (slimm_ctx* a, uint64_t* b), (a, b))
 SLIMM_FORWARD(int, slimm_push_lz4_sam_bytes, (slimm_ctx* a, const uint8_t* b, uint64_t c, uint32_t s, int d, uint64_t* e), (a, b, c, s, d, e))
 SLIMM_FORWARD(int, slimm_get_lz4_stats, (slimm_ctx* a, uint64_t* b), (a, b))
+SLIMM_FORWARD(int, slimm_push_lzip_sam_bytes, (slimm_ctx* a, const uint8_t* b, uint64_t c, uint32_t s, int d, uint64_t* e), (a, b, c, s, d, e))
+SLIMM_FORWARD(int, slimm_get_lzip_stats, (slimm_ctx* a, uint64_t* b), (a, b))
+SLIMM_FORWARD(int, slimm_host_lzip_members, (const char* a, uint64_t* b, uint64_t* c), (a, b, c))
 SLIMM_FORWARD(int, slimm_push_xz_sam_bytes, (slimm_ctx* a, const uint8_t* b, uint64_t c, uint32_t s, int d, uint64_t* e), (a, b, c, s, d, e))
 SLIMM_FORWARD(int, slimm_get_xz_stats, (slimm_ctx* a, uint64_t* b), (a, b))
 SLIMM_FORWARD(int, slimm_pin_host_buffer, (slimm_ctx* a, const void* b, uint64_t c), (a, b, c))
@@ -831,7 +834,30 @@ bool xz_blocks_behind(const std::string& path, uint64_t header_bytes, uint64_t* 
     return true;
 }
 
-enum { kBam, kBgzfSam, kSam, kBzip2Sam, kGzipSam, kZstdSam, kXzSam, kLz4Sam };
+// lzip SAM is decoded a lane per member, as xz a lane per block: the command counts the file's members by their trailers
+// (slimm_host_lzip_members) and takes the device path only for kLzipDeviceMembers members or more -- xz's 16, the project's own
+// stated default, not a measurement (SLIMM_FORCE lzip_device_members=N).  A file whose trailers do not chain to its first byte
+// goes by the host reader as well, which says what is wrong with it
+constexpr uint64_t kLzipDeviceMembers = 16;
+uint64_t lzip_device_members() { return forced_or("lzip_device_members", kLzipDeviceMembers); }
+bool lzip_by_host(const std::string& path, const char* head) {
+    uint64_t members = 0, text = 0;
+    const bool ok = slimm_host_lzip_members(path.c_str(), &members, &text) == SLIMM_OK;
+    if (ok && members >= lzip_device_members()) return false;
+    if (g_trace && ok) fprintf(stderr, "%slzip SAM of %llu member(s): read on the host\n", head, (unsigned long long)members);
+    if (g_trace && !ok) fprintf(stderr, "%slzip SAM whose trailers do not chain to its first byte: read on the host\n", head);
+    return true;
+}
+void lzip_end_line(const char* head, slimm_ctx* const* ctx, uint32_t n) {
+    uint64_t members = 0, text = 0, told = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        uint64_t st[20] = {};
+        if (slimm_get_lzip_stats(ctx[i], st) == SLIMM_OK) ++told, members += st[0], text += st[7];
+    }
+    if (told) fprintf(stderr, "%slzip SAM on the device: %llu members, %llu bytes of text\n", head, (unsigned long long)members, (unsigned long long)text);
+}
+
+enum { kBam, kBgzfSam, kSam, kBzip2Sam, kGzipSam, kZstdSam, kXzSam, kLz4Sam, kLzipSam };
 const InputForm kForms[] = {
     {.name = "BAM", .sam = false, .read = InputForm::Bgzf, .push = push_bam_records, .push_blocks = slimm_push_bgzf_blocks,
      .plan = slimm_host_bgzf_ranges, .planned = "BGZF blocks"},
@@ -853,6 +879,9 @@ const InputForm kForms[] = {
     // (no planner: an lz4 file goes through member 0's decoder whole, and --split-input leaves it there)
     {.name = "lz4", .article = "an", .sam = true, .read = InputForm::Streamed, .push = slimm_push_lz4_sam_bytes, .wide_header_by_host = true,
      .end_line = lz4_end_line},
+    // (no planner either: the cut at member starts, found from the trailers, is not built)
+    {.name = "lzip", .article = "an", .sam = true, .read = InputForm::Streamed, .push = slimm_push_lzip_sam_bytes, .wide_header_by_host = true,
+     .end_line = lzip_end_line, .by_host = lzip_by_host},
 };
 const InputForm& form_of(const AlignmentFile& f) {
     if (f.is_bam()) return kForms[kBam];
@@ -863,6 +892,7 @@ const InputForm& form_of(const AlignmentFile& f) {
         case Compression::Zstd: return kForms[kZstdSam];
         case Compression::Xz: return kForms[kXzSam];
         case Compression::Lz4: return kForms[kLz4Sam];
+        case Compression::Lzip: return kForms[kLzipSam];
         default: return kForms[kSam];
     }
 }

@@ -150,6 +150,19 @@ struct WindowPipeline {
            kXzSha256Unverified, kXzMatchBytes, kXzMaxDist, kXzRounds, kXzText, kXzCompressedBytes, kXzIndexRecords, kXzStats };
     uint64_t xz_stats[kXzStats] = {};
 
+    // lzip SAM (lzip_decode.hip), the decode scratch, as Xz's: the compressed bytes of a round, a descriptor per member (an
+    // xz::Block whose check is CRC32), the round's text (each member's dictionary as well), the CRC32 register of every piece
+    struct Lzip {
+        DevBuf<uint8_t> comp, text;
+        DevBuf<xz::Block> members;
+        DevBuf<xz::Piece> piece;
+        template <typename F>
+        void each_held(F&& f) { f(comp), f(text), f(members), f(piece); }
+    } lzs;
+    // the counters of the lzip file read last (slimm_get_lzip_stats): they outlive the file's state
+    enum { kLzipMembers, kLzipEmpty, kLzipRounds, kLzipCrc32, kLzipMatchBytes, kLzipMaxDist, kLzipMaxDict, kLzipText, kLzipCompressedBytes, kLzipStats };
+    uint64_t lzip_stats[kLzipStats] = {};
+
     // ---- announced before the file's first window (slimm_set_input_size_hint, slimm_set_input_mid_file), cleared when it ends
     struct Announced {
         uint64_t size_hint = 0;   // the file's compressed bytes (0 = not told): what its gathered windows are sized for
@@ -201,10 +214,10 @@ struct WindowPipeline {
         bool found_start = false;   // a range that starts inside the file: its first window holds a record start (false: all head)
         bool has_first = false;     // `first` holds the name of the range's first record (decoded in any window)
         uint64_t head_len = 0;
-        // a streamed codec's SAM (bzip2, gzip, zstd, xz, lz4: the file's bytes as they lie in it, decoded here), what every codec
+        // a streamed codec's SAM (bzip2, gzip, zstd, xz, lz4, lzip: the file's bytes as they lie in it, decoded here), what every codec
         // keeps on the host: the compressed bytes not decoded yet (file offset `base` on; `bit`: the next bit to read --
         // zstd reads at bytes), the decoded bytes still to skip (the header)
-        enum class Codec : uint8_t { None, Bzip2, Gzip, Zstd, Xz, Lz4 };
+        enum class Codec : uint8_t { None, Bzip2, Gzip, Zstd, Xz, Lz4, Lzip };
         struct Stream {
             Codec codec = Codec::None;
             std::vector<uint8_t> pend;
@@ -354,6 +367,14 @@ struct WindowPipeline {
             std::vector<Frame> frames;
             uint64_t text = 0;                // the round's text bytes (behind lz4_round)
         } lz;
+        // lzip SAM, the host's side: the member finder (lzip_walk.h: the members so far, and how far the member at stream.bit
+        // has been searched for its end); the members of the round at hand
+        struct Lzip {
+            lzip::Walker walk;
+            std::vector<xz::Block> ready;
+            std::vector<uint64_t> ready_at;   // the members' file offsets (errors)
+            uint64_t text = 0;                // the round's text bytes (behind lzip_round)
+        } lzip;
     } file;
 
     // the buffers that grow with a file's windows: what held_bytes() counts is what end_file gives back
@@ -367,6 +388,7 @@ struct WindowPipeline {
         zst.each_held(f);
         xzs.each_held(f);
         lz.each_held(f);
+        lzs.each_held(f);
     }
     uint64_t held_bytes() {   // device memory of the window pipeline (slimm_window_memory)
         uint64_t n = 0;
@@ -530,6 +552,18 @@ void xz_trace_file(const slimm_ctx* c);
 // a stream in the ranges on the left are, in order and in number, the index records that the member which met the index kept
 // (those in front of its own blocks' records)
 int split_xz_streams(slimm_ctx* const* members, uint32_t n, uint32_t* bad);
+// (xz_decode.hip) k_xz_check and k_xz_fold on a round's blocks -- xz_emit's, and lzip_emit's, whose members are blocks with a
+// CRC32 check: every block's register from 0 over its text, into Block::crc
+void launch_xz_checks(hipStream_t st, xz::Block* blocks, uint32_t n, uint32_t n_pieces, const uint8_t* text, xz::Piece* piece);
+// lzip_decode.hip (slimm_push_lzip_sam_bytes): lzip_round takes the whole members at hand from lzip::Walker (lzip_walk.h) -- a
+// member whose end is not at hand waits, the search keeping its place -- and leaves them, with their exact text offsets, in
+// file.lzip.ready.  lzip_emit: the members decoded, a lane each, their CRC32 folded from pieces and compared with the
+// trailers', the text written to dst.  An lzip stream is not cut by byte range
+constexpr uint64_t kLzipRoundBytes = 32ull << 20;   // compressed bytes gathered for a round: xz's, a stated default
+int lzip_round(slimm_ctx* c, bool last);
+bool lzip_next_window(const slimm_ctx* c, uint64_t cap, uint64_t* n);
+int lzip_emit(slimm_ctx* c, uint8_t* dst, uint64_t cap, uint64_t* n_out, uint8_t* last_byte);
+void lzip_trace_file(const slimm_ctx* c);
 // the decoders' shared steps (windows.hip).  stream.pend to the device, into `comp` with `tail` zeroed bytes behind it.
 // The candidates a find kernel left at d_cand, counted at count[0]: `launch(cap)` runs it with room for cap of them, again
 // with more room when there were more; *got of them are there (and the stream is idle)

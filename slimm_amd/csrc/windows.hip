@@ -1,7 +1,7 @@
 // The window pipeline (include/slimm_hip.h: slimm_push_bam_bytes, _bgzf_blocks, _sam_bytes, _bgzf_sam_blocks, _bzip2_sam_bytes,
-// _gzip_sam_bytes, _zstd_sam_bytes, _xz_sam_bytes, _lz4_sam_bytes): a file's bytes -- inflated BAM records, whole BGZF blocks of them, SAM text, BGZF blocks of SAM
-// text, SAM text in a streamed codec (bzip2, gzip, zstd, xz, lz4) -- cross the bus in windows; the device inflates (bgzf_tokens.hip,
-// bgzf_inflate.hip) or decodes (the codecs: bzip2_decode.hip, gzip_decode.hip, zstd_decode.hip, xz_decode.hip, lz4_decode.hip) them, finds the
+// _gzip_sam_bytes, _zstd_sam_bytes, _xz_sam_bytes, _lz4_sam_bytes, _lzip_sam_bytes): a file's bytes -- inflated BAM records, whole BGZF blocks of them, SAM text, BGZF blocks of SAM
+// text, SAM text in a streamed codec (bzip2, gzip, zstd, xz, lz4, lzip) -- cross the bus in windows; the device inflates (bgzf_tokens.hip,
+// bgzf_inflate.hip) or decodes (the codecs: bzip2_decode.hip, gzip_decode.hip, zstd_decode.hip, xz_decode.hip, lz4_decode.hip, lzip_decode.hip) them, finds the
 // records (bam_decode.hip, sam_decode.hip) and appends them to the context's record stream.  Its state: windows.h.
 // Replaces seqan::BamFileIn + readRecord of the reference (src/misc.hpp:498-522, src/slimm.hpp:194-208).
 // A push's steps (push_window): check_push, open_file; one of three sources fills window buffers -- push_stream (a streamed
@@ -309,7 +309,7 @@ int add_last_newline(slimm_ctx* c, uint64_t at, hipStream_t st) {   // at: bytes
 }
 
 // ---- a push
-enum { kFormatBam = 0, kFormatBgzf = 1, kFormatSam = 2, kFormatBgzfSam = 3, kFormatBzip2Sam = 4, kFormatGzipSam = 5, kFormatZstdSam = 6, kFormatXzSam = 7, kFormatLz4Sam = 8 };
+enum { kFormatBam = 0, kFormatBgzf = 1, kFormatSam = 2, kFormatBgzfSam = 3, kFormatBzip2Sam = 4, kFormatGzipSam = 5, kFormatZstdSam = 6, kFormatXzSam = 7, kFormatLz4Sam = 8, kFormatLzipSam = 9 };
 
 // What each streamed codec supplies (windows.h: StreamCodec), by File::Codec
 const StreamCodec kCodecs[] = {
@@ -334,6 +334,11 @@ const StreamCodec kCodecs[] = {
     {"lz4", "lz4_round", kLz4RoundBytes, false, false, lz4_round, lz4_next_window, lz4_emit, lz4_check, lz4_trace_file,
      [](const File& F) { return static_cast<int>(F.lz.walk.stage); }, nullptr, [](WindowPipeline& W) { return W.lz_stats; },
      WindowPipeline::kLzStats, WindowPipeline::kLzCompressedBytes, "an", nullptr,
+     false, nullptr, nullptr, nullptr, nullptr},
+    // (not cut by byte range: no split side.  Its rounds go on while the file offset moves: the members taken)
+    {"lzip", "lzip_round", kLzipRoundBytes, false, false, lzip_round, lzip_next_window, lzip_emit, nullptr, lzip_trace_file,
+     [](const File&) { return 0; }, nullptr, [](WindowPipeline& W) { return W.lzip_stats; },
+     WindowPipeline::kLzipStats, WindowPipeline::kLzipCompressedBytes, "an", nullptr,
      false, nullptr, nullptr, nullptr, nullptr},
 };
 
@@ -674,7 +679,7 @@ int release_callers_buffer(slimm_ctx* c, const Push& p) {
 int push_window(slimm_ctx* c, const uint8_t* bytes, uint64_t src_bytes, int format, uint32_t skip, int last, uint64_t* n_records) {
     if (!c) return SLIMM_E_INVALID;
     if (n_records) *n_records = 0;
-    const Codec codec = format == kFormatBzip2Sam ? Codec::Bzip2 : format == kFormatGzipSam ? Codec::Gzip : format == kFormatZstdSam ? Codec::Zstd : format == kFormatXzSam ? Codec::Xz : format == kFormatLz4Sam ? Codec::Lz4 : Codec::None;
+    const Codec codec = format == kFormatBzip2Sam ? Codec::Bzip2 : format == kFormatGzipSam ? Codec::Gzip : format == kFormatZstdSam ? Codec::Zstd : format == kFormatXzSam ? Codec::Xz : format == kFormatLz4Sam ? Codec::Lz4 : format == kFormatLzipSam ? Codec::Lzip : Codec::None;
     const bool sam = format == kFormatSam || format == kFormatBgzfSam || codec != Codec::None;
     Push p{bytes, src_bytes, src_bytes, skip, last != 0, sam, codec, format == kFormatBgzf || format == kFormatBgzfSam};
     SLIMM_TRY(check_push(c, p));
@@ -827,6 +832,15 @@ int slimm_get_lz4_stats(slimm_ctx* c, uint64_t out[16]) {
     if (!c || !out) return SLIMM_E_INVALID;
     static_assert(WindowPipeline::kLzStats == 16, "slimm_get_lz4_stats: sixteen words");
     std::copy(c->win.lz_stats, c->win.lz_stats + WindowPipeline::kLzStats, out);
+    return SLIMM_OK;
+}
+int slimm_push_lzip_sam_bytes(slimm_ctx* c, const uint8_t* bytes, uint64_t n_bytes, uint32_t skip, int last, uint64_t* n_records) {
+    return push_window(c, bytes, n_bytes, kFormatLzipSam, skip, last, n_records);
+}
+int slimm_get_lzip_stats(slimm_ctx* c, uint64_t out[9]) {
+    if (!c || !out) return SLIMM_E_INVALID;
+    static_assert(WindowPipeline::kLzipStats == 9, "slimm_get_lzip_stats: nine counters");
+    std::copy(c->win.lzip_stats, c->win.lzip_stats + WindowPipeline::kLzipStats, out);
     return SLIMM_OK;
 }
 int slimm_get_zstd_stats(slimm_ctx* c, uint64_t out[20]) {

@@ -147,6 +147,15 @@ __global__ __launch_bounds__(64) void k_xz_fold(xz::Block* __restrict__ blocks, 
     b.crc = reg;
 }
 
+}  // namespace
+
+void launch_xz_checks(hipStream_t st, xz::Block* blocks, uint32_t n, uint32_t n_pieces, const uint8_t* text, xz::Piece* piece) {
+    if (n_pieces) hipLaunchKernelGGL(k_xz_check, dim3((n_pieces + 255u) / 256u), dim3(256), 0, st, blocks, n, n_pieces, text, piece);
+    hipLaunchKernelGGL(k_xz_fold, dim3((n + 63u) / 64u), dim3(64), 0, st, blocks, n, piece, gz::crc_x_pow8(gz::kPiece), xz::crc64_x_pow8(gz::kPiece));
+}
+
+namespace {
+
 void push_trace_xz(const char* fmt, ...) {   // "[push xz] ..."
     va_list ap;
     va_start(ap, fmt);
@@ -283,8 +292,7 @@ int xz_emit(slimm_ctx* c, uint8_t* dst, uint64_t, uint64_t* n_out, uint8_t* last
     SLIMM_TRY(stream_upload(c, S.comp, kXzTail));
     HIP_TRY(c, hipMemcpyAsync(S.blocks.p, Z.ready.data(), nb * sizeof(xz::Block), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_xz_decode, dim3(nb), dim3(64), 0, st, S.comp.p, W.file.stream.pend.size(), S.blocks.p, nb, S.text.p);
-    if (pieces) hipLaunchKernelGGL(k_xz_check, dim3((pieces + 255u) / 256u), dim3(256), 0, st, S.blocks.p, nb, pieces, S.text.p, S.piece.p);
-    hipLaunchKernelGGL(k_xz_fold, dim3((nb + 63u) / 64u), dim3(64), 0, st, S.blocks.p, nb, S.piece.p, gz::crc_x_pow8(gz::kPiece), xz::crc64_x_pow8(gz::kPiece));
+    launch_xz_checks(st, S.blocks.p, nb, pieces, S.text.p, S.piece.p);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(Z.ready.data(), S.blocks.p, nb * sizeof(xz::Block), hipMemcpyDeviceToHost, st));
     if (text > drop) {

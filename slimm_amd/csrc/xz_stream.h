@@ -75,6 +75,10 @@ enum Status : uint32_t {
     kBadFooter,
     kBadFooterCrc,
     kBadPadding,
+    kMarkerEarly,
+    kMarkerLength,
+    kSyncFlush,
+    kPastEnd,
     kStatusCount
 };
 inline const char* status_text(uint32_t s) {
@@ -109,7 +113,11 @@ inline const char* status_text(uint32_t s) {
                                                 "index does not match the blocks",
                                                 "bad stream footer",
                                                 "footer CRC32 mismatch",
-                                                "stream padding that is no multiple of four bytes"};
+                                                "stream padding that is no multiple of four bytes",
+                                                "an end marker in front of the stated size",
+                                                "an end marker of a length other than 2",
+                                                "a sync-flush marker",
+                                                "text that goes on behind the stated size"};
     return s < kStatusCount ? t[s] : "unknown error";
 }
 
@@ -412,18 +420,25 @@ SLIMM_XZ_HD inline uint32_t lzma_len(Rc& rc, uint16_t* l, uint32_t pos_state) {
     return 18u + rc.tree(l + 258u, 8);
 }
 
-// One LZMA chunk: `usize` bytes to out[0, usize), of which out[-since, 0) are the `since` bytes of the block written since
-// its last dictionary reset (the dictionary: a distance reaches min(since + written, dict_size) back at most); the
-// compressed bytes are rc's, which has been started (Rc::init).  The state and the probabilities go on from chunk to chunk
-SLIMM_XZ_HD inline uint32_t lzma_chunk(Rc& rc, Lzma& s, uint16_t* probs, uint8_t* out, uint32_t usize, uint64_t since, uint32_t dict_size, Tally& t) {
+// The LZMA symbols of one run of `usize` text bytes to out[0, usize), of which out[-since, 0) are the `since` bytes written
+// since the last dictionary reset (the dictionary: a distance reaches min(since + written, dict_size) back at most); the
+// compressed bytes are rc's, which has been started (Rc::init).  The one body of the two ways a run ends:
+//   an LZMA2 chunk (kMarked = false)   after exactly usize bytes; an end marker is kEndMarker
+//   an lzip member (kMarked = true)    with the end marker -- a match, not a rep, of distance 0xFFFFFFFF and length 2 -- behind
+//                                      exactly usize bytes: earlier kMarkerEarly, a literal or a short rep there kPastEnd, a
+//                                      match there kMatchOverEnd; length 3 is kSyncFlush, any other kMarkerLength
+// Behind either the coder is normalised once and stands at rc.end with code 0.  No byte is written at or behind out[usize]
+template <bool kMarked>
+SLIMM_XZ_HD inline uint32_t lzma_run(Rc& rc, Lzma& s, uint16_t* probs, uint8_t* out, uint32_t usize, uint64_t since, uint32_t dict_size, Tally& t) {
     const uint32_t pos_mask = (1u << s.pb) - 1u, lp_mask = (1u << s.lp) - 1u;
     uint32_t n = 0;
-    while (n < usize) {
+    while (kMarked || n < usize) {
         if (rc.over) return kChunkEnd;
         const uint64_t at = since + n;
         const uint32_t pos_state = static_cast<uint32_t>(at) & pos_mask;
         const int64_t o = static_cast<int64_t>(n);
         if (!rc.bit(probs[kIsMatch + s.state * kPosStatesMax + pos_state])) {
+            if (kMarked && n == usize) return kPastEnd;
             const uint32_t prev = at ? out[o - 1] : 0u;
             uint16_t* lit = probs + kLiteral + kLitSize * (((static_cast<uint32_t>(at) & lp_mask) << s.lc) + (prev >> (8u - s.lc)));
             uint32_t sym = 1;
@@ -463,11 +478,17 @@ SLIMM_XZ_HD inline uint32_t lzma_chunk(Rc& rc, Lzma& s, uint16_t* probs, uint8_t
                     d = (d << 4) + rc.tree_reverse(probs + kAlign, 4);
                 }
             }
-            if (d == 0xffffffffu) return kEndMarker;
+            if (d == 0xffffffffu) {
+                if (!kMarked) return kEndMarker;
+                if (len != 2u) return len == 3u ? kSyncFlush : kMarkerLength;
+                if (n < usize) return kMarkerEarly;
+                break;
+            }
             s.rep[0] = d;
         } else {
             if (!rc.bit(probs[kIsRepG0 + s.state])) {
                 if (!rc.bit(probs[kIsRep0Long + s.state * kPosStatesMax + pos_state])) {
+                    if (kMarked && n == usize) return kPastEnd;
                     if (s.rep[0] >= at || s.rep[0] >= dict_size) return kBadDistance;
                     out[o] = out[o - static_cast<int64_t>(s.rep[0]) - 1];
                     ++n;
@@ -515,6 +536,10 @@ SLIMM_XZ_HD inline uint32_t lzma_chunk(Rc& rc, Lzma& s, uint16_t* probs, uint8_t
     if (rc.over || rc.pos != rc.end) return kChunkEnd;
     if (rc.code != 0) return kBadRangeEnd;
     return kOk;
+}
+// One LZMA chunk of LZMA2: the state and the probabilities go on from chunk to chunk
+SLIMM_XZ_HD inline uint32_t lzma_chunk(Rc& rc, Lzma& s, uint16_t* probs, uint8_t* out, uint32_t usize, uint64_t since, uint32_t dict_size, Tally& t) {
+    return lzma_run<false>(rc, s, probs, out, usize, since, dict_size, t);
 }
 
 // ---- a block for the device decoder (xz_decode.hip): where it lies in the round's bytes and text, and what decoding found

@@ -310,7 +310,7 @@ class Slimm:
         return total
 
     def _push_streamed_sam_bytes(self, push, blob, skip, window, cuts, empty_last) -> int:
-        """The cut-and-push loop of push_bzip2_sam_bytes, _gzip_, _zstd_, _xz_ and _lz4_: `push` is the codec's entry point."""
+        """The cut-and-push loop of push_bzip2_sam_bytes, _gzip_, _zstd_, _xz_, _lz4_ and _lzip_: `push` is the codec's entry point."""
         buf = np.frombuffer(blob, dtype=np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob, dtype=np.uint8)
         n = buf.shape[0]
         if cuts is None:
@@ -381,6 +381,21 @@ class Slimm:
         out = (C.c_uint64 * 16)()
         self._check(self.L.slimm_get_lz4_stats(self.ctx, out))
         return dict(zip(self.LZ4_STATS, [int(v) for v in out]))
+
+    def push_lzip_sam_bytes(self, blob, skip: int = 0, window: int = 0, cuts=None, empty_last: bool = False) -> int:
+        """slimm_push_lzip_sam_bytes: an lzip-compressed SAM file's bytes from its first byte on, of whose decoded text the
+        first `skip` bytes are the header (set_reference_names first); the arguments are those of push_bzip2_sam_bytes.  The
+        host finds the members by their trailers, the device decodes them, a lane each, checks their CRC32, finds the lines
+        and decodes them.  Returns the number of records."""
+        return self._push_streamed_sam_bytes(self.L.slimm_push_lzip_sam_bytes, blob, skip, window, cuts, empty_last)
+
+    LZIP_STATS = ("members", "empty_members", "rounds", "crc32_checked", "match_bytes", "max_dist", "max_dict", "text_bytes", "compressed_bytes")
+
+    def lzip_stats(self) -> dict:
+        """slimm_get_lzip_stats: the counters of the lzip file read last."""
+        out = (C.c_uint64 * 9)()
+        self._check(self.L.slimm_get_lzip_stats(self.ctx, out))
+        return dict(zip(self.LZIP_STATS, [int(v) for v in out]))
 
     def push_xz_sam_bytes(self, blob, skip: int = 0, window: int = 0, cuts=None, empty_last: bool = False) -> int:
         """slimm_push_xz_sam_bytes: an xz-compressed SAM file's bytes from its first byte on, of whose decoded text the first
